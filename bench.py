@@ -2,6 +2,8 @@
 """bench.py -- particle-steps/s of the SPH hot path on MI355X (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2 --dump-outputs DIR     # + the state after the last timed step
+    python bench.py --full                                                 # + every record below
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one iteration of the reference's simulate() loop body (SUMMER_SPH.f90:889-916):
@@ -9,16 +11,30 @@ A "step" is one iteration of the reference's simulate() loop body (SUMMER_SPH.f9
 h update, Variable.f90:1152), on a seeded synthetic Keplerian disc (summersph_amd/ic.py).  Inputs
 are resident in HBM before the timed region starts.  Rank 0 prints ONE JSON line.
 
+A plain run measures the headline workload only: set-up, the untimed pre-heat pass, W warm-up + K
+timed steps, the optional dump, the JSON line.  --full adds what takes runs of its own: restarts of
+the same state (repeat_ms_per_step), the per-group kernel table from further steps, the stream-copy
+ceiling, the strong-scaling records, the N = 1 side workloads and the CPU baselines.
+
+--dump-outputs DIR (1 GPU) writes what the timed path computed in its last timed step, read before
+anything else runs on the context: per-particle fields as DIR/<field>.npy (float64, one row per
+particle the context holds: upload order, except that with accretion + cull (--full-simulate) the
+accreted and culled particles are compacted away and the rows are the survivors in their relative
+upload order; a fixed seeded sample of those rows when all of them exceed DUMP_BUDGET_BYTES, its row
+indices in DIR/sample_index.npy), DIR/n_particles.npy (the number of rows sampled from, i.e. the
+particles left), the sinks as DIR/sinks.npy (one row per sink: SINK_COLUMNS) and the next dt and the
+time reached as DIR/dt_t.npy.  The inputs are seeded: the same arguments give the same IC.
+
 Workloads
   fixed (headline, every N)  uniform disc, N x 1e6 gas particles + 1 sink, fixed h = 2.5: the [F] path
                              (BASELINE configs[1] shape at the metric's N = 1e6); WEAK scaling: shards over GPUs as
                              x-slabs with ghost exchange + migration over RCCL -- the native step loop of
                              libsummersph_halo.so where it applies (--halo auto), else summersph_amd/dist.py.
-  ring4m_strong (every N)    BASELINE configs[3]: the 4e6-particle thin viscous ring split N ways (STRONG scaling; the
-                             >= 6x at 8 GPUs of BASELINE.md is quoted on this).  Side object, own timed region.
-  full_1e7 (every N)         BASELINE configs[4]: 1e7-particle disc + sink, Barnes-Hut self-gravity, accretion + cull --
+  ring4m_strong (--full, every N)  BASELINE configs[3]: the 4e6-particle thin viscous ring split N ways (STRONG scaling;
+                             the >= 6x at 8 GPUs of BASELINE.md is quoted on this).  Side object, own timed region.
+  full_1e7 (--full, every N) BASELINE configs[4]: 1e7-particle disc + sink, Barnes-Hut self-gravity, accretion + cull --
                              simulate() as the reference runs it, split N ways (STRONG scaling).  Side object.
-  variable_h, full_simulate, side_records, fixed_reuse_density (N = 1)
+  variable_h, full_simulate, side_records, fixed_reuse_density (--full, N = 1)
                              BASELINE configs[2] (1e6, per-particle h, grad-h, leaf-box rule, h update), the reference's
                              whole loop body at 1e6, and the kernel selection away from the friendly geometry.
 
@@ -30,11 +46,11 @@ Every figure can be recomputed from the line itself or from a file under profile
                object says `"stale": true` when summersph_amd/csrc has changed since.
   config       mean_neighbours etc. are read from the context directly after the timed region (the state the timed steps
                ran on), before any repeat or breakdown pass.
-  repeat_ms_per_step   restarts of the SAME state (same upload, same warm-up, same K steps): run-to-run spread.
-  cpu_baseline the UNMODIFIED reference (oracle/_ref/ref_driver: /root/reference's module compiled by oracle/build_ref.sh,
-               serial as the reference is) timed on this box's host cores on a bounded sample of the same workload
+  repeat_ms_per_step   (--full) restarts of the SAME state (same upload, same warm-up, same K steps): run-to-run spread.
+  cpu_baseline the UNMODIFIED reference (oracle/_ref/ref_driver: the reference's module compiled by oracle/build_ref.sh,
+               serial as the reference is) timed on the host cores on a bounded sample of the same workload
                (kind "reference"); the CPU restatement (oracle/sph_oracle.c, OpenMP) is reported beside it; if the
-               binary is absent the restatement is the baseline (kind "port").  Rank 0, N = 1 only.
+               binary is absent the restatement is the baseline (kind "port").  Rank 0, N = 1, --full only.
 """
 import argparse
 import glob
@@ -256,6 +272,31 @@ class Workload:
         self.ctx.close()
 
 
+DUMP_BUDGET_BYTES = 60 << 20           # per-particle arrays of --dump-outputs (+ the sample's indices); the whole dump stays < 64 MB
+DUMP_SAMPLE_SEED = 20240917
+SINK_COLUMNS = "x y z vx vy vz m ax ay az radius".split()
+
+
+def dump_outputs(ctx, dt, t, variable, outdir):
+    """what a caller of sph_run receives after the last timed step: the particle state and the rates of the last evaluation
+    (one row per particle left: upload order, accreted and culled particles compacted away), their count, the sinks and the
+    next dt.  More than DUMP_BUDGET_BYTES of particles: the same seeded sample of rows for every field.  Returns {file: shape}."""
+    names = "x y z vx vy vz u alpha rho ax ay az du".split() + (["h", "omega"] if variable else [])
+    n = ctx.n
+    k = min(n, DUMP_BUDGET_BYTES // (8 * (len(names) + 1)))
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, k, replace=False))
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {name: ctx.field(name)[idx] for name in names}
+    arrays["sample_index"] = idx.astype(np.float64)
+    arrays["n_particles"] = np.array([n], dtype=np.float64)
+    sinks = ctx.get_sinks()
+    arrays["sinks"] = np.stack([sinks[c] for c in SINK_COLUMNS], axis=1) if sinks["x"].size else np.zeros((0, len(SINK_COLUMNS)))
+    arrays["dt_t"] = np.array([dt, t], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def stats_dict(st):
     return {"mean_neighbours": st.nlist_mean, "mean_wave_trips": st.nlist_wave_mean, "max_neighbours": st.nlist_max,
             "tile_fit_pct": st.tile_fit_pct, "tile_fit_pct_forces": st.tile_fit_pct_forces, "grid": list(st.grid_dim),
@@ -263,8 +304,9 @@ def stats_dict(st):
             "device_bytes": st.device_bytes, "slots": int(st.n)}
 
 
-def timed_run(wl, steps, warmup, dominant=("forces",), breakdown=True, repeats=0, late_window=None, preheat=True):
-    """-> dict(elapsed, dt, table, stats, repeat_ms, late).  Inside the timed region only the `dominant` kernel groups are
+def timed_run(wl, steps, warmup, dominant=("forces",), breakdown=True, repeats=0, late_window=None, preheat=True, after_timed=None):
+    """-> dict(elapsed, dt, table, stats, repeat_ms, late, after).  `after_timed(ctx, dt, t)` runs directly after the timed
+    region, before anything else touches the context; its result is `after`.  Inside the timed region only the `dominant` kernel groups are
     bracketed by HIP events (the roofline's duration is measured live there; bracketing every group costs ~4 % of a
     fixed-h step).  `stats` is read directly after the timed region: it describes the state the timed steps ran on.
     `repeats`: the context is put back into its initial state (same upload) and the same warm-up + K steps run again --
@@ -297,7 +339,8 @@ def timed_run(wl, steps, warmup, dominant=("forces",), breakdown=True, repeats=0
     for k in dominant:                                  # every EVENT_STRIDE-th launch was bracketed: the group's total, extrapolated
         table[k] = (table[k][0] * EVENT_STRIDE, table[k][1] * EVENT_STRIDE)
     st = ctx.stats()                                   # the state of the timed steps, nothing ran since
-    out = {"elapsed": el, "dt": dt, "stats": st, "n_left": ctx.n, "repeat_ms": None, "late": None}
+    out = {"elapsed": el, "dt": dt, "stats": st, "n_left": ctx.n, "repeat_ms": None, "late": None,
+           "after": after_timed(ctx, dt, t) if after_timed else None}
     if breakdown:
         bs = max(1, min(steps, 10))
         ctx.timing_reset(); ctx.timing(True)
@@ -487,6 +530,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--particles", dest="n", type=int, default=1_000_000, help="gas particles per GPU")
     ap.add_argument("--nngb", type=float, default=85.0, help="midplane neighbour target of the fixed-h IC (mean is ~0.6x)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: repeat_ms_per_step, the per-group kernel "
+                    "table, the stream-copy ceiling, ring4m_strong + full_1e7, the N = 1 side workloads and cpu_baseline "
+                    "(each of the last three can be left out with --no-extras, --no-variable, --no-cpu)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the state after the last timed step as DIR/<name>.npy (1 GPU)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-variable", action="store_true", help="skip the extra records at N = 1 (variable_h, full_simulate, side records)")
     ap.add_argument("--no-extras", action="store_true", help="skip ring4m_strong and full_1e7 (BASELINE configs[3] and [4])")
@@ -515,6 +562,10 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and world > 1:
+        ap.error("--dump-outputs needs a single-GPU run (its state lives in one context)")
 
     import torch
     from summersph_amd import capi, ic
@@ -581,11 +632,12 @@ def main():
     # ---- headline workload -----------------------------------------------------------------------
     lim = load_limiters()
     head_dist = None
+    dump = (lambda ctx, dt, t: dump_outputs(ctx, dt, t, variable, args.dump_outputs)) if args.dump_outputs else None
     if world == 1:
         gas, sinks = ic.split_rows(headline_rows(args.n))
         wl = Workload(capi, torch, local_rank, gas, sinks, flags, variable)
         del gas
-        res = timed_run(wl, args.steps, args.warmup, repeats=3)
+        res = timed_run(wl, args.steps, args.warmup, breakdown=args.full, repeats=3 if args.full else 0, after_timed=dump)
         wl.close()
         elapsed, dt, kt, st = res["elapsed"], res["dt"], res["table"], res["stats"]
         owned, ghosts, plane = [args.n], [0], None
@@ -643,16 +695,20 @@ def main():
             "valu_fp64": {"achieved_tflops_est": flops, "peak_tflops": FP64_PEAK_TFLOPS, "frac": flops / FP64_PEAK_TFLOPS,
                           "pair_visits_per_s": pair_visits},
             "hbm_step": {"algorithmic_bytes_per_particle_step": bps, "achieved_GBs": bps * value / world / 1e9},
-            "kernel_ms_per_step": {k: v[0] / args.steps for k, v in kt.items()},
-            "kernel_ms_note": "the dominant group (forces) timed inside the timed region; the others from further steps of the same "
-                              "trajectory with every group bracketed by HIP events (that costs ~4 % and stays out of `value`)",
+            "kernel_ms_per_step": {k: v[0] / args.steps for k, v in kt.items() if args.full or k == "forces"},
+            "kernel_ms_note": ("the dominant group (forces) timed inside the timed region; the others from further steps of the same "
+                               "trajectory with every group bracketed by HIP events (that costs ~4 % and stays out of `value`)")
+                              if args.full else "the dominant group (forces) timed inside the timed region; the other groups: --full",
             "final_dt": dt, "device_bytes": st.device_bytes, "list_builds": st.nlist_builds, "list_reflags": st.nlist_reflags,
         }
-        copy_gbs = stream_copy_gbs(torch, local_rank)
-        out["roofline"]["stream_copy_GBs"] = copy_gbs
-        out["roofline"]["frac_of_stream_copy"] = achieved / copy_gbs
+        if args.full:
+            copy_gbs = stream_copy_gbs(torch, local_rank)
+            out["roofline"]["stream_copy_GBs"] = copy_gbs
+            out["roofline"]["frac_of_stream_copy"] = achieved / copy_gbs
         out["roofline"]["note"] = ("compulsory HBM traffic is tiny for this path (hbm_step); what the pair kernels wait for is "
                                    "in `limiter`: fp64 vector issue, the LDS tile reads and idle lanes (lane_efficiency)")
+        if world == 1 and res["after"] is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": res["after"], "dtype": "float64"}
         if head_dist is not None:
             out["halo_stats_rank0"] = head_dist["halo_stats_rank0"]
             if "phase_ms_per_step" in head_dist:
@@ -661,7 +717,7 @@ def main():
     default_headline = not variable and args.ic == "disc" and not args.self_gravity and not args.reuse_density and not args.no_tiles
 
     # ---- BASELINE configs[3] and [4]: strong scaling, every N (the N = 1 points of the two curves come from here too) -----
-    if default_headline and not args.no_extras:
+    if args.full and default_headline and not args.no_extras:
         n_ring = max(20_000, int(4_000_000 * args.extras_scale))
         n_full = max(20_000, int(10_000_000 * args.extras_scale))
         full_flags = capi.FLAG_SELF_GRAVITY | capi.FLAG_ACCRETE_CULL
@@ -687,7 +743,7 @@ def main():
                                                   f"self-gravity (theta 0.5), sink accretion + boundary cull: simulate() as the reference runs it, split into {world} x-slab(s)")
 
     if rank == 0:
-        if world == 1 and default_headline and not args.no_variable:
+        if args.full and world == 1 and default_headline and not args.no_variable:
             # BASELINE configs[2] on the same GPU, same step count.  Both list groups are bracketed: `nlist` = builds
             # (nlist_v_tiled) only, `reflag` = the re-flag pass (nlist_v_reflag) -- the roofline is the build's
             gas, sinks = ic.split_rows(ic.keplerian_disc_var(args.n, seed=303))
@@ -761,7 +817,7 @@ def main():
             out["fixed_reuse_density"] = {"value": args.n * args.steps / rr["elapsed"], "unit": "particle-steps/s",
                                           "ms_per_step": rr["elapsed"] / args.steps * 1e3, "final_dt": rr["dt"],
                                           "note": "same results as the headline run, 1 density + 2 force passes per step"}
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.n, args.nngb)
         print(json.dumps(out), flush=True)
     if dist is not None:

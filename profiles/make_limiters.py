@@ -6,7 +6,7 @@
 bench.py quotes the newest JSON in its roofline objects (traffic, limiter) and marks the quote stale when the kernel sources
 have changed since, so every number in the bench line can be recomputed from a file in this directory.
 
-    python3 profiles/make_limiters.py r03 gpurun_out/<tag> fixed variable full
+    python3 profiles/make_limiters.py r03 profile_out/<tag> fixed variable full
 
 Formulas (MI355X: 256 CUs = 256 TAs = 256 LDS, 1024 SIMDs, 32 shader engines):
   cycles      = SQ_BUSY_CYCLES / 32                     (the kernel's duration in shader clocks)
