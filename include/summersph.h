@@ -349,6 +349,44 @@ int sph_dt_candidate(sph_ctx *ctx, double *candidate);
 /* overwrite the sink accelerations (after summing the per-GPU partial sums over ranks)     */
 int sph_set_sink_accel(sph_ctx *ctx, int32_t ns, const double *sax, const double *say, const double *saz);
 
+/* ---- density rendering: replaces the grid loop and the projection of the reference's imaging script
+ *      (Density_Image.py: KD-tree ball query per node of a 120^3 grid, m W(r, h) summed, grid summed along z) --------
+ * For a node g and the selected particles j:  D(g) = sum_j m_j W(|g - r_j|, h_j),  W(r, h) = sigma (1 - 1.5 q^2 + 0.75 q^3)
+ * for q <= 1, sigma 0.25 (2 - q)^3 for 1 < q <= 2, 0 beyond; q = r / h, sigma = 1 / (pi h^3) with the DOUBLE-precision pi.
+ * This is the script's analytic kernel, not the simulation's REAL(4)-pi table: a rendered density is not the rho field.
+ *   selection   the context's owned gas particles (ghosts excluded as sph_owned_bbox excludes them; sinks are never
+ *               rendered) with clip_lo < x < clip_hi on every axis (strict; -INFINITY / +INFINITY: no clip)
+ *   h           > 0: one h for every particle (the script's 1.25); 0: each particle's own h (SPH_F_H on a variable-h
+ *               context, params.h on a fixed-h one)
+ *   nodes       node i on axis a is lo[a] + i (hi[a] - lo[a]) / (n[a] - 1), the last one exactly hi[a] (np.linspace);
+ *               n[a] == 1: the single node lo[a].  SPH_RENDER_AUTO_BOUNDS: lo / hi = min / max of the selected
+ *               particles (the script's default), written back into the descriptor
+ *   output      axis = -1: the n0 n1 n2 grid in C order [i][j][k] (x slowest, meshgrid(indexing='ij')); axis 0, 1, 2: the
+ *               column sums along that axis, the two other axes in order.  A column sum adds the 3-D mode's node values
+ *               in increasing node index (bitwise the sequential sum of the 3-D output).  SPH_RENDER_SPACING multiplies
+ *               the sums by that axis's node spacing (hi - lo) / (n - 1): a column density
+ *   order       every node adds its terms in the (cell, particle id) order of the render's own binning, which depends
+ *               only on the node box, n, h and the clip: results are bitwise reproducible, independent of the context's
+ *               sorted order and of axis / flags
+ *   cost        two stream synchronisations (selection statistics, window size) + the output copy of the host form; no
+ *               state, statistic (other than device_bytes: the render's scratch) or flag of the context changes
+ * SPH_ERR_ARG: null pointer, n < 1, out_len != the output's size, lo > hi, h < 0, axis out of range, SPH_RENDER_SPACING
+ * without a projection axis of n > 1, reserved != 0, SPH_RENDER_AUTO_BOUNDS over an empty selection.  SPH_ERR_NOMEM:
+ * the scratch does not fit.  sph_render_density_dev leaves the result in device memory (ordered on the context's stream). */
+#define SPH_RENDER_AUTO_BOUNDS 1
+#define SPH_RENDER_SPACING 2
+typedef struct sph_render_desc {
+    double  lo[3], hi[3];           /* node box (written back with SPH_RENDER_AUTO_BOUNDS)          */
+    double  clip_lo[3], clip_hi[3]; /* strict particle clip box; -INFINITY / +INFINITY = none        */
+    double  h;                      /* > 0: one h for all; 0: each particle's own h                  */
+    int32_t n[3];                   /* nodes per axis, each >= 1                                     */
+    int32_t axis;                   /* -1: 3-D grid; 0, 1, 2: column sums along that axis            */
+    int32_t flags;                  /* SPH_RENDER_AUTO_BOUNDS | SPH_RENDER_SPACING                   */
+    int32_t reserved;               /* must be 0                                                     */
+} sph_render_desc;
+int sph_render_density(sph_ctx *ctx, sph_render_desc *d, double *host_out, int64_t out_len);
+int sph_render_density_dev(sph_ctx *ctx, sph_render_desc *d, double *d_out, int64_t out_len);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* bounding box of the particle positions at the last grid build (= the current positions

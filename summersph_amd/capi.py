@@ -41,7 +41,10 @@ SYMBOLS = [
     "sph_set_dt", "sph_get_dt", "sph_kick_devdt", "sph_drift_devdt", "sph_dt_candidate_dev", "sph_kick_drift_devdt", "sph_kick_dt_candidate_dev", "sph_kick_dt_candidate_gas_dev", "sph_kick_sinks_devdt", "sph_pack_partials_dev", "sph_pack_partials_ex_dev",
     "sph_apply_partials_dev", "sph_set_boundary_boxes", "sph_forces_part", "sph_set_gravity_sources_dev", "sph_accrete_mark_dev", "sph_accrete_apply_dev", "sph_set_numbers_dev",
     "sph_get_stats", "sph_get_bbox", "sph_timing_enable", "sph_timing_stride", "sph_timing_reset", "sph_timing_get", "sph_synchronize", "sph_stream",
+    "sph_render_density", "sph_render_density_dev",
 ]
+RENDER_AUTO_BOUNDS = 1
+RENDER_SPACING = 2
 
 
 class Params(C.Structure):
@@ -60,6 +63,12 @@ class Stats(C.Structure):
                 ("grid_builds", C.c_int64), ("nlist_builds", C.c_int64), ("density_passes", C.c_int64),
                 ("force_passes", C.c_int64), ("device_bytes", C.c_int64), ("nlist_wave_mean", C.c_double),
                 ("tile_fit_pct_forces", C.c_int32), ("host_syncs", C.c_int32), ("lane_efficiency_forces", C.c_double), ("nlist_reflags", C.c_int64)]
+
+
+class RenderDesc(C.Structure):
+    """sph_render_desc (include/summersph.h): node box, strict clip box, h, nodes per axis, output axis, flags"""
+    _fields_ = [("lo", C.c_double * 3), ("hi", C.c_double * 3), ("clip_lo", C.c_double * 3), ("clip_hi", C.c_double * 3),
+                ("h", C.c_double), ("n", C.c_int32 * 3), ("axis", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
 class SphError(RuntimeError):
@@ -157,6 +166,8 @@ def load():
     lib.sph_timing_enable.argtypes = [C.c_void_p, C.c_int]
     lib.sph_timing_stride.argtypes = [C.c_void_p, C.c_int]
     lib.sph_timing_get.argtypes = [C.c_void_p, C.c_int, _D, C.POINTER(C.c_int64)]
+    lib.sph_render_density.argtypes = [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p, C.c_int64]
+    lib.sph_render_density_dev.argtypes = [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p, C.c_int64]
     _lib = lib
     return lib
 
@@ -186,6 +197,7 @@ class Context:
         for k, v in overrides.items():
             setattr(p, k, v)
         self.params = p
+        self.device = int(device)
         h = C.c_void_p()
         st = self.lib.sph_ctx_create(C.byref(p), int(device), C.byref(h))
         if st != 0:
@@ -445,6 +457,56 @@ class Context:
 
     def state(self) -> dict:
         return {k: self.field(k) for k in FIELDS[:9]}
+
+    # ---- density rendering (sph_render_density) --------------------------------------------------
+    def render_desc(self, shape, bounds=None, axis=None, h=None, clip=None, spacing=False) -> RenderDesc:
+        """The descriptor of render_density's arguments (see there)."""
+        n = (int(shape),) * 3 if np.isscalar(shape) else tuple(int(v) for v in shape)
+        if len(n) != 3:
+            raise ValueError("shape: one node count or three")
+        d = RenderDesc()
+        d.n[:] = n
+        d.axis = -1 if axis is None else ("xyz".index(axis) if isinstance(axis, str) else int(axis))
+        d.h = 0.0 if h is None else float(h)
+        d.flags = (RENDER_AUTO_BOUNDS if bounds is None else 0) | (RENDER_SPACING if spacing else 0)
+        if bounds is not None:
+            b = np.asarray(bounds, dtype=np.float64).reshape(2, 3)
+            d.lo[:] = b[0].tolist(); d.hi[:] = b[1].tolist()
+        cb = np.array([[-np.inf] * 3, [np.inf] * 3]) if clip is None else np.asarray(clip, dtype=np.float64).reshape(2, 3)
+        d.clip_lo[:] = cb[0].tolist(); d.clip_hi[:] = cb[1].tolist()
+        return d
+
+    @staticmethod
+    def render_shape(d: RenderDesc):
+        n = tuple(d.n)
+        return n if d.axis < 0 else tuple(v for a, v in enumerate(n) if a != d.axis)
+
+    def render_density(self, shape, bounds=None, axis=None, h=None, clip=None, spacing=False, device=False):
+        """SPH density m W(|g - r_j|, h_j) summed on an np.linspace node grid (include/summersph.h, sph_render_density).
+        shape: nodes per axis (n or (n0, n1, n2)); bounds: ((lo xyz), (hi xyz)) or None = the selected particles' min / max;
+        axis: None = the 3-D grid (x slowest), 0 / 1 / 2 or 'x' / 'y' / 'z' = column sums along it; h: None = each particle's
+        own h, else one h for all; clip: ((lo xyz), (hi xyz)), strict; spacing: column sums times the node spacing.
+        Returns float64 numpy (device=False) or a torch tensor on the context's GPU; the node box used is left in
+        self.render_bounds."""
+        d = self.render_desc(shape, bounds, axis, h, clip, spacing)
+        oshape = self.render_shape(d)
+        size = int(np.prod(oshape, dtype=np.int64))
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            out = torch.empty(oshape, dtype=torch.float64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()          # the block may still be in use by torch's queued work
+            self._ck(self.lib.sph_render_density_dev(self._h, C.byref(d), C.c_void_p(out.data_ptr()), size))
+            st = self.stream()                                    # torch's later work on `out` waits for the render
+            if st:
+                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
+            else:
+                torch.cuda.synchronize(dev)
+        else:
+            out = np.empty(oshape, dtype=np.float64)
+            self._ck(self.lib.sph_render_density(self._h, C.byref(d), out.ctypes.data, size))
+        self.render_bounds = (np.array(d.lo[:]), np.array(d.hi[:]))
+        return out
 
     # ---- diagnostics ---------------------------------------------------------------------
     def stats(self) -> Stats:

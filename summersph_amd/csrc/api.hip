@@ -600,6 +600,7 @@ int sph_ctx_destroy(sph_ctx *c) {
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
     for (int k = 0; k < 2; k++) { if (c->ev_bbox[k]) (void)hipEventDestroy(c->ev_bbox[k]); if (c->ev_nl[k]) (void)hipEventDestroy(c->ev_nl[k]); }
     ctx_free(c, c->sel_count); ctx_free_ptr(c, c->sel_tmp); ctx_free(c, c->bnd_boxes);
+    render_free(c);
     if (c->stream && c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return SPH_OK;
@@ -1186,6 +1187,18 @@ int sph_timing_get(sph_ctx *c, int id, double *total_ms, int64_t *launches) {
     if (total_ms) *total_ms = c->tslot[id].total_ms;
     if (launches) *launches = c->tslot[id].launches;
     return SPH_OK;
+}
+
+int sph_render_density(sph_ctx *c, sph_render_desc *d, double *host_out, int64_t out_len) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return render_density(c, d, host_out, out_len, true);
+}
+
+int sph_render_density_dev(sph_ctx *c, sph_render_desc *d, double *d_out, int64_t out_len) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return render_density(c, d, d_out, out_len, false);
 }
 
 int sph_synchronize(sph_ctx *c) {

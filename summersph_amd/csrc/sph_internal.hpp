@@ -209,6 +209,11 @@ struct sph_ctx {
     int timing_stride = 1;           // ... every timing_stride-th launch of it (sph_timing_stride)
     int64_t timing_seen[32] = {};    // launches of group k since timing was switched on
     sph::TimingSlot tslot[SPH_K_COUNT];
+
+    // sph_render_density (render.hip): private scratch, never the grid / list buffers above
+    void *rnd_buf = nullptr; size_t rnd_bytes = 0;
+    double *rnd_small = nullptr;     // per-block statistics, their result and the selection cursor
+    double *rnd_pinned = nullptr;    // pinned read-back slots
 };
 
 namespace sph {
@@ -295,5 +300,8 @@ hipError_t launch_eos_only_v(sph_ctx *c, const PairConst &pc);
 hipError_t launch_forces_v(sph_ctx *c, const PairConst &pc);
 hipError_t launch_update_h(sph_ctx *c, const PairConst &pc);   // leaves the local candidate (min * dt_scale) in d_dt[2]
 PairConst make_pair_const(const sph_ctx *c);
+// density rendering (render.hip): out is host memory (host_out) or device memory; two read-backs (+ the host copy)
+int render_density(sph_ctx *c, sph_render_desc *d, double *out, int64_t out_len, bool host_out);
+void render_free(sph_ctx *c);
 
 }  // namespace sph

@@ -26,6 +26,8 @@ module sph_hip_binding
   public :: sph_kick_drift_devdt, sph_kick_dt_candidate_dev, sph_kick_dt_candidate_gas_dev, sph_kick_sinks_devdt
   public :: sph_dt_candidate_dev, sph_pack_partials_dev, sph_pack_partials_ex_dev, sph_apply_partials_dev, sph_set_gravity_sources_dev
   public :: SPH_PARTIALS
+  ! density rendering (Density_Image.py's grid loop and projection)
+  public :: sph_render_desc, sph_render_density, sph_render_density_dev, SPH_RENDER_AUTO_BOUNDS, SPH_RENDER_SPACING
   public :: c_message
 
   integer(c_int), parameter :: SPH_OK = 0
@@ -37,6 +39,7 @@ module sph_hip_binding
   integer(c_int32_t), parameter :: SPH_FLAG_REUSE_DENSITY = 1, SPH_FLAG_VARIABLE_H = 2, SPH_FLAG_SELF_GRAVITY = 16
   integer(c_int32_t), parameter :: SPH_FLAG_ACCRETE_CULL = 32, SPH_FLAG_SINK_CREATION = 64
   integer(c_int32_t), parameter :: SPH_PARTIALS = 199
+  integer(c_int32_t), parameter :: SPH_RENDER_AUTO_BOUNDS = 1, SPH_RENDER_SPACING = 2
 
   type, bind(C) :: sph_params
     real(c_double) :: h, gamma, gamma_m1
@@ -57,6 +60,16 @@ module sph_hip_binding
     real(c_double) :: lane_efficiency_forces
     integer(c_int64_t) :: nlist_reflags
   end type sph_stats
+
+  ! node box, strict clip box (-huge / +huge or IEEE infinities: none), h (0: each particle's own), nodes per axis,
+  ! axis (-1: the 3-D grid, 0/1/2: column sums along x/y/z), flags, reserved (0).  The 3-D output is C order, x slowest:
+  ! a Fortran array out(n(3), n(2), n(1)); column sums along z are out(n(2), n(1)).
+  type, bind(C) :: sph_render_desc
+    real(c_double) :: lo(3), hi(3), clip_lo(3), clip_hi(3)
+    real(c_double) :: h
+    integer(c_int32_t) :: n(3)
+    integer(c_int32_t) :: axis, flags, reserved
+  end type sph_render_desc
 
   interface
     integer(c_int) function sph_abi_version() bind(C, name='sph_abi_version')
@@ -404,6 +417,22 @@ module sph_hip_binding
       type(c_ptr), value :: ctx, d_xyzm
       integer(c_int64_t), value :: n_src
       real(c_double), intent(in) :: lo_hi(6)
+    end function
+
+    ! ---- density rendering: the grid loop and the projection of Density_Image.py (KD-tree ball query per node,
+    ! m W(r, h) with the analytic cubic spline, sum along z); d%lo / d%hi written back with SPH_RENDER_AUTO_BOUNDS
+    integer(c_int) function sph_render_density(ctx, d, host_out, out_len) bind(C, name='sph_render_density')
+      import :: c_int, c_int64_t, c_ptr, c_double, sph_render_desc
+      type(c_ptr), value :: ctx
+      type(sph_render_desc), intent(inout) :: d
+      real(c_double), intent(out) :: host_out(*)
+      integer(c_int64_t), value :: out_len
+    end function
+    integer(c_int) function sph_render_density_dev(ctx, d, d_out, out_len) bind(C, name='sph_render_density_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_render_desc
+      type(c_ptr), value :: ctx, d_out
+      type(sph_render_desc), intent(inout) :: d
+      integer(c_int64_t), value :: out_len
     end function
   end interface
 

@@ -71,3 +71,20 @@ def read_snapshot_v(path: str):
                 continue
             (sinks if len(v) == 8 and v[6] == 0.0 else gas).append(v)
     return np.asarray(gas).reshape(-1, 10), np.asarray(sinks).reshape(-1, 8)
+
+
+SAVE_HEADER = "x  y  z  vx  vy vz energy mass  alpha"
+
+
+def write_save(path: str, gas: np.ndarray, sinks: np.ndarray) -> None:
+    """A save file in make_save's layout (SUMMER_SPH.f90:719-738): header, one record per line, 9 values per gas row
+    (x y z vx vy vz u m alpha), then 8 per sink row (x y z vx vy vz 0 m)."""
+    gas = np.asarray(gas, dtype=np.float64).reshape(-1, 9)
+    sinks = np.asarray(sinks, dtype=np.float64).reshape(-1, 8)
+    with open(path, "w") as f:
+        f.write(SAVE_HEADER + "\n")
+        for r in gas:
+            f.write(" ".join(f"{v:.17e}" for v in r) + "\n")
+        for r in sinks:
+            r = r.copy(); r[6] = 0.0
+            f.write(" ".join(f"{v:.17e}" for v in r) + "\n")
