@@ -40,7 +40,9 @@ enum sph_status {
     SPH_ERR_HIP = 3,          /* a HIP runtime call failed (text in sph_last_error)       */
     SPH_ERR_NOMEM = 4,        /* device or host allocation failed                         */
     SPH_ERR_STATE = 5,        /* call order violated (e.g. forces before density)         */
-    SPH_ERR_GRID = 6,         /* cell grid would exceed 2^31 cells (non-finite positions?) */
+    SPH_ERR_GRID = 6,         /* no cell grid possible: a non-finite box, or one axis needs more than 2^21
+                                 cells of edge 2h (2 <h>) even after the 6-sigma trim (a hashed grid holds
+                                 any box up to that; a dense one up to 2^31 cells)        */
     SPH_ERR_NONFINITE = 7     /* NaN/Inf in particle positions at grid build               */
 };
 
@@ -98,6 +100,11 @@ typedef struct sph_params {
                                     (start of a step, after calc_smoothing); by default that list is derived in place from the
                                     list of the old lengths (varh.hip nlist_v_reflag: the same neighbour sets, entries in a
                                     different order); A/B measurements                                */
+#define SPH_FLAG_HASHED_GRID 1024 /* always index the cell grid with the hashed table (64-bit cell keys, a hash table over
+                                    the occupied cells) instead of the dense one; bitwise the same results.  Without it the
+                                    hashed table is used where the dense one cannot be built: fixed h, a box of 2^31 cells
+                                    or more after the trim; variable h, more than 2^27 cells (far-apart particle groups);
+                                    sph_grid_info tells which one the last build used                     */
 #define SPH_FLAG_REUSE_DENSITY 1 /* skip the density pass when positions and masses did not
                                     change since the last one (bitwise the same rho); OFF by
                                     default: the reference recomputes it, [F]:896,908 */
@@ -130,8 +137,8 @@ enum sph_kernel_id {
 
 typedef struct sph_stats {
     int64_t n;              /* gas particles                                              */
-    int64_t n_cells;        /* cells of the current grid                                  */
-    int32_t grid_dim[3];    /* cells along x, y, z                                        */
+    int64_t n_cells;        /* cells of the current grid (hashed grid: the occupied ones)  */
+    int32_t grid_dim[3];    /* cells along x, y, z (hashed grid: of the index)            */
     int32_t nlist_capacity; /* neighbour slots per particle currently allocated           */
     int32_t nlist_max;      /* largest neighbour count found at the last build            */
     int32_t tile_fit_pct;   /* fixed h: workgroups (%) whose neighbour intervals fit the LDS tile of the
@@ -389,6 +396,17 @@ int sph_render_density_dev(sph_ctx *ctx, sph_render_desc *d, double *d_out, int6
 
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
+/* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too
+ * sparse for the dense table: the occupied cells in a hash table).  Reads the occupied-cell count back (synchronises).   */
+typedef struct sph_grid_info {
+    int32_t kind;             /* 0 dense, 1 hashed, -1 no grid built yet                                  */
+    int32_t dim[3];           /* cells along x, y, z                                                      */
+    int64_t occupied_cells;   /* cells holding particles (dense: every cell of the table)                 */
+    int64_t table_entries;    /* dense: cells + 1; hashed: hash table slots (a power of two >= 4 capacity) */
+    double  index_cells;      /* dim[0] dim[1] dim[2]: the cells the keys address                         */
+    int64_t bytes;            /* device bytes of the cell table (hashed: keys, sort, cells, table)         */
+} sph_grid_info;
+int sph_get_grid_info(const sph_ctx *ctx, sph_grid_info *out);
 /* bounding box of the particle positions at the last grid build (= the current positions
  * after sph_density / sph_step): lo[3], hi[3].  Serves check_bounds ([F]:471-482) without a
  * download.                                                                              */

@@ -26,6 +26,7 @@ FLAG_SINK_CREATION = 64
 FLAG_NO_WHOLE_TILE = 128
 FLAG_REUSE_GRAVITY = 256
 FLAG_NO_REFLAG = 512
+FLAG_HASHED_GRID = 1024
 
 # every symbol include/summersph.h declares (tests check that the library exports them all)
 SYMBOLS = [
@@ -40,7 +41,7 @@ SYMBOLS = [
     "sph_set_stream", "sph_reserve", "sph_owned_bbox", "sph_select_boxes", "sph_selected_ids_dev", "sph_select_boxes_async", "sph_selected_counts", "sph_gather_selected_dev", "sph_replace_ghosts_dev",
     "sph_set_dt", "sph_get_dt", "sph_kick_devdt", "sph_drift_devdt", "sph_dt_candidate_dev", "sph_kick_drift_devdt", "sph_kick_dt_candidate_dev", "sph_kick_dt_candidate_gas_dev", "sph_kick_sinks_devdt", "sph_pack_partials_dev", "sph_pack_partials_ex_dev",
     "sph_apply_partials_dev", "sph_set_boundary_boxes", "sph_forces_part", "sph_set_gravity_sources_dev", "sph_accrete_mark_dev", "sph_accrete_apply_dev", "sph_set_numbers_dev",
-    "sph_get_stats", "sph_get_bbox", "sph_timing_enable", "sph_timing_stride", "sph_timing_reset", "sph_timing_get", "sph_synchronize", "sph_stream",
+    "sph_get_stats", "sph_get_grid_info", "sph_get_bbox", "sph_timing_enable", "sph_timing_stride", "sph_timing_reset", "sph_timing_get", "sph_synchronize", "sph_stream",
     "sph_render_density", "sph_render_density_dev",
 ]
 RENDER_AUTO_BOUNDS = 1
@@ -63,6 +64,13 @@ class Stats(C.Structure):
                 ("grid_builds", C.c_int64), ("nlist_builds", C.c_int64), ("density_passes", C.c_int64),
                 ("force_passes", C.c_int64), ("device_bytes", C.c_int64), ("nlist_wave_mean", C.c_double),
                 ("tile_fit_pct_forces", C.c_int32), ("host_syncs", C.c_int32), ("lane_efficiency_forces", C.c_double), ("nlist_reflags", C.c_int64)]
+
+
+class GridInfo(C.Structure):
+    """sph_grid_info (include/summersph.h): kind 0 dense / 1 hashed / -1 none, cells per axis, occupied cells, table
+    entries, indexed cells (dim product) and the table's device bytes"""
+    _fields_ = [("kind", C.c_int32), ("dim", C.c_int32 * 3), ("occupied_cells", C.c_int64), ("table_entries", C.c_int64),
+                ("index_cells", C.c_double), ("bytes", C.c_int64)]
 
 
 class RenderDesc(C.Structure):
@@ -126,6 +134,7 @@ def load():
     lib.sph_download_field_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
     lib.sph_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     lib.sph_get_bbox.argtypes = [C.c_void_p, _D, _D]
+    lib.sph_get_grid_info.argtypes = [C.c_void_p, C.POINTER(GridInfo)]
     lib.sph_upload_field.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
     lib.sph_upload_field_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
     lib.sph_update_h.argtypes = [C.c_void_p]
@@ -513,6 +522,12 @@ class Context:
         s = Stats()
         self._ck(self.lib.sph_get_stats(self._h, C.byref(s)))
         return s
+
+    def grid_info(self) -> GridInfo:
+        """the cell grid of the last build: kind 1 = hashed (SPH_FLAG_HASHED_GRID or a box too sparse for a dense table)"""
+        g = GridInfo()
+        self._ck(self.lib.sph_get_grid_info(self._h, C.byref(g)))
+        return g
 
     def bbox(self):
         lo = (C.c_double * 3)(); hi = (C.c_double * 3)()

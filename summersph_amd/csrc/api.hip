@@ -594,6 +594,7 @@ int sph_ctx_destroy(sph_ctx *c) {
     resolve_timing(c);
     free_particle_arrays(c);
     ctx_free(c, c->cell_start); c->cell_fill = nullptr; ctx_free(c, c->cell_hmax); ctx_free(c, c->bbox_part); ctx_free(c, c->d_flags);
+    grid_hash_free(c);
     ctx_free(c, c->grav_tab); ctx_free(c, c->sink_radius);
     ctx_free(c, c->w_tab); ctx_free(c, c->dw_tab); ctx_free(c, c->w_pair); ctx_free(c, c->dw_pair); ctx_free(c, c->sink); ctx_free(c, c->sink_part);
     ctx_free(c, c->dt_part); ctx_free(c, c->d_dt);
@@ -742,6 +743,11 @@ int sph_get_stats(sph_ctx *c, sph_stats *o) {
     if (!c || !o) return SPH_ERR_ARG;
     std::memset(o, 0, sizeof(*o));
     o->n = c->n; o->n_cells = c->grid.ncells;
+    if (c->hashed) {
+        DeviceGuard g(c->device);
+        o->n_cells = grid_occupied_cells(c);
+        if (o->n_cells < 0) return SPH_ERR_HIP;
+    }
     for (int a = 0; a < 3; a++) o->grid_dim[a] = c->grid.dim[a];
     o->nlist_capacity = c->nl_cap; o->nlist_max = c->nl_max;
     o->tile_fit_pct = c->whole_tile ? c->wt_fit_pct : -1;
@@ -1146,6 +1152,22 @@ int sph_apply_partials_dev(sph_ctx *c, const double *d_all, int32_t nranks, int3
     if (!c || !d_all || nranks < 1 || stride < SPH_PARTIALS) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
     API_HIP(launch_apply_partials(c, d_all, nranks, stride, apply_dt != 0));
+    return SPH_OK;
+}
+
+int sph_get_grid_info(const sph_ctx *c, sph_grid_info *o) {
+    if (!c || !o) return SPH_ERR_ARG;
+    std::memset(o, 0, sizeof(*o));
+    o->kind = c->grid_builds == 0 ? -1 : (c->hashed ? 1 : 0);
+    if (c->grid_builds == 0) return SPH_OK;
+    DeviceGuard g(c->device);
+    for (int a = 0; a < 3; a++) o->dim[a] = c->grid.dim[a];
+    o->index_cells = c->index_cells;
+    const int64_t occ = grid_occupied_cells(c);
+    if (occ < 0) return SPH_ERR_HIP;
+    o->occupied_cells = occ;
+    o->table_entries = c->hashed ? c->htab_len : c->grid.ncells + 1;
+    o->bytes = c->hashed ? c->hash_bytes : (int64_t)(2 * (size_t)c->cell_cap + 16) * (int64_t)sizeof(int32_t);
     return SPH_OK;
 }
 

@@ -12,6 +12,8 @@
 //   cell_table               -> cell_start[c] = first sorted slot with key >= c
 //   reorder                  -> gathers the 9 state arrays + ids into sorted order and writes
 //                               the 32-byte density gather record {x,y,z,m}
+// Hashed grids (boxes too sparse for a dense table, see grid_rebuild): 64-bit keys, a radix sort over the key bits in use,
+// run heads -> scan -> the occupied cells (ukey, ustart), and a hash table over them (sph_internal.hpp HashView).
 #include <cstdlib>
 #include <cstring>
 
@@ -21,7 +23,7 @@
 #include <cmath>
 #include <utility>
 
-#include "sph_internal.hpp"
+#include "pair_common.hpp"
 
 namespace sph {
 
@@ -243,6 +245,59 @@ __global__ __launch_bounds__(256) void cell_table(const uint32_t *__restrict__ k
     cell_start[c] = (int32_t)lo;
 }
 
+// ---- hashed cell table --------------------------------------------------------------------------
+// key = c2 << sh2 | c1 << sh1 | c0 (permuted axes): the dense key's order.  Replaced ghosts get ~0 and sort behind every cell.
+__global__ __launch_bounds__(256) void hash_keys(GridDesc g, int32_t sh1, int32_t sh2, const double *__restrict__ x,
+                                                 const double *__restrict__ y, const double *__restrict__ z, int64_t n,
+                                                 uint64_t *__restrict__ keys, uint32_t *__restrict__ vals,
+                                                 const int32_t *__restrict__ orig, int32_t n_owned, int64_t dead_below) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const bool dead = i < dead_below && orig[i] >= n_owned;
+    uint64_t k = ~0ull;
+    if (!dead) {
+        int cc[3];
+        cell_coords(g, x[i], y[i], z[i], cc);
+        k = ((uint64_t)cc[2] << sh2) | ((uint64_t)cc[1] << sh1) | (uint64_t)cc[0];
+    }
+    keys[i] = k;
+    vals[i] = (uint32_t)i;
+}
+
+// head[p] = 1 where a run of equal keys starts (p < n live entries of the sorted keys)
+__global__ __launch_bounds__(256) void hash_heads(const uint64_t *__restrict__ keys, int64_t n, int32_t *__restrict__ head) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p < n) head[p] = (p == 0 || keys[p] != keys[p - 1]) ? 1 : 0;
+}
+
+// uidx = inclusive scan of the heads: ukey[u] / ustart[u] of the u-th occupied cell, ustart[m] = n, *m_out = m
+__global__ __launch_bounds__(256) void hash_compact(const uint64_t *__restrict__ keys, const int32_t *__restrict__ uidx, int64_t n,
+                                                   uint64_t *__restrict__ ukey, int32_t *__restrict__ ustart, int32_t *__restrict__ m_out) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const uint64_t k = keys[p];
+    if (p == 0 || k != keys[p - 1]) { ukey[uidx[p] - 1] = k; ustart[uidx[p] - 1] = (int32_t)p; }
+    if (p == n - 1) { const int32_t m = uidx[p]; *m_out = m; ustart[m] = (int32_t)n; ukey[m] = ~0ull; }
+}
+
+__device__ __forceinline__ void hash_put(HashEnt *__restrict__ tab, uint64_t mask, uint64_t key, int32_t idx, int32_t start) {
+    for (uint64_t s = hash_mix(key) & mask;; s = (s + 1) & mask) {
+        const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&tab[s].key), ~0ull, (unsigned long long)key);
+        // a key inserted twice (k + 1 of one cell = the next occupied cell) carries the same values both times
+        if (prev == ~0ull || prev == key) { tab[s].idx = idx; tab[s].start = start; return; }
+    }
+}
+
+// every occupied cell u: key -> {u, ustart[u]} and key + 1 -> {u + 1, ustart[u + 1]} (the lower bound just behind the cell)
+__global__ __launch_bounds__(256) void hash_insert(const uint64_t *__restrict__ ukey, const int32_t *__restrict__ ustart,
+                                                   const int32_t *__restrict__ m_ptr, HashEnt *__restrict__ tab, uint64_t mask) {
+    const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= *m_ptr) return;
+    const uint64_t k = ukey[u];
+    hash_put(tab, mask, k, (int32_t)u, ustart[u]);
+    hash_put(tab, mask, k + 1, (int32_t)u + 1, ustart[u + 1]);
+}
+
 struct ReorderArgs {
     const double *src[10];
     double *dst[10];
@@ -424,6 +479,107 @@ int owned_bbox(sph_ctx *c, double *d_out6, double *h_out6) {
     return SPH_OK;
 }
 
+// the state into the order of c->vals_alt (the sorted slots of the build); n = c->n live entries
+static int reorder_sorted(sph_ctx *c) {
+    const int64_t n = c->n;
+    const unsigned gb = (unsigned)((std::max<int64_t>(n, 1) + 255) / 256);
+    hipStream_t st = c->stream;
+    // ---- reorder state into sorted slots --------------------------------------------------
+    ReorderArgs ra{};
+    for (int k = 0; k < 9; k++) { ra.src[k] = c->f[k]; ra.dst[k] = c->f_alt[k]; }
+    ra.nf = 9; ra.prec = nullptr;
+    if (c->variable) { ra.src[9] = c->f[SPH_F_H]; ra.dst[9] = c->f_alt[9]; ra.nf = 10; ra.prec = c->prec; }
+    reorder<<<dim3(gb), dim3(256), 0, st>>>(ra, c->vals_alt, c->orig, c->orig_alt, c->inv, c->drec, n);
+    GR_CHECK(hipGetLastError());
+    for (int k = 0; k < 9; k++) std::swap(c->f[k], c->f_alt[k]);
+    if (c->variable) std::swap(c->f[SPH_F_H], c->f_alt[9]);
+    std::swap(c->orig, c->orig_alt);
+    c->grid_builds++;
+    return SPH_OK;
+}
+
+void grid_hash_free(sph_ctx *c) {
+    ctx_free(c, c->hkeys); ctx_free(c, c->hkeys_alt); ctx_free(c, c->ukey); ctx_free(c, c->ustart); ctx_free(c, c->uidx);
+    ctx_free(c, c->d_m); ctx_free(c, c->htab);
+    ctx_free_ptr(c, c->hash_tmp); c->hash_tmp = nullptr;
+    c->hash_cap = 0; c->htab_len = 0; c->hash_tmp_bytes = 0; c->hash_bytes = 0;
+    c->hv = HashView{};
+}
+
+int64_t grid_occupied_cells(const sph_ctx *c) {
+    if (!c->hashed) return c->grid.ncells;
+    int32_t m = 0;
+    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&m, c->d_m, sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return m;
+}
+
+// keys, sort, occupied cells and hash table of a hashed grid (c->grid set).  Every buffer is sized from the particle
+// capacity, never from the occupied-cell count, which stays on the device: the build adds no read-back.
+static int hash_build(sph_ctx *c, bool swap) {
+    const GridDesc &g = c->grid;
+    const int64_t n = c->n, ns = c->n_slots;
+    hipStream_t st = c->stream;
+    if (c->hash_cap < c->cap) {
+        grid_hash_free(c);
+        const int64_t cap = c->cap;
+        int64_t tl = 1;
+        while (tl < 4 * cap) tl <<= 1;            // two keys per occupied cell at most 2 cap: load factor <= 1/2
+        size_t sort_b = 0, scan_b = 0;
+        GR_CHECK(rocprim::radix_sort_pairs(nullptr, sort_b, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
+                                           (uint32_t *)nullptr, (size_t)cap, 0u, 64u, st));
+        GR_CHECK(rocprim::inclusive_scan(nullptr, scan_b, (int32_t *)nullptr, (int32_t *)nullptr, (size_t)cap, rocprim::plus<int32_t>(), st));
+        const int64_t before = c->device_bytes;
+        const size_t tmp = std::max(sort_b, scan_b);
+        if (ctx_alloc(c, &c->hkeys, (size_t)cap, "hashed grid keys") != SPH_OK ||
+            ctx_alloc(c, &c->hkeys_alt, (size_t)cap, "hashed grid keys (alt)") != SPH_OK ||
+            ctx_alloc(c, &c->ukey, (size_t)cap + 1, "hashed grid cell keys") != SPH_OK ||
+            ctx_alloc(c, &c->ustart, (size_t)cap + 2, "hashed grid cell starts") != SPH_OK ||
+            ctx_alloc(c, &c->uidx, (size_t)cap, "hashed grid run index") != SPH_OK ||
+            ctx_alloc(c, &c->d_m, 4, "hashed grid cell count") != SPH_OK ||
+            ctx_alloc(c, &c->htab, (size_t)tl, "hashed grid table") != SPH_OK ||
+            ctx_alloc_bytes(c, &c->hash_tmp, tmp ? tmp : 1, "hashed grid scratch") != SPH_OK) {
+            grid_hash_free(c);
+            return SPH_ERR_NOMEM;
+        }
+        c->hash_cap = cap; c->htab_len = tl; c->hash_tmp_bytes = tmp;
+        c->hash_bytes = c->device_bytes - before;
+    }
+    if (c->variable && c->hmax_cap < c->cap + 1) {
+        ctx_free(c, c->cell_hmax);
+        if (ctx_alloc(c, &c->cell_hmax, (size_t)c->cap + 1, "cell hmax") != SPH_OK) { c->hmax_cap = 0; return SPH_ERR_NOMEM; }
+        c->hmax_cap = c->cap + 1;
+    }
+    int b[3];
+    for (int a = 0; a < 3; a++) {
+        b[a] = 0;
+        while (((int64_t)1 << b[a]) < g.dim[g.s[a]]) b[a]++;
+    }
+    const int sh1 = b[0], sh2 = b[0] + b[1];
+    const unsigned bits = (unsigned)std::max(1, sh2 + b[2] + (swap ? 1 : 0));    // ~0 keys of replaced ghosts: all ones, behind every cell
+    const unsigned gbs = (unsigned)((ns + 255) / 256), gb = (unsigned)((std::max<int64_t>(n, 1) + 255) / 256);
+    hash_keys<<<dim3(gbs), dim3(256), 0, st>>>(g, sh1, sh2, c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], ns, c->hkeys, c->vals,
+                                               c->orig, (int32_t)c->n_owned, c->dead_below);
+    GR_CHECK(hipGetLastError());
+    size_t tmp = c->hash_tmp_bytes;
+    GR_CHECK(rocprim::radix_sort_pairs(c->hash_tmp, tmp, c->hkeys, c->hkeys_alt, c->vals, c->vals_alt, (size_t)ns, 0u, bits, st));
+    c->n_slots = n; c->dead_below = 0;     // the replaced ghosts sorted behind the n live entries and are dropped here
+    GR_CHECK(hipMemsetAsync(c->d_m, 0, sizeof(int32_t), st));          // no live particle: no cell (hash_compact writes nothing)
+    GR_CHECK(hipMemsetAsync(c->ustart, 0, sizeof(int32_t), st));
+    if (n > 0) {
+        hash_heads<<<dim3(gb), dim3(256), 0, st>>>(c->hkeys_alt, n, c->uidx);
+        GR_CHECK(hipGetLastError());
+        tmp = c->hash_tmp_bytes;
+        GR_CHECK(rocprim::inclusive_scan(c->hash_tmp, tmp, c->uidx, c->uidx, (size_t)n, rocprim::plus<int32_t>(), st));
+        hash_compact<<<dim3(gb), dim3(256), 0, st>>>(c->hkeys_alt, c->uidx, n, c->ukey, c->ustart, c->d_m);
+    }
+    GR_CHECK(hipMemsetAsync(c->htab, 0xff, sizeof(HashEnt) * (size_t)c->htab_len, st));
+    hash_insert<<<dim3(gb), dim3(256), 0, st>>>(c->ukey, c->ustart, c->d_m, c->htab, (uint64_t)(c->htab_len - 1));
+    GR_CHECK(hipGetLastError());
+    c->hv.tab = c->htab; c->hv.ukey = c->ukey; c->hv.ustart = c->ustart; c->hv.m = c->d_m;
+    c->hv.mask = (uint64_t)(c->htab_len - 1); c->hv.sh1 = sh1; c->hv.sh2 = sh2;
+    return SPH_OK;
+}
+
 int grid_rebuild(sph_ctx *c) {
     const int64_t n = c->n;                 // live particles after the build
     const int64_t ns = c->n_slots;          // occupied slots before it (> n while a ghost swap is pending)
@@ -464,64 +620,94 @@ int grid_rebuild(sph_ctx *c) {
     bb = c->bbox;
     GridDesc g{};
     // fixed h: cells of edge 2h.  variable h: edge 2 <h> with a per-cell maximum of h (varh.hip)
-    double edge = 2.0 * (c->variable ? c->h_mean : c->p.h) * (1.0 + 1e-6);
-    if (c->variable) {
-        // keep the cell table below ~2^27 cells: widen the cells if the box is huge compared with <h>
-        double vol = 1.0;
-        for (int a = 0; a < 3; a++) vol *= std::floor((bb[3 + a] - bb[a]) / edge) + 1.0;
-        if (vol > 134217728.0) edge *= std::cbrt(vol / 134217728.0);
-    }
+    const double edge = 2.0 * (c->variable ? c->h_mean : c->p.h) * (1.0 + 1e-6);
     g.inv_edge = 1.0 / edge;
-    // Very sparse domains (a particle that escaped to 1e5 AU, a diffuse halo): the cell table must not grow with the
-    // VOLUME of the bounding box.  The grid's box need not hold every particle -- a particle outside it is clamped into
-    // a boundary cell, where it still meets all its neighbours (cells are >= 2h wide, so everything within 2h of an
-    // outside particle is clamped to the same layer or sits in the last one) -- so when the exact box would need more
-    // than ~64 cells per particle the grid covers the bulk only: mean +- 6 sigma of the particles inside the current box,
-    // trimmed repeatedly (a far outlier inflates sigma, the next round no longer sees it).  Results do not depend on the
-    // box beyond summation order; only the boundary cells get crowded if MANY particles lie outside.
-    double tb[6] = {bb[0], bb[1], bb[2], bb[3], bb[4], bb[5]};
     auto cells_of = [&](const double *b) {
         double v = 1.0;
         for (int a = 0; a < 3; a++) v *= std::floor((b[3 + a] - b[a]) * g.inv_edge) + 1.0;
         return v;
     };
     const double sparse_limit = 64.0 * (double)ns + 4.0e6;
-    for (int round = 0; round < 8 && cells_of(tb) > sparse_limit; round++) {
-        Box6 bx;
-        for (int a = 0; a < 3; a++) { bx.lo[a] = tb[a]; bx.hi[a] = tb[3 + a]; }
-        double *mpart = c->bbox_part;                                   // >= 1024 * 7 doubles
-        moment_partial<<<dim3(nb), dim3(BB_BLOCK), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], ns, bx, mpart, c->orig,
-                                                            (int32_t)c->n_owned, c->dead_below);
-        moment_final<<<dim3(1), dim3(448), 0, st>>>(mpart, nb, mpart + (size_t)BB_MAX_BLOCKS * 7);
-        GR_CHECK(hipGetLastError());
-        GR_CHECK(hipMemcpyAsync(c->h_pinned + 280, mpart + (size_t)BB_MAX_BLOCKS * 7, 7 * sizeof(double), hipMemcpyDeviceToHost, st));
-        GR_CHECK(hipStreamSynchronize(st));
-        c->host_syncs++;
-        const double *mo = c->h_pinned + 280;
-        if (!(mo[0] >= 1.0)) break;
-        bool shrunk = false;
-        for (int a = 0; a < 3; a++) {
-            const double mean = mo[1 + a] / mo[0];
-            const double sig = std::sqrt(std::max(mo[4 + a] / mo[0] - mean * mean, 0.0));
-            const double half = 6.0 * sig + 2.0 * edge;
-            const double lo = std::max(tb[a], mean - half), hi = std::min(tb[3 + a], mean + half);
-            if (lo > tb[a] || hi < tb[3 + a]) shrunk = true;
-            tb[a] = lo; tb[3 + a] = hi;
-        }
-        if (!shrunk) break;
+    // Dense or hashed.  Dense wherever a dense table can be built (below); hashed when SPH_FLAG_HASHED_GRID asks for it, where
+    // the dense table cannot hold the box (fixed h: 2^31 cells after the trim below; variable h: more than 2^27 cells, where
+    // the cells used to be widened to many smoothing lengths), and -- once a build had to go hashed -- while the untrimmed box
+    // stays sparse: such builds skip the trim rounds and their read-backs.  A hashed grid covers the untrimmed box.
+    bool hashed = (c->p.flags & SPH_FLAG_HASHED_GRID) != 0;
+    if (!hashed && c->hash_sticky) {
+        hashed = cells_of(bb) > sparse_limit;
+        if (!hashed) c->hash_sticky = false;
     }
+    if (!hashed && c->variable && cells_of(bb) > 134217728.0) hashed = c->hash_sticky = true;
+    // Very sparse domains (a particle that escaped to 1e5 AU, a diffuse halo): the cell table must not grow with the
+    // VOLUME of the bounding box.  The grid's box need not hold every particle -- a particle outside it is clamped into
+    // a boundary cell, where it still meets all its neighbours (cells are >= 2h wide, so everything within 2h of an
+    // outside particle is clamped to the same layer or sits in the last one) -- so when the exact box would need more
+    // than ~64 cells per particle the grid covers the bulk only: mean +- 6 sigma of the particles inside the current box,
+    // trimmed repeatedly (a far outlier inflates sigma, the next round no longer sees it).  Results do not depend on the
+    // box beyond summation order; only the boundary cells get crowded if MANY particles lie outside.  A hashed grid trims
+    // only the axes that exceed 2^21 cells (the bits of its keys).
+    double tb[6] = {bb[0], bb[1], bb[2], bb[3], bb[4], bb[5]};
+    auto axis_cells = [&](const double *b, int a) { return std::floor((b[3 + a] - b[a]) * g.inv_edge) + 1.0; };
+    const double axis_limit = (double)(1 << HASH_AXIS_BITS);
+    auto too_long = [&](const double *b) {
+        for (int a = 0; a < 3; a++) if (axis_cells(b, a) > axis_limit) return true;
+        return false;
+    };
+    auto trim = [&](bool for_hash) -> int {
+        for (int round = 0; round < 8 && (for_hash ? too_long(tb) : cells_of(tb) > sparse_limit); round++) {
+            Box6 bx;
+            for (int a = 0; a < 3; a++) { bx.lo[a] = tb[a]; bx.hi[a] = tb[3 + a]; }
+            double *mpart = c->bbox_part;                                   // >= 1024 * 7 doubles
+            moment_partial<<<dim3(nb), dim3(BB_BLOCK), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], ns, bx, mpart, c->orig,
+                                                                (int32_t)c->n_owned, c->dead_below);
+            moment_final<<<dim3(1), dim3(448), 0, st>>>(mpart, nb, mpart + (size_t)BB_MAX_BLOCKS * 7);
+            GR_CHECK(hipGetLastError());
+            GR_CHECK(hipMemcpyAsync(c->h_pinned + 280, mpart + (size_t)BB_MAX_BLOCKS * 7, 7 * sizeof(double), hipMemcpyDeviceToHost, st));
+            GR_CHECK(hipStreamSynchronize(st));
+            c->host_syncs++;
+            const double *mo = c->h_pinned + 280;
+            if (!(mo[0] >= 1.0)) break;
+            bool shrunk = false;
+            for (int a = 0; a < 3; a++) {
+                if (for_hash && axis_cells(tb, a) <= axis_limit) continue;
+                const double mean = mo[1 + a] / mo[0];
+                const double sig = std::sqrt(std::max(mo[4 + a] / mo[0] - mean * mean, 0.0));
+                const double half = 6.0 * sig + 2.0 * edge;
+                const double lo = std::max(tb[a], mean - half), hi = std::min(tb[3 + a], mean + half);
+                if (lo > tb[a] || hi < tb[3 + a]) shrunk = true;
+                tb[a] = lo; tb[3 + a] = hi;
+            }
+            if (!shrunk) break;
+        }
+        return SPH_OK;
+    };
+    if (!hashed) {
+        { const int st2 = trim(false); if (st2 != SPH_OK) return st2; }
+        double ncell_d = 1.0;
+        for (int a = 0; a < 3; a++) {
+            const double d = std::floor((tb[3 + a] - tb[a]) * g.inv_edge) + 1.0;
+            if (!(d >= 1.0)) { c->err = "cell grid dimension out of range"; return SPH_ERR_GRID; }
+            ncell_d *= d;
+        }
+        if (ncell_d >= 2147483647.0) {          // the dense table cannot hold even the trimmed box: hashed, over the whole box
+            hashed = c->hash_sticky = true;
+            for (int a = 0; a < 6; a++) tb[a] = bb[a];
+        }
+    }
+    if (hashed) { const int st2 = trim(true); if (st2 != SPH_OK) return st2; }
     bb = tb;
     double ncell_d = 1.0;
     for (int a = 0; a < 3; a++) {
         g.org[a] = bb[a];
         double ext = bb[3 + a] - bb[a];
         double d = std::floor(ext * g.inv_edge) + 1.0;
-        if (!(d >= 1.0) || d > 2.0e9) { c->err = "cell grid dimension out of range"; return SPH_ERR_GRID; }
+        if (!(d >= 1.0) || d > (hashed ? axis_limit : 2.0e9)) { c->err = "cell grid dimension out of range"; return SPH_ERR_GRID; }
         g.dim[a] = (int32_t)d;
         ncell_d *= d;
     }
-    if (ncell_d >= 2147483647.0) { c->err = "cell grid exceeds 2^31 cells"; return SPH_ERR_GRID; }
-    g.ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
+    if (!hashed && ncell_d >= 2147483647.0) { c->err = "cell grid exceeds 2^31 cells"; return SPH_ERR_GRID; }
+    g.ncells = hashed ? 0 : (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
+    c->index_cells = ncell_d;
     // axis permutation: the axis with the fewest cells runs fastest (a column of cells is short: the thin direction of a
     // disc), the LONGEST of the other two is the middle one.  Rows are then as long as possible, a workgroup of consecutive
     // particles rarely wraps from one row into the next, and its three candidate intervals (tiled.hip) stay a few columns
@@ -534,16 +720,23 @@ int grid_rebuild(sph_ctx *c) {
     std::swap(s[1], s[2]);
     g.s[0] = s[0]; g.s[1] = s[1]; g.s[2] = s[2];
     c->grid = g;
+    c->hashed = hashed;
+    if (hashed) {
+        const int st2 = hash_build(c, swap);
+        if (st2 != SPH_OK) return st2;
+        return reorder_sorted(c);
+    }
 
     if (g.ncells + 2 > c->cell_cap) {
         ctx_free(c, c->cell_start); c->cell_fill = nullptr;
         c->cell_cap = (g.ncells + 2) + (g.ncells + 2) / 4;
         // one allocation: the cell table and, right behind the part in use, the cursors of the counting sort (one fill zeroes both)
         if (ctx_alloc(c, &c->cell_start, 2 * (size_t)c->cell_cap + 16, "cell table + cursors") != SPH_OK) { c->cell_cap = 0; return SPH_ERR_NOMEM; }
-        if (c->variable) {
-            ctx_free(c, c->cell_hmax);
-            if (ctx_alloc(c, &c->cell_hmax, (size_t)c->cell_cap, "cell hmax") != SPH_OK) { c->cell_cap = 0; return SPH_ERR_NOMEM; }
-        }
+    }
+    if (c->variable && c->hmax_cap < c->cell_cap) {
+        ctx_free(c, c->cell_hmax);
+        if (ctx_alloc(c, &c->cell_hmax, (size_t)c->cell_cap, "cell hmax") != SPH_OK) { c->hmax_cap = 0; return SPH_ERR_NOMEM; }
+        c->hmax_cap = c->cell_cap;
     }
 
     // ---- keys, sort, cell table ---------------------------------------------------------
@@ -582,18 +775,7 @@ int grid_rebuild(sph_ctx *c) {
         GR_CHECK(hipGetLastError());
     }
 
-    // ---- reorder state into sorted slots --------------------------------------------------
-    ReorderArgs ra{};
-    for (int k = 0; k < 9; k++) { ra.src[k] = c->f[k]; ra.dst[k] = c->f_alt[k]; }
-    ra.nf = 9; ra.prec = nullptr;
-    if (c->variable) { ra.src[9] = c->f[SPH_F_H]; ra.dst[9] = c->f_alt[9]; ra.nf = 10; ra.prec = c->prec; }
-    reorder<<<dim3(gb), dim3(256), 0, st>>>(ra, c->vals_alt, c->orig, c->orig_alt, c->inv, c->drec, n);
-    GR_CHECK(hipGetLastError());
-    for (int k = 0; k < 9; k++) std::swap(c->f[k], c->f_alt[k]);
-    if (c->variable) std::swap(c->f[SPH_F_H], c->f_alt[9]);
-    std::swap(c->orig, c->orig_alt);
-    c->grid_builds++;
-    return SPH_OK;
+    return reorder_sorted(c);
 }
 
 }  // namespace sph

@@ -27,6 +27,50 @@ __device__ __forceinline__ void cell_coords(const GridDesc &g, double px, double
     cc[0] = c[g.s[0]]; cc[1] = c[g.s[1]]; cc[2] = c[g.s[2]];
 }
 
+// ---- cell tables ------------------------------------------------------------------------------
+// Every consumer asks one question: the first sorted slot whose cell is at or after (c2, c1, c0) in row-major order, for
+// c0 in [0, d0] (d0: the end of the row).  CellTab<false> answers from the dense table, CellTab<true> from the hashed one
+// (sph_internal.hpp HashView) with the same values, so both give the same lists, tiles and sums.  at() = that slot; ent()
+// also returns the lower-bound index among the occupied cells (= the cell's own index when it is occupied: cell_hmax).
+__device__ __forceinline__ uint64_t hash_mix(uint64_t k) {
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
+    return k ^ (k >> 33);
+}
+
+__device__ __forceinline__ int2 hash_find(const HashView &h, uint64_t key) {
+    for (uint64_t s = hash_mix(key) & h.mask;; s = (s + 1) & h.mask) {
+        const HashEnt e = h.tab[s];
+        if (e.key == key) return make_int2(e.idx, e.start);
+        if (e.key == ~0ull) break;
+    }
+    int lo = 0, hi = *h.m;                          // not in the table: an empty cell, the exact lower bound by bisection
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (h.ukey[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return make_int2(lo, h.ustart[lo]);
+}
+
+template <bool HASHED> struct CellTab;
+template <> struct CellTab<false> {
+    const int32_t *__restrict__ start;
+    int d0, d1;
+    typedef int64_t Row;
+    __device__ __forceinline__ CellTab(const GridDesc &g, const int32_t *__restrict__ cell_start, const HashView &)
+        : start(cell_start), d0(g.dim[g.s[0]]), d1(g.dim[g.s[1]]) {}
+    __device__ __forceinline__ Row row(int c2, int c1) const { return ((int64_t)c2 * d1 + c1) * d0; }
+    __device__ __forceinline__ int at(Row r, int c0) const { return start[r + c0]; }
+};
+template <> struct CellTab<true> {
+    HashView h;
+    typedef uint64_t Row;
+    __device__ __forceinline__ CellTab(const GridDesc &, const int32_t *__restrict__, const HashView &hv) : h(hv) {}
+    __device__ __forceinline__ Row row(int c2, int c1) const { return ((uint64_t)c2 << h.sh2) | ((uint64_t)c1 << h.sh1); }
+    __device__ __forceinline__ int at(Row r, int c0) const { return hash_find(h, r + (uint64_t)c0).y; }
+    __device__ __forceinline__ int2 ent(Row r, int c0) const { return hash_find(h, r + (uint64_t)c0); }
+};
+
 __device__ __forceinline__ int wave_max_i32(int v) {
     for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
     return v;

@@ -39,12 +39,13 @@ constexpr int PAIR_BLOCK = 256;
 // neighbour list: every j != i with |x_i - x_j|^2 <= rcut2 (rcut2 a hair above (2h)^2; the
 // evaluation kernels re-test q <= 2 exactly as lookup_kernel does, [F]:113)
 // ------------------------------------------------------------------------------------------
+template <bool HASHED>
 __global__ __launch_bounds__(PAIR_BLOCK) void nlist_kernel(GridDesc g, const double4 *__restrict__ drec,
                                                            const int32_t *__restrict__ cell_start, int64_t n,
                                                            double rcut2, int32_t cap, int32_t *__restrict__ nlist,
                                                            int32_t *__restrict__ ncount, int32_t *__restrict__ wave_max,
                                                            int32_t *__restrict__ wave_need, const int32_t *__restrict__ orig,
-                                                           int32_t n_owned) {
+                                                           int32_t n_owned, HashView hv) {
     const int64_t i = (int64_t)xcd_chunk(blockIdx.x, gridDim.x) * PAIR_BLOCK + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const int64_t w = i >> 6;
@@ -56,6 +57,7 @@ __global__ __launch_bounds__(PAIR_BLOCK) void nlist_kernel(GridDesc g, const dou
         cell_coords(g, pi.x, pi.y, pi.z, cc);
         const int d0 = g.dim[g.s[0]], d1 = g.dim[g.s[1]], d2 = g.dim[g.s[2]];
         const int lo0 = max(cc[0] - 1, 0), hi0 = min(cc[0] + 1, d0 - 1);
+        const CellTab<HASHED> tab(g, cell_start, hv);
         int32_t *mine = nlist + ((size_t)w * cap) * 64 + lane;
         for (int o2 = -1; o2 <= 1; o2++) {
             const int c2 = cc[2] + o2;
@@ -63,8 +65,14 @@ __global__ __launch_bounds__(PAIR_BLOCK) void nlist_kernel(GridDesc g, const dou
             for (int o1 = -1; o1 <= 1; o1++) {
                 const int c1 = cc[1] + o1;
                 if (c1 < 0 || c1 >= d1) continue;
-                const int64_t row = ((int64_t)c2 * d1 + c1) * d0;
-                const int jb = cell_start[row + lo0], je = cell_start[row + hi0 + 1];
+                int jb, je;
+                if constexpr (HASHED) {
+                    const auto row = tab.row(c2, c1);
+                    jb = tab.at(row, lo0); je = tab.at(row, hi0 + 1);
+                } else {
+                    const int64_t row = ((int64_t)c2 * d1 + c1) * d0;
+                    jb = cell_start[row + lo0]; je = cell_start[row + hi0 + 1];
+                }
                 // 4 candidates per trip: the loads are independent, so four gathers are in flight
                 for (int j = jb; j < je; j += 4) {
                     double r2[4];
@@ -368,9 +376,10 @@ int nlist_build(sph_ctx *c) {
     const PairConst pc = make_pair_const(c);
     for (int attempt = 0; attempt < 8; attempt++) {
         // per-wave longest lists go to wave_class (written again by classify_waves only after the build), their maximum straight to the host
-        nlist_kernel<<<dim3(pair_blocks(n)), dim3(PAIR_BLOCK), 0, c->stream>>>(
+        auto nl = c->hashed ? nlist_kernel<true> : nlist_kernel<false>;
+        nl<<<dim3(pair_blocks(n)), dim3(PAIR_BLOCK), 0, c->stream>>>(
             c->grid, reinterpret_cast<const double4 *>(c->drec), c->cell_start, n, pc.rcut2, c->nl_cap, c->nlist,
-            c->ncount, c->wave_max, c->wave_class, c->orig, (int32_t)c->n_owned);
+            c->ncount, c->wave_max, c->wave_class, c->orig, (int32_t)c->n_owned, c->hv);
         max_to_host<<<dim3(1), dim3(1024), 0, c->stream>>>(c->wave_class, (n + 63) / 64, reinterpret_cast<int32_t *>(c->h_pinned + 9));
         NL_CHECK(hipGetLastError());
         NL_CHECK(hipStreamSynchronize(c->stream));

@@ -34,6 +34,24 @@ struct GridDesc {
     int64_t ncells;
 };
 
+// Hashed cell table (grid.hip; domains whose box is too sparse for a dense table).  The same GridDesc, but the cell of
+// (c2, c1, c0) (permuted axes, c2 slowest) is the 64-bit key c2 << sh2 | c1 << sh1 | c0 with bit widths >= log2 of each
+// dimension: key order is the dense row-major order, so the sorted particle order is the dense one.  The occupied cells
+// are compacted into ukey[0..m) / ustart[0..m] (ustart[m] = live particles) and hashed (open addressing, linear probing):
+// every occupied key k maps to {its index, ustart}, and k + 1 to {index + 1, ustart[index + 1]} (the end of a cell run).
+// A lookup answers what the dense table answers -- the lower bound of the key in the sorted order -- and falls back to a
+// binary search over ukey for the keys the table does not hold.
+constexpr int HASH_AXIS_BITS = 21;            // cells per axis of a hashed grid: at most 2^21 (three axes fit 63 bits)
+struct HashEnt { uint64_t key; int32_t idx, start; };      // empty: key = ~0
+struct HashView {
+    const HashEnt *tab;
+    const uint64_t *ukey;      // occupied cell keys, ascending
+    const int32_t *ustart;     // first sorted slot of each, [m] = live particles
+    const int32_t *m;          // occupied cells (device)
+    uint64_t mask;             // table entries - 1 (a power of two)
+    int32_t sh1, sh2;          // bit offsets of c1 and c2 in a key
+};
+
 // Constants every pair kernel needs; passed by value as a kernel argument (SGPRs).
 struct PairConst {
     double h;            // smoothing length
@@ -163,6 +181,18 @@ struct sph_ctx {
     bool bbox_exact = true;          // c->bbox is the exact box of the last build (not the previous one widened)
     bool no_stale = false;           // SPH_SYNC_EVERY_BUILD: wait for every read-back (A/B switch)
     int64_t host_syncs = 0;          // stream synchronisations inside the build path (statistics)
+    // hashed cell table (grid.hip): used instead of cell_start when the current grid is hashed
+    bool hashed = false;             // the current grid build is hashed
+    bool hash_sticky = false;        // a build had to go hashed: later ones skip the dense attempt while the box stays sparse
+    sph::HashView hv{};
+    int64_t hash_cap = 0;            // particles the hashed buffers hold
+    uint64_t *hkeys = nullptr, *hkeys_alt = nullptr;    // 64-bit cell keys and the sorted copy
+    uint64_t *ukey = nullptr; int32_t *ustart = nullptr, *uidx = nullptr, *d_m = nullptr;
+    sph::HashEnt *htab = nullptr; int64_t htab_len = 0;
+    void *hash_tmp = nullptr; size_t hash_tmp_bytes = 0;
+    int64_t hash_bytes = 0;          // device bytes of the buffers above
+    double index_cells = 0.0;        // cells the current grid indexes (dim product; hashed: most of them empty)
+    int64_t hmax_cap = 0;            // entries cell_hmax holds
 
     // neighbour list: slot k of particle i (wave w = i/64, lane = i%64) lives at
     // nlist[(w*nl_cap + k)*64 + lane]  -> a wave reads 64 consecutive ints per k
@@ -235,6 +265,8 @@ inline void ctx_free(sph_ctx *c, T *&p) {
 hipError_t grid_sort_tmp_bytes(int64_t n, size_t *bytes);
 // builds sorted order + cell table from the current positions.  Synchronises once (bbox read-back).
 int grid_rebuild(sph_ctx *c);
+void grid_hash_free(sph_ctx *c);
+int64_t grid_occupied_cells(const sph_ctx *c);   // hashed: reads the occupied-cell count back (synchronises); dense: ncells
 // builds the neighbour list; synchronises once (overflow check), grows the list if needed
 int nlist_build(sph_ctx *c);
 hipError_t launch_density(sph_ctx *c, const PairConst &pc);

@@ -63,7 +63,8 @@ struct Rows {
     int jb[3], je[3];     // this target's three cell rows (o1 = -1, 0, +1) of the current o2
 };
 
-__device__ __forceinline__ void target_rows(const GridDesc &g, const int32_t *__restrict__ cell_start, const int cc[3], bool live,
+template <bool HASHED>
+__device__ __forceinline__ void target_rows(const GridDesc &g, const CellTab<HASHED> &tab, const int cc[3], bool live,
                                             int o2, Rows &r) {
     const int d0 = g.dim[g.s[0]], d1 = g.dim[g.s[1]], d2 = g.dim[g.s[2]];
     const int c2 = cc[2] + o2;
@@ -73,9 +74,9 @@ __device__ __forceinline__ void target_rows(const GridDesc &g, const int32_t *__
         const int c1 = cc[1] + o1;
         const bool ok = live && c2 >= 0 && c2 < d2 && c1 >= 0 && c1 < d1;
         if (ok) {
-            const int64_t row = ((int64_t)c2 * d1 + c1) * d0;
-            r.jb[o1 + 1] = cell_start[row + lo0];
-            r.je[o1 + 1] = cell_start[row + hi0 + 1];
+            const auto row = tab.row(c2, c1);
+            r.jb[o1 + 1] = tab.at(row, lo0);
+            r.je[o1 + 1] = tab.at(row, hi0 + 1);
         } else {
             r.jb[o1 + 1] = 0; r.je[o1 + 1] = 0;
         }
@@ -99,8 +100,9 @@ __device__ __forceinline__ void block_interval(const Rows &r, int *s_lo, int *s_
 // neighbour list build: every j != i with |x_i - x_j|^2 <= rcut2.  The workgroup stages its candidate intervals
 // chunk-wise (coalesced), each lane scans its 9 cell rows out of LDS and appends 16-byte quads to its list column.
 // ------------------------------------------------------------------------------------------
+template <bool HASHED>
 __global__ __launch_bounds__(TB) void nlist_tiled(GridDesc g, const double4 *__restrict__ drec,
-                                                  const int32_t *__restrict__ cell_start, int64_t n, double rcut2, int32_t cap,
+                                                  const int32_t *__restrict__ cell_start, HashView hv, int64_t n, double rcut2, int32_t cap,
                                                   int4 *__restrict__ nlist4, int32_t *__restrict__ ncount,
                                                   int32_t *__restrict__ wave_max, int32_t *__restrict__ flags,
                                                   const int32_t *__restrict__ orig, int32_t n_owned, int2 *__restrict__ deal,
@@ -115,6 +117,7 @@ __global__ __launch_bounds__(TB) void nlist_tiled(GridDesc g, const double4 *__r
     const double4 pi = drec[i < n ? i : n - 1];
     int cc[3];
     cell_coords(g, pi.x, pi.y, pi.z, cc);
+    const CellTab<HASHED> tab(g, cell_start, hv);
     const int cap8 = cap >> 3;
     int4 *mine = nlist4 + ((size_t)w * cap8) * 64 + lane;
     uint16_t *myrow = reinterpret_cast<uint16_t *>(&rowbuf[threadIdx.x]);
@@ -126,7 +129,7 @@ __global__ __launch_bounds__(TB) void nlist_tiled(GridDesc g, const double4 *__r
 #pragma unroll
     for (int o2 = -1; o2 <= 1; o2++) {
         Rows r;
-        target_rows(g, cell_start, cc, live, o2, r);
+        target_rows(g, tab, cc, live, o2, r);
         int lo, hi;
         block_interval(r, s_lo, s_hi, lo, hi);
         plo[o2 + 1] = lo; plen[o2 + 1] = hi > lo ? hi - lo : 0;
@@ -226,14 +229,14 @@ __global__ __launch_bounds__(TB) void nlist_tiled(GridDesc g, const double4 *__r
 // unconditional loads and a scalar trip count; enough waves per SIMD.
 // ------------------------------------------------------------------------------------------
 // s_lo / s_hi: LDS scratch of 3 * NW ints each (NW = waves per workgroup); one barrier for the three intervals
-template <int NW>
-__device__ __forceinline__ void tile_map(const GridDesc &g, const int32_t *__restrict__ cell_start, const int cc[3], bool live,
+template <int NW, bool HASHED>
+__device__ __forceinline__ void tile_map(const GridDesc &g, const CellTab<HASHED> &tab, const int cc[3], bool live,
                                          int *s_lo, int *s_hi, TileMap &m) {
     int mn[3], mx[3];
 #pragma unroll
     for (int q = 0; q < 3; q++) {
         Rows r;
-        target_rows(g, cell_start, cc, live, q - 1, r);
+        target_rows(g, tab, cc, live, q - 1, r);
         mn[q] = 0x7fffffff; mx[q] = 0;
 #pragma unroll
         for (int k = 0; k < 3; k++)
@@ -782,7 +785,8 @@ int nlist_build_tiled(sph_ctx *c) {
         if (4 * (int64_t)prev[0] > 3 * (int64_t)c->nl_cap) { const int st = regrow(prev[0] + prev[0] / 2 + 8); if (st != SPH_OK) return st; }
     }
     for (int attempt = 0; attempt < 8; attempt++) {
-        nlist_tiled<<<dim3(tb_blocks(n)), dim3(TB), 0, c->stream>>>(c->grid, reinterpret_cast<const double4 *>(c->drec), c->cell_start,
+        auto nl = c->hashed ? nlist_tiled<true> : nlist_tiled<false>;
+        nl<<<dim3(tb_blocks(n)), dim3(TB), 0, c->stream>>>(c->grid, reinterpret_cast<const double4 *>(c->drec), c->cell_start, c->hv,
                                                                     n, pc.rcut2, c->nl_cap, reinterpret_cast<int4 *>(c->nlist),
                                                                     c->ncount, c->wave_max, c->d_flags, c->orig, (int32_t)c->n_owned,
                                                                     c->whole_tile ? reinterpret_cast<int2 *>(c->deal) : nullptr,

@@ -224,6 +224,16 @@ __global__ __launch_bounds__(VBLOCK) void cell_hmax_kernel(const int32_t *__rest
     hmax[c] = 4.0 * m * m * (1.0 + 1e-12);          // stored as the squared reach (2 hmax)^2 (1 + 1e-12), what the build compares with
 }
 
+// the same per occupied cell of a hashed grid (cells [0, *m): their count is known on the device only)
+__global__ __launch_bounds__(VBLOCK) void cell_hmax_hashed(const int32_t *__restrict__ ustart, const int32_t *__restrict__ m_ptr,
+                                                           const double4 *__restrict__ prec, double *__restrict__ hmax) {
+    const int64_t c = (int64_t)blockIdx.x * VBLOCK + threadIdx.x;
+    if (c >= *m_ptr) return;
+    double m = 0.0;
+    for (int j = ustart[c]; j < ustart[c + 1]; j++) m = fmax(m, prec[j].w);
+    hmax[c] = 4.0 * m * m * (1.0 + 1e-12);
+}
+
 __device__ __forceinline__ bool reaches(const double4 &leaf, double x, double y, double z) {
     return ((int)(fabs(x - leaf.x) < leaf.w) & (int)(fabs(y - leaf.y) < leaf.w) & (int)(fabs(z - leaf.z) < leaf.w)) != 0;     // no short circuit: no branches
 }
@@ -271,9 +281,10 @@ __device__ __forceinline__ void pair_flags(const double4 &pi, const double4 &li,
 
 // grow2 = (largest growth of any h the list shall survive)^2: candidates within 2 grow max(h_i, h_j) that count for nothing
 // now are kept in the margin shell too, so that nlist_v_reflag finds every pair a new h can switch on.
+template <bool HASHED>
 __global__ __launch_bounds__(VBLOCK) void nlist_v_tiled(GridDesc g, int R, double h_glob, double grow2, const double4 *__restrict__ prec,
                                                         const double4 *__restrict__ lrec, const int32_t *__restrict__ orig,
-                                                        const int32_t *__restrict__ cell_start, const double *__restrict__ cell_hmax,
+                                                        const int32_t *__restrict__ cell_start, HashView hv, const double *__restrict__ cell_hmax,
                                                         int64_t n, int32_t n_owned, int32_t cap, int32_t *__restrict__ nlist,
                                                         int32_t *__restrict__ ncount, int32_t *__restrict__ ntail,
                                                         int32_t *__restrict__ wave_max, int32_t *__restrict__ wave_need,
@@ -296,6 +307,7 @@ __global__ __launch_bounds__(VBLOCK) void nlist_v_tiled(GridDesc g, int R, doubl
     cell_coords(g, pi.x, pi.y, pi.z, cc);
     const int s0 = g.s[0], s1 = g.s[1], s2 = g.s[2];
     const int d0 = g.dim[s0], d1 = g.dim[s1], d2 = g.dim[s2];
+    const CellTab<HASHED> tab(g, cell_start, hv);
     const double e = 1.0 / g.inv_edge;
     const double hi = pi.w, him = pi.w * H_MARGIN;
     const double rg = 2.0 * fmax(him, h_glob), rg2 = rg * rg * (1.0 + 1e-12);
@@ -316,8 +328,8 @@ __global__ __launch_bounds__(VBLOCK) void nlist_v_tiled(GridDesc g, int R, doubl
         // the workgroup's interval for this offset
         int mn = 0x7fffffff, mx = 0;
         if (use2) {
-            mn = cell_start[((int64_t)c2 * d1 + c1lo) * d0 + c0lo];
-            mx = cell_start[((int64_t)c2 * d1 + c1hi) * d0 + c0hi + 1];
+            mn = tab.at(tab.row(c2, c1lo), c0lo);
+            mx = tab.at(tab.row(c2, c1hi), c0hi + 1);
             if (mx <= mn) { mn = 0x7fffffff; mx = 0; }
         }
         for (int o = 32; o > 0; o >>= 1) { mn = min(mn, __shfl_xor(mn, o, 64)); mx = max(mx, __shfl_xor(mx, o, 64)); }
@@ -338,16 +350,22 @@ __global__ __launch_bounds__(VBLOCK) void nlist_v_tiled(GridDesc g, int R, doubl
             for (int c1 = c1lo; c1 <= c1hi; c1++) {
                 const double g21 = g2 + axis_gap2(p[s1], g.org[s1] + c1 * e, e);
                 if (g21 > rg2) continue;
-                const int64_t row = ((int64_t)c2 * d1 + c1) * d0;
-                int js = cell_start[row + c0lo];
-                if (cell_start[row + c0hi + 1] <= cb || js >= ce) continue;                       // row not in this chunk
+                const auto row = tab.row(c2, c1);
+                int js, ci = 0;                                          // hashed: ci = index of cell c0 among the occupied ones
+                if constexpr (HASHED) { const int2 e0 = tab.ent(row, c0lo); js = e0.y; ci = e0.x; } else js = tab.at(row, c0lo);
+                if (tab.at(row, c0hi + 1) <= cb || js >= ce) continue;                       // row not in this chunk
                 for (int c0 = c0lo; c0 <= c0hi; c0++) {
-                    const int jn = cell_start[row + c0 + 1];             // one table read per cell: the end is the next start
+                    int jn, cn = 0;                                      // one table read per cell: the end is the next start
+                    if constexpr (HASHED) { const int2 e1 = tab.ent(row, c0 + 1); jn = e1.y; cn = e1.x; } else jn = tab.at(row, c0 + 1);
                     const int jb = max(js, cb), je = min(jn, ce);
                     js = jn;
+                    const int cc0 = ci;
+                    ci = cn;
                     if (jb >= je) continue;
                     const double gap = g21 + axis_gap2(p[s0], g.org[s0] + c0 * e, e);
-                    if (gap > fmax(rim2, grow2 * cell_hmax[row + c0])) continue;     // (2 max(1.1 h_i, grow hmax_C))^2 (1 + 1e-12)
+                    double hm;
+                    if constexpr (HASHED) hm = cell_hmax[cc0]; else hm = cell_hmax[row + c0];
+                    if (gap > fmax(rim2, grow2 * hm)) continue;     // (2 max(1.1 h_i, grow hmax_C))^2 (1 + 1e-12)
                     for (int j = jb; j < je; j++) {
                         const double4 pj = tile[j - cb];
                         const double dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
@@ -942,8 +960,9 @@ __device__ __forceinline__ void h_trial_finish(const PairConst &pc, double hn, c
 
 // rho and Omega of ONE body with trial length hn on the tree of the last evaluation (leaf boxes and
 // reaches hold the OLD h of every particle), [V]:531-535 -> density_tree_search
+template <bool HASHED>
 __device__ void density_one(const GridDesc &g, const double4 *__restrict__ drec, const double4 *__restrict__ lrec,
-                            const int32_t *__restrict__ cell_start, const double *__restrict__ w_tab,
+                            const CellTab<HASHED> &tab, const double *__restrict__ w_tab,
                             const double *__restrict__ dw_tab, const PairConst &pc, const double4 &pi, double hn, double &rho,
                             double &om) {
     int cc[3];
@@ -954,8 +973,8 @@ __device__ void density_one(const GridDesc &g, const double4 *__restrict__ drec,
     const double inv_hn = 1.0 / hn, inv_dq = 0.5 * pc.nq, rt2 = 4.0 * hn * hn * (1.0 + 1e-12);
     for (int c2 = max(cc[2] - R, 0); c2 <= min(cc[2] + R, d2 - 1); c2++)
         for (int c1 = max(cc[1] - R, 0); c1 <= min(cc[1] + R, d1 - 1); c1++) {
-            const int64_t row = ((int64_t)c2 * d1 + c1) * d0;
-            const int jb = cell_start[row + max(cc[0] - R, 0)], je = cell_start[row + min(cc[0] + R, d0 - 1) + 1];
+            const auto row = tab.row(c2, c1);
+            const int jb = tab.at(row, max(cc[0] - R, 0)), je = tab.at(row, min(cc[0] + R, d0 - 1) + 1);
             for (int j = jb; j < je; j++) {
                 const double4 pj = drec[j];
                 const double n0 = pi.x - pj.x, n1 = pi.y - pj.y, n2 = pi.z - pj.z;
@@ -1001,8 +1020,9 @@ __device__ void density_list(const double4 *__restrict__ drec, const int4 *__res
     h_trial_finish(pc, hn, d, rho, om);
 }
 
+template <bool HASHED>
 __global__ __launch_bounds__(VBLOCK) void update_h_kernel(GridDesc g, PairConst pc, const double4 *__restrict__ drec,
-                                                          const double4 *__restrict__ lrec, const int32_t *__restrict__ cell_start,
+                                                          const double4 *__restrict__ lrec, const int32_t *__restrict__ cell_start, HashView hv,
                                                           const double *__restrict__ w_tab, const double *__restrict__ dw_tab,
                                                           int64_t n, const double *__restrict__ h_old, double *__restrict__ h_out,
                                                           double *__restrict__ rho, double *__restrict__ omega,
@@ -1058,7 +1078,7 @@ __global__ __launch_bounds__(VBLOCK) void update_h_kernel(GridDesc g, PairConst 
     while (((hn - old_len) / old_len) > pc.h_tol && hn < pc.h_iter_cap) {                // [V]:529
         old_len = hn;
         if (has_margin && hn <= H_MARGIN * h0) density_list(drec, mine, cap4, cnt, tcnt, w_tab, dw_tab, pc, pi, hn, r, om);
-        else density_one(g, drec, lrec, cell_start, w_tab, dw_tab, pc, pi, hn, r, om);    // [V]:531-535
+        else density_one<HASHED>(g, drec, lrec, CellTab<HASHED>(g, cell_start, hv), w_tab, dw_tab, pc, pi, hn, r, om);    // [V]:531-535
         t = pc.eta / hn;
         hn = hn * (1.0 + ((pi.w * (t * t * t)) / r - 1.0) / (3.0 * om));                 // [V]:538
     }
@@ -1105,6 +1125,17 @@ int varh_h_stats(sph_ctx *c, bool with_growth) {
     return SPH_OK;
 }
 
+// per-cell maximum of h: one entry per cell of the dense table, or per occupied cell of the hashed one (their count is
+// known on the device only: the launch covers n, the upper bound)
+static hipError_t launch_cell_hmax(sph_ctx *c, const double4 *prec) {
+    if (c->hashed)
+        cell_hmax_hashed<<<dim3((unsigned)((c->n + VBLOCK - 1) / VBLOCK)), dim3(VBLOCK), 0, c->stream>>>(c->ustart, c->d_m, prec, c->cell_hmax);
+    else
+        cell_hmax_kernel<<<dim3((unsigned)((c->grid.ncells + VBLOCK - 1) / VBLOCK)), dim3(VBLOCK), 0, c->stream>>>(
+            c->cell_start, c->grid.ncells, prec, c->cell_hmax);
+    return hipGetLastError();
+}
+
 int varh_leaf_build(sph_ctx *c) {
     const int64_t n = c->n;
     if (n == 0) return SPH_OK;
@@ -1142,9 +1173,7 @@ int varh_leaf_build(sph_ctx *c) {
         VH_CHECK(hipGetLastError());
         c->path_keys_valid = true;           // the gravity tree and the accretion pass of this grid build take them from here
     }
-    cell_hmax_kernel<<<dim3((unsigned)((c->grid.ncells + VBLOCK - 1) / VBLOCK)), dim3(VBLOCK), 0, c->stream>>>(
-        c->cell_start, c->grid.ncells, prec, c->cell_hmax);
-    VH_CHECK(hipGetLastError());
+    VH_CHECK(launch_cell_hmax(c, prec));
     return SPH_OK;
 }
 
@@ -1154,9 +1183,7 @@ int varh_refresh_h(sph_ctx *c) {
     if (n == 0) return SPH_OK;
     refresh_h_records<<<dim3((unsigned)((n + VBLOCK - 1) / VBLOCK)), dim3(VBLOCK), 0, c->stream>>>(
         n, c->f[SPH_F_H], c->leaf_half, reinterpret_cast<double4 *>(c->prec), reinterpret_cast<double4 *>(c->lrec));
-    cell_hmax_kernel<<<dim3((unsigned)((c->grid.ncells + VBLOCK - 1) / VBLOCK)), dim3(VBLOCK), 0, c->stream>>>(
-        c->cell_start, c->grid.ncells, reinterpret_cast<const double4 *>(c->prec), c->cell_hmax);
-    VH_CHECK(hipGetLastError());
+    VH_CHECK(launch_cell_hmax(c, reinterpret_cast<const double4 *>(c->prec)));
     return SPH_OK;
 }
 
@@ -1170,9 +1197,10 @@ int varh_nlist_build(sph_ctx *c) {
     const double grow = no_reflag ? 1.0 : REFLAG_GROW;
     for (int attempt = 0; attempt < 8; attempt++) {
         // per-wave row needs go to wave_class (free in variable-h mode: no split force evaluation), their maximum straight to the host
-        nlist_v_tiled<<<dim3(gb), dim3(VBLOCK), 0, c->stream>>>(
+        auto nl = c->hashed ? nlist_v_tiled<true> : nlist_v_tiled<false>;
+        nl<<<dim3(gb), dim3(VBLOCK), 0, c->stream>>>(
             c->grid, R, c->h_max_glob, grow * grow, reinterpret_cast<const double4 *>(c->prec), reinterpret_cast<const double4 *>(c->lrec), c->orig,
-            c->cell_start, c->cell_hmax, n, (int32_t)c->n_owned, c->nl_cap, c->nlist, c->ncount, c->ntail, c->wave_max, c->wave_class,
+            c->cell_start, c->hv, c->cell_hmax, n, (int32_t)c->n_owned, c->nl_cap, c->nlist, c->ncount, c->ntail, c->wave_max, c->wave_class,
             c->numbers_set ? c->number : nullptr);
         max_to_host<<<dim3(1), dim3(1024), 0, c->stream>>>(c->wave_class, (n + 63) / 64, reinterpret_cast<int32_t *>(c->h_pinned + 9));
         VH_CHECK(hipGetLastError());
@@ -1258,8 +1286,9 @@ hipError_t launch_forces_v(sph_ctx *c, const PairConst &pc) {
 
 hipError_t launch_update_h(sph_ctx *c, const PairConst &pc) {
     if (c->n == 0) return hipSuccess;
-    update_h_kernel<<<dim3((unsigned)((c->n + VBLOCK - 1) / VBLOCK)), dim3(VBLOCK), 0, c->stream>>>(
-        c->grid, pc, reinterpret_cast<const double4 *>(c->drec), reinterpret_cast<const double4 *>(c->lrec), c->cell_start,
+    auto uh = c->hashed ? update_h_kernel<true> : update_h_kernel<false>;
+    uh<<<dim3((unsigned)((c->n + VBLOCK - 1) / VBLOCK)), dim3(VBLOCK), 0, c->stream>>>(
+        c->grid, pc, reinterpret_cast<const double4 *>(c->drec), reinterpret_cast<const double4 *>(c->lrec), c->cell_start, c->hv,
         c->w_tab, c->dw_tab, c->n, c->f[SPH_F_H], c->h_new, c->f[SPH_F_RHO], c->f[SPH_F_OMEGA], c->orig, (int32_t)c->n_owned,
         c->nlist, c->nl_cap, c->ncount, c->ntail, c->list_has_margin ? 1 : 0);
     hipError_t e = hipGetLastError();

@@ -18,6 +18,8 @@ module sph_hip_binding
   public :: SPH_F_H, SPH_F_OMEGA
   public :: SPH_FLAG_REUSE_DENSITY, SPH_FLAG_VARIABLE_H, SPH_FLAG_SELF_GRAVITY, SPH_FLAG_ACCRETE_CULL
   public :: SPH_FLAG_SINK_CREATION, sph_sink_count, sph_get_sink_radii
+  ! cell grid: the hashed table (far-apart particle groups) and what the last build used
+  public :: SPH_FLAG_HASHED_GRID, sph_grid_info, sph_get_grid_info
   ! multi-GPU building blocks (device pointers as type(c_ptr), e.g. from hipMalloc or an MPI library's GPU buffers)
   public :: sph_set_owned, sph_set_rank, sph_reserve, sph_owned_bbox, sph_select_boxes, sph_selected_ids_dev
   public :: sph_select_boxes_async, sph_selected_counts, sph_gather_selected_dev
@@ -38,6 +40,7 @@ module sph_hip_binding
   integer(c_int), parameter :: SPH_F_H = 17, SPH_F_OMEGA = 18
   integer(c_int32_t), parameter :: SPH_FLAG_REUSE_DENSITY = 1, SPH_FLAG_VARIABLE_H = 2, SPH_FLAG_SELF_GRAVITY = 16
   integer(c_int32_t), parameter :: SPH_FLAG_ACCRETE_CULL = 32, SPH_FLAG_SINK_CREATION = 64
+  integer(c_int32_t), parameter :: SPH_FLAG_HASHED_GRID = 1024
   integer(c_int32_t), parameter :: SPH_PARTIALS = 199
   integer(c_int32_t), parameter :: SPH_RENDER_AUTO_BOUNDS = 1, SPH_RENDER_SPACING = 2
 
@@ -48,6 +51,14 @@ module sph_hip_binding
     real(c_double) :: eta, h_tol, h_max_length, h_min_length, h_iter_cap     ! variable-h path only
     real(c_double) :: theta                                                   ! self-gravity opening angle
   end type sph_params
+
+  type, bind(C) :: sph_grid_info
+    integer(c_int32_t) :: kind              ! 0 dense, 1 hashed, -1 no grid built yet
+    integer(c_int32_t) :: dim(3)
+    integer(c_int64_t) :: occupied_cells, table_entries
+    real(c_double) :: index_cells
+    integer(c_int64_t) :: bytes
+  end type sph_grid_info
 
   type, bind(C) :: sph_stats
     integer(c_int64_t) :: n, n_cells
@@ -254,6 +265,13 @@ module sph_hip_binding
       import :: c_int, c_ptr, sph_stats
       type(c_ptr), value :: ctx
       type(sph_stats), intent(out) :: st
+    end function
+
+    ! the cell grid of the last build (dense or hashed); reads the occupied-cell count back
+    integer(c_int) function sph_get_grid_info(ctx, gi) bind(C, name='sph_get_grid_info')
+      import :: c_int, c_ptr, sph_grid_info
+      type(c_ptr), value :: ctx
+      type(sph_grid_info), intent(out) :: gi
     end function
 
     ! bounding box of the current positions: what check_bounds (:471-482) needs
