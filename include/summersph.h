@@ -394,6 +394,45 @@ typedef struct sph_render_desc {
 int sph_render_density(sph_ctx *ctx, sph_render_desc *d, double *host_out, int64_t out_len);
 int sph_render_density_dev(sph_ctx *ctx, sph_render_desc *d, double *d_out, int64_t out_len);
 
+/* ---- field rendering: any per-particle quantity A on the density render's nodes (temperature, moment-1 velocity,
+ *      alpha maps ...) -----------------------------------------------------------------------------------------------
+ * The same selection, nodes, kernel, h rule and summation order as sph_render_density (base: exactly its descriptor,
+ * auto bounds written back).  With s_j = 1 / (pi h_j^3) as there, for a node g:
+ *   ws_j = m_j s_j            SPH_RENDER_WEIGHT_MASS   (bitwise the density render's term weight)
+ *        = (m_j / rho_j) s_j  SPH_RENDER_WEIGHT_VOLUME (rho_j: the context's SPH_F_RHO)
+ *   wa_j = ws_j A_j,   num(g) = sum_j wa_j Wn(q),   den(g) = sum_j ws_j Wn(q)   (Wn = W / s_j, the same skip test)
+ *   output      normalise 0: num (3-D) or col_num * scale (projection; scale = the node spacing with SPH_RENDER_SPACING,
+ *               else 1) -- MASS: sum m A W (e.g. momentum density); VOLUME: the SPH interpolant sum (m / rho) A W.
+ *               normalise 1: num / den (3-D) or col_num / col_den (projection, no scale), exactly 0.0 where the
+ *               denominator is 0.0 -- MASS + projection: the density-weighted line-of-sight mean (a temperature or
+ *               moment-1 map); VOLUME: the Shepard-normalised interpolant.
+ *               Column sums add the node values in increasing index, as the density render does.
+ *   weight      optional (NULL = none): den (3-D) or col_den * scale.  Summing images and weights of separate contexts
+ *               or ranks and dividing gives the normalised image of the union.
+ *   field       an SPH_F_* id, read from the context (SPH_ERR_STATE where sph_download_field would refuse it as stale),
+ *               or SPH_RENDER_FIELD_VALUES with values: sph_count(ctx) doubles in sph_download_field's order (upload
+ *               order; after a cull, the survivors' order) -- host memory for sph_render_field, device memory for _dev.
+ *               Only the selected (owned) particles' entries are read.
+ *   VOLUME reads the rho that sph_download_field(SPH_F_RHO) would return: SPH_ERR_STATE exactly when that call would be.
+ *   cost        as sph_render_density (two read-backs + the output copies), plus the copy of values in the host form; no
+ *               state, statistic (other than device_bytes) or flag of the context changes.
+ * SPH_ERR_ARG: everything sph_render_density rejects, a field id out of range, values NULL with SPH_RENDER_FIELD_VALUES
+ * or non-NULL with a field id, weight not MASS / VOLUME, normalise not 0 / 1, reserved != 0. */
+#define SPH_RENDER_FIELD_VALUES (-1)
+#define SPH_RENDER_WEIGHT_MASS 0
+#define SPH_RENDER_WEIGHT_VOLUME 1
+typedef struct sph_render_field_desc {
+    sph_render_desc base;           /* as for sph_render_density; base.reserved must be 0            */
+    int32_t field;                  /* SPH_F_* or SPH_RENDER_FIELD_VALUES                            */
+    int32_t weight;                 /* SPH_RENDER_WEIGHT_MASS / SPH_RENDER_WEIGHT_VOLUME             */
+    int32_t normalise;              /* 0: num; 1: num / den                                          */
+    int32_t reserved;               /* must be 0                                                     */
+} sph_render_field_desc;            /* 144 bytes */
+int sph_render_field(sph_ctx *ctx, sph_render_field_desc *d, const double *values, double *host_out, double *host_weight,
+                     int64_t out_len);
+int sph_render_field_dev(sph_ctx *ctx, sph_render_field_desc *d, const double *d_values, double *d_out, double *d_weight,
+                         int64_t out_len);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too

@@ -42,10 +42,13 @@ SYMBOLS = [
     "sph_set_dt", "sph_get_dt", "sph_kick_devdt", "sph_drift_devdt", "sph_dt_candidate_dev", "sph_kick_drift_devdt", "sph_kick_dt_candidate_dev", "sph_kick_dt_candidate_gas_dev", "sph_kick_sinks_devdt", "sph_pack_partials_dev", "sph_pack_partials_ex_dev",
     "sph_apply_partials_dev", "sph_set_boundary_boxes", "sph_forces_part", "sph_set_gravity_sources_dev", "sph_accrete_mark_dev", "sph_accrete_apply_dev", "sph_set_numbers_dev",
     "sph_get_stats", "sph_get_grid_info", "sph_get_bbox", "sph_timing_enable", "sph_timing_stride", "sph_timing_reset", "sph_timing_get", "sph_synchronize", "sph_stream",
-    "sph_render_density", "sph_render_density_dev",
+    "sph_render_density", "sph_render_density_dev", "sph_render_field", "sph_render_field_dev",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
+RENDER_FIELD_VALUES = -1
+RENDER_WEIGHT_MASS = 0
+RENDER_WEIGHT_VOLUME = 1
 
 
 class Params(C.Structure):
@@ -77,6 +80,13 @@ class RenderDesc(C.Structure):
     """sph_render_desc (include/summersph.h): node box, strict clip box, h, nodes per axis, output axis, flags"""
     _fields_ = [("lo", C.c_double * 3), ("hi", C.c_double * 3), ("clip_lo", C.c_double * 3), ("clip_hi", C.c_double * 3),
                 ("h", C.c_double), ("n", C.c_int32 * 3), ("axis", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RenderFieldDesc(C.Structure):
+    """sph_render_field_desc (include/summersph.h): the density render's descriptor, field id (or RENDER_FIELD_VALUES),
+    weight (RENDER_WEIGHT_MASS / _VOLUME), normalise (0 / 1), reserved"""
+    _fields_ = [("base", RenderDesc), ("field", C.c_int32), ("weight", C.c_int32), ("normalise", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class SphError(RuntimeError):
@@ -177,6 +187,8 @@ def load():
     lib.sph_timing_get.argtypes = [C.c_void_p, C.c_int, _D, C.POINTER(C.c_int64)]
     lib.sph_render_density.argtypes = [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p, C.c_int64]
     lib.sph_render_density_dev.argtypes = [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p, C.c_int64]
+    lib.sph_render_field.argtypes = [C.c_void_p, C.POINTER(RenderFieldDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sph_render_field_dev.argtypes = [C.c_void_p, C.POINTER(RenderFieldDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     _lib = lib
     return lib
 
@@ -516,6 +528,71 @@ class Context:
             self._ck(self.lib.sph_render_density(self._h, C.byref(d), out.ctypes.data, size))
         self.render_bounds = (np.array(d.lo[:]), np.array(d.hi[:]))
         return out
+
+    def render_field_desc(self, field, shape, bounds=None, axis=None, h=None, clip=None, spacing=False, weight="mass",
+                          normalise=False) -> RenderFieldDesc:
+        """The descriptor of render_field's arguments (field: an SPH_F_* name or id, or RENDER_FIELD_VALUES)."""
+        d = RenderFieldDesc()
+        d.base = self.render_desc(shape, bounds, axis, h, clip, spacing)
+        d.field = FIELDS.index(field) if isinstance(field, str) else int(field)
+        d.weight = {"mass": RENDER_WEIGHT_MASS, "volume": RENDER_WEIGHT_VOLUME}[weight] if isinstance(weight, str) else int(weight)
+        d.normalise = int(normalise)
+        return d
+
+    def render_field(self, field, shape, bounds=None, axis=None, h=None, clip=None, spacing=False, weight="mass",
+                     normalise=False, weight_out=False, device=False):
+        """Any per-particle quantity A on render_density's nodes (include/summersph.h, sph_render_field): with
+        ws = w_j / (pi h_j^3), w_j = m_j (weight='mass') or m_j / rho_j ('volume'), num = sum ws A Wn and den = sum ws Wn.
+        Returns num (column sums times the spacing with spacing=True) or, normalise=True, num / den (0 where den is 0); with
+        weight_out=True, (image, den) (the column den times the spacing).  field: an SPH_F_* name ('u', 'vz', 'rho', ...)
+        read from the context, or sph_count() values in the upload order -- a float64 numpy array (host form, device must
+        be False) or a contiguous float64 torch tensor on the context's GPU (device form, device must be True).  The
+        other arguments and self.render_bounds are render_density's."""
+        values = None
+        if isinstance(field, str):
+            fid = field
+        else:
+            fid = RENDER_FIELD_VALUES
+            values = field
+            if isinstance(values, np.ndarray):
+                if device:
+                    raise ValueError("render_field: a numpy values array renders with device=False")
+                values = np.ascontiguousarray(values, dtype=np.float64)
+                n = values.size
+            else:
+                import torch
+                if not (isinstance(values, torch.Tensor) and values.dtype == torch.float64 and values.is_contiguous()
+                        and values.device == torch.device("cuda", self.device)):
+                    raise ValueError("render_field: values must be float64 numpy or a contiguous float64 tensor on the context's GPU")
+                if not device:
+                    raise ValueError("render_field: a device values tensor renders with device=True")
+                n = values.numel()
+            if n != self.n:
+                raise ValueError(f"render_field: {n} values for {self.n} particles")
+        d = self.render_field_desc(fid, shape, bounds, axis, h, clip, spacing, weight, normalise)
+        oshape = self.render_shape(d.base)
+        size = int(np.prod(oshape, dtype=np.int64))
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            out = torch.empty(oshape, dtype=torch.float64, device=dev)
+            wout = torch.empty(oshape, dtype=torch.float64, device=dev) if weight_out else None
+            torch.cuda.current_stream(dev).synchronize()          # the blocks and values may still be in use by torch's work
+            self._ck(self.lib.sph_render_field_dev(self._h, C.byref(d), None if values is None else C.c_void_p(values.data_ptr()),
+                                                   C.c_void_p(out.data_ptr()), None if wout is None else C.c_void_p(wout.data_ptr()),
+                                                   size))
+            st = self.stream()                                    # torch's later work on the outputs waits for the render
+            if st:
+                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
+            else:
+                torch.cuda.synchronize(dev)
+        else:
+            out = np.empty(oshape, dtype=np.float64)
+            wout = np.empty(oshape, dtype=np.float64) if weight_out else None
+            self._ck(self.lib.sph_render_field(self._h, C.byref(d), None if values is None else values.ctypes.data,
+                                               out.ctypes.data, None if wout is None else wout.ctypes.data, size))
+        self.render_bounds = (np.array(d.base.lo[:]), np.array(d.base.hi[:]))
+        return (out, wout) if weight_out else out
 
     # ---- diagnostics ---------------------------------------------------------------------
     def stats(self) -> Stats:

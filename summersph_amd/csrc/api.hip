@@ -1223,6 +1223,20 @@ int sph_render_density_dev(sph_ctx *c, sph_render_desc *d, double *d_out, int64_
     return render_density(c, d, d_out, out_len, false);
 }
 
+int sph_render_field(sph_ctx *c, sph_render_field_desc *d, const double *values, double *host_out, double *host_weight,
+                     int64_t out_len) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return render_field(c, d, values, host_out, host_weight, out_len, true, field_ready);
+}
+
+int sph_render_field_dev(sph_ctx *c, sph_render_field_desc *d, const double *d_values, double *d_out, double *d_weight,
+                         int64_t out_len) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return render_field(c, d, d_values, d_out, d_weight, out_len, false, field_ready);
+}
+
 int sph_synchronize(sph_ctx *c) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);

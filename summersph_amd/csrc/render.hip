@@ -10,11 +10,14 @@
 //                                and slot, compacted with an atomic cursor                            (read-back 2)
 //   rocprim radix sort           (cell, particle id): the order every node adds its terms in
 //   render_cells / render_records  cell table; SoA records {x, y, z, m sigma_j, 1/h_j} in sorted order
+//   render_field_records         (sph_render_field) SoA records {x, y, z, w_j sigma_j, w_j sigma_j A_j, 1/h_j} in sorted order
 //   render_gather<W>             one workgroup per tile of 8 x 8 node columns; lanes walk axis W in segments of KW nodes.
 //                                The records of the cells that overlap a segment's brick (+ the reach) are staged into LDS
 //                                in chunks, in increasing (cell, id) order, and every lane adds its KW nodes' terms in that
 //                                staged order.  3-D mode stores the node values; projected mode adds them, node by node
 //                                in increasing index, into the column sum and never materialises the grid.
+//   field_gather<W, DEN>         (sph_render_field) the same walk and staging with a sixth plane: num += w sigma A Wn and,
+//                                with DEN, den += w sigma Wn per accepted pair; the epilogue divides / scales.
 // A node's value is therefore the sum of its contributing terms in the global (cell, id) order of a binning that depends
 // only on the node box, n, h and the clip: independent of the context's sorted order, of the launch geometry and of the
 // output mode (terms of particles beyond 2h are skipped or are exact +0.0, which changes no sum).
@@ -42,7 +45,8 @@ constexpr int NSTAT = 9;           // min xyz, max xyz, max h, max(-h), count
 constexpr int TU = RENDER_TILE, TV = RENDER_TILE;   // node columns per workgroup (v fastest)
 constexpr int GT = TU * TV;        // threads per gather workgroup
 constexpr int KW = 8;              // nodes per lane along the walk axis per segment
-constexpr int CH = 4 * GT;         // records per LDS chunk (5 planes of doubles: 10 KB for 8 x 8 columns)
+constexpr int CH = 4 * GT;         // records per LDS chunk (5 planes of doubles: 10 KB for 8 x 8 columns; the field
+                                   // render's 6 planes: 12 KB)
 constexpr int64_t MAX_CELLS = (int64_t)1 << 26;
 
 struct Sel {
@@ -68,6 +72,7 @@ struct Nodes {
 struct Recs {
     const double *x, *y, *z, *ms, *ih;
     const int32_t *cell_start;
+    const double *wa;              // the field render's w sigma A plane (unused by the density render)
 };
 
 __device__ __forceinline__ bool selected(const Sel &s, int64_t i, double px, double py, double pz) {
@@ -193,6 +198,30 @@ __global__ __launch_bounds__(256) void render_records(const double *__restrict__
     rec[4 * stride + i] = 1.0 / h;
 }
 
+// the field render's records in sorted order: x, y, z, ws = w_j sigma_j, wa = ws A_j, 1 / h_j with w_j = m_j (rho null) or
+// m_j / rho_j, A_j = a[j] (a field plane in slot order) or values[orig[j]] (the caller's order).  ws of the mass weight is
+// bitwise render_records' m sigma_j.
+__global__ __launch_bounds__(256) void render_field_records(const double *__restrict__ x, const double *__restrict__ y,
+                                                            const double *__restrict__ z, const double *__restrict__ m,
+                                                            const double *__restrict__ rho, const double *__restrict__ a,
+                                                            const double *__restrict__ values, Sel s,
+                                                            const uint32_t *__restrict__ vals, int64_t n,
+                                                            double *__restrict__ rec, int64_t stride) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t j = vals[i];
+    const double h = s.h > 0.0 ? s.h : s.hf[j];
+    const double sigma = 1.0 / (M_PI * (h * h * h));
+    const double ws = (rho ? m[j] / rho[j] : m[j]) * sigma;
+    const double av = values ? values[s.orig[j]] : a[j];
+    rec[i] = x[j];
+    rec[stride + i] = y[j];
+    rec[2 * stride + i] = z[j];
+    rec[3 * stride + i] = ws;
+    rec[4 * stride + i] = ws * av;
+    rec[5 * stride + i] = 1.0 / h;
+}
+
 // m sigma W(|g - p|, h) with W/sigma = 1 - 1.5 q^2 + 0.75 q^3 (q <= 1), 0.25 (2 - q)^3 (1 < q <= 2), 0 beyond.
 // The squared distance is summed in x, y, z order in every instantiation.
 __device__ __forceinline__ double kernel_w(double q) {
@@ -211,15 +240,20 @@ struct GatherArgs {
     int32_t project;   // 1: column sums along W
     int32_t tiles_v;   // tiles along V
     int32_t nseg;      // segments of KW nodes along W
+    int32_t normalise; // field render: num / den (0 where den == 0), unscaled
     double *out;
+    double *wout;      // field render: den (3-D) or the column den times scale; null = none
 };
 
 // W: walk axis; U < V the two others (V fastest in both outputs).  3-D mode runs W = 0: lanes then span the two fastest
 // output axes and the stores of a segment are rows of TV consecutive doubles.
-template <int W>
-__global__ __launch_bounds__(GT) void render_gather(GatherArgs A) {
+// FIELD: the field render (a sixth record plane wa; num += wa Wn), DEN: it also accumulates den += ws Wn.  Without FIELD
+// this is the density render: acc += ms W.
+template <int W, bool FIELD, bool DEN>
+__device__ __forceinline__ void gather_body(const GatherArgs &A) {
     constexpr int U = W == 0 ? 1 : 0, V = W == 2 ? 1 : 2;
     __shared__ double sx[CH], sy[CH], sz[CH], sms[CH], sih[CH];
+    __shared__ double swa[FIELD ? CH : 1];
     __shared__ int32_t s_start[GT], s_off[GT];
     __shared__ int32_t s_wsum[GT / WAVE];
 
@@ -232,13 +266,17 @@ __global__ __launch_bounds__(GT) void render_gather(GatherArgs A) {
     const int u0 = tu * TU, u1 = min(nd.n[U], u0 + TU) - 1;
     const int v0 = tv * TV, v1 = min(nd.n[V], v0 + TV) - 1;
     const int d1 = A.g.dim[1], d2 = A.g.dim[2];
-    double col = 0.0;
+    double col = 0.0, cold = 0.0;
 
     for (int seg = blockIdx.y; seg < A.nseg; seg += gridDim.y) {
         const int w0 = seg * KW, w1 = min(nd.n[W], w0 + KW) - 1;
-        double cw[KW], acc[KW];
+        double cw[KW], acc[KW], accd[DEN ? KW : 1];
 #pragma unroll
         for (int k = 0; k < KW; k++) { cw[k] = node_coord(nd, W, min(w0 + k, w1)); acc[k] = 0.0; }
+        if constexpr (DEN) {
+#pragma unroll
+            for (int k = 0; k < KW; k++) accd[k] = 0.0;
+        }
         // candidate cells: the brick's box widened by the reach, in x y z
         int clo[3], chi[3];
         {
@@ -285,11 +323,13 @@ __global__ __launch_bounds__(GT) void render_gather(GatherArgs A) {
                     }
                     const int64_t idx = (int64_t)s_start[lo] + (pos - s_off[lo]);
                     sx[e] = A.r.x[idx]; sy[e] = A.r.y[idx]; sz[e] = A.r.z[idx]; sms[e] = A.r.ms[idx]; sih[e] = A.r.ih[idx];
+                    if constexpr (FIELD) swa[e] = A.r.wa[idx];
                 }
                 __syncthreads();
                 for (int j = 0; j < cnt; j++) {                // every lane reads the same record: LDS broadcast
                     const double p[3] = {sx[j], sy[j], sz[j]};
                     const double ms = sms[j], ih = sih[j], ih2 = ih * ih;
+                    const double wa = FIELD ? swa[j] : 0.0;
                     const double du = cu - p[U];
                     const double dv = cv - p[V];
 #pragma unroll
@@ -299,7 +339,13 @@ __global__ __launch_bounds__(GT) void render_gather(GatherArgs A) {
                         const double r2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
                         if (r2 * ih2 <= 4.0000001) {           // beyond it q > 2: the term is +0.0, skipped
                             const double q = sqrt(r2) * ih;
-                            acc[k] += ms * kernel_w(q);
+                            if constexpr (FIELD) {
+                                const double wn = kernel_w(q);
+                                acc[k] += wa * wn;
+                                if constexpr (DEN) accd[k] += ms * wn;
+                            } else {
+                                acc[k] += ms * kernel_w(q);
+                            }
                         }
                     }
                 }
@@ -309,19 +355,43 @@ __global__ __launch_bounds__(GT) void render_gather(GatherArgs A) {
         if (A.project) {
 #pragma unroll
             for (int k = 0; k < KW; k++)
-                if (w0 + k <= w1) col += acc[k];               // node by node, increasing index: the sequential sum
+                if (w0 + k <= w1) {
+                    col += acc[k];                             // node by node, increasing index: the sequential sum
+                    if constexpr (DEN) cold += accd[k];
+                }
         } else if (valid) {
 #pragma unroll
             for (int k = 0; k < KW; k++) {
                 if (w0 + k > w1) break;
                 int64_t i3[3];
                 i3[W] = w0 + k; i3[U] = iu; i3[V] = iv;
-                A.out[(i3[0] * nd.n[1] + i3[1]) * nd.n[2] + i3[2]] = acc[k];
+                const int64_t o = (i3[0] * nd.n[1] + i3[1]) * nd.n[2] + i3[2];
+                if constexpr (DEN) {
+                    A.out[o] = A.normalise ? (accd[k] != 0.0 ? acc[k] / accd[k] : 0.0) : acc[k];
+                    if (A.wout) A.wout[o] = accd[k];
+                } else {
+                    A.out[o] = acc[k];
+                }
             }
         }
     }
-    if (A.project && valid) A.out[(int64_t)iu * nd.n[V] + iv] = col * A.scale;
+    if (A.project && valid) {
+        const int64_t o = (int64_t)iu * nd.n[V] + iv;
+        if constexpr (DEN) {
+            A.out[o] = A.normalise ? (cold != 0.0 ? col / cold : 0.0) : col * A.scale;
+            if (A.wout) A.wout[o] = cold * A.scale;
+        } else {
+            A.out[o] = col * A.scale;
+        }
+    }
 }
+
+template <int W>
+__global__ __launch_bounds__(GT) void render_gather(GatherArgs A) { gather_body<W, false, false>(A); }
+
+// the field render's gather (sph_render_field): its name must not contain the density gather's
+template <int W, bool DEN>
+__global__ __launch_bounds__(GT) void field_gather(GatherArgs A) { gather_body<W, true, DEN>(A); }
 
 #define RD_HIP(expr)                                                        \
     do {                                                                    \
@@ -338,8 +408,8 @@ __global__ __launch_bounds__(GT) void render_gather(GatherArgs A) {
         if (_s != SPH_OK) return _s;   \
     } while (0)
 
-int rd_arg(sph_ctx *c, const char *what) {
-    c->err = std::string("sph_render_density: ") + what;
+int rd_arg(sph_ctx *c, const char *what, const char *who = "sph_render_density") {
+    c->err = std::string(who) + ": " + what;
     return SPH_ERR_ARG;
 }
 
@@ -364,36 +434,51 @@ hipError_t launch_gather(const GatherArgs &a, int tiles, int ysegs, hipStream_t 
     return hipGetLastError();
 }
 
-}  // namespace
-
-void render_free(sph_ctx *c) {
-    ctx_free_ptr(c, c->rnd_buf); c->rnd_buf = nullptr; c->rnd_bytes = 0;
-    ctx_free(c, c->rnd_small);
-    if (c->rnd_pinned) (void)hipHostFree(c->rnd_pinned);
-    c->rnd_pinned = nullptr;
+template <int W>
+hipError_t launch_field_gather(const GatherArgs &a, bool den, int tiles, int ysegs, hipStream_t st) {
+    if (den) field_gather<W, true><<<dim3((unsigned)tiles, (unsigned)ysegs), dim3(GT), 0, st>>>(a);
+    else field_gather<W, false><<<dim3((unsigned)tiles, (unsigned)ysegs), dim3(GT), 0, st>>>(a);
+    return hipGetLastError();
 }
 
-int render_density(sph_ctx *c, sph_render_desc *d, double *out, int64_t out_len, bool host_out) {
-    if (!d || !out) return rd_arg(c, "null descriptor or output");
-    if (d->reserved != 0) return rd_arg(c, "reserved must be 0");
-    if (d->flags & ~(SPH_RENDER_AUTO_BOUNDS | SPH_RENDER_SPACING)) return rd_arg(c, "unknown flags");
+// what sph_render_field adds to the density render's pipeline
+struct FieldSpec {
+    const double *a;           // the field's plane (slot order), or null
+    const double *values;      // the caller's values (original order; host memory when host_values), or null
+    bool host_values;
+    const double *rho;         // VOLUME weight: the rho plane; null = MASS
+    bool normalise;
+    double *wout;              // weight output (host or device, as the image), or null
+    bool stale;                // the field or rho would be refused by sph_download_field
+};
+
+// the density render (fs null) and the field render: shared selection, binning, sort and cells; records and gather differ
+int render_impl(sph_ctx *c, sph_render_desc *d, const FieldSpec *fs, double *out, int64_t out_len, bool host_out) {
+    const char *who = fs ? "sph_render_field" : "sph_render_density";
+    if (!d || !out) return rd_arg(c, "null descriptor or output", who);
+    if (d->reserved != 0) return rd_arg(c, "reserved must be 0", who);
+    if (d->flags & ~(SPH_RENDER_AUTO_BOUNDS | SPH_RENDER_SPACING)) return rd_arg(c, "unknown flags", who);
     const bool autob = (d->flags & SPH_RENDER_AUTO_BOUNDS) != 0, spacing = (d->flags & SPH_RENDER_SPACING) != 0;
     int64_t total = 1;
     for (int a = 0; a < 3; a++) {
-        if (d->n[a] < 1) return rd_arg(c, "n must be >= 1 on every axis");
+        if (d->n[a] < 1) return rd_arg(c, "n must be >= 1 on every axis", who);
         total *= d->n[a];
-        if (total > ((int64_t)1 << 40)) return rd_arg(c, "too many nodes");
+        if (total > ((int64_t)1 << 40)) return rd_arg(c, "too many nodes", who);
     }
-    if (d->axis < -1 || d->axis > 2) return rd_arg(c, "axis must be -1, 0, 1 or 2");
-    if (spacing && (d->axis < 0 || d->n[d->axis] == 1)) return rd_arg(c, "SPH_RENDER_SPACING needs a projection axis with n > 1");
-    if (!(d->h >= 0.0) || !std::isfinite(d->h)) return rd_arg(c, "h must be finite and >= 0");
+    if (d->axis < -1 || d->axis > 2) return rd_arg(c, "axis must be -1, 0, 1 or 2", who);
+    if (spacing && (d->axis < 0 || d->n[d->axis] == 1)) return rd_arg(c, "SPH_RENDER_SPACING needs a projection axis with n > 1", who);
+    if (!(d->h >= 0.0) || !std::isfinite(d->h)) return rd_arg(c, "h must be finite and >= 0", who);
     const int64_t want = d->axis < 0 ? total : total / d->n[d->axis];
-    if (out_len != want) return rd_arg(c, "out_len does not match the node counts");
+    if (out_len != want) return rd_arg(c, "out_len does not match the node counts", who);
     if (!autob)
         for (int a = 0; a < 3; a++)
-            if (!(d->lo[a] <= d->hi[a]) || !std::isfinite(d->lo[a]) || !std::isfinite(d->hi[a])) return rd_arg(c, "lo > hi");
+            if (!(d->lo[a] <= d->hi[a]) || !std::isfinite(d->lo[a]) || !std::isfinite(d->hi[a])) return rd_arg(c, "lo > hi", who);
     for (int a = 0; a < 3; a++)
-        if (std::isnan(d->clip_lo[a]) || std::isnan(d->clip_hi[a])) return rd_arg(c, "NaN clip box");
+        if (std::isnan(d->clip_lo[a]) || std::isnan(d->clip_hi[a])) return rd_arg(c, "NaN clip box", who);
+    if (fs && fs->stale) {
+        c->err = "sph_render_field: the field or rho is stale (sph_download_field would refuse it)";
+        return SPH_ERR_STATE;
+    }
 
     hipStream_t st = c->stream;
     Sel s{};
@@ -421,10 +506,10 @@ int render_density(sph_ctx *c, sph_render_desc *d, double *out, int64_t out_len,
         for (int k = 0; k < NSTAT; k++) hs[k] = c->rnd_pinned[k];
     }
     const int64_t count = (int64_t)hs[8];
-    if (count == 0 && autob) return rd_arg(c, "SPH_RENDER_AUTO_BOUNDS over an empty selection");
+    if (count == 0 && autob) return rd_arg(c, "SPH_RENDER_AUTO_BOUNDS over an empty selection", who);
     const double h_max = hs[6], h_min = -hs[7];
     if (count > 0 && !(h_min > 0.0 && std::isfinite(h_max))) {
-        c->err = "sph_render_density: a selected particle has h <= 0 or a non-finite h";
+        c->err = std::string(who) + ": a selected particle has h <= 0 or a non-finite h";
         return SPH_ERR_STATE;
     }
     Nodes nd{};
@@ -461,10 +546,13 @@ int render_density(sph_ctx *c, sph_render_desc *d, double *out, int64_t out_len,
     size_t sort_bytes = 0;
     RD_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
                                      (uint32_t *)nullptr, (size_t)cap, 0u, 64u, st));
-    size_t off[8], bytes = 0;
-    const size_t sizes[8] = {8 * (size_t)cap, 8 * (size_t)cap, 4 * (size_t)cap, 4 * (size_t)cap, sort_bytes,
-                             4 * (size_t)(ncells + 2), 40 * (size_t)cap, host_out ? 8 * (size_t)out_len : 0};
-    for (int k = 0; k < 8; k++) { off[k] = bytes; bytes += align_up(sizes[k]); }
+    const int nplanes = fs ? 6 : 5;
+    const bool host_w = fs && fs->wout && host_out, host_v = fs && fs->values && fs->host_values;
+    size_t off[10], bytes = 0;
+    const size_t sizes[10] = {8 * (size_t)cap, 8 * (size_t)cap, 4 * (size_t)cap, 4 * (size_t)cap, sort_bytes,
+                              4 * (size_t)(ncells + 2), 8 * (size_t)nplanes * (size_t)cap, host_out ? 8 * (size_t)out_len : 0,
+                              host_w ? 8 * (size_t)out_len : 0, host_v ? 8 * (size_t)std::max<int64_t>(c->n, 0) : 0};
+    for (int k = 0; k < 10; k++) { off[k] = bytes; bytes += align_up(sizes[k]); }
     char *buf = nullptr;
     RD_TRY(scratch(c, bytes, &buf));
     uint64_t *keys = reinterpret_cast<uint64_t *>(buf + off[0]), *keys_alt = reinterpret_cast<uint64_t *>(buf + off[1]);
@@ -473,6 +561,9 @@ int render_density(sph_ctx *c, sph_render_desc *d, double *out, int64_t out_len,
     int32_t *cell_start = reinterpret_cast<int32_t *>(buf + off[5]);
     double *rec = reinterpret_cast<double *>(buf + off[6]);
     double *d_out = host_out ? reinterpret_cast<double *>(buf + off[7]) : out;
+    double *d_wout = host_w ? reinterpret_cast<double *>(buf + off[8]) : (fs ? fs->wout : nullptr);
+    double *values_copy = reinterpret_cast<double *>(buf + off[9]);     // the host form's values, on the device
+    const double *d_values = host_v ? values_copy : (fs ? fs->values : nullptr);
 
     // ---- read-back 2: the particles that can reach a node -----------------------------------------------------------
     int64_t nsel = 0;
@@ -488,37 +579,90 @@ int render_density(sph_ctx *c, sph_render_desc *d, double *out, int64_t out_len,
 
     if (nsel == 0) {
         RD_HIP(hipMemsetAsync(d_out, 0, (size_t)out_len * sizeof(double), st));
+        if (d_wout) RD_HIP(hipMemsetAsync(d_wout, 0, (size_t)out_len * sizeof(double), st));
     } else {
         unsigned cbits = 1;
         while (cbits < 32 && ((int64_t)1 << cbits) < ncells) cbits++;
         size_t tmp = sort_bytes;
         RD_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)nsel, 0u, 32u + cbits, st));
         render_cells<<<dim3((unsigned)((ncells + 1 + 255) / 256)), dim3(256), 0, st>>>(keys_alt, nsel, ncells, cell_start);
-        render_records<<<dim3((unsigned)((nsel + 255) / 256)), dim3(256), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z],
-                                                                                   c->f[SPH_F_M], s, vals_alt, nsel, rec, cap);
+        if (!fs) {
+            render_records<<<dim3((unsigned)((nsel + 255) / 256)), dim3(256), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z],
+                                                                                       c->f[SPH_F_M], s, vals_alt, nsel, rec, cap);
+        } else {
+            if (host_v) RD_HIP(hipMemcpyAsync(values_copy, fs->values, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, st));
+            render_field_records<<<dim3((unsigned)((nsel + 255) / 256)), dim3(256), 0, st>>>(
+                c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], c->f[SPH_F_M], fs->rho, fs->a, d_values, s, vals_alt, nsel, rec, cap);
+        }
         RD_HIP(hipGetLastError());
         GatherArgs a{};
         a.nd = ndk; a.g = g; a.reach = reach;
-        a.r = Recs{rec, rec + cap, rec + 2 * cap, rec + 3 * cap, rec + 4 * cap, cell_start};
+        if (!fs) a.r = Recs{rec, rec + cap, rec + 2 * cap, rec + 3 * cap, rec + 4 * cap, cell_start, nullptr};
+        else a.r = Recs{rec, rec + cap, rec + 2 * cap, rec + 3 * cap, rec + 5 * cap, cell_start, rec + 4 * cap};
         a.project = d->axis >= 0;
         const int W = d->axis >= 0 ? d->axis : 0, U = W == 0 ? 1 : 0, V = W == 2 ? 1 : 2;
         a.scale = spacing ? nd.step[W] : 1.0;
         a.tiles_v = (nd.n[V] + TV - 1) / TV;
         a.nseg = (nd.n[W] + KW - 1) / KW;
         a.out = d_out;
+        a.wout = d_wout;
+        a.normalise = fs && fs->normalise;
         const int64_t tiles = (int64_t)((nd.n[U] + TU - 1) / TU) * a.tiles_v;
         if (tiles > 0x7fffffff) return rd_arg(c, "too many node columns");
         const int ysegs = a.project ? 1 : std::min(a.nseg, 65535);
-        RD_HIP(W == 0 ? launch_gather<0>(a, (int)tiles, ysegs, st)
-                      : (W == 1 ? launch_gather<1>(a, (int)tiles, ysegs, st) : launch_gather<2>(a, (int)tiles, ysegs, st)));
+        if (!fs) {
+            RD_HIP(W == 0 ? launch_gather<0>(a, (int)tiles, ysegs, st)
+                          : (W == 1 ? launch_gather<1>(a, (int)tiles, ysegs, st) : launch_gather<2>(a, (int)tiles, ysegs, st)));
+        } else {
+            const bool den = fs->normalise || fs->wout;
+            RD_HIP(W == 0 ? launch_field_gather<0>(a, den, (int)tiles, ysegs, st)
+                          : (W == 1 ? launch_field_gather<1>(a, den, (int)tiles, ysegs, st)
+                                    : launch_field_gather<2>(a, den, (int)tiles, ysegs, st)));
+        }
     }
     if (host_out) {
         RD_HIP(hipMemcpyAsync(out, d_out, (size_t)out_len * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (host_w) RD_HIP(hipMemcpyAsync(fs->wout, d_wout, (size_t)out_len * sizeof(double), hipMemcpyDeviceToHost, st));
         RD_HIP(hipStreamSynchronize(st));
     }
     if (autob)
         for (int a = 0; a < 3; a++) { d->lo[a] = nd.lo[a]; d->hi[a] = nd.hi[a]; }
     return SPH_OK;
+}
+
+}  // namespace
+
+void render_free(sph_ctx *c) {
+    ctx_free_ptr(c, c->rnd_buf); c->rnd_buf = nullptr; c->rnd_bytes = 0;
+    ctx_free(c, c->rnd_small);
+    if (c->rnd_pinned) (void)hipHostFree(c->rnd_pinned);
+    c->rnd_pinned = nullptr;
+}
+
+int render_density(sph_ctx *c, sph_render_desc *d, double *out, int64_t out_len, bool host_out) {
+    return render_impl(c, d, nullptr, out, out_len, host_out);
+}
+
+int render_field(sph_ctx *c, sph_render_field_desc *d, const double *values, double *out, double *wout, int64_t out_len,
+                 bool host, bool (*ready)(const sph_ctx *, int)) {
+    const char *who = "sph_render_field";
+    if (!d) return rd_arg(c, "null descriptor", who);
+    if (d->reserved != 0) return rd_arg(c, "reserved must be 0", who);
+    if (d->field < SPH_RENDER_FIELD_VALUES || d->field >= SPH_F_COUNT) return rd_arg(c, "field id out of range", who);
+    if ((d->field == SPH_RENDER_FIELD_VALUES) != (values != nullptr))
+        return rd_arg(c, "values must be given with SPH_RENDER_FIELD_VALUES and only then", who);
+    if (d->weight != SPH_RENDER_WEIGHT_MASS && d->weight != SPH_RENDER_WEIGHT_VOLUME) return rd_arg(c, "unknown weight", who);
+    if (d->normalise != 0 && d->normalise != 1) return rd_arg(c, "normalise must be 0 or 1", who);
+    const bool volume = d->weight == SPH_RENDER_WEIGHT_VOLUME;
+    FieldSpec fs{};
+    fs.a = d->field >= 0 ? c->f[d->field] : nullptr;
+    fs.values = values;
+    fs.host_values = host;
+    fs.rho = volume ? c->f[SPH_F_RHO] : nullptr;
+    fs.normalise = d->normalise != 0;
+    fs.wout = wout;
+    fs.stale = (d->field >= 0 && !ready(c, d->field)) || (volume && !ready(c, SPH_F_RHO));
+    return render_impl(c, &d->base, &fs, out, out_len, host);
 }
 
 }  // namespace sph

@@ -334,6 +334,9 @@ hipError_t launch_update_h(sph_ctx *c, const PairConst &pc);   // leaves the loc
 PairConst make_pair_const(const sph_ctx *c);
 // density rendering (render.hip): out is host memory (host_out) or device memory; two read-backs (+ the host copy)
 int render_density(sph_ctx *c, sph_render_desc *d, double *out, int64_t out_len, bool host_out);
+// field rendering (render.hip): host (values, out and wout host memory) or device form; ready = sph_download_field's rule
+int render_field(sph_ctx *c, sph_render_field_desc *d, const double *values, double *out, double *wout, int64_t out_len,
+                 bool host, bool (*ready)(const sph_ctx *, int));
 void render_free(sph_ctx *c);
 
 }  // namespace sph

@@ -30,6 +30,9 @@ module sph_hip_binding
   public :: SPH_PARTIALS
   ! density rendering (Density_Image.py's grid loop and projection)
   public :: sph_render_desc, sph_render_density, sph_render_density_dev, SPH_RENDER_AUTO_BOUNDS, SPH_RENDER_SPACING
+  ! field rendering (any per-particle quantity: temperature, moment-1 velocity, alpha maps ...)
+  public :: sph_render_field_desc, sph_render_field, sph_render_field_dev
+  public :: SPH_RENDER_FIELD_VALUES, SPH_RENDER_WEIGHT_MASS, SPH_RENDER_WEIGHT_VOLUME
   public :: c_message
 
   integer(c_int), parameter :: SPH_OK = 0
@@ -43,6 +46,7 @@ module sph_hip_binding
   integer(c_int32_t), parameter :: SPH_FLAG_HASHED_GRID = 1024
   integer(c_int32_t), parameter :: SPH_PARTIALS = 199
   integer(c_int32_t), parameter :: SPH_RENDER_AUTO_BOUNDS = 1, SPH_RENDER_SPACING = 2
+  integer(c_int32_t), parameter :: SPH_RENDER_FIELD_VALUES = -1, SPH_RENDER_WEIGHT_MASS = 0, SPH_RENDER_WEIGHT_VOLUME = 1
 
   type, bind(C) :: sph_params
     real(c_double) :: h, gamma, gamma_m1
@@ -81,6 +85,13 @@ module sph_hip_binding
     integer(c_int32_t) :: n(3)
     integer(c_int32_t) :: axis, flags, reserved
   end type sph_render_desc
+
+  ! base: as for sph_render_density; field: SPH_F_* or SPH_RENDER_FIELD_VALUES; weight: SPH_RENDER_WEIGHT_MASS / _VOLUME;
+  ! normalise: 0 (num) / 1 (num / den); reserved: 0.  144 bytes.
+  type, bind(C) :: sph_render_field_desc
+    type(sph_render_desc) :: base
+    integer(c_int32_t) :: field, weight, normalise, reserved
+  end type sph_render_field_desc
 
   interface
     integer(c_int) function sph_abi_version() bind(C, name='sph_abi_version')
@@ -450,6 +461,24 @@ module sph_hip_binding
       import :: c_int, c_int64_t, c_ptr, sph_render_desc
       type(c_ptr), value :: ctx, d_out
       type(sph_render_desc), intent(inout) :: d
+      integer(c_int64_t), value :: out_len
+    end function
+
+    ! ---- field rendering: sum ws A W (and sum ws W) on the density render's nodes, ws = m sigma or (m / rho) sigma;
+    ! values (sph_count doubles in the upload order, with field = SPH_RENDER_FIELD_VALUES) and host_weight are
+    ! c_loc(...) or c_null_ptr
+    integer(c_int) function sph_render_field(ctx, d, values, host_out, host_weight, out_len) bind(C, name='sph_render_field')
+      import :: c_int, c_int64_t, c_ptr, c_double, sph_render_field_desc
+      type(c_ptr), value :: ctx, values, host_weight
+      type(sph_render_field_desc), intent(inout) :: d
+      real(c_double), intent(out) :: host_out(*)
+      integer(c_int64_t), value :: out_len
+    end function
+    integer(c_int) function sph_render_field_dev(ctx, d, d_values, d_out, d_weight, out_len) &
+        bind(C, name='sph_render_field_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_render_field_desc
+      type(c_ptr), value :: ctx, d_values, d_out, d_weight
+      type(sph_render_field_desc), intent(inout) :: d
       integer(c_int64_t), value :: out_len
     end function
   end interface
