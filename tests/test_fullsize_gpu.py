@@ -336,10 +336,17 @@ def test_disc_1e7_gravity_subset_vs_oracle_tree_and_accretion(capi):
     ga = [np.zeros(pick.size) for _ in range(3)]
     orc_grav.gravity(t, tx, ty, tz, *ga, nthreads=orc.max_threads())
     t.free()
+    mine = np.stack([(a_full[k] - a_sph[k])[pick] for k in range(3)])
     for k in range(3):
-        mine = (a_full[k] - a_sph[k])[pick]
         scale = np.max(np.abs(ga[k]))
-        assert np.max(np.abs(mine - ga[k])) <= 1e-9 * scale, k
+        assert np.max(np.abs(mine[k] - ga[k])) <= 1e-9 * scale, k
+    # and every target within 1e-7 of its own |a| (observed on the MI355X: at most 3.1e-12)
+    ga = np.stack(ga)
+    d = np.linalg.norm(mine - ga, axis=0)
+    an = np.linalg.norm(ga, axis=0)
+    worst = int(np.argmax(d / an))
+    print(f"1e7 disc: worst target {pick[worst]}: |da|/|a| = {d[worst] / an[worst]:.3g}")
+    assert np.all(d <= 1e-7 * an), (pick[worst], d[worst], an[worst])
     # accretion: the particles inside the sink's accretion geometry go, mass and momentum are conserved
     m0 = gas["m"].sum() + sinks["m"].sum()
     dt, tt = ctx.step(1e-2)
