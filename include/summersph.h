@@ -433,6 +433,81 @@ int sph_render_field(sph_ctx *ctx, sph_render_field_desc *d, const double *value
 int sph_render_field_dev(sph_ctx *ctx, sph_render_field_desc *d, const double *d_values, double *d_out, double *d_weight,
                          int64_t out_len);
 
+/* ---- disc profiles: binned, mass-weighted moments of the owned gas particles in rings (and ring sectors) about a
+ *      centre, in the frame of a disc normal (surface density, rotation, epicyclic frequency, scale height, Toomre Q,
+ *      radial drift and accretion rate, tilt, twist and eccentricity of each ring) ----------------------------------------
+ * Frame    n^ = normal / |normal|; a = x^ if |n^_x| <= 0.9 else y^; e1 = (a - (a.n^) n^) / |a - (a.n^) n^|; e2 = n^ x e1
+ *          (n^ = z^ gives the lab axes).  Centre c and velocity v_c: centre / centre_v, or sink `sink`'s position and
+ *          velocity on the device (then central_mass is that sink's mass).  Per particle, in this order, with no fused
+ *          multiply-adds (a.b = (a0 b0 + a1 b1) + a2 b2):  r' = r - c, v' = v - v_c, X = r'.e1, Y = r'.e2, z' = r'.n^,
+ *          R = sqrt(X X + Y Y), v1 = v'.e1, v2 = v'.e2, v_z = v'.n^, v_R = (X v1 + Y v2) / R, v_phi = (X v2 - Y v1) / R
+ *          (both 0 where R == 0), phi = atan2(Y, X) with +pi taken as -pi.
+ * Select   the owned gas particles (ghosts and sinks excluded, as the renders select) with r_min <= R < r_max and
+ *          |z'| < z_max (strict; INFINITY: no cut).
+ * Bins     ring edges computed once on the host: edge[k] = r_min + (k (r_max - r_min)) / n_r, or with SPH_PROFILE_LOG
+ *          r_min pow(r_max / r_min, k / n_r); edge[n_r] = r_max exactly.  Ring k: edge[k] <= R < edge[k + 1] against that
+ *          table.  Sector j: -pi + (2 pi j) / n_phi <= phi < -pi + (2 pi (j + 1)) / n_phi.  Bin b = k n_phi + j.
+ * Sums     sums[b * SPH_PROFILE_NSUM + s], s = 0..19:  N (count as a double), M = sum m, then sum m q for q =
+ *          R, z', z' z', v_R, v_phi, v_z, v_R v_R, v_phi v_phi, v_z v_z, u, alpha, h (params.h; SPH_F_H with variable h),
+ *          l_x, l_y, l_z, e_x, e_y, e_z  (each term m * q).  Lab components: l = r' x v' =
+ *          (r'y v'z - r'z v'y, r'z v'x - r'x v'z, r'x v'y - r'y v'x) and e = w / (G M_c) - r' / |r'| with w = v' x l (the
+ *          same component form), |r'| = sqrt((r'x r'x + r'y r'y) + r'z r'z), r' / |r'| = 0 where |r'| == 0, G = params.G,
+ *          M_c = central_mass; e = 0 where G M_c <= 0.  The sums are additive: those of two contexts or ranks add up to
+ *          the sums of the union.
+ * Order    the selected particles are sorted by (bin, original id); every bin's sums are reduced in a fixed shape that
+ *          depends only on that sorted sequence (pieces of 1024 sorted positions, each added by a 64-lane wavefront, then
+ *          the pieces by another): the sums are bitwise reproducible, independent of the context's sorted order, of the
+ *          dense or hashed grid and of repeated calls.  No float atomics.
+ * AUTO_NORMAL  normal = sum m (r' x v') over the owned gas in the shell r_min <= |r'| < r_max (no z cut), by the same
+ *          sorted reduction and one read-back; SPH_ERR_STATE if it is zero.  The normalised normal used is written back in
+ *          every case.
+ * Table    sph_profile_finish (pure host code: no context, no device), table[b * SPH_PROFILE_NCOL + col] with
+ *          mean(q) = (sum m q) / M and disp(q) = sqrt(v) for v = mean(q q) - mean(q)^2 >= 0, else 0:
+ *           0 R_lo = edge[k]            1 R_hi = edge[k + 1]           2 R_mean = mean(R)           3 N
+ *           4 M                         5 Sigma = M / area, area = (pi (R_hi R_hi - R_lo R_lo)) / n_phi
+ *           6 z_mean = mean(z')         7 H = disp(z')                 8 vR_mean    9 vphi_mean    10 vz_mean
+ *          11 sigma_R = disp(v_R)      12 sigma_phi = disp(v_phi)     13 sigma_z = disp(v_z)      14 u_mean
+ *          15 c_s = sqrt((gamma gamma_m1) u_mean) (params; the reference's EOS)                    16 alpha_mean
+ *          17 h_mean                   18 Omega = vphi_mean / R_mean
+ *          19 kappa = sqrt(kappa2) over the ring-combined sums (sectors added in j order): R_k = mean(R), W_k = mean(v_phi)
+ *             / R_k, f_k = ((R_k R_k)(R_k R_k))(W_k W_k), kappa2_k = ((f_b - f_a) / (R_b - R_a)) / ((R_k R_k) R_k) with
+ *             (a, b) = (k - 1, k + 1) inside, (0, 1) and (n_r - 2, n_r - 1) at the ends; NaN with one ring or kappa2 < 0
+ *          20 Q = (c_s kappa) / ((pi G) Sigma) (the sector's own Sigma and c_s)
+ *          21 Mdot = -(((2 pi) R_mean) Sigma) vR_mean
+ *          22 j = |L| / M, L = (sum m l), |L| = sqrt((Lx Lx + Ly Ly) + Lz Lz)
+ *          23 tilt = atan2(sqrt(a1 a1 + a2 a2), a3) = the angle between L^ and n^, with L^ = L / |L|, a1 = L^.e1, a2 = L^.e2,
+ *             a3 = L^.n^ (acos(a3) would lose accuracy for small tilts)      24 twist = atan2(a2, a1)
+ *          25 ecc = |E| / M, E = (sum m e)        26 peri = atan2(E.e2, E.e1) (NaN where M == 0): periapsis longitude
+ *          27 phi_lo = -pi + (2 pi j) / n_phi    28 phi_hi = -pi + (2 pi (j + 1)) / n_phi
+ *          A quantity whose denominator is zero is NaN (0 / 0 in empty bins, a ring's missing neighbour for kappa); N, M and
+ *          Sigma of an empty bin are 0.  The edges are recomputed from the descriptor (normal: the written-back one).
+ * cost     host form: one read-back of the sums (plus one for AUTO_NORMAL); device form: sums only, ordered on the
+ *          context's stream, no synchronisation (AUTO_NORMAL: one).  No state, statistic (other than device_bytes: the
+ *          render's scratch), flag, grid, list or dt of the context changes.
+ * SPH_ERR_ARG: null pointers, both outputs null, n_bins != n_r n_phi, n_r < 1, n_phi < 1, n_r n_phi > 2^20, r_min < 0,
+ * r_min >= r_max, a non-finite r_min / r_max, LOG with r_min == 0, a zero or non-finite normal (without AUTO_NORMAL), a
+ * non-finite centre (sink < 0), NaN z_max, sink < -1 or >= sph_sink_count, unknown flags, reserved != 0, rings so narrow
+ * that two edges coincide.  SPH_ERR_NOMEM: the scratch does not fit. */
+#define SPH_PROFILE_LOG          1   /* logarithmic ring edges (r_min > 0)                                    */
+#define SPH_PROFILE_AUTO_NORMAL  2   /* normal = total angular momentum of the shell about the centre          */
+#define SPH_PROFILE_NSUM  20         /* raw sums per bin                                                        */
+#define SPH_PROFILE_NCOL  29         /* derived columns per bin                                                 */
+typedef struct sph_profile_desc {
+    double  centre[3], centre_v[3];  /* frame origin and velocity (ignored when sink >= 0)                      */
+    double  central_mass;            /* for the eccentricity vector; <= 0: no eccentricity (zeros)              */
+    double  normal[3];               /* disc normal, any length > 0; written back normalised                   */
+    double  r_min, r_max;            /* ring range [r_min, r_max)                                               */
+    double  z_max;                   /* strict |z'| < z_max; INFINITY = none                                    */
+    int32_t n_r, n_phi;              /* rings >= 1, sectors per ring >= 1, n_r n_phi <= 2^20                    */
+    int32_t sink;                    /* >= 0: centre, centre_v and central_mass are that sink's state; -1: none */
+    int32_t flags;                   /* SPH_PROFILE_LOG | SPH_PROFILE_AUTO_NORMAL                               */
+    int32_t reserved[2];             /* must be 0                                                               */
+} sph_profile_desc;                  /* 128 bytes */
+/* either output may be NULL, not both; table needs no sums output (they are read back in any case) */
+int sph_profile(sph_ctx *ctx, sph_profile_desc *d, double *host_sums, double *host_table, int64_t n_bins);
+int sph_profile_dev(sph_ctx *ctx, sph_profile_desc *d, double *d_sums, int64_t n_bins);
+int sph_profile_finish(const sph_profile_desc *d, const sph_params *p, const double *sums, double *table, int64_t n_bins);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too

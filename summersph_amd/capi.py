@@ -43,12 +43,23 @@ SYMBOLS = [
     "sph_apply_partials_dev", "sph_set_boundary_boxes", "sph_forces_part", "sph_set_gravity_sources_dev", "sph_accrete_mark_dev", "sph_accrete_apply_dev", "sph_set_numbers_dev",
     "sph_get_stats", "sph_get_grid_info", "sph_get_bbox", "sph_timing_enable", "sph_timing_stride", "sph_timing_reset", "sph_timing_get", "sph_synchronize", "sph_stream",
     "sph_render_density", "sph_render_density_dev", "sph_render_field", "sph_render_field_dev",
+    "sph_profile", "sph_profile_dev", "sph_profile_finish",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
 RENDER_FIELD_VALUES = -1
 RENDER_WEIGHT_MASS = 0
 RENDER_WEIGHT_VOLUME = 1
+PROFILE_LOG = 1
+PROFILE_AUTO_NORMAL = 2
+PROFILE_NSUM = 20
+PROFILE_NCOL = 29
+# sph_profile_finish's columns (include/summersph.h, "Table") and the raw sums' order ("Sums")
+PROFILE_COLUMNS = ["R_lo", "R_hi", "R_mean", "N", "M", "Sigma", "z_mean", "H", "vR_mean", "vphi_mean", "vz_mean", "sigma_R",
+                   "sigma_phi", "sigma_z", "u_mean", "c_s", "alpha_mean", "h_mean", "Omega", "kappa", "Q", "Mdot", "j", "tilt",
+                   "twist", "ecc", "peri", "phi_lo", "phi_hi"]
+PROFILE_SUMS = ["N", "M", "mR", "mz", "mzz", "mvR", "mvphi", "mvz", "mvRvR", "mvphivphi", "mvzvz", "mu", "malpha", "mh",
+                "mlx", "mly", "mlz", "mex", "mey", "mez"]
 
 
 class Params(C.Structure):
@@ -87,6 +98,59 @@ class RenderFieldDesc(C.Structure):
     weight (RENDER_WEIGHT_MASS / _VOLUME), normalise (0 / 1), reserved"""
     _fields_ = [("base", RenderDesc), ("field", C.c_int32), ("weight", C.c_int32), ("normalise", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class ProfileDesc(C.Structure):
+    """sph_profile_desc (include/summersph.h): centre and its velocity, central mass, normal (written back normalised),
+    ring range, z cut, rings, sectors, sink (-1: none), flags (PROFILE_LOG | PROFILE_AUTO_NORMAL), reserved"""
+    _fields_ = [("centre", C.c_double * 3), ("centre_v", C.c_double * 3), ("central_mass", C.c_double),
+                ("normal", C.c_double * 3), ("r_min", C.c_double), ("r_max", C.c_double), ("z_max", C.c_double),
+                ("n_r", C.c_int32), ("n_phi", C.c_int32), ("sink", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+def profile_desc(r_min, r_max, n_r, n_phi=1, log=False, centre=None, sink=None, normal=(0.0, 0.0, 1.0),
+                 z_max=np.inf) -> ProfileDesc:
+    """The descriptor of Context.profile's arguments (see there)."""
+    d = ProfileDesc()
+    d.r_min, d.r_max, d.z_max = float(r_min), float(r_max), float(z_max)
+    d.n_r, d.n_phi = int(n_r), int(n_phi)
+    d.flags = PROFILE_LOG if log else 0
+    if sink is not None:
+        if centre is not None:
+            raise ValueError("profile: give centre or sink, not both")
+        d.sink = int(sink)
+    else:
+        d.sink = -1
+        if centre is not None:
+            xyz, vxyz, mass = centre
+            d.centre[:] = [float(v) for v in xyz]
+            d.centre_v[:] = [float(v) for v in vxyz]
+            d.central_mass = float(mass)
+    if isinstance(normal, str):
+        if normal != "auto":
+            raise ValueError("profile: normal must be three numbers or 'auto'")
+        d.flags |= PROFILE_AUTO_NORMAL
+    else:
+        d.normal[:] = [float(v) for v in normal]
+    return d
+
+
+def profile_table(table: np.ndarray) -> np.ndarray:
+    """(n_bins, PROFILE_NCOL) float64 -> a structured array of n_bins records with the PROFILE_COLUMNS names"""
+    t = np.ascontiguousarray(table, dtype=np.float64).reshape(-1, PROFILE_NCOL)
+    return t.view([(c, np.float64) for c in PROFILE_COLUMNS]).reshape(-1)
+
+
+def profile_finish(desc: ProfileDesc, params: Params, sums) -> np.ndarray:
+    """sph_profile_finish: raw sums (n_bins, PROFILE_NSUM) -- e.g. the sums of several contexts or ranks added up -> the
+    derived table as a structured array (PROFILE_COLUMNS).  Host code only: no context, no device."""
+    s = np.ascontiguousarray(sums, dtype=np.float64).reshape(-1, PROFILE_NSUM)
+    out = np.empty((s.shape[0], PROFILE_NCOL))
+    st = load().sph_profile_finish(C.byref(desc), C.byref(params), s.ctypes.data, out.ctypes.data, s.shape[0])
+    if st != 0:
+        raise SphError(st, load().sph_strerror(st).decode() + " -- sph_profile_finish")
+    return profile_table(out)
 
 
 class SphError(RuntimeError):
@@ -189,6 +253,9 @@ def load():
     lib.sph_render_density_dev.argtypes = [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p, C.c_int64]
     lib.sph_render_field.argtypes = [C.c_void_p, C.POINTER(RenderFieldDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     lib.sph_render_field_dev.argtypes = [C.c_void_p, C.POINTER(RenderFieldDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sph_profile.argtypes = [C.c_void_p, C.POINTER(ProfileDesc), C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sph_profile_dev.argtypes = [C.c_void_p, C.POINTER(ProfileDesc), C.c_void_p, C.c_int64]
+    lib.sph_profile_finish.argtypes = [C.POINTER(ProfileDesc), C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_int64]
     _lib = lib
     return lib
 
@@ -593,6 +660,37 @@ class Context:
                                                out.ctypes.data, None if wout is None else wout.ctypes.data, size))
         self.render_bounds = (np.array(d.base.lo[:]), np.array(d.base.hi[:]))
         return (out, wout) if weight_out else out
+
+    # ---- disc profiles (sph_profile) -----------------------------------------------------------
+    def profile(self, r_min, r_max, n_r, n_phi=1, log=False, centre=None, sink=None, normal=(0.0, 0.0, 1.0), z_max=np.inf,
+                sums_only=False, device=False):
+        """Mass-weighted moments of the owned gas in rings (n_phi > 1: ring sectors) about a centre (include/summersph.h,
+        sph_profile).  centre: None (the origin at rest, no eccentricity) or (xyz, vxyz, central mass); sink=k: sink k's
+        position, velocity and mass instead; normal: three numbers or 'auto' (the shell's total angular momentum);
+        z_max: strict |z'| cut; log: logarithmic ring edges.  Bin b = ring * n_phi + sector.
+        Returns (table, sums): table a structured array of n_bins records (PROFILE_COLUMNS), sums (n_bins, PROFILE_NSUM)
+        float64; sums_only=True: (None, sums).  device=True: the sums only, as a torch tensor on the context's GPU.  The
+        descriptor used (normal written back) is left in self.profile_desc."""
+        d = profile_desc(r_min, r_max, n_r, n_phi, log, centre, sink, normal, z_max)
+        nb = int(n_r) * int(n_phi)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            out = torch.empty((nb, PROFILE_NSUM), dtype=torch.float64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()          # the block may still be in use by torch's queued work
+            self._ck(self.lib.sph_profile_dev(self._h, C.byref(d), C.c_void_p(out.data_ptr()), nb))
+            st = self.stream()                                    # torch's later work on `out` waits for the profile
+            if st:
+                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
+            else:
+                torch.cuda.synchronize(dev)
+            self.profile_desc = d
+            return out
+        sums = np.empty((nb, PROFILE_NSUM))
+        table = None if sums_only else np.empty((nb, PROFILE_NCOL))
+        self._ck(self.lib.sph_profile(self._h, C.byref(d), sums.ctypes.data, None if table is None else table.ctypes.data, nb))
+        self.profile_desc = d
+        return (None if table is None else profile_table(table)), sums
 
     # ---- diagnostics ---------------------------------------------------------------------
     def stats(self) -> Stats:

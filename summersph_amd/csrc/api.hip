@@ -602,6 +602,7 @@ int sph_ctx_destroy(sph_ctx *c) {
     for (int k = 0; k < 2; k++) { if (c->ev_bbox[k]) (void)hipEventDestroy(c->ev_bbox[k]); if (c->ev_nl[k]) (void)hipEventDestroy(c->ev_nl[k]); }
     ctx_free(c, c->sel_count); ctx_free_ptr(c, c->sel_tmp); ctx_free(c, c->bnd_boxes);
     render_free(c);
+    profile_free(c);
     if (c->stream && c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return SPH_OK;
@@ -1235,6 +1236,18 @@ int sph_render_field_dev(sph_ctx *c, sph_render_field_desc *d, const double *d_v
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
     return render_field(c, d, d_values, d_out, d_weight, out_len, false, field_ready);
+}
+
+int sph_profile(sph_ctx *c, sph_profile_desc *d, double *host_sums, double *host_table, int64_t n_bins) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return profile_sums(c, d, host_sums, host_table, n_bins, true);
+}
+
+int sph_profile_dev(sph_ctx *c, sph_profile_desc *d, double *d_sums, int64_t n_bins) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return profile_sums(c, d, d_sums, nullptr, n_bins, false);
 }
 
 int sph_synchronize(sph_ctx *c) {

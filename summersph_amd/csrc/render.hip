@@ -632,6 +632,8 @@ int render_impl(sph_ctx *c, sph_render_desc *d, const FieldSpec *fs, double *out
 
 }  // namespace
 
+int render_scratch(sph_ctx *c, size_t bytes, char **out) { return scratch(c, bytes, out); }
+
 void render_free(sph_ctx *c) {
     ctx_free_ptr(c, c->rnd_buf); c->rnd_buf = nullptr; c->rnd_bytes = 0;
     ctx_free(c, c->rnd_small);

@@ -244,6 +244,9 @@ struct sph_ctx {
     void *rnd_buf = nullptr; size_t rnd_bytes = 0;
     double *rnd_small = nullptr;     // per-block statistics, their result and the selection cursor
     double *rnd_pinned = nullptr;    // pinned read-back slots
+    // sph_profile (profile.hip): the ring edge table's pinned staging copy and the event of its last upload
+    double *prf_edge = nullptr; size_t prf_edge_cap = 0;
+    hipEvent_t prf_evt = nullptr;
 };
 
 namespace sph {
@@ -338,5 +341,10 @@ int render_density(sph_ctx *c, sph_render_desc *d, double *out, int64_t out_len,
 int render_field(sph_ctx *c, sph_render_field_desc *d, const double *values, double *out, double *wout, int64_t out_len,
                  bool host, bool (*ready)(const sph_ctx *, int));
 void render_free(sph_ctx *c);
+// the render's scratch (grows, never shrinks); sph_profile uses it too
+int render_scratch(sph_ctx *c, size_t bytes, char **out);
+// disc profiles (profile.hip): host form (sums and / or table host memory, one read-back) or device form (sums only)
+int profile_sums(sph_ctx *c, sph_profile_desc *d, double *sums, double *table, int64_t n_bins, bool host);
+void profile_free(sph_ctx *c);
 
 }  // namespace sph

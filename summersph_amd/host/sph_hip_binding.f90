@@ -33,6 +33,9 @@ module sph_hip_binding
   ! field rendering (any per-particle quantity: temperature, moment-1 velocity, alpha maps ...)
   public :: sph_render_field_desc, sph_render_field, sph_render_field_dev
   public :: SPH_RENDER_FIELD_VALUES, SPH_RENDER_WEIGHT_MASS, SPH_RENDER_WEIGHT_VOLUME
+  ! disc profiles (binned mass-weighted moments in rings about a centre, and their derived table)
+  public :: sph_profile_desc, sph_profile, sph_profile_dev, sph_profile_finish
+  public :: SPH_PROFILE_LOG, SPH_PROFILE_AUTO_NORMAL, SPH_PROFILE_NSUM, SPH_PROFILE_NCOL
   public :: c_message
 
   integer(c_int), parameter :: SPH_OK = 0
@@ -47,6 +50,7 @@ module sph_hip_binding
   integer(c_int32_t), parameter :: SPH_PARTIALS = 199
   integer(c_int32_t), parameter :: SPH_RENDER_AUTO_BOUNDS = 1, SPH_RENDER_SPACING = 2
   integer(c_int32_t), parameter :: SPH_RENDER_FIELD_VALUES = -1, SPH_RENDER_WEIGHT_MASS = 0, SPH_RENDER_WEIGHT_VOLUME = 1
+  integer(c_int32_t), parameter :: SPH_PROFILE_LOG = 1, SPH_PROFILE_AUTO_NORMAL = 2, SPH_PROFILE_NSUM = 20, SPH_PROFILE_NCOL = 29
 
   type, bind(C) :: sph_params
     real(c_double) :: h, gamma, gamma_m1
@@ -92,6 +96,18 @@ module sph_hip_binding
     type(sph_render_desc) :: base
     integer(c_int32_t) :: field, weight, normalise, reserved
   end type sph_render_field_desc
+
+  ! centre / centre_v / central_mass (ignored with sink >= 0), normal (written back normalised), rings [r_min, r_max),
+  ! strict |z'| < z_max (IEEE +infinity: none), n_r rings x n_phi sectors, sink (-1: none), flags, reserved (0).
+  ! sums(SPH_PROFILE_NSUM, n_bins) and table(SPH_PROFILE_NCOL, n_bins), bin = ring * n_phi + sector.  128 bytes.
+  type, bind(C) :: sph_profile_desc
+    real(c_double) :: centre(3), centre_v(3)
+    real(c_double) :: central_mass
+    real(c_double) :: normal(3)
+    real(c_double) :: r_min, r_max, z_max
+    integer(c_int32_t) :: n_r, n_phi, sink, flags
+    integer(c_int32_t) :: reserved(2)
+  end type sph_profile_desc
 
   interface
     integer(c_int) function sph_abi_version() bind(C, name='sph_abi_version')
@@ -480,6 +496,28 @@ module sph_hip_binding
       type(c_ptr), value :: ctx, d_values, d_out, d_weight
       type(sph_render_field_desc), intent(inout) :: d
       integer(c_int64_t), value :: out_len
+    end function
+
+    ! ---- disc profiles: host_sums / host_table are c_loc(...) or c_null_ptr (not both); sph_profile_finish is host code
+    integer(c_int) function sph_profile(ctx, d, host_sums, host_table, n_bins) bind(C, name='sph_profile')
+      import :: c_int, c_int64_t, c_ptr, sph_profile_desc
+      type(c_ptr), value :: ctx, host_sums, host_table
+      type(sph_profile_desc), intent(inout) :: d
+      integer(c_int64_t), value :: n_bins
+    end function
+    integer(c_int) function sph_profile_dev(ctx, d, d_sums, n_bins) bind(C, name='sph_profile_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_profile_desc
+      type(c_ptr), value :: ctx, d_sums
+      type(sph_profile_desc), intent(inout) :: d
+      integer(c_int64_t), value :: n_bins
+    end function
+    integer(c_int) function sph_profile_finish(d, p, sums, table, n_bins) bind(C, name='sph_profile_finish')
+      import :: c_int, c_int64_t, c_double, sph_profile_desc, sph_params
+      type(sph_profile_desc), intent(in) :: d
+      type(sph_params), intent(in) :: p
+      real(c_double), intent(in) :: sums(*)
+      real(c_double), intent(out) :: table(*)
+      integer(c_int64_t), value :: n_bins
     end function
   end interface
 
