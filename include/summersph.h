@@ -508,6 +508,56 @@ int sph_profile(sph_ctx *ctx, sph_profile_desc *d, double *host_sums, double *ho
 int sph_profile_dev(sph_ctx *ctx, sph_profile_desc *d, double *d_sums, int64_t n_bins);
 int sph_profile_finish(const sph_profile_desc *d, const sph_params *p, const double *sums, double *table, int64_t n_bins);
 
+/* ---- conserved totals and the gravitational potential: energy, momentum and angular momentum of the gas and the
+ *      sinks, with the Barnes-Hut gas self-potential and the sink potentials, and the potential of every particle -------
+ * Particles the state as sph_download_field returns it, in every state of the context (after an upload, a drift, an
+ *          sph_step with SPH_FLAG_ACCRETE_CULL, a cull).  Targets: the owned gas (original ids < n_owned), never ghosts;
+ *          sinks: the context's sink arrays.  h_i = SPH_F_H with variable h, else params.h.  G = params.G.
+ * Phi_sink,i = -sum_s G M_s / |r_i - R_s| in sink order, unsoftened as the sink accelerations are ([F]:559-591), with
+ *          |d| = sqrt((dx dx + dy dy) + dz dz) and each term (G M_s) / |d|; massless sinks add 0.
+ * Phi_self,i  0 without SPH_FLAG_SELF_GRAVITY (the energy of the equations the context integrates).  With it: the
+ *          Barnes-Hut walk of the force (same acceptance test, theta, soft2 = 0.001 * 2.5 and target h) over the tree of the
+ *          sources; an accepted node or leaf of mass m_j adds (G m_j / h_i) phi(q), s = sqrt(d.d + soft2), q = s / h_i, where
+ *          phi is the potential of the cubic-spline softening whose mass fraction is the reference's grav_table polynomial
+ *          ([F]:81-101), q^2 phi'(q) = that polynomial:
+ *            q < 1:      phi = (2/3) q^2 - (3/10) q^4 + (1/10) q^5 - 7/5
+ *            1 <= q < 2: phi = (4/3) q^2 - q^3 + (3/10) q^4 - (1/30) q^5 - 8/5 + 1 / (15 q)
+ *            q >= 2:     phi = -1 / q
+ *          evaluated analytically (the force interpolates its table; the two differ by O(dq^2)).  The target's own source is
+ *          excluded by identity, not by distance: two distinct coincident particles see each other.  As in the force walk,
+ *          a node smaller than theta sqrt(soft2) that contains the target can be accepted, its monopole then including the
+ *          target.  With variable h, Phi_self,i uses h_i (as the force): W_self is a diagnostic, not an exact pair sum.
+ * Sources  without sph_set_gravity_sources_dev: the owned gas records {x, y, z, m} in the caller's order and their exact
+ *          bounding box; src_offset is ignored.  With external sources: those records and box, the tree sph_forces builds;
+ *          the particle of original id k is source src_offset + k (its own source, for the exclusion).  Phi_self,i is a
+ *          function of the source records in order, their box and the target's own record only: a single context and a
+ *          set of contexts fed the same records and box through sph_set_gravity_sources_dev give bitwise the same values.
+ * Sums     sums[0..SPH_ENERGY_NSUM), per gas particle terms in this order, without fused multiply-adds:
+ *           0 N (count as a double)    1 M = sum m             2-4 sum m r            5-7 sum m v
+ *           8-10 sum m (r x v) = m (y vz - z vy, z vx - x vz, x vy - y vx) about the origin
+ *          11 K = sum (0.5 m) ((vx vx + vy vy) + vz vz)     12 U = sum m u
+ *          13 W_self = sum (0.5 m) Phi_self,i               14 W_gs = sum m Phi_sink,i
+ *          additive over contexts and ranks.  The sink part, on rank 0 only (sph_set_rank; 0 elsewhere), so that the whole
+ *          array adds over ranks: 15 number of sinks  16 M_s  17-19 sum M R  20-22 sum M V  23-25 sum M (R x V)
+ *          26 K_s = sum (0.5 M) V.V  27 W_ss = -sum_{s<t} (G (M_s M_t)) / |R_s - R_t| (pairs with M_s M_t == 0 add 0).
+ *          Derived (capi.energy_total): E = K + U + W_self + W_gs + K_s + W_ss, P = [5-7] + [20-22], L = [8-10] + [23-25].
+ * Order    the gas terms are reduced in the caller's particle order in a fixed shape: pieces of 1024 ids, each added by
+ *          one 64-lane wavefront (lanes strided, then a xor butterfly), then the pieces by one wavefront.  Bitwise
+ *          reproducible over calls, sorted orders, dense or hashed grids, and whether forces were just evaluated.  No
+ *          float atomics.
+ * phi      (optional) Phi_self,i + Phi_sink,i: n_phi == sph_count doubles in sph_download_field order, 0 for ghosts
+ *          (e.g. the values of sph_render_field with SPH_RENDER_FIELD_VALUES).
+ * cost     host form: one read-back (one more for the root box with self-gravity and no external sources); device form:
+ *          ordered on the context's stream, synchronising only for that root box.  No state, field, statistic (other than
+ *          device_bytes), dt, grid or list changes; a run that calls sph_energy after every step is bitwise the run
+ *          without it.  With self-gravity and no external sources the tree is built into the context's tree arrays, so the
+ *          next sph_forces builds its own tree again (one more tree build, the same results).
+ * SPH_ERR_ARG: both outputs null, n_phi != sph_count with phi given, src_offset outside [0, n_src - n_owned] with external
+ * sources.  An empty context returns zeros (and the sink part). */
+#define SPH_ENERGY_NSUM 28
+int sph_energy(sph_ctx *ctx, int64_t src_offset, double *host_sums, double *host_phi, int64_t n_phi);
+int sph_energy_dev(sph_ctx *ctx, int64_t src_offset, double *d_sums, double *d_phi, int64_t n_phi);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too

@@ -44,6 +44,7 @@ SYMBOLS = [
     "sph_get_stats", "sph_get_grid_info", "sph_get_bbox", "sph_timing_enable", "sph_timing_stride", "sph_timing_reset", "sph_timing_get", "sph_synchronize", "sph_stream",
     "sph_render_density", "sph_render_density_dev", "sph_render_field", "sph_render_field_dev",
     "sph_profile", "sph_profile_dev", "sph_profile_finish",
+    "sph_energy", "sph_energy_dev",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
@@ -58,6 +59,11 @@ PROFILE_NCOL = 29
 PROFILE_COLUMNS = ["R_lo", "R_hi", "R_mean", "N", "M", "Sigma", "z_mean", "H", "vR_mean", "vphi_mean", "vz_mean", "sigma_R",
                    "sigma_phi", "sigma_z", "u_mean", "c_s", "alpha_mean", "h_mean", "Omega", "kappa", "Q", "Mdot", "j", "tilt",
                    "twist", "ecc", "peri", "phi_lo", "phi_hi"]
+ENERGY_NSUM = 28
+# sph_energy's sums (include/summersph.h, "Sums"): the gas part (additive over contexts and ranks), then the sink part
+# (rank 0 only)
+ENERGY_SUMS = ["N", "M", "mx", "my", "mz", "px", "py", "pz", "lx", "ly", "lz", "K", "U", "W_self", "W_gs",
+               "Ns", "Ms", "Mx_s", "My_s", "Mz_s", "Px_s", "Py_s", "Pz_s", "Lx_s", "Ly_s", "Lz_s", "K_s", "W_ss"]
 PROFILE_SUMS = ["N", "M", "mR", "mz", "mzz", "mvR", "mvphi", "mvz", "mvRvR", "mvphivphi", "mvzvz", "mu", "malpha", "mh",
                 "mlx", "mly", "mlz", "mex", "mey", "mez"]
 
@@ -151,6 +157,20 @@ def profile_finish(desc: ProfileDesc, params: Params, sums) -> np.ndarray:
     if st != 0:
         raise SphError(st, load().sph_strerror(st).decode() + " -- sph_profile_finish")
     return profile_table(out)
+
+
+def energy_total(sums) -> dict:
+    """sph_energy's sums (ENERGY_NSUM values, e.g. those of several contexts or ranks added up) -> a dict of the named
+    sums (ENERGY_SUMS) and the derived totals: E = K + U + W_self + W_gs + K_s + W_ss, P and L (gas + sinks, numpy arrays
+    of 3) and com, the centre of mass of gas and sinks (zeros without mass)."""
+    s = np.asarray(sums, dtype=np.float64).reshape(ENERGY_NSUM)
+    d = {k: float(v) for k, v in zip(ENERGY_SUMS, s)}
+    d["E"] = float(s[11] + s[12] + s[13] + s[14] + s[26] + s[27])
+    d["P"] = s[5:8] + s[20:23]
+    d["L"] = s[8:11] + s[23:26]
+    mt = s[1] + s[16]
+    d["com"] = (s[2:5] + s[17:20]) / mt if mt > 0 else np.zeros(3)
+    return d
 
 
 class SphError(RuntimeError):
@@ -256,6 +276,8 @@ def load():
     lib.sph_profile.argtypes = [C.c_void_p, C.POINTER(ProfileDesc), C.c_void_p, C.c_void_p, C.c_int64]
     lib.sph_profile_dev.argtypes = [C.c_void_p, C.POINTER(ProfileDesc), C.c_void_p, C.c_int64]
     lib.sph_profile_finish.argtypes = [C.POINTER(ProfileDesc), C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sph_energy.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sph_energy_dev.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
     _lib = lib
     return lib
 
@@ -691,6 +713,39 @@ class Context:
         self._ck(self.lib.sph_profile(self._h, C.byref(d), sums.ctypes.data, None if table is None else table.ctypes.data, nb))
         self.profile_desc = d
         return (None if table is None else profile_table(table)), sums
+
+    # ---- conserved totals and the potential (sph_energy) ---------------------------------------
+    def energy(self, phi=False, device=False, src_offset=0):
+        """Energy, momentum and angular momentum of the owned gas and the sinks, with the gravitational potential
+        (include/summersph.h, sph_energy).  Returns energy_total(sums) (the named sums, E, P, L, com) plus "sums", the raw
+        ENERGY_NSUM values (they add over contexts and ranks).  phi=True: also "phi", Phi_self + Phi_sink of every particle
+        in the upload order (sph_count values, 0 for ghosts).  device=True: "sums" and "phi" are torch tensors on the
+        context's GPU (sph_energy_dev); the named values are read from them.  src_offset: the position of this context's
+        owned particles in the external source set (sph_set_gravity_sources_dev), ignored without one."""
+        n = self.n
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            sums = torch.empty(ENERGY_NSUM, dtype=torch.float64, device=dev)
+            ph = torch.empty(n, dtype=torch.float64, device=dev) if phi else None
+            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
+            self._ck(self.lib.sph_energy_dev(self._h, int(src_offset), C.c_void_p(sums.data_ptr()),
+                                             C.c_void_p(ph.data_ptr()) if ph is not None else None, n))
+            st = self.stream()                                    # torch's later work waits for the energy
+            if st:
+                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
+            else:
+                torch.cuda.synchronize(dev)
+            out = energy_total(sums.cpu().numpy())
+        else:
+            sums = np.empty(ENERGY_NSUM)
+            ph = np.empty(n) if phi else None
+            self._ck(self.lib.sph_energy(self._h, int(src_offset), sums.ctypes.data, None if ph is None else ph.ctypes.data, n))
+            out = energy_total(sums)
+        out["sums"] = sums
+        if phi:
+            out["phi"] = ph
+        return out
 
     # ---- diagnostics ---------------------------------------------------------------------
     def stats(self) -> Stats:

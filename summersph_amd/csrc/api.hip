@@ -1250,6 +1250,18 @@ int sph_profile_dev(sph_ctx *c, sph_profile_desc *d, double *d_sums, int64_t n_b
     return profile_sums(c, d, d_sums, nullptr, n_bins, false);
 }
 
+int sph_energy(sph_ctx *c, int64_t src_offset, double *host_sums, double *host_phi, int64_t n_phi) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return energy_sums(c, src_offset, host_sums, host_phi, n_phi, true);
+}
+
+int sph_energy_dev(sph_ctx *c, int64_t src_offset, double *d_sums, double *d_phi, int64_t n_phi) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return energy_sums(c, src_offset, d_sums, d_phi, n_phi, false);
+}
+
 int sph_synchronize(sph_ctx *c) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);

@@ -413,6 +413,67 @@ __global__ __launch_bounds__(GB) void grav_walk_wave(int nt, int n, const WalkRe
     }
 }
 
+// phi(q) of the cubic-spline softening whose mass fraction is the grav_table polynomial ([F]:81-101): q^2 phi'(q) equals
+// that polynomial, phi(q) = -1/q for q >= 2 (rq = 1/q, used only there and in the middle piece)
+__device__ __forceinline__ double soft_phi(double q, double rq) {
+    const double q2 = q * q;
+    if (q < 1.0) return q2 * ((2.0 / 3.0) + q2 * (-0.3 + 0.1 * q)) - 1.4;
+    if (q < 2.0) return (q2 * ((4.0 / 3.0) + q * (-1.0 + q * (0.3 - q * (1.0 / 30.0)))) - 1.6) + rq * (1.0 / 15.0);
+    return -rq;
+}
+
+// The potential of the same Barnes-Hut walk (sph_energy): grav_walk_wave's traversal and acceptance test over the same
+// records, but each accepted node or leaf of mass m adds (G m / h) phi(s / h), s = sqrt(d^2 + soft2), to the target's
+// potential, and the target's own leaf is skipped by identity (it would add -1.4 G m / h, not 0).  Targets: the context's
+// slots (cell-sorted: neighbouring lanes walk nearly the same nodes), owned particles only; position and h are read from
+// the state fields.  The source of the target with original id k is source src_off + k, its leaf leaf_of[src_off + k].
+// Writes phi[k]; never touches the accelerations.
+__global__ __launch_bounds__(GB) void grav_potential_wave(int nt, int n, const WalkRec *__restrict__ rec, const double *__restrict__ x,
+                                                          const double *__restrict__ y, const double *__restrict__ z,
+                                                          const double *__restrict__ hvar, double hfix, double soft2,
+                                                          const int32_t *__restrict__ orig, int32_t n_owned,
+                                                          const int32_t *__restrict__ leaf_of, int64_t src_off, double *__restrict__ phi) {
+    const int i = xcd_chunk(blockIdx.x, gridDim.x) * GB + threadIdx.x;
+    const int self = i < nt ? i : nt - 1;
+    const int32_t id = orig[self];
+    const bool live = i < nt && id >= 0 && id < n_owned;
+    const int own = live ? n - 1 + leaf_of[src_off + id] : END;
+    const double px = x[self], py = y[self], pz = z[self];
+    const double hp = hvar ? hvar[self] : hfix;
+    const double inv_hp = 1.0 / hp;
+    double acc = 0.0;
+    int resume = END;
+    int node = n >= 2 ? 0 : END;
+    constexpr int CMP_EQ = 32, CMP_NE = 33, CMP_OLT = 4;
+    unsigned long long act_m = __builtin_amdgcn_ballot_w64(live);
+    while (node != END) {
+        node = __builtin_amdgcn_readfirstlane(node);
+        const WalkRec r = rec[node];
+        act_m |= __builtin_amdgcn_uicmp((unsigned)resume, (unsigned)node, CMP_EQ);
+        const int n_open = r.next_open, n_skip = r.next_skip;
+        const double d0 = px - r.cx, d1 = py - r.cy, d2c = pz - r.cz;
+        const double d2 = fma(d2c, d2c, fma(d1, d1, fma(d0, d0, soft2)));     // the force walk's d2 and acceptance test
+        const unsigned long long acc_m = __builtin_amdgcn_fcmp(r.size2, d2, CMP_OLT);
+        const unsigned long long done_m = act_m & acc_m;
+        const bool open_any = (act_m & ~acc_m) != 0;
+        if (r.has_mass) {
+            if (__builtin_amdgcn_inverse_ballot_w64(done_m & __builtin_amdgcn_uicmp((unsigned)own, (unsigned)node, CMP_NE))) {
+                const double rs = fast_rsqrt(d2);                  // 1 / s
+                const double q = (d2 * rs) * inv_hp;               // s / h
+                acc += (r.gm * inv_hp) * soft_phi(q, hp * rs);
+            }
+        }
+        if (open_any) {
+            resume = __builtin_amdgcn_inverse_ballot_w64(done_m) ? n_skip : resume;
+            act_m &= ~done_m;
+            node = n_open;
+        } else {
+            node = n_skip;
+        }
+    }
+    if (live) phi[id] = acc;
+}
+
 }  // namespace
 
 #define GR_CHECK2(expr)                                                     \
@@ -495,40 +556,9 @@ int global_keys_sorted(sph_ctx *c) {
     return SPH_OK;
 }
 
-// builds the tree over the context's own particles (current cell-sorted positions) or over the external source set
-int gravity_tree_build(sph_ctx *c) {
-    const bool ext = c->gx_src != nullptr;
-    const int64_t n = ext ? c->gx_n : c->n;
-    if (n == 0) return SPH_OK;
-    if (n > 2000000000LL) { c->err = "gravity: more than 2e9 sources"; return SPH_ERR_ARG; }
-    { const int st = gravity_reserve(c, ext ? n : std::max(c->cap, n)); if (st != SPH_OK) return st; }
-    const double *bb = ext ? c->gx_box : c->bbox;
-    RootBox rb;
-    double size = 0.0;
-    for (int a = 0; a < 3; a++) {
-        rb.c[a] = (bb[3 + a] + bb[a]) / 2.0;                            // [F]:803-805
-        size = std::max(size, bb[3 + a] - bb[a]);                       // [F]:806-808
-    }
-    rb.size = size;
-    for (int a = 0; a < 3; a++) c->root_box[a] = rb.c[a];
-    c->root_box[3] = size;
+// the tree over n sources whose sorted path keys are in g_keys_alt / g_vals_alt: leaves, radix tree, node sums, walk records
+static int tree_from_sorted_keys(sph_ctx *c, const double4 *drec, int64_t n, const RootBox &rb) {
     const unsigned gb = (unsigned)((n + GB - 1) / GB);
-    const double4 *drec = reinterpret_cast<const double4 *>(ext ? c->gx_src : c->drec);
-    if (ext) {
-        const int st = global_keys_sorted(c);
-        if (st != SPH_OK) return st;
-    } else {
-        if (c->path_keys_valid && c->mkeys_alt && c->mvals_alt) {
-            // variable h: the leaf-box build of this grid build sorted the same keys (same positions, same root box)
-            GR_CHECK2(hipMemcpyAsync(c->g_keys_alt, c->mkeys_alt, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
-            GR_CHECK2(hipMemcpyAsync(c->g_vals_alt, c->mvals_alt, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-        } else {
-            grav_keys<<<dim3(gb), dim3(GB), 0, c->stream>>>(rb, drec, n, c->g_keys, c->g_vals);
-            GR_CHECK2(hipGetLastError());
-            size_t tmp = c->g_sort_tmp_bytes;
-            GR_CHECK2(rocprim::radix_sort_pairs(c->g_sort_tmp, tmp, c->g_keys, c->g_keys_alt, c->g_vals, c->g_vals_alt, (size_t)n, 0u, 63u, c->stream));
-        }
-    }
     TreeArrays t = tree_arrays(c);
     leaf_data<<<dim3(gb), dim3(GB), 0, c->stream>>>(c->g_vals_alt, drec, (int)n, t);
     if (n >= 2) {
@@ -551,6 +581,78 @@ int gravity_tree_build(sph_ctx *c) {
     node_wave_records<<<dim3(gb), dim3(GB), 0, c->stream>>>((int)n, t, rb, c->p.theta * c->p.theta, c->p.G, reinterpret_cast<WalkRec *>(c->g_wrec), c->g_leaf_of);
     GR_CHECK2(hipGetLastError());
     return SPH_OK;
+}
+
+// root box of a source set: bbox-midpoint centre, edge = largest extent ([F]:803-808)
+static RootBox root_of(const double *bb) {
+    RootBox rb;
+    double size = 0.0;
+    for (int a = 0; a < 3; a++) {
+        rb.c[a] = (bb[3 + a] + bb[a]) / 2.0;
+        size = std::max(size, bb[3 + a] - bb[a]);
+    }
+    rb.size = size;
+    return rb;
+}
+
+// builds the tree over the context's own particles (current cell-sorted positions) or over the external source set
+int gravity_tree_build(sph_ctx *c) {
+    const bool ext = c->gx_src != nullptr;
+    const int64_t n = ext ? c->gx_n : c->n;
+    if (n == 0) return SPH_OK;
+    if (n > 2000000000LL) { c->err = "gravity: more than 2e9 sources"; return SPH_ERR_ARG; }
+    { const int st = gravity_reserve(c, ext ? n : std::max(c->cap, n)); if (st != SPH_OK) return st; }
+    const RootBox rb = root_of(ext ? c->gx_box : c->bbox);
+    for (int a = 0; a < 3; a++) c->root_box[a] = rb.c[a];
+    c->root_box[3] = rb.size;
+    const unsigned gb = (unsigned)((n + GB - 1) / GB);
+    const double4 *drec = reinterpret_cast<const double4 *>(ext ? c->gx_src : c->drec);
+    if (ext) {
+        const int st = global_keys_sorted(c);
+        if (st != SPH_OK) return st;
+    } else {
+        if (c->path_keys_valid && c->mkeys_alt && c->mvals_alt) {
+            // variable h: the leaf-box build of this grid build sorted the same keys (same positions, same root box)
+            GR_CHECK2(hipMemcpyAsync(c->g_keys_alt, c->mkeys_alt, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+            GR_CHECK2(hipMemcpyAsync(c->g_vals_alt, c->mvals_alt, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+        } else {
+            grav_keys<<<dim3(gb), dim3(GB), 0, c->stream>>>(rb, drec, n, c->g_keys, c->g_vals);
+            GR_CHECK2(hipGetLastError());
+            size_t tmp = c->g_sort_tmp_bytes;
+            GR_CHECK2(rocprim::radix_sort_pairs(c->g_sort_tmp, tmp, c->g_keys, c->g_keys_alt, c->g_vals, c->g_vals_alt, (size_t)n, 0u, 63u, c->stream));
+        }
+    }
+    return tree_from_sorted_keys(c, drec, n, rb);
+}
+
+// sph_energy: the tree over n caller-given {x, y, z, m} records in their order and their box -- the tree that
+// gravity_tree_build makes of an external source set with the same records and box (the same keys, the same stable
+// sort, the same kernels).  Built into the context's tree arrays: the context's own tree, the sorted external keys
+// and the cached self-gravity term are no longer there, so they are marked stale (the next sph_forces rebuilds them).
+int gravity_tree_build_records(sph_ctx *c, const double *rec, int64_t n, const double box[6]) {
+    c->tree_valid = false; c->grav_valid = false; c->gx_keys_valid = false;
+    if (n == 0) return SPH_OK;
+    if (n > 2000000000LL) { c->err = "gravity: more than 2e9 sources"; return SPH_ERR_ARG; }
+    { const int st = gravity_reserve(c, std::max(c->cap, n)); if (st != SPH_OK) return st; }
+    const RootBox rb = root_of(box);
+    const double4 *drec = reinterpret_cast<const double4 *>(rec);
+    grav_keys<<<dim3((unsigned)((n + GB - 1) / GB)), dim3(GB), 0, c->stream>>>(rb, drec, n, c->g_keys, c->g_vals);
+    GR_CHECK2(hipGetLastError());
+    size_t tmp = c->g_sort_tmp_bytes;
+    GR_CHECK2(rocprim::radix_sort_pairs(c->g_sort_tmp, tmp, c->g_keys, c->g_keys_alt, c->g_vals, c->g_vals_alt, (size_t)n, 0u, 63u, c->stream));
+    return tree_from_sorted_keys(c, drec, n, rb);
+}
+
+// sph_energy: the self-potential of every owned particle by the walk over the tree in place (n_src leaves; source
+// src_off + k is the particle of original id k) -> phi[k], k < n_owned
+hipError_t launch_potential(sph_ctx *c, int64_t n_src, int64_t src_off, double *phi) {
+    const int64_t nt = c->n_slots;
+    if (nt == 0 || n_src == 0 || c->n_owned == 0) return hipSuccess;
+    const double soft2 = 0.001 * 2.5;                                   // as launch_gravity
+    grav_potential_wave<<<dim3((unsigned)((nt + GB - 1) / GB)), dim3(GB), 0, c->stream>>>(
+        (int)nt, (int)n_src, reinterpret_cast<const WalkRec *>(c->g_wrec), c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z],
+        c->variable ? c->f[SPH_F_H] : nullptr, c->p.h, soft2, c->orig, (int32_t)c->n_owned, c->g_leaf_of, src_off, phi);
+    return hipGetLastError();
 }
 
 hipError_t launch_gravity(sph_ctx *c) {

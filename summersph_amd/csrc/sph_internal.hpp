@@ -313,6 +313,10 @@ int gravity_tree_build(sph_ctx *c);
 int global_keys_sorted(sph_ctx *c);      // sorted path keys of the external source set -> c->g_keys_alt / g_vals_alt
 void gravity_free(sph_ctx *c);
 hipError_t launch_gravity(sph_ctx *c);
+// sph_energy (gravity.hip): the tree over caller-order {x,y,z,m} records and their box, built into the context's tree
+// arrays (clears tree_valid, grav_valid, gx_keys_valid), and the potential walk over the tree in place
+int gravity_tree_build_records(sph_ctx *c, const double *rec, int64_t n, const double box[6]);
+hipError_t launch_potential(sph_ctx *c, int64_t n_src, int64_t src_off, double *phi);
 // accretion + boundary cull (accrete.hip)
 int accrete_and_cull(sph_ctx *c, int64_t *removed, int32_t *d_keep_out = nullptr);
 int sink_creation(sph_ctx *c, int32_t *created);
@@ -346,5 +350,8 @@ int render_scratch(sph_ctx *c, size_t bytes, char **out);
 // disc profiles (profile.hip): host form (sums and / or table host memory, one read-back) or device form (sums only)
 int profile_sums(sph_ctx *c, sph_profile_desc *d, double *sums, double *table, int64_t n_bins, bool host);
 void profile_free(sph_ctx *c);
+// conserved totals and the gravitational potential (energy.hip): host form (sums / phi host memory, one read-back) or
+// device form
+int energy_sums(sph_ctx *c, int64_t src_offset, double *sums, double *phi, int64_t n_phi, bool host);
 
 }  // namespace sph

@@ -36,6 +36,8 @@ module sph_hip_binding
   ! disc profiles (binned mass-weighted moments in rings about a centre, and their derived table)
   public :: sph_profile_desc, sph_profile, sph_profile_dev, sph_profile_finish
   public :: SPH_PROFILE_LOG, SPH_PROFILE_AUTO_NORMAL, SPH_PROFILE_NSUM, SPH_PROFILE_NCOL
+  ! conserved totals and the gravitational potential (energy, momentum, angular momentum; phi per particle)
+  public :: sph_energy, sph_energy_dev, SPH_ENERGY_NSUM
   public :: c_message
 
   integer(c_int), parameter :: SPH_OK = 0
@@ -51,6 +53,7 @@ module sph_hip_binding
   integer(c_int32_t), parameter :: SPH_RENDER_AUTO_BOUNDS = 1, SPH_RENDER_SPACING = 2
   integer(c_int32_t), parameter :: SPH_RENDER_FIELD_VALUES = -1, SPH_RENDER_WEIGHT_MASS = 0, SPH_RENDER_WEIGHT_VOLUME = 1
   integer(c_int32_t), parameter :: SPH_PROFILE_LOG = 1, SPH_PROFILE_AUTO_NORMAL = 2, SPH_PROFILE_NSUM = 20, SPH_PROFILE_NCOL = 29
+  integer(c_int32_t), parameter :: SPH_ENERGY_NSUM = 28
 
   type, bind(C) :: sph_params
     real(c_double) :: h, gamma, gamma_m1
@@ -518,6 +521,19 @@ module sph_hip_binding
       real(c_double), intent(in) :: sums(*)
       real(c_double), intent(out) :: table(*)
       integer(c_int64_t), value :: n_bins
+    end function
+
+    ! ---- conserved totals and the potential: host_sums (SPH_ENERGY_NSUM doubles) / host_phi (sph_count doubles, the
+    !      download order) are c_loc(...) or c_null_ptr (not both); src_offset: this rank's first source (external sources)
+    integer(c_int) function sph_energy(ctx, src_offset, host_sums, host_phi, n_phi) bind(C, name='sph_energy')
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: ctx, host_sums, host_phi
+      integer(c_int64_t), value :: src_offset, n_phi
+    end function
+    integer(c_int) function sph_energy_dev(ctx, src_offset, d_sums, d_phi, n_phi) bind(C, name='sph_energy_dev')
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: ctx, d_sums, d_phi
+      integer(c_int64_t), value :: src_offset, n_phi
     end function
   end interface
 

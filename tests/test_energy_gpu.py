@@ -1,0 +1,343 @@
+"""GPU tests of sph_energy (include/summersph.h, "conserved totals and the gravitational potential") on the MI355X: the
+sink terms and phi against the numpy restatement (fixed and variable h), the exact self-potential (theta -> 0 opens every
+node: the walk is the direct sum), the Barnes-Hut error at theta = 0.5, the self-exclusion, parity with the reference's
+own trajectories, momentum and accretion bookkeeping, the order rule, no side effects on a running simulation,
+additivity over contexts fed external sources, the device form, the argument errors and the command line."""
+import json
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, load_golden
+import energy_ref
+from summersph_amd import ic, txtio
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-12
+SPH_ERR_ARG = 1
+# theta = 0.5: |W_self - direct| / |direct| measured on the MI355X 3.6e-3 on the 20 000-particle
+# heavy disc, 2.0e-3 and 2.3e-3 on the disc3000 / bin2000 fixture states; the bound keeps a margin of 2.7 over the largest
+BH_TOL = 1e-2
+TINY_THETA = 1e-9
+
+
+@pytest.fixture(scope="module")
+def capi():
+    from summersph_amd import capi as m
+    m.load()
+    return m
+
+
+def _ctx(capi, gas, sinks, variable=False, flags=0, **kw):
+    if variable:
+        flags |= capi.FLAG_VARIABLE_H
+    ctx = capi.Context(device=0, variable=variable, **({"flags": flags} if flags else {}), **kw)
+    ctx.upload(gas)
+    if sinks is not None:
+        ctx.set_sinks(sinks)
+    return ctx
+
+
+def _var_kw(g):
+    gamma, eta, tol, maxlen, scale = g["params"]
+    return dict(gamma=gamma, gamma_m1=gamma - 1.0, eta=eta, h_tol=tol, h_max_length=maxlen, dt_scale=scale)
+
+
+def _cmp_sums(got, want, scale, tol, which=range(energy_ref.NSUM)):
+    for k in which:
+        s = max(abs(want[k]), scale[k])
+        assert abs(got[k] - want[k]) <= tol * s, (energy_ref.SUMS[k], got[k], want[k])
+
+
+def _rel(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-300)))
+
+
+def _state(ctx, variable=False):
+    gas = {k: ctx.field(k) for k in "x y z vx vy vz u m alpha".split() + (["h"] if variable else [])}
+    s = ctx.get_sinks()
+    return gas, {k: s[k] for k in "x y z vx vy vz m".split()}
+
+
+@pytest.mark.parametrize("name", ["disc3000_eval", "bin2000_eval", "discv3000_eval"])
+def test_sink_terms_without_self_gravity(capi, name):
+    g = load_golden(name)
+    variable = name.startswith("discv")
+    gas, sinks = (ic.split_rows_var if variable else ic.split_rows)(g["ic"])
+    ctx = _ctx(capi, gas, sinks, variable, **(_var_kw(g) if variable else {}))
+    e = ctx.energy(phi=True)
+    h = gas["h"] if variable else ctx.params.h
+    want, phi, sc = energy_ref.energy_sums(gas, sinks, ctx.params.G, h, self_gravity=False, scales=True)
+    _cmp_sums(e["sums"], want, sc, TOL)
+    assert e["W_self"] == 0.0
+    assert _rel(e["phi"], phi) <= TOL
+    if name == "bin2000_eval":
+        assert e["Ns"] == 2 and e["W_ss"] < 0.0
+    t = energy_ref.totals(want)
+    assert abs(e["E"] - t["E"]) <= TOL * sc[11:15].sum()
+    ctx.close()
+
+
+@pytest.mark.parametrize("case", ["disc3000_full_s5", "sinkcv1500_full_s3"])
+def test_exact_self_potential_is_the_direct_sum(capi, case):
+    variable = case.startswith("sinkcv")
+    g = load_golden("sinkcv1500_traj" if variable else "disc3000_traj")
+    gas, sinks = energy_ref.rows_to_dicts(g, "full_s3_" if variable else "full_s5_", variable)
+    ctx = _ctx(capi, gas, sinks, variable, flags=capi.FLAG_SELF_GRAVITY, theta=TINY_THETA, **(_var_kw(g) if variable else {}))
+    e = ctx.energy(phi=True)
+    h = gas["h"] if variable else ctx.params.h
+    want, phi, sc = energy_ref.energy_sums(gas, sinks, ctx.params.G, h, self_gravity=True, scales=True)
+    assert _rel(e["phi"], phi) <= TOL
+    assert abs(e["W_self"] - want[13]) <= TOL * abs(want[13])
+    _cmp_sums(e["sums"], want, sc, TOL)
+    ctx.close()
+
+
+def test_barnes_hut_self_potential_at_theta_half(capi):
+    gas, sinks = ic.split_rows(ic.keplerian_disc(20000, seed=5, m_disc=0.5))
+    ctx = _ctx(capi, gas, sinks, flags=capi.FLAG_SELF_GRAVITY)
+    e = ctx.energy(phi=True)
+    direct = energy_ref.self_potential(gas["x"], gas["y"], gas["z"], gas["m"], ctx.params.h, ctx.params.G)
+    w = 0.5 * float(np.sum(gas["m"] * direct))
+    err = abs(e["W_self"] - w) / abs(w)
+    print(f"theta 0.5, 20000 particles: |W_self - direct| / |direct| = {err:.3e}")
+    assert err <= BH_TOL
+    ctx.close()
+    exact = _ctx(capi, gas, sinks, flags=capi.FLAG_SELF_GRAVITY, theta=TINY_THETA)
+    assert abs(exact.energy()["W_self"] - w) <= TOL * abs(w)
+    exact.close()
+
+
+def test_self_exclusion(capi):
+    one = {k: np.array([v]) for k, v in zip("x y z vx vy vz u m".split(), (3.0, -2.0, 0.5, 0.1, 0.2, 0.0, 0.3, 1e-3))}
+    ctx = _ctx(capi, one, None, flags=capi.FLAG_SELF_GRAVITY)
+    e = ctx.energy(phi=True)
+    assert e["W_self"] == 0.0 and e["phi"][0] == 0.0
+    ctx.close()
+    # a coincident pair (different masses) plus far-away particles
+    rng = np.random.default_rng(9)
+    nf = 40
+    far = rng.uniform(-400.0, 400.0, (nf, 3)) + np.array([600.0, 0.0, 0.0])
+    pos = np.concatenate([np.array([[1.0, 2.0, 3.0], [1.0, 2.0, 3.0]]), far])
+    m = np.concatenate([[2e-3, 5e-3], rng.uniform(1e-4, 1e-3, nf)])
+    gas = {"x": pos[:, 0], "y": pos[:, 1], "z": pos[:, 2], "vx": np.zeros(nf + 2), "vy": np.zeros(nf + 2), "vz": np.zeros(nf + 2),
+           "u": np.full(nf + 2, 0.25), "m": m}
+    ctx = _ctx(capi, gas, None, flags=capi.FLAG_SELF_GRAVITY, theta=TINY_THETA)
+    p = ctx.params
+    e = ctx.energy(phi=True)
+    pair = lambda mj: (p.G * mj / p.h) * energy_ref.phi_kernel(np.sqrt(energy_ref.SOFT2) / p.h)
+    for i, j in ((0, 1), (1, 0)):
+        d = np.sqrt(((pos[2:] - pos[i])**2).sum(axis=1) + energy_ref.SOFT2)
+        rest = np.sum((p.G * m[2:] / p.h) * energy_ref.phi_kernel(d / p.h))
+        assert abs(e["phi"][i] - (pair(m[j]) + rest)) <= TOL * abs(pair(m[j]) + rest), i
+    ctx.close()
+
+
+def _parity_run(capi, g, flags, steps):
+    gas, sinks = ic.split_rows(g["ic"])
+    ctx = _ctx(capi, gas, sinks, flags=flags)
+    dt, t = 1e-2, 0.0
+    out = {}
+    for k in range(1, max(steps) + 1):
+        dt, t = ctx.step(dt, t)
+        if k in steps:
+            out[k] = (ctx.energy(), _state(ctx))
+    ctx.close()
+    return out
+
+
+@pytest.mark.parametrize("name,prefix,flags,steps", [("disc3000_traj", "sph", 0, (1, 5)), ("disc3000_traj", "full", "sg", (5,)),
+                                                     ("bin2000_traj", "sph", 0, (3,)), ("bin2000_traj", "full", "sg_acc", (1, 3))])
+def test_parity_with_the_reference_trajectories(capi, name, prefix, flags, steps):
+    g = load_golden(name)
+    fl = {0: 0, "sg": capi.FLAG_SELF_GRAVITY, "sg_acc": capi.FLAG_SELF_GRAVITY | capi.FLAG_ACCRETE_CULL}[flags]
+    runs = _parity_run(capi, g, fl, steps)
+    G, h = capi.default_params().G, capi.default_params().h
+    for k in steps:
+        e, (gas_gpu, sinks_gpu) = runs[k]
+        gas, sinks = energy_ref.rows_to_dicts(g, f"{prefix}_s{k}_")
+        sg = bool(fl & capi.FLAG_SELF_GRAVITY)
+        want, _, sc = energy_ref.energy_sums(gas, sinks, G, h, self_gravity=sg, scales=True)
+        # K, U, W_gs, P, L of the gas; K_s, W_ss, P, L of the sinks
+        _cmp_sums(e["sums"], want, sc, 1e-9, which=[0, 1, 5, 6, 7, 8, 9, 10, 11, 12, 14, 15, 16, 20, 21, 22, 23, 24, 25, 26, 27])
+        if sg:
+            assert abs(e["W_self"] - want[13]) <= BH_TOL * abs(want[13]), k
+            exact = _ctx(capi, gas_gpu, sinks_gpu, flags=capi.FLAG_SELF_GRAVITY, theta=TINY_THETA)
+            assert abs(exact.energy()["W_self"] - want[13]) <= 1e-9 * abs(want[13]), k
+            exact.close()
+        else:
+            assert e["W_self"] == 0.0
+
+
+def test_momentum_is_conserved_without_self_gravity(capi):
+    g = load_golden("disc3000_traj")
+    gas, sinks = ic.split_rows(g["ic"])
+    ctx = _ctx(capi, gas, sinks)
+    e0 = ctx.energy()
+    dt, t = 1e-2, 0.0
+    for _ in range(10):
+        dt, t = ctx.step(dt, t)
+    e1 = ctx.energy()
+    gs, ss = _state(ctx)
+    scale = np.sum(gs["m"] * np.sqrt(gs["vx"]**2 + gs["vy"]**2 + gs["vz"]**2)) + \
+        np.sum(ss["m"] * np.sqrt(ss["vx"]**2 + ss["vy"]**2 + ss["vz"]**2))
+    assert np.max(np.abs(e1["P"] - e0["P"])) <= 1e-12 * scale, (e1["P"] - e0["P"], scale)
+    ctx.close()
+
+
+def test_accretion_keeps_total_mass_and_momentum(capi):
+    g = load_golden("acc2000_traj")
+    gas, sinks = ic.split_rows(g["ic"])
+    ctx = _ctx(capi, gas, sinks, bounding_size=1e12)
+    ctx.step(1e-2)                 # no accretion flag: the reference accretes four particles at the end of this step
+    ctx.density()                  # the grid of the current positions (sph_accrete_and_cull needs it)
+    e0 = ctx.energy()
+    gs, _ = _state(ctx)
+    removed = ctx.accrete_and_cull()
+    e1 = ctx.energy()
+    assert removed > 0 and e1["N"] == e0["N"] - removed
+    mt0, mt1 = e0["M"] + e0["Ms"], e1["M"] + e1["Ms"]
+    assert abs(mt1 - mt0) <= 1e-13 * mt0
+    scale = np.sum(np.abs(gs["m"][:, None] * np.stack([gs["vx"], gs["vy"], gs["vz"]], axis=1)))
+    assert np.max(np.abs(e1["P"] - e0["P"])) <= 1e-13 * scale
+    ctx.close()
+
+
+def test_order_rule_is_bitwise(capi):
+    gas, sinks = ic.split_rows(ic.keplerian_disc(30000, seed=17, m_disc=0.1))
+    res = []
+    for flags in (capi.FLAG_SELF_GRAVITY, capi.FLAG_SELF_GRAVITY | capi.FLAG_HASHED_GRID):
+        ctx = _ctx(capi, gas, sinks, flags=flags)
+        a = ctx.energy(phi=True)                   # upload order, no grid yet
+        ctx.density(); ctx.forces()                # cell-sorted, forces just evaluated
+        b = ctx.energy(phi=True)
+        c = ctx.energy(phi=True)
+        for x in (b, c):
+            assert np.array_equal(x["sums"], a["sums"]) and np.array_equal(x["phi"], a["phi"])
+        res.append(a)
+        ctx.close()
+    assert np.array_equal(res[0]["sums"], res[1]["sums"]) and np.array_equal(res[0]["phi"], res[1]["phi"])
+
+
+def _run5(capi, gas, sinks, flags, with_energy, variable=False, kw=None):
+    ctx = _ctx(capi, gas, sinks, variable, flags=flags, **(kw or {}))
+    dt, t = 1e-2, 0.0
+    seq = []
+    for _ in range(5):
+        dt, t = ctx.step(dt, t)
+        seq.append((dt, t, ctx.n))
+        if with_energy:
+            ctx.energy(phi=True)
+    fields = {k: ctx.field(k) for k in "x y z vx vy vz u m alpha".split() + (["h"] if variable else [])}
+    s = ctx.get_sinks()
+    st = ctx.stats()
+    stats = {f: (getattr(st, f)[:] if hasattr(getattr(st, f), "__len__") else getattr(st, f))
+             for f, _ in st._fields_ if f != "device_bytes"}
+    ctx.close()
+    return seq, fields, s, stats
+
+
+@pytest.mark.parametrize("case", ["plain", "sg_acc", "sg_reuse", "variable"])
+def test_no_side_effects_on_a_run(capi, case):
+    kw = None
+    if case == "variable":
+        g = load_golden("discv3000_traj")
+        gas, sinks = ic.split_rows_var(g["ic"])
+        flags, variable, kw = capi.FLAG_SELF_GRAVITY, True, _var_kw(g)
+    else:
+        g = load_golden("acc2000_traj" if case == "sg_acc" else "disc3000_traj")
+        gas, sinks = ic.split_rows(g["ic"])
+        flags = {"plain": 0, "sg_acc": capi.FLAG_SELF_GRAVITY | capi.FLAG_ACCRETE_CULL,
+                 "sg_reuse": capi.FLAG_SELF_GRAVITY | capi.FLAG_REUSE_GRAVITY}[case]
+        variable = False
+    a = _run5(capi, gas, sinks, flags, False, variable, kw)
+    b = _run5(capi, gas, sinks, flags, True, variable, kw)
+    assert a[0] == b[0]
+    for k in a[1]:
+        assert np.array_equal(a[1][k], b[1][k]), k
+    for k in a[2]:
+        assert np.array_equal(a[2][k], b[2][k]), k
+    assert a[3] == b[3]
+
+
+def test_additive_over_contexts_with_external_sources(capi):
+    import torch
+    gas, sinks = ic.split_rows(ic.keplerian_disc(12000, seed=23, m_disc=0.3))
+    n = gas["x"].size
+    single = _ctx(capi, gas, sinks, flags=capi.FLAG_SELF_GRAVITY)
+    e = single.energy(phi=True)
+    n0 = 5000
+    rec = np.stack([gas["x"], gas["y"], gas["z"], gas["m"]], axis=1)
+    box = np.concatenate([rec[:, :3].min(axis=0), rec[:, :3].max(axis=0)])
+    d_rec = torch.tensor(rec, dtype=torch.float64, device="cuda:0").contiguous()
+    torch.cuda.synchronize()
+    parts = []
+    for rank, sl in ((0, slice(0, n0)), (1, slice(n0, n))):
+        ctx = _ctx(capi, {k: v[sl] for k, v in gas.items()}, sinks, flags=capi.FLAG_SELF_GRAVITY)
+        ctx.set_rank(rank, 2)
+        ctx.set_gravity_sources_dev(n, d_rec.data_ptr(), box)
+        parts.append(ctx.energy(phi=True, src_offset=sl.start))
+        ctx.close()
+    phi = np.concatenate([parts[0]["phi"], parts[1]["phi"]])
+    assert np.array_equal(phi, e["phi"])
+    tot = parts[0]["sums"] + parts[1]["sums"]
+    _, _, sc = energy_ref.energy_sums(gas, sinks, single.params.G, single.params.h, phi_self=np.zeros(n), scales=True)
+    sc[13] = abs(e["sums"][13])
+    _cmp_sums(tot, e["sums"], sc, 1e-13)
+    assert np.all(parts[1]["sums"][15:] == 0.0) and np.array_equal(parts[0]["sums"][15:], e["sums"][15:])
+    single.close()
+
+
+def test_device_form_and_errors(capi):
+    import torch
+    g = load_golden("bin2000_eval")
+    gas, sinks = ic.split_rows(g["ic"])
+    ctx = _ctx(capi, gas, sinks, flags=capi.FLAG_SELF_GRAVITY)
+    h = ctx.energy(phi=True)
+    d = ctx.energy(phi=True, device=True)
+    assert np.array_equal(d["sums"].cpu().numpy(), h["sums"]) and np.array_equal(d["phi"].cpu().numpy(), h["phi"])
+    lib, n = ctx.lib, ctx.n
+    sums = np.empty(28)
+    ph = np.empty(n)
+    assert lib.sph_energy(ctx._h, 0, None, None, n) == SPH_ERR_ARG
+    assert lib.sph_energy(ctx._h, 0, None, ph.ctypes.data, n - 1) == SPH_ERR_ARG
+    assert lib.sph_energy_dev(ctx._h, 0, None, None, n) == SPH_ERR_ARG
+    assert lib.sph_energy(ctx._h, 0, sums.ctypes.data, None, 0) == 0          # n_phi is ignored without phi
+    assert np.array_equal(sums, h["sums"])
+    rec = torch.zeros((n + 10, 4), dtype=torch.float64, device="cuda:0")
+    ctx.set_gravity_sources_dev(n + 10, rec.data_ptr(), np.array([-1.0, -1, -1, 1, 1, 1]))
+    assert lib.sph_energy(ctx._h, 11, sums.ctypes.data, None, 0) == SPH_ERR_ARG
+    assert lib.sph_energy(ctx._h, -1, sums.ctypes.data, None, 0) == SPH_ERR_ARG
+    ctx.close()
+    empty = capi.Context(device=0, flags=capi.FLAG_SELF_GRAVITY)
+    e = empty.energy(phi=True)
+    assert np.all(e["sums"] == 0.0) and e["phi"].size == 0
+    empty.close()
+
+
+def test_cli_json_and_phi_renders(capi, tmp_path):
+    gas, sinks = ic.split_rows(ic.keplerian_disc(4000, seed=31, m_disc=0.05))
+    rows = np.stack([gas[k] for k in "x y z vx vy vz u m".split()] + [np.zeros(gas["x"].size)], axis=1)
+    srows = np.stack([sinks[k] for k in ("x", "y", "z", "vx", "vy", "vz")] + [np.zeros(1), sinks["m"]], axis=1)
+    save = tmp_path / "save.txt"
+    txtio.write_save(str(save), rows, srows)
+    phi_out = tmp_path / "phi.npy"
+    r = subprocess.run([sys.executable, "-m", "summersph_amd.energy", str(save), "--json", "--phi", str(phi_out)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    got = json.loads(r.stdout)
+    g2 = {k: rows[:, i] for i, k in enumerate("x y z vx vy vz u m alpha".split())}
+    s2 = {k: srows[:, i] for i, k in zip((0, 1, 2, 3, 4, 5, 7), "x y z vx vy vz m".split())}
+    ctx = _ctx(capi, g2, s2, flags=capi.FLAG_SELF_GRAVITY)
+    e = ctx.energy(phi=True)
+    assert got["sums"] == e["sums"].tolist()
+    for k in ("E", "K", "W_self", "W_gs"):
+        assert got[k] == e[k], k
+    assert got["P"] == e["P"].tolist() and got["L"] == e["L"].tolist()
+    assert np.array_equal(np.load(phi_out), e["phi"])
+    img = ctx.render_field(e["phi"], 32, axis="z", bounds=((-60.0, -60.0, -60.0), (60.0, 60.0, 60.0)), normalise=True)
+    assert np.all(np.isfinite(img)) and np.min(img) < 0.0
+    ctx.close()
