@@ -558,6 +558,63 @@ int sph_profile_finish(const sph_profile_desc *d, const sph_params *p, const dou
 int sph_energy(sph_ctx *ctx, int64_t src_offset, double *host_sums, double *host_phi, int64_t n_phi);
 int sph_energy_dev(sph_ctx *ctx, int64_t src_offset, double *d_sums, double *d_phi, int64_t n_phi);
 
+/* ---- friends-of-friends groups: the clumps of the owned gas (which particles form them, how many there are, their
+ *      mass, size, spin and bulk motion) -------------------------------------------------------------------------------
+ * Select   the owned gas (original ids < n_owned; ghosts and sinks excluded, as the renders select) with rho >= rho_min
+ *          (-INFINITY: every particle whose rho is not NaN) and clip_lo < x < clip_hi on every axis (strict; -INFINITY /
+ *          +INFINITY: no cut; a non-finite position is never selected).  rho is the value sph_download_field(SPH_F_RHO)
+ *          would return: SPH_ERR_STATE exactly when that call would refuse it.  One context's owned particles only: groups
+ *          that cross ranks (dist.py, the native multi-GPU loop) are not joined.
+ * Link     selected i and j are linked iff d2 < b * b, d2 = (dx dx + dy dy) + dz dz with dx = x_i - x_j (each product
+ *          and sum rounded on its own, no fused multiply-adds).  b = link; with SPH_GROUPS_LINK_H b = link * max(h_i, h_j)
+ *          (rounded once), h = SPH_F_H with variable h, else params.h.
+ * Groups   the connected components of the links with >= min_members members; smaller components are dropped.  They
+ *          are numbered 0 .. n_groups - 1 by N descending, ties by the smallest original id ascending: the partition is
+ *          unique, so the numbering depends only on the positions, the selection and the descriptor.
+ * Labels   (optional) int32 per particle in sph_download_field order, n_labels == sph_count: the group number, -1 for
+ *          unselected particles, particles of dropped components and ghosts.
+ * Table    (optional) table[g * SPH_GROUPS_NCOL + col] for the first min(n_groups, max_groups) groups; *n_groups
+ *          receives the full count in every case.  Per member, in this order, without fused multiply-adds:
+ *          first pass  m, m x, m y, m z, m vx, m vy, m vz, m u;
+ *          second pass dr = r - R, dv = v - V, d2 = (dr_x dr_x + dr_y dr_y) + dr_z dr_z, m d2,
+ *                      m (dr_y dv_z - dr_z dv_y), m (dr_z dv_x - dr_x dv_z), m (dr_x dv_y - dr_y dv_x),
+ *                      (0.5 m) ((dv_x dv_x + dv_y dv_y) + dv_z dv_z), sqrt(d2) (max), rho (max).
+ *           0 N (count, as a double)     1 M = sum m                  2-4 R = (sum m r) / M (each axis)
+ *           5-7 V = (sum m v) / M        8 r_rms = sqrt((sum m d2) / M)            9 r_max = max sqrt(d2)
+ *          10-12 spin S = sum m (dr x dv)                        13 K_int = sum (0.5 m) |dv|^2
+ *          14 U = sum m u                15 rho_max                   16-18 position of the densest member
+ *          19 original id of the densest member (the smallest id on ties)           20 smallest original id
+ *          (M == 0: R, V and r_rms are NaN.)
+ * Order    each group's members are sorted by original id and its sums reduced in a fixed shape: pieces of 1024 sorted
+ *          positions counted from the group's start, each added by one 64-lane wavefront (lane l: positions l, l + 64,
+ *          ... in turn, then a xor butterfly over the lanes), then the pieces by one wavefront in the same shape.  First
+ *          pass N, M, sum m r, sum m v, sum m u; R and V from it on the device; second pass the moments about R and V.
+ *          max and argmax are order-free.  No float atomics.  Labels and table are bitwise the same over repeated calls,
+ *          over the context's sorted order and over dense or hashed grids.
+ * cost     host form: one synchronisation, which copies out the count, the table rows and the labels.  Device form
+ *          (labels, table and the int64 count in device memory): ordered on the context's stream, no synchronisation; a
+ *          selected h <= 0 or non-finite under LINK_H then shows as *d_n_groups == -1 with every label -1.  No state,
+ *          field, statistic (other than device_bytes: the render's scratch), flag, grid, list or dt of the context
+ *          changes; a run that calls sph_groups after every step is bitwise the run without it.
+ * SPH_ERR_ARG: null descriptor or count pointer, link <= 0 or non-finite, NaN rho_min or clip, min_members < 1, labels
+ * given with n_labels != sph_count, max_groups < 0, a table with max_groups == 0, unknown flags, reserved != 0.
+ * SPH_ERR_STATE: stale rho; under LINK_H params.h <= 0 (fixed h) or, host form, a selected h <= 0 or non-finite.  An empty
+ * selection gives 0 groups. */
+#define SPH_GROUPS_LINK_H  1         /* b = link * max(h_i, h_j)                                                 */
+#define SPH_GROUPS_NCOL    21        /* table columns per group                                                  */
+typedef struct sph_groups_desc {
+    double  link;                    /* linking length (LINK_H: in units of h), finite, > 0                      */
+    double  rho_min;                 /* rho >= rho_min; -INFINITY: no cut                                        */
+    double  clip_lo[3], clip_hi[3];  /* strict particle clip box; -INFINITY / +INFINITY = none                   */
+    int64_t min_members;             /* >= 1                                                                     */
+    int32_t flags;                   /* SPH_GROUPS_LINK_H                                                        */
+    int32_t reserved;                /* must be 0                                                                */
+} sph_groups_desc;                   /* 80 bytes */
+int sph_groups(sph_ctx *ctx, const sph_groups_desc *d, int32_t *host_labels, int64_t n_labels, double *host_table,
+               int64_t max_groups, int64_t *n_groups);
+int sph_groups_dev(sph_ctx *ctx, const sph_groups_desc *d, int32_t *d_labels, int64_t n_labels, double *d_table,
+                   int64_t max_groups, int64_t *d_n_groups);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too

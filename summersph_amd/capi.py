@@ -45,6 +45,7 @@ SYMBOLS = [
     "sph_render_density", "sph_render_density_dev", "sph_render_field", "sph_render_field_dev",
     "sph_profile", "sph_profile_dev", "sph_profile_finish",
     "sph_energy", "sph_energy_dev",
+    "sph_groups", "sph_groups_dev",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
@@ -64,6 +65,11 @@ ENERGY_NSUM = 28
 # (rank 0 only)
 ENERGY_SUMS = ["N", "M", "mx", "my", "mz", "px", "py", "pz", "lx", "ly", "lz", "K", "U", "W_self", "W_gs",
                "Ns", "Ms", "Mx_s", "My_s", "Mz_s", "Px_s", "Py_s", "Pz_s", "Lx_s", "Ly_s", "Lz_s", "K_s", "W_ss"]
+GROUPS_LINK_H = 1
+GROUPS_NCOL = 21
+# sph_groups' table columns (include/summersph.h, "Table")
+GROUPS_COLUMNS = ["N", "M", "x", "y", "z", "vx", "vy", "vz", "r_rms", "r_max", "Sx", "Sy", "Sz", "K_int", "U", "rho_max",
+                  "x_dense", "y_dense", "z_dense", "id_dense", "id_min"]
 PROFILE_SUMS = ["N", "M", "mR", "mz", "mzz", "mvR", "mvphi", "mvz", "mvRvR", "mvphivphi", "mvzvz", "mu", "malpha", "mh",
                 "mlx", "mly", "mlz", "mex", "mey", "mez"]
 
@@ -113,6 +119,30 @@ class ProfileDesc(C.Structure):
                 ("normal", C.c_double * 3), ("r_min", C.c_double), ("r_max", C.c_double), ("z_max", C.c_double),
                 ("n_r", C.c_int32), ("n_phi", C.c_int32), ("sink", C.c_int32), ("flags", C.c_int32),
                 ("reserved", C.c_int32 * 2)]
+
+
+class GroupsDesc(C.Structure):
+    """sph_groups_desc (include/summersph.h): linking length, rho cut, strict clip box, min_members, flags
+    (GROUPS_LINK_H), reserved"""
+    _fields_ = [("link", C.c_double), ("rho_min", C.c_double), ("clip_lo", C.c_double * 3), ("clip_hi", C.c_double * 3),
+                ("min_members", C.c_int64), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+def groups_desc(link, rho_min=-np.inf, min_members=1, link_h=False, clip=None) -> GroupsDesc:
+    """The descriptor of Context.groups' arguments (see there)."""
+    d = GroupsDesc()
+    d.link, d.rho_min, d.min_members = float(link), float(rho_min), int(min_members)
+    d.flags = GROUPS_LINK_H if link_h else 0
+    lo, hi = ((-np.inf,) * 3, (np.inf,) * 3) if clip is None else clip
+    d.clip_lo[:] = [float(v) for v in lo]
+    d.clip_hi[:] = [float(v) for v in hi]
+    return d
+
+
+def groups_table(table: np.ndarray) -> np.ndarray:
+    """(n, GROUPS_NCOL) float64 -> a structured array of n records with the GROUPS_COLUMNS names"""
+    t = np.ascontiguousarray(table, dtype=np.float64).reshape(-1, GROUPS_NCOL)
+    return t.view([(c, np.float64) for c in GROUPS_COLUMNS]).reshape(-1)
 
 
 def profile_desc(r_min, r_max, n_r, n_phi=1, log=False, centre=None, sink=None, normal=(0.0, 0.0, 1.0),
@@ -278,6 +308,10 @@ def load():
     lib.sph_profile_finish.argtypes = [C.POINTER(ProfileDesc), C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_int64]
     lib.sph_energy.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
     lib.sph_energy_dev.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sph_groups.argtypes = [C.c_void_p, C.POINTER(GroupsDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                               C.POINTER(C.c_int64)]
+    lib.sph_groups_dev.argtypes = [C.c_void_p, C.POINTER(GroupsDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                   C.c_void_p]
     _lib = lib
     return lib
 
@@ -746,6 +780,46 @@ class Context:
         if phi:
             out["phi"] = ph
         return out
+
+    # ---- friends-of-friends groups (sph_groups) --------------------------------------------------
+    def groups(self, link, rho_min=-np.inf, min_members=1, link_h=False, clip=None, max_groups=None, labels=True,
+               device=False):
+        """The friends-of-friends groups of the owned gas (include/summersph.h, sph_groups): particles with rho >= rho_min
+        inside the strict clip box ((lo xyz, hi xyz) or None) are linked when closer than link (link_h=True: link *
+        max(h_i, h_j)); components with >= min_members members are numbered by N descending, then the smallest id.
+        Returns (labels, table, n_groups): labels int32 per particle in the upload order (-1: in no group; None with
+        labels=False), table a structured array (GROUPS_COLUMNS) of the first min(n_groups, max_groups) groups (None with
+        max_groups == 0; max_groups=None: every group), n_groups the full count.  device=True: labels and the table rows
+        (max_groups of them, the first min(n_groups, max_groups) written) are torch tensors on the context's GPU
+        (sph_groups_dev); the table is then an (max_groups, GROUPS_NCOL) float64 tensor.  The descriptor used is left in
+        self.groups_desc."""
+        d = groups_desc(link, rho_min, min_members, link_h, clip)
+        n = self.n
+        mg = n if max_groups is None else int(max_groups)
+        self.groups_desc = d
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            lab = torch.empty(n, dtype=torch.int32, device=dev) if labels else None
+            tab = torch.empty((mg, GROUPS_NCOL), dtype=torch.float64, device=dev) if mg > 0 else None
+            cnt = torch.empty(1, dtype=torch.int64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
+            self._ck(self.lib.sph_groups_dev(self._h, C.byref(d), C.c_void_p(lab.data_ptr()) if lab is not None else None, n,
+                                             C.c_void_p(tab.data_ptr()) if tab is not None else None, mg,
+                                             C.c_void_p(cnt.data_ptr())))
+            st = self.stream()                                    # torch's later work waits for the groups
+            if st:
+                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
+            else:
+                torch.cuda.synchronize(dev)
+            return lab, tab, int(cnt.item())
+        lab = np.empty(n, dtype=np.int32) if labels else None
+        tab = np.empty((mg, GROUPS_NCOL)) if mg > 0 else None
+        ng = C.c_int64(0)
+        self._ck(self.lib.sph_groups(self._h, C.byref(d), None if lab is None else lab.ctypes.data, n,
+                                     None if tab is None else tab.ctypes.data, mg, C.byref(ng)))
+        ng = int(ng.value)
+        return lab, (None if tab is None else groups_table(tab[:min(ng, mg)])), ng
 
     # ---- diagnostics ---------------------------------------------------------------------
     def stats(self) -> Stats:

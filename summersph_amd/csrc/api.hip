@@ -1262,6 +1262,20 @@ int sph_energy_dev(sph_ctx *c, int64_t src_offset, double *d_sums, double *d_phi
     return energy_sums(c, src_offset, d_sums, d_phi, n_phi, false);
 }
 
+int sph_groups(sph_ctx *c, const sph_groups_desc *d, int32_t *host_labels, int64_t n_labels, double *host_table,
+               int64_t max_groups, int64_t *n_groups) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return groups_run(c, d, host_labels, n_labels, host_table, max_groups, n_groups, true, field_ready);
+}
+
+int sph_groups_dev(sph_ctx *c, const sph_groups_desc *d, int32_t *d_labels, int64_t n_labels, double *d_table,
+                   int64_t max_groups, int64_t *d_n_groups) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return groups_run(c, d, d_labels, n_labels, d_table, max_groups, d_n_groups, false, field_ready);
+}
+
 int sph_synchronize(sph_ctx *c) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);

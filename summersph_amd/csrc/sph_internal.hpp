@@ -353,5 +353,9 @@ void profile_free(sph_ctx *c);
 // conserved totals and the gravitational potential (energy.hip): host form (sums / phi host memory, one read-back) or
 // device form
 int energy_sums(sph_ctx *c, int64_t src_offset, double *sums, double *phi, int64_t n_phi, bool host);
+// friends-of-friends groups (groups.hip): host form (labels / table / count host memory, one synchronisation) or device
+// form; ready = sph_download_field's rule
+int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_labels, double *table, int64_t max_groups,
+               int64_t *n_groups, bool host, bool (*ready)(const sph_ctx *, int));
 
 }  // namespace sph

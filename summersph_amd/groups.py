@@ -1,0 +1,100 @@
+"""Friends-of-friends groups (clumps) of a save file on the GPU: which particles form them, how many there are, and
+their mass, size, spin and bulk motion.
+
+    python -m summersph_amd.groups SAVE.txt -o OUT.npz [--csv OUT.csv] [--json] [--variable] --link B [--link-h]
+                                   [--rho-min R] [--min-members K] [--clip x0,y0,z0,x1,y1,z1] [--top T]
+
+SAVE.txt is a save file as for `python -m summersph_amd.profile`: records of 9 values (10 with --variable: .. alpha h)
+are gas, records of 8 values are sinks.  The gas and the sinks are uploaded into a fresh context, sph_density gives rho,
+and sph_groups (capi.Context.groups) links every two selected particles closer than B (--link-h: B max(h_i, h_j)).
+Selected: rho >= --rho-min, strictly inside --clip.  Components with fewer than --min-members members are dropped.
+
+OUT.npz holds `labels` (int32 per gas row: the group number, -1 in none), every table column by name
+(capi.GROUPS_COLUMNS, one value per group, largest first), `n_groups` and the descriptor used (`desc_*`).  --csv also
+writes the table as text; --json prints the count and the table of the --top largest groups as one JSON line.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+
+import numpy as np
+
+from .profile import read_save
+
+
+def parse_clip(spec: str):
+    """'x0,y0,z0,x1,y1,z1' -> ((x0, y0, z0), (x1, y1, z1)), no NaN and lo <= hi on every axis"""
+    v = [float(t) for t in spec.split(",")]
+    if len(v) != 6 or any(np.isnan(v)) or any(v[a] > v[3 + a] for a in range(3)):
+        raise ValueError(f"--clip wants x0,y0,z0,x1,y1,z1 with x0 <= x1 ..., not {spec!r}")
+    return tuple(v[:3]), tuple(v[3:])
+
+
+def groups_rows(gas, sinks, link, rho_min=-np.inf, min_members=1, link_h=False, clip=None, variable=False, device=0):
+    """Uploads the rows into a fresh context, evaluates rho and finds the groups: (labels, table, n_groups, descriptor)."""
+    from . import capi
+    ctx = capi.Context(device=device, variable=variable)
+    try:
+        names = "x y z vx vy vz u m alpha".split() + (["h"] if variable else [])
+        ctx.upload({k: gas[:, i] for i, k in enumerate(names)})
+        if sinks.shape[0]:
+            ctx.set_sinks({k: sinks[:, i] for i, k in zip((0, 1, 2, 3, 4, 5, 7), "x y z vx vy vz m".split())})
+        ctx.density()
+        labels, table, ng = ctx.groups(link, rho_min=rho_min, min_members=min_members, link_h=link_h, clip=clip)
+        return labels, table, ng, ctx.groups_desc
+    finally:
+        ctx.close()
+
+
+def main(argv=None) -> int:
+    from . import capi
+    ap = argparse.ArgumentParser(prog="python -m summersph_amd.groups", description=__doc__.split("\n\n")[0])
+    ap.add_argument("save", help="save file")
+    ap.add_argument("-o", "--out", required=True, help="output .npz")
+    ap.add_argument("--csv", default=None, help="also write the table as CSV")
+    ap.add_argument("--json", action="store_true", help="print the count and the largest groups as one JSON line")
+    ap.add_argument("--variable", action="store_true", help="10-value gas records (.. alpha h), variable-h context")
+    ap.add_argument("--link", type=float, required=True, help="linking length (--link-h: in units of h)")
+    ap.add_argument("--link-h", action="store_true", help="link * max(h_i, h_j)")
+    ap.add_argument("--rho-min", type=float, default=-np.inf)
+    ap.add_argument("--min-members", type=int, default=1)
+    ap.add_argument("--clip", default=None, help="x0,y0,z0,x1,y1,z1 (strict)")
+    ap.add_argument("--top", type=int, default=20, help="groups in the --json table")
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    try:
+        clip = None if a.clip is None else parse_clip(a.clip)
+    except ValueError as e:
+        ap.error(str(e))
+    if not (np.isfinite(a.link) and a.link > 0):
+        ap.error("--link must be finite and > 0")
+    if np.isnan(a.rho_min):
+        ap.error("--rho-min is NaN")
+    if a.min_members < 1 or a.top < 0:
+        ap.error("--min-members must be >= 1 and --top >= 0")
+
+    gas, sinks = read_save(a.save, a.variable)
+    labels, table, ng, d = groups_rows(gas, sinks, a.link, a.rho_min, a.min_members, a.link_h, clip, a.variable, a.device)
+    out = {"labels": labels, "n_groups": np.array(ng)}
+    out.update({c: np.ascontiguousarray(table[c]) for c in capi.GROUPS_COLUMNS})
+    for f, _ in capi.GroupsDesc._fields_:
+        v = getattr(d, f)
+        out["desc_" + f] = np.array(v[:] if hasattr(v, "__len__") else v)
+    np.savez(a.out, **out)
+    if a.csv:
+        np.savetxt(a.csv, np.stack([table[c] for c in capi.GROUPS_COLUMNS], axis=1).reshape(-1, capi.GROUPS_NCOL),
+                   delimiter=",", header=",".join(capi.GROUPS_COLUMNS), comments="")
+    if a.json:
+        top = table[:a.top]
+        print(json.dumps({"n_groups": ng, "columns": capi.GROUPS_COLUMNS,
+                          "table": [[float(r[c]) for c in capi.GROUPS_COLUMNS] for r in top]}))
+    else:
+        print(f"{a.out}: {ng} groups from {gas.shape[0]} gas rows ({sinks.shape[0]} sinks), "
+              f"{int(np.sum(labels >= 0))} particles in groups")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

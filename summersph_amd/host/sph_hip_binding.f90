@@ -38,6 +38,8 @@ module sph_hip_binding
   public :: SPH_PROFILE_LOG, SPH_PROFILE_AUTO_NORMAL, SPH_PROFILE_NSUM, SPH_PROFILE_NCOL
   ! conserved totals and the gravitational potential (energy, momentum, angular momentum; phi per particle)
   public :: sph_energy, sph_energy_dev, SPH_ENERGY_NSUM
+  ! friends-of-friends groups (clumps of the owned gas: labels per particle and a table per group)
+  public :: sph_groups_desc, sph_groups, sph_groups_dev, SPH_GROUPS_LINK_H, SPH_GROUPS_NCOL
   public :: c_message
 
   integer(c_int), parameter :: SPH_OK = 0
@@ -54,6 +56,7 @@ module sph_hip_binding
   integer(c_int32_t), parameter :: SPH_RENDER_FIELD_VALUES = -1, SPH_RENDER_WEIGHT_MASS = 0, SPH_RENDER_WEIGHT_VOLUME = 1
   integer(c_int32_t), parameter :: SPH_PROFILE_LOG = 1, SPH_PROFILE_AUTO_NORMAL = 2, SPH_PROFILE_NSUM = 20, SPH_PROFILE_NCOL = 29
   integer(c_int32_t), parameter :: SPH_ENERGY_NSUM = 28
+  integer(c_int32_t), parameter :: SPH_GROUPS_LINK_H = 1, SPH_GROUPS_NCOL = 21
 
   type, bind(C) :: sph_params
     real(c_double) :: h, gamma, gamma_m1
@@ -111,6 +114,15 @@ module sph_hip_binding
     integer(c_int32_t) :: n_r, n_phi, sink, flags
     integer(c_int32_t) :: reserved(2)
   end type sph_profile_desc
+
+  ! linking length (LINK_H: in units of max(h_i, h_j)), rho >= rho_min (IEEE -infinity: none), strict clip box
+  ! (+-infinity: none), min_members >= 1, flags, reserved (0).  table(SPH_GROUPS_NCOL, max_groups).  80 bytes.
+  type, bind(C) :: sph_groups_desc
+    real(c_double) :: link, rho_min
+    real(c_double) :: clip_lo(3), clip_hi(3)
+    integer(c_int64_t) :: min_members
+    integer(c_int32_t) :: flags, reserved
+  end type sph_groups_desc
 
   interface
     integer(c_int) function sph_abi_version() bind(C, name='sph_abi_version')
@@ -534,6 +546,24 @@ module sph_hip_binding
       import :: c_int, c_int64_t, c_ptr
       type(c_ptr), value :: ctx, d_sums, d_phi
       integer(c_int64_t), value :: src_offset, n_phi
+    end function
+
+    ! ---- friends-of-friends groups: host_labels (int32, sph_count of them, the download order) / host_table
+    !      (SPH_GROUPS_NCOL doubles per group, max_groups groups) are c_loc(...) or c_null_ptr; n_groups: the full count
+    integer(c_int) function sph_groups(ctx, d, host_labels, n_labels, host_table, max_groups, n_groups) &
+        bind(C, name='sph_groups')
+      import :: c_int, c_int64_t, c_ptr, sph_groups_desc
+      type(c_ptr), value :: ctx, host_labels, host_table
+      type(sph_groups_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_labels, max_groups
+      integer(c_int64_t), intent(out) :: n_groups
+    end function
+    integer(c_int) function sph_groups_dev(ctx, d, d_labels, n_labels, d_table, max_groups, d_n_groups) &
+        bind(C, name='sph_groups_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_groups_desc
+      type(c_ptr), value :: ctx, d_labels, d_table, d_n_groups
+      type(sph_groups_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_labels, max_groups
     end function
   end interface
 
