@@ -615,6 +615,64 @@ int sph_groups(sph_ctx *ctx, const sph_groups_desc *d, int32_t *host_labels, int
 int sph_groups_dev(sph_ctx *ctx, const sph_groups_desc *d, int32_t *d_labels, int64_t n_labels, double *d_table,
                    int64_t max_groups, int64_t *d_n_groups);
 
+/* ---- SPH gradients: the gradient of up to four per-particle fields at every owned gas particle (vorticity, divergence,
+ *      gradients of rho, u, P or any caller's array), in the standard difference form or the matrix-corrected form -------
+ * Kernel   the renders' analytic cubic spline with the DOUBLE-precision pi (not the simulation's REAL(4)-pi table):
+ *          W(r, h) = sigma w(q), q = r / h, sigma = 1 / (pi h^3), w = 1 - 1.5 q^2 + 0.75 q^3 (q <= 1), 0.25 (2 - q)^3
+ *          (1 < q <= 2), 0 beyond; F(r, h) = -W'(r) / r = (sigma / h^2) f(q), f = 3 - 2.25 q (q <= 1), 0.75 (2 - q)^2 / q
+ *          (1 < q <= 2), 0 beyond (finite at q = 0).
+ * h        every target i gathers with its own h_i: desc.h when desc.h > 0, else each particle's own h (SPH_F_H on a
+ *          variable-h context, params.h on a fixed-h one) -- the renders' h rule.
+ * Targets  the owned gas (original ids < n_owned) with finite positions strictly inside clip_lo < x < clip_hi on every axis
+ *          (-INFINITY / +INFINITY: no clip).
+ * Sources  every gas slot with a finite position, owned AND ghost, no clip; sinks are neither.  A rank whose ghost layer
+ *          covers 2 h of its targets gets the rows of the union to rounding.
+ * Sums     for target i and every source j with d2 <= 4 h_i^2 (d2 = (dx dx + dy dy) + dz dz, x_ij = x_i - x_j):
+ *          rho~_i = sum_j m_j W(r_ij, h_i) (j = i included: the SPH density of this kernel's gather),
+ *          C_i = sum_j m_j F x_ij x_ij^T (symmetric, 6 sums), b_i^(k) = sum_j m_j F (A_i^(k) - A_j^(k)) x_ij per field k;
+ *          j = i and coincident particles (d2 == 0) add nothing to C or b.  No fused multiply-adds.
+ * Forms    standard (default): grad A_i = b_i / rho~_i (Monaghan's difference form).  SPH_GRAD_CORRECTED: grad A_i =
+ *          adj(C_i) b_i / det C_i, exact for linear A on any particle set.  A target is singular in the corrected form when
+ *          !(det C_i > 1e-6 (tr C_i / 3)^3) (fewer than three non-coplanar neighbours: an isolated particle, a planar set):
+ *          its gradients are NaN, its rho~ is written, and it is counted.
+ * Fields   fields[k], k < n_fields <= SPH_GRAD_MAX_FIELDS, all in one neighbour walk (velocity: three fields in one call):
+ *          an SPH_F_* id, read as sph_download_field reads it (SPH_ERR_STATE exactly when that call would refuse the field
+ *          as stale), or SPH_GRAD_VALUES: row k of values, values[k * n + id], n = sph_count, in sph_download_field order
+ *          with ghosts -- host memory for sph_gradients, device memory for _dev.
+ * Output   out[(3 k + a) n + id], a = x, y, z, n_out == 3 n_fields sph_count: every gradient component is a contiguous row
+ *          in download order (render values for sph_render_field).  Rows of non-targets are NaN.  rho_out (optional,
+ *          sph_count doubles, download order): rho~, NaN for non-targets.
+ * Counts   host form: optional *n_targets and *n_singular; device form: optional int64 d_counts[2] (targets, singular).
+ * Order    every target adds its sources over its stencil cells in increasing cell key and within a cell in increasing
+ *          original id.  The cell edge E is a function of the source set and desc.h only (2 h (1 + 1e-6) with one h; with
+ *          per-particle h, 2 h_ref (1 + 1e-6), h_ref the upper edge of the quarter octave holding the median source h), so a
+ *          target's row depends only on the sources and the target: bitwise the same over repeated calls, the context's
+ *          slot order (a fresh upload, or after sph_density re-sorts), dense or SPH_FLAG_HASHED_GRID grids, any clip box
+ *          that contains the target, and an owned / ghost split of the same upload (sph_set_owned).  No float atomics.
+ * cost     host form: one synchronisation, then the copies out.  Device form: ordered on the context's stream, no
+ *          synchronisation; a bad target h shows as d_counts[0] == -1 with NaN rows.  No state, field, statistic (other than
+ *          device_bytes: the render's scratch), flag, grid, list or dt of the context changes; a run that calls
+ *          sph_gradients after every step is bitwise the run without it.
+ * SPH_ERR_ARG: null descriptor or output, n_fields outside 1 .. SPH_GRAD_MAX_FIELDS, a bad field id, values missing while
+ * a field is SPH_GRAD_VALUES or given while none is, n_out != 3 n_fields sph_count, h < 0 or NaN, a NaN clip, unknown
+ * flags, reserved != 0.  SPH_ERR_STATE: a stale field; params.h <= 0 on a fixed-h context with desc.h == 0; host form, a
+ * target h <= 0 or non-finite.  An empty target set gives 0 targets and all-NaN output. */
+#define SPH_GRAD_CORRECTED   1       /* adj(C) b / det C                                                         */
+#define SPH_GRAD_MAX_FIELDS  4
+#define SPH_GRAD_VALUES    (-1)      /* fields[k]: row k of values                                               */
+typedef struct sph_gradients_desc {
+    double  clip_lo[3], clip_hi[3];        /* strict target clip box; -INFINITY / +INFINITY = none */
+    double  h;                             /* > 0: one h for every target; 0: each particle's own h */
+    int32_t fields[SPH_GRAD_MAX_FIELDS];   /* SPH_F_* or SPH_GRAD_VALUES (row k of values)          */
+    int32_t n_fields;                      /* 1 .. SPH_GRAD_MAX_FIELDS                              */
+    int32_t flags;                         /* SPH_GRAD_CORRECTED                                    */
+    int32_t reserved[2];                   /* must be 0                                             */
+} sph_gradients_desc;                      /* 88 bytes */
+int sph_gradients(sph_ctx *ctx, const sph_gradients_desc *d, const double *values, double *host_out, int64_t n_out,
+                  double *host_rho, int64_t *n_targets, int64_t *n_singular);
+int sph_gradients_dev(sph_ctx *ctx, const sph_gradients_desc *d, const double *d_values, double *d_out, int64_t n_out,
+                      double *d_rho, int64_t *d_counts);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too

@@ -46,6 +46,7 @@ SYMBOLS = [
     "sph_profile", "sph_profile_dev", "sph_profile_finish",
     "sph_energy", "sph_energy_dev",
     "sph_groups", "sph_groups_dev",
+    "sph_gradients", "sph_gradients_dev",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
@@ -70,6 +71,9 @@ GROUPS_NCOL = 21
 # sph_groups' table columns (include/summersph.h, "Table")
 GROUPS_COLUMNS = ["N", "M", "x", "y", "z", "vx", "vy", "vz", "r_rms", "r_max", "Sx", "Sy", "Sz", "K_int", "U", "rho_max",
                   "x_dense", "y_dense", "z_dense", "id_dense", "id_min"]
+GRAD_CORRECTED = 1
+GRAD_MAX_FIELDS = 4
+GRAD_VALUES = -1
 PROFILE_SUMS = ["N", "M", "mR", "mz", "mzz", "mvR", "mvphi", "mvz", "mvRvR", "mvphivphi", "mvzvz", "mu", "malpha", "mh",
                 "mlx", "mly", "mlz", "mex", "mey", "mez"]
 
@@ -143,6 +147,48 @@ def groups_table(table: np.ndarray) -> np.ndarray:
     """(n, GROUPS_NCOL) float64 -> a structured array of n records with the GROUPS_COLUMNS names"""
     t = np.ascontiguousarray(table, dtype=np.float64).reshape(-1, GROUPS_NCOL)
     return t.view([(c, np.float64) for c in GROUPS_COLUMNS]).reshape(-1)
+
+
+class GradientsDesc(C.Structure):
+    """sph_gradients_desc (include/summersph.h): strict target clip box, h (0: each particle's own), field ids (SPH_F_* or
+    GRAD_VALUES), n_fields, flags (GRAD_CORRECTED), reserved"""
+    _fields_ = [("clip_lo", C.c_double * 3), ("clip_hi", C.c_double * 3), ("h", C.c_double),
+                ("fields", C.c_int32 * GRAD_MAX_FIELDS), ("n_fields", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+def gradients_desc(fields=("vx", "vy", "vz"), corrected=True, h=None, clip=None) -> GradientsDesc:
+    """The descriptor of Context.gradients' arguments (fields: SPH_F_* names or ids, or GRAD_VALUES; see there)."""
+    fields = list(fields)
+    if not 1 <= len(fields) <= GRAD_MAX_FIELDS:
+        raise ValueError(f"gradients: 1 .. {GRAD_MAX_FIELDS} fields, not {len(fields)}")
+    d = GradientsDesc()
+    d.fields[:] = [FIELDS.index(f) if isinstance(f, str) else int(f) for f in fields] + [0] * (GRAD_MAX_FIELDS - len(fields))
+    d.n_fields = len(fields)
+    d.flags = GRAD_CORRECTED if corrected else 0
+    d.h = 0.0 if h is None else float(h)
+    lo, hi = ((-np.inf,) * 3, (np.inf,) * 3) if clip is None else clip
+    d.clip_lo[:] = [float(v) for v in lo]
+    d.clip_hi[:] = [float(v) for v in hi]
+    return d
+
+
+def velocity_derivatives(grad):
+    """(3, 3, n) gradients of vx, vy, vz (Context.gradients with fields ('vx', 'vy', 'vz')): grad[k, a] = d v_k / d x_a ->
+    dict divv = div v, curl = (3, n) curl v, curl_mag = |curl v|.  numpy or torch, as given."""
+    g = grad
+    divv = (g[0, 0] + g[1, 1]) + g[2, 2]
+    cx = g[2, 1] - g[1, 2]
+    cy = g[0, 2] - g[2, 0]
+    cz = g[1, 0] - g[0, 1]
+    if isinstance(g, np.ndarray):
+        curl = np.stack([cx, cy, cz])
+        mag = np.sqrt((cx * cx + cy * cy) + cz * cz)
+    else:
+        import torch
+        curl = torch.stack([cx, cy, cz])
+        mag = torch.sqrt((cx * cx + cy * cy) + cz * cz)
+    return {"divv": divv, "curl": curl, "curl_mag": mag}
 
 
 def profile_desc(r_min, r_max, n_r, n_phi=1, log=False, centre=None, sink=None, normal=(0.0, 0.0, 1.0),
@@ -312,6 +358,10 @@ def load():
                                C.POINTER(C.c_int64)]
     lib.sph_groups_dev.argtypes = [C.c_void_p, C.POINTER(GroupsDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                    C.c_void_p]
+    lib.sph_gradients.argtypes = [C.c_void_p, C.POINTER(GradientsDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.sph_gradients_dev.argtypes = [C.c_void_p, C.POINTER(GradientsDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_void_p]
     _lib = lib
     return lib
 
@@ -820,6 +870,59 @@ class Context:
                                      None if tab is None else tab.ctypes.data, mg, C.byref(ng)))
         ng = int(ng.value)
         return lab, (None if tab is None else groups_table(tab[:min(ng, mg)])), ng
+
+    # ---- SPH gradients (sph_gradients) ------------------------------------------------------------
+    def gradients(self, fields=("vx", "vy", "vz"), values=None, corrected=True, h=None, clip=None, rho=False, device=False):
+        """SPH gradients at the owned gas inside the strict clip box ((lo xyz, hi xyz) or None) (include/summersph.h,
+        sph_gradients): corrected=True: adj(C) b / det C (exact for linear fields; NaN at singular targets), False: the
+        standard difference form b / rho~.  fields: up to four SPH_F_* names or ids, or GRAD_VALUES for row k of values,
+        an (n_rows, sph_count) array in the upload order (float64 numpy; device=True: a contiguous float64 torch tensor on
+        the context's GPU).  h: None = each particle's own h, else one h for every target.  Returns (grad, rho~, counts):
+        grad an (n_fields, 3, n) array (NaN rows for non-targets), rho~ (n,) or None (rho=False), counts = (n_targets,
+        n_singular).  device=True: grad and rho~ are torch tensors on the context's GPU (sph_gradients_dev).  The
+        descriptor used is left in self.gradients_desc."""
+        d = gradients_desc(fields, corrected, h, clip)
+        n, nf = self.n, d.n_fields
+        n_out = 3 * nf * n
+        self.gradients_desc = d
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if values is not None:
+                if not (isinstance(values, torch.Tensor) and values.dtype == torch.float64 and values.is_contiguous()
+                        and values.device == dev):
+                    raise ValueError("gradients: device values must be a contiguous float64 tensor on the context's GPU")
+                if values.numel() < nf * n and any(d.fields[k] == GRAD_VALUES for k in range(nf)):
+                    raise ValueError(f"gradients: values need {nf} rows of {n}")
+            out = torch.empty((nf, 3, n), dtype=torch.float64, device=dev)
+            r = torch.empty(n, dtype=torch.float64, device=dev) if rho else None
+            cnt = torch.empty(2, dtype=torch.int64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
+            self._ck(self.lib.sph_gradients_dev(self._h, C.byref(d), None if values is None else C.c_void_p(values.data_ptr()),
+                                                C.c_void_p(out.data_ptr()), n_out, None if r is None else C.c_void_p(r.data_ptr()),
+                                                C.c_void_p(cnt.data_ptr())))
+            st = self.stream()                                    # torch's later work waits for the gradients
+            if st:
+                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
+            else:
+                torch.cuda.synchronize(dev)
+            c = cnt.cpu().tolist()
+            return out, r, (int(c[0]), int(c[1]))
+        v = None
+        if values is not None:
+            v = np.ascontiguousarray(values, dtype=np.float64)
+            if v.ndim == 1:
+                v = v.reshape(1, -1)
+            if v.shape[1] != n:
+                raise ValueError(f"gradients: values rows of {v.shape[1]} for {n} particles")
+            if v.shape[0] < nf:                                   # row k belongs to field k: pad the rows no field reads
+                v = np.concatenate([v, np.zeros((nf - v.shape[0], n))])
+        out = np.empty((nf, 3, n), dtype=np.float64)
+        r = np.empty(n, dtype=np.float64) if rho else None
+        nt, ns = C.c_int64(0), C.c_int64(0)
+        self._ck(self.lib.sph_gradients(self._h, C.byref(d), None if v is None else v.ctypes.data, out.ctypes.data, n_out,
+                                        None if r is None else r.ctypes.data, C.byref(nt), C.byref(ns)))
+        return out, r, (int(nt.value), int(ns.value))
 
     # ---- diagnostics ---------------------------------------------------------------------
     def stats(self) -> Stats:

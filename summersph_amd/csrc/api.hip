@@ -1276,6 +1276,25 @@ int sph_groups_dev(sph_ctx *c, const sph_groups_desc *d, int32_t *d_labels, int6
     return groups_run(c, d, d_labels, n_labels, d_table, max_groups, d_n_groups, false, field_ready);
 }
 
+int sph_gradients(sph_ctx *c, const sph_gradients_desc *d, const double *values, double *host_out, int64_t n_out,
+                  double *host_rho, int64_t *n_targets, int64_t *n_singular) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    int64_t counts[2] = {0, 0};
+    const int st = gradients_run(c, d, values, host_out, n_out, host_rho, counts, true, field_ready);
+    if (st != SPH_OK) return st;
+    if (n_targets) *n_targets = counts[0];
+    if (n_singular) *n_singular = counts[1];
+    return SPH_OK;
+}
+
+int sph_gradients_dev(sph_ctx *c, const sph_gradients_desc *d, const double *d_values, double *d_out, int64_t n_out,
+                      double *d_rho, int64_t *d_counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return gradients_run(c, d, d_values, d_out, n_out, d_rho, d_counts, false, field_ready);
+}
+
 int sph_synchronize(sph_ctx *c) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);

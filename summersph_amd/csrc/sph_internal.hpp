@@ -357,5 +357,9 @@ int energy_sums(sph_ctx *c, int64_t src_offset, double *sums, double *phi, int64
 // form; ready = sph_download_field's rule
 int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_labels, double *table, int64_t max_groups,
                int64_t *n_groups, bool host, bool (*ready)(const sph_ctx *, int));
+// SPH gradients (gradients.hip): host form (values / out / rho host memory, counts[2] host, one synchronisation) or device
+// form (counts[2] device memory or null); ready = sph_download_field's rule
+int gradients_run(sph_ctx *c, const sph_gradients_desc *d, const double *values, double *out, int64_t n_out, double *rho_out,
+                  int64_t *counts, bool host, bool (*ready)(const sph_ctx *, int));
 
 }  // namespace sph

@@ -40,6 +40,8 @@ module sph_hip_binding
   public :: sph_energy, sph_energy_dev, SPH_ENERGY_NSUM
   ! friends-of-friends groups (clumps of the owned gas: labels per particle and a table per group)
   public :: sph_groups_desc, sph_groups, sph_groups_dev, SPH_GROUPS_LINK_H, SPH_GROUPS_NCOL
+  ! SPH gradients (standard or matrix-corrected) of up to four fields at the owned gas
+  public :: sph_gradients_desc, sph_gradients, sph_gradients_dev, SPH_GRAD_CORRECTED, SPH_GRAD_MAX_FIELDS, SPH_GRAD_VALUES
   public :: c_message
 
   integer(c_int), parameter :: SPH_OK = 0
@@ -123,6 +125,18 @@ module sph_hip_binding
     integer(c_int64_t) :: min_members
     integer(c_int32_t) :: flags, reserved
   end type sph_groups_desc
+
+  ! sph_gradients: strict target clip box (+-infinity: none), h (> 0: one h for all; 0: each particle's own), fields
+  ! (SPH_F_* or SPH_GRAD_VALUES: row k of values), n_fields 1 .. 4, flags (SPH_GRAD_CORRECTED), reserved (0).  out holds
+  ! out(id, a, k) in Fortran order: (sph_count, 3, n_fields).  88 bytes.
+  integer(c_int32_t), parameter :: SPH_GRAD_CORRECTED = 1, SPH_GRAD_MAX_FIELDS = 4, SPH_GRAD_VALUES = -1
+  type, bind(C) :: sph_gradients_desc
+    real(c_double) :: clip_lo(3), clip_hi(3)
+    real(c_double) :: h
+    integer(c_int32_t) :: fields(SPH_GRAD_MAX_FIELDS)
+    integer(c_int32_t) :: n_fields, flags
+    integer(c_int32_t) :: reserved(2)
+  end type sph_gradients_desc
 
   interface
     integer(c_int) function sph_abi_version() bind(C, name='sph_abi_version')
@@ -564,6 +578,23 @@ module sph_hip_binding
       type(c_ptr), value :: ctx, d_labels, d_table, d_n_groups
       type(sph_groups_desc), intent(in) :: d
       integer(c_int64_t), value :: n_labels, max_groups
+    end function
+    ! ---- SPH gradients: values (n_fields rows of sph_count doubles, download order, or c_null_ptr), host_out
+    !      (3 n_fields sph_count doubles), host_rho (sph_count doubles or c_null_ptr); n_targets, n_singular: the counts
+    integer(c_int) function sph_gradients(ctx, d, values, host_out, n_out, host_rho, n_targets, n_singular) &
+        bind(C, name='sph_gradients')
+      import :: c_int, c_int64_t, c_ptr, sph_gradients_desc
+      type(c_ptr), value :: ctx, values, host_out, host_rho
+      type(sph_gradients_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_out
+      integer(c_int64_t), intent(out) :: n_targets, n_singular
+    end function
+    integer(c_int) function sph_gradients_dev(ctx, d, d_values, d_out, n_out, d_rho, d_counts) &
+        bind(C, name='sph_gradients_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_gradients_desc
+      type(c_ptr), value :: ctx, d_values, d_out, d_rho, d_counts
+      type(sph_gradients_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_out
     end function
   end interface
 
