@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "pair_common.hpp"
+#include "reduce_common.hpp"
 
 namespace sph {
 
@@ -186,11 +187,6 @@ __global__ void acc_partials_final(const double *__restrict__ part, int nb, doub
     out[threadIdx.x] = r;
 }
 
-__device__ __forceinline__ double wave_sumd(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // per sink: sum of m, m x, m v over its accreted particles (two stages, fixed order)
 __global__ __launch_bounds__(AB) void acc_sums_partial(int64_t n, int k, const unsigned long long *__restrict__ accmask,
                                                        const double4 *__restrict__ drec, const double *__restrict__ vx,
@@ -206,7 +202,7 @@ __global__ __launch_bounds__(AB) void acc_sums_partial(int64_t n, int k, const u
         }
     }
     for (int q = 0; q < 7; q++) {
-        const double r = wave_sumd(v[q]);
+        const double r = wave_sum(v[q]);
         if ((threadIdx.x & 63) == 0) sm[q][threadIdx.x >> 6] = r;
     }
     __syncthreads();
@@ -253,15 +249,6 @@ __global__ __launch_bounds__(AB) void acc_compact(CompactArgs a, const int32_t *
 
 }  // namespace
 
-#define AC_CHECK(expr)                                                      \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) {                                             \
-            c->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return SPH_ERR_HIP;                                             \
-        }                                                                   \
-    } while (0)
-
 __global__ void sink_cull(int ns, double bound, double *__restrict__ sink, double *__restrict__ srad, int32_t *__restrict__ ns_out);
 int sinks_cull(sph_ctx *c);
 
@@ -286,13 +273,13 @@ int accrete_and_cull(sph_ctx *c, int64_t *removed, int32_t *d_keep_out) {
     // tree of the last evaluation (same positions, same root box, same key), or computed and sorted here (0.2 ms at 1e6)
     if (c->path_keys_valid) {
     } else if (c->gravity && c->tree_valid && !c->gx_src && c->g_keys_alt && c->g_vals_alt) {
-        AC_CHECK(hipMemcpyAsync(c->mkeys_alt, c->g_keys_alt, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
-        AC_CHECK(hipMemcpyAsync(c->mvals_alt, c->g_vals_alt, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+        SPH_HIP(hipMemcpyAsync(c->mkeys_alt, c->g_keys_alt, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+        SPH_HIP(hipMemcpyAsync(c->mvals_alt, c->g_vals_alt, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
         c->path_keys_valid = true;
     } else {
         acc_keys<<<dim3(gb), dim3(AB), 0, c->stream>>>(rb, drec, n, c->mkeys, c->mvals);
         size_t tmp = c->msort_tmp_bytes;
-        AC_CHECK(rocprim::radix_sort_pairs(c->msort_tmp, tmp, c->mkeys, c->mkeys_alt, c->mvals, c->mvals_alt, (size_t)n, 0u, 63u, c->stream));
+        SPH_HIP(rocprim::radix_sort_pairs(c->msort_tmp, tmp, c->mkeys, c->mkeys_alt, c->mvals, c->mvals_alt, (size_t)n, 0u, 63u, c->stream));
         c->path_keys_valid = true;
     }
     int32_t *keep = reinterpret_cast<int32_t *>(c->keys);          // the cell-key buffers are free between grid builds
@@ -300,32 +287,32 @@ int accrete_and_cull(sph_ctx *c, int64_t *removed, int32_t *d_keep_out) {
     unsigned long long *accmask = reinterpret_cast<unsigned long long *>(c->scratch);
     acc_mark<<<dim3(gb), dim3(AB), 0, c->stream>>>(rb, c->mkeys_alt, c->mvals_alt, n, drec, c->orig, c->sink, c->sink_radius, c->ns,
                                                    c->variable ? 1 : 0, c->p.bounding_size, keep, accmask);
-    AC_CHECK(hipGetLastError());
-    if (d_keep_out) AC_CHECK(hipMemcpyAsync(d_keep_out, keep, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+    SPH_HIP(hipGetLastError());
+    if (d_keep_out) SPH_HIP(hipMemcpyAsync(d_keep_out, keep, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
     {
         const int nb = (int)std::min<int64_t>((n + AB - 1) / AB, 256);
         for (int k = 0; k < c->ns; k++) {
             acc_sums_partial<<<dim3(nb), dim3(AB), 0, c->stream>>>(n, k, accmask, drec, c->f[SPH_F_VX], c->f[SPH_F_VY], c->f[SPH_F_VZ], c->sink_part);
             acc_sink_update<<<dim3(1), dim3(64), 0, c->stream>>>(k, c->ns, c->sink_part, nb, c->sink);      // no-op without a massive sink
         }
-        AC_CHECK(hipGetLastError());
+        SPH_HIP(hipGetLastError());
     }
     // exclusive scan of keep[] over original ids -> new ids
     size_t sb = 0;
-    AC_CHECK(rocprim::exclusive_scan(nullptr, sb, keep, pos, 0, (size_t)n, rocprim::plus<int32_t>(), c->stream));
+    SPH_HIP(rocprim::exclusive_scan(nullptr, sb, keep, pos, 0, (size_t)n, rocprim::plus<int32_t>(), c->stream));
     if (sb > c->sort_tmp_bytes) { c->err = "accrete: scan scratch too small"; return SPH_ERR_NOMEM; }
-    AC_CHECK(rocprim::exclusive_scan(c->sort_tmp, sb, keep, pos, 0, (size_t)n, rocprim::plus<int32_t>(), c->stream));
+    SPH_HIP(rocprim::exclusive_scan(c->sort_tmp, sb, keep, pos, 0, (size_t)n, rocprim::plus<int32_t>(), c->stream));
     // ONE read-back per call: how many particles stay (and, variable h, how many sinks: [V]'s check_bounds culls sinks too)
     if (c->variable && c->ns > 0) {
         sink_cull<<<dim3(1), dim3(64), 0, c->stream>>>(c->ns, c->p.bounding_size, c->sink, c->sink_radius, c->d_flags + 2);
-        AC_CHECK(hipGetLastError());
+        SPH_HIP(hipGetLastError());
     }
     int32_t *last = reinterpret_cast<int32_t *>(c->h_pinned + 300);
     last[2] = c->ns;
-    AC_CHECK(hipMemcpyAsync(&last[0], pos + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    AC_CHECK(hipMemcpyAsync(&last[1], keep + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (c->variable && c->ns > 0) AC_CHECK(hipMemcpyAsync(&last[2], c->d_flags + 2, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    AC_CHECK(hipStreamSynchronize(c->stream));
+    SPH_HIP(hipMemcpyAsync(&last[0], pos + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipMemcpyAsync(&last[1], keep + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (c->variable && c->ns > 0) SPH_HIP(hipMemcpyAsync(&last[2], c->d_flags + 2, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
     c->host_syncs++;
     if (last[2] != c->ns) { c->ns = last[2]; c->rates_valid = false; }
     const int64_t n_new = (int64_t)last[0] + last[1];
@@ -335,7 +322,7 @@ int accrete_and_cull(sph_ctx *c, int64_t *removed, int32_t *d_keep_out) {
     ca.nf = 9;
     if (c->variable) { ca.src[9] = c->f[SPH_F_H]; ca.dst[9] = c->f_alt[9]; ca.nf = 10; }
     acc_compact<<<dim3(gb), dim3(AB), 0, c->stream>>>(ca, keep, pos, c->inv, n);
-    AC_CHECK(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     for (int k = 0; k < 9; k++) std::swap(c->f[k], c->f_alt[k]);
     if (c->variable) std::swap(c->f[SPH_F_H], c->f_alt[9]);
     // the reference's pack ([F]:481,554) keeps the survivors' density, pressure, accelerations and rates of the last
@@ -350,12 +337,12 @@ int accrete_and_cull(sph_ctx *c, int64_t *removed, int32_t *d_keep_out) {
             acc_compact<<<dim3(gb), dim3(AB), 0, c->stream>>>(cd, keep, pos, c->inv, n);
             std::swap(c->f[k], c->scratch);
         }
-        AC_CHECK(hipGetLastError());
+        SPH_HIP(hipGetLastError());
     }
     c->n = n_new; c->n_slots = n_new; c->dead_below = 0;
     c->n_owned = n_new;
-    AC_CHECK(launch_iota(c, c->orig, n_new));
-    AC_CHECK(launch_iota(c, c->inv, n_new));
+    SPH_HIP(launch_iota(c, c->orig, n_new));
+    SPH_HIP(launch_iota(c, c->inv, n_new));
     c->grid_valid = c->rho_valid = c->eos_valid = c->rates_valid = c->tree_valid = c->order_valid = false;
     c->h_refresh_ok = false;
     c->path_keys_valid = false;
@@ -384,10 +371,10 @@ __global__ void sink_cull(int ns, double bound, double *__restrict__ sink, doubl
 int sinks_cull(sph_ctx *c) {
     if (!c->variable || c->ns == 0) return SPH_OK;
     sink_cull<<<dim3(1), dim3(64), 0, c->stream>>>(c->ns, c->p.bounding_size, c->sink, c->sink_radius, c->d_flags + 2);
-    AC_CHECK(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     int32_t ns_new = c->ns;
-    AC_CHECK(hipMemcpyAsync(&ns_new, c->d_flags + 2, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    AC_CHECK(hipStreamSynchronize(c->stream));
+    SPH_HIP(hipMemcpyAsync(&ns_new, c->d_flags + 2, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
     if (ns_new != c->ns) { c->ns = ns_new; c->rates_valid = false; }
     return SPH_OK;
 }
@@ -445,7 +432,7 @@ int sink_candidate(sph_ctx *c, double *d_cand) {
     if (!c->variable) { c->err = "sink creation: variable-h contexts only"; return SPH_ERR_STATE; }
     if (c->n > 0 && !c->order_valid) { c->err = "sink creation: needs the sorted order of the current positions"; return SPH_ERR_STATE; }
     const int32_t big = 0x7fffffff;
-    AC_CHECK(hipMemcpyAsync(c->d_flags + 3, &big, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    SPH_HIP(hipMemcpyAsync(c->d_flags + 3, &big, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     const unsigned gb = (unsigned)((std::max<int64_t>(c->n, 1) + AB - 1) / AB);
     const int32_t *num = c->numbers_set ? c->number : nullptr;
     sink_create_scan<<<dim3(gb), dim3(AB), 0, c->stream>>>(reinterpret_cast<const double4 *>(c->drec), c->f[SPH_F_H], c->orig, num, c->n,
@@ -453,7 +440,7 @@ int sink_candidate(sph_ctx *c, double *d_cand) {
     sink_create_fetch<<<dim3(gb), dim3(AB), 0, c->stream>>>(reinterpret_cast<const double4 *>(c->drec), c->f[SPH_F_H], c->f[SPH_F_VX],
                                                             c->f[SPH_F_VY], c->f[SPH_F_VZ], c->orig, num, c->n, (int32_t)c->n_owned,
                                                             c->d_flags + 3, d_cand);
-    AC_CHECK(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     return SPH_OK;
 }
 
@@ -461,10 +448,10 @@ int sink_candidate(sph_ctx *c, double *d_cand) {
 int sink_add_checked(sph_ctx *c, const double *d_cand, int32_t *created) {
     *created = 0;
     sink_create_apply<<<dim3(1), dim3(64), 0, c->stream>>>(d_cand, c->ns, c->sink, c->sink_radius, c->d_flags + 2);
-    AC_CHECK(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     int32_t flag = 0;
-    AC_CHECK(hipMemcpyAsync(&flag, c->d_flags + 2, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    AC_CHECK(hipStreamSynchronize(c->stream));
+    SPH_HIP(hipMemcpyAsync(&flag, c->d_flags + 2, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
     if (flag) { c->ns += 1; *created = 1; c->rates_valid = false; }
     return SPH_OK;
 }
@@ -492,14 +479,14 @@ int accrete_mark_ext(sph_ctx *c, int64_t src_off, double *d_partials) {
     rb.size = size;
     int32_t *keep = reinterpret_cast<int32_t *>(c->keys);
     unsigned long long *accmask = reinterpret_cast<unsigned long long *>(c->scratch);
-    AC_CHECK(hipMemsetAsync(keep, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1), c->stream));
-    AC_CHECK(hipMemsetAsync(accmask, 0, sizeof(unsigned long long) * (size_t)std::max<int64_t>(n, 1), c->stream));
-    AC_CHECK(hipMemsetAsync(d_partials, 0, sizeof(double) * 7 * MAX_SINKS, c->stream));
+    SPH_HIP(hipMemsetAsync(keep, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1), c->stream));
+    SPH_HIP(hipMemsetAsync(accmask, 0, sizeof(unsigned long long) * (size_t)std::max<int64_t>(n, 1), c->stream));
+    SPH_HIP(hipMemsetAsync(d_partials, 0, sizeof(double) * 7 * MAX_SINKS, c->stream));
     if (no > 0 && ng > 0)
         acc_mark_ext<<<dim3((unsigned)((ng + AB - 1) / AB)), dim3(AB), 0, c->stream>>>(
             rb, c->g_keys_alt, c->g_vals_alt, ng, src_off, no, reinterpret_cast<const double4 *>(c->drec), c->inv, c->sink,
             c->sink_radius, c->ns, c->variable ? 1 : 0, c->p.bounding_size, keep, accmask);
-    AC_CHECK(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     if (n > 0) {             // (all zero without a massive sink: nothing is marked then)
         const int nb = (int)std::min<int64_t>((n + AB - 1) / AB, 256);
         for (int k = 0; k < c->ns; k++) {
@@ -507,7 +494,7 @@ int accrete_mark_ext(sph_ctx *c, int64_t src_off, double *d_partials) {
                                                                    c->f[SPH_F_VX], c->f[SPH_F_VY], c->f[SPH_F_VZ], c->sink_part);
             acc_partials_final<<<dim3(1), dim3(64), 0, c->stream>>>(c->sink_part, nb, d_partials + (size_t)k * 7);
         }
-        AC_CHECK(hipGetLastError());
+        SPH_HIP(hipGetLastError());
     }
     c->acc_marked = true;
     return SPH_OK;
@@ -520,27 +507,27 @@ int accrete_apply_ext(sph_ctx *c, const double *d_all, int nranks, int stride, i
     const int64_t n = c->n, no = c->n_owned;
     if (c->ns > 0)
         acc_sink_update_ranks<<<dim3(1), dim3(64), 0, c->stream>>>(c->ns, d_all, nranks, stride, c->sink);
-    AC_CHECK(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     int32_t *keep = reinterpret_cast<int32_t *>(c->keys);
     int32_t *pos = reinterpret_cast<int32_t *>(c->keys_alt);
-    if (d_keep_out && no > 0) AC_CHECK(hipMemcpyAsync(d_keep_out, keep, sizeof(int32_t) * (size_t)no, hipMemcpyDeviceToDevice, c->stream));
+    if (d_keep_out && no > 0) SPH_HIP(hipMemcpyAsync(d_keep_out, keep, sizeof(int32_t) * (size_t)no, hipMemcpyDeviceToDevice, c->stream));
     int64_t n_new = 0;
     if (n > 0) {
         size_t sb = 0;
-        AC_CHECK(rocprim::exclusive_scan(nullptr, sb, keep, pos, 0, (size_t)n, rocprim::plus<int32_t>(), c->stream));
+        SPH_HIP(rocprim::exclusive_scan(nullptr, sb, keep, pos, 0, (size_t)n, rocprim::plus<int32_t>(), c->stream));
         if (sb > c->sort_tmp_bytes) { c->err = "accrete: scan scratch too small"; return SPH_ERR_NOMEM; }
-        AC_CHECK(rocprim::exclusive_scan(c->sort_tmp, sb, keep, pos, 0, (size_t)n, rocprim::plus<int32_t>(), c->stream));
+        SPH_HIP(rocprim::exclusive_scan(c->sort_tmp, sb, keep, pos, 0, (size_t)n, rocprim::plus<int32_t>(), c->stream));
         int32_t last[2];
-        AC_CHECK(hipMemcpyAsync(&last[0], pos + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        AC_CHECK(hipMemcpyAsync(&last[1], keep + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        AC_CHECK(hipStreamSynchronize(c->stream));
+        SPH_HIP(hipMemcpyAsync(&last[0], pos + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        SPH_HIP(hipMemcpyAsync(&last[1], keep + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        SPH_HIP(hipStreamSynchronize(c->stream));
         n_new = (int64_t)last[0] + last[1];
         CompactArgs ca{};
         for (int k = 0; k < 9; k++) { ca.src[k] = c->f[k]; ca.dst[k] = c->f_alt[k]; }
         ca.nf = 9;
         if (c->variable) { ca.src[9] = c->f[SPH_F_H]; ca.dst[9] = c->f_alt[9]; ca.nf = 10; }
         acc_compact<<<dim3((unsigned)((n + AB - 1) / AB)), dim3(AB), 0, c->stream>>>(ca, keep, pos, c->inv, n);
-        AC_CHECK(hipGetLastError());
+        SPH_HIP(hipGetLastError());
         for (int k = 0; k < 9; k++) std::swap(c->f[k], c->f_alt[k]);
         if (c->variable) std::swap(c->f[SPH_F_H], c->f_alt[9]);
     }
@@ -548,9 +535,9 @@ int accrete_apply_ext(sph_ctx *c, const double *d_all, int nranks, int stride, i
     *removed = no - n_new;                             // owned particles that left; the ghosts are dropped as well
     c->n = n_new; c->n_slots = n_new; c->dead_below = 0;
     c->n_owned = n_new;
-    AC_CHECK(launch_iota(c, c->orig, n_new));
-    AC_CHECK(launch_iota(c, c->inv, n_new));
-    AC_CHECK(hipStreamSynchronize(c->stream));
+    SPH_HIP(launch_iota(c, c->orig, n_new));
+    SPH_HIP(launch_iota(c, c->inv, n_new));
+    SPH_HIP(hipStreamSynchronize(c->stream));
     c->grid_valid = c->rho_valid = c->eos_valid = c->rates_valid = c->tree_valid = c->order_valid = false;
     return sinks_cull(c);                              // [V]:610-613; the sinks are replicated: every rank drops the same ones
 }

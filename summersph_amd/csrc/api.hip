@@ -14,21 +14,6 @@ using namespace sph;
 
 namespace {
 
-#define API_HIP(expr)                                                       \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) {                                             \
-            c->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return SPH_ERR_HIP;                                             \
-        }                                                                   \
-    } while (0)
-
-#define API_TRY(expr)                          \
-    do {                                       \
-        int _s = (expr);                       \
-        if (_s != SPH_OK) return _s;           \
-    } while (0)
-
 struct DeviceGuard {
     int prev = -1;
     explicit DeviceGuard(int dev) { (void)hipGetDevice(&prev); if (prev != dev) (void)hipSetDevice(dev); else prev = -1; }
@@ -59,49 +44,49 @@ int ensure_capacity(sph_ctx *c, int64_t n) {
     if (std::max(n, c->reserve) <= c->cap) return SPH_OK;
     free_particle_arrays(c);
     const int64_t cap = std::max<int64_t>(n + n / 16 + 64, c->reserve);
-    for (auto &p : c->f) API_TRY(ctx_alloc(c, &p, (size_t)cap, "state"));
-    for (auto &p : c->f_alt) API_TRY(ctx_alloc(c, &p, (size_t)cap, "state (alt)"));
-    API_TRY(ctx_alloc(c, &c->orig, (size_t)cap, "ids"));
-    API_TRY(ctx_alloc(c, &c->orig_alt, (size_t)cap, "ids (alt)"));
-    API_TRY(ctx_alloc(c, &c->inv, (size_t)cap, "ids (inverse)"));
-    API_TRY(ctx_alloc(c, &c->number, (size_t)cap, "particle numbers"));
-    API_TRY(ctx_alloc(c, &c->scratch, (size_t)cap, "scratch"));
-    API_TRY(ctx_alloc(c, &c->drec, (size_t)cap * 4, "density records"));
-    API_TRY(ctx_alloc(c, &c->frec, (size_t)cap * FREC, "force records"));
-    API_TRY(ctx_alloc(c, &c->keys, (size_t)cap, "keys"));
-    API_TRY(ctx_alloc(c, &c->keys_alt, (size_t)cap, "keys (alt)"));
-    API_TRY(ctx_alloc(c, &c->vals, (size_t)cap, "vals"));
-    API_TRY(ctx_alloc(c, &c->vals_alt, (size_t)cap, "vals (alt)"));
+    for (auto &p : c->f) SPH_TRY(ctx_alloc(c, &p, (size_t)cap, "state"));
+    for (auto &p : c->f_alt) SPH_TRY(ctx_alloc(c, &p, (size_t)cap, "state (alt)"));
+    SPH_TRY(ctx_alloc(c, &c->orig, (size_t)cap, "ids"));
+    SPH_TRY(ctx_alloc(c, &c->orig_alt, (size_t)cap, "ids (alt)"));
+    SPH_TRY(ctx_alloc(c, &c->inv, (size_t)cap, "ids (inverse)"));
+    SPH_TRY(ctx_alloc(c, &c->number, (size_t)cap, "particle numbers"));
+    SPH_TRY(ctx_alloc(c, &c->scratch, (size_t)cap, "scratch"));
+    SPH_TRY(ctx_alloc(c, &c->drec, (size_t)cap * 4, "density records"));
+    SPH_TRY(ctx_alloc(c, &c->frec, (size_t)cap * FREC, "force records"));
+    SPH_TRY(ctx_alloc(c, &c->keys, (size_t)cap, "keys"));
+    SPH_TRY(ctx_alloc(c, &c->keys_alt, (size_t)cap, "keys (alt)"));
+    SPH_TRY(ctx_alloc(c, &c->vals, (size_t)cap, "vals"));
+    SPH_TRY(ctx_alloc(c, &c->vals_alt, (size_t)cap, "vals (alt)"));
     size_t tmp = 0;
-    API_HIP(grid_sort_tmp_bytes(cap, &tmp));
+    SPH_HIP(grid_sort_tmp_bytes(cap, &tmp));
     c->sort_tmp_bytes = tmp;
-    API_TRY(ctx_alloc_bytes(c, &c->sort_tmp, tmp ? tmp : 1, "sort scratch"));
+    SPH_TRY(ctx_alloc_bytes(c, &c->sort_tmp, tmp ? tmp : 1, "sort scratch"));
     c->nl_waves_cap = (cap + 63) / 64;
     c->nl_cap = 96;   // grows on demand (nlist_build); the tiled fixed-h build writes 16-bit entries (tile_common.hpp)
-    API_TRY(ctx_alloc(c, &c->nlist, (size_t)c->nl_waves_cap * c->nl_cap * (c->tiled ? 32 : 64), "neighbour list"));
-    API_TRY(ctx_alloc(c, &c->ncount, (size_t)cap, "neighbour counts"));
-    API_TRY(ctx_alloc(c, &c->wave_max, (size_t)c->nl_waves_cap, "wave max"));
-    API_TRY(ctx_alloc(c, &c->wave_class, (size_t)c->nl_waves_cap, "wave classes"));
-    API_TRY(ctx_alloc(c, &c->plan_d, (size_t)(cap / 256 + 2) * 8, "tile plans (density)"));
-    API_TRY(ctx_alloc(c, &c->plan_f, (size_t)(cap / 256 + 2) * 8, "tile plans (forces)"));
-    API_TRY(ctx_alloc(c, &c->plan_h, (size_t)(cap / 256 + 2) * 16, "tile plans (forces, half groups)"));
-    API_TRY(ctx_alloc(c, &c->deal, 2 * ((size_t)cap + 256), "dealing order"));
+    SPH_TRY(ctx_alloc(c, &c->nlist, (size_t)c->nl_waves_cap * c->nl_cap * (c->tiled ? 32 : 64), "neighbour list"));
+    SPH_TRY(ctx_alloc(c, &c->ncount, (size_t)cap, "neighbour counts"));
+    SPH_TRY(ctx_alloc(c, &c->wave_max, (size_t)c->nl_waves_cap, "wave max"));
+    SPH_TRY(ctx_alloc(c, &c->wave_class, (size_t)c->nl_waves_cap, "wave classes"));
+    SPH_TRY(ctx_alloc(c, &c->plan_d, (size_t)(cap / 256 + 2) * 8, "tile plans (density)"));
+    SPH_TRY(ctx_alloc(c, &c->plan_f, (size_t)(cap / 256 + 2) * 8, "tile plans (forces)"));
+    SPH_TRY(ctx_alloc(c, &c->plan_h, (size_t)(cap / 256 + 2) * 16, "tile plans (forces, half groups)"));
+    SPH_TRY(ctx_alloc(c, &c->deal, 2 * ((size_t)cap + 256), "dealing order"));
     if (c->variable) {
-        API_TRY(ctx_alloc(c, &c->prec, (size_t)cap * 4, "position+h records"));
-        API_TRY(ctx_alloc(c, &c->lrec, (size_t)cap * 4, "leaf boxes"));
-        API_TRY(ctx_alloc(c, &c->h_new, (size_t)cap, "h scratch"));
-        API_TRY(ctx_alloc(c, &c->ntail, (size_t)cap, "margin counts"));
-        API_TRY(ctx_alloc(c, &c->leaf_half, (size_t)cap, "leaf half edges"));
+        SPH_TRY(ctx_alloc(c, &c->prec, (size_t)cap * 4, "position+h records"));
+        SPH_TRY(ctx_alloc(c, &c->lrec, (size_t)cap * 4, "leaf boxes"));
+        SPH_TRY(ctx_alloc(c, &c->h_new, (size_t)cap, "h scratch"));
+        SPH_TRY(ctx_alloc(c, &c->ntail, (size_t)cap, "margin counts"));
+        SPH_TRY(ctx_alloc(c, &c->leaf_half, (size_t)cap, "leaf half edges"));
     }
     {   // octree path keys: leaf boxes (variable h), self-gravity tree, accretion
-        API_TRY(ctx_alloc(c, &c->mkeys, (size_t)cap, "octree keys"));
-        API_TRY(ctx_alloc(c, &c->mkeys_alt, (size_t)cap, "octree keys (alt)"));
-        API_TRY(ctx_alloc(c, &c->mvals, (size_t)cap, "octree vals"));
-        API_TRY(ctx_alloc(c, &c->mvals_alt, (size_t)cap, "octree vals (alt)"));
+        SPH_TRY(ctx_alloc(c, &c->mkeys, (size_t)cap, "octree keys"));
+        SPH_TRY(ctx_alloc(c, &c->mkeys_alt, (size_t)cap, "octree keys (alt)"));
+        SPH_TRY(ctx_alloc(c, &c->mvals, (size_t)cap, "octree vals"));
+        SPH_TRY(ctx_alloc(c, &c->mvals_alt, (size_t)cap, "octree vals (alt)"));
         size_t mt = 0;
-        API_HIP(varh_sort_tmp_bytes(cap, &mt));
+        SPH_HIP(varh_sort_tmp_bytes(cap, &mt));
         c->msort_tmp_bytes = mt;
-        API_TRY(ctx_alloc_bytes(c, &c->msort_tmp, mt ? mt : 1, "octree sort scratch"));
+        SPH_TRY(ctx_alloc_bytes(c, &c->msort_tmp, mt ? mt : 1, "octree sort scratch"));
     }
     c->cap = cap;
     return SPH_OK;
@@ -191,50 +176,50 @@ int do_density(sph_ctx *c) {
         // the leaf cells stand; only what depends on h is redone -- and a self-gravity tree stays valid
         // growth of h against the lengths the list was built with -- known only when sph_update_h produced the new h (its
         // swap left the old lengths in h_new); after an upload / scatter of h the list is built, never re-flagged
-        API_TRY(varh_h_stats(c, c->h_new_is_build));
+        SPH_TRY(varh_h_stats(c, c->h_new_is_build));
         c->h_new_is_build = false;
-        { Timed t(c, SPH_K_LEAF); API_TRY(varh_refresh_h(c)); }
+        { Timed t(c, SPH_K_LEAF); SPH_TRY(varh_refresh_h(c)); }
         // the list of the new lengths: re-flagged from the list in place when no h outgrew its margin, else built.  The
         // re-flag pass and the density pass that follows it walk the same rows: one kernel does both (SPH_NO_FUSED_REFLAG: A/B)
         static const bool no_fused = getenv("SPH_NO_FUSED_REFLAG") != nullptr;
         c->rates_valid = false; c->rho_valid = false; c->eos_valid = false;
         if (varh_can_reflag(c) && !no_fused) {
             Timed t(c, SPH_K_REFLAG);
-            API_TRY(varh_reflag_density(c, make_pair_const(c)));
+            SPH_TRY(varh_reflag_density(c, make_pair_const(c)));
             c->grid_valid = true; c->h_refresh_ok = false;
             c->density_passes++;
             c->rho_valid = true; c->eos_valid = true;
             return SPH_OK;
         }
-        if (varh_can_reflag(c)) { Timed t(c, SPH_K_REFLAG); API_TRY(varh_nlist_reflag(c)); }
-        else { Timed t(c, SPH_K_NLIST); API_TRY(varh_nlist_build(c)); }
+        if (varh_can_reflag(c)) { Timed t(c, SPH_K_REFLAG); SPH_TRY(varh_nlist_reflag(c)); }
+        else { Timed t(c, SPH_K_NLIST); SPH_TRY(varh_nlist_build(c)); }
         c->grid_valid = true;
     }
     c->h_refresh_ok = false;
     if (!c->grid_valid) {
         c->h_new_is_build = false;
-        if (c->variable) API_TRY(varh_h_stats(c));
-        { Timed t(c, SPH_K_GRID); API_TRY(grid_rebuild(c)); }
+        if (c->variable) SPH_TRY(varh_h_stats(c));
+        { Timed t(c, SPH_K_GRID); SPH_TRY(grid_rebuild(c)); }
         c->order_valid = true; c->derived_kept = false; c->grav_valid = false;
         c->path_keys_valid = false;
         c->rates_valid = false; c->rho_valid = false; c->eos_valid = false; c->tree_valid = false;
         c->wave_class_valid = false; c->interior_done = false;
         if (c->variable) {
             c->leaf_valid = false;
-            { Timed t(c, SPH_K_LEAF); API_TRY(varh_leaf_build(c)); }
+            { Timed t(c, SPH_K_LEAF); SPH_TRY(varh_leaf_build(c)); }
             c->leaf_valid = true;
-            { Timed t(c, SPH_K_NLIST); API_TRY(varh_nlist_build(c)); }
+            { Timed t(c, SPH_K_NLIST); SPH_TRY(varh_nlist_build(c)); }
         } else {
-            Timed t(c, SPH_K_NLIST); API_TRY(c->tiled ? nlist_build_tiled(c) : nlist_build(c));
+            Timed t(c, SPH_K_NLIST); SPH_TRY(c->tiled ? nlist_build_tiled(c) : nlist_build(c));
         }
         c->grid_valid = true;
     }
     const PairConst pc = make_pair_const(c);
     Timed t(c, SPH_K_DENSITY);
     if ((c->p.flags & SPH_FLAG_REUSE_DENSITY) && c->rho_valid) {
-        API_HIP(c->variable ? launch_eos_only_v(c, pc) : launch_eos_only(c, pc));
+        SPH_HIP(c->variable ? launch_eos_only_v(c, pc) : launch_eos_only(c, pc));
     } else {
-        API_HIP(c->variable ? launch_density_v(c, pc) : (use_tile_kernel(c, false) ? launch_density_wt(c, pc) : launch_density(c, pc)));
+        SPH_HIP(c->variable ? launch_density_v(c, pc) : (use_tile_kernel(c, false) ? launch_density_wt(c, pc) : launch_density(c, pc)));
         c->density_passes++;
     }
     c->rho_valid = true; c->eos_valid = true;
@@ -250,24 +235,24 @@ int do_forces(sph_ctx *c) {
         const size_t bytes = (size_t)c->n * sizeof(double);
         if (reuse && c->grav_valid && c->tree_valid) {
             // same positions, masses, h, tree and sorted order as at the last walk: the same accelerations, bit for bit
-            API_HIP(hipMemcpyAsync(c->f[SPH_F_AX], c->g_cache[0], bytes, hipMemcpyDeviceToDevice, c->stream));
-            API_HIP(hipMemcpyAsync(c->f[SPH_F_AY], c->g_cache[1], bytes, hipMemcpyDeviceToDevice, c->stream));
-            API_HIP(hipMemcpyAsync(c->f[SPH_F_AZ], c->g_cache[2], bytes, hipMemcpyDeviceToDevice, c->stream));
+            SPH_HIP(hipMemcpyAsync(c->f[SPH_F_AX], c->g_cache[0], bytes, hipMemcpyDeviceToDevice, c->stream));
+            SPH_HIP(hipMemcpyAsync(c->f[SPH_F_AY], c->g_cache[1], bytes, hipMemcpyDeviceToDevice, c->stream));
+            SPH_HIP(hipMemcpyAsync(c->f[SPH_F_AZ], c->g_cache[2], bytes, hipMemcpyDeviceToDevice, c->stream));
         } else {
-            if (!c->tree_valid) { API_TRY(gravity_tree_build(c)); c->tree_valid = true; }
-            { Timed tw(c, SPH_K_GRAV_WALK); API_HIP(launch_gravity(c)); }
+            if (!c->tree_valid) { SPH_TRY(gravity_tree_build(c)); c->tree_valid = true; }
+            { Timed tw(c, SPH_K_GRAV_WALK); SPH_HIP(launch_gravity(c)); }
             if (reuse) {
                 for (auto &g : c->g_cache)
-                    if (!g) API_TRY(ctx_alloc(c, &g, (size_t)c->cap, "gravity cache"));
-                API_HIP(hipMemcpyAsync(c->g_cache[0], c->f[SPH_F_AX], bytes, hipMemcpyDeviceToDevice, c->stream));
-                API_HIP(hipMemcpyAsync(c->g_cache[1], c->f[SPH_F_AY], bytes, hipMemcpyDeviceToDevice, c->stream));
-                API_HIP(hipMemcpyAsync(c->g_cache[2], c->f[SPH_F_AZ], bytes, hipMemcpyDeviceToDevice, c->stream));
+                    if (!g) SPH_TRY(ctx_alloc(c, &g, (size_t)c->cap, "gravity cache"));
+                SPH_HIP(hipMemcpyAsync(c->g_cache[0], c->f[SPH_F_AX], bytes, hipMemcpyDeviceToDevice, c->stream));
+                SPH_HIP(hipMemcpyAsync(c->g_cache[1], c->f[SPH_F_AY], bytes, hipMemcpyDeviceToDevice, c->stream));
+                SPH_HIP(hipMemcpyAsync(c->g_cache[2], c->f[SPH_F_AZ], bytes, hipMemcpyDeviceToDevice, c->stream));
                 c->grav_valid = true;
             }
         }
     }
-    { Timed t(c, SPH_K_SINKACC); API_HIP(launch_sink_accel(c, pc)); }
-    { Timed t(c, SPH_K_FORCES); API_HIP(c->variable ? launch_forces_v(c, pc) : (use_tile_kernel(c, true) ? launch_forces_wt(c, pc, 0) : launch_forces(c, pc))); }
+    { Timed t(c, SPH_K_SINKACC); SPH_HIP(launch_sink_accel(c, pc)); }
+    { Timed t(c, SPH_K_FORCES); SPH_HIP(c->variable ? launch_forces_v(c, pc) : (use_tile_kernel(c, true) ? launch_forces_wt(c, pc, 0) : launch_forces(c, pc))); }
     c->force_passes++;
     c->rates_valid = true;
     return SPH_OK;
@@ -280,15 +265,15 @@ int do_forces_part(sph_ctx *c, int part) {
     if (!c->eos_valid || !c->grid_valid) { c->err = "sph_forces_part: call sph_density first"; return SPH_ERR_STATE; }
     const PairConst pc = make_pair_const(c);
     if (part == 1) {
-        if (!c->wave_class_valid) { API_HIP(launch_classify_waves(c)); c->wave_class_valid = true; }
-        { Timed t(c, SPH_K_SINKACC); API_HIP(launch_sink_accel(c, pc)); }
-        { Timed t(c, SPH_K_FORCES); API_HIP(use_tile_kernel(c, true) ? launch_forces_wt(c, pc, 1) : launch_forces(c, pc, 1)); }
+        if (!c->wave_class_valid) { SPH_HIP(launch_classify_waves(c)); c->wave_class_valid = true; }
+        { Timed t(c, SPH_K_SINKACC); SPH_HIP(launch_sink_accel(c, pc)); }
+        { Timed t(c, SPH_K_FORCES); SPH_HIP(use_tile_kernel(c, true) ? launch_forces_wt(c, pc, 1) : launch_forces(c, pc, 1)); }
         c->interior_done = true;
         c->rates_valid = false;
         return SPH_OK;
     }
     if (!c->interior_done) { c->err = "sph_forces_part: part 2 before part 1"; return SPH_ERR_STATE; }
-    { Timed t(c, SPH_K_FORCES); API_HIP(use_tile_kernel(c, true) ? launch_forces_wt(c, pc, 2) : launch_forces(c, pc, 2)); }
+    { Timed t(c, SPH_K_FORCES); SPH_HIP(use_tile_kernel(c, true) ? launch_forces_wt(c, pc, 2) : launch_forces(c, pc, 2)); }
     c->interior_done = false;
     c->force_passes++;
     c->rates_valid = true;
@@ -298,21 +283,21 @@ int do_forces_part(sph_ctx *c, int part) {
 int do_kick(sph_ctx *c, double dt, bool dev) {
     if (!c->rates_valid) { c->err = "sph_kick: rates are stale, call sph_forces first"; return SPH_ERR_STATE; }
     Timed t(c, SPH_K_KICK);
-    API_HIP(launch_kick(c, dt, dev));
+    SPH_HIP(launch_kick(c, dt, dev));
     c->eos_valid = false;
     return SPH_OK;
 }
 
 int do_drift(sph_ctx *c, double dt, bool dev) {
     Timed t(c, SPH_K_DRIFT);
-    API_HIP(launch_drift(c, dt, dev));
+    SPH_HIP(launch_drift(c, dt, dev));
     c->grid_valid = false; c->rho_valid = false; c->eos_valid = false; c->order_valid = false;
     return SPH_OK;
 }
 
 int put_dt(sph_ctx *c, double dt, double t) {
     c->h_pinned[16] = dt; c->h_pinned[17] = t; c->h_pinned[18] = 0.0;
-    API_HIP(hipMemcpyAsync(c->d_dt, c->h_pinned + 16, 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    SPH_HIP(hipMemcpyAsync(c->d_dt, c->h_pinned + 16, 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     return SPH_OK;
 }
 
@@ -337,9 +322,9 @@ int drain_reports(sph_ctx *c) {
 }
 
 int get_dt(sph_ctx *c, double *dt, double *t) {
-    API_HIP(hipMemcpyAsync(c->h_pinned + 20, c->d_dt, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    API_HIP(hipStreamSynchronize(c->stream));
-    API_TRY(drain_reports(c));
+    SPH_HIP(hipMemcpyAsync(c->h_pinned + 20, c->d_dt, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    SPH_TRY(drain_reports(c));
     if (dt) *dt = c->h_pinned[20];
     if (t) *t = c->h_pinned[21];
     return SPH_OK;
@@ -350,7 +335,7 @@ int do_update_h(sph_ctx *c) {
     if (!c->variable) { c->err = "sph_update_h: context is not in variable-h mode"; return SPH_ERR_STATE; }
     if (!c->grid_valid || !c->rho_valid) { c->err = "sph_update_h: needs the density of the current positions"; return SPH_ERR_STATE; }
     const PairConst pc = make_pair_const(c);
-    { Timed t(c, SPH_K_UPDATE_H); API_HIP(launch_update_h(c, pc)); }
+    { Timed t(c, SPH_K_UPDATE_H); SPH_HIP(launch_update_h(c, pc)); }
     // h changed: reaches, neighbour sets, rho all depend on it -- but nothing else does (do_density's short path)
     c->grid_valid = false; c->rho_valid = false; c->eos_valid = false;
     c->h_refresh_ok = true;
@@ -363,42 +348,42 @@ int do_accrete(sph_ctx *c, int64_t *removed, int32_t *d_keep = nullptr) {
     if (!c->order_valid) { c->err = "sph_accrete_and_cull: needs the grid of the current positions (call sph_density first)"; return SPH_ERR_STATE; }
     if (c->n_owned != c->n) { c->err = "sph_accrete_and_cull: not available with ghost particles"; return SPH_ERR_STATE; }
     if (!c->bbox_exact) {       // the octree's root box is the exact bounding box: take it from the last build's read-back slot
-        API_HIP(hipStreamSynchronize(c->stream));
+        SPH_HIP(hipStreamSynchronize(c->stream));
         const double *bb = c->h_pinned + 200 + 16 * (1 - c->ring_bbox);
         for (int a = 0; a < 6; a++) c->bbox[a] = bb[a];
         c->bbox_exact = true;
     }
-    API_TRY(accrete_and_cull(c, removed, d_keep));      // includes [V]'s cull of the sinks (Variable.f90:610-613)
+    SPH_TRY(accrete_and_cull(c, removed, d_keep));      // includes [V]'s cull of the sinks (Variable.f90:610-613)
     if (*removed > 0) c->numbers_set = false;           // the caller's numbering changed with the pack()
     return SPH_OK;
 }
 
 int one_step_device_dt(sph_ctx *c) {
     // SUMMER_SPH.f90:889-916
-    API_TRY(do_density(c));
-    API_TRY(do_forces(c));
+    SPH_TRY(do_density(c));
+    SPH_TRY(do_forces(c));
     {   // kick + drift, one pass over the state (bitwise what sph_kick + sph_drift give)
         if (!c->rates_valid) { c->err = "sph_step: rates are stale"; return SPH_ERR_STATE; }
         Timed t(c, SPH_K_KICK);
-        API_HIP(launch_kick_drift(c));
+        SPH_HIP(launch_kick_drift(c));
         c->grid_valid = false; c->rho_valid = false; c->eos_valid = false; c->order_valid = false;
     }
-    API_TRY(do_density(c));
-    API_TRY(do_forces(c));
+    SPH_TRY(do_density(c));
+    SPH_TRY(do_forces(c));
     {   // closing kick + get_next_timestep, one pass (bitwise what sph_kick + sph_next_dt give)
         if (!c->rates_valid) { c->err = "sph_step: rates are stale"; return SPH_ERR_STATE; }
         Timed t(c, SPH_K_DT);
-        API_HIP(launch_kick_next_dt(c, true));
+        SPH_HIP(launch_kick_next_dt(c, true));
         c->eos_valid = false;
     }
-    if (c->variable) API_TRY(do_update_h(c));          // Variable.f90:1152
+    if (c->variable) SPH_TRY(do_update_h(c));          // Variable.f90:1152
     if (c->variable && (c->p.flags & SPH_FLAG_SINK_CREATION)) {      // Variable.f90:1155, before accretion and bounds
         int32_t created = 0;
-        API_TRY(sink_creation(c, &created));
+        SPH_TRY(sink_creation(c, &created));
     }
     if (c->p.flags & SPH_FLAG_ACCRETE_CULL) {          // SUMMER_SPH.f90:919-920
         int64_t removed = 0;
-        API_TRY(do_accrete(c, &removed));
+        SPH_TRY(do_accrete(c, &removed));
     }
     return SPH_OK;
 }
@@ -626,19 +611,19 @@ static int upload_impl(sph_ctx *c, int64_t n, const double *const src[9], hipMem
     for (int k = 0; k < 8; k++)
         if (n > 0 && !src[k]) { c->err = "sph_upload: null array"; return SPH_ERR_ARG; }
     DeviceGuard g(c->device);
-    API_TRY(ensure_capacity(c, n));
+    SPH_TRY(ensure_capacity(c, n));
     c->n = n; c->n_slots = n; c->dead_below = 0;
     c->numbers_set = false;
     c->n_owned = n;
     for (int k = 0; k < 9; k++) {
         if (n == 0) break;
-        if (src[k]) API_HIP(hipMemcpyAsync(c->f[k], src[k], (size_t)n * sizeof(double), kind, c->stream));
-        else API_HIP(hipMemsetAsync(c->f[k], 0, (size_t)n * sizeof(double), c->stream));   // alpha = 0, SUMMER_SPH.f90:681
+        if (src[k]) SPH_HIP(hipMemcpyAsync(c->f[k], src[k], (size_t)n * sizeof(double), kind, c->stream));
+        else SPH_HIP(hipMemsetAsync(c->f[k], 0, (size_t)n * sizeof(double), c->stream));   // alpha = 0, SUMMER_SPH.f90:681
     }
-    API_HIP(launch_iota(c, c->orig, n));
-    API_HIP(launch_iota(c, c->inv, n));
-    if (c->variable) API_HIP(launch_fill(c, c->f[SPH_F_H], c->p.h, n));    // until sph_upload_field(SPH_F_H) sets it
-    API_HIP(hipStreamSynchronize(c->stream));
+    SPH_HIP(launch_iota(c, c->orig, n));
+    SPH_HIP(launch_iota(c, c->inv, n));
+    if (c->variable) SPH_HIP(launch_fill(c, c->f[SPH_F_H], c->p.h, n));    // until sph_upload_field(SPH_F_H) sets it
+    SPH_HIP(hipStreamSynchronize(c->stream));
     c->grid_valid = c->rho_valid = c->eos_valid = c->rates_valid = c->order_valid = c->tree_valid = false;
     c->derived_kept = false;
     c->ring_bbox_valid = c->ring_nl_valid = false;       // a new particle set: the next build waits for its own read-backs
@@ -667,10 +652,10 @@ int sph_set_sinks(sph_ctx *c, int32_t ns, const double *sx, const double *sy, co
     DeviceGuard g(c->device);
     std::vector<double> buf((size_t)10 * MAX_SINKS, 0.0);
     for (int k = 0; k < 7; k++) for (int s = 0; s < ns; s++) buf[(size_t)k * MAX_SINKS + s] = src[k][s];
-    API_HIP(hipStreamSynchronize(c->stream));
-    API_HIP(hipMemcpy(c->sink, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    SPH_HIP(hipMemcpy(c->sink, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice));
     std::vector<double> rad((size_t)MAX_SINKS, c->variable ? 5.0 : 3.5);      // Variable.f90:830 / SUMMER_SPH.f90:694
-    API_HIP(hipMemcpy(c->sink_radius, rad.data(), rad.size() * sizeof(double), hipMemcpyHostToDevice));
+    SPH_HIP(hipMemcpy(c->sink_radius, rad.data(), rad.size() * sizeof(double), hipMemcpyHostToDevice));
     c->ns = ns;
     c->rates_valid = false;
     return SPH_OK;
@@ -681,8 +666,8 @@ int sph_get_sinks(sph_ctx *c, int32_t ns, double *sx, double *sy, double *sz, do
     if (!c || ns < 0 || ns > c->ns) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
     std::vector<double> buf((size_t)10 * MAX_SINKS);
-    API_HIP(hipStreamSynchronize(c->stream));
-    API_HIP(hipMemcpy(buf.data(), c->sink, buf.size() * sizeof(double), hipMemcpyDeviceToHost));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    SPH_HIP(hipMemcpy(buf.data(), c->sink, buf.size() * sizeof(double), hipMemcpyDeviceToHost));
     double *dst[10] = {sx, sy, sz, svx, svy, svz, sm, sax, say, saz};
     for (int k = 0; k < 10; k++) if (dst[k]) for (int s = 0; s < ns; s++) dst[k][s] = buf[(size_t)k * MAX_SINKS + s];
     return SPH_OK;
@@ -697,16 +682,16 @@ int sph_next_dt(sph_ctx *c, double *dt) {
     if (!c || !dt) return SPH_ERR_ARG;
     if (!c->rates_valid) { c->err = "sph_next_dt: rates are stale"; return SPH_ERR_STATE; }
     DeviceGuard g(c->device);
-    API_TRY(put_dt(c, *dt, 0.0));
-    { Timed t(c, SPH_K_DT); API_HIP(launch_next_dt(c, false)); }
+    SPH_TRY(put_dt(c, *dt, 0.0));
+    { Timed t(c, SPH_K_DT); SPH_HIP(launch_next_dt(c, false)); }
     return get_dt(c, dt, nullptr);
 }
 
 int sph_run(sph_ctx *c, int32_t nsteps, double *dt, double *t) {
     if (!c || !dt || nsteps < 0) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    API_TRY(put_dt(c, *dt, t ? *t : 0.0));
-    for (int k = 0; k < nsteps; k++) API_TRY(one_step_device_dt(c));
+    SPH_TRY(put_dt(c, *dt, t ? *t : 0.0));
+    for (int k = 0; k < nsteps; k++) SPH_TRY(one_step_device_dt(c));
     return get_dt(c, dt, t);
 }
 
@@ -716,8 +701,8 @@ int sph_download_field_dev(sph_ctx *c, int field, double *d_out, int64_t n) {
     if (!c || field < 0 || field >= SPH_F_COUNT || n != c->n || (n > 0 && !d_out)) return SPH_ERR_ARG;
     if (!field_ready(c, field)) { c->err = "sph_download_field: field is stale"; return SPH_ERR_STATE; }
     DeviceGuard g(c->device);
-    API_HIP(launch_unpermute(c, c->f[field], d_out));
-    API_HIP(hipStreamSynchronize(c->stream));
+    SPH_HIP(launch_unpermute(c, c->f[field], d_out));
+    SPH_HIP(hipStreamSynchronize(c->stream));
     return drain_reports(c);
 }
 
@@ -726,9 +711,9 @@ int sph_download_field(sph_ctx *c, int field, double *host, int64_t n) {
     if (!field_ready(c, field)) { c->err = "sph_download_field: field is stale"; return SPH_ERR_STATE; }
     if (n == 0) return SPH_OK;
     DeviceGuard g(c->device);
-    API_HIP(launch_unpermute(c, c->f[field], c->scratch));
-    API_HIP(hipMemcpyAsync(host, c->scratch, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    API_HIP(hipStreamSynchronize(c->stream));
+    SPH_HIP(launch_unpermute(c, c->f[field], c->scratch));
+    SPH_HIP(hipMemcpyAsync(host, c->scratch, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
     return drain_reports(c);
 }
 
@@ -736,7 +721,7 @@ int sph_download_state(sph_ctx *c, int64_t n, double *x, double *y, double *z, d
                        double *u, double *m, double *alpha) {
     double *dst[9] = {x, y, z, vx, vy, vz, u, m, alpha};
     for (int k = 0; k < 9; k++)
-        if (dst[k]) API_TRY(sph_download_field(c, k, dst[k], n));
+        if (dst[k]) SPH_TRY(sph_download_field(c, k, dst[k], n));
     return SPH_OK;
 }
 
@@ -761,9 +746,9 @@ int sph_get_stats(sph_ctx *c, sph_stats *o) {
     if (c->n > 0 && c->nlist_builds > 0 && c->ncount && c->n <= c->cap) {      // counts of the last build
         DeviceGuard g(c->device);
         std::vector<int32_t> cnt((size_t)c->n);
-        API_HIP(hipStreamSynchronize(c->stream));
-        API_TRY(drain_reports(c));
-        API_HIP(hipMemcpy(cnt.data(), c->ncount, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        SPH_HIP(hipStreamSynchronize(c->stream));
+        SPH_TRY(drain_reports(c));
+        SPH_HIP(hipMemcpy(cnt.data(), c->ncount, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         double s = 0.0, sw = 0.0;
         for (int32_t v : cnt) s += v;
         o->nlist_mean = s / (double)c->n;
@@ -787,12 +772,12 @@ static int upload_field_impl(sph_ctx *c, int field, const double *src, int64_t n
     DeviceGuard g(c->device);
     const double *dsrc = src;
     if (host) {
-        API_HIP(hipMemcpyAsync(c->scratch, src, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        SPH_HIP(hipMemcpyAsync(c->scratch, src, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
         dsrc = c->scratch;
     }
     const int f = field;
-    API_HIP(launch_scatter_fields(c, 1, &f, 0, n, dsrc));
-    API_HIP(hipStreamSynchronize(c->stream));
+    SPH_HIP(launch_scatter_fields(c, 1, &f, 0, n, dsrc));
+    SPH_HIP(hipStreamSynchronize(c->stream));
     field_written(c, field);
     return SPH_OK;
 }
@@ -803,16 +788,16 @@ int sph_upload_field_dev(sph_ctx *c, int field, const double *d_vals, int64_t n)
 int sph_set_sink_radii(sph_ctx *c, int32_t ns, const double *radius) {
     if (!c || ns != c->ns || (ns > 0 && !radius)) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    API_HIP(hipStreamSynchronize(c->stream));
-    if (ns > 0) API_HIP(hipMemcpy(c->sink_radius, radius, (size_t)ns * sizeof(double), hipMemcpyHostToDevice));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    if (ns > 0) SPH_HIP(hipMemcpy(c->sink_radius, radius, (size_t)ns * sizeof(double), hipMemcpyHostToDevice));
     return SPH_OK;
 }
 
 int sph_get_sink_radii(sph_ctx *c, int32_t ns, double *radius) {
     if (!c || ns < 0 || ns > c->ns || (ns > 0 && !radius)) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    API_HIP(hipStreamSynchronize(c->stream));
-    if (ns > 0) API_HIP(hipMemcpy(radius, c->sink_radius, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    if (ns > 0) SPH_HIP(hipMemcpy(radius, c->sink_radius, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
     return SPH_OK;
 }
 
@@ -854,7 +839,7 @@ int sph_scatter_field_dev(sph_ctx *c, int field, int64_t first, int64_t count, c
     if (!c || field < 0 || field >= SPH_F_COUNT || first < 0 || count < 0 || first + count > c->n || (count > 0 && !d_vals))
         return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    API_HIP(launch_scatter_field(c, c->f[field], first, count, d_vals));
+    SPH_HIP(launch_scatter_field(c, c->f[field], first, count, d_vals));
     if ((field == SPH_F_H || field == SPH_F_OMEGA) && !c->variable) { c->err = "field needs SPH_FLAG_VARIABLE_H"; return SPH_ERR_ARG; }
     field_written(c, field);
     return SPH_OK;
@@ -873,8 +858,8 @@ int sph_gather_fields_dev(sph_ctx *c, int32_t nf, const int32_t *fields, int64_t
     if (!c || count < 0 || count > c->n || (count > 0 && !d_out)) return SPH_ERR_ARG;
     if (!fields_ok(c, nf, fields, true)) { c->err = "sph_gather_fields_dev: bad or stale field"; return SPH_ERR_ARG; }
     DeviceGuard g(c->device);
-    API_HIP(launch_gather_fields(c, nf, fields, d_ids, count, d_out));
-    if (c->own_stream) API_HIP(hipStreamSynchronize(c->stream));
+    SPH_HIP(launch_gather_fields(c, nf, fields, d_ids, count, d_out));
+    if (c->own_stream) SPH_HIP(hipStreamSynchronize(c->stream));
     return SPH_OK;
 }
 
@@ -882,7 +867,7 @@ int sph_scatter_fields_dev(sph_ctx *c, int32_t nf, const int32_t *fields, int64_
     if (!c || first < 0 || count < 0 || first + count > c->n || (count > 0 && !d_vals)) return SPH_ERR_ARG;
     if (!fields_ok(c, nf, fields, false)) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    API_HIP(launch_scatter_fields(c, nf, fields, first, count, d_vals));
+    SPH_HIP(launch_scatter_fields(c, nf, fields, first, count, d_vals));
     for (int f = 0; f < nf; f++) field_written(c, fields[f]);
     return SPH_OK;
 }
@@ -893,8 +878,8 @@ static int refresh_eos_impl(sph_ctx *c, bool ghosts_only) {
     DeviceGuard g(c->device);
     const PairConst pc = make_pair_const(c);
     Timed t(c, SPH_K_DENSITY);
-    if (c->variable) API_HIP(launch_eos_only_v(c, pc));
-    else API_HIP(launch_eos_only(c, pc, ghosts_only));
+    if (c->variable) SPH_HIP(launch_eos_only_v(c, pc));
+    else SPH_HIP(launch_eos_only(c, pc, ghosts_only));
     c->eos_valid = true;
     return SPH_OK;
 }
@@ -906,9 +891,9 @@ int sph_dt_candidate(sph_ctx *c, double *cand) {
     if (!c || !cand) return SPH_ERR_ARG;
     if (!c->rates_valid) { c->err = "sph_dt_candidate: rates are stale"; return SPH_ERR_STATE; }
     DeviceGuard g(c->device);
-    { Timed t(c, SPH_K_DT); API_HIP(launch_dt_partial_only(c)); }
-    API_HIP(hipMemcpyAsync(c->h_pinned + 24, c->d_dt + 2, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    API_HIP(hipStreamSynchronize(c->stream));
+    { Timed t(c, SPH_K_DT); SPH_HIP(launch_dt_partial_only(c)); }
+    SPH_HIP(hipMemcpyAsync(c->h_pinned + 24, c->d_dt + 2, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
     *cand = c->h_pinned[24];
     return SPH_OK;
 }
@@ -916,17 +901,17 @@ int sph_dt_candidate(sph_ctx *c, double *cand) {
 int sph_set_sink_accel(sph_ctx *c, int32_t ns, const double *sax, const double *say, const double *saz) {
     if (!c || ns != c->ns || (ns > 0 && (!sax || !say || !saz))) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    API_HIP(hipStreamSynchronize(c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
     const double *src[3] = {sax, say, saz};
     for (int k = 0; k < 3; k++)
-        if (ns > 0) API_HIP(hipMemcpy(c->sink + (size_t)(7 + k) * MAX_SINKS, src[k], (size_t)ns * sizeof(double), hipMemcpyHostToDevice));
+        if (ns > 0) SPH_HIP(hipMemcpy(c->sink + (size_t)(7 + k) * MAX_SINKS, src[k], (size_t)ns * sizeof(double), hipMemcpyHostToDevice));
     return SPH_OK;
 }
 
 int sph_set_stream(sph_ctx *c, void *stream) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    API_HIP(hipStreamSynchronize(c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
     resolve_timing(c);
     if (c->own_stream) { (void)hipStreamDestroy(c->stream); c->stream = nullptr; }
     c->stream = reinterpret_cast<hipStream_t>(stream);      // NULL = the device's default stream
@@ -950,7 +935,7 @@ int sph_select_boxes(sph_ctx *c, int32_t nbox, const double *boxes, int64_t *cou
     if (!c || nbox < 0 || nbox > MAX_SEL_BOXES || (nbox > 0 && (!boxes || !counts))) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
     c->sel_boxes = 0;
-    API_TRY(domain_select_boxes(c, nbox, boxes, counts));
+    SPH_TRY(domain_select_boxes(c, nbox, boxes, counts));
     c->sel_boxes = nbox;
     for (int b = 0; b < nbox; b++) c->sel_counts[b] = counts[b];
     return SPH_OK;
@@ -960,7 +945,7 @@ int sph_select_boxes_async(sph_ctx *c, int32_t nbox, const double *boxes) {
     if (!c || nbox < 0 || nbox > MAX_SEL_BOXES || (nbox > 0 && !boxes)) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
     c->sel_boxes = 0;
-    API_TRY(domain_select_boxes_enqueue(c, nbox, boxes));
+    SPH_TRY(domain_select_boxes_enqueue(c, nbox, boxes));
     c->sel_boxes = nbox;
     for (int b = 0; b < nbox; b++) c->sel_counts[b] = -1;          // unknown until sph_selected_counts
     return SPH_OK;
@@ -978,10 +963,10 @@ int sph_gather_selected_dev(sph_ctx *c, int32_t box, int32_t nf, const int32_t *
     if (!fields_ok(c, nf, fields, true)) { c->err = "sph_gather_selected_dev: bad or stale field"; return SPH_ERR_ARG; }
     DeviceGuard g(c->device);
     if (c->n_owned == 0) {            // nothing selected, no id list: the header alone
-        API_HIP(hipMemsetAsync(d_out, 0, 2 * sizeof(double), c->stream));
+        SPH_HIP(hipMemsetAsync(d_out, 0, 2 * sizeof(double), c->stream));
         return SPH_OK;
     }
-    API_HIP(launch_gather_selected(c, nf, fields, box, capacity, d_out));
+    SPH_HIP(launch_gather_selected(c, nf, fields, box, capacity, d_out));
     return SPH_OK;
 }
 
@@ -989,8 +974,8 @@ int sph_selected_ids_dev(sph_ctx *c, int32_t box, int64_t count, int64_t *d_ids)
     if (!c || box < 0 || box >= c->sel_boxes || count != c->sel_counts[box] || (count > 0 && !d_ids)) return SPH_ERR_ARG;
     if (count == 0) return SPH_OK;
     DeviceGuard g(c->device);
-    API_HIP(hipMemcpyAsync(d_ids, c->sel_ids + (size_t)box * c->sel_stride, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToDevice, c->stream));
-    if (c->own_stream) API_HIP(hipStreamSynchronize(c->stream));
+    SPH_HIP(hipMemcpyAsync(d_ids, c->sel_ids + (size_t)box * c->sel_stride, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToDevice, c->stream));
+    if (c->own_stream) SPH_HIP(hipStreamSynchronize(c->stream));
     return SPH_OK;
 }
 
@@ -998,8 +983,8 @@ int sph_replace_ghosts_dev(sph_ctx *c, int64_t count, const double *d_state) {
     if (!c || count < 0 || (count > 0 && !d_state)) return SPH_ERR_ARG;
     if (c->dead_below > 0) { c->err = "sph_replace_ghosts_dev: a ghost swap is already pending (call sph_density)"; return SPH_ERR_STATE; }
     DeviceGuard g(c->device);
-    API_TRY(domain_replace_ghosts(c, count, d_state));
-    if (c->own_stream) API_HIP(hipStreamSynchronize(c->stream));
+    SPH_TRY(domain_replace_ghosts(c, count, d_state));
+    if (c->own_stream) SPH_HIP(hipStreamSynchronize(c->stream));
     c->grid_valid = c->rho_valid = c->eos_valid = c->rates_valid = c->order_valid = c->tree_valid = false;
     return SPH_OK;
 }
@@ -1007,9 +992,9 @@ int sph_replace_ghosts_dev(sph_ctx *c, int64_t count, const double *d_state) {
 int sph_set_boundary_boxes(sph_ctx *c, int32_t nbox, const double *boxes) {
     if (!c || nbox < 0 || nbox > MAX_SEL_BOXES || (nbox > 0 && !boxes)) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    if (!c->bnd_boxes) API_TRY(ctx_alloc(c, &c->bnd_boxes, (size_t)6 * MAX_SEL_BOXES, "boundary boxes"));
+    if (!c->bnd_boxes) SPH_TRY(ctx_alloc(c, &c->bnd_boxes, (size_t)6 * MAX_SEL_BOXES, "boundary boxes"));
     for (int k = 0; k < 6 * nbox; k++) c->h_pinned[128 + k] = boxes[k];      // pinned staging: no host synchronisation
-    if (nbox > 0) API_HIP(hipMemcpyAsync(c->bnd_boxes, c->h_pinned + 128, (size_t)6 * nbox * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (nbox > 0) SPH_HIP(hipMemcpyAsync(c->bnd_boxes, c->h_pinned + 128, (size_t)6 * nbox * sizeof(double), hipMemcpyHostToDevice, c->stream));
     c->n_bnd_boxes = nbox;
     c->wave_class_valid = false;
     return SPH_OK;
@@ -1053,7 +1038,7 @@ int sph_accrete_apply_dev(sph_ctx *c, const double *d_all, int32_t nranks, int32
 int sph_set_numbers_dev(sph_ctx *c, int64_t first, int64_t count, const int64_t *d_numbers) {
     if (!c || first < 0 || count < 0 || first + count > c->cap || (count > 0 && !d_numbers)) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    API_HIP(launch_set_numbers(c, first, count, d_numbers));
+    SPH_HIP(launch_set_numbers(c, first, count, d_numbers));
     c->numbers_set = true;
     if (c->variable) { c->grid_valid = false; c->rho_valid = false; c->eos_valid = false; }
     return SPH_OK;
@@ -1095,7 +1080,7 @@ int sph_kick_drift_devdt(sph_ctx *c) {
     if (!c->rates_valid) { c->err = "sph_kick_drift_devdt: rates are stale, call sph_forces first"; return SPH_ERR_STATE; }
     DeviceGuard g(c->device);
     Timed t(c, SPH_K_KICK);
-    API_HIP(launch_kick_drift(c));
+    SPH_HIP(launch_kick_drift(c));
     c->grid_valid = false; c->rho_valid = false; c->eos_valid = false; c->order_valid = false;
     return SPH_OK;
 }
@@ -1106,7 +1091,7 @@ int sph_kick_dt_candidate_dev(sph_ctx *c) {
     if (!c->rates_valid) { c->err = "sph_kick_dt_candidate_dev: rates are stale, call sph_forces first"; return SPH_ERR_STATE; }
     DeviceGuard g(c->device);
     Timed t(c, SPH_K_DT);
-    API_HIP(launch_kick_dt_candidate(c));
+    SPH_HIP(launch_kick_dt_candidate(c));
     c->eos_valid = false;
     return SPH_OK;
 }
@@ -1118,7 +1103,7 @@ int sph_kick_dt_candidate_gas_dev(sph_ctx *c) {
     if (!c->rates_valid) { c->err = "sph_kick_dt_candidate_gas_dev: rates are stale, call sph_forces first"; return SPH_ERR_STATE; }
     DeviceGuard g(c->device);
     Timed t(c, SPH_K_DT);
-    API_HIP(launch_kick_dt_candidate(c, false));
+    SPH_HIP(launch_kick_dt_candidate(c, false));
     c->eos_valid = false;
     return SPH_OK;
 }
@@ -1126,7 +1111,7 @@ int sph_kick_dt_candidate_gas_dev(sph_ctx *c) {
 int sph_kick_sinks_devdt(sph_ctx *c) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    API_HIP(launch_kick_sinks(c));
+    SPH_HIP(launch_kick_sinks(c));
     return SPH_OK;
 }
 
@@ -1135,15 +1120,15 @@ int sph_dt_candidate_dev(sph_ctx *c) {
     if (!c->rates_valid) { c->err = "sph_dt_candidate_dev: rates are stale"; return SPH_ERR_STATE; }
     DeviceGuard g(c->device);
     Timed t(c, SPH_K_DT);
-    API_HIP(launch_dt_partial_only(c));
+    SPH_HIP(launch_dt_partial_only(c));
     return SPH_OK;
 }
 
 int sph_pack_partials_ex_dev(sph_ctx *c, double *d_out, int32_t predict_box) {
     if (!c || !d_out) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    API_HIP(launch_pack_partials(c, d_out, predict_box != 0));
-    if (c->own_stream) API_HIP(hipStreamSynchronize(c->stream));
+    SPH_HIP(launch_pack_partials(c, d_out, predict_box != 0));
+    if (c->own_stream) SPH_HIP(hipStreamSynchronize(c->stream));
     return SPH_OK;
 }
 
@@ -1152,7 +1137,7 @@ int sph_pack_partials_dev(sph_ctx *c, double *d_out) { return sph_pack_partials_
 int sph_apply_partials_dev(sph_ctx *c, const double *d_all, int32_t nranks, int32_t stride, int32_t apply_dt) {
     if (!c || !d_all || nranks < 1 || stride < SPH_PARTIALS) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    API_HIP(launch_apply_partials(c, d_all, nranks, stride, apply_dt != 0));
+    SPH_HIP(launch_apply_partials(c, d_all, nranks, stride, apply_dt != 0));
     return SPH_OK;
 }
 
@@ -1176,7 +1161,7 @@ int sph_get_bbox(sph_ctx *c, double *lo, double *hi) {
     if (!c || !lo || !hi) return SPH_ERR_ARG;
     if (!c->grid_valid) { c->err = "sph_get_bbox: no grid built for the current positions"; return SPH_ERR_STATE; }
     DeviceGuard g(c->device);
-    API_HIP(hipStreamSynchronize(c->stream));             // the exact box of the last build sits in its read-back slot
+    SPH_HIP(hipStreamSynchronize(c->stream));             // the exact box of the last build sits in its read-back slot
     const double *bb = c->h_pinned + 200 + 16 * (1 - c->ring_bbox);
     for (int a = 0; a < 3; a++) { lo[a] = bb[a]; hi[a] = bb[3 + a]; }
     return SPH_OK;
@@ -1298,7 +1283,7 @@ int sph_gradients_dev(sph_ctx *c, const sph_gradients_desc *d, const double *d_v
 int sph_synchronize(sph_ctx *c) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    API_HIP(hipStreamSynchronize(c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
     return drain_reports(c);
 }
 

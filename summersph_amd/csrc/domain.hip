@@ -134,15 +134,6 @@ __global__ void apply_partials(const double *__restrict__ all, int nranks, int s
 
 }  // namespace
 
-#define DM_CHECK(expr)                                                      \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) {                                             \
-            c->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return SPH_ERR_HIP;                                             \
-        }                                                                   \
-    } while (0)
-
 // ids (ascending original id) of the owned particles inside each of nbox boxes -> c->sel_ids + b * n_owned; the counts stay
 // on the device (c->sel_count) and travel to pinned memory behind the selection, without a wait
 int domain_select_boxes_enqueue(sph_ctx *c, int nbox, const double *boxes) {
@@ -154,7 +145,7 @@ int domain_select_boxes_enqueue(sph_ctx *c, int nbox, const double *boxes) {
         if (ctx_alloc(c, &c->sel_count, (size_t)MAX_SEL_BOXES, "selection counts") != SPH_OK) return SPH_ERR_NOMEM;
     }
     if (nbox == 0) return SPH_OK;
-    if (no == 0) { DM_CHECK(hipMemsetAsync(c->sel_count, 0, (size_t)nbox * sizeof(int64_t), c->stream)); return SPH_OK; }
+    if (no == 0) { SPH_HIP(hipMemsetAsync(c->sel_count, 0, (size_t)nbox * sizeof(int64_t), c->stream)); return SPH_OK; }
     const size_t need = (size_t)nbox * (size_t)no;
     if (need > c->sel_cap) {
         ctx_free(c, c->sel_ids);
@@ -167,18 +158,18 @@ int domain_select_boxes_enqueue(sph_ctx *c, int nbox, const double *boxes) {
         InBox pred{c->inv, c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z],
                    {boxes[b * 6 + 0], boxes[b * 6 + 1], boxes[b * 6 + 2]}, {boxes[b * 6 + 3], boxes[b * 6 + 4], boxes[b * 6 + 5]}};
         size_t tmp = 0;
-        DM_CHECK(rocprim::select(nullptr, tmp, first, c->sel_ids + (size_t)b * no, c->sel_count + b, (size_t)no, pred, c->stream));
+        SPH_HIP(rocprim::select(nullptr, tmp, first, c->sel_ids + (size_t)b * no, c->sel_count + b, (size_t)no, pred, c->stream));
         if (tmp > c->sel_tmp_bytes) {
-            DM_CHECK(hipStreamSynchronize(c->stream));
+            SPH_HIP(hipStreamSynchronize(c->stream));
             ctx_free_ptr(c, c->sel_tmp);
             c->sel_tmp = nullptr; c->sel_tmp_bytes = 0;
             if (ctx_alloc_bytes(c, &c->sel_tmp, tmp, "selection scratch") != SPH_OK) return SPH_ERR_NOMEM;
             c->sel_tmp_bytes = tmp;
         }
         tmp = c->sel_tmp_bytes;
-        DM_CHECK(rocprim::select(c->sel_tmp, tmp, first, c->sel_ids + (size_t)b * no, c->sel_count + b, (size_t)no, pred, c->stream));
+        SPH_HIP(rocprim::select(c->sel_tmp, tmp, first, c->sel_ids + (size_t)b * no, c->sel_count + b, (size_t)no, pred, c->stream));
     }
-    DM_CHECK(hipMemcpyAsync(h, c->sel_count, (size_t)nbox * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipMemcpyAsync(h, c->sel_count, (size_t)nbox * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     return SPH_OK;
 }
 
@@ -190,7 +181,7 @@ void domain_selected_counts(sph_ctx *c, int nbox, int64_t *counts) {
 int domain_select_boxes(sph_ctx *c, int nbox, const double *boxes, int64_t *counts) {
     const int st = domain_select_boxes_enqueue(c, nbox, boxes);
     if (st != SPH_OK) return st;
-    DM_CHECK(hipStreamSynchronize(c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
     domain_selected_counts(c, nbox, counts);
     return SPH_OK;
 }
@@ -205,7 +196,7 @@ int domain_replace_ghosts(sph_ctx *c, int64_t count, const double *d_vals) {
         FieldPtrs9 fp{};
         for (int f = 0; f < 9; f++) fp.p[f] = c->f[f];
         append_ghosts<<<dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream>>>(fp, c->variable ? c->f[SPH_F_H] : nullptr, c->orig, n_old, c->n_owned, count, d_vals);
-        DM_CHECK(hipGetLastError());
+        SPH_HIP(hipGetLastError());
     }
     c->dead_below = n_old;             // slots below with an original id >= n_owned are the old ghosts
     c->n_slots = n_old + count;

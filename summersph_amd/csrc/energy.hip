@@ -3,7 +3,7 @@
 // Not part of the step loop: the state, the derived fields, the grid, the list, the statistics and dt stay as they are.
 // With SPH_FLAG_SELF_GRAVITY the Barnes-Hut tree of the potential is built into the context's tree arrays (gravity.hip,
 // gravity_tree_build_records), which marks the context's own tree stale: the next sph_forces builds it again, bitwise the
-// same.  The other scratch is the render's (render_scratch).
+// same.  The other scratch is the one the analysis calls share (analysis_scratch).
 //
 // Pipeline (all on ctx->stream):
 //   [self-gravity, no external sources]
@@ -21,7 +21,7 @@
 #include <cmath>
 #include <vector>
 
-#include "sph_internal.hpp"
+#include "reduce_common.hpp"
 
 // the per-particle arithmetic is written in one documented order (summersph.h); no contraction into fused multiply-adds
 #pragma clang fp contract(off)
@@ -31,7 +31,6 @@ namespace sph {
 namespace {
 
 constexpr int NG = 15;                 // gas sums
-constexpr int PIECE = 16 * WAVE;       // ids per piece: 16 per lane
 constexpr int EB = 256;                // stage block
 constexpr int BOX_BLOCKS = 1024;       // stage blocks at most (grid-stride beyond)
 
@@ -80,11 +79,6 @@ __global__ __launch_bounds__(WAVE) void energy_box(const double *__restrict__ bo
         }
     if (lane == 0)
         for (int a = 0; a < 6; a++) out[a] = v[a];
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);     // the butterfly: every lane ends with the same sum
-    return v;
 }
 
 struct GasFields { const double *x, *y, *z, *vx, *vy, *vz, *u, *m; };
@@ -185,58 +179,40 @@ __global__ __launch_bounds__(WAVE) void energy_final(const double *__restrict__ 
     }
 }
 
-#define EN_HIP(expr)                                                        \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) {                                             \
-            c->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return SPH_ERR_HIP;                                             \
-        }                                                                   \
-    } while (0)
-
-#define EN_TRY(expr)                   \
-    do {                               \
-        int _s = (expr);               \
-        if (_s != SPH_OK) return _s;   \
-    } while (0)
-
-size_t align_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int en_arg(sph_ctx *c, const char *what) {
-    c->err = std::string("sph_energy: ") + what;
-    return SPH_ERR_ARG;
-}
-
 }  // namespace
 
 int energy_sums(sph_ctx *c, int64_t src_offset, double *sums, double *phi, int64_t n_phi, bool host) {
-    if (!sums && !phi) return en_arg(c, "both outputs are null");
-    if (phi && n_phi != c->n) return en_arg(c, "n_phi != sph_count");
+    const char *who = "sph_energy";
+    if (!sums && !phi) return arg_error(c, who, "both outputs are null");
+    if (phi && n_phi != c->n) return arg_error(c, who, "n_phi != sph_count");
     const bool ext = c->gx_src != nullptr;
     const int64_t no = c->n_owned;
     if (ext && (src_offset < 0 || src_offset > c->gx_n - no))
-        return en_arg(c, "src_offset out of range of the external sources");
+        return arg_error(c, who, "src_offset out of range of the external sources");
     const bool self = c->gravity && no > 0;
 
     hipStream_t st = c->stream;
     const int64_t n_pieces = (no + PIECE - 1) / PIECE;
     const int64_t no1 = std::max<int64_t>(no, 1);
     const int nb = (int)std::min<int64_t>((no1 + EB - 1) / EB, BOX_BLOCKS);
-    // scratch: staged records, Phi_self, box partials + box, pieces, sums (host form)
-    const size_t sizes[6] = {self && !ext ? 32 * (size_t)no1 : 0, self ? 8 * (size_t)no1 : 0, 8 * 6 * ((size_t)nb + 1),
-                             8 * NG * (size_t)std::max<int64_t>(n_pieces, 1), 8 * SPH_ENERGY_NSUM, 0};
-    size_t off[6], bytes = 0;
-    for (int k = 0; k < 6; k++) { off[k] = bytes; bytes += align_up(sizes[k]); }
+    double4 *rec;
+    double *phi_buf, *box_part, *part, *sums_buf;
+    auto layout = [&](Carve cv) {
+        rec = cv.take<double4>(self && !ext ? no1 : 0);               // the staged records
+        phi_buf = cv.take<double>(self ? no1 : 0);
+        box_part = cv.take<double>(6 * ((size_t)nb + 1));             // the blocks' partials, then the box
+        part = cv.take<double>(NG * (size_t)std::max<int64_t>(n_pieces, 1));
+        sums_buf = cv.take<double>(SPH_ENERGY_NSUM);
+        return cv.bytes;
+    };
     char *buf = nullptr;
-    EN_TRY(render_scratch(c, bytes, &buf));
-    double4 *rec = reinterpret_cast<double4 *>(buf + off[0]);
-    double *phi_self = self ? reinterpret_cast<double *>(buf + off[1]) : nullptr;
-    double *box_part = reinterpret_cast<double *>(buf + off[2]);
+    SPH_TRY(analysis_scratch(c, layout(Carve{}), &buf));
+    layout(Carve{buf});
+    double *phi_self = self ? phi_buf : nullptr;
     double *box = box_part + 6 * (size_t)nb;
-    double *part = reinterpret_cast<double *>(buf + off[3]);
-    double *d_sums = host || !sums ? reinterpret_cast<double *>(buf + off[4]) : sums;
+    double *d_sums = host || !sums ? sums_buf : sums;
     double *d_phi = phi ? (host ? c->scratch : phi) : nullptr;      // host form: the download buffer (cap >= n doubles)
-    if (!c->rnd_pinned) EN_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->rnd_pinned), 32 * sizeof(double), hipHostMallocDefault));
+    SPH_TRY(analysis_pinned(c));
 
     if (self) {
         int64_t n_src = no;
@@ -244,12 +220,12 @@ int energy_sums(sph_ctx *c, int64_t src_offset, double *sums, double *phi, int64
             energy_stage<<<dim3((unsigned)nb), dim3(EB), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], c->f[SPH_F_M], c->inv,
                                                                   no, rec, box_part);
             energy_box<<<dim3(1), dim3(WAVE), 0, st>>>(box_part, nb, box);
-            EN_HIP(hipGetLastError());
-            EN_HIP(hipMemcpyAsync(c->rnd_pinned, box, 6 * sizeof(double), hipMemcpyDeviceToHost, st));
-            EN_HIP(hipStreamSynchronize(st));
+            SPH_HIP(hipGetLastError());
+            SPH_HIP(hipMemcpyAsync(c->rnd_pinned, box, 6 * sizeof(double), hipMemcpyDeviceToHost, st));
+            SPH_HIP(hipStreamSynchronize(st));
             double bb[6];
             for (int a = 0; a < 6; a++) bb[a] = c->rnd_pinned[a];
-            EN_TRY(gravity_tree_build_records(c, reinterpret_cast<const double *>(rec), no, bb));
+            SPH_TRY(gravity_tree_build_records(c, reinterpret_cast<const double *>(rec), no, bb));
             src_offset = 0;
         } else {
             // the tree sph_forces builds over the external sources (it does not depend on the context's own particles)
@@ -257,12 +233,12 @@ int energy_sums(sph_ctx *c, int64_t src_offset, double *sums, double *phi, int64
             if (!c->tree_valid) {
                 double rb[4];
                 for (int a = 0; a < 4; a++) rb[a] = c->root_box[a];
-                EN_TRY(gravity_tree_build(c));
+                SPH_TRY(gravity_tree_build(c));
                 for (int a = 0; a < 4; a++) c->root_box[a] = rb[a];
                 c->grav_valid = false;
             }
         }
-        EN_HIP(launch_potential(c, n_src, src_offset, phi_self));
+        SPH_HIP(launch_potential(c, n_src, src_offset, phi_self));
     }
     if (n_pieces > 0) {
         GasFields gf{c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], c->f[SPH_F_VX], c->f[SPH_F_VY], c->f[SPH_F_VZ], c->f[SPH_F_U],
@@ -271,13 +247,13 @@ int energy_sums(sph_ctx *c, int64_t src_offset, double *sums, double *phi, int64
         energy_pieces<<<dim3((unsigned)((n_pieces + wpb - 1) / wpb)), dim3(256), 0, st>>>(gf, c->inv, no, n_pieces, c->sink, c->ns,
                                                                                          c->p.G, phi_self, d_phi, part);
     }
-    if (d_phi && c->n > no) EN_HIP(hipMemsetAsync(d_phi + no, 0, (size_t)(c->n - no) * sizeof(double), st));   // ghosts
+    if (d_phi && c->n > no) SPH_HIP(hipMemsetAsync(d_phi + no, 0, (size_t)(c->n - no) * sizeof(double), st));   // ghosts
     energy_final<<<dim3(1), dim3(WAVE), 0, st>>>(part, n_pieces, c->sink, c->ns, c->rank == 0 ? 1 : 0, c->p.G, d_sums);
-    EN_HIP(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     if (host) {
-        if (sums) EN_HIP(hipMemcpyAsync(sums, d_sums, SPH_ENERGY_NSUM * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (phi && c->n > 0) EN_HIP(hipMemcpyAsync(phi, d_phi, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, st));
-        EN_HIP(hipStreamSynchronize(st));
+        if (sums) SPH_HIP(hipMemcpyAsync(sums, d_sums, SPH_ENERGY_NSUM * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (phi && c->n > 0) SPH_HIP(hipMemcpyAsync(phi, d_phi, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, st));
+        SPH_HIP(hipStreamSynchronize(st));
     }
     return SPH_OK;
 }

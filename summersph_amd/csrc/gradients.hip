@@ -2,7 +2,7 @@
 // form or the matrix-corrected form that is exact for linear fields (include/summersph.h, sph_gradients).
 //
 // Not part of the step loop: nothing here reads or writes the context's grid, cell table, neighbour list, statistics or
-// flags.  The scratch is the render's (render_scratch).
+// flags.  The scratch is the one the analysis calls share (analysis_scratch).
 //
 // Pipeline (all on ctx->stream; counts, box and cell edge stay on the device):
 //   grad_select   every slot: source (a live gas slot with a finite position) and target (a source with original id <
@@ -31,7 +31,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "sph_internal.hpp"
+#include "cell_table.hpp"
 
 // the per-pair and per-target arithmetic is written in one documented order (summersph.h); no contraction into fused
 // multiply-adds, so that the numpy restatement (tests/gradients_ref.py) reproduces it closely
@@ -45,9 +45,6 @@ constexpr int GB = 256;                    // block of the per-slot and walk ker
 constexpr int BOX_BLOCKS = 1024;           // select blocks at most (grid-stride beyond)
 constexpr int NBP = 9;                     // box partials: lo (3), hi (3), sources, targets, bad
 constexpr int HBINS = 8192;                // quarter octaves of a positive double: bits >> 50
-constexpr int AXIS_BITS = 21;
-constexpr uint64_t AXIS_MASK = ((uint64_t)1 << AXIS_BITS) - 1;
-constexpr double AXIS_CELLS = (double)((1 << AXIS_BITS) - 8);     // cells per axis the edge is enlarged to stay under
 constexpr double PI_DP = 3.14159265358979323846;
 
 struct Sel {
@@ -66,8 +63,6 @@ struct Info {
     int64_t counts[2];                     // targets (-1: a target has a bad h), singular targets
     int32_t bad;
 };
-
-struct Ent { uint64_t key; int32_t start, end; };    // hash table entry; empty: key = ~0
 
 // the fields read: ptr[k] is a context field in slot order (by_id 0) or a row of the caller's values by original id
 struct Vals {
@@ -201,11 +196,6 @@ __global__ __launch_bounds__(WAVE) void grad_box(const double *__restrict__ part
     info->bad = bad ? 1 : 0;
 }
 
-__device__ __forceinline__ uint64_t cell_axis(double p, double lo, double inv_e) {
-    // fmax drops a NaN (an overflowing product) to 0; the clamp keeps every key inside its 21 bits
-    return (uint64_t)fmin(fmax(floor((p - lo) * inv_e), 0.0), (double)AXIS_MASK);
-}
-
 // keys[id] = the cell key of a source (~0 otherwise), vals[id] = its slot
 __global__ __launch_bounds__(GB) void grad_keys(const double *__restrict__ x, const double *__restrict__ y,
                                                 const double *__restrict__ z, const int32_t *__restrict__ orig, int64_t n_slots,
@@ -217,27 +207,9 @@ __global__ __launch_bounds__(GB) void grad_keys(const double *__restrict__ x, co
     if (!live(s, i, id)) return;
     const double px = x[i], py = y[i], pz = z[i];
     uint64_t key = ~0ull;
-    if (finite3(px, py, pz)) {
-        const double ie = info->inv_e;
-        key = (cell_axis(px, info->lo[0], ie) << (2 * AXIS_BITS)) | (cell_axis(py, info->lo[1], ie) << AXIS_BITS) |
-              cell_axis(pz, info->lo[2], ie);
-    }
+    if (finite3(px, py, pz)) key = cell_key(px, py, pz, info->lo, info->inv_e);
     keys[id] = key;
     vals[id] = (uint32_t)i;
-}
-
-__device__ __forceinline__ uint64_t hash_mix(uint64_t k) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
-    return k ^ (k >> 33);
-}
-
-__device__ __forceinline__ int64_t hash_slot(const Ent *__restrict__ tab, uint64_t mask, uint64_t key) {
-    for (uint64_t t = hash_mix(key) & mask;; t = (t + 1) & mask) {
-        const uint64_t k = tab[t].key;
-        if (k == key) return (int64_t)t;
-        if (k == ~0ull) return -1;
-    }
 }
 
 // {x, y, z, m}, the values (stride KS), the original id and the target flag in sorted order; every cell's first position
@@ -258,24 +230,12 @@ __global__ __launch_bounds__(GB) void grad_gather(const double *__restrict__ x, 
     for (int k = 0; k < nf; k++) av[p * ks + k] = vf.by_id[k] ? vf.ptr[k][id] : vf.ptr[k][i];
     sid[p] = id;
     tflag[p] = (info->bad == 0 && id < s.n_owned && inside(s, px, py, pz)) ? 1 : 0;
-    const uint64_t key = skey[p];
-    if (p > 0 && skey[p - 1] == key) return;
-    for (uint64_t t = hash_mix(key) & mask;; t = (t + 1) & mask) {
-        const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&tab[t].key), ~0ull,
-                                                  (unsigned long long)key);
-        if (prev == ~0ull) { tab[t].start = (int32_t)p; return; }     // every key is inserted once: by its first position
-    }
+    cell_enter(skey, p, tab, mask);
 }
 
 __global__ __launch_bounds__(GB) void grad_tails(const uint64_t *__restrict__ skey, const Info *__restrict__ info, int64_t n,
                                                  Ent *__restrict__ tab, uint64_t mask) {
-    const int64_t p = (int64_t)blockIdx.x * GB + threadIdx.x;
-    const int64_t ns = info->n_src;
-    if (p >= n || p >= ns) return;
-    const uint64_t key = skey[p];
-    if (p + 1 < ns && skey[p + 1] == key) return;
-    const int64_t t = hash_slot(tab, mask, key);           // put there by the cell's first position
-    if (t >= 0) tab[t].end = (int32_t)(p + 1);
+    cell_close(skey, (int64_t)blockIdx.x * GB + threadIdx.x, n, info->n_src, tab, mask);
 }
 
 // one lane per target (t-th target in sorted order: sorted position tlist[t])
@@ -385,52 +345,29 @@ hipError_t launch_walk(bool corrected, unsigned nb, hipStream_t st, const double
     return hipGetLastError();
 }
 
-#define GD_HIP(expr)                                                        \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) {                                             \
-            c->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return SPH_ERR_HIP;                                             \
-        }                                                                   \
-    } while (0)
-
-#define GD_TRY(expr)                   \
-    do {                               \
-        int _s = (expr);               \
-        if (_s != SPH_OK) return _s;   \
-    } while (0)
-
-size_t align_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int gd_arg(sph_ctx *c, const char *what) {
-    c->err = std::string("sph_gradients: ") + what;
-    return SPH_ERR_ARG;
-}
-
-unsigned blocks(int64_t n, int per) { return (unsigned)std::max<int64_t>((n + per - 1) / per, 1); }
-
 }  // namespace
 
 int gradients_run(sph_ctx *c, const sph_gradients_desc *d, const double *values, double *out, int64_t n_out, double *rho_out,
                   int64_t *counts, bool host, bool (*ready)(const sph_ctx *, int)) {
-    if (!d) return gd_arg(c, "null descriptor");
-    if (d->reserved[0] != 0 || d->reserved[1] != 0) return gd_arg(c, "reserved must be 0");
-    if (d->flags & ~SPH_GRAD_CORRECTED) return gd_arg(c, "unknown flags");
+    const char *who = "sph_gradients";
+    if (!d) return arg_error(c, who, "null descriptor");
+    if (d->reserved[0] != 0 || d->reserved[1] != 0) return arg_error(c, who, "reserved must be 0");
+    if (d->flags & ~SPH_GRAD_CORRECTED) return arg_error(c, who, "unknown flags");
     const int nf = d->n_fields;
-    if (nf < 1 || nf > SPH_GRAD_MAX_FIELDS) return gd_arg(c, "n_fields must be 1 .. SPH_GRAD_MAX_FIELDS");
+    if (nf < 1 || nf > SPH_GRAD_MAX_FIELDS) return arg_error(c, who, "n_fields must be 1 .. SPH_GRAD_MAX_FIELDS");
     bool any_values = false;
     for (int k = 0; k < nf; k++) {
         if (d->fields[k] != SPH_GRAD_VALUES && (d->fields[k] < 0 || d->fields[k] >= SPH_F_COUNT))
-            return gd_arg(c, "field id out of range");
+            return arg_error(c, who, "field id out of range");
         any_values = any_values || d->fields[k] == SPH_GRAD_VALUES;
     }
-    if (any_values != (values != nullptr)) return gd_arg(c, "values must be given with SPH_GRAD_VALUES and only then");
+    if (any_values != (values != nullptr)) return arg_error(c, who, "values must be given with SPH_GRAD_VALUES and only then");
     const int64_t n = c->n;
-    if (n_out != 3 * (int64_t)nf * n) return gd_arg(c, "n_out != 3 n_fields sph_count");
-    if (!out && n_out > 0) return gd_arg(c, "null output");
-    if (std::isnan(d->h) || d->h < 0.0) return gd_arg(c, "h must be >= 0");
+    if (n_out != 3 * (int64_t)nf * n) return arg_error(c, who, "n_out != 3 n_fields sph_count");
+    if (!out && n_out > 0) return arg_error(c, who, "null output");
+    if (std::isnan(d->h) || d->h < 0.0) return arg_error(c, who, "h must be >= 0");
     for (int a = 0; a < 3; a++)
-        if (std::isnan(d->clip_lo[a]) || std::isnan(d->clip_hi[a])) return gd_arg(c, "the clip box has a NaN");
+        if (std::isnan(d->clip_lo[a]) || std::isnan(d->clip_hi[a])) return arg_error(c, who, "the clip box has a NaN");
     for (int k = 0; k < nf; k++)
         if (d->fields[k] >= 0 && !ready(c, d->fields[k])) {
             c->err = "sph_gradients: a field is stale (as sph_download_field would refuse it)";
@@ -450,7 +387,7 @@ int gradients_run(sph_ctx *c, const sph_gradients_desc *d, const double *values,
         if (host) {
             if (counts) { counts[0] = 0; counts[1] = 0; }
         } else if (counts) {
-            GD_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), st));
+            SPH_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), st));
         }
         return SPH_OK;
     }
@@ -459,38 +396,49 @@ int gradients_run(sph_ctx *c, const sph_gradients_desc *d, const double *values,
     int64_t tl = 1;
     while (tl < 2 * n) tl <<= 1;                                 // hash table: load <= 1/2
     size_t sort_bytes = 0, select_bytes = 0;
-    GD_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                     (uint32_t *)nullptr, (size_t)n, 0u, 64u, st));
-    GD_HIP(rocprim::select(nullptr, select_bytes, rocprim::counting_iterator<int32_t>(0), (const uint8_t *)nullptr,
-                           (int32_t *)nullptr, (uint32_t *)nullptr, (size_t)n, st));
-    // scratch: keys, keys_alt, vals, vals_alt, sort, select, rec, av, sid, tflag, tlist, select count, table, box partials,
-    // histogram, info, values (host form), out (host form), rho (host form)
-    const size_t sizes[19] = {8 * (size_t)n, 8 * (size_t)n, 4 * (size_t)n, 4 * (size_t)n, sort_bytes, select_bytes,
-                              32 * (size_t)n, 8 * (size_t)ks * (size_t)n, 4 * (size_t)n, (size_t)n, 4 * (size_t)n, 8,
-                              sizeof(Ent) * (size_t)tl, 8 * NBP * (size_t)nb, per_particle ? 4 * (size_t)HBINS : 0, sizeof(Info),
-                              host && values ? 8 * (size_t)nf * (size_t)n : 0, host ? 8 * (size_t)n_out : 0,
-                              host && rho_out ? 8 * (size_t)n : 0};
-    size_t off[19], bytes = 0;
-    for (int k = 0; k < 19; k++) { off[k] = bytes; bytes += align_up(sizes[k]); }
+    SPH_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
+                                      (uint32_t *)nullptr, (size_t)n, 0u, 64u, st));
+    SPH_HIP(rocprim::select(nullptr, select_bytes, rocprim::counting_iterator<int32_t>(0), (const uint8_t *)nullptr,
+                            (int32_t *)nullptr, (uint32_t *)nullptr, (size_t)n, st));
+    uint64_t *keys, *keys_alt;
+    uint32_t *vals, *vals_alt, *sel_count, *hist_buf;
+    char *sort_tmp, *select_tmp;
+    double4 *rec;
+    Ent *tab;
+    Info *info;
+    int32_t *sid, *tlist;
+    uint8_t *tflag;
+    double *av, *box_part, *h_values, *h_out, *h_rho;
+    auto layout = [&](Carve cv) {
+        keys = cv.take<uint64_t>(n);
+        keys_alt = cv.take<uint64_t>(n);
+        vals = cv.take<uint32_t>(n);
+        vals_alt = cv.take<uint32_t>(n);
+        sort_tmp = cv.take<char>(sort_bytes);
+        select_tmp = cv.take<char>(select_bytes);
+        rec = cv.take<double4>(n);
+        av = cv.take<double>((size_t)ks * (size_t)n);
+        sid = cv.take<int32_t>(n);
+        tflag = cv.take<uint8_t>(n);
+        tlist = cv.take<int32_t>(n);
+        sel_count = cv.take<uint32_t>(1);
+        tab = cv.take<Ent>(tl);
+        box_part = cv.take<double>(NBP * (size_t)nb);
+        hist_buf = cv.take<uint32_t>(per_particle ? HBINS : 0);
+        info = cv.take<Info>(1);
+        h_values = cv.take<double>(host && values ? (size_t)nf * (size_t)n : 0);     // the host form's device copies
+        h_out = cv.take<double>(host ? n_out : 0);
+        h_rho = cv.take<double>(host && rho_out ? n : 0);
+        return cv.bytes;
+    };
     char *buf = nullptr;
-    GD_TRY(render_scratch(c, bytes, &buf));
-    uint64_t *keys = reinterpret_cast<uint64_t *>(buf + off[0]), *keys_alt = reinterpret_cast<uint64_t *>(buf + off[1]);
-    uint32_t *vals = reinterpret_cast<uint32_t *>(buf + off[2]), *vals_alt = reinterpret_cast<uint32_t *>(buf + off[3]);
-    void *sort_tmp = buf + off[4], *select_tmp = buf + off[5];
-    double4 *rec = reinterpret_cast<double4 *>(buf + off[6]);
-    double *av = reinterpret_cast<double *>(buf + off[7]);
-    int32_t *sid = reinterpret_cast<int32_t *>(buf + off[8]);
-    uint8_t *tflag = reinterpret_cast<uint8_t *>(buf + off[9]);
-    int32_t *tlist = reinterpret_cast<int32_t *>(buf + off[10]);
-    uint32_t *sel_count = reinterpret_cast<uint32_t *>(buf + off[11]);
-    Ent *tab = reinterpret_cast<Ent *>(buf + off[12]);
-    double *box_part = reinterpret_cast<double *>(buf + off[13]);
-    uint32_t *hist = per_particle ? reinterpret_cast<uint32_t *>(buf + off[14]) : nullptr;
-    Info *info = reinterpret_cast<Info *>(buf + off[15]);
-    const double *d_values = host && values ? reinterpret_cast<double *>(buf + off[16]) : values;
-    double *d_out = host ? reinterpret_cast<double *>(buf + off[17]) : out;
-    double *d_rho = host ? (rho_out ? reinterpret_cast<double *>(buf + off[18]) : nullptr) : rho_out;
-    if (host && !c->rnd_pinned) GD_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->rnd_pinned), 32 * sizeof(double), hipHostMallocDefault));
+    SPH_TRY(analysis_scratch(c, layout(Carve{}), &buf));
+    layout(Carve{buf});
+    uint32_t *hist = per_particle ? hist_buf : nullptr;
+    const double *d_values = host && values ? h_values : values;
+    double *d_out = host ? h_out : out;
+    double *d_rho = host ? (rho_out ? h_rho : nullptr) : rho_out;
+    if (host) SPH_TRY(analysis_pinned(c));
 
     Sel s{};
     for (int a = 0; a < 3; a++) { s.clip_lo[a] = d->clip_lo[a]; s.clip_hi[a] = d->clip_hi[a]; }
@@ -503,33 +451,33 @@ int gradients_run(sph_ctx *c, const sph_gradients_desc *d, const double *values,
         const bool by_id = d->fields[k] == SPH_GRAD_VALUES;
         vf.by_id[k] = by_id ? 1 : 0;
         vf.ptr[k] = by_id ? d_values + (size_t)k * (size_t)n : c->f[d->fields[k]];
-        if (by_id && host) GD_HIP(hipMemcpyAsync(const_cast<double *>(vf.ptr[k]), values + (size_t)k * (size_t)n,
-                                                 (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+        if (by_id && host) SPH_HIP(hipMemcpyAsync(const_cast<double *>(vf.ptr[k]), values + (size_t)k * (size_t)n,
+                                                  (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
     }
     const double *x = c->f[SPH_F_X], *y = c->f[SPH_F_Y], *z = c->f[SPH_F_Z];
 
     // every row NaN until its target writes it
-    GD_HIP(hipMemsetAsync(d_out, 0xff, (size_t)n_out * sizeof(double), st));
-    if (d_rho) GD_HIP(hipMemsetAsync(d_rho, 0xff, (size_t)n * sizeof(double), st));
+    SPH_HIP(hipMemsetAsync(d_out, 0xff, (size_t)n_out * sizeof(double), st));
+    if (d_rho) SPH_HIP(hipMemsetAsync(d_rho, 0xff, (size_t)n * sizeof(double), st));
     // selection, box, cell edge
-    if (hist) GD_HIP(hipMemsetAsync(hist, 0, 4 * (size_t)HBINS, st));
+    if (hist) SPH_HIP(hipMemsetAsync(hist, 0, 4 * (size_t)HBINS, st));
     grad_select<<<dim3((unsigned)nb), dim3(GB), 0, st>>>(x, y, z, c->orig, ns, s, box_part, hist);
     grad_box<<<dim3(1), dim3(WAVE), 0, st>>>(box_part, nb, hist, h_one, info);
-    GD_HIP(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     // cell keys by original id, sort, hash table over the occupied cells
     grad_keys<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(x, y, z, c->orig, ns, s, info, keys, vals);
     size_t tmp = sort_bytes;
-    GD_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)n, 0u, 64u, st));
-    GD_HIP(hipMemsetAsync(tab, 0xff, sizeof(Ent) * (size_t)tl, st));
-    GD_HIP(hipMemsetAsync(tflag, 0, (size_t)n, st));
+    SPH_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)n, 0u, 64u, st));
+    SPH_HIP(hipMemsetAsync(tab, 0xff, sizeof(Ent) * (size_t)tl, st));
+    SPH_HIP(hipMemsetAsync(tflag, 0, (size_t)n, st));
     grad_gather<<<dim3(blocks(n, GB)), dim3(GB), 0, st>>>(x, y, z, c->f[SPH_F_M], c->orig, s, vf, nf, ks, keys_alt, vals_alt,
                                                            info, n, rec, av, sid, tflag, tab, (uint64_t)(tl - 1));
     grad_tails<<<dim3(blocks(n, GB)), dim3(GB), 0, st>>>(keys_alt, info, n, tab, (uint64_t)(tl - 1));
-    GD_HIP(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     // the targets in sorted order
     tmp = select_bytes;
-    GD_HIP(rocprim::select(select_tmp, tmp, rocprim::counting_iterator<int32_t>(0), (const uint8_t *)tflag, tlist, sel_count,
-                           (size_t)n, st));
+    SPH_HIP(rocprim::select(select_tmp, tmp, rocprim::counting_iterator<int32_t>(0), (const uint8_t *)tflag, tlist, sel_count,
+                            (size_t)n, st));
     const unsigned wb = blocks(n, GB);
     hipError_t e = hipSuccess;
     switch (nf) {
@@ -538,16 +486,16 @@ int gradients_run(sph_ctx *c, const sph_gradients_desc *d, const double *values,
         case 3: e = launch_walk<3>(corrected, wb, st, rec, av, sid, keys_alt, vals_alt, tlist, info, n, tab, (uint64_t)(tl - 1), h_one, s.hf, d_out, d_rho); break;
         default: e = launch_walk<4>(corrected, wb, st, rec, av, sid, keys_alt, vals_alt, tlist, info, n, tab, (uint64_t)(tl - 1), h_one, s.hf, d_out, d_rho); break;
     }
-    GD_HIP(e);
+    SPH_HIP(e);
     if (!host) {
-        if (counts) GD_HIP(hipMemcpyAsync(counts, info->counts, 2 * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        if (counts) SPH_HIP(hipMemcpyAsync(counts, info->counts, 2 * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
         return SPH_OK;
     }
     // host form: the counts, the rows and rho~ in one read-back
-    GD_HIP(hipMemcpyAsync(c->rnd_pinned, info->counts, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    GD_HIP(hipMemcpyAsync(out, d_out, (size_t)n_out * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (rho_out) GD_HIP(hipMemcpyAsync(rho_out, d_rho, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    GD_HIP(hipStreamSynchronize(st));
+    SPH_HIP(hipMemcpyAsync(c->rnd_pinned, info->counts, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    SPH_HIP(hipMemcpyAsync(out, d_out, (size_t)n_out * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (rho_out) SPH_HIP(hipMemcpyAsync(rho_out, d_rho, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    SPH_HIP(hipStreamSynchronize(st));
     int64_t cnt[2] = {0, 0};
     std::memcpy(cnt, c->rnd_pinned, sizeof(cnt));
     if (cnt[0] < 0) {

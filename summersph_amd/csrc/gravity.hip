@@ -476,15 +476,6 @@ __global__ __launch_bounds__(GB) void grav_potential_wave(int nt, int n, const W
 
 }  // namespace
 
-#define GR_CHECK2(expr)                                                     \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) {                                             \
-            c->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return SPH_ERR_HIP;                                             \
-        }                                                                   \
-    } while (0)
-
 hipError_t grav_sort_tmp_bytes(int64_t n, size_t *bytes) {
     size_t b = 0;
     hipError_t e = rocprim::radix_sort_pairs(nullptr, b, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
@@ -528,7 +519,7 @@ static int gravity_reserve(sph_ctx *c, int64_t need) {
     G_ALLOC(c->g_vals, cap, "tree vals"); G_ALLOC(c->g_vals_alt, cap, "tree vals (alt)");
 #undef G_ALLOC
     size_t tmp = 0;
-    GR_CHECK2(grav_sort_tmp_bytes((int64_t)cap, &tmp));
+    SPH_HIP(grav_sort_tmp_bytes((int64_t)cap, &tmp));
     if (ctx_alloc_bytes(c, &c->g_sort_tmp, tmp ? tmp : 1, "tree sort scratch") != SPH_OK) return SPH_ERR_NOMEM;
     c->g_sort_tmp_bytes = tmp;
     c->g_cap = (int64_t)cap;
@@ -549,9 +540,9 @@ int global_keys_sorted(sph_ctx *c) {
     }
     rb.size = size;
     grav_keys<<<dim3((unsigned)((n + GB - 1) / GB)), dim3(GB), 0, c->stream>>>(rb, reinterpret_cast<const double4 *>(c->gx_src), n, c->g_keys, c->g_vals);
-    GR_CHECK2(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     size_t tmp = c->g_sort_tmp_bytes;
-    GR_CHECK2(rocprim::radix_sort_pairs(c->g_sort_tmp, tmp, c->g_keys, c->g_keys_alt, c->g_vals, c->g_vals_alt, (size_t)n, 0u, 63u, c->stream));
+    SPH_HIP(rocprim::radix_sort_pairs(c->g_sort_tmp, tmp, c->g_keys, c->g_keys_alt, c->g_vals, c->g_vals_alt, (size_t)n, 0u, 63u, c->stream));
     c->gx_keys_valid = true;
     return SPH_OK;
 }
@@ -579,7 +570,7 @@ static int tree_from_sorted_keys(sph_ctx *c, const double4 *drec, int64_t n, con
     node_finish<<<dim3(gb), dim3(GB), 0, c->stream>>>((int)n, t);
     node_walk_records<<<dim3(gb), dim3(GB), 0, c->stream>>>((int)n, t);
     node_wave_records<<<dim3(gb), dim3(GB), 0, c->stream>>>((int)n, t, rb, c->p.theta * c->p.theta, c->p.G, reinterpret_cast<WalkRec *>(c->g_wrec), c->g_leaf_of);
-    GR_CHECK2(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     return SPH_OK;
 }
 
@@ -613,13 +604,13 @@ int gravity_tree_build(sph_ctx *c) {
     } else {
         if (c->path_keys_valid && c->mkeys_alt && c->mvals_alt) {
             // variable h: the leaf-box build of this grid build sorted the same keys (same positions, same root box)
-            GR_CHECK2(hipMemcpyAsync(c->g_keys_alt, c->mkeys_alt, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
-            GR_CHECK2(hipMemcpyAsync(c->g_vals_alt, c->mvals_alt, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+            SPH_HIP(hipMemcpyAsync(c->g_keys_alt, c->mkeys_alt, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+            SPH_HIP(hipMemcpyAsync(c->g_vals_alt, c->mvals_alt, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
         } else {
             grav_keys<<<dim3(gb), dim3(GB), 0, c->stream>>>(rb, drec, n, c->g_keys, c->g_vals);
-            GR_CHECK2(hipGetLastError());
+            SPH_HIP(hipGetLastError());
             size_t tmp = c->g_sort_tmp_bytes;
-            GR_CHECK2(rocprim::radix_sort_pairs(c->g_sort_tmp, tmp, c->g_keys, c->g_keys_alt, c->g_vals, c->g_vals_alt, (size_t)n, 0u, 63u, c->stream));
+            SPH_HIP(rocprim::radix_sort_pairs(c->g_sort_tmp, tmp, c->g_keys, c->g_keys_alt, c->g_vals, c->g_vals_alt, (size_t)n, 0u, 63u, c->stream));
         }
     }
     return tree_from_sorted_keys(c, drec, n, rb);
@@ -637,9 +628,9 @@ int gravity_tree_build_records(sph_ctx *c, const double *rec, int64_t n, const d
     const RootBox rb = root_of(box);
     const double4 *drec = reinterpret_cast<const double4 *>(rec);
     grav_keys<<<dim3((unsigned)((n + GB - 1) / GB)), dim3(GB), 0, c->stream>>>(rb, drec, n, c->g_keys, c->g_vals);
-    GR_CHECK2(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     size_t tmp = c->g_sort_tmp_bytes;
-    GR_CHECK2(rocprim::radix_sort_pairs(c->g_sort_tmp, tmp, c->g_keys, c->g_keys_alt, c->g_vals, c->g_vals_alt, (size_t)n, 0u, 63u, c->stream));
+    SPH_HIP(rocprim::radix_sort_pairs(c->g_sort_tmp, tmp, c->g_keys, c->g_keys_alt, c->g_vals, c->g_vals_alt, (size_t)n, 0u, 63u, c->stream));
     return tree_from_sorted_keys(c, drec, n, rb);
 }
 

@@ -450,15 +450,6 @@ hipError_t launch_unpermute(sph_ctx *c, const double *src_sorted, double *dst_or
 
 // device-side cell key for the pair kernels lives in pairs.hip (same formula)
 
-#define GR_CHECK(expr)                                                      \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) {                                             \
-            c->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return SPH_ERR_HIP;                                             \
-        }                                                                   \
-    } while (0)
-
 // bounding box of the owned particles at their current positions -> d_out6 (device) and/or h_out6 (host, synchronises)
 int owned_bbox(sph_ctx *c, double *d_out6, double *h_out6) {
     hipStream_t st = c->stream;
@@ -469,11 +460,11 @@ int owned_bbox(sph_ctx *c, double *d_out6, double *h_out6) {
     bbox_partial<<<dim3(nb), dim3(BB_BLOCK), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], ns, c->bbox_part, c->d_flags + 2,
                                                       c->orig, (int32_t)c->n_owned, 0, 1);
     bbox_final<<<dim3(1), dim3(384), 0, st>>>(c->bbox_part, nb, res);
-    GR_CHECK(hipGetLastError());
-    if (d_out6) GR_CHECK(hipMemcpyAsync(d_out6, res, 6 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    SPH_HIP(hipGetLastError());
+    if (d_out6) SPH_HIP(hipMemcpyAsync(d_out6, res, 6 * sizeof(double), hipMemcpyDeviceToDevice, st));
     if (h_out6) {
-        GR_CHECK(hipMemcpyAsync(c->h_pinned + 48, res, 6 * sizeof(double), hipMemcpyDeviceToHost, st));
-        GR_CHECK(hipStreamSynchronize(st));
+        SPH_HIP(hipMemcpyAsync(c->h_pinned + 48, res, 6 * sizeof(double), hipMemcpyDeviceToHost, st));
+        SPH_HIP(hipStreamSynchronize(st));
         for (int a = 0; a < 6; a++) h_out6[a] = c->h_pinned[48 + a];
     }
     return SPH_OK;
@@ -490,7 +481,7 @@ static int reorder_sorted(sph_ctx *c) {
     ra.nf = 9; ra.prec = nullptr;
     if (c->variable) { ra.src[9] = c->f[SPH_F_H]; ra.dst[9] = c->f_alt[9]; ra.nf = 10; ra.prec = c->prec; }
     reorder<<<dim3(gb), dim3(256), 0, st>>>(ra, c->vals_alt, c->orig, c->orig_alt, c->inv, c->drec, n);
-    GR_CHECK(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     for (int k = 0; k < 9; k++) std::swap(c->f[k], c->f_alt[k]);
     if (c->variable) std::swap(c->f[SPH_F_H], c->f_alt[9]);
     std::swap(c->orig, c->orig_alt);
@@ -525,9 +516,9 @@ static int hash_build(sph_ctx *c, bool swap) {
         int64_t tl = 1;
         while (tl < 4 * cap) tl <<= 1;            // two keys per occupied cell at most 2 cap: load factor <= 1/2
         size_t sort_b = 0, scan_b = 0;
-        GR_CHECK(rocprim::radix_sort_pairs(nullptr, sort_b, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                           (uint32_t *)nullptr, (size_t)cap, 0u, 64u, st));
-        GR_CHECK(rocprim::inclusive_scan(nullptr, scan_b, (int32_t *)nullptr, (int32_t *)nullptr, (size_t)cap, rocprim::plus<int32_t>(), st));
+        SPH_HIP(rocprim::radix_sort_pairs(nullptr, sort_b, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
+                                          (uint32_t *)nullptr, (size_t)cap, 0u, 64u, st));
+        SPH_HIP(rocprim::inclusive_scan(nullptr, scan_b, (int32_t *)nullptr, (int32_t *)nullptr, (size_t)cap, rocprim::plus<int32_t>(), st));
         const int64_t before = c->device_bytes;
         const size_t tmp = std::max(sort_b, scan_b);
         if (ctx_alloc(c, &c->hkeys, (size_t)cap, "hashed grid keys") != SPH_OK ||
@@ -559,22 +550,22 @@ static int hash_build(sph_ctx *c, bool swap) {
     const unsigned gbs = (unsigned)((ns + 255) / 256), gb = (unsigned)((std::max<int64_t>(n, 1) + 255) / 256);
     hash_keys<<<dim3(gbs), dim3(256), 0, st>>>(g, sh1, sh2, c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], ns, c->hkeys, c->vals,
                                                c->orig, (int32_t)c->n_owned, c->dead_below);
-    GR_CHECK(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     size_t tmp = c->hash_tmp_bytes;
-    GR_CHECK(rocprim::radix_sort_pairs(c->hash_tmp, tmp, c->hkeys, c->hkeys_alt, c->vals, c->vals_alt, (size_t)ns, 0u, bits, st));
+    SPH_HIP(rocprim::radix_sort_pairs(c->hash_tmp, tmp, c->hkeys, c->hkeys_alt, c->vals, c->vals_alt, (size_t)ns, 0u, bits, st));
     c->n_slots = n; c->dead_below = 0;     // the replaced ghosts sorted behind the n live entries and are dropped here
-    GR_CHECK(hipMemsetAsync(c->d_m, 0, sizeof(int32_t), st));          // no live particle: no cell (hash_compact writes nothing)
-    GR_CHECK(hipMemsetAsync(c->ustart, 0, sizeof(int32_t), st));
+    SPH_HIP(hipMemsetAsync(c->d_m, 0, sizeof(int32_t), st));          // no live particle: no cell (hash_compact writes nothing)
+    SPH_HIP(hipMemsetAsync(c->ustart, 0, sizeof(int32_t), st));
     if (n > 0) {
         hash_heads<<<dim3(gb), dim3(256), 0, st>>>(c->hkeys_alt, n, c->uidx);
-        GR_CHECK(hipGetLastError());
+        SPH_HIP(hipGetLastError());
         tmp = c->hash_tmp_bytes;
-        GR_CHECK(rocprim::inclusive_scan(c->hash_tmp, tmp, c->uidx, c->uidx, (size_t)n, rocprim::plus<int32_t>(), st));
+        SPH_HIP(rocprim::inclusive_scan(c->hash_tmp, tmp, c->uidx, c->uidx, (size_t)n, rocprim::plus<int32_t>(), st));
         hash_compact<<<dim3(gb), dim3(256), 0, st>>>(c->hkeys_alt, c->uidx, n, c->ukey, c->ustart, c->d_m);
     }
-    GR_CHECK(hipMemsetAsync(c->htab, 0xff, sizeof(HashEnt) * (size_t)c->htab_len, st));
+    SPH_HIP(hipMemsetAsync(c->htab, 0xff, sizeof(HashEnt) * (size_t)c->htab_len, st));
     hash_insert<<<dim3(gb), dim3(256), 0, st>>>(c->ukey, c->ustart, c->d_m, c->htab, (uint64_t)(c->htab_len - 1));
-    GR_CHECK(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     c->hv.tab = c->htab; c->hv.ukey = c->ukey; c->hv.ustart = c->ustart; c->hv.m = c->d_m;
     c->hv.mask = (uint64_t)(c->htab_len - 1); c->hv.sh1 = sh1; c->hv.sh2 = sh2;
     return SPH_OK;
@@ -595,19 +586,19 @@ int grid_rebuild(sph_ctx *c) {
     const int p = c->ring_bbox;
     double *slot = c->h_pinned + 200 + 16 * p;
     bbox_final<<<dim3(1), dim3(384), 0, st>>>(c->bbox_part, nb, c->bbox_part + (size_t)BB_MAX_BLOCKS * 6, slot, c->d_flags);
-    GR_CHECK(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     // the exact box of the current positions -> read-back slot p.  Who needs it NOW (octree root boxes: variable h,
     // self-gravity, accretion; the first build of a particle set) waits for it; the plain fixed-h path takes the box of the
     // previous build, which arrived long ago, widened by one cell: particles outside the grid's box are clamped into its
     // boundary cells and still meet all their neighbours there, so the box only has to be roughly right.
-    GR_CHECK(hipEventRecord(c->ev_bbox[p], st));        // bbox_final wrote the slot itself (pinned memory)
+    SPH_HIP(hipEventRecord(c->ev_bbox[p], st));        // bbox_final wrote the slot itself (pinned memory)
     const bool stale = c->ring_bbox_valid && !c->no_stale && !c->variable && !c->gravity && !(c->p.flags & SPH_FLAG_ACCRETE_CULL);
     const double *bb = slot;
     if (stale) {
-        GR_CHECK(hipEventSynchronize(c->ev_bbox[1 - p]));
+        SPH_HIP(hipEventSynchronize(c->ev_bbox[1 - p]));
         bb = c->h_pinned + 200 + 16 * (1 - p);
     } else {
-        GR_CHECK(hipStreamSynchronize(st));
+        SPH_HIP(hipStreamSynchronize(st));
         c->host_syncs++;
     }
     c->ring_bbox = 1 - p; c->ring_bbox_valid = true; c->bbox_exact = !stale;
@@ -661,9 +652,9 @@ int grid_rebuild(sph_ctx *c) {
             moment_partial<<<dim3(nb), dim3(BB_BLOCK), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], ns, bx, mpart, c->orig,
                                                                 (int32_t)c->n_owned, c->dead_below);
             moment_final<<<dim3(1), dim3(448), 0, st>>>(mpart, nb, mpart + (size_t)BB_MAX_BLOCKS * 7);
-            GR_CHECK(hipGetLastError());
-            GR_CHECK(hipMemcpyAsync(c->h_pinned + 280, mpart + (size_t)BB_MAX_BLOCKS * 7, 7 * sizeof(double), hipMemcpyDeviceToHost, st));
-            GR_CHECK(hipStreamSynchronize(st));
+            SPH_HIP(hipGetLastError());
+            SPH_HIP(hipMemcpyAsync(c->h_pinned + 280, mpart + (size_t)BB_MAX_BLOCKS * 7, 7 * sizeof(double), hipMemcpyDeviceToHost, st));
+            SPH_HIP(hipStreamSynchronize(st));
             c->host_syncs++;
             const double *mo = c->h_pinned + 280;
             if (!(mo[0] >= 1.0)) break;
@@ -746,33 +737,33 @@ int grid_rebuild(sph_ctx *c) {
     size_t scan_tmp = 0;
     bool counting = !force_radix && g.ncells <= 4 * ns + 1000000;
     if (counting) {
-        GR_CHECK(rocprim::exclusive_scan(nullptr, scan_tmp, c->cell_start, c->cell_start, 0, (size_t)(g.ncells + 2), rocprim::plus<int32_t>(), st));
+        SPH_HIP(rocprim::exclusive_scan(nullptr, scan_tmp, c->cell_start, c->cell_start, 0, (size_t)(g.ncells + 2), rocprim::plus<int32_t>(), st));
         counting = scan_tmp <= c->sort_tmp_bytes;
     }
     if (counting) {
         const size_t table = ((size_t)(g.ncells + 2) + 3) & ~(size_t)3, cursors = ((size_t)(g.ncells + 1) + 3) & ~(size_t)3;
         c->cell_fill = c->cell_start + table;
-        GR_CHECK(hipMemsetAsync(c->cell_start, 0, sizeof(int32_t) * (table + cursors), st));        // multiples of 16 bytes: one fill kernel
+        SPH_HIP(hipMemsetAsync(c->cell_start, 0, sizeof(int32_t) * (table + cursors), st));        // multiples of 16 bytes: one fill kernel
         cell_keys_count<<<dim3(gbs), dim3(256), 0, st>>>(g, c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], ns, c->keys, c->cell_start,
                                                         c->orig, (int32_t)c->n_owned, c->dead_below);
-        GR_CHECK(hipGetLastError());
+        SPH_HIP(hipGetLastError());
         // in place: cell_start[c] = first sorted slot of cell c; [ncells] = live particles; the replaced ghosts sort behind them
-        GR_CHECK(rocprim::exclusive_scan(c->sort_tmp, scan_tmp, c->cell_start, c->cell_start, 0, (size_t)(g.ncells + 2), rocprim::plus<int32_t>(), st));
+        SPH_HIP(rocprim::exclusive_scan(c->sort_tmp, scan_tmp, c->cell_start, c->cell_start, 0, (size_t)(g.ncells + 2), rocprim::plus<int32_t>(), st));
         cell_scatter<<<dim3(gbs), dim3(256), 0, st>>>(c->keys, ns, c->cell_start, c->cell_fill, c->vals);
         cell_rank<<<dim3(gb), dim3(256), 0, st>>>(c->keys, n, c->cell_start, c->vals, c->vals_alt);
-        GR_CHECK(hipGetLastError());
+        SPH_HIP(hipGetLastError());
         c->n_slots = n; c->dead_below = 0;
     } else {
         cell_keys<<<dim3(gbs), dim3(256), 0, st>>>(g, c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], ns, c->keys,
                                                   c->vals, c->orig, (int32_t)c->n_owned, c->dead_below);
-        GR_CHECK(hipGetLastError());
+        SPH_HIP(hipGetLastError());
         unsigned bits = 1;
         while (bits < 32 && ((int64_t)1 << bits) < g.ncells + (swap ? 1 : 0)) bits++;
         size_t tmp = c->sort_tmp_bytes;
-        GR_CHECK(rocprim::radix_sort_pairs(c->sort_tmp, tmp, c->keys, c->keys_alt, c->vals, c->vals_alt, (size_t)ns, 0u, bits, st));
+        SPH_HIP(rocprim::radix_sort_pairs(c->sort_tmp, tmp, c->keys, c->keys_alt, c->vals, c->vals_alt, (size_t)ns, 0u, bits, st));
         c->n_slots = n; c->dead_below = 0;     // the replaced ghosts sorted behind the n live entries and are dropped here
         cell_table<<<dim3((unsigned)((g.ncells + 1 + 255) / 256)), dim3(256), 0, st>>>(c->keys_alt, n, g.ncells, c->cell_start);
-        GR_CHECK(hipGetLastError());
+        SPH_HIP(hipGetLastError());
     }
 
     return reorder_sorted(c);

@@ -2,7 +2,7 @@
 // every two selected particles closer than a linking length (include/summersph.h, sph_groups).
 //
 // Not part of the step loop: nothing here reads or writes the context's grid, cell table, neighbour list, statistics or
-// flags.  The scratch is the render's (render_scratch).
+// flags.  The scratch is the one the analysis calls share (analysis_scratch).
 //
 // Pipeline (all on ctx->stream; counts, box and cell edge stay on the device):
 //   groups_select    every slot: the selection; parent[id] = id (selected) or -1, count 0, number -1; per-block box, h_max,
@@ -45,7 +45,8 @@
 #include <cstring>
 #include <vector>
 
-#include "sph_internal.hpp"
+#include "cell_table.hpp"
+#include "reduce_common.hpp"
 
 // the predicate and the per-particle arithmetic are written in one documented order (summersph.h); no contraction into
 // fused multiply-adds, so that the numpy restatement reproduces them bit for bit
@@ -57,15 +58,11 @@ namespace {
 
 constexpr int GB = 256;                    // block of the per-slot kernels
 constexpr int BOX_BLOCKS = 1024;           // select blocks at most (grid-stride beyond)
-constexpr int PIECE = 16 * WAVE;           // sorted positions per piece: 16 per lane
 constexpr int NP1 = 8;                     // first pass: M, sum m r (3), sum m v (3), sum m u
 constexpr int NP2 = 9;                     // second pass: sum m d2, spin (3), K_int, r_max, rho_max, its id, its slot
 constexpr int NGS = 9;                     // per group after the first pass: N, M, R (3), V (3), U
 constexpr int JUMP = 16;                   // links a lane follows per jump round
 constexpr int COUNT_RUN = 16;              // consecutive ids per thread of groups_count
-constexpr int AXIS_BITS = 21;
-constexpr uint64_t AXIS_MASK = ((uint64_t)1 << AXIS_BITS) - 1;
-constexpr double AXIS_CELLS = (double)((1 << AXIS_BITS) - 8);     // cells per axis the edge is enlarged to stay under
 
 struct Sel {
     double rho_min, clip_lo[3], clip_hi[3];
@@ -82,8 +79,6 @@ struct Info {
     int64_t n_groups;                      // -1: a selected particle has a bad h under LINK_H
     int32_t bad;
 };
-
-struct Ent { uint64_t key; int32_t start, end; };    // hash table entry; empty: key = ~0
 
 __device__ __forceinline__ bool selected(const Sel &s, double x, double y, double z, double rho) {
     return rho >= s.rho_min && s.clip_lo[0] < x && x < s.clip_hi[0] && s.clip_lo[1] < y && y < s.clip_hi[1] &&
@@ -162,11 +157,6 @@ __global__ __launch_bounds__(WAVE) void groups_box(const double *__restrict__ pa
     info->bad = bad ? 1 : 0;
 }
 
-__device__ __forceinline__ uint64_t cell_axis(double p, double lo, double inv_e) {
-    // fmax drops a NaN (an overflowing product) to 0; the clamp keeps every key inside its 21 bits
-    return (uint64_t)fmin(fmax(floor((p - lo) * inv_e), 0.0), (double)AXIS_MASK);
-}
-
 __global__ __launch_bounds__(GB) void groups_keys(const double *__restrict__ x, const double *__restrict__ y,
                                                   const double *__restrict__ z, const double *__restrict__ rho,
                                                   const int32_t *__restrict__ orig, int64_t n_slots, int64_t n_owned, Sel s,
@@ -177,20 +167,10 @@ __global__ __launch_bounds__(GB) void groups_keys(const double *__restrict__ x, 
     uint64_t key = ~0ull;
     if (orig[i] < n_owned && info->n_sel > 0) {
         const double px = x[i], py = y[i], pz = z[i];
-        if (selected(s, px, py, pz, rho[i])) {
-            const double ie = info->inv_e;
-            key = (cell_axis(px, info->lo[0], ie) << (2 * AXIS_BITS)) | (cell_axis(py, info->lo[1], ie) << AXIS_BITS) |
-                  cell_axis(pz, info->lo[2], ie);
-        }
+        if (selected(s, px, py, pz, rho[i])) key = cell_key(px, py, pz, info->lo, info->inv_e);
     }
     keys[i] = key;
     vals[i] = (uint32_t)i;
-}
-
-__device__ __forceinline__ uint64_t hash_mix(uint64_t k) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
-    return k ^ (k >> 33);
 }
 
 // {x, y, z, h} and the original id in sorted order; every cell's first position enters the table
@@ -204,32 +184,12 @@ __global__ __launch_bounds__(GB) void groups_gather(const double *__restrict__ x
     const uint32_t i = sval[p];
     rec[p] = make_double4(x[i], y[i], z[i], h_of(s, i));
     sid[p] = orig[i];
-    const uint64_t key = skey[p];
-    if (p > 0 && skey[p - 1] == key) return;
-    for (uint64_t t = hash_mix(key) & mask;; t = (t + 1) & mask) {
-        const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&tab[t].key), ~0ull,
-                                                  (unsigned long long)key);
-        if (prev == ~0ull) { tab[t].start = (int32_t)p; return; }     // every key is inserted once: by its first position
-    }
-}
-
-__device__ __forceinline__ int64_t hash_slot(const Ent *__restrict__ tab, uint64_t mask, uint64_t key) {
-    for (uint64_t t = hash_mix(key) & mask;; t = (t + 1) & mask) {
-        const uint64_t k = tab[t].key;
-        if (k == key) return (int64_t)t;
-        if (k == ~0ull) return -1;
-    }
+    cell_enter(skey, p, tab, mask);
 }
 
 __global__ __launch_bounds__(GB) void groups_tails(const uint64_t *__restrict__ skey, const Info *__restrict__ info, int64_t n_slots,
                                                    Ent *__restrict__ tab, uint64_t mask) {
-    const int64_t p = (int64_t)blockIdx.x * GB + threadIdx.x;
-    const int64_t ns = info->n_sel;
-    if (p >= n_slots || p >= ns) return;
-    const uint64_t key = skey[p];
-    if (p + 1 < ns && skey[p + 1] == key) return;
-    const int64_t t = hash_slot(tab, mask, key);           // put there by the cell's first position
-    if (t >= 0) tab[t].end = (int32_t)(p + 1);
+    cell_close(skey, (int64_t)blockIdx.x * GB + threadIdx.x, n_slots, info->n_sel, tab, mask);
 }
 
 // the node a chain of parent links from x ends at (plain loads: possibly an older root of x's tree, see the top); every
@@ -386,13 +346,6 @@ __global__ __launch_bounds__(GB) void groups_starts(const uint64_t *__restrict__
     if (p + 1 == n_slots || keys[p + 1] == ~0ull) start[g + 1] = (int32_t)(p + 1);
 }
 
-__device__ __forceinline__ int64_t piece_base(const int32_t *start, int64_t g) { return start[g] / PIECE + g; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);     // the butterfly: every lane ends with the same sum
-    return v;
-}
-
 // the densest member: larger rho, then the smaller id (order-free)
 __device__ __forceinline__ void best_of(double &rho, double &id, double &slot, double rho2, double id2, double slot2) {
     if (rho2 > rho || (rho2 == rho && id2 < id)) { rho = rho2; id = id2; slot = slot2; }
@@ -410,15 +363,8 @@ __global__ __launch_bounds__(GB) void groups_pieces(Fields f, const uint32_t *__
     const int lane = threadIdx.x & 63;
     const int64_t ng = info->n_groups;
     if (w >= n_pieces || ng <= 0 || w > start[ng] / PIECE + ng) return;     // past the last piece slot in use
-    int64_t lo = 0, hi = ng - 1;                        // the last group whose base is <= w
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (piece_base(start, mid) <= w) lo = mid; else hi = mid - 1;
-    }
-    const int64_t g = lo, k = w - piece_base(start, g);
-    const int64_t p0 = (int64_t)start[g] + k * PIECE, end = start[g + 1];
-    if (k < 0 || p0 >= end) return;
-    const int64_t p1 = min(end, p0 + PIECE);
+    int64_t g, p0, p1;
+    if (!piece_locate(start, ng, w, g, p0, p1)) return;
     double acc[NP];
 #pragma unroll
     for (int s = 0; s < NP; s++) acc[s] = 0.0;
@@ -525,46 +471,23 @@ __global__ __launch_bounds__(GB) void groups_final(const int32_t *__restrict__ s
     }
 }
 
-#define GR_HIP(expr)                                                        \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) {                                             \
-            c->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return SPH_ERR_HIP;                                             \
-        }                                                                   \
-    } while (0)
-
-#define GR_TRY(expr)                   \
-    do {                               \
-        int _s = (expr);               \
-        if (_s != SPH_OK) return _s;   \
-    } while (0)
-
-size_t align_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int gr_arg(sph_ctx *c, const char *what) {
-    c->err = std::string("sph_groups: ") + what;
-    return SPH_ERR_ARG;
-}
-
-unsigned blocks(int64_t n, int per) { return (unsigned)std::max<int64_t>((n + per - 1) / per, 1); }
-
 }  // namespace
 
 int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_labels, double *table, int64_t max_groups,
                int64_t *n_groups, bool host, bool (*ready)(const sph_ctx *, int)) {
-    if (!d) return gr_arg(c, "null descriptor");
-    if (!n_groups) return gr_arg(c, "null count pointer");
-    if (d->reserved != 0) return gr_arg(c, "reserved must be 0");
-    if (d->flags & ~SPH_GROUPS_LINK_H) return gr_arg(c, "unknown flags");
-    if (!(d->link > 0.0) || !std::isfinite(d->link)) return gr_arg(c, "link must be finite and > 0");
-    if (std::isnan(d->rho_min)) return gr_arg(c, "rho_min is NaN");
+    const char *who = "sph_groups";
+    if (!d) return arg_error(c, who, "null descriptor");
+    if (!n_groups) return arg_error(c, who, "null count pointer");
+    if (d->reserved != 0) return arg_error(c, who, "reserved must be 0");
+    if (d->flags & ~SPH_GROUPS_LINK_H) return arg_error(c, who, "unknown flags");
+    if (!(d->link > 0.0) || !std::isfinite(d->link)) return arg_error(c, who, "link must be finite and > 0");
+    if (std::isnan(d->rho_min)) return arg_error(c, who, "rho_min is NaN");
     for (int a = 0; a < 3; a++)
-        if (std::isnan(d->clip_lo[a]) || std::isnan(d->clip_hi[a])) return gr_arg(c, "the clip box has a NaN");
-    if (d->min_members < 1) return gr_arg(c, "min_members must be >= 1");
-    if (labels && n_labels != c->n) return gr_arg(c, "n_labels != sph_count");
-    if (max_groups < 0) return gr_arg(c, "max_groups < 0");
-    if (table && max_groups == 0) return gr_arg(c, "a table needs max_groups > 0");
+        if (std::isnan(d->clip_lo[a]) || std::isnan(d->clip_hi[a])) return arg_error(c, who, "the clip box has a NaN");
+    if (d->min_members < 1) return arg_error(c, who, "min_members must be >= 1");
+    if (labels && n_labels != c->n) return arg_error(c, who, "n_labels != sph_count");
+    if (max_groups < 0) return arg_error(c, who, "max_groups < 0");
+    if (table && max_groups == 0) return arg_error(c, who, "a table needs max_groups > 0");
     if (!ready(c, SPH_F_RHO)) { c->err = "sph_groups: rho is stale (call sph_density)"; return SPH_ERR_STATE; }
     const bool link_h = (d->flags & SPH_GROUPS_LINK_H) != 0;
     if (link_h && !c->variable && !(c->p.h > 0.0 && std::isfinite(c->p.h))) {
@@ -581,8 +504,8 @@ int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_
             if (labels) std::fill(labels, labels + n, -1);
             *n_groups = 0;
         } else {
-            if (labels && n > 0) GR_HIP(hipMemsetAsync(labels, 0xff, (size_t)n * sizeof(int32_t), st));
-            GR_HIP(hipMemsetAsync(n_groups, 0, sizeof(int64_t), st));
+            if (labels && n > 0) SPH_HIP(hipMemsetAsync(labels, 0xff, (size_t)n * sizeof(int32_t), st));
+            SPH_HIP(hipMemsetAsync(n_groups, 0, sizeof(int64_t), st));
         }
         return SPH_OK;
     }
@@ -593,37 +516,45 @@ int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_
     int64_t tl = 1;
     while (tl < 2 * ns) tl <<= 1;                                // hash table: load <= 1/2
     size_t sort_pairs = 0, sort_keys = 0;
-    GR_HIP(rocprim::radix_sort_pairs(nullptr, sort_pairs, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                     (uint32_t *)nullptr, (size_t)ns, 0u, 64u, st));
-    GR_HIP(rocprim::radix_sort_keys(nullptr, sort_keys, (uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)no, 0u, 64u, st));
+    SPH_HIP(rocprim::radix_sort_pairs(nullptr, sort_pairs, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
+                                      (uint32_t *)nullptr, (size_t)ns, 0u, 64u, st));
+    SPH_HIP(rocprim::radix_sort_keys(nullptr, sort_keys, (uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)no, 0u, 64u, st));
     const size_t sort_bytes = std::max(sort_pairs, sort_keys);
-    // scratch: keys, keys_alt, vals, vals_alt, sort, rec, sid, table, parent, cnt, gnum, box partials, info, start, part,
-    // gstat, labels (host form), table rows (host form)
-    const size_t sizes[18] = {8 * (size_t)ns, 8 * (size_t)ns, 4 * (size_t)ns, 4 * (size_t)ns, sort_bytes, 32 * (size_t)ns,
-                              4 * (size_t)ns, sizeof(Ent) * (size_t)tl, 4 * (size_t)no, 4 * (size_t)no, 4 * (size_t)no,
-                              8 * 9 * (size_t)nb, sizeof(Info), 4 * (size_t)(gb + 1), 8 * NP2 * (size_t)n_pieces,
-                              8 * NGS * (size_t)std::max<int64_t>(gb, 1), host && labels ? 4 * (size_t)n : 0,
-                              host ? 8 * SPH_GROUPS_NCOL * (size_t)rows : 0};
-    size_t off[18], bytes = 0;
-    for (int k = 0; k < 18; k++) { off[k] = bytes; bytes += align_up(sizes[k]); }
+    uint64_t *keys, *keys_alt;
+    uint32_t *vals, *vals_alt;
+    char *sort_tmp;
+    double4 *rec;
+    Ent *tab;
+    Info *info;
+    int32_t *sid, *parent, *cnt, *gnum, *start, *h_labels;
+    double *box_part, *part, *gstat, *h_table;
+    auto layout = [&](Carve cv) {
+        keys = cv.take<uint64_t>(ns);
+        keys_alt = cv.take<uint64_t>(ns);
+        vals = cv.take<uint32_t>(ns);
+        vals_alt = cv.take<uint32_t>(ns);
+        sort_tmp = cv.take<char>(sort_bytes);
+        rec = cv.take<double4>(ns);
+        sid = cv.take<int32_t>(ns);
+        tab = cv.take<Ent>(tl);
+        parent = cv.take<int32_t>(no);
+        cnt = cv.take<int32_t>(no);
+        gnum = cv.take<int32_t>(no);
+        box_part = cv.take<double>(9 * (size_t)nb);
+        info = cv.take<Info>(1);
+        start = cv.take<int32_t>(gb + 1);
+        part = cv.take<double>(NP2 * (size_t)n_pieces);
+        gstat = cv.take<double>(NGS * (size_t)std::max<int64_t>(gb, 1));
+        h_labels = cv.take<int32_t>(host && labels ? n : 0);                     // the host form's device copies
+        h_table = cv.take<double>(host ? SPH_GROUPS_NCOL * (size_t)rows : 0);
+        return cv.bytes;
+    };
     char *buf = nullptr;
-    GR_TRY(render_scratch(c, bytes, &buf));
-    uint64_t *keys = reinterpret_cast<uint64_t *>(buf + off[0]), *keys_alt = reinterpret_cast<uint64_t *>(buf + off[1]);
-    uint32_t *vals = reinterpret_cast<uint32_t *>(buf + off[2]), *vals_alt = reinterpret_cast<uint32_t *>(buf + off[3]);
-    void *sort_tmp = buf + off[4];
-    double4 *rec = reinterpret_cast<double4 *>(buf + off[5]);
-    int32_t *sid = reinterpret_cast<int32_t *>(buf + off[6]);
-    Ent *tab = reinterpret_cast<Ent *>(buf + off[7]);
-    int32_t *parent = reinterpret_cast<int32_t *>(buf + off[8]), *cnt = reinterpret_cast<int32_t *>(buf + off[9]);
-    int32_t *gnum = reinterpret_cast<int32_t *>(buf + off[10]);
-    double *box_part = reinterpret_cast<double *>(buf + off[11]);
-    Info *info = reinterpret_cast<Info *>(buf + off[12]);
-    int32_t *start = reinterpret_cast<int32_t *>(buf + off[13]);
-    double *part = reinterpret_cast<double *>(buf + off[14]);
-    double *gstat = reinterpret_cast<double *>(buf + off[15]);
-    int32_t *d_labels = labels ? (host ? reinterpret_cast<int32_t *>(buf + off[16]) : labels) : nullptr;
-    double *d_table = host ? reinterpret_cast<double *>(buf + off[17]) : table;
-    if (host && !c->rnd_pinned) GR_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->rnd_pinned), 32 * sizeof(double), hipHostMallocDefault));
+    SPH_TRY(analysis_scratch(c, layout(Carve{}), &buf));
+    layout(Carve{buf});
+    int32_t *d_labels = labels ? (host ? h_labels : labels) : nullptr;
+    double *d_table = host ? h_table : table;
+    if (host) SPH_TRY(analysis_pinned(c));
 
     Sel s{};
     s.rho_min = d->rho_min;
@@ -638,19 +569,19 @@ int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_
     // selection, box, cell edge
     groups_select<<<dim3((unsigned)nb), dim3(GB), 0, st>>>(x, y, z, rho, c->orig, ns, no, s, parent, cnt, gnum, box_part);
     groups_box<<<dim3(1), dim3(WAVE), 0, st>>>(box_part, nb, s, info);
-    GR_HIP(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     // cell keys, sort, hash table over the occupied cells
     groups_keys<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(x, y, z, rho, c->orig, ns, no, s, info, keys, vals);
     size_t tmp = sort_bytes;
-    GR_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)ns, 0u, 64u, st));
-    GR_HIP(hipMemsetAsync(tab, 0xff, sizeof(Ent) * (size_t)tl, st));
+    SPH_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)ns, 0u, 64u, st));
+    SPH_HIP(hipMemsetAsync(tab, 0xff, sizeof(Ent) * (size_t)tl, st));
     groups_gather<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(x, y, z, c->orig, s, keys_alt, vals_alt, info, ns, rec, sid, tab,
                                                               (uint64_t)(tl - 1));
     groups_tails<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(keys_alt, info, ns, tab, (uint64_t)(tl - 1));
     // links, then the flattening: every round multiplies the links a pointer spans by JUMP (>= 16^rounds >= no)
     groups_link<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(rec, sid, keys_alt, info, ns, tab, (uint64_t)(tl - 1), d->link, b2,
                                                             s.link_h, parent);
-    GR_HIP(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     int rounds = 1;
     for (double span = JUMP; span < (double)no; span *= JUMP) rounds++;
     for (int r = 0; r < rounds; r++) groups_jump<<<dim3(blocks(no, GB)), dim3(GB), 0, st>>>(parent, no);
@@ -658,15 +589,15 @@ int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_
     // numbering: (N descending, root id)
     groups_root_keys<<<dim3(blocks(no, GB)), dim3(GB), 0, st>>>(parent, cnt, no, d->min_members, info, keys);
     tmp = sort_bytes;
-    GR_HIP(rocprim::radix_sort_keys(sort_tmp, tmp, keys, keys_alt, (size_t)no, 0u, 64u, st));
+    SPH_HIP(rocprim::radix_sort_keys(sort_tmp, tmp, keys, keys_alt, (size_t)no, 0u, 64u, st));
     groups_number<<<dim3(blocks(no, GB)), dim3(GB), 0, st>>>(keys_alt, no, gnum, info);
     // members in (group, id) order, labels
-    if (d_labels && n > no) GR_HIP(hipMemsetAsync(d_labels + no, 0xff, (size_t)(n - no) * sizeof(int32_t), st));   // ghosts
+    if (d_labels && n > no) SPH_HIP(hipMemsetAsync(d_labels + no, 0xff, (size_t)(n - no) * sizeof(int32_t), st));   // ghosts
     groups_members<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(c->orig, ns, no, parent, gnum, keys, vals, d_labels);
     tmp = sort_bytes;
-    GR_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)ns, 0u, 64u, st));
+    SPH_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)ns, 0u, 64u, st));
     groups_starts<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(keys_alt, ns, start);
-    GR_HIP(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     // the two reductions
     Fields f{x, y, z, c->f[SPH_F_VX], c->f[SPH_F_VY], c->f[SPH_F_VZ], c->f[SPH_F_U], c->f[SPH_F_M], rho, c->orig};
     const int wpb = GB / WAVE;
@@ -676,17 +607,17 @@ int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_
         groups_pieces<2><<<dim3(blocks(n_pieces, wpb)), dim3(GB), 0, st>>>(f, vals_alt, start, info, n_pieces, gstat, part);
         groups_final<2><<<dim3(blocks(rows, wpb)), dim3(GB), 0, st>>>(start, info, gb, part, keys_alt, f, gstat, d_table, rows);
     }
-    GR_HIP(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     if (!host) {
-        GR_HIP(hipMemcpyAsync(n_groups, &info->n_groups, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        SPH_HIP(hipMemcpyAsync(n_groups, &info->n_groups, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
         return SPH_OK;
     }
     // host form: the count, the labels and the table rows in one read-back
     std::vector<double> trow((size_t)rows * SPH_GROUPS_NCOL);
-    GR_HIP(hipMemcpyAsync(c->rnd_pinned, &info->n_groups, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    if (labels && n > 0) GR_HIP(hipMemcpyAsync(labels, d_labels, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (rows > 0) GR_HIP(hipMemcpyAsync(trow.data(), d_table, trow.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    GR_HIP(hipStreamSynchronize(st));
+    SPH_HIP(hipMemcpyAsync(c->rnd_pinned, &info->n_groups, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (labels && n > 0) SPH_HIP(hipMemcpyAsync(labels, d_labels, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (rows > 0) SPH_HIP(hipMemcpyAsync(trow.data(), d_table, trow.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    SPH_HIP(hipStreamSynchronize(st));
     int64_t ng = 0;
     std::memcpy(&ng, c->rnd_pinned, sizeof(int64_t));
     if (ng < 0) {

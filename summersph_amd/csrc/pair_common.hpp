@@ -32,12 +32,6 @@ __device__ __forceinline__ void cell_coords(const GridDesc &g, double px, double
 // c0 in [0, d0] (d0: the end of the row).  CellTab<false> answers from the dense table, CellTab<true> from the hashed one
 // (sph_internal.hpp HashView) with the same values, so both give the same lists, tiles and sums.  at() = that slot; ent()
 // also returns the lower-bound index among the occupied cells (= the cell's own index when it is occupied: cell_hmax).
-__device__ __forceinline__ uint64_t hash_mix(uint64_t k) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
-    return k ^ (k >> 33);
-}
-
 __device__ __forceinline__ int2 hash_find(const HashView &h, uint64_t key) {
     for (uint64_t s = hash_mix(key) & h.mask;; s = (s + 1) & h.mask) {
         const HashEnt e = h.tab[s];

@@ -27,6 +27,7 @@
 #include <cmath>
 
 #include "pair_common.hpp"
+#include "reduce_common.hpp"
 #include "tile_common.hpp"
 
 namespace sph {
@@ -274,11 +275,6 @@ __global__ __launch_bounds__(BLOCK) void forces_kernel(PairConst pc, const doubl
 // ------------------------------------------------------------------------------------------
 constexpr int SA_BLOCK = 256;
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(SA_BLOCK) void sink_accel_partial(PairConst pc, const double4 *__restrict__ drec, int64_t n,
                                                                const double *__restrict__ sink, double *__restrict__ part,
                                                                const int32_t *__restrict__ orig, int32_t n_owned) {
@@ -361,15 +357,6 @@ PairConst make_pair_const(const sph_ctx *c) {
 
 static inline unsigned pair_blocks(int64_t n) { return (unsigned)((n + PAIR_BLOCK - 1) / PAIR_BLOCK); }
 
-#define NL_CHECK(expr)                                                      \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) {                                             \
-            c->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return SPH_ERR_HIP;                                             \
-        }                                                                   \
-    } while (0)
-
 int nlist_build(sph_ctx *c) {
     const int64_t n = c->n;
     if (n == 0) return SPH_OK;
@@ -381,8 +368,8 @@ int nlist_build(sph_ctx *c) {
             c->grid, reinterpret_cast<const double4 *>(c->drec), c->cell_start, n, pc.rcut2, c->nl_cap, c->nlist,
             c->ncount, c->wave_max, c->wave_class, c->orig, (int32_t)c->n_owned, c->hv);
         max_to_host<<<dim3(1), dim3(1024), 0, c->stream>>>(c->wave_class, (n + 63) / 64, reinterpret_cast<int32_t *>(c->h_pinned + 9));
-        NL_CHECK(hipGetLastError());
-        NL_CHECK(hipStreamSynchronize(c->stream));
+        SPH_HIP(hipGetLastError());
+        SPH_HIP(hipStreamSynchronize(c->stream));
         c->wave_class_valid = false;
         const int32_t mx = *reinterpret_cast<int32_t *>(c->h_pinned + 9);
         c->nl_max = mx;

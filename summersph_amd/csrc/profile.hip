@@ -2,7 +2,7 @@
 // (and ring sectors) about a centre, in the frame of a disc normal (include/summersph.h, sph_profile).
 //
 // Not part of the step loop: nothing here reads or writes the context's grid, cell table, neighbour list, statistics or
-// flags.  The scratch is the render's (render_scratch).
+// flags.  The scratch is the one the analysis calls share (analysis_scratch).
 //
 // Pipeline (all on ctx->stream):
 //   [AUTO_NORMAL: the same four kernels over the spherical shell r_min <= |r'| < r_max as one bin, read-back of L]
@@ -21,7 +21,7 @@
 #include <cmath>
 #include <vector>
 
-#include "sph_internal.hpp"
+#include "reduce_common.hpp"
 
 // the per-particle arithmetic is written in one documented order (summersph.h); no contraction into fused multiply-adds,
 // so that a numpy restatement reproduces it
@@ -32,7 +32,6 @@ namespace sph {
 namespace {
 
 constexpr int NS = SPH_PROFILE_NSUM;
-constexpr int PIECE = 16 * WAVE;   // sorted positions per piece: 16 per lane
 constexpr int KB = 256;            // key / starts block
 
 struct Frame {
@@ -128,8 +127,6 @@ __global__ __launch_bounds__(KB) void profile_starts(const uint64_t *__restrict_
     start[b] = (int32_t)lo;
 }
 
-__device__ __forceinline__ int64_t piece_base(const int32_t *start, int64_t b) { return start[b] / PIECE + b; }
-
 // the 20 moments of one particle (summersph.h, "Raw sums"), added to acc in index order
 __device__ __forceinline__ void add_moments(const Frame &f, const double c[3], const double cv[3], double gm,
                                             const double *const *fld, int64_t i, double acc[NS]) {
@@ -155,11 +152,6 @@ __device__ __forceinline__ void add_moments(const Frame &f, const double c[3], c
     for (int s = 0; s < NS; s++) acc[s] += q[s];
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);     // the butterfly: every lane ends with the same sum
-    return v;
-}
-
 struct Fields { const double *p[10]; };    // x y z vx vy vz u m alpha, [9] unused
 
 // one wavefront per piece slot g; gaps (slots no (bin, piece) maps to) return at once
@@ -168,15 +160,8 @@ __global__ __launch_bounds__(KB) void profile_pieces(Fields fl, Frame f, const u
     const int64_t g = (int64_t)blockIdx.x * (KB / WAVE) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (g >= n_pieces) return;
-    int64_t lo = 0, hi = (int64_t)n_bins - 1;            // the last bin whose base is <= g
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (piece_base(start, mid) <= g) lo = mid; else hi = mid - 1;
-    }
-    const int64_t b = lo, k = g - piece_base(start, b);
-    const int64_t p0 = (int64_t)start[b] + k * PIECE, end = start[b + 1];
-    if (k < 0 || p0 >= end) return;
-    const int64_t p1 = min(end, p0 + PIECE);
+    int64_t b, p0, p1;
+    if (!piece_locate(start, (int64_t)n_bins, g, b, p0, p1)) return;
     double c[3], cv[3], cm;
     centre_of(f, c, cv, cm);
     const double gm = cm > 0.0 ? f.G * cm : 0.0;
@@ -214,23 +199,6 @@ __global__ __launch_bounds__(KB) void profile_final(const int32_t *__restrict__ 
         for (int s = 0; s < NS; s++) sums[b * NS + s] = acc[s];
     }
 }
-
-#define PF_HIP(expr)                                                        \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) {                                             \
-            c->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return SPH_ERR_HIP;                                             \
-        }                                                                   \
-    } while (0)
-
-#define PF_TRY(expr)                   \
-    do {                               \
-        int _s = (expr);               \
-        if (_s != SPH_OK) return _s;   \
-    } while (0)
-
-size_t align_up(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // the checks that need no context; what == null: fine
 const char *check_desc(const sph_profile_desc *d, int64_t n_bins, bool need_normal) {
@@ -278,31 +246,35 @@ void ring_edges(const sph_profile_desc *d, double *edge) {
     edge[nr] = d->r_max;
 }
 
-int pf_arg(sph_ctx *c, const char *what) {
-    c->err = std::string("sph_profile: ") + what;
-    return SPH_ERR_ARG;
-}
+// the scratch of a pass (both passes of a call use the same)
+struct PassBufs {
+    uint64_t *keys, *keys_alt;
+    uint32_t *vals, *vals_alt;
+    char *sort_tmp;
+    int32_t *start;
+    double *part;
+};
 
 // one pass of the pipeline: the sums of n_bins bins into d_sums (device)
-int run_pass(sph_ctx *c, const Frame &f, const Bins &b, uint32_t n_bins, char *buf, const size_t *off, size_t sort_bytes,
-             int64_t n_slots, double *d_sums) {
+int run_pass(sph_ctx *c, const Frame &f, const Bins &b, uint32_t n_bins, const PassBufs &pb, size_t sort_bytes, int64_t n_slots,
+             double *d_sums) {
     hipStream_t st = c->stream;
-    uint64_t *keys = reinterpret_cast<uint64_t *>(buf + off[0]), *keys_alt = reinterpret_cast<uint64_t *>(buf + off[1]);
-    uint32_t *vals = reinterpret_cast<uint32_t *>(buf + off[2]), *vals_alt = reinterpret_cast<uint32_t *>(buf + off[3]);
-    void *sort_tmp = buf + off[4];
-    int32_t *start = reinterpret_cast<int32_t *>(buf + off[6]);
-    double *part = reinterpret_cast<double *>(buf + off[7]);
+    uint64_t *keys = pb.keys, *keys_alt = pb.keys_alt;
+    uint32_t *vals = pb.vals, *vals_alt = pb.vals_alt;
+    char *sort_tmp = pb.sort_tmp;
+    int32_t *start = pb.start;
+    double *part = pb.part;
     if (n_slots == 0) {
-        PF_HIP(hipMemsetAsync(d_sums, 0, (size_t)n_bins * NS * sizeof(double), st));
+        SPH_HIP(hipMemsetAsync(d_sums, 0, (size_t)n_bins * NS * sizeof(double), st));
         return SPH_OK;
     }
     profile_keys<<<dim3((unsigned)((n_slots + KB - 1) / KB)), dim3(KB), 0, st>>>(
         c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], c->orig, n_slots, c->n_owned, f, b, n_bins, keys, vals);
-    PF_HIP(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     unsigned bbits = 1;
     while (bbits < 32 && ((uint64_t)1 << bbits) <= n_bins) bbits++;
     size_t tmp = sort_bytes;
-    PF_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)n_slots, 0u, 32u + bbits, st));
+    SPH_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)n_slots, 0u, 32u + bbits, st));
     profile_starts<<<dim3((unsigned)((n_bins + 1 + KB - 1) / KB)), dim3(KB), 0, st>>>(keys_alt, n_slots, n_bins, start);
     const int64_t n_pieces = n_slots / PIECE + n_bins + 1;
     Fields fl{};
@@ -311,41 +283,51 @@ int run_pass(sph_ctx *c, const Frame &f, const Bins &b, uint32_t n_bins, char *b
     profile_pieces<<<dim3((unsigned)((n_pieces + wpb - 1) / wpb)), dim3(KB), 0, st>>>(fl, f, vals_alt, start, n_bins,
                                                                                        n_pieces, part);
     profile_final<<<dim3((unsigned)((n_bins + wpb - 1) / wpb)), dim3(KB), 0, st>>>(start, n_bins, part, d_sums);
-    PF_HIP(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     return SPH_OK;
 }
 
 }  // namespace
 
 int profile_sums(sph_ctx *c, sph_profile_desc *d, double *sums, double *table, int64_t n_bins, bool host) {
-    if (!d) return pf_arg(c, "null descriptor");
-    if (host ? (!sums && !table) : !sums) return pf_arg(c, host ? "both outputs are null" : "null output");
+    const char *who = "sph_profile";
+    if (!d) return arg_error(c, who, "null descriptor");
+    if (host ? (!sums && !table) : !sums) return arg_error(c, who, host ? "both outputs are null" : "null output");
     const bool autonorm = (d->flags & SPH_PROFILE_AUTO_NORMAL) != 0;
-    if (const char *why = check_desc(d, n_bins, !autonorm)) return pf_arg(c, why);
-    if (d->sink < -1 || d->sink >= c->ns) return pf_arg(c, "sink out of range");
+    if (const char *why = check_desc(d, n_bins, !autonorm)) return arg_error(c, who, why);
+    if (d->sink < -1 || d->sink >= c->ns) return arg_error(c, who, "sink out of range");
     if (d->sink < 0)
         for (int a = 0; a < 3; a++)
-            if (!std::isfinite(d->centre[a]) || !std::isfinite(d->centre_v[a])) return pf_arg(c, "the centre is not finite");
+            if (!std::isfinite(d->centre[a]) || !std::isfinite(d->centre_v[a])) return arg_error(c, who, "the centre is not finite");
 
     hipStream_t st = c->stream;
     const int64_t n_slots = c->cap > 0 ? c->n_slots : 0;
     const uint32_t nb = (uint32_t)n_bins;
     const int64_t n_pieces = n_slots / PIECE + n_bins + 1;
     size_t sort_bytes = 0;
-    PF_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                     (uint32_t *)nullptr, (size_t)std::max<int64_t>(n_slots, 1), 0u, 64u, st));
+    SPH_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
+                                      (uint32_t *)nullptr, (size_t)std::max<int64_t>(n_slots, 1), 0u, 64u, st));
     const int64_t ns1 = std::max<int64_t>(n_slots, 1);
-    const size_t sizes[10] = {8 * (size_t)ns1, 8 * (size_t)ns1, 4 * (size_t)ns1, 4 * (size_t)ns1, sort_bytes,
-                              8 * (size_t)(d->n_r + 1), 4 * (size_t)(n_bins + 1), 8 * NS * (size_t)n_pieces,
-                              host ? 8 * NS * (size_t)n_bins : 0, 8 * NS};
-    size_t off[10], bytes = 0;
-    for (int k = 0; k < 10; k++) { off[k] = bytes; bytes += align_up(sizes[k]); }
+    PassBufs pb{};
+    double *d_edge, *h_sums, *d_auto;
+    auto layout = [&](Carve cv) {
+        pb.keys = cv.take<uint64_t>(ns1);
+        pb.keys_alt = cv.take<uint64_t>(ns1);
+        pb.vals = cv.take<uint32_t>(ns1);
+        pb.vals_alt = cv.take<uint32_t>(ns1);
+        pb.sort_tmp = cv.take<char>(sort_bytes);
+        d_edge = cv.take<double>(d->n_r + 1);
+        pb.start = cv.take<int32_t>(n_bins + 1);
+        pb.part = cv.take<double>(NS * (size_t)n_pieces);
+        h_sums = cv.take<double>(host ? NS * (size_t)n_bins : 0);     // the host form's device copy
+        d_auto = cv.take<double>(NS);                                  // AUTO_NORMAL: the shell's sums
+        return cv.bytes;
+    };
     char *buf = nullptr;
-    PF_TRY(render_scratch(c, bytes, &buf));
-    double *d_edge = reinterpret_cast<double *>(buf + off[5]);
-    double *d_out = host ? reinterpret_cast<double *>(buf + off[8]) : sums;
-    double *d_auto = reinterpret_cast<double *>(buf + off[9]);
-    if (!c->rnd_pinned) PF_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->rnd_pinned), 32 * sizeof(double), hipHostMallocDefault));
+    SPH_TRY(analysis_scratch(c, layout(Carve{}), &buf));
+    layout(Carve{buf});
+    double *d_out = host ? h_sums : sums;
+    SPH_TRY(analysis_pinned(c));
 
     Frame f{};
     for (int a = 0; a < 3; a++) { f.c[a] = d->centre[a]; f.cv[a] = d->centre_v[a]; }
@@ -368,9 +350,9 @@ int profile_sums(sph_ctx *c, sph_profile_desc *d, double *sums, double *table, i
         frame_axes(ez, f.n, f.e1, f.e2);
         Bins sb = b;
         sb.shell = 1;
-        PF_TRY(run_pass(c, f, sb, 1u, buf, off, sort_bytes, n_slots, d_auto));
-        PF_HIP(hipMemcpyAsync(c->rnd_pinned, d_auto + 14, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-        PF_HIP(hipStreamSynchronize(st));
+        SPH_TRY(run_pass(c, f, sb, 1u, pb, sort_bytes, n_slots, d_auto));
+        SPH_HIP(hipMemcpyAsync(c->rnd_pinned, d_auto + 14, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        SPH_HIP(hipStreamSynchronize(st));
         for (int a = 0; a < 3; a++) nrm[a] = c->rnd_pinned[a];
         if (!(std::isfinite(nrm[0]) && std::isfinite(nrm[1]) && std::isfinite(nrm[2])) ||
             (nrm[0] == 0.0 && nrm[1] == 0.0 && nrm[2] == 0.0)) {
@@ -380,31 +362,31 @@ int profile_sums(sph_ctx *c, sph_profile_desc *d, double *sums, double *table, i
     } else {
         for (int a = 0; a < 3; a++) nrm[a] = d->normal[a];
     }
-    if (!frame_axes(nrm, f.n, f.e1, f.e2)) return pf_arg(c, "the normal cannot be normalised");
+    if (!frame_axes(nrm, f.n, f.e1, f.e2)) return arg_error(c, who, "the normal cannot be normalised");
 
     // the edge table travels in the stream's order from a pinned staging copy, rewritten only once its last upload is done
     const size_t ne = (size_t)d->n_r + 1;
-    if (!c->prf_evt) PF_HIP(hipEventCreateWithFlags(&c->prf_evt, hipEventDisableTiming));
-    PF_HIP(hipEventSynchronize(c->prf_evt));
+    if (!c->prf_evt) SPH_HIP(hipEventCreateWithFlags(&c->prf_evt, hipEventDisableTiming));
+    SPH_HIP(hipEventSynchronize(c->prf_evt));
     if (ne > c->prf_edge_cap) {
-        if (c->prf_edge) PF_HIP(hipHostFree(c->prf_edge));
+        if (c->prf_edge) SPH_HIP(hipHostFree(c->prf_edge));
         c->prf_edge = nullptr; c->prf_edge_cap = 0;
-        PF_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->prf_edge), ne * sizeof(double), hipHostMallocDefault));
+        SPH_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->prf_edge), ne * sizeof(double), hipHostMallocDefault));
         c->prf_edge_cap = ne;
     }
     double *edge = c->prf_edge;
     ring_edges(d, edge);
     for (int k = 0; k < d->n_r; k++)
-        if (!(edge[k] < edge[k + 1])) return pf_arg(c, "ring edges are not strictly increasing (rings too narrow)");
-    PF_HIP(hipMemcpyAsync(d_edge, edge, ne * sizeof(double), hipMemcpyHostToDevice, st));
-    PF_HIP(hipEventRecord(c->prf_evt, st));
-    PF_TRY(run_pass(c, f, b, nb, buf, off, sort_bytes, n_slots, d_out));
+        if (!(edge[k] < edge[k + 1])) return arg_error(c, who, "ring edges are not strictly increasing (rings too narrow)");
+    SPH_HIP(hipMemcpyAsync(d_edge, edge, ne * sizeof(double), hipMemcpyHostToDevice, st));
+    SPH_HIP(hipEventRecord(c->prf_evt, st));
+    SPH_TRY(run_pass(c, f, b, nb, pb, sort_bytes, n_slots, d_out));
     if (host) {
         std::vector<double> hs;
         double *hsum = sums;
         if (!hsum) { hs.resize((size_t)n_bins * NS); hsum = hs.data(); }
-        PF_HIP(hipMemcpyAsync(hsum, d_out, (size_t)n_bins * NS * sizeof(double), hipMemcpyDeviceToHost, st));
-        PF_HIP(hipStreamSynchronize(st));
+        SPH_HIP(hipMemcpyAsync(hsum, d_out, (size_t)n_bins * NS * sizeof(double), hipMemcpyDeviceToHost, st));
+        SPH_HIP(hipStreamSynchronize(st));
         for (int a = 0; a < 3; a++) d->normal[a] = f.n[a];
         if (table) return sph_profile_finish(d, &c->p, hsum, table, n_bins);
     } else {

@@ -26,7 +26,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "sph_internal.hpp"
+#include "reduce_common.hpp"
 
 // the 3-D values and the column sums must be bitwise the same per node: no contraction into fused multiply-adds that
 // the compiler might choose differently in the three instantiations of the gather
@@ -88,19 +88,6 @@ __device__ __forceinline__ int32_t cell_1d(const RGrid &g, int a, double p) {
 // np.linspace: i * step + lo, the last node exactly hi
 __device__ __forceinline__ double node_coord(const Nodes &nd, int a, int i) {
     return i >= nd.n[a] - 1 ? nd.hi[a] : (double)i * nd.step[a] + nd.lo[a];
-}
-
-__device__ __forceinline__ double wave_min(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // partial[b * NSTAT + k]: min x y z, max x y z, max h, max -h, count over block b's grid-stride share of the selection
@@ -393,41 +380,6 @@ __global__ __launch_bounds__(GT) void render_gather(GatherArgs A) { gather_body<
 template <int W, bool DEN>
 __global__ __launch_bounds__(GT) void field_gather(GatherArgs A) { gather_body<W, true, DEN>(A); }
 
-#define RD_HIP(expr)                                                        \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) {                                             \
-            c->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return SPH_ERR_HIP;                                             \
-        }                                                                   \
-    } while (0)
-
-#define RD_TRY(expr)                   \
-    do {                               \
-        int _s = (expr);               \
-        if (_s != SPH_OK) return _s;   \
-    } while (0)
-
-int rd_arg(sph_ctx *c, const char *what, const char *who = "sph_render_density") {
-    c->err = std::string(who) + ": " + what;
-    return SPH_ERR_ARG;
-}
-
-size_t align_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// the render's scratch: grows, never shrinks; freed with the context.  A grown buffer replaces the old one only after the
-// stream has drained (a previous _dev render may still read it).
-int scratch(sph_ctx *c, size_t bytes, char **out) {
-    if (bytes > c->rnd_bytes) {
-        RD_HIP(hipStreamSynchronize(c->stream));
-        ctx_free_ptr(c, c->rnd_buf); c->rnd_buf = nullptr; c->rnd_bytes = 0;
-        RD_TRY(ctx_alloc_bytes(c, &c->rnd_buf, bytes, "render scratch"));
-        c->rnd_bytes = bytes;
-    }
-    *out = static_cast<char *>(c->rnd_buf);
-    return SPH_OK;
-}
-
 template <int W>
 hipError_t launch_gather(const GatherArgs &a, int tiles, int ysegs, hipStream_t st) {
     render_gather<W><<<dim3((unsigned)tiles, (unsigned)ysegs), dim3(GT), 0, st>>>(a);
@@ -455,26 +407,26 @@ struct FieldSpec {
 // the density render (fs null) and the field render: shared selection, binning, sort and cells; records and gather differ
 int render_impl(sph_ctx *c, sph_render_desc *d, const FieldSpec *fs, double *out, int64_t out_len, bool host_out) {
     const char *who = fs ? "sph_render_field" : "sph_render_density";
-    if (!d || !out) return rd_arg(c, "null descriptor or output", who);
-    if (d->reserved != 0) return rd_arg(c, "reserved must be 0", who);
-    if (d->flags & ~(SPH_RENDER_AUTO_BOUNDS | SPH_RENDER_SPACING)) return rd_arg(c, "unknown flags", who);
+    if (!d || !out) return arg_error(c, who, "null descriptor or output");
+    if (d->reserved != 0) return arg_error(c, who, "reserved must be 0");
+    if (d->flags & ~(SPH_RENDER_AUTO_BOUNDS | SPH_RENDER_SPACING)) return arg_error(c, who, "unknown flags");
     const bool autob = (d->flags & SPH_RENDER_AUTO_BOUNDS) != 0, spacing = (d->flags & SPH_RENDER_SPACING) != 0;
     int64_t total = 1;
     for (int a = 0; a < 3; a++) {
-        if (d->n[a] < 1) return rd_arg(c, "n must be >= 1 on every axis", who);
+        if (d->n[a] < 1) return arg_error(c, who, "n must be >= 1 on every axis");
         total *= d->n[a];
-        if (total > ((int64_t)1 << 40)) return rd_arg(c, "too many nodes", who);
+        if (total > ((int64_t)1 << 40)) return arg_error(c, who, "too many nodes");
     }
-    if (d->axis < -1 || d->axis > 2) return rd_arg(c, "axis must be -1, 0, 1 or 2", who);
-    if (spacing && (d->axis < 0 || d->n[d->axis] == 1)) return rd_arg(c, "SPH_RENDER_SPACING needs a projection axis with n > 1", who);
-    if (!(d->h >= 0.0) || !std::isfinite(d->h)) return rd_arg(c, "h must be finite and >= 0", who);
+    if (d->axis < -1 || d->axis > 2) return arg_error(c, who, "axis must be -1, 0, 1 or 2");
+    if (spacing && (d->axis < 0 || d->n[d->axis] == 1)) return arg_error(c, who, "SPH_RENDER_SPACING needs a projection axis with n > 1");
+    if (!(d->h >= 0.0) || !std::isfinite(d->h)) return arg_error(c, who, "h must be finite and >= 0");
     const int64_t want = d->axis < 0 ? total : total / d->n[d->axis];
-    if (out_len != want) return rd_arg(c, "out_len does not match the node counts", who);
+    if (out_len != want) return arg_error(c, who, "out_len does not match the node counts");
     if (!autob)
         for (int a = 0; a < 3; a++)
-            if (!(d->lo[a] <= d->hi[a]) || !std::isfinite(d->lo[a]) || !std::isfinite(d->hi[a])) return rd_arg(c, "lo > hi", who);
+            if (!(d->lo[a] <= d->hi[a]) || !std::isfinite(d->lo[a]) || !std::isfinite(d->hi[a])) return arg_error(c, who, "lo > hi");
     for (int a = 0; a < 3; a++)
-        if (std::isnan(d->clip_lo[a]) || std::isnan(d->clip_hi[a])) return rd_arg(c, "NaN clip box", who);
+        if (std::isnan(d->clip_lo[a]) || std::isnan(d->clip_hi[a])) return arg_error(c, who, "NaN clip box");
     if (fs && fs->stale) {
         c->err = "sph_render_field: the field or rho is stale (sph_download_field would refuse it)";
         return SPH_ERR_STATE;
@@ -489,8 +441,8 @@ int render_impl(sph_ctx *c, sph_render_desc *d, const FieldSpec *fs, double *out
     s.n_slots = c->cap > 0 ? c->n_slots : 0;
     s.n_owned = (int32_t)c->n_owned;
 
-    if (!c->rnd_small) RD_TRY(ctx_alloc(c, &c->rnd_small, (size_t)RB_MAX * NSTAT + 16, "render statistics"));
-    if (!c->rnd_pinned) RD_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->rnd_pinned), 32 * sizeof(double), hipHostMallocDefault));
+    if (!c->rnd_small) SPH_TRY(ctx_alloc(c, &c->rnd_small, (size_t)RB_MAX * NSTAT + 16, "render statistics"));
+    SPH_TRY(analysis_pinned(c));
     double *stats = c->rnd_small + (size_t)RB_MAX * NSTAT;
     uint32_t *cursor = reinterpret_cast<uint32_t *>(stats + NSTAT + 1);
 
@@ -500,13 +452,13 @@ int render_impl(sph_ctx *c, sph_render_desc *d, const FieldSpec *fs, double *out
         const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((s.n_slots + RB - 1) / RB, RB_MAX));
         render_stats_partial<<<dim3(nb), dim3(RB), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], s, c->rnd_small);
         render_stats_final<<<dim3(1), dim3(NSTAT * 64), 0, st>>>(c->rnd_small, nb, stats);
-        RD_HIP(hipGetLastError());
-        RD_HIP(hipMemcpyAsync(c->rnd_pinned, stats, NSTAT * sizeof(double), hipMemcpyDeviceToHost, st));
-        RD_HIP(hipStreamSynchronize(st));
+        SPH_HIP(hipGetLastError());
+        SPH_HIP(hipMemcpyAsync(c->rnd_pinned, stats, NSTAT * sizeof(double), hipMemcpyDeviceToHost, st));
+        SPH_HIP(hipStreamSynchronize(st));
         for (int k = 0; k < NSTAT; k++) hs[k] = c->rnd_pinned[k];
     }
     const int64_t count = (int64_t)hs[8];
-    if (count == 0 && autob) return rd_arg(c, "SPH_RENDER_AUTO_BOUNDS over an empty selection", who);
+    if (count == 0 && autob) return arg_error(c, who, "SPH_RENDER_AUTO_BOUNDS over an empty selection");
     const double h_max = hs[6], h_min = -hs[7];
     if (count > 0 && !(h_min > 0.0 && std::isfinite(h_max))) {
         c->err = std::string(who) + ": a selected particle has h <= 0 or a non-finite h";
@@ -544,57 +496,65 @@ int render_impl(sph_ctx *c, sph_render_desc *d, const FieldSpec *fs, double *out
     // ---- scratch ----------------------------------------------------------------------------------------------------
     const int64_t cap = std::max<int64_t>(count, 1);
     size_t sort_bytes = 0;
-    RD_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                     (uint32_t *)nullptr, (size_t)cap, 0u, 64u, st));
+    SPH_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
+                                      (uint32_t *)nullptr, (size_t)cap, 0u, 64u, st));
     const int nplanes = fs ? 6 : 5;
     const bool host_w = fs && fs->wout && host_out, host_v = fs && fs->values && fs->host_values;
-    size_t off[10], bytes = 0;
-    const size_t sizes[10] = {8 * (size_t)cap, 8 * (size_t)cap, 4 * (size_t)cap, 4 * (size_t)cap, sort_bytes,
-                              4 * (size_t)(ncells + 2), 8 * (size_t)nplanes * (size_t)cap, host_out ? 8 * (size_t)out_len : 0,
-                              host_w ? 8 * (size_t)out_len : 0, host_v ? 8 * (size_t)std::max<int64_t>(c->n, 0) : 0};
-    for (int k = 0; k < 10; k++) { off[k] = bytes; bytes += align_up(sizes[k]); }
+    uint64_t *keys, *keys_alt;
+    uint32_t *vals, *vals_alt;
+    char *sort_tmp;
+    int32_t *cell_start;
+    double *rec, *h_out, *h_wout, *values_copy;
+    auto layout = [&](Carve cv) {
+        keys = cv.take<uint64_t>(cap);
+        keys_alt = cv.take<uint64_t>(cap);
+        vals = cv.take<uint32_t>(cap);
+        vals_alt = cv.take<uint32_t>(cap);
+        sort_tmp = cv.take<char>(sort_bytes);
+        cell_start = cv.take<int32_t>(ncells + 2);
+        rec = cv.take<double>((size_t)nplanes * (size_t)cap);
+        h_out = cv.take<double>(host_out ? out_len : 0);              // the host form's device copies
+        h_wout = cv.take<double>(host_w ? out_len : 0);
+        values_copy = cv.take<double>(host_v ? std::max<int64_t>(c->n, 0) : 0);     // the host form's values, on the device
+        return cv.bytes;
+    };
     char *buf = nullptr;
-    RD_TRY(scratch(c, bytes, &buf));
-    uint64_t *keys = reinterpret_cast<uint64_t *>(buf + off[0]), *keys_alt = reinterpret_cast<uint64_t *>(buf + off[1]);
-    uint32_t *vals = reinterpret_cast<uint32_t *>(buf + off[2]), *vals_alt = reinterpret_cast<uint32_t *>(buf + off[3]);
-    void *sort_tmp = buf + off[4];
-    int32_t *cell_start = reinterpret_cast<int32_t *>(buf + off[5]);
-    double *rec = reinterpret_cast<double *>(buf + off[6]);
-    double *d_out = host_out ? reinterpret_cast<double *>(buf + off[7]) : out;
-    double *d_wout = host_w ? reinterpret_cast<double *>(buf + off[8]) : (fs ? fs->wout : nullptr);
-    double *values_copy = reinterpret_cast<double *>(buf + off[9]);     // the host form's values, on the device
+    SPH_TRY(analysis_scratch(c, layout(Carve{}), &buf));
+    layout(Carve{buf});
+    double *d_out = host_out ? h_out : out;
+    double *d_wout = host_w ? h_wout : (fs ? fs->wout : nullptr);
     const double *d_values = host_v ? values_copy : (fs ? fs->values : nullptr);
 
     // ---- read-back 2: the particles that can reach a node -----------------------------------------------------------
     int64_t nsel = 0;
     if (count > 0) {
-        RD_HIP(hipMemsetAsync(cursor, 0, sizeof(uint32_t), st));
+        SPH_HIP(hipMemsetAsync(cursor, 0, sizeof(uint32_t), st));
         const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((s.n_slots + RB - 1) / RB, 4 * RB_MAX));
         render_select<<<dim3(nb), dim3(RB), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], s, ndk, g, keys, vals, cursor, cap);
-        RD_HIP(hipGetLastError());
-        RD_HIP(hipMemcpyAsync(c->rnd_pinned + 16, cursor, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        RD_HIP(hipStreamSynchronize(st));
+        SPH_HIP(hipGetLastError());
+        SPH_HIP(hipMemcpyAsync(c->rnd_pinned + 16, cursor, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SPH_HIP(hipStreamSynchronize(st));
         nsel = std::min<int64_t>(*reinterpret_cast<const uint32_t *>(c->rnd_pinned + 16), cap);
     }
 
     if (nsel == 0) {
-        RD_HIP(hipMemsetAsync(d_out, 0, (size_t)out_len * sizeof(double), st));
-        if (d_wout) RD_HIP(hipMemsetAsync(d_wout, 0, (size_t)out_len * sizeof(double), st));
+        SPH_HIP(hipMemsetAsync(d_out, 0, (size_t)out_len * sizeof(double), st));
+        if (d_wout) SPH_HIP(hipMemsetAsync(d_wout, 0, (size_t)out_len * sizeof(double), st));
     } else {
         unsigned cbits = 1;
         while (cbits < 32 && ((int64_t)1 << cbits) < ncells) cbits++;
         size_t tmp = sort_bytes;
-        RD_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)nsel, 0u, 32u + cbits, st));
+        SPH_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)nsel, 0u, 32u + cbits, st));
         render_cells<<<dim3((unsigned)((ncells + 1 + 255) / 256)), dim3(256), 0, st>>>(keys_alt, nsel, ncells, cell_start);
         if (!fs) {
             render_records<<<dim3((unsigned)((nsel + 255) / 256)), dim3(256), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z],
                                                                                        c->f[SPH_F_M], s, vals_alt, nsel, rec, cap);
         } else {
-            if (host_v) RD_HIP(hipMemcpyAsync(values_copy, fs->values, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, st));
+            if (host_v) SPH_HIP(hipMemcpyAsync(values_copy, fs->values, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, st));
             render_field_records<<<dim3((unsigned)((nsel + 255) / 256)), dim3(256), 0, st>>>(
                 c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], c->f[SPH_F_M], fs->rho, fs->a, d_values, s, vals_alt, nsel, rec, cap);
         }
-        RD_HIP(hipGetLastError());
+        SPH_HIP(hipGetLastError());
         GatherArgs a{};
         a.nd = ndk; a.g = g; a.reach = reach;
         if (!fs) a.r = Recs{rec, rec + cap, rec + 2 * cap, rec + 3 * cap, rec + 4 * cap, cell_start, nullptr};
@@ -608,22 +568,22 @@ int render_impl(sph_ctx *c, sph_render_desc *d, const FieldSpec *fs, double *out
         a.wout = d_wout;
         a.normalise = fs && fs->normalise;
         const int64_t tiles = (int64_t)((nd.n[U] + TU - 1) / TU) * a.tiles_v;
-        if (tiles > 0x7fffffff) return rd_arg(c, "too many node columns");
+        if (tiles > 0x7fffffff) return arg_error(c, "sph_render_density", "too many node columns");
         const int ysegs = a.project ? 1 : std::min(a.nseg, 65535);
         if (!fs) {
-            RD_HIP(W == 0 ? launch_gather<0>(a, (int)tiles, ysegs, st)
-                          : (W == 1 ? launch_gather<1>(a, (int)tiles, ysegs, st) : launch_gather<2>(a, (int)tiles, ysegs, st)));
+            SPH_HIP(W == 0 ? launch_gather<0>(a, (int)tiles, ysegs, st)
+                           : (W == 1 ? launch_gather<1>(a, (int)tiles, ysegs, st) : launch_gather<2>(a, (int)tiles, ysegs, st)));
         } else {
             const bool den = fs->normalise || fs->wout;
-            RD_HIP(W == 0 ? launch_field_gather<0>(a, den, (int)tiles, ysegs, st)
-                          : (W == 1 ? launch_field_gather<1>(a, den, (int)tiles, ysegs, st)
-                                    : launch_field_gather<2>(a, den, (int)tiles, ysegs, st)));
+            SPH_HIP(W == 0 ? launch_field_gather<0>(a, den, (int)tiles, ysegs, st)
+                           : (W == 1 ? launch_field_gather<1>(a, den, (int)tiles, ysegs, st)
+                                     : launch_field_gather<2>(a, den, (int)tiles, ysegs, st)));
         }
     }
     if (host_out) {
-        RD_HIP(hipMemcpyAsync(out, d_out, (size_t)out_len * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (host_w) RD_HIP(hipMemcpyAsync(fs->wout, d_wout, (size_t)out_len * sizeof(double), hipMemcpyDeviceToHost, st));
-        RD_HIP(hipStreamSynchronize(st));
+        SPH_HIP(hipMemcpyAsync(out, d_out, (size_t)out_len * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (host_w) SPH_HIP(hipMemcpyAsync(fs->wout, d_wout, (size_t)out_len * sizeof(double), hipMemcpyDeviceToHost, st));
+        SPH_HIP(hipStreamSynchronize(st));
     }
     if (autob)
         for (int a = 0; a < 3; a++) { d->lo[a] = nd.lo[a]; d->hi[a] = nd.hi[a]; }
@@ -632,7 +592,23 @@ int render_impl(sph_ctx *c, sph_render_desc *d, const FieldSpec *fs, double *out
 
 }  // namespace
 
-int render_scratch(sph_ctx *c, size_t bytes, char **out) { return scratch(c, bytes, out); }
+// the analysis calls' scratch: grows, never shrinks; freed with the context.  A grown buffer replaces the old one only
+// after the stream has drained (a previous _dev call may still read it).
+int analysis_scratch(sph_ctx *c, size_t bytes, char **out) {
+    if (bytes > c->rnd_bytes) {
+        SPH_HIP(hipStreamSynchronize(c->stream));
+        ctx_free_ptr(c, c->rnd_buf); c->rnd_buf = nullptr; c->rnd_bytes = 0;
+        SPH_TRY(ctx_alloc_bytes(c, &c->rnd_buf, bytes, "render scratch"));
+        c->rnd_bytes = bytes;
+    }
+    *out = static_cast<char *>(c->rnd_buf);
+    return SPH_OK;
+}
+
+int analysis_pinned(sph_ctx *c) {
+    if (!c->rnd_pinned) SPH_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->rnd_pinned), 32 * sizeof(double), hipHostMallocDefault));
+    return SPH_OK;
+}
 
 void render_free(sph_ctx *c) {
     ctx_free_ptr(c, c->rnd_buf); c->rnd_buf = nullptr; c->rnd_bytes = 0;
@@ -648,13 +624,13 @@ int render_density(sph_ctx *c, sph_render_desc *d, double *out, int64_t out_len,
 int render_field(sph_ctx *c, sph_render_field_desc *d, const double *values, double *out, double *wout, int64_t out_len,
                  bool host, bool (*ready)(const sph_ctx *, int)) {
     const char *who = "sph_render_field";
-    if (!d) return rd_arg(c, "null descriptor", who);
-    if (d->reserved != 0) return rd_arg(c, "reserved must be 0", who);
-    if (d->field < SPH_RENDER_FIELD_VALUES || d->field >= SPH_F_COUNT) return rd_arg(c, "field id out of range", who);
+    if (!d) return arg_error(c, who, "null descriptor");
+    if (d->reserved != 0) return arg_error(c, who, "reserved must be 0");
+    if (d->field < SPH_RENDER_FIELD_VALUES || d->field >= SPH_F_COUNT) return arg_error(c, who, "field id out of range");
     if ((d->field == SPH_RENDER_FIELD_VALUES) != (values != nullptr))
-        return rd_arg(c, "values must be given with SPH_RENDER_FIELD_VALUES and only then", who);
-    if (d->weight != SPH_RENDER_WEIGHT_MASS && d->weight != SPH_RENDER_WEIGHT_VOLUME) return rd_arg(c, "unknown weight", who);
-    if (d->normalise != 0 && d->normalise != 1) return rd_arg(c, "normalise must be 0 or 1", who);
+        return arg_error(c, who, "values must be given with SPH_RENDER_FIELD_VALUES and only then");
+    if (d->weight != SPH_RENDER_WEIGHT_MASS && d->weight != SPH_RENDER_WEIGHT_VOLUME) return arg_error(c, who, "unknown weight");
+    if (d->normalise != 0 && d->normalise != 1) return arg_error(c, who, "normalise must be 0 or 1");
     const bool volume = d->weight == SPH_RENDER_WEIGHT_VOLUME;
     FieldSpec fs{};
     fs.a = d->field >= 0 ? c->f[d->field] : nullptr;

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <unordered_map>
@@ -51,6 +52,12 @@ struct HashView {
     uint64_t mask;             // table entries - 1 (a power of two)
     int32_t sh1, sh2;          // bit offsets of c1 and c2 in a key
 };
+// where a 64-bit cell key starts probing (this table and the analysis calls' cell_table.hpp)
+__device__ __forceinline__ uint64_t hash_mix(uint64_t k) {
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
+    return k ^ (k >> 33);
+}
 
 // Constants every pair kernel needs; passed by value as a kernel argument (SGPRs).
 struct PairConst {
@@ -240,7 +247,7 @@ struct sph_ctx {
     int64_t timing_seen[32] = {};    // launches of group k since timing was switched on
     sph::TimingSlot tslot[SPH_K_COUNT];
 
-    // sph_render_density (render.hip): private scratch, never the grid / list buffers above
+    // the analysis calls (render, profile, energy, groups, gradients): private scratch, never the grid / list buffers above
     void *rnd_buf = nullptr; size_t rnd_bytes = 0;
     double *rnd_small = nullptr;     // per-block statistics, their result and the selection cursor
     double *rnd_pinned = nullptr;    // pinned read-back slots
@@ -249,7 +256,49 @@ struct sph_ctx {
     hipEvent_t prf_evt = nullptr;
 };
 
+// Host scaffolding of every launcher that has the context as `c` and returns a status.
+// SPH_HIP: a failing HIP call goes into c->err, as its own text and HIP's, and returns SPH_ERR_HIP.
+#define SPH_HIP(expr)                                                       \
+    do {                                                                    \
+        hipError_t _e = (expr);                                             \
+        if (_e != hipSuccess) {                                             \
+            c->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
+            return SPH_ERR_HIP;                                             \
+        }                                                                   \
+    } while (0)
+
+// SPH_TRY: a status other than SPH_OK is returned as it is (whoever produced it has set c->err)
+#define SPH_TRY(expr)                  \
+    do {                               \
+        int _s = (expr);               \
+        if (_s != SPH_OK) return _s;   \
+    } while (0)
+
 namespace sph {
+
+inline int arg_error(sph_ctx *c, const char *who, const char *what) {
+    c->err = std::string(who) + ": " + what;
+    return SPH_ERR_ARG;
+}
+
+inline size_t align_up(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// blocks of `per` items over n items, at least one (an empty launch is an error)
+inline unsigned blocks(int64_t n, int per) { return (unsigned)std::max<int64_t>((n + per - 1) / per, 1); }
+
+// A call's buffers inside one scratch allocation.  The call writes its layout once, as a function that take()s every
+// buffer in order, and runs it twice: on a null base for the size, then on the allocation.  A buffer's element type and
+// count are stated where its pointer is made, every buffer starts 256-byte aligned, and a count of 0 takes no room.
+struct Carve {
+    char *base = nullptr;
+    size_t bytes = 0;
+    template <class T>
+    T *take(size_t count) {
+        T *p = base ? reinterpret_cast<T *>(base + bytes) : nullptr;
+        bytes += align_up(count * sizeof(T));
+        return p;
+    }
+};
 
 // device memory owned by the context (tracked so that sph_stats.device_bytes is exact)
 int ctx_alloc_bytes(sph_ctx *c, void **p, size_t bytes, const char *what);
@@ -345,8 +394,10 @@ int render_density(sph_ctx *c, sph_render_desc *d, double *out, int64_t out_len,
 int render_field(sph_ctx *c, sph_render_field_desc *d, const double *values, double *out, double *wout, int64_t out_len,
                  bool host, bool (*ready)(const sph_ctx *, int));
 void render_free(sph_ctx *c);
-// the render's scratch (grows, never shrinks); sph_profile uses it too
-int render_scratch(sph_ctx *c, size_t bytes, char **out);
+// what the analysis calls share (render.hip; freed by render_free): their scratch, which grows and never shrinks, and the
+// 32 pinned doubles of their read-backs, allocated at the first call that needs them
+int analysis_scratch(sph_ctx *c, size_t bytes, char **out);
+int analysis_pinned(sph_ctx *c);
 // disc profiles (profile.hip): host form (sums and / or table host memory, one read-back) or device form (sums only)
 int profile_sums(sph_ctx *c, sph_profile_desc *d, double *sums, double *table, int64_t n_bins, bool host);
 void profile_free(sph_ctx *c);

@@ -708,15 +708,6 @@ int32_t tile_cap_q(int nq, bool tablds = true) {
 
 }  // namespace
 
-#define TL_CHECK(expr)                                                      \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) {                                             \
-            c->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return SPH_ERR_HIP;                                             \
-        }                                                                   \
-    } while (0)
-
 // a context whose groups outgrow the 16-bit entries leaves the tiled path for good: the untiled 32-bit list of pairs.hip
 static int leave_tiled_path(sph_ctx *c) {
     c->tiled = false; c->whole_tile = false; c->packed_list = false;
@@ -776,7 +767,7 @@ int nlist_build_tiled(sph_ctx *c) {
     const int p = c->ring_nl;
     int32_t *slot = reinterpret_cast<int32_t *>(c->h_pinned + 240 + 8 * p);
     if (trusted) {
-        TL_CHECK(hipEventSynchronize(c->ev_nl[1 - p]));
+        SPH_HIP(hipEventSynchronize(c->ev_nl[1 - p]));
         const int32_t *prev = reinterpret_cast<const int32_t *>(c->h_pinned + 240 + 8 * (1 - p));
         if (prev[0] > c->nl_cap) { c->err = "neighbour list overflowed in the previous build (lists grew by more than a third within one step)"; return SPH_ERR_STATE; }
         if (prev[3] >= LIST16_MAX_NEED) { c->err = "neighbour list: a group's candidate intervals outgrew the 16-bit entries within one step"; return SPH_ERR_STATE; }
@@ -791,18 +782,18 @@ int nlist_build_tiled(sph_ctx *c) {
                                                                     c->ncount, c->wave_max, c->d_flags, c->orig, (int32_t)c->n_owned,
                                                                     c->whole_tile ? reinterpret_cast<int2 *>(c->deal) : nullptr,
                                                                     c->plan_f, c->whole_tile ? c->plan_h : nullptr);
-        TL_CHECK(hipGetLastError());
+        SPH_HIP(hipGetLastError());
         {
             const int64_t ngd = (n + WT_BS - 1) / WT_BS, ngf = (n + FQ_T - 1) / FQ_T;
             plan_reduce_kernel<<<dim3(1), dim3(1024), 0, c->stream>>>(
                 ngd, ngf, c->plan_f, c->whole_tile ? tile_cap(pc.nq, 4, true) : 0, c->whole_tile ? tile_cap_q(pc.nq) : LIST16_MAX_NEED,
                 c->whole_tile ? tile_cap(pc.nq, 4, false) : 0, c->whole_tile ? tile_cap_q(pc.nq, false) : LIST16_MAX_NEED,
                 c->whole_tile ? c->plan_d : nullptr, c->whole_tile ? c->plan_h : nullptr, slot);
-            TL_CHECK(hipGetLastError());
+            SPH_HIP(hipGetLastError());
         }
-        TL_CHECK(hipEventRecord(c->ev_nl[p], c->stream));
+        SPH_HIP(hipEventRecord(c->ev_nl[p], c->stream));
         if (trusted) break;
-        TL_CHECK(hipStreamSynchronize(c->stream));
+        SPH_HIP(hipStreamSynchronize(c->stream));
         c->host_syncs++;
         if (2 * (int64_t)slot[3] >= LIST16_MAX_NEED) return leave_tiled_path(c);
         digest(slot);

@@ -1088,15 +1088,6 @@ __global__ __launch_bounds__(VBLOCK) void update_h_kernel(GridDesc g, PairConst 
 
 }  // namespace
 
-#define VH_CHECK(expr)                                                      \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) {                                             \
-            c->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return SPH_ERR_HIP;                                             \
-        }                                                                   \
-    } while (0)
-
 hipError_t varh_sort_tmp_bytes(int64_t n, size_t *bytes) {
     size_t b = 0;
     hipError_t e = rocprim::radix_sort_pairs(nullptr, b, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
@@ -1114,9 +1105,9 @@ int varh_h_stats(sph_ctx *c, bool with_growth) {
     // with_growth: c->h_new holds the lengths the list in place was built with (launch_update_h swapped the two arrays)
     h_stats_partial<<<dim3(nb), dim3(VBLOCK), 0, c->stream>>>(c->f[SPH_F_H], with_growth ? c->h_new : nullptr, n, part);
     h_stats_final<<<dim3(1), dim3(64), 0, c->stream>>>(part, nb, part + 2048);
-    VH_CHECK(hipGetLastError());
-    VH_CHECK(hipMemcpyAsync(c->h_pinned + 28, part + 2048, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    VH_CHECK(hipStreamSynchronize(c->stream));
+    SPH_HIP(hipGetLastError());
+    SPH_HIP(hipMemcpyAsync(c->h_pinned + 28, part + 2048, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
     c->h_max_glob = c->h_pinned[28];
     c->h_mean = c->h_pinned[29] / (double)n;
     c->h_shrink = INFINITY;
@@ -1163,17 +1154,17 @@ int varh_leaf_build(sph_ctx *c) {
         c->root_box[3] = size;
         { const int st = global_keys_sorted(c); if (st != SPH_OK) return st; }
         leaf_boxes_ext<<<dim3(gb), dim3(VBLOCK), 0, c->stream>>>(rb, c->g_keys_alt, c->gx_n, n, prec, reinterpret_cast<double4 *>(c->lrec), c->leaf_half);
-        VH_CHECK(hipGetLastError());
+        SPH_HIP(hipGetLastError());
     } else {
         leaf_keys<<<dim3(gb), dim3(VBLOCK), 0, c->stream>>>(rb, prec, n, c->mkeys, c->mvals);
-        VH_CHECK(hipGetLastError());
+        SPH_HIP(hipGetLastError());
         size_t tmp = c->msort_tmp_bytes;
-        VH_CHECK(rocprim::radix_sort_pairs(c->msort_tmp, tmp, c->mkeys, c->mkeys_alt, c->mvals, c->mvals_alt, (size_t)n, 0u, 63u, c->stream));
+        SPH_HIP(rocprim::radix_sort_pairs(c->msort_tmp, tmp, c->mkeys, c->mkeys_alt, c->mvals, c->mvals_alt, (size_t)n, 0u, 63u, c->stream));
         leaf_boxes<<<dim3(gb), dim3(VBLOCK), 0, c->stream>>>(rb, c->mkeys_alt, c->mvals_alt, n, prec, reinterpret_cast<double4 *>(c->lrec), c->leaf_half);
-        VH_CHECK(hipGetLastError());
+        SPH_HIP(hipGetLastError());
         c->path_keys_valid = true;           // the gravity tree and the accretion pass of this grid build take them from here
     }
-    VH_CHECK(launch_cell_hmax(c, prec));
+    SPH_HIP(launch_cell_hmax(c, prec));
     return SPH_OK;
 }
 
@@ -1183,7 +1174,7 @@ int varh_refresh_h(sph_ctx *c) {
     if (n == 0) return SPH_OK;
     refresh_h_records<<<dim3((unsigned)((n + VBLOCK - 1) / VBLOCK)), dim3(VBLOCK), 0, c->stream>>>(
         n, c->f[SPH_F_H], c->leaf_half, reinterpret_cast<double4 *>(c->prec), reinterpret_cast<double4 *>(c->lrec));
-    VH_CHECK(launch_cell_hmax(c, reinterpret_cast<const double4 *>(c->prec)));
+    SPH_HIP(launch_cell_hmax(c, reinterpret_cast<const double4 *>(c->prec)));
     return SPH_OK;
 }
 
@@ -1203,8 +1194,8 @@ int varh_nlist_build(sph_ctx *c) {
             c->cell_start, c->hv, c->cell_hmax, n, (int32_t)c->n_owned, c->nl_cap, c->nlist, c->ncount, c->ntail, c->wave_max, c->wave_class,
             c->numbers_set ? c->number : nullptr);
         max_to_host<<<dim3(1), dim3(1024), 0, c->stream>>>(c->wave_class, (n + 63) / 64, reinterpret_cast<int32_t *>(c->h_pinned + 9));
-        VH_CHECK(hipGetLastError());
-        VH_CHECK(hipStreamSynchronize(c->stream));
+        SPH_HIP(hipGetLastError());
+        SPH_HIP(hipStreamSynchronize(c->stream));
         const int32_t mx = *reinterpret_cast<int32_t *>(c->h_pinned + 9);
         c->nl_max = mx;
         if (mx <= c->nl_cap) {
@@ -1235,7 +1226,7 @@ int varh_nlist_reflag(sph_ctx *c) {
     nlist_v_reflag<<<dim3((unsigned)((n + VBLOCK - 1) / VBLOCK)), dim3(VBLOCK), 0, c->stream>>>(
         reinterpret_cast<const double4 *>(c->prec), reinterpret_cast<const double4 *>(c->lrec), c->orig, n, (int32_t)c->n_owned, c->nl_cap,
         c->nlist, c->ncount, c->ntail, c->wave_max, c->numbers_set ? c->number : nullptr);
-    VH_CHECK(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     c->list_has_margin = false;        // the margin rows may be overwritten: calc_smoothing falls back to its cell walk on this list
     c->nlist_reflags++;
     return SPH_OK;
@@ -1251,7 +1242,7 @@ int varh_reflag_density(sph_ctx *c, const PairConst &pc) {
         c->f[SPH_F_M], c->orig, n, (int32_t)c->n_owned, c->nl_cap, c->nlist, c->ncount, c->ntail, c->wave_max,
         c->numbers_set ? c->number : nullptr, c->w_tab, c->dw_tab, c->f[SPH_F_U], c->f[SPH_F_ALPHA], c->f[SPH_F_VX], c->f[SPH_F_VY],
         c->f[SPH_F_VZ], c->f[SPH_F_RHO], c->f[SPH_F_OMEGA], c->f[SPH_F_P], c->f[SPH_F_C], c->frec);
-    VH_CHECK(hipGetLastError());
+    SPH_HIP(hipGetLastError());
     c->list_has_margin = false;
     c->nlist_reflags++;
     return SPH_OK;
