@@ -673,6 +673,67 @@ int sph_gradients(sph_ctx *ctx, const sph_gradients_desc *d, const double *value
 int sph_gradients_dev(sph_ctx *ctx, const sph_gradients_desc *d, const double *d_values, double *d_out, int64_t n_out,
                       double *d_rho, int64_t *d_counts);
 
+/* ---- SPH interpolation at arbitrary points: density, any field, or the caller's values at points that move independently
+ *      of the gas (an unwrapped (R, phi) map, an (R, z) cut, an inclined plane, a probe line, tracers) -------------------
+ * Sources  exactly the renders' selection: the context's owned gas particles (original ids < n_owned; ghosts and sinks
+ *          never) with a finite position strictly inside clip_lo < x < clip_hi on every axis (-INFINITY / +INFINITY: no
+ *          clip).  Partial results of ranks or contexts therefore add: summing num and den over ranks and dividing gives
+ *          the union's normalised value, as sph_render_field documents for images.
+ * h        the renders' rule: desc.h when desc.h > 0, else each particle's own h (SPH_F_H on a variable-h context, params.h
+ *          on a fixed-h one).  The points have no h: this is the scatter form, every source spreads with its own h_j.
+ * Sums     the renders' kernel, weights and term arithmetic, without fused multiply-adds: s_j = 1 / (pi h_j^3) with the
+ *          DOUBLE-precision pi, ws_j = m_j s_j (SPH_RENDER_WEIGHT_MASS) or (m_j / rho_j) s_j (SPH_RENDER_WEIGHT_VOLUME; rho
+ *          as sph_download_field(SPH_F_RHO) returns it, SPH_ERR_STATE exactly when that call would refuse),
+ *          q = sqrt((dx dx + dy dy) + dz dz) * (1 / h_j) with dx = p_x - x_j, Wn = 1 - 1.5 q^2 + 0.75 q^3 (q <= 1),
+ *          0.25 (2 - q)^3 (1 < q <= 2); den(p) = sum ws_j Wn, num_k(p) = sum (ws_j A_j^(k)) Wn.  A source contributes iff
+ *          q <= 2.  A point farther than 2 h_j from every source gets den, num and the normalised value exactly 0.0.
+ * Fields   fields[k], k < n_fields <= SPH_SAMPLE_MAX_FIELDS, all in one walk: an SPH_F_* id read as sph_download_field
+ *          reads it (SPH_ERR_STATE when stale), or SPH_SAMPLE_VALUES: row k of values, values[k * n + id], n = sph_count,
+ *          in sph_download_field order -- host memory for sph_sample, device memory for _dev.  Only the sources' entries
+ *          are read.
+ * Points   three arrays of n_points doubles (struct of arrays, as sph_upload), host memory for sph_sample, device memory
+ *          for _dev.  0 <= n_points <= 2^31 - 1; n_points == 0 succeeds and writes no row (counts, if given: 0, 0).  A
+ *          point with a non-finite coordinate gets NaN in every output row and is counted.
+ * Output   out[k * n_points + p] = num_k(p), or with SPH_SAMPLE_NORMALISE num_k(p) / den(p) (exactly 0.0 where den == 0.0);
+ *          n_out == n_fields * n_points.  weight (optional unless n_fields == 0): den(p), n_points doubles; with the MASS
+ *          weight and n_fields == 0 this is the SPH density at the points.  counts (optional, 2 x int64): the points with
+ *          den != 0, the points with a non-finite coordinate.
+ * Order    the search structure is a function of the source set and the descriptor only, never of the points.  The
+ *          sources are binned by LEVELS of h: with one h there is one level; with per-particle h a level is an aligned
+ *          group of 2^g quarter octaves of h (half octaves, g = 1, unless more than 64 such groups are occupied: g then
+ *          grows until at most 64 are), level l with upper edge H_l in cells of edge 2 H_l (1 + 1e-6) over the source box
+ *          (enlarged where an axis would need more than 2^19 - 8 cells).  Every point adds its sources level by level in
+ *          ascending h, within a level over the <= 27 cells around it in ascending cell key (x slowest), within a cell in
+ *          ascending original id.  A point's values are therefore bitwise the same over repeated calls, any order or
+ *          subset of the points (one point alone included), the context's slot order (a fresh upload, or after
+ *          sph_density re-sorts), dense or SPH_FLAG_HASHED_GRID grids, and the host and device forms.  No float atomics.
+ * cost     host form: the copies in, one synchronisation, the copies out.  Device form: ordered on the context's stream,
+ *          no synchronisation; a source with h <= 0 or a non-finite h shows as d_counts[0] == -1 and NaN outputs (host
+ *          form: SPH_ERR_STATE).  No state, field, statistic (other than device_bytes: the render's scratch), flag, grid,
+ *          list or dt of the context changes; a run that samples after every step is bitwise the run without it.
+ * SPH_ERR_ARG: null descriptor, null point arrays with n_points > 0, n_points out of range, n_fields outside 0 ..
+ * SPH_SAMPLE_MAX_FIELDS, a bad field id, values missing while a field is SPH_SAMPLE_VALUES or given while none is,
+ * n_out != n_fields n_points, null out with n_fields > 0, null weight with n_fields == 0, weight not MASS / VOLUME, unknown
+ * flags, reserved != 0, h < 0 or NaN, a NaN clip; nothing is written then.  SPH_ERR_STATE: a stale field or rho; params.h <= 0
+ * on a fixed-h context with desc.h == 0; host form, a source h <= 0 or non-finite.  SPH_ERR_NOMEM: the scratch does not fit.
+ * An empty source set gives all-zero outputs, not an error. */
+#define SPH_SAMPLE_NORMALISE   1        /* out = num / den (0 where den == 0)                                        */
+#define SPH_SAMPLE_MAX_FIELDS  4
+#define SPH_SAMPLE_VALUES    (-1)       /* fields[k]: row k of values                                                */
+typedef struct sph_sample_desc {
+    double  clip_lo[3], clip_hi[3];          /* strict SOURCE clip box; -INFINITY / +INFINITY = none              */
+    double  h;                               /* > 0: one h for every source; 0: each particle's own h             */
+    int32_t fields[SPH_SAMPLE_MAX_FIELDS];   /* SPH_F_* or SPH_SAMPLE_VALUES (row k of values)                    */
+    int32_t n_fields;                        /* 0 .. SPH_SAMPLE_MAX_FIELDS; 0: the weight alone (weight required) */
+    int32_t weight;                          /* SPH_RENDER_WEIGHT_MASS / SPH_RENDER_WEIGHT_VOLUME                 */
+    int32_t flags;                           /* SPH_SAMPLE_NORMALISE                                              */
+    int32_t reserved;                        /* must be 0                                                         */
+} sph_sample_desc;                           /* 88 bytes */
+int sph_sample(sph_ctx *ctx, const sph_sample_desc *d, int64_t n_points, const double *px, const double *py, const double *pz,
+               const double *values, double *host_out, int64_t n_out, double *host_weight, int64_t *counts);
+int sph_sample_dev(sph_ctx *ctx, const sph_sample_desc *d, int64_t n_points, const double *d_px, const double *d_py,
+                   const double *d_pz, const double *d_values, double *d_out, int64_t n_out, double *d_weight, int64_t *d_counts);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too

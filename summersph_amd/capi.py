@@ -47,6 +47,7 @@ SYMBOLS = [
     "sph_energy", "sph_energy_dev",
     "sph_groups", "sph_groups_dev",
     "sph_gradients", "sph_gradients_dev",
+    "sph_sample", "sph_sample_dev",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
@@ -74,6 +75,9 @@ GROUPS_COLUMNS = ["N", "M", "x", "y", "z", "vx", "vy", "vz", "r_rms", "r_max", "
 GRAD_CORRECTED = 1
 GRAD_MAX_FIELDS = 4
 GRAD_VALUES = -1
+SAMPLE_NORMALISE = 1
+SAMPLE_MAX_FIELDS = 4
+SAMPLE_VALUES = -1
 PROFILE_SUMS = ["N", "M", "mR", "mz", "mzz", "mvR", "mvphi", "mvz", "mvRvR", "mvphivphi", "mvzvz", "mu", "malpha", "mh",
                 "mlx", "mly", "mlz", "mex", "mey", "mez"]
 
@@ -166,6 +170,31 @@ def gradients_desc(fields=("vx", "vy", "vz"), corrected=True, h=None, clip=None)
     d.fields[:] = [FIELDS.index(f) if isinstance(f, str) else int(f) for f in fields] + [0] * (GRAD_MAX_FIELDS - len(fields))
     d.n_fields = len(fields)
     d.flags = GRAD_CORRECTED if corrected else 0
+    d.h = 0.0 if h is None else float(h)
+    lo, hi = ((-np.inf,) * 3, (np.inf,) * 3) if clip is None else clip
+    d.clip_lo[:] = [float(v) for v in lo]
+    d.clip_hi[:] = [float(v) for v in hi]
+    return d
+
+
+class SampleDesc(C.Structure):
+    """sph_sample_desc (include/summersph.h): strict source clip box, h (0: each particle's own), field ids (SPH_F_* or
+    SAMPLE_VALUES), n_fields (0: the weight alone), weight (RENDER_WEIGHT_MASS / _VOLUME), flags (SAMPLE_NORMALISE), reserved"""
+    _fields_ = [("clip_lo", C.c_double * 3), ("clip_hi", C.c_double * 3), ("h", C.c_double),
+                ("fields", C.c_int32 * SAMPLE_MAX_FIELDS), ("n_fields", C.c_int32), ("weight", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+def sample_desc(fields=(), weight="mass", normalise=False, h=None, clip=None) -> SampleDesc:
+    """The descriptor of Context.sample's arguments (fields: SPH_F_* names or ids, or SAMPLE_VALUES; see there)."""
+    fields = list(fields)
+    if len(fields) > SAMPLE_MAX_FIELDS:
+        raise ValueError(f"sample: 0 .. {SAMPLE_MAX_FIELDS} fields, not {len(fields)}")
+    d = SampleDesc()
+    d.fields[:] = [FIELDS.index(f) if isinstance(f, str) else int(f) for f in fields] + [0] * (SAMPLE_MAX_FIELDS - len(fields))
+    d.n_fields = len(fields)
+    d.weight = {"mass": RENDER_WEIGHT_MASS, "volume": RENDER_WEIGHT_VOLUME}[weight] if isinstance(weight, str) else int(weight)
+    d.flags = SAMPLE_NORMALISE if normalise else 0
     d.h = 0.0 if h is None else float(h)
     lo, hi = ((-np.inf,) * 3, (np.inf,) * 3) if clip is None else clip
     d.clip_lo[:] = [float(v) for v in lo]
@@ -360,6 +389,9 @@ def load():
                                    C.c_void_p]
     lib.sph_gradients.argtypes = [C.c_void_p, C.POINTER(GradientsDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    for fn in (lib.sph_sample, lib.sph_sample_dev):
+        fn.argtypes = [C.c_void_p, C.POINTER(SampleDesc), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                       C.c_int64, C.c_void_p, C.c_void_p]
     lib.sph_gradients_dev.argtypes = [C.c_void_p, C.POINTER(GradientsDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                       C.c_void_p]
     _lib = lib
@@ -923,6 +955,92 @@ class Context:
         self._ck(self.lib.sph_gradients(self._h, C.byref(d), None if v is None else v.ctypes.data, out.ctypes.data, n_out,
                                         None if r is None else r.ctypes.data, C.byref(nt), C.byref(ns)))
         return out, r, (int(nt.value), int(ns.value))
+
+    # ---- SPH interpolation at arbitrary points (sph_sample) ----------------------------------------
+    def sample(self, points, fields=(), values=None, weight="mass", normalise=False, h=None, clip=None, weight_out=False,
+               counts=False, device=False):
+        """The SPH interpolant of the owned gas at arbitrary points (include/summersph.h, sph_sample): with ws = w_j /
+        (pi h_j^3), w_j = m_j (weight='mass') or m_j / rho_j ('volume'), den = sum ws Wn and num_k = sum ws A_k Wn over the
+        sources strictly inside the clip box ((lo xyz, hi xyz) or None).  points: an (M, 3) array or three arrays of M --
+        float64 numpy (host form) or, device=True, contiguous float64 torch tensors on the context's GPU (an (M, 3) tensor
+        is split into three).  fields: up to four SPH_F_* names or ids, or SAMPLE_VALUES for row k of values, an (n_rows,
+        sph_count) array in the upload order (numpy, or a device tensor with device=True); fields=() gives the weight
+        alone (with weight='mass' the SPH density at the points).  h: None = each particle's own h, else one h for all.
+        Returns the (K, M) array num, or num / den (0 where den is 0) with normalise=True; with weight_out (always with
+        fields=()) and / or counts a tuple (out, den, (n_hit, n_nonfinite)) of the parts asked for -- with fields=() and
+        neither flag just den.  device=True: torch tensors (sph_sample_dev).  The descriptor used is left in
+        self.sample_desc."""
+        d = sample_desc(fields, weight, normalise, h, clip)
+        n, nf = self.n, d.n_fields
+        want_w = weight_out or nf == 0
+        self.sample_desc = d
+        uses_values = any(d.fields[k] == SAMPLE_VALUES for k in range(nf))
+        three = isinstance(points, (tuple, list)) and len(points) == 3
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+
+            def ok(t):
+                return isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == dev
+            if three:
+                p = list(points)
+            elif ok(points) and points.ndim == 2 and points.shape[1] == 3:
+                p = [points[:, a].contiguous() for a in range(3)]
+            else:
+                p = [None]
+            if not all(ok(t) and t.ndim == 1 and t.is_contiguous() and t.numel() == p[0].numel() for t in p):
+                raise ValueError("sample: device points must be an (M, 3) or three contiguous float64 tensors on the context's GPU")
+            m = p[0].numel()
+            if values is not None:
+                if not (ok(values) and values.is_contiguous()):
+                    raise ValueError("sample: device values must be a contiguous float64 tensor on the context's GPU")
+                if uses_values and values.numel() < nf * n:
+                    raise ValueError(f"sample: values need {nf} rows of {n}")
+            out = torch.empty((nf, m), dtype=torch.float64, device=dev)
+            w = torch.empty(m, dtype=torch.float64, device=dev) if want_w else None
+            cnt = torch.empty(2, dtype=torch.int64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
+            self._ck(self.lib.sph_sample_dev(self._h, C.byref(d), m, *(C.c_void_p(t.data_ptr()) for t in p),
+                                             None if values is None else C.c_void_p(values.data_ptr()),
+                                             C.c_void_p(out.data_ptr()) if nf else None, nf * m,
+                                             None if w is None else C.c_void_p(w.data_ptr()), C.c_void_p(cnt.data_ptr())))
+            st = self.stream()                                    # torch's later work waits for the sample
+            if st:
+                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
+            else:
+                torch.cuda.synchronize(dev)
+            cn = tuple(int(v) for v in cnt.cpu().tolist()) if counts else None
+        else:
+            if three:
+                p = [np.ascontiguousarray(t, dtype=np.float64).reshape(-1) for t in points]
+            else:
+                a = np.asarray(points, dtype=np.float64)
+                if a.ndim != 2 or a.shape[1] != 3:
+                    raise ValueError("sample: points must be an (M, 3) array or three arrays")
+                p = [np.ascontiguousarray(a[:, k]) for k in range(3)]
+            m = p[0].size
+            if p[1].size != m or p[2].size != m:
+                raise ValueError("sample: the three point arrays differ in length")
+            v = None
+            if values is not None:
+                v = np.ascontiguousarray(values, dtype=np.float64)
+                if v.ndim == 1:
+                    v = v.reshape(1, -1)
+                if v.shape[1] != n:
+                    raise ValueError(f"sample: values rows of {v.shape[1]} for {n} particles")
+                if v.shape[0] < nf:                               # row k belongs to field k: pad the rows no field reads
+                    v = np.concatenate([v, np.zeros((nf - v.shape[0], n))])
+            out = np.empty((nf, m), dtype=np.float64)
+            w = np.empty(m, dtype=np.float64) if want_w else None
+            cc = (C.c_int64 * 2)(0, 0)
+            self._ck(self.lib.sph_sample(self._h, C.byref(d), m, p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data,
+                                         None if v is None else v.ctypes.data, out.ctypes.data if nf else None, nf * m,
+                                         None if w is None else w.ctypes.data, cc))
+            cn = (int(cc[0]), int(cc[1])) if counts else None
+        if nf == 0 and not weight_out and not counts:
+            return w
+        parts = [out] + ([w] if want_w else []) + ([cn] if counts else [])
+        return parts[0] if len(parts) == 1 else tuple(parts)
 
     # ---- diagnostics ---------------------------------------------------------------------
     def stats(self) -> Stats:

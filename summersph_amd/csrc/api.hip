@@ -1280,6 +1280,20 @@ int sph_gradients_dev(sph_ctx *c, const sph_gradients_desc *d, const double *d_v
     return gradients_run(c, d, d_values, d_out, n_out, d_rho, d_counts, false, field_ready);
 }
 
+int sph_sample(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const double *px, const double *py, const double *pz,
+               const double *values, double *host_out, int64_t n_out, double *host_weight, int64_t *counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return sample_run(c, d, n_points, px, py, pz, values, host_out, n_out, host_weight, counts, true, field_ready);
+}
+
+int sph_sample_dev(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const double *d_px, const double *d_py,
+                   const double *d_pz, const double *d_values, double *d_out, int64_t n_out, double *d_weight, int64_t *d_counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return sample_run(c, d, n_points, d_px, d_py, d_pz, d_values, d_out, n_out, d_weight, d_counts, false, field_ready);
+}
+
 int sph_synchronize(sph_ctx *c) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);

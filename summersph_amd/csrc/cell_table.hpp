@@ -1,5 +1,5 @@
-// cell_table.hpp -- the hashed table over the occupied cells of a sorted particle sequence, as sph_groups and sph_gradients
-// build it (groups.hip, gradients.hip; not the step loop's hashed grid of grid.hip, which is a different table).
+// cell_table.hpp -- the hashed table over the occupied cells of a sorted particle sequence, as sph_groups, sph_gradients and
+// sph_sample build it (groups.hip, gradients.hip, sample.hip; not the step loop's hashed grid of grid.hip, which is a different table).
 //
 // A cell is the 63-bit key cx << 42 | cy << 21 | cz of its integer coordinates in a box {lo, 1 / edge}, 21 bits per axis.
 // The particles are radix-sorted by key; the table maps every occupied key to the sorted positions [start, end) of its
@@ -27,6 +27,23 @@ __device__ __forceinline__ uint64_t cell_axis(double p, double lo, double inv_e)
 __device__ __forceinline__ uint64_t cell_key(double px, double py, double pz, const double *lo, double inv_e) {
     return (cell_axis(px, lo[0], inv_e) << (2 * AXIS_BITS)) | (cell_axis(py, lo[1], inv_e) << AXIS_BITS) |
            cell_axis(pz, lo[2], inv_e);
+}
+
+// Several cell grids in one table (sample.hip: one grid per level of smoothing lengths over the same box): the key
+// level << 57 | cx << 38 | cy << 19 | cz with 6 bits of level and 19 bits per axis.  Key order is (level, cell).
+constexpr int LEVEL_AXIS_BITS = 19;
+constexpr int LEVEL_BITS = 6;
+constexpr int MAX_LEVELS = 1 << LEVEL_BITS;
+constexpr uint64_t LEVEL_AXIS_MASK = ((uint64_t)1 << LEVEL_AXIS_BITS) - 1;
+constexpr double LEVEL_AXIS_CELLS = (double)((1 << LEVEL_AXIS_BITS) - 8);     // cells per axis a level's edge is enlarged to stay under
+
+__device__ __forceinline__ uint64_t level_key(uint64_t level, uint64_t cx, uint64_t cy, uint64_t cz) {
+    return (level << (3 * LEVEL_AXIS_BITS)) | (cx << (2 * LEVEL_AXIS_BITS)) | (cy << LEVEL_AXIS_BITS) | cz;
+}
+
+// the cell of a particle inside the box along one axis, clamped to [0, cmax] (cmax < 2^19)
+__device__ __forceinline__ uint64_t level_cell_axis(double p, double lo, double inv_e, int32_t cmax) {
+    return (uint64_t)fmin(fmax(floor((p - lo) * inv_e), 0.0), (double)cmax);
 }
 
 // the entry of key, or -1 when the table does not hold it

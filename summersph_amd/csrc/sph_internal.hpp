@@ -247,7 +247,7 @@ struct sph_ctx {
     int64_t timing_seen[32] = {};    // launches of group k since timing was switched on
     sph::TimingSlot tslot[SPH_K_COUNT];
 
-    // the analysis calls (render, profile, energy, groups, gradients): private scratch, never the grid / list buffers above
+    // the analysis calls (render, profile, energy, groups, gradients, sample): private scratch, never the grid / list buffers above
     void *rnd_buf = nullptr; size_t rnd_bytes = 0;
     double *rnd_small = nullptr;     // per-block statistics, their result and the selection cursor
     double *rnd_pinned = nullptr;    // pinned read-back slots
@@ -412,5 +412,10 @@ int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_
 // form (counts[2] device memory or null); ready = sph_download_field's rule
 int gradients_run(sph_ctx *c, const sph_gradients_desc *d, const double *values, double *out, int64_t n_out, double *rho_out,
                   int64_t *counts, bool host, bool (*ready)(const sph_ctx *, int));
+// SPH interpolation at arbitrary points (sample.hip): host form (points / values / out / weight host memory, counts[2] host,
+// one synchronisation) or device form (counts[2] device memory or null); ready = sph_download_field's rule
+int sample_run(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const double *px, const double *py, const double *pz,
+               const double *values, double *out, int64_t n_out, double *weight, int64_t *counts, bool host,
+               bool (*ready)(const sph_ctx *, int));
 
 }  // namespace sph

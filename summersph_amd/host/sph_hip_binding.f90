@@ -42,6 +42,8 @@ module sph_hip_binding
   public :: sph_groups_desc, sph_groups, sph_groups_dev, SPH_GROUPS_LINK_H, SPH_GROUPS_NCOL
   ! SPH gradients (standard or matrix-corrected) of up to four fields at the owned gas
   public :: sph_gradients_desc, sph_gradients, sph_gradients_dev, SPH_GRAD_CORRECTED, SPH_GRAD_MAX_FIELDS, SPH_GRAD_VALUES
+  ! SPH interpolation at arbitrary points (density, fields or the caller's values where the caller wants them)
+  public :: sph_sample_desc, sph_sample, sph_sample_dev, SPH_SAMPLE_NORMALISE, SPH_SAMPLE_MAX_FIELDS, SPH_SAMPLE_VALUES
   public :: c_message
 
   integer(c_int), parameter :: SPH_OK = 0
@@ -137,6 +139,18 @@ module sph_hip_binding
     integer(c_int32_t) :: n_fields, flags
     integer(c_int32_t) :: reserved(2)
   end type sph_gradients_desc
+
+  ! sph_sample: strict SOURCE clip box (+-infinity: none), h (> 0: one h for all; 0: each particle's own), fields (SPH_F_*
+  ! or SPH_SAMPLE_VALUES: row k of values), n_fields 0 .. 4 (0: the weight alone), weight (SPH_RENDER_WEIGHT_MASS /
+  ! _VOLUME), flags (SPH_SAMPLE_NORMALISE), reserved (0).  out holds out(p, k) in Fortran order: (n_points, n_fields).
+  ! 88 bytes.
+  integer(c_int32_t), parameter :: SPH_SAMPLE_NORMALISE = 1, SPH_SAMPLE_MAX_FIELDS = 4, SPH_SAMPLE_VALUES = -1
+  type, bind(C) :: sph_sample_desc
+    real(c_double) :: clip_lo(3), clip_hi(3)
+    real(c_double) :: h
+    integer(c_int32_t) :: fields(SPH_SAMPLE_MAX_FIELDS)
+    integer(c_int32_t) :: n_fields, weight, flags, reserved
+  end type sph_sample_desc
 
   interface
     integer(c_int) function sph_abi_version() bind(C, name='sph_abi_version')
@@ -595,6 +609,23 @@ module sph_hip_binding
       type(c_ptr), value :: ctx, d_values, d_out, d_rho, d_counts
       type(sph_gradients_desc), intent(in) :: d
       integer(c_int64_t), value :: n_out
+    end function
+    ! ---- SPH interpolation at points: px, py, pz (n_points doubles each), values (n_fields rows of sph_count doubles,
+    !      download order, or c_null_ptr), host_out (n_fields n_points doubles or c_null_ptr with n_fields == 0), host_weight
+    !      (n_points doubles, or c_null_ptr unless n_fields == 0), counts (2 x int64: reached, non-finite; or c_null_ptr)
+    integer(c_int) function sph_sample(ctx, d, n_points, px, py, pz, values, host_out, n_out, host_weight, counts) &
+        bind(C, name='sph_sample')
+      import :: c_int, c_int64_t, c_ptr, sph_sample_desc
+      type(c_ptr), value :: ctx, px, py, pz, values, host_out, host_weight, counts
+      type(sph_sample_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_points, n_out
+    end function
+    integer(c_int) function sph_sample_dev(ctx, d, n_points, d_px, d_py, d_pz, d_values, d_out, n_out, d_weight, d_counts) &
+        bind(C, name='sph_sample_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_sample_desc
+      type(c_ptr), value :: ctx, d_px, d_py, d_pz, d_values, d_out, d_weight, d_counts
+      type(sph_sample_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_points, n_out
     end function
   end interface
 
