@@ -258,6 +258,8 @@ int accrete_and_cull(sph_ctx *c, int64_t *removed, int32_t *d_keep_out) {
     const int64_t n = c->n;
     *removed = 0;
     if (n == 0) return sinks_cull(c);
+    SPH_HIP(ensure_inv(c));
+    c->keys_early = false;
     RootBox rb;
     double size = 0.0;
     for (int a = 0; a < 3; a++) {
@@ -343,6 +345,7 @@ int accrete_and_cull(sph_ctx *c, int64_t *removed, int32_t *d_keep_out) {
     c->n_owned = n_new;
     SPH_HIP(launch_iota(c, c->orig, n_new));
     SPH_HIP(launch_iota(c, c->inv, n_new));
+    c->inv_valid = true;
     c->grid_valid = c->rho_valid = c->eos_valid = c->rates_valid = c->tree_valid = c->order_valid = false;
     c->h_refresh_ok = false;
     c->path_keys_valid = false;
@@ -468,6 +471,7 @@ int sink_creation(sph_ctx *c, int32_t *created) {
 int accrete_mark_ext(sph_ctx *c, int64_t src_off, double *d_partials) {
     if (!c->gx_src) { c->err = "sph_accrete_mark_dev: needs the all-gathered sources (sph_set_gravity_sources_dev)"; return SPH_ERR_STATE; }
     { const int st = global_keys_sorted(c); if (st != SPH_OK) return st; }
+    SPH_HIP(ensure_inv(c));
     const int64_t n = c->n, no = c->n_owned, ng = c->gx_n;
     if (src_off < 0 || src_off + no > ng) { c->err = "sph_accrete_mark_dev: owned block outside the source set"; return SPH_ERR_ARG; }
     RootBox rb;
@@ -504,6 +508,8 @@ int accrete_apply_ext(sph_ctx *c, const double *d_all, int nranks, int stride, i
     *removed = 0;
     if (!c->acc_marked) { c->err = "sph_accrete_apply_dev: call sph_accrete_mark_dev first"; return SPH_ERR_STATE; }
     c->acc_marked = false;
+    SPH_HIP(ensure_inv(c));
+    c->keys_early = false;
     const int64_t n = c->n, no = c->n_owned;
     if (c->ns > 0)
         acc_sink_update_ranks<<<dim3(1), dim3(64), 0, c->stream>>>(c->ns, d_all, nranks, stride, c->sink);
@@ -537,6 +543,7 @@ int accrete_apply_ext(sph_ctx *c, const double *d_all, int nranks, int stride, i
     c->n_owned = n_new;
     SPH_HIP(launch_iota(c, c->orig, n_new));
     SPH_HIP(launch_iota(c, c->inv, n_new));
+    c->inv_valid = true;
     SPH_HIP(hipStreamSynchronize(c->stream));
     c->grid_valid = c->rho_valid = c->eos_valid = c->rates_valid = c->tree_valid = c->order_valid = false;
     return sinks_cull(c);                              // [V]:610-613; the sinks are replicated: every rank drops the same ones

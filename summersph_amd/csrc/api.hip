@@ -364,8 +364,12 @@ int one_step_device_dt(sph_ctx *c) {
     SPH_TRY(do_forces(c));
     {   // kick + drift, one pass over the state (bitwise what sph_kick + sph_drift give)
         if (!c->rates_valid) { c->err = "sph_step: rates are stale"; return SPH_ERR_STATE; }
+        // ... and, where the next grid build is the plain one, the keys, the histogram and the box partials of that build
         Timed t(c, SPH_K_KICK);
-        SPH_HIP(launch_kick_drift(c));
+        SPH_TRY(grid_prepare_early(c));
+        const hipError_t e = c->keys_early ? launch_kick_drift_keys(c) : launch_kick_drift(c);
+        if (e != hipSuccess) c->keys_early = false;
+        SPH_HIP(e);
         c->grid_valid = false; c->rho_valid = false; c->eos_valid = false; c->order_valid = false;
     }
     SPH_TRY(do_density(c));
@@ -400,7 +404,7 @@ void field_written(sph_ctx *c, int field) {
         // so the next build waits for its own read-backs instead of trusting them
         c->ring_nl_valid = false; c->ring_bbox_valid = false;
     }
-    if (field <= SPH_F_Z) c->order_valid = false;
+    if (field <= SPH_F_Z) { c->order_valid = false; c->keys_early = false; }     // the keys of launch_kick_drift_keys too
     if (field <= SPH_F_ALPHA || field == SPH_F_RHO || field == SPH_F_H || field == SPH_F_OMEGA) c->eos_valid = false;
     c->derived_kept = false;
     c->grav_valid = false;
@@ -537,7 +541,7 @@ int sph_ctx_create(const sph_params *p, int device, sph_ctx **out) {
     c->no_stale = getenv("SPH_SYNC_EVERY_BUILD") != nullptr;
     if (hipHostMalloc(reinterpret_cast<void **>(&c->h_pinned), 640 * sizeof(double), hipHostMallocDefault) != hipSuccess) return fail(SPH_ERR_NOMEM);
     std::memset(c->h_pinned, 0, 640 * sizeof(double));
-    if ((st = ctx_alloc(c, &c->bbox_part, (size_t)1024 * 8 + 64, "bbox")) != SPH_OK) return fail(st);
+    if ((st = ctx_alloc(c, &c->bbox_part, BBOX_PART_CLASSIC + (size_t)EARLY_MAX_BLOCKS * 6, "bbox")) != SPH_OK) return fail(st);
     if ((st = ctx_alloc(c, &c->d_flags, 8, "flags")) != SPH_OK) return fail(st);
     if (hipMemset(c->d_flags, 0, 8 * sizeof(int32_t)) != hipSuccess) return fail(SPH_ERR_HIP);
     if ((st = ctx_alloc(c, &c->w_tab, (size_t)TAB_LEN(p->nq), "W table")) != SPH_OK) return fail(st);
@@ -622,6 +626,7 @@ static int upload_impl(sph_ctx *c, int64_t n, const double *const src[9], hipMem
     }
     SPH_HIP(launch_iota(c, c->orig, n));
     SPH_HIP(launch_iota(c, c->inv, n));
+    c->inv_valid = true; c->keys_early = false;
     if (c->variable) SPH_HIP(launch_fill(c, c->f[SPH_F_H], c->p.h, n));    // until sph_upload_field(SPH_F_H) sets it
     SPH_HIP(hipStreamSynchronize(c->stream));
     c->grid_valid = c->rho_valid = c->eos_valid = c->rates_valid = c->order_valid = c->tree_valid = false;
@@ -824,7 +829,7 @@ int sph_update_h(sph_ctx *c) { if (!c) return SPH_ERR_ARG; DeviceGuard g(c->devi
 int sph_set_owned(sph_ctx *c, int64_t n_owned) {
     if (!c || n_owned < 0 || n_owned > c->n) return SPH_ERR_ARG;
     c->n_owned = n_owned;
-    c->h_refresh_ok = false;
+    c->h_refresh_ok = false; c->keys_early = false;
     c->grid_valid = c->rho_valid = c->eos_valid = c->rates_valid = false;
     return SPH_OK;
 }

@@ -153,6 +153,7 @@ int domain_select_boxes_enqueue(sph_ctx *c, int nbox, const double *boxes) {
         if (ctx_alloc(c, &c->sel_ids, need, "selection ids") != SPH_OK) return SPH_ERR_NOMEM;
         c->sel_cap = need;
     }
+    SPH_HIP(ensure_inv(c));
     rocprim::counting_iterator<int64_t> first(0);
     for (int b = 0; b < nbox; b++) {
         InBox pred{c->inv, c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z],
@@ -192,6 +193,8 @@ int domain_replace_ghosts(sph_ctx *c, int64_t count, const double *d_vals) {
         c->err = "ghost capacity exceeded (sph_reserve more slots before sph_upload)";
         return SPH_ERR_NOMEM;
     }
+    SPH_HIP(ensure_inv(c));            // from the reorder's orig, before ghosts are appended to it
+    c->keys_early = false;
     if (count > 0) {
         FieldPtrs9 fp{};
         for (int f = 0; f < 9; f++) fp.p[f] = c->f[f];

@@ -213,6 +213,7 @@ int energy_sums(sph_ctx *c, int64_t src_offset, double *sums, double *phi, int64
     double *d_sums = host || !sums ? sums_buf : sums;
     double *d_phi = phi ? (host ? c->scratch : phi) : nullptr;      // host form: the download buffer (cap >= n doubles)
     SPH_TRY(analysis_pinned(c));
+    SPH_HIP(ensure_inv(c));
 
     if (self) {
         int64_t n_src = no;

@@ -12,6 +12,10 @@
 //   cell_table               -> cell_start[c] = first sorted slot with key >= c
 //   reorder                  -> gathers the 9 state arrays + ids into sorted order and writes
 //                               the 32-byte density gather record {x,y,z,m}
+// Inside sph_run / sph_step the steady state of the plain fixed-h path (dense table, counting sort, the box of the previous
+// build) folds four of these launches into their neighbours: the opening kick + drift writes keys, histogram and box partials
+// (kick_drift_keys), the box is finished by one workgroup more of cell_scatter, reorder_ranked takes the rank within the cell
+// itself; a context of one rank without ghosts leaves inv to ensure_inv.  Same keys, table, box, permutation: same bits.
 // Hashed grids (boxes too sparse for a dense table, see grid_rebuild): 64-bit keys, a radix sort over the key bits in use,
 // run heads -> scan -> the occupied cells (ukey, ustart), and a hash table over them (sph_internal.hpp HashView).
 #include <cstdlib>
@@ -24,6 +28,7 @@
 #include <utility>
 
 #include "pair_common.hpp"
+#include "integ_common.hpp"
 
 namespace sph {
 
@@ -80,9 +85,8 @@ __global__ __launch_bounds__(BB_BLOCK) void bbox_partial(const double *__restric
 // 6 waves, one per bbox component; lanes stride over the per-block partials.  host_slot (pinned host memory, mapped into the
 // device's address space) gets the box and the non-finite flag directly: a separate device-to-host copy of 52 bytes costs
 // a copy kernel of ~16 us on the stream (two of them per grid build were 3 % of the bench step)
-__global__ __launch_bounds__(384) void bbox_final(const double *__restrict__ partial, int nblocks, double *__restrict__ out,
-                                                  double *__restrict__ host_slot = nullptr, int32_t *__restrict__ flags = nullptr) {
-    const int comp = threadIdx.x >> 6, lane = threadIdx.x & 63;
+__device__ __forceinline__ void bbox_final_comp(int comp, int lane, const double *__restrict__ partial, int nblocks,
+                                                double *__restrict__ out, double *__restrict__ host_slot, int32_t *__restrict__ flags) {
     double r = comp < 3 ? INFINITY : -INFINITY;
     for (int b = lane; b < nblocks; b += 64) {
         const double v = partial[b * 6 + comp];
@@ -96,6 +100,11 @@ __global__ __launch_bounds__(384) void bbox_final(const double *__restrict__ par
             if (comp == 0) { *reinterpret_cast<int32_t *>(host_slot + 6) = flags[0]; flags[0] = 0; }     // ... and cleared for the next build
         }
     }
+}
+
+__global__ __launch_bounds__(384) void bbox_final(const double *__restrict__ partial, int nblocks, double *__restrict__ out,
+                                                  double *__restrict__ host_slot = nullptr, int32_t *__restrict__ flags = nullptr) {
+    bbox_final_comp(threadIdx.x >> 6, threadIdx.x & 63, partial, nblocks, out, host_slot, flags);
 }
 
 // count, sum and sum of squares per axis of the live particles inside box (lo, hi): partial[b*7 + ...].  For the trimmed
@@ -206,8 +215,116 @@ __global__ __launch_bounds__(256) void cell_keys_count(GridDesc g, const double 
     if (run_len > 0) atomicAdd(&count[k], run_len);
 }
 
+// The opening kick + drift of a fixed-h step (integrate.hip: kick_drift_kernel, the same expressions and bits) which goes on
+// with the new position while it is in registers: the work of cell_keys_count (key, histogram) and of bbox_partial (mode 0, no
+// replaced ghosts).  Minimum, maximum and integer counts do not depend on the order: keys, table, box and flag are those of
+// the separate launches.  Blocks stride over the particles beyond EARLY_MAX_BLOCKS * 256 of them.
+struct KickDriftArgs {
+    double *x, *y, *z, *vx, *vy, *vz, *u, *alpha;
+    const double *ax, *ay, *az, *du, *dalpha;
+};
+
+__global__ __launch_bounds__(256) void kick_drift_keys(KickDriftArgs a, GridDesc g, int64_t n, const double *__restrict__ dt_ptr,
+                                                       double *__restrict__ sink, int ns, uint32_t *__restrict__ keys,
+                                                       int32_t *__restrict__ count, double *__restrict__ partial,
+                                                       int32_t *__restrict__ flags) {
+    __shared__ double sm[6][256 / WAVE];
+    const double dt = dt_ptr[0];
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool bad = false;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < n; base += (int64_t)gridDim.x * 256) {
+        const int64_t i = base + threadIdx.x;
+        const bool valid = i < n;
+        uint32_t k = 0;
+        if (valid) {
+            const double vx = kick_half(a.vx[i], a.ax[i], dt), vy = kick_half(a.vy[i], a.ay[i], dt), vz = kick_half(a.vz[i], a.az[i], dt);
+            a.vx[i] = vx; a.vy[i] = vy; a.vz[i] = vz;
+            a.u[i] = kick_half(a.u[i], a.du[i], dt);
+            a.alpha[i] = kick_alpha(a.alpha[i], a.dalpha[i], dt);
+            const double v[3] = {drift_pos(a.x[i], vx, dt), drift_pos(a.y[i], vy, dt), drift_pos(a.z[i], vz, dt)};
+            a.x[i] = v[0]; a.y[i] = v[1]; a.z[i] = v[2];
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+                bad |= !isfinite(v[d]);
+                lo[d] = fmin(lo[d], v[d]);
+                hi[d] = fmax(hi[d], v[d]);
+            }
+            int cc[3];
+            k = cell_key(g, v[0], v[1], v[2], cc);
+            keys[i] = k;
+        }
+        int run_len, head_lane;
+        run_of_equal_keys(k, valid, run_len, head_lane);
+        if (run_len > 0) atomicAdd(&count[k], run_len);
+    }
+    if (bad) flags[0] = 1;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        const double mn = wave_min(lo[d]), mx = wave_max(hi[d]);
+        if (lane == 0) { sm[d][wv] = mn; sm[3 + d][wv] = mx; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        double r = sm[threadIdx.x][0];
+        for (int w = 1; w < 256 / WAVE; w++)
+            r = threadIdx.x < 3 ? fmin(r, sm[threadIdx.x][w]) : fmax(r, sm[threadIdx.x][w]);
+        partial[(int64_t)blockIdx.x * 6 + threadIdx.x] = r;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < ns) {
+        const int s = threadIdx.x;
+        for (int d = 0; d < 3; d++) {
+            const double v = sink[(3 + d) * MAX_SINKS + s] + 0.5 * sink[(7 + d) * MAX_SINKS + s] * dt;
+            sink[(3 + d) * MAX_SINKS + s] = v;
+            sink[d * MAX_SINKS + s] = sink[d * MAX_SINKS + s] + v * dt;
+        }
+    }
+}
+
+// the box partials of kick_drift_keys: reduced by one workgroup more of cell_scatter, a few launches later, instead of
+// by a launch of their own (no fence: the partials come from an earlier kernel of the stream)
+struct BoxFinal {
+    const double *partial;
+    int nblocks;
+    double *out, *host_slot;
+    int32_t *flags;
+};
+
+// 256 threads stride over the blocks' partials (six contiguous doubles each: three 16-byte loads in flight per trip), then
+// the waves and the workgroup; minimum and maximum do not depend on the order
+__device__ __forceinline__ void bbox_final_block(const BoxFinal &bf) {
+    __shared__ double sm[6][256 / WAVE];
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int b = threadIdx.x; b < bf.nblocks; b += 256) {
+        const double2 *q = reinterpret_cast<const double2 *>(bf.partial + (size_t)b * 6);
+        const double2 v0 = q[0], v1 = q[1], v2 = q[2];
+        lo[0] = fmin(lo[0], v0.x); lo[1] = fmin(lo[1], v0.y); lo[2] = fmin(lo[2], v1.x);
+        hi[0] = fmax(hi[0], v1.y); hi[1] = fmax(hi[1], v2.x); hi[2] = fmax(hi[2], v2.y);
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        const double mn = wave_min(lo[d]), mx = wave_max(hi[d]);
+        if (lane == 0) { sm[d][wv] = mn; sm[3 + d][wv] = mx; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        double r = sm[threadIdx.x][0];
+        for (int w = 1; w < 256 / WAVE; w++)
+            r = threadIdx.x < 3 ? fmin(r, sm[threadIdx.x][w]) : fmax(r, sm[threadIdx.x][w]);
+        bf.out[threadIdx.x] = r;
+        bf.host_slot[threadIdx.x] = r;
+        if (threadIdx.x == 0) { *reinterpret_cast<int32_t *>(bf.host_slot + 6) = bf.flags[0]; bf.flags[0] = 0; }     // as bbox_final
+    }
+}
+
+template <bool BOX>
 __global__ __launch_bounds__(256) void cell_scatter(const uint32_t *__restrict__ keys, int64_t n, const int32_t *__restrict__ cell_start,
-                                                    int32_t *__restrict__ fill, uint32_t *__restrict__ slots) {
+                                                    int32_t *__restrict__ fill, uint32_t *__restrict__ slots, BoxFinal bf) {
+    if (BOX && blockIdx.x == gridDim.x - 1) {
+        bbox_final_block(bf);
+        return;
+    }
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool valid = i < n;
     const uint32_t k = valid ? keys[i] : 0u;
@@ -320,9 +437,40 @@ __global__ __launch_bounds__(256) void reorder(ReorderArgs a, const uint32_t *__
     if (a.prec) reinterpret_cast<double4 *>(a.prec)[i] = make_double4(v[SPH_F_X], v[SPH_F_Y], v[SPH_F_Z], v[9]);
     const int32_t id = orig_in[s];
     orig_out[i] = id;
-    inv[id] = (int32_t)i;                 // original id -> sorted slot
+    if (inv) inv[id] = (int32_t)i;        // original id -> sorted slot (nullptr: rebuilt from orig when somebody asks, ensure_inv)
     double4 r = make_double4(v[SPH_F_X], v[SPH_F_Y], v[SPH_F_Z], v[SPH_F_M]);
     reinterpret_cast<double4 *>(drec)[i] = r;
+}
+
+// cell_rank and reorder in one pass for the fixed-h state (nine fields): entry slots[p] of cell k moves straight to
+// cell_start[k] + its rank among the cell's entries -- the permutation cell_rank writes for reorder to read back, so the same
+// bits; the stores of a wave scatter within its few cells, i.e. within the lines the wave fills anyway
+__global__ __launch_bounds__(256) void reorder_ranked(ReorderArgs a, const uint32_t *__restrict__ keys, const int32_t *__restrict__ cell_start,
+                                                      const uint32_t *__restrict__ slots, const int32_t *__restrict__ orig_in,
+                                                      int32_t *__restrict__ orig_out, int32_t *__restrict__ inv,
+                                                      double *__restrict__ drec, int64_t n) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t s = slots[p];
+    const uint32_t k = keys[s];
+    const int cs = cell_start[k], ce = cell_start[k + 1];
+    double v[9];
+#pragma unroll
+    for (int f = 0; f < 9; f++) v[f] = a.src[f][s];
+    const int32_t id = orig_in[s];
+    int rank = 0;
+    for (int q = cs; q < ce; q++) rank += slots[q] < s ? 1 : 0;
+    const int64_t i = cs + rank;
+#pragma unroll
+    for (int f = 0; f < 9; f++) a.dst[f][i] = v[f];
+    orig_out[i] = id;
+    if (inv) inv[id] = (int32_t)i;
+    reinterpret_cast<double4 *>(drec)[i] = make_double4(v[SPH_F_X], v[SPH_F_Y], v[SPH_F_Z], v[SPH_F_M]);
+}
+
+__global__ __launch_bounds__(256) void inv_from_orig(const int32_t *__restrict__ orig, int32_t *__restrict__ inv, int64_t n) {
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) inv[orig[i]] = (int32_t)i;
 }
 
 __global__ __launch_bounds__(256) void iota_kernel(int32_t *p, int64_t n) {
@@ -393,6 +541,7 @@ hipError_t launch_gather_fields(sph_ctx *c, int nf, const int *fields, const int
     FieldPtrs fp{};
     fp.nf = nf;
     for (int f = 0; f < nf; f++) fp.p[f] = c->f[fields[f]];
+    if (hipError_t e = ensure_inv(c); e != hipSuccess) return e;
     gather_by_id<<<dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream>>>(fp, c->inv, ids, count, out);
     return hipGetLastError();
 }
@@ -402,6 +551,7 @@ hipError_t launch_gather_selected(sph_ctx *c, int nf, const int *fields, int box
     fp.nf = nf;
     for (int f = 0; f < nf; f++) fp.p[f] = c->f[fields[f]];
     const int64_t threads = std::max<int64_t>(capacity, 1);
+    if (hipError_t e = ensure_inv(c); e != hipSuccess) return e;
     gather_selected<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, c->stream>>>(fp, c->inv, c->sel_ids + (size_t)box * c->sel_stride,
                                                                                         c->sel_count + box, capacity, out);
     return hipGetLastError();
@@ -412,7 +562,27 @@ hipError_t launch_scatter_fields(sph_ctx *c, int nf, const int *fields, int64_t 
     FieldPtrs fp{};
     fp.nf = nf;
     for (int f = 0; f < nf; f++) fp.p[f] = c->f[fields[f]];
+    if (hipError_t e = ensure_inv(c); e != hipSuccess) return e;
     scatter_many_by_id<<<dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream>>>(fp, c->inv, first, count, vals);
+    return hipGetLastError();
+}
+
+// A context of one rank without ghosts does not gather by id every step: its reorder leaves inv alone (a scattered 4-byte
+// store per particle) and whoever needs inv asks here first.  orig[0, n) is the reorder's own output as long as no ghost
+// swap is pending; domain_replace_ghosts asks before it appends.  SPH_NO_LAZY_INV: A/B switch, every reorder stores inv.
+hipError_t ensure_inv(sph_ctx *c) {
+    if (c->inv_valid) return hipSuccess;
+    if (c->n > 0) inv_from_orig<<<dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, c->stream>>>(c->orig, c->inv, c->n);
+    c->inv_valid = true;
+    return hipGetLastError();
+}
+
+hipError_t launch_kick_drift_keys(sph_ctx *c) {
+    KickDriftArgs a{c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], c->f[SPH_F_VX], c->f[SPH_F_VY], c->f[SPH_F_VZ], c->f[SPH_F_U], c->f[SPH_F_ALPHA],
+                    c->f[SPH_F_AX], c->f[SPH_F_AY], c->f[SPH_F_AZ], c->f[SPH_F_DU], c->f[SPH_F_DALPHA]};
+    c->early_blocks = (int)std::min<int64_t>((c->n + 255) / 256, EARLY_MAX_BLOCKS);
+    kick_drift_keys<<<dim3(c->early_blocks), dim3(256), 0, c->stream>>>(a, c->grid_early, c->n, c->d_dt, c->sink, c->ns, c->keys, c->cell_start,
+                                                                        c->bbox_part + BBOX_PART_CLASSIC, c->d_flags);
     return hipGetLastError();
 }
 
@@ -471,7 +641,7 @@ int owned_bbox(sph_ctx *c, double *d_out6, double *h_out6) {
 }
 
 // the state into the order of c->vals_alt (the sorted slots of the build); n = c->n live entries
-static int reorder_sorted(sph_ctx *c) {
+static int reorder_sorted(sph_ctx *c, bool ranked = false) {
     const int64_t n = c->n;
     const unsigned gb = (unsigned)((std::max<int64_t>(n, 1) + 255) / 256);
     hipStream_t st = c->stream;
@@ -480,7 +650,11 @@ static int reorder_sorted(sph_ctx *c) {
     for (int k = 0; k < 9; k++) { ra.src[k] = c->f[k]; ra.dst[k] = c->f_alt[k]; }
     ra.nf = 9; ra.prec = nullptr;
     if (c->variable) { ra.src[9] = c->f[SPH_F_H]; ra.dst[9] = c->f_alt[9]; ra.nf = 10; ra.prec = c->prec; }
-    reorder<<<dim3(gb), dim3(256), 0, st>>>(ra, c->vals_alt, c->orig, c->orig_alt, c->inv, c->drec, n);
+    static const bool store_inv = getenv("SPH_NO_LAZY_INV") != nullptr;                 // A/B switch
+    c->inv_valid = store_inv || c->nranks > 1 || c->n_owned != n;
+    // ranked: c->vals holds the cells' entries in arrival order (cell_scatter); the rank is taken on the way
+    if (ranked) reorder_ranked<<<dim3(gb), dim3(256), 0, st>>>(ra, c->keys, c->cell_start, c->vals, c->orig, c->orig_alt, c->inv_valid ? c->inv : nullptr, c->drec, n);
+    else reorder<<<dim3(gb), dim3(256), 0, st>>>(ra, c->vals_alt, c->orig, c->orig_alt, c->inv_valid ? c->inv : nullptr, c->drec, n);
     SPH_HIP(hipGetLastError());
     for (int k = 0; k < 9; k++) std::swap(c->f[k], c->f_alt[k]);
     if (c->variable) std::swap(c->f[SPH_F_H], c->f_alt[9]);
@@ -571,28 +745,98 @@ static int hash_build(sph_ctx *c, bool swap) {
     return SPH_OK;
 }
 
+static bool sort_radix_forced() {
+    static const bool force_radix = getenv("SPH_SORT_RADIX") != nullptr;             // A/B switch
+    return force_radix;
+}
+
+static bool same_grid(const GridDesc &a, const GridDesc &b) {
+    bool same = a.inv_edge == b.inv_edge && a.ncells == b.ncells;
+    for (int k = 0; k < 3; k++) same = same && a.org[k] == b.org[k] && a.dim[k] == b.dim[k] && a.s[k] == b.s[k];
+    return same;
+}
+
+// What grid_rebuild will decide on the host, taken before the opening kick + drift of a step so that this pass can leave the
+// keys, the histogram and the box partials behind (launch_kick_drift_keys): the steady state of the plain fixed-h path, where
+// the grid comes from the box of the previous build (read-back slot 1 - ring_bbox, which arrived a step ago: the wait below
+// is the one grid_rebuild does a few launches later).  Only the build that needs nothing else is taken early -- dense table
+// within the capacity in place, no trim, counting sort, no ghosts pending -- and grid_rebuild checks that its own grid is this
+// one before it believes the keys.  Zeroes the table and the cursors on the stream; sets c->keys_early.  SPH_NO_DRIFT_KEYS: A/B.
+int grid_prepare_early(sph_ctx *c) {
+    static const bool off = getenv("SPH_NO_DRIFT_KEYS") != nullptr;
+    c->keys_early = false;
+    const int64_t n = c->n;
+    if (off || n <= 0 || c->n_slots != n || c->dead_below != 0 || c->variable || c->gravity ||
+        (c->p.flags & (SPH_FLAG_ACCRETE_CULL | SPH_FLAG_HASHED_GRID)) || !c->ring_bbox_valid || c->no_stale || c->hash_sticky ||
+        sort_radix_forced())
+        return SPH_OK;
+    const int q = 1 - c->ring_bbox;
+    SPH_HIP(hipEventSynchronize(c->ev_bbox[q]));
+    const double *bb = c->h_pinned + 200 + 16 * q;
+    if (*reinterpret_cast<const int32_t *>(bb + 6) != 0) return SPH_OK;         // grid_rebuild reports it
+    const double guard = 2.0 * c->p.h * (1.0 + 1e-6);
+    double box[6];
+    for (int a = 0; a < 3; a++) { box[a] = bb[a] - guard; box[3 + a] = bb[3 + a] + guard; }
+    GridDesc g{};
+    g.inv_edge = 1.0 / (2.0 * c->p.h * (1.0 + 1e-6));
+    double ncell_d = 1.0;
+    for (int a = 0; a < 3; a++) {
+        g.org[a] = box[a];
+        const double d = std::floor((box[3 + a] - box[a]) * g.inv_edge) + 1.0;
+        if (!(d >= 1.0) || d > 2.0e9) return SPH_OK;
+        g.dim[a] = (int32_t)d;
+        ncell_d *= d;
+    }
+    if (ncell_d > 64.0 * (double)n + 4.0e6 || ncell_d >= 2147483647.0) return SPH_OK;       // the trimmed or hashed build
+    g.ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
+    int s[3] = {0, 1, 2};
+    for (int i = 0; i < 3; i++)
+        for (int j = i + 1; j < 3; j++)
+            if (g.dim[s[j]] < g.dim[s[i]]) std::swap(s[i], s[j]);
+    std::swap(s[1], s[2]);
+    g.s[0] = s[0]; g.s[1] = s[1]; g.s[2] = s[2];
+    if (g.ncells + 2 > c->cell_cap || g.ncells > 4 * n + 1000000) return SPH_OK;              // table regrown / radix sort
+    size_t scan_tmp = 0;
+    SPH_HIP(rocprim::exclusive_scan(nullptr, scan_tmp, c->cell_start, c->cell_start, 0, (size_t)(g.ncells + 2), rocprim::plus<int32_t>(), c->stream));
+    if (scan_tmp > c->sort_tmp_bytes) return SPH_OK;
+    const size_t table = ((size_t)(g.ncells + 2) + 3) & ~(size_t)3, cursors = ((size_t)(g.ncells + 1) + 3) & ~(size_t)3;
+    SPH_HIP(hipMemsetAsync(c->cell_start, 0, sizeof(int32_t) * (table + cursors), c->stream));
+    c->grid_early = g;
+    c->keys_early = true;
+    return SPH_OK;
+}
+
 int grid_rebuild(sph_ctx *c) {
     const int64_t n = c->n;                 // live particles after the build
     const int64_t ns = c->n_slots;          // occupied slots before it (> n while a ghost swap is pending)
     const bool swap = c->dead_below > 0;
     hipStream_t st = c->stream;
+    // keys, histogram and box partials of the current positions are there already (launch_kick_drift_keys)
+    bool early = c->keys_early;
+    c->keys_early = false;
     if (ns == 0) { c->grid_valid = true; return SPH_OK; }
 
     // ---- bounding box ---------------------------------------------------------------
     int nb = (int)std::min<int64_t>((ns + BB_BLOCK - 1) / BB_BLOCK, BB_MAX_BLOCKS);
-    // d_flags[0] (non-finite position seen) is zero here: cleared at creation and by every bbox_final
-    bbox_partial<<<dim3(nb), dim3(BB_BLOCK), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], ns, c->bbox_part, c->d_flags,
-                                                      c->orig, (int32_t)c->n_owned, c->dead_below, 0);
     const int p = c->ring_bbox;
     double *slot = c->h_pinned + 200 + 16 * p;
-    bbox_final<<<dim3(1), dim3(384), 0, st>>>(c->bbox_part, nb, c->bbox_part + (size_t)BB_MAX_BLOCKS * 6, slot, c->d_flags);
-    SPH_HIP(hipGetLastError());
+    const bool stale = c->ring_bbox_valid && !c->no_stale && !c->variable && !c->gravity && !(c->p.flags & SPH_FLAG_ACCRETE_CULL);
+    early = early && stale && !swap && ns == n;
+    auto box_launches = [&]() -> int {
+        // d_flags[0] (non-finite position seen) is zero here: cleared at creation and by every bbox_final
+        bbox_partial<<<dim3(nb), dim3(BB_BLOCK), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], ns, c->bbox_part, c->d_flags,
+                                                          c->orig, (int32_t)c->n_owned, c->dead_below, 0);
+        bbox_final<<<dim3(1), dim3(384), 0, st>>>(c->bbox_part, nb, c->bbox_part + (size_t)BB_MAX_BLOCKS * 6, slot, c->d_flags);
+        SPH_HIP(hipGetLastError());
+        SPH_HIP(hipEventRecord(c->ev_bbox[p], st));        // bbox_final wrote the slot itself (pinned memory)
+        return SPH_OK;
+    };
     // the exact box of the current positions -> read-back slot p.  Who needs it NOW (octree root boxes: variable h,
     // self-gravity, accretion; the first build of a particle set) waits for it; the plain fixed-h path takes the box of the
     // previous build, which arrived long ago, widened by one cell: particles outside the grid's box are clamped into its
     // boundary cells and still meet all their neighbours there, so the box only has to be roughly right.
-    SPH_HIP(hipEventRecord(c->ev_bbox[p], st));        // bbox_final wrote the slot itself (pinned memory)
-    const bool stale = c->ring_bbox_valid && !c->no_stale && !c->variable && !c->gravity && !(c->p.flags & SPH_FLAG_ACCRETE_CULL);
+    // With the partials of launch_kick_drift_keys in place the box is finished further down, on cell_scatter.
+    if (!early) SPH_TRY(box_launches());
     const double *bb = slot;
     if (stale) {
         SPH_HIP(hipEventSynchronize(c->ev_bbox[1 - p]));
@@ -712,6 +956,8 @@ int grid_rebuild(sph_ctx *c) {
     g.s[0] = s[0]; g.s[1] = s[1]; g.s[2] = s[2];
     c->grid = g;
     c->hashed = hashed;
+    // the early keys hold for the early grid only; any other decision below (hashed, table regrown, radix sort) drops them too
+    if (early && (hashed || !same_grid(g, c->grid_early) || g.ncells + 2 > c->cell_cap)) { early = false; SPH_TRY(box_launches()); }
     if (hashed) {
         const int st2 = hash_build(c, swap);
         if (st2 != SPH_OK) return st2;
@@ -733,24 +979,44 @@ int grid_rebuild(sph_ctx *c) {
     // ---- keys, sort, cell table ---------------------------------------------------------
     const unsigned gb = (unsigned)((std::max<int64_t>(n, 1) + 255) / 256);
     const unsigned gbs = (unsigned)((ns + 255) / 256);
-    static const bool force_radix = getenv("SPH_SORT_RADIX") != nullptr;             // A/B switch
     size_t scan_tmp = 0;
-    bool counting = !force_radix && g.ncells <= 4 * ns + 1000000;
+    bool ranked = false;
+    bool counting = !sort_radix_forced() && g.ncells <= 4 * ns + 1000000;
     if (counting) {
         SPH_HIP(rocprim::exclusive_scan(nullptr, scan_tmp, c->cell_start, c->cell_start, 0, (size_t)(g.ncells + 2), rocprim::plus<int32_t>(), st));
         counting = scan_tmp <= c->sort_tmp_bytes;
     }
+    if (early && !counting) { early = false; SPH_TRY(box_launches()); }
     if (counting) {
         const size_t table = ((size_t)(g.ncells + 2) + 3) & ~(size_t)3, cursors = ((size_t)(g.ncells + 1) + 3) & ~(size_t)3;
         c->cell_fill = c->cell_start + table;
-        SPH_HIP(hipMemsetAsync(c->cell_start, 0, sizeof(int32_t) * (table + cursors), st));        // multiples of 16 bytes: one fill kernel
-        cell_keys_count<<<dim3(gbs), dim3(256), 0, st>>>(g, c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], ns, c->keys, c->cell_start,
-                                                        c->orig, (int32_t)c->n_owned, c->dead_below);
-        SPH_HIP(hipGetLastError());
+        if (!early) {
+            SPH_HIP(hipMemsetAsync(c->cell_start, 0, sizeof(int32_t) * (table + cursors), st));        // multiples of 16 bytes: one fill kernel
+            cell_keys_count<<<dim3(gbs), dim3(256), 0, st>>>(g, c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], ns, c->keys, c->cell_start,
+                                                            c->orig, (int32_t)c->n_owned, c->dead_below);
+            SPH_HIP(hipGetLastError());
+        }
         // in place: cell_start[c] = first sorted slot of cell c; [ncells] = live particles; the replaced ghosts sort behind them
         SPH_HIP(rocprim::exclusive_scan(c->sort_tmp, scan_tmp, c->cell_start, c->cell_start, 0, (size_t)(g.ncells + 2), rocprim::plus<int32_t>(), st));
-        cell_scatter<<<dim3(gbs), dim3(256), 0, st>>>(c->keys, ns, c->cell_start, c->cell_fill, c->vals);
-        cell_rank<<<dim3(gb), dim3(256), 0, st>>>(c->keys, n, c->cell_start, c->vals, c->vals_alt);
+        if (early) {
+            // SPH_NO_BOX_RIDE (A/B switch): the box of the early partials by a launch of its own
+            static const bool no_ride = getenv("SPH_NO_BOX_RIDE") != nullptr;
+            const BoxFinal bf{c->bbox_part + BBOX_PART_CLASSIC, c->early_blocks, c->bbox_part + (size_t)BB_MAX_BLOCKS * 6, slot, c->d_flags};
+            if (no_ride) {
+                bbox_final<<<dim3(1), dim3(384), 0, st>>>(bf.partial, bf.nblocks, bf.out, bf.host_slot, bf.flags);
+                cell_scatter<false><<<dim3(gbs), dim3(256), 0, st>>>(c->keys, ns, c->cell_start, c->cell_fill, c->vals, BoxFinal{});
+            } else {
+                cell_scatter<true><<<dim3(gbs + 1), dim3(256), 0, st>>>(c->keys, ns, c->cell_start, c->cell_fill, c->vals, bf);
+            }
+            SPH_HIP(hipGetLastError());
+            SPH_HIP(hipEventRecord(c->ev_bbox[p], st));
+        } else {
+            cell_scatter<false><<<dim3(gbs), dim3(256), 0, st>>>(c->keys, ns, c->cell_start, c->cell_fill, c->vals, BoxFinal{});
+        }
+        // SPH_NO_RANK_REORDER (A/B switch): the rank by a launch of its own, as every other configuration has it
+        static const bool no_ranked = getenv("SPH_NO_RANK_REORDER") != nullptr;
+        ranked = early && !no_ranked;
+        if (!ranked) cell_rank<<<dim3(gb), dim3(256), 0, st>>>(c->keys, n, c->cell_start, c->vals, c->vals_alt);
         SPH_HIP(hipGetLastError());
         c->n_slots = n; c->dead_below = 0;
     } else {
@@ -766,7 +1032,7 @@ int grid_rebuild(sph_ctx *c) {
         SPH_HIP(hipGetLastError());
     }
 
-    return reorder_sorted(c);
+    return reorder_sorted(c, ranked);
 }
 
 }  // namespace sph

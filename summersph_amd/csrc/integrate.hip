@@ -61,6 +61,8 @@ __global__ __launch_bounds__(EW_BLOCK) void drift_kernel(double *__restrict__ x,
 
 // kick immediately followed by drift (first half of a step, [F]:899-900): one pass instead of two; same expressions,
 // same results as kick_kernel + drift_kernel
+// (sph_run / sph_step on the plain fixed-h path launch grid.hip's kick_drift_keys instead: this pass + the cell keys, the
+// histogram and the box partials of the grid build that follows)
 __global__ __launch_bounds__(EW_BLOCK) void kick_drift_kernel(KickArgs a, double *__restrict__ x, double *__restrict__ y,
                                                               double *__restrict__ z, int64_t n, const double *__restrict__ dt_ptr,
                                                               double *__restrict__ sink, int ns) {

@@ -115,6 +115,7 @@ struct sph_ctx {
     double *f_alt[10] = {};          // ping-pong targets for the state fields on reorder (9, +h when variable)
     int32_t *orig = nullptr, *orig_alt = nullptr;   // sorted slot -> original index
     int32_t *inv = nullptr;                         // original index -> sorted slot
+    bool inv_valid = true;           // false: the last reorder left inv alone (one rank, no ghosts); ensure_inv rebuilds it from orig
     double *scratch = nullptr;       // n doubles (un-permute on download)
 
     // gather records (array-of-structs: one particle = one or few cache lines)
@@ -176,6 +177,11 @@ struct sph_ctx {
     int32_t *cell_start = nullptr; int64_t cell_cap = 0;
     int32_t *cell_fill = nullptr;    // counting sort of the grid build: per-cell cursor (inside the cell_start allocation, behind the table)
     double *bbox_part = nullptr;     // per-block partial min/max
+    // fixed-h steps (sph_run / sph_step): the opening kick + drift also wrote the cell keys, the histogram and the box
+    // partials of the new positions for the grid grid_early (grid.hip: grid_prepare_early); the next grid build takes them
+    bool keys_early = false;
+    sph::GridDesc grid_early{};
+    int early_blocks = 0;            // ... and the number of box partials it left behind the classic ones in bbox_part
     double *h_pinned = nullptr;      // pinned host scratch (bbox[6], flags, dt, ...)
     int32_t *d_flags = nullptr;      // [0] nonfinite, [1] nlist max count
     // Read-backs one build stale (no host wait on the step that is being enqueued): the fixed-h path sizes its grid from
@@ -338,6 +344,13 @@ hipError_t launch_gather_selected(sph_ctx *c, int nf, const int *fields, int box
 hipError_t launch_scatter_fields(sph_ctx *c, int nf, const int *fields, int64_t first, int64_t count, const double *vals);
 hipError_t launch_dt_partial_only(sph_ctx *c);
 hipError_t launch_kick_drift(sph_ctx *c);
+// the same pass + cell keys, histogram and box partials of the new positions (grid.hip); needs grid_prepare_early, which
+// sets c->keys_early where the next build is the plain dense counting-sort build over the previous build's box
+int grid_prepare_early(sph_ctx *c);
+hipError_t launch_kick_drift_keys(sph_ctx *c);
+hipError_t ensure_inv(sph_ctx *c);               // inv of the current sorted order (a kernel only if the last reorder skipped it)
+constexpr int EARLY_MAX_BLOCKS = 4096;           // box partials of launch_kick_drift_keys
+constexpr size_t BBOX_PART_CLASSIC = (size_t)1024 * 8 + 64;      // doubles of bbox_part the classic build and owned_bbox use
 hipError_t launch_kick_next_dt(sph_ctx *c, bool advance_t);   // closing kick + get_next_timestep in one pass      // kick + drift with the device dt in one pass (sph_step / sph_run)
 hipError_t launch_kick_dt_candidate(sph_ctx *c, bool with_sinks = true);
 hipError_t launch_kick_sinks(sph_ctx *c);

@@ -634,8 +634,21 @@ __global__ __launch_bounds__(1024) void plan_reduce_kernel(int64_t ngroups_d, in
     int misfit_h = 0, misfit_hb = 0;                                                              // half groups (128 targets) of forces_q
     for (int64_t gd = threadIdx.x; gd < ngroups_d; gd += 1024) {
         int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {0, 0, 0};
-        for (int64_t gf = 4 * gd; gf < std::min<int64_t>(4 * gd + 4, ngroups_f); gf++) {
-            const int4 a = *reinterpret_cast<const int4 *>(plan_f + 8 * gf), b = *reinterpret_cast<const int4 *>(plan_f + 8 * gf + 4);
+        // the records of the (up to) four groups are loaded before any is looked at: one memory latency, not four in a row
+        const int cnt = (int)std::min<int64_t>(4, ngroups_f - 4 * gd);
+        int4 ra[4], rb[4];
+        int rh[8];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (j >= cnt) continue;
+            const int64_t gf = 4 * gd + j;
+            ra[j] = *reinterpret_cast<const int4 *>(plan_f + 8 * gf); rb[j] = *reinterpret_cast<const int4 *>(plan_f + 8 * gf + 4);
+            if (plan_h) { rh[2 * j] = plan_h[8 * (2 * gf) + 6]; rh[2 * j + 1] = plan_h[8 * (2 * gf + 1) + 6]; }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (j >= cnt) continue;
+            const int4 a = ra[j], b = rb[j];
             const int l[3] = {a.x, a.y, a.z}, len[3] = {a.w, b.x, b.y};
             for (int q = 0; q < 3; q++)
                 if (len[q] > 0) { lo[q] = min(lo[q], l[q]); hi[q] = max(hi[q], l[q] + len[q]); }
@@ -644,7 +657,7 @@ __global__ __launch_bounds__(1024) void plan_reduce_kernel(int64_t ngroups_d, in
             misfit_fb += b.z > tcap_f_big ? 1 : 0;
             if (plan_h) {
                 for (int hf = 0; hf < 2; hf++) {
-                    const int nh = plan_h[8 * (2 * gf + hf) + 6];
+                    const int nh = rh[2 * j + hf];
                     misfit_h += nh > tcap_f ? 1 : 0; misfit_hb += nh > tcap_f_big ? 1 : 0;
                 }
             }
