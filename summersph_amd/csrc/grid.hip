@@ -876,7 +876,9 @@ int grid_rebuild(sph_ctx *c) {
     // Very sparse domains (a particle that escaped to 1e5 AU, a diffuse halo): the cell table must not grow with the
     // VOLUME of the bounding box.  The grid's box need not hold every particle -- a particle outside it is clamped into
     // a boundary cell, where it still meets all its neighbours (cells are >= 2h wide, so everything within 2h of an
-    // outside particle is clamped to the same layer or sits in the last one) -- so when the exact box would need more
+    // outside particle is clamped to the same layer or sits in the last one: enough for the fixed-h builds, which scan +-1
+    // cell without a distance test; the variable-h build prunes cells by their distance from the particle and therefore
+    // treats the boundary cells as open-ended, varh.hip axis_gap2) -- so when the exact box would need more
     // than ~64 cells per particle the grid covers the bulk only: mean +- 6 sigma of the particles inside the current box,
     // trimmed repeatedly (a far outlier inflates sigma, the next round no longer sees it).  Results do not depend on the
     // box beyond summation order; only the boundary cells get crowded if MANY particles lie outside.  A hashed grid trims

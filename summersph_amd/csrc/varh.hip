@@ -238,9 +238,14 @@ __device__ __forceinline__ bool reaches(const double4 &leaf, double x, double y,
     return ((int)(fabs(x - leaf.x) < leaf.w) & (int)(fabs(y - leaf.y) < leaf.w) & (int)(fabs(z - leaf.z) < leaf.w)) != 0;     // no short circuit: no branches
 }
 
-// distance^2 from coordinate p to the cell interval [lo, lo+e] along one axis
-__device__ __forceinline__ double axis_gap2(double p, double lo, double e) {
-    const double d = fmax(fmax(lo - p, p - (lo + e)), 0.0);
+// distance^2 along one axis from coordinate p to what cell c of `dim` (lower face lo, edge e) holds.  The two boundary cells are
+// open-ended: a particle outside the grid's box (trimmed to the bulk of a sparse domain, grid.hip) is clamped into them
+// (cell_coords), so cell 0 holds everything below its upper face and cell dim - 1 everything above its lower face -- measured
+// against the nominal interval, a clamped particle would be as far from its own cell as it lies outside the box and would
+// prune the cells its clamped neighbours sit in.  For a particle inside the box the value is the nominal interval's (never larger).
+__device__ __forceinline__ double axis_gap2(double p, double lo, double e, int c, int dim) {
+    const double below = c > 0 ? lo - p : 0.0, above = c < dim - 1 ? p - (lo + e) : 0.0;
+    const double d = fmax(fmax(below, above), 0.0);
     return d * d;
 }
 
@@ -323,7 +328,7 @@ __global__ __launch_bounds__(VBLOCK) void nlist_v_tiled(GridDesc g, int R, doubl
     for (int o2 = -R; o2 <= R; o2++) {
         const int c2 = cc[2] + o2;
         const bool in2 = live && c2 >= 0 && c2 < d2;
-        const double g2 = in2 ? axis_gap2(p[s2], g.org[s2] + c2 * e, e) : 0.0;
+        const double g2 = in2 ? axis_gap2(p[s2], g.org[s2] + c2 * e, e, c2, d2) : 0.0;
         const bool use2 = in2 && g2 <= rg2;
         // the workgroup's interval for this offset
         int mn = 0x7fffffff, mx = 0;
@@ -348,7 +353,7 @@ __global__ __launch_bounds__(VBLOCK) void nlist_v_tiled(GridDesc g, int R, doubl
             // parallel; a wave-uniform walk with scalar table loads was measured 2x slower because waves that
             // straddle two columns then serialise)
             for (int c1 = c1lo; c1 <= c1hi; c1++) {
-                const double g21 = g2 + axis_gap2(p[s1], g.org[s1] + c1 * e, e);
+                const double g21 = g2 + axis_gap2(p[s1], g.org[s1] + c1 * e, e, c1, d1);
                 if (g21 > rg2) continue;
                 const auto row = tab.row(c2, c1);
                 int js, ci = 0;                                          // hashed: ci = index of cell c0 among the occupied ones
@@ -362,7 +367,7 @@ __global__ __launch_bounds__(VBLOCK) void nlist_v_tiled(GridDesc g, int R, doubl
                     const int cc0 = ci;
                     ci = cn;
                     if (jb >= je) continue;
-                    const double gap = g21 + axis_gap2(p[s0], g.org[s0] + c0 * e, e);
+                    const double gap = g21 + axis_gap2(p[s0], g.org[s0] + c0 * e, e, c0, d0);
                     double hm;
                     if constexpr (HASHED) hm = cell_hmax[cc0]; else hm = cell_hmax[row + c0];
                     if (gap > fmax(rim2, grow2 * hm)) continue;     // (2 max(1.1 h_i, grow hmax_C))^2 (1 + 1e-12)
