@@ -734,6 +734,69 @@ int sph_sample(sph_ctx *ctx, const sph_sample_desc *d, int64_t n_points, const d
 int sph_sample_dev(sph_ctx *ctx, const sph_sample_desc *d, int64_t n_points, const double *d_px, const double *d_py,
                    const double *d_pz, const double *d_values, double *d_out, int64_t n_out, double *d_weight, int64_t *d_counts);
 
+/* ---- gravitational potential and acceleration at arbitrary points: the Barnes-Hut field of the gas and the field of the
+ *      sinks where no particle is (a rotation curve, a potential map, torque maps, the tidal field at a candidate sink
+ *      position, tracers) ------------------------------------------------------------------------------------------------
+ * Sources  sph_energy's rule.  Without sph_set_gravity_sources_dev: the owned gas records {x, y, z, m} in the caller's order
+ *          and their exact bounding box, in every state of the context (after an upload, a drift, a cull); ghosts never.
+ *          With external sources: those records and box, the tree sph_forces builds.  The gas part is computed whether or
+ *          not SPH_FLAG_SELF_GRAVITY is set.  theta = params.theta, G = params.G.  The fields of contexts with disjoint
+ *          source sets add (up to the Barnes-Hut approximation); with external sources every rank holds the whole field.
+ * Points   three arrays of n_points doubles, and optionally ph, n_points softening lengths -- host memory for
+ *          sph_gravity_at, device memory for _dev.  h_p = ph[p], else desc.h when desc.h > 0, else params.h (fixed-h
+ *          contexts only).  A point may lie anywhere, far outside the source box included.  Points are not sources: nothing
+ *          is excluded, and a point placed on particle i sees particle i.
+ * Gas      (SPH_GRAVAT_GAS) the walk of the force over the tree of the sources.  For an accepted node or leaf of mass m at c,
+ *          with d = p - c: d2 = fma(dz, dz, fma(dy, dy, fma(dx, dx, soft2))), the force walk's softened squared distance
+ *          and its acceptance test on it; s = sqrt(d2), q = s / h_p;
+ *            q < 2:   Phi += (G m / h_p) phi(q),   a -= ((G m / h_p^3) gamma(q)) d
+ *            q >= 2:  Phi -= (G m) (1 / s),        a -= ((G m) (1 / s)^3) d
+ *          phi is sph_energy's softening potential and gamma(q) = M(q) / q^3 the force's mass-fraction polynomial
+ *          ([F]:81-101) divided by q^3 analytically (q phi'(q) = gamma(q) q^2):
+ *            q < 1:      gamma = 4/3 - (6/5) q^2 + (1/2) q^3
+ *            1 <= q < 2: gamma = 8/3 - 3 q + (6/5) q^2 - (1/6) q^3 - 1 / (15 q^3)
+ *          Both are finite at s = 0: a point exactly on a source with soft2 = 0 gets -1.4 G m / h_p and no pull from it.
+ *          The force interpolates its table of M(q) linearly; this call is analytic (they differ by O(dq^2) inside 2 h).
+ * Sinks    (SPH_GRAVAT_SINKS) in sink order, unsoftened as sink_gravforces ([F]:559-591), without fused multiply-adds:
+ *          d = p - R_s, |d| = sqrt((dx dx + dy dy) + dz dz), Phi -= (G M_s) / |d|, a -= ((G M_s) / ((|d| |d|) |d|)) d.  A
+ *          massless sink adds 0.  A point on a massive sink gets Phi = -INFINITY and a = NaN; that is not an error.
+ * Output   out[c * n_points + p], c = 0 Phi, 1..3 a, of the sum of the selected parts (gas + sinks, in that order, as
+ *          sph_energy's phi); n_out == 4 n_points.  With SPH_GRAVAT_SPLIT (needs both parts) rows 0-3 are the gas and rows
+ *          4-7 the sinks; n_out == 8 n_points.  counts (optional, 2 x int64): the points with a non-finite coordinate, the
+ *          points whose softening length is <= 0 or non-finite; both kinds get NaN in every row.  n_points == 0 succeeds
+ *          and writes no row.  An empty source set gives zeros for the gas part.
+ * Order    a point's rows are a function of the source records in order with their box, the sinks, and the point's own
+ *          {x, y, z, h} only: every lane of the walk adds exactly its own walk's contributions in its own walk's order,
+ *          and the per-lane arithmetic does not depend on the other lanes.  The rows are bitwise the same over repeated
+ *          calls, any order or subset of the points (one point alone included), the context's slot order, dense or
+ *          SPH_FLAG_HASHED_GRID grids, the host and device forms, and a single context versus a context fed the same records
+ *          and box through sph_set_gravity_sources_dev.  (The points are walked in the order of their 63-bit path keys in
+ *          the tree's root box; that is a matter of speed only.)  No float atomics.
+ * cost     sph_energy's.  Without external sources the tree is built into the context's tree arrays at every call (one
+ *          read-back for the root box), so the next sph_forces builds its own tree again, with the same results; with
+ *          external sources the tree in place is used, or built.  Host form: the copies in, that read-back, the copies out;
+ *          a bad softening length is SPH_ERR_STATE (the rows are written).  Device form: ordered on the context's stream.
+ *          No state, field, statistic (other than device_bytes), dt, grid or list changes; a run that calls it between the
+ *          steps is bitwise the run without it.
+ * SPH_ERR_ARG: null descriptor, null point arrays with n_points > 0, n_points outside 0 .. 2^31 - 1, n_out != 4 (8 with
+ * SPLIT) n_points, null out with n_points > 0, no part selected, SPLIT without both parts, unknown flags, reserved != 0, h < 0
+ * or NaN, soft2 < 0 or NaN, h == 0 without ph on a variable-h context; nothing is written then.  SPH_ERR_STATE: params.h <= 0
+ * with h == 0 and no ph on a fixed-h context; host form, a point's softening length <= 0 or non-finite.  SPH_ERR_NOMEM: the
+ * scratch does not fit. */
+#define SPH_GRAVAT_GAS    1   /* the Barnes-Hut field of the gas sources                       */
+#define SPH_GRAVAT_SINKS  2   /* the sinks' field, unsoftened as sink_gravforces ([F]:559-591) */
+#define SPH_GRAVAT_SPLIT  4   /* 8 output rows: gas (phi, ax, ay, az), then sinks; needs both parts */
+typedef struct sph_gravity_at_desc {
+    double  h;            /* > 0: softening length of every point; 0: params.h (fixed-h contexts only); unused with ph */
+    double  soft2;        /* >= 0, added to d.d as the force walk does; 0.001 * 2.5 is the force's value */
+    int32_t flags;        /* SPH_GRAVAT_*; at least one of GAS, SINKS */
+    int32_t reserved[3];  /* must be 0 */
+} sph_gravity_at_desc;    /* 32 bytes */
+int sph_gravity_at(sph_ctx *ctx, const sph_gravity_at_desc *d, int64_t n_points, const double *px, const double *py,
+                   const double *pz, const double *ph, double *host_out, int64_t n_out, int64_t *counts);
+int sph_gravity_at_dev(sph_ctx *ctx, const sph_gravity_at_desc *d, int64_t n_points, const double *d_px, const double *d_py,
+                       const double *d_pz, const double *d_ph, double *d_out, int64_t n_out, int64_t *d_counts);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too

@@ -48,6 +48,7 @@ SYMBOLS = [
     "sph_groups", "sph_groups_dev",
     "sph_gradients", "sph_gradients_dev",
     "sph_sample", "sph_sample_dev",
+    "sph_gravity_at", "sph_gravity_at_dev",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
@@ -78,6 +79,10 @@ GRAD_VALUES = -1
 SAMPLE_NORMALISE = 1
 SAMPLE_MAX_FIELDS = 4
 SAMPLE_VALUES = -1
+GRAVAT_GAS = 1
+GRAVAT_SINKS = 2
+GRAVAT_SPLIT = 4
+GRAVAT_REF_SOFT2 = 0.001 * 2.5      # the force walk's softening term (0.001_dp * smoothing)
 PROFILE_SUMS = ["N", "M", "mR", "mz", "mzz", "mvR", "mvphi", "mvz", "mvRvR", "mvphivphi", "mvzvz", "mu", "malpha", "mh",
                 "mlx", "mly", "mlz", "mex", "mey", "mez"]
 
@@ -199,6 +204,20 @@ def sample_desc(fields=(), weight="mass", normalise=False, h=None, clip=None) ->
     lo, hi = ((-np.inf,) * 3, (np.inf,) * 3) if clip is None else clip
     d.clip_lo[:] = [float(v) for v in lo]
     d.clip_hi[:] = [float(v) for v in hi]
+    return d
+
+
+class GravityAtDesc(C.Structure):
+    """sph_gravity_at_desc (include/summersph.h): h (0: params.h; unused with ph), soft2, flags (GRAVAT_*), reserved"""
+    _fields_ = [("h", C.c_double), ("soft2", C.c_double), ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+def gravity_at_desc(h=None, soft2=GRAVAT_REF_SOFT2, gas=True, sinks=True, split=False) -> GravityAtDesc:
+    """The descriptor of Context.gravity_at's arguments."""
+    d = GravityAtDesc()
+    d.h = 0.0 if h is None else float(h)
+    d.soft2 = float(soft2)
+    d.flags = (GRAVAT_GAS if gas else 0) | (GRAVAT_SINKS if sinks else 0) | (GRAVAT_SPLIT if split else 0)
     return d
 
 
@@ -394,6 +413,9 @@ def load():
                        C.c_int64, C.c_void_p, C.c_void_p]
     lib.sph_gradients_dev.argtypes = [C.c_void_p, C.POINTER(GradientsDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                       C.c_void_p]
+    for fn in (lib.sph_gravity_at, lib.sph_gravity_at_dev):
+        fn.argtypes = [C.c_void_p, C.POINTER(GravityAtDesc), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                       C.c_int64, C.c_void_p]
     _lib = lib
     return lib
 
@@ -1041,6 +1063,77 @@ class Context:
             return w
         parts = [out] + ([w] if want_w else []) + ([cn] if counts else [])
         return parts[0] if len(parts) == 1 else tuple(parts)
+
+    # ---- potential and acceleration at arbitrary points (sph_gravity_at) ---------------------------
+    def gravity_at(self, points, h=None, ph=None, soft2=GRAVAT_REF_SOFT2, gas=True, sinks=True, split=False, counts=False,
+                   device=False):
+        """The gravitational potential and acceleration at arbitrary points (include/summersph.h, sph_gravity_at): the
+        Barnes-Hut field of the gas sources (gas=True, with or without FLAG_SELF_GRAVITY) and the unsoftened field of the
+        sinks (sinks=True).  points: as Context.sample takes them.  The points' softening length: ph, an array (a device
+        tensor with device=True) of M values, else h, else params.h (fixed-h contexts).  Returns (phi, acc) of shapes (M,)
+        and (3, M), the sum of the selected parts; split=True: (2, M) and (2, 3, M), the gas first, then the sinks.
+        counts=True: (phi, acc, (n_nonfinite_points, n_bad_h)).  device=True: torch tensors (sph_gravity_at_dev).  The
+        descriptor used is left in self.gravity_at_desc."""
+        d = gravity_at_desc(h, soft2, gas, sinks, split)
+        self.gravity_at_desc = d
+        rows = 8 if split else 4
+        three = isinstance(points, (tuple, list)) and len(points) == 3
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+
+            def ok(t):
+                return isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == dev
+            if three:
+                p = list(points)
+            elif ok(points) and points.ndim == 2 and points.shape[1] == 3:
+                p = [points[:, a].contiguous() for a in range(3)]
+            else:
+                p = [None]
+            if ph is not None:
+                p = p + [ph]
+            if not all(ok(t) and t.ndim == 1 and t.is_contiguous() and t.numel() == p[0].numel() for t in p):
+                raise ValueError("gravity_at: device points (and ph) must be contiguous float64 tensors on the context's GPU")
+            m = p[0].numel()
+            out = torch.empty((rows, m), dtype=torch.float64, device=dev)
+            cnt = torch.empty(2, dtype=torch.int64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
+            self._ck(self.lib.sph_gravity_at_dev(self._h, C.byref(d), m, *(C.c_void_p(t.data_ptr()) for t in p[:3]),
+                                                 None if ph is None else C.c_void_p(p[3].data_ptr()),
+                                                 C.c_void_p(out.data_ptr()), rows * m, C.c_void_p(cnt.data_ptr())))
+            st = self.stream()                                    # torch's later work waits for the walk
+            if st:
+                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
+            else:
+                torch.cuda.synchronize(dev)
+            cn = tuple(int(v) for v in cnt.cpu().tolist()) if counts else None
+        else:
+            if three:
+                p = [np.ascontiguousarray(t, dtype=np.float64).reshape(-1) for t in points]
+            else:
+                a = np.asarray(points, dtype=np.float64)
+                if a.ndim != 2 or a.shape[1] != 3:
+                    raise ValueError("gravity_at: points must be an (M, 3) array or three arrays")
+                p = [np.ascontiguousarray(a[:, k]) for k in range(3)]
+            m = p[0].size
+            if p[1].size != m or p[2].size != m:
+                raise ValueError("gravity_at: the three point arrays differ in length")
+            hh = None
+            if ph is not None:
+                hh = np.ascontiguousarray(ph, dtype=np.float64).reshape(-1)
+                if hh.size != m:
+                    raise ValueError(f"gravity_at: ph has {hh.size} values for {m} points")
+            out = np.empty((rows, m), dtype=np.float64)
+            cc = (C.c_int64 * 2)(0, 0)
+            self._ck(self.lib.sph_gravity_at(self._h, C.byref(d), m, p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data,
+                                             None if hh is None else hh.ctypes.data, out.ctypes.data, rows * m, cc))
+            cn = (int(cc[0]), int(cc[1])) if counts else None
+        if split:
+            out = out.reshape(2, 4, m)
+            phi, acc = out[:, 0], out[:, 1:]
+        else:
+            phi, acc = out[0], out[1:]
+        return (phi, acc, cn) if counts else (phi, acc)
 
     # ---- diagnostics ---------------------------------------------------------------------
     def stats(self) -> Stats:

@@ -1299,6 +1299,20 @@ int sph_sample_dev(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const
     return sample_run(c, d, n_points, d_px, d_py, d_pz, d_values, d_out, n_out, d_weight, d_counts, false, field_ready);
 }
 
+int sph_gravity_at(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_points, const double *px, const double *py,
+                   const double *pz, const double *ph, double *host_out, int64_t n_out, int64_t *counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return gravity_at_run(c, d, n_points, px, py, pz, ph, host_out, n_out, counts, true);
+}
+
+int sph_gravity_at_dev(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_points, const double *d_px, const double *d_py,
+                       const double *d_pz, const double *d_ph, double *d_out, int64_t n_out, int64_t *d_counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return gravity_at_run(c, d, n_points, d_px, d_py, d_pz, d_ph, d_out, n_out, d_counts, false);
+}
+
 int sph_synchronize(sph_ctx *c) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);

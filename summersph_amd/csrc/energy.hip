@@ -181,6 +181,28 @@ __global__ __launch_bounds__(WAVE) void energy_final(const double *__restrict__ 
 
 }  // namespace
 
+// The source set of sph_energy and sph_gravity_at without external sources: the owned gas as {x, y, z, m} records in the
+// caller's order (rec: n_owned double4) and their exact box (bb: min xyz, max xyz; one read-back through the pinned slots,
+// which the caller has made sure of).  box_part: 6 (stage_blocks + 1) doubles; c->inv is current (ensure_inv).
+int stage_blocks(int64_t n_owned) {
+    return (int)std::min<int64_t>((std::max<int64_t>(n_owned, 1) + EB - 1) / EB, BOX_BLOCKS);
+}
+
+int stage_sources(sph_ctx *c, double *rec, double *box_part, double bb[6]) {
+    hipStream_t st = c->stream;
+    const int64_t no = c->n_owned;
+    const int nb = stage_blocks(no);
+    double *box = box_part + 6 * (size_t)nb;
+    energy_stage<<<dim3((unsigned)nb), dim3(EB), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], c->f[SPH_F_M], c->inv, no,
+                                                          reinterpret_cast<double4 *>(rec), box_part);
+    energy_box<<<dim3(1), dim3(WAVE), 0, st>>>(box_part, nb, box);
+    SPH_HIP(hipGetLastError());
+    SPH_HIP(hipMemcpyAsync(c->rnd_pinned, box, 6 * sizeof(double), hipMemcpyDeviceToHost, st));
+    SPH_HIP(hipStreamSynchronize(st));
+    for (int a = 0; a < 6; a++) bb[a] = c->rnd_pinned[a];
+    return SPH_OK;
+}
+
 int energy_sums(sph_ctx *c, int64_t src_offset, double *sums, double *phi, int64_t n_phi, bool host) {
     const char *who = "sph_energy";
     if (!sums && !phi) return arg_error(c, who, "both outputs are null");
@@ -194,7 +216,7 @@ int energy_sums(sph_ctx *c, int64_t src_offset, double *sums, double *phi, int64
     hipStream_t st = c->stream;
     const int64_t n_pieces = (no + PIECE - 1) / PIECE;
     const int64_t no1 = std::max<int64_t>(no, 1);
-    const int nb = (int)std::min<int64_t>((no1 + EB - 1) / EB, BOX_BLOCKS);
+    const int nb = stage_blocks(no);
     double4 *rec;
     double *phi_buf, *box_part, *part, *sums_buf;
     auto layout = [&](Carve cv) {
@@ -209,7 +231,6 @@ int energy_sums(sph_ctx *c, int64_t src_offset, double *sums, double *phi, int64
     SPH_TRY(analysis_scratch(c, layout(Carve{}), &buf));
     layout(Carve{buf});
     double *phi_self = self ? phi_buf : nullptr;
-    double *box = box_part + 6 * (size_t)nb;
     double *d_sums = host || !sums ? sums_buf : sums;
     double *d_phi = phi ? (host ? c->scratch : phi) : nullptr;      // host form: the download buffer (cap >= n doubles)
     SPH_TRY(analysis_pinned(c));
@@ -218,14 +239,8 @@ int energy_sums(sph_ctx *c, int64_t src_offset, double *sums, double *phi, int64
     if (self) {
         int64_t n_src = no;
         if (!ext) {
-            energy_stage<<<dim3((unsigned)nb), dim3(EB), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], c->f[SPH_F_M], c->inv,
-                                                                  no, rec, box_part);
-            energy_box<<<dim3(1), dim3(WAVE), 0, st>>>(box_part, nb, box);
-            SPH_HIP(hipGetLastError());
-            SPH_HIP(hipMemcpyAsync(c->rnd_pinned, box, 6 * sizeof(double), hipMemcpyDeviceToHost, st));
-            SPH_HIP(hipStreamSynchronize(st));
             double bb[6];
-            for (int a = 0; a < 6; a++) bb[a] = c->rnd_pinned[a];
+            SPH_TRY(stage_sources(c, reinterpret_cast<double *>(rec), box_part, bb));
             SPH_TRY(gravity_tree_build_records(c, reinterpret_cast<const double *>(rec), no, bb));
             src_offset = 0;
         } else {

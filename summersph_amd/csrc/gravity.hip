@@ -474,6 +474,82 @@ __global__ __launch_bounds__(GB) void grav_potential_wave(int nt, int n, const W
     if (live) phi[id] = acc;
 }
 
+// gamma(q) = M(q) / q^3 inside the softening support, M the grav_table polynomial ([F]:81-101) divided analytically (finite
+// at q = 0); rq = 1 / q, used in the middle piece only.  phi'(q) = q gamma(q): the pull that belongs to soft_phi.
+__device__ __forceinline__ double soft_gamma(double q, double rq) {
+#pragma clang fp contract(off)
+    if (q < 1.0) return (4.0 / 3.0) + (q * q) * (-1.2 + 0.5 * q);
+    return ((8.0 / 3.0) + q * (-3.0 + q * (1.2 - q * (1.0 / 6.0)))) - ((rq * rq) * rq) * (1.0 / 15.0);
+}
+
+// The field of the same Barnes-Hut walk at points that are not particles (sph_gravity_at): grav_potential_wave's traversal,
+// acceptance test and sleeping lanes over the same records, one wave per 64 points of the walk order (pidx: the points
+// sorted by their path key, or null: the caller's order).  Each accepted node or leaf of mass m adds, with
+// s = sqrt(d^2 + soft2) and q = s / h_p,
+//   q < 2:   Phi += (G m / h_p) phi(q),  a -= ((G m / h_p^3) gamma(q)) d
+//   q >= 2:  Phi -= (G m) (1 / s),       a -= ((G m) (1 / s)^3) d
+// Points are not sources: nothing is excluded, and s = 0 (a point on a source, soft2 = 0) is q = 0, finite.  Dead lanes
+// (the tail, a non-finite coordinate, h <= 0 or non-finite) never wake and write nothing.  A lane's arithmetic does not
+// depend on the other lanes, so a point's rows do not depend on its neighbours in the wave.  (A wave-uniform test "every
+// contributing lane has q >= 2" that skips the softening branch altogether measured 4 % slower, 1.95 against 1.88 ms for
+// 10^6 points: the branch is already skipped by the lanes' own compare, and the mask costs a scalar round trip per visit.)
+// Writes the four rows out[c * m + point], c = 0 Phi, 1..3 a, with plain stores.
+__global__ __launch_bounds__(GB) void grav_field_points(int64_t m, int n, const WalkRec *__restrict__ rec, const double *__restrict__ px,
+                                                        const double *__restrict__ py, const double *__restrict__ pz,
+                                                        const double *__restrict__ ph, double hfix, double soft2,
+                                                        const uint32_t *__restrict__ pidx, double *__restrict__ out) {
+#pragma clang fp contract(off)
+    const int64_t t = (int64_t)xcd_chunk(blockIdx.x, gridDim.x) * GB + threadIdx.x;
+    const int64_t tc = t < m ? t : m - 1;
+    const int64_t idx = pidx ? (int64_t)pidx[tc] : tc;
+    const double x = px[idx], y = py[idx], z = pz[idx];
+    const double hp = ph ? ph[idx] : hfix;
+    constexpr double BIG = 1.7976931348623157e308;
+    const bool live = t < m && fabs(x) <= BIG && fabs(y) <= BIG && fabs(z) <= BIG && hp > 0.0 && hp <= BIG;
+    const double inv_hp = 1.0 / hp;
+    const double inv_hp3 = (inv_hp * inv_hp) * inv_hp;
+    double phi = 0.0, a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    int resume = END;
+    int node = n >= 1 ? 0 : END;                  // one source: its leaf is record 0 and ends the walk
+    constexpr int CMP_EQ = 32, CMP_OLT = 4;
+    unsigned long long act_m = __builtin_amdgcn_ballot_w64(live);
+    while (node != END) {
+        node = __builtin_amdgcn_readfirstlane(node);
+        const WalkRec r = rec[node];
+        act_m |= __builtin_amdgcn_uicmp((unsigned)resume, (unsigned)node, CMP_EQ);
+        const int n_open = r.next_open, n_skip = r.next_skip;
+        const double d0 = x - r.cx, d1 = y - r.cy, d2c = z - r.cz;
+        const double d2 = fma(d2c, d2c, fma(d1, d1, fma(d0, d0, soft2)));     // the force walk's d2 and acceptance test
+        const unsigned long long acc_m = __builtin_amdgcn_fcmp(r.size2, d2, CMP_OLT);
+        const unsigned long long done_m = act_m & acc_m;
+        const bool open_any = (act_m & ~acc_m) != 0;
+        if (r.has_mass) {
+            if (__builtin_amdgcn_inverse_ballot_w64(done_m)) {
+                const double rs = d2 > 0.0 ? fast_rsqrt(d2) : 0.0;            // 1 / s (unused at s = 0)
+                const double q = (d2 * rs) * inv_hp;                          // s / h
+                double pt = -(r.gm * rs), f = r.gm * ((rs * rs) * rs);        // q >= 2
+                if (q < 2.0) {
+                    const double rq = hp * rs;
+                    pt = (r.gm * inv_hp) * soft_phi(q, rq);
+                    f = (r.gm * inv_hp3) * soft_gamma(q, rq);
+                }
+                phi += pt;
+                a0 = fma(-f, d0, a0); a1 = fma(-f, d1, a1); a2 = fma(-f, d2c, a2);
+            }
+        }
+        if (open_any) {
+            resume = __builtin_amdgcn_inverse_ballot_w64(done_m) ? n_skip : resume;
+            act_m &= ~done_m;
+            node = n_open;
+        } else {
+            node = n_skip;
+        }
+    }
+    if (live) {
+        out[idx] = phi; out[m + idx] = a0; out[2 * m + idx] = a1; out[3 * m + idx] = a2;
+    }
+}
+
 }  // namespace
 
 hipError_t grav_sort_tmp_bytes(int64_t n, size_t *bytes) {
@@ -643,6 +719,16 @@ hipError_t launch_potential(sph_ctx *c, int64_t n_src, int64_t src_off, double *
     grav_potential_wave<<<dim3((unsigned)((nt + GB - 1) / GB)), dim3(GB), 0, c->stream>>>(
         (int)nt, (int)n_src, reinterpret_cast<const WalkRec *>(c->g_wrec), c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z],
         c->variable ? c->f[SPH_F_H] : nullptr, c->p.h, soft2, c->orig, (int32_t)c->n_owned, c->g_leaf_of, src_off, phi);
+    return hipGetLastError();
+}
+
+// sph_gravity_at: Phi and a of the tree in place (n_src >= 1 leaves) at m points -> out[c * m + p], c < 4; ph: the points'
+// softening lengths or null (h_one for all); pidx: the walk order or null
+hipError_t launch_field_points(sph_ctx *c, int64_t n_src, int64_t m, const double *px, const double *py, const double *pz,
+                               const double *ph, double h_one, double soft2, const uint32_t *pidx, double *out) {
+    if (m == 0 || n_src == 0) return hipSuccess;
+    grav_field_points<<<dim3((unsigned)((m + GB - 1) / GB)), dim3(GB), 0, c->stream>>>(
+        m, (int)n_src, reinterpret_cast<const WalkRec *>(c->g_wrec), px, py, pz, ph, h_one, soft2, pidx, out);
     return hipGetLastError();
 }
 

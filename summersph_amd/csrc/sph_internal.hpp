@@ -82,6 +82,10 @@ struct TimingSlot {
     double total_ms = 0.0;
     int64_t launches = 0;
 };
+// potential and acceleration at arbitrary points (gravity_at.hip): host form (points / ph / out host memory, counts[2]
+// host) or device form (counts[2] device memory or null)
+int gravity_at_run(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_points, const double *px, const double *py,
+                   const double *pz, const double *ph, double *out, int64_t n_out, int64_t *counts, bool host);
 
 }  // namespace sph
 
@@ -379,6 +383,9 @@ hipError_t launch_gravity(sph_ctx *c);
 // arrays (clears tree_valid, grav_valid, gx_keys_valid), and the potential walk over the tree in place
 int gravity_tree_build_records(sph_ctx *c, const double *rec, int64_t n, const double box[6]);
 hipError_t launch_potential(sph_ctx *c, int64_t n_src, int64_t src_off, double *phi);
+// sph_gravity_at (gravity.hip): the walk over the tree in place with the caller's points as targets -> out[c * m + p], c < 4
+hipError_t launch_field_points(sph_ctx *c, int64_t n_src, int64_t m, const double *px, const double *py, const double *pz,
+                               const double *ph, double h_one, double soft2, const uint32_t *pidx, double *out);
 // accretion + boundary cull (accrete.hip)
 int accrete_and_cull(sph_ctx *c, int64_t *removed, int32_t *d_keep_out = nullptr);
 int sink_creation(sph_ctx *c, int32_t *created);
@@ -417,6 +424,9 @@ void profile_free(sph_ctx *c);
 // conserved totals and the gravitational potential (energy.hip): host form (sums / phi host memory, one read-back) or
 // device form
 int energy_sums(sph_ctx *c, int64_t src_offset, double *sums, double *phi, int64_t n_phi, bool host);
+// the staged source records of sph_energy and sph_gravity_at (energy.hip): the owned gas in the caller's order + their box
+int stage_blocks(int64_t n_owned);
+int stage_sources(sph_ctx *c, double *rec, double *box_part, double bb[6]);
 // friends-of-friends groups (groups.hip): host form (labels / table / count host memory, one synchronisation) or device
 // form; ready = sph_download_field's rule
 int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_labels, double *table, int64_t max_groups,
@@ -430,5 +440,9 @@ int gradients_run(sph_ctx *c, const sph_gradients_desc *d, const double *values,
 int sample_run(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const double *px, const double *py, const double *pz,
                const double *values, double *out, int64_t n_out, double *weight, int64_t *counts, bool host,
                bool (*ready)(const sph_ctx *, int));
+// potential and acceleration at arbitrary points (gravity_at.hip): host form (points / ph / out host memory, counts[2]
+// host) or device form (counts[2] device memory or null)
+int gravity_at_run(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_points, const double *px, const double *py,
+                   const double *pz, const double *ph, double *out, int64_t n_out, int64_t *counts, bool host);
 
 }  // namespace sph

@@ -44,6 +44,8 @@ module sph_hip_binding
   public :: sph_gradients_desc, sph_gradients, sph_gradients_dev, SPH_GRAD_CORRECTED, SPH_GRAD_MAX_FIELDS, SPH_GRAD_VALUES
   ! SPH interpolation at arbitrary points (density, fields or the caller's values where the caller wants them)
   public :: sph_sample_desc, sph_sample, sph_sample_dev, SPH_SAMPLE_NORMALISE, SPH_SAMPLE_MAX_FIELDS, SPH_SAMPLE_VALUES
+  ! gravitational potential and acceleration at arbitrary points (the gas' Barnes-Hut field and the sinks' field)
+  public :: sph_gravity_at_desc, sph_gravity_at, sph_gravity_at_dev, SPH_GRAVAT_GAS, SPH_GRAVAT_SINKS, SPH_GRAVAT_SPLIT
   public :: c_message
 
   integer(c_int), parameter :: SPH_OK = 0
@@ -151,6 +153,17 @@ module sph_hip_binding
     integer(c_int32_t) :: fields(SPH_SAMPLE_MAX_FIELDS)
     integer(c_int32_t) :: n_fields, weight, flags, reserved
   end type sph_sample_desc
+
+  ! sph_gravity_at: h (> 0: the softening length of every point; 0: params.h, fixed-h contexts only; unused with ph), soft2
+  ! (>= 0, added to d.d; 0.0025 is the force's value), flags (SPH_GRAVAT_GAS, _SINKS, _SPLIT), reserved (0).  out holds
+  ! out(p, c) in Fortran order: (n_points, 4) -- c = 1 Phi, 2..4 a -- or (n_points, 8) with SPLIT (the gas, then the sinks).
+  ! 32 bytes.
+  integer(c_int32_t), parameter :: SPH_GRAVAT_GAS = 1, SPH_GRAVAT_SINKS = 2, SPH_GRAVAT_SPLIT = 4
+  type, bind(C) :: sph_gravity_at_desc
+    real(c_double) :: h, soft2
+    integer(c_int32_t) :: flags
+    integer(c_int32_t) :: reserved(3)
+  end type sph_gravity_at_desc
 
   interface
     integer(c_int) function sph_abi_version() bind(C, name='sph_abi_version')
@@ -625,6 +638,23 @@ module sph_hip_binding
       import :: c_int, c_int64_t, c_ptr, sph_sample_desc
       type(c_ptr), value :: ctx, d_px, d_py, d_pz, d_values, d_out, d_weight, d_counts
       type(sph_sample_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_points, n_out
+    end function
+    ! ---- potential and acceleration at points: px, py, pz (n_points doubles each), ph (n_points softening lengths or
+    !      c_null_ptr), host_out (4 n_points doubles, 8 n_points with SPH_GRAVAT_SPLIT), counts (2 x int64: points with a
+    !      non-finite coordinate, points with a bad softening length; or c_null_ptr)
+    integer(c_int) function sph_gravity_at(ctx, d, n_points, px, py, pz, ph, host_out, n_out, counts) &
+        bind(C, name='sph_gravity_at')
+      import :: c_int, c_int64_t, c_ptr, sph_gravity_at_desc
+      type(c_ptr), value :: ctx, px, py, pz, ph, host_out, counts
+      type(sph_gravity_at_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_points, n_out
+    end function
+    integer(c_int) function sph_gravity_at_dev(ctx, d, n_points, d_px, d_py, d_pz, d_ph, d_out, n_out, d_counts) &
+        bind(C, name='sph_gravity_at_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_gravity_at_desc
+      type(c_ptr), value :: ctx, d_px, d_py, d_pz, d_ph, d_out, d_counts
+      type(sph_gravity_at_desc), intent(in) :: d
       integer(c_int64_t), value :: n_points, n_out
     end function
   end interface
