@@ -797,6 +797,90 @@ int sph_gravity_at(sph_ctx *ctx, const sph_gravity_at_desc *d, int64_t n_points,
 int sph_gravity_at_dev(sph_ctx *ctx, const sph_gravity_at_desc *d, int64_t n_points, const double *d_px, const double *d_py,
                        const double *d_pz, const double *d_ph, double *d_out, int64_t n_out, int64_t *d_counts);
 
+/* ---- binding energies and unbinding of clumps: is a group gravitationally bound, and which of its members form the
+ *      bound core -- the group's OWN softened potential by a direct pair sum, the members' energies in the group's frame,
+ *      and the iterated removal of the unbound members ------------------------------------------------------------------
+ * labels   one int32 per particle in sph_download_field order, n_labels == sph_count: what sph_groups writes, or any
+ *          partition of the caller's (the call does not depend on friends-of-friends).  Host memory for sph_bound, device
+ *          memory for _dev.
+ * Members  of group g, 0 <= g < n_groups: the owned gas particles (original id < n_owned) with a finite position and
+ *          label g.  Every other label value means "in no group".  Ghosts and sinks are never members.  One context's
+ *          owned particles only, as sph_groups.
+ * h        the renders' rule: desc.h when desc.h > 0, else each particle's own h (SPH_F_H on a variable-h context,
+ *          params.h on a fixed-h one).  G = params.G.  f = 1 with SPH_BOUND_THERMAL, else 0.
+ * One evaluation of a member set S of group g, without fused multiply-adds:
+ *          M = sum m, V = (sum m v) / M per axis.
+ *          Phi_i = sum_{j in S, j != i} ((G m_j) (1 / h_i)) phi(q), d = r_i - r_j, d2 = ((dx dx + dy dy) + dz dz) + soft2,
+ *          s = d2 rs with rs = 1 / sqrt(d2) to rounding (s = 0 where d2 == 0), q = s (1 / h_i); phi is sph_energy's
+ *          softening potential, evaluated analytically in Horner form, its 1 / q taken as h_i rs.  j != i is decided by
+ *          identity, never by distance: two distinct coincident members see each other, and phi(0) = -1.4 is finite.
+ *          d2 must not overflow.
+ *          k_i = 0.5 ((dvx dvx + dvy dvy) + dvz dvz), dv = v_i - V;  e_i = (k_i + u_i) + Phi_i (THERMAL) or k_i + Phi_i.
+ *          The set's sums: K = sum (0.5 m) |dv|^2, U = sum m u, W = sum (0.5 m) Phi, sum m r.
+ * Rounds   S_0 is the group, S_{r+1} = { i in S_r : e_i < 0 } (a NaN e_i is not < 0).  S_0, S_1, ... are evaluated, and
+ *          the group stops after the evaluation of S_R with the first of these that holds:
+ *          status 0  S_{R+1} == S_R: converged;
+ *          status 1  R == max_rounds: no further removal is allowed (max_rounds == 0 evaluates once and removes nothing);
+ *          status 2  |S_{R+1}| < min_members: dissolved.  Also N_0 < min_members (empty groups included): R = 0 and
+ *                    nothing is evaluated.
+ *          A group with N_0 > max_members is status 3: never evaluated, its row is NaN apart from N_0 and the status, its
+ *          labels are -1, and it is counted.  Every evaluation is complete: Phi is recomputed over the current set, never
+ *          decremented, so a value depends on the set alone, not on the path to it.
+ * Order    a group's members are taken in ascending original id.  Phi_i is one accumulation chain over the members of
+ *          S_0 in that order, in which a removed member and i itself add nothing.  The set sums run over the sorted
+ *          positions of S_0 (a removed member adds nothing) in the fixed shape of sph_groups: pieces of 1024 sorted
+ *          positions counted from the group's start, each added by one 64-lane wavefront (lane l: positions l, l + 64, ...
+ *          in turn, then a xor butterfly over the lanes), then the pieces by one wavefront in the same shape.  The minimum
+ *          and its member are order-free.  No float atomics.  A group's row and its members' outputs are a function of
+ *          that group's id-sorted member records and the descriptor only: bitwise the same over repeated calls, the
+ *          context's slot order, dense or hashed grids, the host and device forms, and whatever other groups the labels
+ *          hold.  Removed members are masked (zero-mass sources), not compacted away.
+ * Outputs  all optional, at least one given.
+ *          bound_labels[id] (sph_count int32): g if the member is in the last evaluated set of g, e_i < 0 and g ended with
+ *          status 0 or 1; else -1 (a dissolved group has no bound member).
+ *          out[0 * n + id] = e_i, out[1 * n + id] = Phi_i, n = sph_count, n_out == 2 n: from the last evaluation that
+ *          included the member, so a removed member keeps the e_i >= 0 that removed it; NaN for non-members and for the
+ *          members of groups that were never evaluated.
+ *          table[g * SPH_BOUND_NCOL + c], n_groups rows:
+ *           0 N_0   1 M_0   2 K_0   3 U_0   4 W_0   5 E_0 = (K_0 + f U_0) + W_0   6 (K_0 + f U_0) / |W_0|       (of S_0)
+ *           7 N_R   8 M_R   9-11 R_R = (sum m r) / M   12-14 V_R   15 K_R   16 U_R   17 W_R   18 E_R   (of the last set)
+ *          19 members of S_R with e < 0      20 R      21 status
+ *          22 original id of the most bound member of S_R (the smallest e, the smallest id on ties; -1 if none)  23 its e
+ *          Dissolved groups: columns 7, 8 and 19 are 0, 9-18 and 23 NaN, 22 is -1; 0-6 stay those of S_0 where S_0 was
+ *          evaluated (NaN apart from N_0 where it was not).
+ *          counts[4] (int64): members, groups skipped over the cap, groups dissolved, groups stopped at max_rounds.
+ * cost     sum over rounds and groups of N_0 N_r pair terms (a removed member is still streamed as a source, but no
+ *          longer a target; where the removed members lie scattered over the 64-lane target tiles, N_0^2 a round), so
+ *          max_members is a cost decision.  Device form: ordered on the context's stream, never
+ *          synchronises; min(max_rounds, min(n_owned, max_members) - 1) + 1 rounds of six launches are enqueued, whose
+ *          grids n_groups and the slot count bound from the host; the per-round work list is built on the device and the
+ *          launches of a round in which no group is active leave at once.  Host form: reads one "groups still active"
+ *          count per round and stops enqueueing at 0, then one synchronisation for the copies out.  A member with h <= 0
+ *          or a non-finite h (per-particle h only): device form d_counts[0] == -1, every row NaN, every label -1; host form
+ *          SPH_ERR_STATE.  The scratch is the render's.  No state, field, statistic (other than device_bytes), flag, grid,
+ *          list or dt of the context changes; a run that calls sph_bound after every step is bitwise the run without it.
+ *          Works in every state of the context (after an upload, a step, a cull); rho is not needed.
+ * SPH_ERR_ARG: null descriptor or labels, no output, n_labels != sph_count, n_out != 2 sph_count with out given, n_groups
+ * outside 0 .. 2^31 - 1, min_members < 1, max_members < 1, max_rounds < 0, h < 0 or NaN, soft2 < 0 or NaN, unknown flags,
+ * reserved != 0; nothing is written then.  SPH_ERR_STATE: params.h <= 0 with h == 0 on a fixed-h context; host form, a
+ * member with h <= 0 or a non-finite h.  SPH_ERR_NOMEM: the scratch does not fit.  n_groups == 0, an empty context or all
+ * labels -1 succeed with zero members. */
+#define SPH_BOUND_THERMAL  1     /* e_i includes u_i */
+#define SPH_BOUND_NCOL    24     /* table columns per group */
+typedef struct sph_bound_desc {
+    double  h;            /* > 0: one softening length for every member; 0: each particle's own h (SPH_F_H / params.h) */
+    double  soft2;        /* >= 0, added to d.d; 0.001 * 2.5 is the force's value */
+    int64_t min_members;  /* >= 1: a set that falls below it dissolves */
+    int64_t max_members;  /* >= 1: groups with more initial members are skipped (cost cap) */
+    int32_t max_rounds;   /* >= 0: removals allowed; 0 = evaluate once, remove nothing */
+    int32_t flags;        /* SPH_BOUND_THERMAL */
+    int32_t reserved[2];  /* must be 0 */
+} sph_bound_desc;         /* 48 bytes */
+int sph_bound(sph_ctx *ctx, const sph_bound_desc *d, const int32_t *labels, int64_t n_labels, int64_t n_groups,
+              int32_t *bound_labels, double *host_out, int64_t n_out, double *host_table, int64_t *counts);
+int sph_bound_dev(sph_ctx *ctx, const sph_bound_desc *d, const int32_t *d_labels, int64_t n_labels, int64_t n_groups,
+                  int32_t *d_bound_labels, double *d_out, int64_t n_out, double *d_table, int64_t *d_counts);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too

@@ -49,6 +49,7 @@ SYMBOLS = [
     "sph_gradients", "sph_gradients_dev",
     "sph_sample", "sph_sample_dev",
     "sph_gravity_at", "sph_gravity_at_dev",
+    "sph_bound", "sph_bound_dev",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
@@ -83,6 +84,13 @@ GRAVAT_GAS = 1
 GRAVAT_SINKS = 2
 GRAVAT_SPLIT = 4
 GRAVAT_REF_SOFT2 = 0.001 * 2.5      # the force walk's softening term (0.001_dp * smoothing)
+BOUND_THERMAL = 1
+BOUND_NCOL = 24
+# sph_bound's table columns (include/summersph.h, "Outputs"): S_0's, the last evaluated set's, the outcome
+BOUND_COLUMNS = ["N0", "M0", "K0", "U0", "W0", "E0", "virial0", "N", "M", "x", "y", "z", "vx", "vy", "vz", "K", "U", "W", "E",
+                 "n_bound", "rounds", "status", "id_most_bound", "e_most_bound"]
+BOUND_STATUS = ["converged", "max_rounds", "dissolved", "skipped"]
+BOUND_COUNTS = ["members", "skipped", "dissolved", "max_rounds"]
 PROFILE_SUMS = ["N", "M", "mR", "mz", "mzz", "mvR", "mvphi", "mvz", "mvRvR", "mvphivphi", "mvzvz", "mu", "malpha", "mh",
                 "mlx", "mly", "mlz", "mex", "mey", "mez"]
 
@@ -219,6 +227,29 @@ def gravity_at_desc(h=None, soft2=GRAVAT_REF_SOFT2, gas=True, sinks=True, split=
     d.soft2 = float(soft2)
     d.flags = (GRAVAT_GAS if gas else 0) | (GRAVAT_SINKS if sinks else 0) | (GRAVAT_SPLIT if split else 0)
     return d
+
+
+class BoundDesc(C.Structure):
+    """sph_bound_desc (include/summersph.h): h (0: each particle's own), soft2, min_members, max_members (cost cap),
+    max_rounds (0: evaluate once), flags (BOUND_THERMAL), reserved"""
+    _fields_ = [("h", C.c_double), ("soft2", C.c_double), ("min_members", C.c_int64), ("max_members", C.c_int64),
+                ("max_rounds", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+def bound_desc(h=None, soft2=GRAVAT_REF_SOFT2, thermal=False, max_rounds=0, min_members=1, max_members=2**31 - 1) -> BoundDesc:
+    """The descriptor of Context.bound's arguments (see there)."""
+    d = BoundDesc()
+    d.h = 0.0 if h is None else float(h)
+    d.soft2 = float(soft2)
+    d.min_members, d.max_members, d.max_rounds = int(min_members), int(max_members), int(max_rounds)
+    d.flags = BOUND_THERMAL if thermal else 0
+    return d
+
+
+def bound_table(table: np.ndarray) -> np.ndarray:
+    """(n, BOUND_NCOL) float64 -> a structured array of n records with the BOUND_COLUMNS names"""
+    t = np.ascontiguousarray(table, dtype=np.float64).reshape(-1, BOUND_NCOL)
+    return t.view([(c, np.float64) for c in BOUND_COLUMNS]).reshape(-1)
 
 
 def velocity_derivatives(grad):
@@ -416,6 +447,10 @@ def load():
     for fn in (lib.sph_gravity_at, lib.sph_gravity_at_dev):
         fn.argtypes = [C.c_void_p, C.POINTER(GravityAtDesc), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                        C.c_int64, C.c_void_p]
+    lib.sph_bound.argtypes = [C.c_void_p, C.POINTER(BoundDesc), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                              C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.sph_bound_dev.argtypes = [C.c_void_p, C.POINTER(BoundDesc), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                  C.c_int64, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -1134,6 +1169,52 @@ class Context:
         else:
             phi, acc = out[0], out[1:]
         return (phi, acc, cn) if counts else (phi, acc)
+
+    # ---- binding energies and unbinding of groups (sph_bound) ----------------------------------------
+    def bound(self, labels, n_groups, h=None, soft2=GRAVAT_REF_SOFT2, thermal=False, max_rounds=0, min_members=1,
+              max_members=2**31 - 1, device=False):
+        """Is each group bound, and which members form its bound core (include/summersph.h, sph_bound): labels is one
+        int32 per particle in the upload order (Context.groups' labels, or any partition; values outside 0 ..
+        n_groups - 1 mean "in no group").  Every group's own softened potential Phi is a direct pair sum over its members,
+        e = 0.5 |v - V|^2 (+ u with thermal=True) + Phi, and up to max_rounds times the members with e >= 0 are removed
+        and the rest evaluated again; a set that falls below min_members dissolves, a group with more than max_members
+        members is skipped (the cost is the sum of N^2).  h: None = each particle's own h, else one softening length.
+        Returns (bound_labels, e, phi, table, counts): bound_labels int32 (the group, or -1), e and phi per particle (NaN
+        for non-members), table a structured array (BOUND_COLUMNS) of n_groups rows, counts = (members, skipped,
+        dissolved, stopped at max_rounds).  device=True: labels is an int32 tensor on the context's GPU and bound_labels,
+        e, phi and the (n_groups, BOUND_NCOL) table are torch tensors (sph_bound_dev); counts[0] == -1 then tells of a
+        member with an unusable h.  The descriptor used is left in self.bound_desc."""
+        d = bound_desc(h, soft2, thermal, max_rounds, min_members, max_members)
+        n, ng = self.n, int(n_groups)
+        self.bound_desc = d
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if not (isinstance(labels, torch.Tensor) and labels.dtype == torch.int32 and labels.is_contiguous()
+                    and labels.device == dev and labels.numel() == n):
+                raise ValueError("bound: device labels must be a contiguous int32 tensor of sph_count values on the context's GPU")
+            bl = torch.empty(n, dtype=torch.int32, device=dev)
+            out = torch.empty((2, n), dtype=torch.float64, device=dev)
+            tab = torch.empty((max(ng, 0), BOUND_NCOL), dtype=torch.float64, device=dev)
+            cnt = torch.empty(4, dtype=torch.int64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
+            self._ck(self.lib.sph_bound_dev(self._h, C.byref(d), C.c_void_p(labels.data_ptr()), n, ng, C.c_void_p(bl.data_ptr()),
+                                            C.c_void_p(out.data_ptr()), 2 * n, C.c_void_p(tab.data_ptr()),
+                                            C.c_void_p(cnt.data_ptr())))
+            st = self.stream()                                    # torch's later work waits for the rounds
+            if st:
+                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
+            else:
+                torch.cuda.synchronize(dev)
+            return bl, out[0], out[1], tab, tuple(int(v) for v in cnt.cpu().tolist())
+        lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        bl = np.empty(n, dtype=np.int32)
+        out = np.empty((2, n), dtype=np.float64)
+        tab = np.empty((max(ng, 0), BOUND_NCOL), dtype=np.float64)
+        cc = (C.c_int64 * 4)(0, 0, 0, 0)
+        self._ck(self.lib.sph_bound(self._h, C.byref(d), lab.ctypes.data, lab.size, ng, bl.ctypes.data, out.ctypes.data, 2 * n,
+                                    tab.ctypes.data, cc))
+        return bl, out[0], out[1], bound_table(tab), tuple(int(v) for v in cc)
 
     # ---- diagnostics ---------------------------------------------------------------------
     def stats(self) -> Stats:

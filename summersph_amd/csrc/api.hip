@@ -1313,6 +1313,20 @@ int sph_gravity_at_dev(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_point
     return gravity_at_run(c, d, n_points, d_px, d_py, d_pz, d_ph, d_out, n_out, d_counts, false);
 }
 
+int sph_bound(sph_ctx *c, const sph_bound_desc *d, const int32_t *labels, int64_t n_labels, int64_t n_groups,
+              int32_t *bound_labels, double *host_out, int64_t n_out, double *host_table, int64_t *counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return bound_run(c, d, labels, n_labels, n_groups, bound_labels, host_out, n_out, host_table, counts, true);
+}
+
+int sph_bound_dev(sph_ctx *c, const sph_bound_desc *d, const int32_t *d_labels, int64_t n_labels, int64_t n_groups,
+                  int32_t *d_bound_labels, double *d_out, int64_t n_out, double *d_table, int64_t *d_counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return bound_run(c, d, d_labels, n_labels, n_groups, d_bound_labels, d_out, n_out, d_table, d_counts, false);
+}
+
 int sph_synchronize(sph_ctx *c) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);

@@ -444,5 +444,9 @@ int sample_run(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const dou
 // host) or device form (counts[2] device memory or null)
 int gravity_at_run(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_points, const double *px, const double *py,
                    const double *pz, const double *ph, double *out, int64_t n_out, int64_t *counts, bool host);
+// binding energies and unbinding of groups (bound.hip): host form (labels in, every output and counts[4] host memory) or
+// device form (all device memory, no synchronisation)
+int bound_run(sph_ctx *c, const sph_bound_desc *d, const int32_t *labels, int64_t n_labels, int64_t n_groups,
+              int32_t *bound_labels, double *out, int64_t n_out, double *table, int64_t *counts, bool host);
 
 }  // namespace sph

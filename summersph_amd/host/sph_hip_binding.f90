@@ -46,6 +46,8 @@ module sph_hip_binding
   public :: sph_sample_desc, sph_sample, sph_sample_dev, SPH_SAMPLE_NORMALISE, SPH_SAMPLE_MAX_FIELDS, SPH_SAMPLE_VALUES
   ! gravitational potential and acceleration at arbitrary points (the gas' Barnes-Hut field and the sinks' field)
   public :: sph_gravity_at_desc, sph_gravity_at, sph_gravity_at_dev, SPH_GRAVAT_GAS, SPH_GRAVAT_SINKS, SPH_GRAVAT_SPLIT
+  ! binding energies and unbinding of groups (each group's own potential, the members' energies, the bound core)
+  public :: sph_bound_desc, sph_bound, sph_bound_dev, SPH_BOUND_THERMAL, SPH_BOUND_NCOL
   public :: c_message
 
   integer(c_int), parameter :: SPH_OK = 0
@@ -164,6 +166,18 @@ module sph_hip_binding
     integer(c_int32_t) :: flags
     integer(c_int32_t) :: reserved(3)
   end type sph_gravity_at_desc
+
+  ! sph_bound: h (> 0: one softening length for every member; 0: each particle's own h), soft2 (>= 0, added to d.d; 0.0025
+  ! is the force's value), min_members (>= 1: a set that falls below it dissolves), max_members (>= 1: larger groups are
+  ! skipped), max_rounds (>= 0 removals; 0: evaluate once), flags (SPH_BOUND_THERMAL), reserved (0).  out holds out(id, c) in
+  ! Fortran order: (sph_count, 2) -- c = 1 e, 2 Phi; table(SPH_BOUND_NCOL, n_groups); counts(4).  48 bytes.
+  integer(c_int32_t), parameter :: SPH_BOUND_THERMAL = 1, SPH_BOUND_NCOL = 24
+  type, bind(C) :: sph_bound_desc
+    real(c_double) :: h, soft2
+    integer(c_int64_t) :: min_members, max_members
+    integer(c_int32_t) :: max_rounds, flags
+    integer(c_int32_t) :: reserved(2)
+  end type sph_bound_desc
 
   interface
     integer(c_int) function sph_abi_version() bind(C, name='sph_abi_version')
@@ -656,6 +670,24 @@ module sph_hip_binding
       type(c_ptr), value :: ctx, d_px, d_py, d_pz, d_ph, d_out, d_counts
       type(sph_gravity_at_desc), intent(in) :: d
       integer(c_int64_t), value :: n_points, n_out
+    end function
+    ! ---- binding energies and unbinding of groups: labels (sph_count int32: the group of every particle, e.g. what
+    !      sph_groups wrote), bound_labels (sph_count int32), host_out (2 sph_count doubles: e, then Phi), host_table
+    !      (SPH_BOUND_NCOL doubles per group), counts (4 x int64: members, groups skipped, dissolved, stopped at
+    !      max_rounds); every output is c_loc(...) or c_null_ptr, at least one given
+    integer(c_int) function sph_bound(ctx, d, labels, n_labels, n_groups, bound_labels, host_out, n_out, host_table, counts) &
+        bind(C, name='sph_bound')
+      import :: c_int, c_int64_t, c_ptr, sph_bound_desc
+      type(c_ptr), value :: ctx, labels, bound_labels, host_out, host_table, counts
+      type(sph_bound_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_labels, n_groups, n_out
+    end function
+    integer(c_int) function sph_bound_dev(ctx, d, d_labels, n_labels, n_groups, d_bound_labels, d_out, n_out, d_table, &
+                                          d_counts) bind(C, name='sph_bound_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_bound_desc
+      type(c_ptr), value :: ctx, d_labels, d_bound_labels, d_out, d_table, d_counts
+      type(sph_bound_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_labels, n_groups, n_out
     end function
   end interface
 
