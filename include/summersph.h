@@ -881,6 +881,60 @@ int sph_bound(sph_ctx *ctx, const sph_bound_desc *d, const int32_t *labels, int6
 int sph_bound_dev(sph_ctx *ctx, const sph_bound_desc *d, const int32_t *d_labels, int64_t n_labels, int64_t n_groups,
                   int32_t *d_bound_labels, double *d_out, int64_t n_out, double *d_table, int64_t *d_counts);
 
+/* ---- spectral cubes: the optically thin position-position-velocity cube of the owned gas seen along any direction
+ *      (channel maps, position-velocity diagrams, line profiles; moments with summersph_amd/cube.py) ------------------
+ * Frame    rot[9], row-major: the rows are the image axes u^, v^ and the line of sight w^ (orthonormal and right-handed
+ *          within 1e-12, else SPH_ERR_ARG).  P_j = rot (r_j - centre), every row evaluated in the fixed order
+ *          ((a0 dx + a1 dy) + a2 dz) with no fused multiply-adds; V_j = w^ . (v_j - v_ref) in the same order.  w^ points
+ *          away from the observer: V > 0 is receding.
+ * Select   as sph_render_density: the owned gas particles (ghosts and sinks never) with clip_lo < r < clip_hi on every
+ *          axis of the SIMULATION frame (strict; -INFINITY / +INFINITY: no clip).  h > 0: one h for every particle; 0:
+ *          each particle's own h (SPH_F_H on a variable-h context, params.h on a fixed-h one).
+ * Nodes    node i on image axis a is lo[a] + i (hi[a] - lo[a]) / (n - 1), the last one exactly hi[a] (np.linspace);
+ *          n == 1: the single node lo[a].  Nodes are point-sampled, as in the renders.
+ * Footprint  the renders' cubic spline integrated along the line of sight analytically:
+ *          Y_j(b) = m_j A_j F(b / h_j) / (pi h_j^2), pi in double precision; A_j = values[id] (sph_count doubles in
+ *          sph_download_field's order; host memory for sph_cube, device memory for _dev) or 1 without values.
+ *          With p = b / h, r(t) = sqrt(p^2 + t^2), L(t) = p^2 ln(t + r) (0 at p == 0):
+ *            I1 = (t r + L) / 2,  I2 = p^2 t + t^3 / 3,  I3 = t r^3 / 4 + 3 p^2 t r / 8 + 3 p^2 L / 8
+ *            G_in(t) = t - 1.5 I2 + 0.75 I3,  G_out(t) = 2 t - 3 I1 + 1.5 I2 - 0.25 I3,  t1 = sqrt(1 - p^2), t2 = sqrt(4 - p^2)
+ *            F = 2 [G_in(t1) - G_in(0) + G_out(t2) - G_out(t1)]  (p < 1),  2 [G_out(t2) - G_out(0)]  (1 <= p < 2),  0  (p >= 2)
+ *          F(0) = 1.5 and the integral of F 2 p dp is 1: a particle's footprint integrates to its m A.
+ * Line     sigma_j = sqrt((sigma_scale c_j)^2 + sigma_floor^2), c_j the context's SPH_F_C (SPH_ERR_STATE exactly when
+ *          sph_download_field(SPH_F_C) would refuse, unless sigma_scale == 0).  Channel edges e_k = (k - 0.5) dv + v0,
+ *          k = 0 .. n_chan: channel k is centred on v0 + k dv.  With x = (e - V_j) / sigma_j:
+ *          cdf(x) = erf(x / sqrt 2) / 2 for |x| < 8.5 and exactly -1/2, +1/2 beyond (the truncation is part of the
+ *          definition: a particle's far channels get an exact +0.0 and are skipped).  sigma_j == 0: the particle goes into
+ *          the one channel with e_k <= V_j < e_{k+1}.
+ * Output   voxel[k][iu][iv] = sum_j Y_j(|node - P_j,uv|) (cdf_j(e_{k+1}) - cdf_j(e_k)), doubles in C order, n_chan n_u n_v
+ *          of them; SPH_CUBE_PER_VELOCITY divides by dv.  sph_cube copies it to host memory; sph_cube_dev leaves it in
+ *          device memory, ordered on the context's stream.
+ * Order    every voxel adds its terms in the (image-plane cell, particle id) order of the pass's own binning, which
+ *          depends only on the descriptor and the selected particles' h range: a repeated call, the host and the device
+ *          form are bitwise equal, and the result does not depend on the context's sorted order.
+ * Cost     two stream synchronisations (selection statistics, window size) + the copies of the host form.  No state,
+ *          statistic (other than device_bytes: the analysis scratch) or flag of the context changes.
+ * SPH_ERR_ARG: null descriptor or output, n_u, n_v or n_chan < 1, out_len != n_chan n_u n_v, lo > hi or non-finite, h < 0
+ * or non-finite, a NaN clip, a non-finite centre, v_ref or v0, dv <= 0 or non-finite, a negative or non-finite sigma_scale
+ * or sigma_floor, a bad rot, unknown flags, reserved != 0.  SPH_ERR_STATE: a stale c with sigma_scale > 0; a selected h <= 0
+ * or non-finite.  SPH_ERR_NOMEM: the scratch does not fit. */
+#define SPH_CUBE_PER_VELOCITY 1
+typedef struct sph_cube_desc {
+    double  rot[9];                 /* rows u^, v^, w^ (row-major)                                   */
+    double  centre[3], v_ref[3];    /* origin of the image plane, velocity of the reference frame    */
+    double  lo[2], hi[2];           /* node box on the image axes u, v                               */
+    double  clip_lo[3], clip_hi[3]; /* strict particle clip box (simulation axes); -/+INFINITY = none */
+    double  h;                      /* > 0: one h for all; 0: each particle's own h                  */
+    double  v0, dv;                 /* centre of channel 0, channel width (> 0)                      */
+    double  sigma_scale, sigma_floor; /* sigma_j = sqrt((sigma_scale c_j)^2 + sigma_floor^2), both >= 0 */
+    int32_t n_u, n_v;               /* image nodes per axis, each >= 1                               */
+    int32_t n_chan;                 /* channels, >= 1                                                */
+    int32_t flags;                  /* SPH_CUBE_PER_VELOCITY                                         */
+    int64_t reserved;               /* must be 0                                                     */
+} sph_cube_desc;                    /* 264 bytes */
+int sph_cube(sph_ctx *ctx, const sph_cube_desc *d, const double *values, double *host_out, int64_t out_len);
+int sph_cube_dev(sph_ctx *ctx, const sph_cube_desc *d, const double *d_values, double *d_out, int64_t out_len);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too

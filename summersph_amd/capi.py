@@ -50,6 +50,7 @@ SYMBOLS = [
     "sph_sample", "sph_sample_dev",
     "sph_gravity_at", "sph_gravity_at_dev",
     "sph_bound", "sph_bound_dev",
+    "sph_cube", "sph_cube_dev",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
@@ -84,6 +85,8 @@ GRAVAT_GAS = 1
 GRAVAT_SINKS = 2
 GRAVAT_SPLIT = 4
 GRAVAT_REF_SOFT2 = 0.001 * 2.5      # the force walk's softening term (0.001_dp * smoothing)
+CUBE_PER_VELOCITY = 1
+CUBE_CHUNK = 32               # channels per workgroup of cube_gather (csrc/cube.hip, CUBE_CHUNK): more run in several chunks
 BOUND_THERMAL = 1
 BOUND_NCOL = 24
 # sph_bound's table columns (include/summersph.h, "Outputs"): S_0's, the last evaluated set's, the outcome
@@ -243,6 +246,37 @@ def bound_desc(h=None, soft2=GRAVAT_REF_SOFT2, thermal=False, max_rounds=0, min_
     d.soft2 = float(soft2)
     d.min_members, d.max_members, d.max_rounds = int(min_members), int(max_members), int(max_rounds)
     d.flags = BOUND_THERMAL if thermal else 0
+    return d
+
+
+class CubeDesc(C.Structure):
+    """sph_cube_desc (include/summersph.h): rot (rows u^, v^, w^), centre, v_ref, image node box, strict clip box, h, channel 0's
+    centre and the channel width, sigma_scale, sigma_floor, image nodes, channels, flags (CUBE_PER_VELOCITY), reserved"""
+    _fields_ = [("rot", C.c_double * 9), ("centre", C.c_double * 3), ("v_ref", C.c_double * 3), ("lo", C.c_double * 2),
+                ("hi", C.c_double * 2), ("clip_lo", C.c_double * 3), ("clip_hi", C.c_double * 3), ("h", C.c_double),
+                ("v0", C.c_double), ("dv", C.c_double), ("sigma_scale", C.c_double), ("sigma_floor", C.c_double),
+                ("n_u", C.c_int32), ("n_v", C.c_int32), ("n_chan", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int64)]
+
+
+def cube_desc(shape, bounds, v0, dv, n_chan, rot=None, centre=(0.0, 0.0, 0.0), v_ref=(0.0, 0.0, 0.0), sigma_scale=0.0,
+              sigma_floor=0.0, h=None, clip=None, per_velocity=False) -> CubeDesc:
+    """The descriptor of Context.cube's arguments (see there)."""
+    n = (int(shape),) * 2 if np.isscalar(shape) else tuple(int(v) for v in shape)
+    if len(n) != 2:
+        raise ValueError("shape: one node count or (n_u, n_v)")
+    d = CubeDesc()
+    d.rot[:] = np.asarray(np.eye(3) if rot is None else rot, dtype=np.float64).reshape(9).tolist()
+    d.centre[:] = [float(v) for v in centre]
+    d.v_ref[:] = [float(v) for v in v_ref]
+    b = np.asarray(bounds, dtype=np.float64).reshape(2, 2)
+    d.lo[:] = b[0].tolist(); d.hi[:] = b[1].tolist()
+    cb = np.array([[-np.inf] * 3, [np.inf] * 3]) if clip is None else np.asarray(clip, dtype=np.float64).reshape(2, 3)
+    d.clip_lo[:] = cb[0].tolist(); d.clip_hi[:] = cb[1].tolist()
+    d.h = 0.0 if h is None else float(h)
+    d.v0, d.dv, d.n_chan = float(v0), float(dv), int(n_chan)
+    d.sigma_scale, d.sigma_floor = float(sigma_scale), float(sigma_floor)
+    d.n_u, d.n_v = n
+    d.flags = CUBE_PER_VELOCITY if per_velocity else 0
     return d
 
 
@@ -451,6 +485,8 @@ def load():
                               C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
     lib.sph_bound_dev.argtypes = [C.c_void_p, C.POINTER(BoundDesc), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                   C.c_int64, C.c_void_p, C.c_void_p]
+    for fn in (lib.sph_cube, lib.sph_cube_dev):
+        fn.argtypes = [C.c_void_p, C.POINTER(CubeDesc), C.c_void_p, C.c_void_p, C.c_int64]
     _lib = lib
     return lib
 
@@ -1098,6 +1134,46 @@ class Context:
             return w
         parts = [out] + ([w] if want_w else []) + ([cn] if counts else [])
         return parts[0] if len(parts) == 1 else tuple(parts)
+
+    # ---- spectral cubes (sph_cube) -----------------------------------------------------------------
+    def cube(self, shape, bounds, v0, dv, n_chan, rot=None, centre=(0.0, 0.0, 0.0), v_ref=(0.0, 0.0, 0.0), sigma_scale=0.0,
+             sigma_floor=0.0, values=None, h=None, clip=None, per_velocity=False, device=False):
+        """The optically thin position-position-velocity cube of the owned gas (include/summersph.h, sph_cube), shape
+        (n_chan, n_u, n_v).  shape: image nodes (n or (n_u, n_v)) on the np.linspace node box bounds = ((lo_u, lo_v), (hi_u,
+        hi_v)); rot: the 3 x 3 matrix with rows u^, v^, w^ (summersph_amd.cube.view; None = the identity: looking down z);
+        channel k is centred on v0 + k dv; sigma_j = sqrt((sigma_scale c_j)^2 + sigma_floor^2); values: None (A = 1: the
+        column of mass per channel) or sph_count() numbers in the upload order -- float64 numpy (device=False) or a
+        contiguous float64 torch tensor on the context's GPU (device=True); h, clip: as render_density; per_velocity:
+        divide by dv.  Returns float64 numpy or, device=True, a torch tensor (sph_cube_dev).  The descriptor used is left
+        in self.cube_desc."""
+        d = cube_desc(shape, bounds, v0, dv, n_chan, rot, centre, v_ref, sigma_scale, sigma_floor, h, clip, per_velocity)
+        self.cube_desc = d
+        oshape = (d.n_chan, d.n_u, d.n_v)
+        size = int(np.prod(oshape, dtype=np.int64)) if min(oshape) > 0 else 0
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if values is not None and not (isinstance(values, torch.Tensor) and values.dtype == torch.float64 and
+                                           values.is_contiguous() and values.device == dev and values.numel() == self.n):
+                raise ValueError("cube: device values must be a contiguous float64 tensor of sph_count() on the context's GPU")
+            out = torch.empty([max(v, 0) for v in oshape], dtype=torch.float64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()          # the blocks and values may still be in use by torch's work
+            self._ck(self.lib.sph_cube_dev(self._h, C.byref(d), None if values is None else C.c_void_p(values.data_ptr()),
+                                           C.c_void_p(out.data_ptr()), size))
+            st = self.stream()                                    # torch's later work on `out` waits for the cube
+            if st:
+                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
+            else:
+                torch.cuda.synchronize(dev)
+        else:
+            v = None
+            if values is not None:
+                v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+                if v.size != self.n:
+                    raise ValueError(f"cube: {v.size} values for {self.n} particles")
+            out = np.empty([max(v_, 0) for v_ in oshape], dtype=np.float64)
+            self._ck(self.lib.sph_cube(self._h, C.byref(d), None if v is None else v.ctypes.data, out.ctypes.data, size))
+        return out
 
     # ---- potential and acceleration at arbitrary points (sph_gravity_at) ---------------------------
     def gravity_at(self, points, h=None, ph=None, soft2=GRAVAT_REF_SOFT2, gas=True, sinks=True, split=False, counts=False,

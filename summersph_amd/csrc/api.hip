@@ -1327,6 +1327,18 @@ int sph_bound_dev(sph_ctx *c, const sph_bound_desc *d, const int32_t *d_labels, 
     return bound_run(c, d, d_labels, n_labels, n_groups, d_bound_labels, d_out, n_out, d_table, d_counts, false);
 }
 
+int sph_cube(sph_ctx *c, const sph_cube_desc *d, const double *values, double *host_out, int64_t out_len) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return cube_run(c, d, values, host_out, out_len, true, field_ready);
+}
+
+int sph_cube_dev(sph_ctx *c, const sph_cube_desc *d, const double *d_values, double *d_out, int64_t out_len) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return cube_run(c, d, d_values, d_out, out_len, false, field_ready);
+}
+
 int sph_synchronize(sph_ctx *c) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);

@@ -448,5 +448,9 @@ int gravity_at_run(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_points, c
 // device form (all device memory, no synchronisation)
 int bound_run(sph_ctx *c, const sph_bound_desc *d, const int32_t *labels, int64_t n_labels, int64_t n_groups,
               int32_t *bound_labels, double *out, int64_t n_out, double *table, int64_t *counts, bool host);
+// position-position-velocity cubes (cube.hip): host form (values / out host memory, two read-backs + the copy out) or device
+// form; ready = sph_download_field's rule
+int cube_run(sph_ctx *c, const sph_cube_desc *d, const double *values, double *out, int64_t out_len, bool host,
+             bool (*ready)(const sph_ctx *, int));
 
 }  // namespace sph

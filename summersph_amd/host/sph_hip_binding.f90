@@ -48,6 +48,8 @@ module sph_hip_binding
   public :: sph_gravity_at_desc, sph_gravity_at, sph_gravity_at_dev, SPH_GRAVAT_GAS, SPH_GRAVAT_SINKS, SPH_GRAVAT_SPLIT
   ! binding energies and unbinding of groups (each group's own potential, the members' energies, the bound core)
   public :: sph_bound_desc, sph_bound, sph_bound_dev, SPH_BOUND_THERMAL, SPH_BOUND_NCOL
+  ! spectral cubes (the optically thin position-position-velocity cube of the owned gas seen along any direction)
+  public :: sph_cube_desc, sph_cube, sph_cube_dev, SPH_CUBE_PER_VELOCITY
   public :: c_message
 
   integer(c_int), parameter :: SPH_OK = 0
@@ -178,6 +180,24 @@ module sph_hip_binding
     integer(c_int32_t) :: max_rounds, flags
     integer(c_int32_t) :: reserved(2)
   end type sph_bound_desc
+
+  ! sph_cube: rot (row-major in C: rot(1:3) = u^, rot(4:6) = v^, rot(7:9) = w^, the line of sight, away from the observer),
+  ! centre, v_ref, image node box lo / hi (u, v), strict clip box (simulation axes; +-infinity: none), h (> 0: one h for all;
+  ! 0: each particle's own), v0 (centre of channel 0), dv (channel width, > 0), sigma_scale, sigma_floor (sigma_j =
+  ! sqrt((sigma_scale c_j)^2 + sigma_floor^2)), n_u, n_v, n_chan, flags (SPH_CUBE_PER_VELOCITY), reserved (0).  out holds
+  ! out(iv, iu, k) in Fortran order: (n_v, n_u, n_chan).  264 bytes.
+  integer(c_int32_t), parameter :: SPH_CUBE_PER_VELOCITY = 1
+  type, bind(C) :: sph_cube_desc
+    real(c_double) :: rot(9)
+    real(c_double) :: centre(3), v_ref(3)
+    real(c_double) :: lo(2), hi(2)
+    real(c_double) :: clip_lo(3), clip_hi(3)
+    real(c_double) :: h
+    real(c_double) :: v0, dv
+    real(c_double) :: sigma_scale, sigma_floor
+    integer(c_int32_t) :: n_u, n_v, n_chan, flags
+    integer(c_int64_t) :: reserved
+  end type sph_cube_desc
 
   interface
     integer(c_int) function sph_abi_version() bind(C, name='sph_abi_version')
@@ -688,6 +708,20 @@ module sph_hip_binding
       type(c_ptr), value :: ctx, d_labels, d_bound_labels, d_out, d_table, d_counts
       type(sph_bound_desc), intent(in) :: d
       integer(c_int64_t), value :: n_labels, n_groups, n_out
+    end function
+    ! ---- spectral cubes: values (sph_count doubles in the download order, or c_null_ptr: A = 1), host_out (n_chan n_u n_v
+    !      doubles, C order [k][iu][iv]), out_len = n_chan n_u n_v
+    integer(c_int) function sph_cube(ctx, d, values, host_out, out_len) bind(C, name='sph_cube')
+      import :: c_int, c_int64_t, c_ptr, sph_cube_desc
+      type(c_ptr), value :: ctx, values, host_out
+      type(sph_cube_desc), intent(in) :: d
+      integer(c_int64_t), value :: out_len
+    end function
+    integer(c_int) function sph_cube_dev(ctx, d, d_values, d_out, out_len) bind(C, name='sph_cube_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_cube_desc
+      type(c_ptr), value :: ctx, d_values, d_out
+      type(sph_cube_desc), intent(in) :: d
+      integer(c_int64_t), value :: out_len
     end function
   end interface
 
