@@ -935,6 +935,65 @@ typedef struct sph_cube_desc {
 int sph_cube(sph_ctx *ctx, const sph_cube_desc *d, const double *values, double *host_out, int64_t out_len);
 int sph_cube_dev(sph_ctx *ctx, const sph_cube_desc *d, const double *d_values, double *d_out, int64_t out_len);
 
+/* ---- the rates of sph_forces split by physical term: which term moves angular momentum at a radius (torque by term per
+ *      ring), where the artificial viscosity heats the gas (a shock-heating map through sph_render_field), how large the
+ *      numerical dissipation is beside the PdV work ----------------------------------------------------------------------
+ * Definition  the acceleration, du/dt and dalpha/dt that sph_forces would write now, with every sum taken apart where the
+ *          force pass folds terms together: the pair accumulator m_j ((P_i/rho_i^2 + P_j/rho_j^2) + Pi_ij) of [F]:381-383
+ *          ([V]:413-416), the factor (P_i/rho_i^2 + Pi_ij/2) of [F]:387 ([V]:419-421), the start value of the acceleration
+ *          (self-gravity, then the sinks) and the two addends of the alpha rate.  Every quantity is read from the context's
+ *          force records exactly as sph_forces would read them; the state required is that of sph_forces (the grid, the list
+ *          and the density current, the EOS valid), else SPH_ERR_STATE "call sph_density first" -- after sph_step call
+ *          sph_density first, the closing kick made the records stale.
+ * Targets  the owned gas (original ids < n_owned).  The rows of ghosts are NaN.
+ * Sources  whatever the target's neighbour list holds, ghosts included; the sinks; the gravity sources of sph_forces (the
+ *          context's own particles, or the external set of sph_set_gravity_sources_dev).
+ * Rows     out[row * n + id], n = sph_count, n_out == SPH_TERMS_NROW * n, id in sph_download_field's order: every row is a
+ *          contiguous array that sph_render_field accepts as values.  g: the normalised kernel gradient the force pass uses
+ *          for the pair, v_ij = v_i - v_j, Pi_ij: the force pass's visc (vdotr = min(v.r, 0), visc_eps, the halved records
+ *          and the reciprocal helpers of the force pass).
+ *            0-2   a_P   pressure gradient      fixed h -sum m_j (P_i/rho_i^2 + P_j/rho_j^2) g         [F]:381-383
+ *                                               variable h -sum m_j (C_i g_i + C_j g_j), C = P/(Omega rho^2)   [V]:413-416
+ *            3-5   a_V   artificial viscosity   fixed h -sum m_j Pi_ij g                               [F]:373-383
+ *                                               variable h -sum m_j Pi_ij (g_i + g_j)/2                [V]:405-416
+ *            6-8   a_S   sink gravity on the gas: the force pass's sink loop ([F]:567-576, [V]:691-), started from 0
+ *            9-11  a_G   gas self-gravity: with SPH_FLAG_SELF_GRAVITY the Barnes-Hut term sph_forces starts its sums from
+ *                        ([F]:825) -- the same tree, walk and acceptance test, written here and not to SPH_F_AX..AZ; +0.0
+ *                        without self-gravity; NaN with SPH_TERMS_SKIP_GAS_GRAVITY (no tree is built or walked)
+ *            12    du_P  PdV work               sum m_j (v_ij . g) P_i/rho_i^2 (variable h: C_i)       [F]:387, [V]:419-421
+ *            13    du_V  viscous heating        sum m_j (v_ij . g) Pi_ij/2: every pair term is >= 0    [F]:387, [V]:419-421
+ *            14    alpha source                 max(sum m_j (v_ij . g) / rho_i, 0)                     [F]:316-318,390, [V]:346,427
+ *            15    alpha decay                  alpha_decay (alpha_floor - alpha_i) c_i / h_i          [F]:316-318, [V]:346
+ *          Rows 0-11 summed per axis are SPH_F_AX..AZ, rows 12 + 13 SPH_F_DU and rows 14 + 15 SPH_F_DALPHA of sph_forces, to
+ *          rounding.  A coincident pair (r == 0) and a pair beyond the support add exact zeros, as in the force pass; the
+ *          table normalisation 1 / (pi h^4) is applied once at the end ([F]:126).  a_P and a_V are pairwise antisymmetric
+ *          at fixed h: without ghosts sum m a and sum m r x a of either vanish to rounding, and so do sum m (v . a_P + du_P)
+ *          and sum m (v . a_V + du_V).
+ * Order    a target's sums run over its neighbour list in list order, so they depend on the context's sorted order and its
+ *          list layout: repeated calls, the host and device forms, and calls before and after an intervening sph_forces agree
+ *          bitwise; different contexts (another slot order, flags that change the list) agree to rounding only -- unlike the
+ *          (cell, id)-ordered analysis calls above.  No float atomics.
+ * cost     one gather pass over the lists (the memory traffic of the gather force kernel; a 128-byte record per slot) and a
+ *          pass that turns the records into rows, plus the tree walk when rows 9-11 are asked for; with self-gravity and no
+ *          valid tree in place the tree sph_forces would build is built and KEPT (the next sph_forces uses it: the same tree,
+ *          bit for bit).  Scratch (16 n doubles, + 3 n with the walk) from the analysis calls' shared buffer.  Host form: one
+ *          synchronisation, then the copy is complete; device form: ordered on the
+ *          context's stream, no synchronisation (but one when the scratch has to grow).  No field (SPH_F_AX..DALPHA
+ *          included, bitwise), list, grid, flag, dt, validity of a field or statistic (other than device_bytes) changes;
+ *          force_passes does not move; a run that calls sph_density and this between the steps is bitwise the run that calls
+ *          sph_density alone.
+ * SPH_ERR_ARG: null descriptor, n_out != SPH_TERMS_NROW * sph_count, null output with n > 0, unknown flags, reserved != 0;
+ * nothing is written then.  n == 0 succeeds and writes nothing.  SPH_ERR_STATE: see Definition.  SPH_ERR_NOMEM: the scratch
+ * does not fit. */
+#define SPH_TERMS_NROW 16
+#define SPH_TERMS_SKIP_GAS_GRAVITY 1   /* do not walk the tree: rows 9..11 are NaN */
+typedef struct sph_force_terms_desc {
+    int32_t flags;        /* SPH_TERMS_* */
+    int32_t reserved[3];  /* must be 0 */
+} sph_force_terms_desc;   /* 16 bytes */
+int sph_force_terms(sph_ctx *ctx, const sph_force_terms_desc *d, double *host_out, int64_t n_out);
+int sph_force_terms_dev(sph_ctx *ctx, const sph_force_terms_desc *d, double *d_out, int64_t n_out);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too

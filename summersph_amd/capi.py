@@ -51,6 +51,7 @@ SYMBOLS = [
     "sph_gravity_at", "sph_gravity_at_dev",
     "sph_bound", "sph_bound_dev",
     "sph_cube", "sph_cube_dev",
+    "sph_force_terms", "sph_force_terms_dev",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
@@ -87,6 +88,12 @@ GRAVAT_SPLIT = 4
 GRAVAT_REF_SOFT2 = 0.001 * 2.5      # the force walk's softening term (0.001_dp * smoothing)
 CUBE_PER_VELOCITY = 1
 CUBE_CHUNK = 32               # channels per workgroup of cube_gather (csrc/cube.hip, CUBE_CHUNK): more run in several chunks
+TERMS_NROW = 16
+TERMS_SKIP_GAS_GRAVITY = 1
+# sph_force_terms' rows (include/summersph.h, "Rows"): pressure gradient, artificial viscosity, sink gravity, gas
+# self-gravity, PdV work, viscous heating, the two addends of the alpha rate
+TERM_ROWS = ["aP_x", "aP_y", "aP_z", "aV_x", "aV_y", "aV_z", "aS_x", "aS_y", "aS_z", "aG_x", "aG_y", "aG_z",
+             "du_P", "du_V", "dalpha_source", "dalpha_decay"]
 BOUND_THERMAL = 1
 BOUND_NCOL = 24
 # sph_bound's table columns (include/summersph.h, "Outputs"): S_0's, the last evaluated set's, the outcome
@@ -237,6 +244,11 @@ class BoundDesc(C.Structure):
     max_rounds (0: evaluate once), flags (BOUND_THERMAL), reserved"""
     _fields_ = [("h", C.c_double), ("soft2", C.c_double), ("min_members", C.c_int64), ("max_members", C.c_int64),
                 ("max_rounds", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class ForceTermsDesc(C.Structure):
+    """sph_force_terms_desc (include/summersph.h): flags (TERMS_*), reserved"""
+    _fields_ = [("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 def bound_desc(h=None, soft2=GRAVAT_REF_SOFT2, thermal=False, max_rounds=0, min_members=1, max_members=2**31 - 1) -> BoundDesc:
@@ -487,6 +499,8 @@ def load():
                                   C.c_int64, C.c_void_p, C.c_void_p]
     for fn in (lib.sph_cube, lib.sph_cube_dev):
         fn.argtypes = [C.c_void_p, C.POINTER(CubeDesc), C.c_void_p, C.c_void_p, C.c_int64]
+    for fn in (lib.sph_force_terms, lib.sph_force_terms_dev):
+        fn.argtypes = [C.c_void_p, C.POINTER(ForceTermsDesc), C.c_void_p, C.c_int64]
     _lib = lib
     return lib
 
@@ -1173,6 +1187,34 @@ class Context:
                     raise ValueError(f"cube: {v.size} values for {self.n} particles")
             out = np.empty([max(v_, 0) for v_ in oshape], dtype=np.float64)
             self._ck(self.lib.sph_cube(self._h, C.byref(d), None if v is None else v.ctypes.data, out.ctypes.data, size))
+        return out
+
+    # ---- the rates split by physical term (sph_force_terms) -----------------------------------------
+    def force_terms(self, skip_gas_gravity=False, device=False, refresh=False):
+        """The rates sph_forces would write now, split by term (include/summersph.h, sph_force_terms): a (16, n) array whose
+        rows are TERM_ROWS, n = sph_count(), columns in the upload order; ghosts' columns are NaN.  The context must be in
+        the state sph_forces needs; refresh=True calls density() first (after a step the records are stale).
+        skip_gas_gravity: rows 9-11 are NaN and no tree is walked.  Returns float64 numpy or, device=True, a torch tensor on
+        the context's GPU (sph_force_terms_dev).  Every row is a contiguous array that render_field accepts as values."""
+        if refresh:
+            self.density()
+        d = ForceTermsDesc()
+        d.flags = TERMS_SKIP_GAS_GRAVITY if skip_gas_gravity else 0
+        n = self.n
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            out = torch.empty((TERMS_NROW, n), dtype=torch.float64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()          # the block may still be in use by torch's queued work
+            self._ck(self.lib.sph_force_terms_dev(self._h, C.byref(d), C.c_void_p(out.data_ptr()), TERMS_NROW * n))
+            st = self.stream()                                    # torch's later work on `out` waits for the pass
+            if st:
+                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
+            else:
+                torch.cuda.synchronize(dev)
+        else:
+            out = np.empty((TERMS_NROW, n), dtype=np.float64)
+            self._ck(self.lib.sph_force_terms(self._h, C.byref(d), out.ctypes.data, TERMS_NROW * n))
         return out
 
     # ---- potential and acceleration at arbitrary points (sph_gravity_at) ---------------------------

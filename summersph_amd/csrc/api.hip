@@ -1339,6 +1339,18 @@ int sph_cube_dev(sph_ctx *c, const sph_cube_desc *d, const double *d_values, dou
     return cube_run(c, d, d_values, d_out, out_len, false, field_ready);
 }
 
+int sph_force_terms(sph_ctx *c, const sph_force_terms_desc *d, double *host_out, int64_t n_out) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return force_terms_run(c, d, host_out, n_out, true);
+}
+
+int sph_force_terms_dev(sph_ctx *c, const sph_force_terms_desc *d, double *d_out, int64_t n_out) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return force_terms_run(c, d, d_out, n_out, false);
+}
+
 int sph_synchronize(sph_ctx *c) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);

@@ -732,7 +732,10 @@ hipError_t launch_field_points(sph_ctx *c, int64_t n_src, int64_t m, const doubl
     return hipGetLastError();
 }
 
-hipError_t launch_gravity(sph_ctx *c) {
+// ax, ay, az: where the term goes, slot order (null: the context's SPH_F_AX..AZ, what sph_forces continues from;
+// sph_force_terms gives its own scratch and leaves the fields alone)
+hipError_t launch_gravity(sph_ctx *c, double *ax, double *ay, double *az) {
+    if (!ax) { ax = c->f[SPH_F_AX]; ay = c->f[SPH_F_AY]; az = c->f[SPH_F_AZ]; }
     const bool ext = c->gx_src != nullptr;
     const int64_t nt = c->n;                     // targets: the context's slots
     const int64_t n = ext ? c->gx_n : c->n;      // leaves of the tree
@@ -754,7 +757,7 @@ hipError_t launch_gravity(sph_ctx *c) {
         walk<<<dim3((unsigned)((nt + GB - 1) / GB)), dim3(GB), 0, c->stream>>>(
             (int)nt, (int)n, reinterpret_cast<const WalkRec *>(c->g_wrec), ta.leafA, reinterpret_cast<const double4 *>(c->drec),
             ext ? nullptr : c->g_leaf_of, c->variable ? c->f[SPH_F_H] : nullptr, c->p.h, soft2,
-            c->p.theta, c->p.G, c->grav_tab, c->p.nq, 2.0 / c->p.nq, c->f[SPH_F_AX], c->f[SPH_F_AY], c->f[SPH_F_AZ], c->orig,
+            c->p.theta, c->p.G, c->grav_tab, c->p.nq, 2.0 / c->p.nq, ax, ay, az, c->orig,
             (int32_t)c->n_owned, stats, rb.size);
         if (stats) {
             unsigned long long h[18] = {0};
@@ -771,7 +774,7 @@ hipError_t launch_gravity(sph_ctx *c) {
     }
     grav_walk<<<dim3((unsigned)((n + GB - 1) / GB)), dim3(GB), 0, c->stream>>>(
         (int)n, tree_arrays(c), rb, reinterpret_cast<const double4 *>(c->drec), c->variable ? c->f[SPH_F_H] : nullptr, c->p.h, soft2,
-        c->p.theta, c->p.G, c->grav_tab, c->p.nq, 2.0 / c->p.nq, c->f[SPH_F_AX], c->f[SPH_F_AY], c->f[SPH_F_AZ], c->orig,
+        c->p.theta, c->p.G, c->grav_tab, c->p.nq, 2.0 / c->p.nq, ax, ay, az, c->orig,
         (int32_t)c->n_owned);
     return hipGetLastError();
 }

@@ -218,6 +218,10 @@ __device__ __forceinline__ void table_lerp2(const double *__restrict__ tw, const
 
 // ---- the pair terms, written ONCE (pairs.hip, tiled.hip and varh.hip all call these) -----------------------------------
 
+// an entry of the variable-h neighbour list (varh.hip): the neighbour's sorted index and what the pair counts for -- D: j is in
+// the target's density set, F: {i, j} is a force pair, R: the target's walk reaches j's leaf
+constexpr uint32_t FLAG_D = 0x80000000u, FLAG_F = 0x40000000u, FLAG_R = 0x20000000u, IDX_MASK = 0x1fffffffu;
+
 // force gather record (FREC doubles): A = x y z m | B = vx vy vz rho/2 | C = c/2  alpha/2  P/rho^2  h
 // (halved values: 0.5*(a_i + a_j) == a_i/2 + a_j/2 exactly, which saves three multiplies per pair; variable h stores
 // P/(Omega rho^2) in C.z, Variable.f90:413, and its h in C.w)

@@ -119,30 +119,7 @@ __global__ __launch_bounds__(1024) void max_to_host(const int32_t *__restrict__ 
 // ------------------------------------------------------------------------------------------
 // density + EOS
 // ------------------------------------------------------------------------------------------
-// entry k of a lane's list -> sorted index of the neighbour.  PACKED = false: wave-strided dwords holding the index itself
-// (nlist_kernel).  PACKED = true: the 16-bit tile slots of the tiled build (tile_common.hpp), turned into an index with the
-// plan of the lane's group of 256.  Both are read in lockstep.
-template <bool PACKED>
-struct ListColumn {
-    const int32_t *m32;
-    const uint16_t *m16;
-    EntryMap em;
-    __device__ __forceinline__ ListColumn(const int32_t *nlist, const int32_t *plan_f, int64_t w, int32_t cap, int lane, int self) {
-        if (PACKED) {
-            m32 = nullptr;
-            m16 = reinterpret_cast<const uint16_t *>(nlist) + (((size_t)w * (cap >> 3)) * 64 + lane) * 8;
-            em = entry_to_index(plan_f, __builtin_amdgcn_readfirstlane(self >> 8));
-        } else {
-            m32 = nlist + ((size_t)w * cap) * 64 + lane;
-            m16 = nullptr;
-            em = EntryMap{0, 0, 0, 0, 0};
-        }
-    }
-    __device__ __forceinline__ int operator()(int k) const {
-        return PACKED ? em((int)m16[(size_t)(k >> 3) * 512 + ent_pos(k & 7)]) : m32[(size_t)k * 64];
-    }
-};
-
+// (ListColumn: entry k of a lane's list -> sorted index of the neighbour, tile_common.hpp)
 template <int BLOCK, bool PACKED>
 __global__ __launch_bounds__(BLOCK) void density_kernel(PairConst pc, const double4 *__restrict__ drec,
                                                         const int32_t *__restrict__ nlist, int32_t cap,

@@ -378,7 +378,7 @@ hipError_t grav_sort_tmp_bytes(int64_t n, size_t *bytes);
 int gravity_tree_build(sph_ctx *c);
 int global_keys_sorted(sph_ctx *c);      // sorted path keys of the external source set -> c->g_keys_alt / g_vals_alt
 void gravity_free(sph_ctx *c);
-hipError_t launch_gravity(sph_ctx *c);
+hipError_t launch_gravity(sph_ctx *c, double *ax = nullptr, double *ay = nullptr, double *az = nullptr);   // null: SPH_F_AX..AZ
 // sph_energy (gravity.hip): the tree over caller-order {x,y,z,m} records and their box, built into the context's tree
 // arrays (clears tree_valid, grav_valid, gx_keys_valid), and the potential walk over the tree in place
 int gravity_tree_build_records(sph_ctx *c, const double *rec, int64_t n, const double box[6]);
@@ -452,5 +452,7 @@ int bound_run(sph_ctx *c, const sph_bound_desc *d, const int32_t *labels, int64_
 // form; ready = sph_download_field's rule
 int cube_run(sph_ctx *c, const sph_cube_desc *d, const double *values, double *out, int64_t out_len, bool host,
              bool (*ready)(const sph_ctx *, int));
+// the rates of sph_forces split by term (terms.hip): host form (out host memory, one synchronisation) or device form
+int force_terms_run(sph_ctx *c, const sph_force_terms_desc *d, double *out, int64_t n_out, bool host);
 
 }  // namespace sph

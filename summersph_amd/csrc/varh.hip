@@ -37,7 +37,7 @@ namespace {
 
 constexpr int VBLOCK = 256;
 constexpr int LEVELS = 21;            // 63-bit path keys
-constexpr uint32_t FLAG_D = 0x80000000u, FLAG_F = 0x40000000u, FLAG_R = 0x20000000u, IDX_MASK = 0x1fffffffu;
+// (FLAG_D, FLAG_F, FLAG_R, IDX_MASK: the bits of a list entry, pair_common.hpp)
 // calc_smoothing re-evaluates rho with a trial length h' > h: the list also keeps (behind the D/F entries, from the
 // last row of the lane's column downwards) the particles whose leaf the body's walk reaches within 2 h (1 + margin)
 constexpr double H_MARGIN = 1.1;

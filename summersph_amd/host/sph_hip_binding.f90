@@ -50,6 +50,8 @@ module sph_hip_binding
   public :: sph_bound_desc, sph_bound, sph_bound_dev, SPH_BOUND_THERMAL, SPH_BOUND_NCOL
   ! spectral cubes (the optically thin position-position-velocity cube of the owned gas seen along any direction)
   public :: sph_cube_desc, sph_cube, sph_cube_dev, SPH_CUBE_PER_VELOCITY
+  ! the rates of sph_forces split by physical term (pressure, viscosity, sink gravity, self-gravity, PdV, heating, alpha)
+  public :: sph_force_terms_desc, sph_force_terms, sph_force_terms_dev, SPH_TERMS_NROW, SPH_TERMS_SKIP_GAS_GRAVITY
   public :: c_message
 
   integer(c_int), parameter :: SPH_OK = 0
@@ -198,6 +200,15 @@ module sph_hip_binding
     integer(c_int32_t) :: n_u, n_v, n_chan, flags
     integer(c_int64_t) :: reserved
   end type sph_cube_desc
+
+  ! sph_force_terms: flags (SPH_TERMS_SKIP_GAS_GRAVITY: rows 9-11 are NaN, no tree walk), reserved (0).  out holds
+  ! out(id, row) in Fortran order: (sph_count, SPH_TERMS_NROW), rows a_P(3) a_V(3) a_S(3) a_G(3) du_P du_V and the source and
+  ! decay parts of dalpha/dt.  16 bytes.
+  integer(c_int32_t), parameter :: SPH_TERMS_NROW = 16, SPH_TERMS_SKIP_GAS_GRAVITY = 1
+  type, bind(C) :: sph_force_terms_desc
+    integer(c_int32_t) :: flags
+    integer(c_int32_t) :: reserved(3)
+  end type sph_force_terms_desc
 
   interface
     integer(c_int) function sph_abi_version() bind(C, name='sph_abi_version')
@@ -722,6 +733,20 @@ module sph_hip_binding
       type(c_ptr), value :: ctx, d_values, d_out
       type(sph_cube_desc), intent(in) :: d
       integer(c_int64_t), value :: out_len
+    end function
+    ! ---- the rates split by term: host_out / d_out (SPH_TERMS_NROW sph_count doubles, C order [row][id]), n_out = their number;
+    !      the state sph_forces needs (after sph_step: call sph_density first)
+    integer(c_int) function sph_force_terms(ctx, d, host_out, n_out) bind(C, name='sph_force_terms')
+      import :: c_int, c_int64_t, c_ptr, sph_force_terms_desc
+      type(c_ptr), value :: ctx, host_out
+      type(sph_force_terms_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_out
+    end function
+    integer(c_int) function sph_force_terms_dev(ctx, d, d_out, n_out) bind(C, name='sph_force_terms_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_force_terms_desc
+      type(c_ptr), value :: ctx, d_out
+      type(sph_force_terms_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_out
     end function
   end interface
 
