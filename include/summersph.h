@@ -39,7 +39,16 @@ enum sph_status {
     SPH_ERR_NO_DEVICE = 2,    /* no HIP device / device index out of range                */
     SPH_ERR_HIP = 3,          /* a HIP runtime call failed (text in sph_last_error)       */
     SPH_ERR_NOMEM = 4,        /* device or host allocation failed                         */
-    SPH_ERR_STATE = 5,        /* call order violated (e.g. forces before density)         */
+    SPH_ERR_STATE = 5,        /* call order violated (e.g. forces before density).  Also the fixed-h list overflow: a
+                                 build reads the PREVIOUS build's reports, so a neighbour list that outgrows its
+                                 third of headroom between two builds is reported one build late -- by the next
+                                 sph_density / sph_step / sph_run, or at the end of the call that returns (every
+                                 call that waits for the stream: sph_step, sph_run, sph_download_field, sph_get_stats)
+                                 -- never as truncated sums handed out.  The sums of that build were incomplete and
+                                 the context cannot tell what was integrated from them, so from then on
+                                 sph_density, sph_forces, sph_step and sph_run return SPH_ERR_STATE and the derived
+                                 fields are stale, until sph_upload brings a new particle set (sph_upload_field
+                                 does not lift the refusal, whichever fields it rewrites)                  */
     SPH_ERR_GRID = 6,         /* no cell grid possible: a non-finite box, or one axis needs more than 2^21
                                  cells of edge 2h (2 <h>) even after the 6-sigma trim (a hashed grid holds
                                  any box up to that; a dense one up to 2^31 cells)        */

@@ -615,6 +615,8 @@ class Context:
 
     # ---- hot path ------------------------------------------------------------------------
     def density(self):
+        """density, forces, step and run raise SphError (SPH_ERR_STATE) after a fixed-h list overflow was reported, until the
+        next upload (include/summersph.h, SPH_ERR_STATE)"""
         self._ck(self.lib.sph_density(self._h))
 
     def forces(self):

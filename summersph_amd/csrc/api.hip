@@ -171,6 +171,13 @@ bool use_tile_kernel(const sph_ctx *c, bool forces) {
 
 int do_density(sph_ctx *c) {
     static const bool no_refresh = getenv("SPH_NO_H_REFRESH") != nullptr;      // A/B switch
+    if (c->nl_overflowed) {
+        // drain_reports cleared the stale report along with the validity flags, so the next build would wait for its own, regrow
+        // and go on -- inside sph_step / sph_run from velocities that the truncated sums kicked.  The context cannot tell whether
+        // the caller integrated anything from the incomplete sums, so it refuses in every case (include/summersph.h, SPH_ERR_STATE)
+        c->err = "neighbour list overflowed in an earlier build: the state is incomplete, upload the particle set again";
+        return SPH_ERR_STATE;
+    }
     if (!no_refresh && !c->grid_valid && c->variable && c->h_refresh_ok && c->order_valid && c->leaf_valid && c->n_slots == c->n) {
         // same positions, same particles, new h (calc_smoothing, Variable.f90:1152): the sorted order, the cell table and
         // the leaf cells stand; only what depends on h is redone -- and a self-gravity tree stays valid
@@ -311,6 +318,7 @@ int drain_reports(sph_ctx *c) {
         if (rep[0] > c->nl_cap || (c->tiled && rep[3] >= 65536)) {
             c->err = "neighbour list overflowed in the last build (lists or candidate intervals grew beyond their headroom within one step): results are incomplete";
             c->ring_nl_valid = false; c->grid_valid = false; c->rho_valid = false; c->eos_valid = false; c->rates_valid = false;
+            c->nl_overflowed = true;
             return SPH_ERR_STATE;
         }
     }
@@ -632,6 +640,7 @@ static int upload_impl(sph_ctx *c, int64_t n, const double *const src[9], hipMem
     c->grid_valid = c->rho_valid = c->eos_valid = c->rates_valid = c->order_valid = c->tree_valid = false;
     c->derived_kept = false;
     c->ring_bbox_valid = c->ring_nl_valid = false;       // a new particle set: the next build waits for its own read-backs
+    c->nl_overflowed = false;
     c->h_new_is_build = false; c->h_refresh_ok = false;
     return SPH_OK;
 }

@@ -195,6 +195,8 @@ struct sph_ctx {
     hipEvent_t ev_bbox[2] = {nullptr, nullptr}, ev_nl[2] = {nullptr, nullptr};
     int ring_bbox = 0, ring_nl = 0;
     bool ring_bbox_valid = false, ring_nl_valid = false;
+    // a list overflow was reported: the state may carry a kick from truncated sums.  Every evaluation is refused until sph_upload
+    bool nl_overflowed = false;
     bool bbox_exact = true;          // c->bbox is the exact box of the last build (not the previous one widened)
     bool no_stale = false;           // SPH_SYNC_EVERY_BUILD: wait for every read-back (A/B switch)
     int64_t host_syncs = 0;          // stream synchronisations inside the build path (statistics)

@@ -782,8 +782,9 @@ int nlist_build_tiled(sph_ctx *c) {
     if (trusted) {
         SPH_HIP(hipEventSynchronize(c->ev_nl[1 - p]));
         const int32_t *prev = reinterpret_cast<const int32_t *>(c->h_pinned + 240 + 8 * (1 - p));
-        if (prev[0] > c->nl_cap) { c->err = "neighbour list overflowed in the previous build (lists grew by more than a third within one step)"; return SPH_ERR_STATE; }
-        if (prev[3] >= LIST16_MAX_NEED) { c->err = "neighbour list: a group's candidate intervals outgrew the 16-bit entries within one step"; return SPH_ERR_STATE; }
+        // either way the context refuses every evaluation from here on (nl_overflowed, do_density)
+        if (prev[0] > c->nl_cap) { c->nl_overflowed = true; c->err = "neighbour list overflowed in the previous build (lists grew by more than a third within one step)"; return SPH_ERR_STATE; }
+        if (prev[3] >= LIST16_MAX_NEED) { c->nl_overflowed = true; c->err = "neighbour list: a group's candidate intervals outgrew the 16-bit entries within one step"; return SPH_ERR_STATE; }
         if (2 * (int64_t)prev[3] >= LIST16_MAX_NEED) return leave_tiled_path(c);
         digest(prev);
         if (4 * (int64_t)prev[0] > 3 * (int64_t)c->nl_cap) { const int st = regrow(prev[0] + prev[0] / 2 + 8); if (st != SPH_OK) return st; }
