@@ -1003,6 +1003,79 @@ typedef struct sph_force_terms_desc {
 int sph_force_terms(sph_ctx *ctx, const sph_force_terms_desc *d, double *host_out, int64_t n_out);
 int sph_force_terms_dev(sph_ctx *ctx, const sph_force_terms_desc *d, double *d_out, int64_t n_out);
 
+/* ---- binned sums: the count, the sum of a weight and the sums of the weight times up to eight quantities (and their
+ *      squares) of the owned gas over one or two binned axes -- phase diagrams (rho x u), distribution functions, the mean
+ *      of any quantity against any other, ring sums of the rows sph_gradients and sph_force_terms write.  The generic form
+ *      of sph_profile's reduction: the same order rule, the same bitwise reproducibility ------------------------------------
+ * Sources  an axis or a quantity is an SPH_F_* id, read as sph_download_field reads it (SPH_ERR_STATE exactly when that call
+ *          would refuse the field as stale), or SPH_BINNED_ROW(k): row k of values, values[k * n + id], n = sph_count, id in
+ *          sph_download_field's order (ghosts included) -- the layout sph_gradients_dev, sph_force_terms_dev and
+ *          sph_energy_dev's phi write, so those outputs pass straight in.  values is host memory in the host form and device
+ *          memory in the device form; it is NULL if and only if n_rows == 0.  Only the rows some source names are read.
+ * Edges    one table per axis, computed once on the host: edge[k] = lo + (k (hi - lo)) / n, or with SPH_BINNED_LOGa
+ *          lo pow(hi / lo, k / n); edge[n] = hi exactly (sph_profile's ring edges).  With SPH_BINNED_EDGESa the table is the
+ *          caller's: n[a] + 1 strictly increasing finite doubles in edges (host memory in both forms; the tables of the axes
+ *          that have one, axis 0's first), lo / hi of that axis ignored.  sph_binned_edges returns the table the call will
+ *          use (pure host code: no context, no device) and refuses what the call refuses of the descriptor and the tables.
+ *          Bin along axis a: edge[k] <= value < edge[k + 1] against that table, never by a formula alone.  Bin b =
+ *          k0 n[1] + k1.
+ * Select   the owned gas particles (ghosts and sinks excluded, as the renders and sph_profile select) whose every axis
+ *          value lies in [edge[0], edge[n]) (a NaN is outside).  With SPH_BINNED_SKIP_NAN a particle inside the range with
+ *          a NaN among its quantities is dropped (the rows of sph_gradients and sph_force_terms are NaN at non-targets);
+ *          without it the NaN is summed and poisons its bin.
+ * Weight   w = 1 (SPH_BINNED_W_ONE), m (SPH_BINNED_W_MASS) or m / rho (SPH_BINNED_W_VOLUME; rho as
+ *          sph_download_field(SPH_F_RHO) returns it, SPH_ERR_STATE exactly when that call would refuse).
+ * Sums     sums[b * nsum + s], nsum = 2 + n_q (1 + squares), n_sums == n[0] n[1] nsum:  s = 0 N (the count as a double),
+ *          s = 1 sum w, s = 2 + k sum w * A_k, and with SPH_BINNED_SQUARES s = 2 + n_q + k sum w * (A_k * A_k); every term in
+ *          exactly that parenthesisation, no fused multiply-adds.  The sums are additive: those of two contexts or ranks add
+ *          up to the sums of the union.
+ * Counts   counts[3] (may be NULL; device memory in the device form): selected, owned gas outside the range, owned gas
+ *          inside the range dropped by SPH_BINNED_SKIP_NAN.  Exact (integers); they add up to the owned gas.
+ * Order    sph_profile's: the selected particles are sorted by (bin, original id); every bin's run is cut into pieces of
+ *          1024 sorted positions from its own start, each added by a 64-lane wavefront (lane l: positions l, l + 64, ..., then
+ *          a xor butterfly), then the pieces by another in the same shape.  The sums are bitwise reproducible, independent
+ *          of the context's sorted order, of the dense or hashed grid, of the host or device form and of repeated calls; a
+ *          ring-binned sum with weight m of SPH_F_U is bitwise sph_profile's sum 11 where both select the same particles.
+ *          No float atomics.
+ * cost     host form: one read-back (sums and counts); device form: ordered on the context's stream, no synchronisation
+ *          (but one when the scratch has to grow).  The scratch is the analysis calls' shared buffer.  No state, field,
+ *          statistic (other than device_bytes), flag, grid, list or dt of the context changes.
+ * SPH_ERR_ARG: null descriptor or output, n_axes not 1 or 2, n[a] < 1, n[1] != 1 with one axis, n[0] n[1] > 2^20, n_sums
+ * != n[0] n[1] nsum, n_q outside 0 .. SPH_BINNED_MAX_Q, a source that is neither an SPH_F_* id nor a row below n_rows, n_rows
+ * outside 0 .. 16, values NULL with n_rows > 0 or given with n_rows == 0, edges NULL with SPH_BINNED_EDGESa or given without, a
+ * caller's table that is not strictly increasing or not finite, a non-finite lo or hi, lo >= hi, LOG with lo <= 0, LOG and
+ * EDGES on one axis, a flag of axis 1 with one axis, bins so narrow that two computed edges coincide, an unknown weight,
+ * unknown flags, reserved != 0; nothing is written then.  SPH_ERR_STATE: a stale field.  SPH_ERR_NOMEM: the scratch does
+ * not fit.  An empty context or an empty selection gives zero sums. */
+#define SPH_BINNED_MAX_Q     8
+#define SPH_BINNED_ROW(k)    (-1 - (k))   /* a source: row k of values, k < n_rows <= 16 */
+#define SPH_BINNED_W_ONE     0            /* w = 1 */
+#define SPH_BINNED_W_MASS    1            /* w = m */
+#define SPH_BINNED_W_VOLUME  2            /* w = m / rho */
+#define SPH_BINNED_LOG0      1            /* axis 0: logarithmic edges (lo > 0) */
+#define SPH_BINNED_LOG1      2
+#define SPH_BINNED_EDGES0    4            /* axis 0: the caller's edge table */
+#define SPH_BINNED_EDGES1    8
+#define SPH_BINNED_SQUARES   16           /* also sum w A A per quantity */
+#define SPH_BINNED_SKIP_NAN  32           /* drop a particle if any of its quantities is NaN */
+typedef struct sph_binned_desc {
+    double  lo[2], hi[2];           /* axis range [lo, hi); ignored with SPH_BINNED_EDGESa             */
+    int32_t axis[2];                /* source of each axis: SPH_F_* or SPH_BINNED_ROW(k)                */
+    int32_t n[2];                   /* bins per axis >= 1; n[1] == 1 with one axis; n[0] n[1] <= 2^20   */
+    int32_t n_axes;                 /* 1 or 2                                                           */
+    int32_t n_q;                    /* quantities, 0 .. SPH_BINNED_MAX_Q                                */
+    int32_t q[SPH_BINNED_MAX_Q];    /* their sources                                                    */
+    int32_t weight;                 /* SPH_BINNED_W_*                                                   */
+    int32_t n_rows;                 /* rows of values, 0 .. 16                                          */
+    int32_t flags;                  /* SPH_BINNED_LOG* | EDGES* | SQUARES | SKIP_NAN                    */
+    int32_t reserved[3];            /* must be 0                                                        */
+} sph_binned_desc;                  /* 112 bytes */
+int sph_binned(sph_ctx *ctx, const sph_binned_desc *d, const double *values, const double *edges, double *host_sums,
+               int64_t n_sums, int64_t *counts);
+int sph_binned_dev(sph_ctx *ctx, const sph_binned_desc *d, const double *d_values, const double *edges, double *d_sums,
+                   int64_t n_sums, int64_t *d_counts);
+int sph_binned_edges(const sph_binned_desc *d, const double *edges, int32_t axis, double *out);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too

@@ -52,6 +52,7 @@ SYMBOLS = [
     "sph_bound", "sph_bound_dev",
     "sph_cube", "sph_cube_dev",
     "sph_force_terms", "sph_force_terms_dev",
+    "sph_binned", "sph_binned_dev", "sph_binned_edges",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
@@ -94,6 +95,11 @@ TERMS_SKIP_GAS_GRAVITY = 1
 # self-gravity, PdV work, viscous heating, the two addends of the alpha rate
 TERM_ROWS = ["aP_x", "aP_y", "aP_z", "aV_x", "aV_y", "aV_z", "aS_x", "aS_y", "aS_z", "aG_x", "aG_y", "aG_z",
              "du_P", "du_V", "dalpha_source", "dalpha_decay"]
+BINNED_MAX_Q = 8
+BINNED_MAX_ROWS = 16
+BINNED_W_ONE, BINNED_W_MASS, BINNED_W_VOLUME = 0, 1, 2
+BINNED_WEIGHTS = {"one": BINNED_W_ONE, "mass": BINNED_W_MASS, "volume": BINNED_W_VOLUME}
+BINNED_LOG0, BINNED_LOG1, BINNED_EDGES0, BINNED_EDGES1, BINNED_SQUARES, BINNED_SKIP_NAN = 1, 2, 4, 8, 16, 32
 BOUND_THERMAL = 1
 BOUND_NCOL = 24
 # sph_bound's table columns (include/summersph.h, "Outputs"): S_0's, the last evaluated set's, the outcome
@@ -249,6 +255,90 @@ class BoundDesc(C.Structure):
 class ForceTermsDesc(C.Structure):
     """sph_force_terms_desc (include/summersph.h): flags (TERMS_*), reserved"""
     _fields_ = [("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class BinnedDesc(C.Structure):
+    _fields_ = [("lo", C.c_double * 2), ("hi", C.c_double * 2), ("axis", C.c_int32 * 2), ("n", C.c_int32 * 2),
+                ("n_axes", C.c_int32), ("n_q", C.c_int32), ("q", C.c_int32 * BINNED_MAX_Q), ("weight", C.c_int32),
+                ("n_rows", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+def binned_row(k: int) -> int:
+    """the source id of row k of values (SPH_BINNED_ROW)"""
+    return -1 - int(k)
+
+
+def _binned_source(s) -> int:
+    """a source: a field name, an SPH_F_* id, or a negative id from binned_row(k)"""
+    return FIELDS.index(s) if isinstance(s, str) else int(s)
+
+
+def binned_desc(axes, bins, ranges=None, edges=None, log=(), q=(), weight="mass", n_rows=0, squares=False, skip_nan=True):
+    """(BinnedDesc, edge table or None) of a sph_binned call (include/summersph.h).  axes: one source or a sequence of one or
+    two; bins: an int or one per axis; ranges: (lo, hi) per axis (or one pair with one axis), None for an axis that has
+    edges; edges: None, or per axis None or its n + 1 edges (one axis: the array itself); log: the axes (0, 1) with
+    logarithmic edges."""
+    if isinstance(axes, (str, int, np.integer)):
+        axes = (axes,)
+    na = len(axes)
+    if na not in (1, 2):
+        raise ValueError("binned: one or two axes")
+    bins = (int(bins),) * na if isinstance(bins, (int, np.integer)) else tuple(int(b) for b in bins)
+    if len(bins) != na:
+        raise ValueError("binned: one bin count per axis")
+    if edges is None:
+        edges = (None,) * na
+    elif na == 1 and not (isinstance(edges, (tuple, list)) and len(edges) == 1 and (edges[0] is None or np.ndim(edges[0]) == 1)):
+        edges = (edges,)
+    if ranges is None:
+        ranges = (None,) * na
+    elif na == 1 and np.ndim(ranges) == 1 and len(ranges) == 2 and ranges[0] is not None and np.ndim(ranges[0]) == 0:
+        ranges = (ranges,)
+    if len(edges) != na or len(ranges) != na:
+        raise ValueError("binned: ranges and edges go by axis")
+    q = (q,) if isinstance(q, (str, int, np.integer)) else tuple(q)
+    if len(q) > BINNED_MAX_Q:
+        raise ValueError(f"binned: at most {BINNED_MAX_Q} quantities")
+    d = BinnedDesc()
+    d.n_axes, d.n_q, d.n_rows = na, len(q), int(n_rows)
+    d.n[0], d.n[1] = bins[0], bins[1] if na == 2 else 1
+    d.weight = BINNED_WEIGHTS[weight] if isinstance(weight, str) else int(weight)
+    flags = (BINNED_SQUARES if squares else 0) | (BINNED_SKIP_NAN if skip_nan else 0)
+    tables = []
+    for a in range(na):
+        d.axis[a] = _binned_source(axes[a])
+        if edges[a] is not None:
+            e = np.ascontiguousarray(edges[a], dtype=np.float64)
+            if e.shape != (bins[a] + 1,):
+                raise ValueError(f"binned: axis {a} wants {bins[a] + 1} edges")
+            tables.append(e)
+            flags |= BINNED_EDGES0 << a
+        else:
+            if ranges[a] is None:
+                raise ValueError(f"binned: axis {a} needs a range or edges")
+            d.lo[a], d.hi[a] = float(ranges[a][0]), float(ranges[a][1])
+        if a in tuple(log):
+            flags |= BINNED_LOG0 << a
+    for k, s in enumerate(q):
+        d.q[k] = _binned_source(s)
+    d.flags = flags
+    return d, (np.concatenate(tables) if tables else None)
+
+
+def binned_nsum(n_q: int, squares: bool) -> int:
+    return 2 + int(n_q) * (2 if squares else 1)
+
+
+def binned_edges(desc: BinnedDesc, edges=None, axis: int = 0) -> np.ndarray:
+    """the edge table sph_binned uses for an axis of the descriptor (pure host code: no context, no device)"""
+    if not 0 <= int(axis) < 2:
+        raise SphError(1, "axis out of range")
+    out = np.empty(max(int(desc.n[int(axis)]), 0) + 1, dtype=np.float64)
+    e = None if edges is None else np.ascontiguousarray(edges, dtype=np.float64)
+    st = load().sph_binned_edges(C.byref(desc), None if e is None else e.ctypes.data, int(axis), out.ctypes.data)
+    if st != 0:
+        raise SphError(st, load().sph_strerror(st).decode())
+    return out
 
 
 def bound_desc(h=None, soft2=GRAVAT_REF_SOFT2, thermal=False, max_rounds=0, min_members=1, max_members=2**31 - 1) -> BoundDesc:
@@ -501,6 +591,9 @@ def load():
         fn.argtypes = [C.c_void_p, C.POINTER(CubeDesc), C.c_void_p, C.c_void_p, C.c_int64]
     for fn in (lib.sph_force_terms, lib.sph_force_terms_dev):
         fn.argtypes = [C.c_void_p, C.POINTER(ForceTermsDesc), C.c_void_p, C.c_int64]
+    for fn in (lib.sph_binned, lib.sph_binned_dev):
+        fn.argtypes = [C.c_void_p, C.POINTER(BinnedDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.sph_binned_edges.argtypes = [C.POINTER(BinnedDesc), C.c_void_p, C.c_int32, C.c_void_p]
     _lib = lib
     return lib
 
@@ -1218,6 +1311,59 @@ class Context:
             out = np.empty((TERMS_NROW, n), dtype=np.float64)
             self._ck(self.lib.sph_force_terms(self._h, C.byref(d), out.ctypes.data, TERMS_NROW * n))
         return out
+
+    # ---- binned sums (sph_binned) ---------------------------------------------------------------------
+    def binned(self, axes, bins, ranges=None, edges=None, log=(), q=(), weight="mass", values=None, squares=False,
+               skip_nan=True, device=False):
+        """Per-bin count, sum of a weight and sums of the weight times up to eight quantities of the owned gas over one or
+        two binned axes (include/summersph.h, sph_binned).  A source (axes, q) is a field name, an SPH_F_* id or
+        binned_row(k): row k of values, an (n_rows, sph_count) array in the upload order (float64 numpy; device=True: a
+        contiguous float64 torch tensor on the context's GPU, e.g. what force_terms(device=True) returned).  bins, ranges,
+        edges, log: see binned_desc.  weight: "one", "mass" or "volume" (m / rho).  squares: also the sums of w A A;
+        skip_nan: drop a particle with a NaN quantity (the non-targets of gradients and force_terms).
+        Returns (sums, counts): sums (n0, n1, nsum) float64 with nsum = 2 + n_q (1 + squares), [..., 0] = N, [..., 1] =
+        sum w, [..., 2 + k] = sum w A_k, [..., 2 + n_q + k] = sum w A_k A_k (binned.finish turns them into means and
+        dispersions); counts = (selected, outside the range, dropped as NaN).  device=True: sums and counts (int64) are torch
+        tensors on the context's GPU (sph_binned_dev), ordered after the call on torch's current stream; nothing waits.  The descriptor used is left in self.binned_desc."""
+        n = self.n
+        n_rows = 0
+        if values is not None:
+            n_rows = int(values.shape[0]) if values.ndim == 2 else 1
+        d, tab = binned_desc(axes, bins, ranges, edges, log, q, weight, n_rows, squares, skip_nan)
+        self.binned_desc = d
+        n0, n1, nsum = int(d.n[0]), int(d.n[1]), binned_nsum(d.n_q, squares)
+        size = max(n0, 0) * max(n1, 0) * nsum
+        ep = None if tab is None else tab.ctypes.data
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if values is not None:
+                if not (isinstance(values, torch.Tensor) and values.dtype == torch.float64 and values.is_contiguous()
+                        and values.device == dev):
+                    raise ValueError("binned: device values must be a contiguous float64 tensor on the context's GPU")
+                if values.numel() != n_rows * n:
+                    raise ValueError(f"binned: values rows of {values.numel() // max(n_rows, 1)} for {n} particles")
+            out = torch.empty((max(n0, 0), max(n1, 0), nsum), dtype=torch.float64, device=dev)
+            cnt = torch.empty(3, dtype=torch.int64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
+            self._ck(self.lib.sph_binned_dev(self._h, C.byref(d), None if values is None else C.c_void_p(values.data_ptr()), ep,
+                                             C.c_void_p(out.data_ptr()), size, C.c_void_p(cnt.data_ptr())))
+            st = self.stream()                                    # torch's later work waits for the sums
+            if st:
+                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
+            else:
+                torch.cuda.synchronize(dev)
+            return out, cnt
+        v = None
+        if values is not None:
+            v = np.ascontiguousarray(values, dtype=np.float64).reshape(n_rows, -1)
+            if v.shape[1] != n:
+                raise ValueError(f"binned: values rows of {v.shape[1]} for {n} particles")
+        out = np.empty((max(n0, 0), max(n1, 0), nsum), dtype=np.float64)
+        cnt = np.zeros(3, dtype=np.int64)
+        self._ck(self.lib.sph_binned(self._h, C.byref(d), None if v is None else v.ctypes.data, ep, out.ctypes.data, size,
+                                     cnt.ctypes.data))
+        return out, tuple(int(c) for c in cnt)
 
     # ---- potential and acceleration at arbitrary points (sph_gravity_at) ---------------------------
     def gravity_at(self, points, h=None, ph=None, soft2=GRAVAT_REF_SOFT2, gas=True, sinks=True, split=False, counts=False,

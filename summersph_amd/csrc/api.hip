@@ -1360,6 +1360,20 @@ int sph_force_terms_dev(sph_ctx *c, const sph_force_terms_desc *d, double *d_out
     return force_terms_run(c, d, d_out, n_out, false);
 }
 
+int sph_binned(sph_ctx *c, const sph_binned_desc *d, const double *values, const double *edges, double *host_sums,
+               int64_t n_sums, int64_t *counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return binned_run(c, d, values, edges, host_sums, n_sums, counts, true, field_ready);
+}
+
+int sph_binned_dev(sph_ctx *c, const sph_binned_desc *d, const double *d_values, const double *edges, double *d_sums,
+                   int64_t n_sums, int64_t *d_counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return binned_run(c, d, d_values, edges, d_sums, n_sums, d_counts, false, field_ready);
+}
+
 int sph_synchronize(sph_ctx *c) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);

@@ -263,7 +263,7 @@ struct sph_ctx {
     void *rnd_buf = nullptr; size_t rnd_bytes = 0;
     double *rnd_small = nullptr;     // per-block statistics, their result and the selection cursor
     double *rnd_pinned = nullptr;    // pinned read-back slots
-    // sph_profile (profile.hip): the ring edge table's pinned staging copy and the event of its last upload
+    // sph_profile and sph_binned (profile.hip, binned.hip): the edge table's pinned staging copy and the event of its last upload
     double *prf_edge = nullptr; size_t prf_edge_cap = 0;
     hipEvent_t prf_evt = nullptr;
 };
@@ -456,5 +456,9 @@ int cube_run(sph_ctx *c, const sph_cube_desc *d, const double *values, double *o
              bool (*ready)(const sph_ctx *, int));
 // the rates of sph_forces split by term (terms.hip): host form (out host memory, one synchronisation) or device form
 int force_terms_run(sph_ctx *c, const sph_force_terms_desc *d, double *out, int64_t n_out, bool host);
+// binned sums (binned.hip): host form (values / sums / counts[3] host memory, one read-back) or device form (counts[3] device
+// memory or null); edges is host memory in both; ready = sph_download_field's rule
+int binned_run(sph_ctx *c, const sph_binned_desc *d, const double *values, const double *edges, double *sums, int64_t n_sums,
+               int64_t *counts, bool host, bool (*ready)(const sph_ctx *, int));
 
 }  // namespace sph

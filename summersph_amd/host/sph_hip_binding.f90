@@ -52,6 +52,10 @@ module sph_hip_binding
   public :: sph_cube_desc, sph_cube, sph_cube_dev, SPH_CUBE_PER_VELOCITY
   ! the rates of sph_forces split by physical term (pressure, viscosity, sink gravity, self-gravity, PdV, heating, alpha)
   public :: sph_force_terms_desc, sph_force_terms, sph_force_terms_dev, SPH_TERMS_NROW, SPH_TERMS_SKIP_GAS_GRAVITY
+  ! binned sums (weighted 1-D and 2-D sums of any fields or caller rows; the generic form of sph_profile's reduction)
+  public :: sph_binned_desc, sph_binned, sph_binned_dev, sph_binned_edges, SPH_BINNED_MAX_Q
+  public :: SPH_BINNED_W_ONE, SPH_BINNED_W_MASS, SPH_BINNED_W_VOLUME, SPH_BINNED_LOG0, SPH_BINNED_LOG1
+  public :: SPH_BINNED_EDGES0, SPH_BINNED_EDGES1, SPH_BINNED_SQUARES, SPH_BINNED_SKIP_NAN
   public :: c_message
 
   integer(c_int), parameter :: SPH_OK = 0
@@ -209,6 +213,23 @@ module sph_hip_binding
     integer(c_int32_t) :: flags
     integer(c_int32_t) :: reserved(3)
   end type sph_force_terms_desc
+
+  ! sph_binned: a source (axis, q) is an SPH_F_* id or -1 - k: row k of values (C: SPH_BINNED_ROW(k)), values(id, row) in
+  ! Fortran order: (sph_count, n_rows).  sums(s, k1, k0) in Fortran order: (nsum, n(2), n(1)), nsum = 2 + n_q (1 + squares).
+  ! 112 bytes.
+  integer(c_int32_t), parameter :: SPH_BINNED_MAX_Q = 8
+  integer(c_int32_t), parameter :: SPH_BINNED_W_ONE = 0, SPH_BINNED_W_MASS = 1, SPH_BINNED_W_VOLUME = 2
+  integer(c_int32_t), parameter :: SPH_BINNED_LOG0 = 1, SPH_BINNED_LOG1 = 2, SPH_BINNED_EDGES0 = 4, SPH_BINNED_EDGES1 = 8
+  integer(c_int32_t), parameter :: SPH_BINNED_SQUARES = 16, SPH_BINNED_SKIP_NAN = 32
+  type, bind(C) :: sph_binned_desc
+    real(c_double) :: lo(2), hi(2)
+    integer(c_int32_t) :: axis(2)
+    integer(c_int32_t) :: n(2)
+    integer(c_int32_t) :: n_axes, n_q
+    integer(c_int32_t) :: q(SPH_BINNED_MAX_Q)
+    integer(c_int32_t) :: weight, n_rows, flags
+    integer(c_int32_t) :: reserved(3)
+  end type sph_binned_desc
 
   interface
     integer(c_int) function sph_abi_version() bind(C, name='sph_abi_version')
@@ -747,6 +768,28 @@ module sph_hip_binding
       type(c_ptr), value :: ctx, d_out
       type(sph_force_terms_desc), intent(in) :: d
       integer(c_int64_t), value :: n_out
+    end function
+    ! ---- binned sums: values / d_values (n_rows sph_count doubles or c_null_ptr), edges (host memory in both forms, or
+    !      c_null_ptr), sums (n_sums doubles), counts (3 int64 or c_null_ptr: selected, outside, dropped as NaN)
+    integer(c_int) function sph_binned(ctx, d, values, edges, host_sums, n_sums, counts) bind(C, name='sph_binned')
+      import :: c_int, c_int64_t, c_ptr, sph_binned_desc
+      type(c_ptr), value :: ctx, values, edges, host_sums, counts
+      type(sph_binned_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_sums
+    end function
+    integer(c_int) function sph_binned_dev(ctx, d, d_values, edges, d_sums, n_sums, d_counts) bind(C, name='sph_binned_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_binned_desc
+      type(c_ptr), value :: ctx, d_values, edges, d_sums, d_counts
+      type(sph_binned_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_sums
+    end function
+    ! the edge table the call uses for an axis (0 or 1): out holds n(axis + 1) + 1 doubles; host only, no context
+    integer(c_int) function sph_binned_edges(d, edges, axis, out) bind(C, name='sph_binned_edges')
+      import :: c_int, c_int32_t, c_double, c_ptr, sph_binned_desc
+      type(sph_binned_desc), intent(in) :: d
+      type(c_ptr), value :: edges
+      integer(c_int32_t), value :: axis
+      real(c_double), intent(out) :: out(*)
     end function
   end interface
 
