@@ -743,6 +743,74 @@ int sph_sample(sph_ctx *ctx, const sph_sample_desc *d, int64_t n_points, const d
 int sph_sample_dev(sph_ctx *ctx, const sph_sample_desc *d, int64_t n_points, const double *d_px, const double *d_py,
                    const double *d_pz, const double *d_values, double *d_out, int64_t n_out, double *d_weight, int64_t *d_counts);
 
+/* ---- field lines of an SPH-interpolated vector field: streamlines of the gas velocity (in the inertial frame or one that
+ *      rotates with a sink), of g, of the vorticity, ... -- n_seeds lines of n_steps classical RK4 steps each through the
+ *      FROZEN field, in one kernel after one build of sph_sample's search structure ---------------------------------------
+ * Field    at a point q, w_k(q) (k = 0, 1, 2) is exactly what sph_sample returns there with SPH_SAMPLE_NORMALISE for
+ *          fields[k] with this descriptor's weight, h and clip: num_k(q) / den(q) in sph_sample's order rule (level, cell
+ *          key, original id), same kernel, same arithmetic; 0.0 where den == 0.  fields[k] is an SPH_F_* id or
+ *          SPH_TRACE_VALUES: row k of values, values[k * n + id] (n = sph_count, sph_download_field order; host memory for
+ *          sph_trace, device memory for _dev).  Then, without fused multiply-adds and in this order:
+ *            t = q - centre;  f = (om_y t_z - om_z t_y, om_z t_x - om_x t_z, om_x t_y - om_y t_x);  v = w - f;
+ *            SPH_TRACE_PLANAR:     d = (v_x n_x + v_y n_y) + v_z n_z;  v_a = v_a - d n_a, with n = normal / |normal| and
+ *                                  |normal| = sqrt((n_x n_x + n_y n_y) + n_z n_z), formed once on the host;
+ *            SPH_TRACE_ARCLENGTH:  sp = sqrt((v_x v_x + v_y v_y) + v_z v_z);  v_a = v_a / sp.
+ * Step     hs = 0.5 * ds and s6 = ds / 6.0, formed once on the host.  k1 = v(p), k2 = v(p + hs k1), k3 = v(p + hs k2),
+ *          k4 = v(p + ds k3), p' = p + s6 ((k1 + 2 k2) + (2 k3 + k4)), per component, every product rounded before it is
+ *          added.  ds is a time, or with SPH_TRACE_ARCLENGTH a length; ds < 0 traces upstream.
+ * Stops    status per seed.  SPH_TRACE_NONFINITE: the seed has a non-finite coordinate; all its rows are NaN, row 0 included,
+ *          n_done = 0.  SPH_TRACE_LEFT_BOX: a vertex is not strictly inside box_lo < p < box_hi on every axis (so a vertex
+ *          that became non-finite also ends here); the seed itself: n_done = 0; a new vertex: it is recorded if its index is
+ *          a multiple of stride, then the line stops.  SPH_TRACE_LEFT_GAS: den == 0 at one of the four stage points (no
+ *          source reaches it); the step is not taken and the line ends at its last vertex.  SPH_TRACE_STAGNANT
+ *          (SPH_TRACE_ARCLENGTH only): sp == 0 or not finite at a stage, in the same way.  SPH_TRACE_DONE: n_steps taken.
+ *          n_done: the steps completed.  An empty source set makes every finite seed inside the box SPH_TRACE_LEFT_GAS.
+ * Output   n_rec = n_steps / stride; path[(r * 3 + a) * n_seeds + p] is coordinate a of vertex r * stride of line p, r = 0 ..
+ *          n_rec; row 0 is the seed; rows after the line's last vertex are NaN.  n_path == 3 (n_rec + 1) n_seeds.
+ *          carry_out[r * n_seeds + p] (iff carry != SPH_TRACE_NONE): sph_sample's normalised value of the field `carry`
+ *          (an SPH_F_* id, or SPH_TRACE_VALUES: row 3 of values) at every recorded vertex, 0.0 where den == 0; NaN in the rows
+ *          path has NaN in.  counts (optional, 5 x int64): the seeds per status code.
+ * Order    a line depends on the sources, the descriptor and its own seed only: bitwise the same over repeated calls, any
+ *          order or subset of the seeds (one seed alone included), the context's slot order, dense or SPH_FLAG_HASHED_GRID
+ *          grids, and the host and device forms.  The seeds are sorted by cell for the work distribution only.  No float
+ *          atomics.
+ * cost     sph_sample's: the host form has one synchronisation, the device form none (ordered on the context's stream); a
+ *          source with h <= 0 or a non-finite h shows as d_counts[0] == -1 (the other four 0) with NaN paths, status
+ *          SPH_TRACE_NONFINITE and n_done 0 in the device form, as SPH_ERR_STATE in the host form.  No state of the
+ *          context changes (device_bytes may grow: the analysis scratch).
+ * SPH_ERR_ARG, nothing written: null descriptor; null seed arrays with n_seeds > 0; n_seeds outside 0 .. 2^31 - 1; ds zero
+ * or non-finite; n_steps outside 1 .. 65535; stride < 1 or not dividing n_steps; a bad field or carry id; values given with no
+ * SPH_TRACE_VALUES id or missing while one is used; n_path != 3 (n_rec + 1) n_seeds; null path, status or n_done; carry_out
+ * present without a carry or missing with one; unknown flags; reserved != 0; SPH_TRACE_PLANAR with a zero or non-finite
+ * normal; a non-finite omega or centre; a NaN in either box; h < 0 or NaN; a bad weight.  SPH_ERR_STATE, SPH_ERR_NOMEM: as
+ * sph_sample.  n_seeds == 0 succeeds (counts, if given: zeros). */
+#define SPH_TRACE_ARCLENGTH  1   /* step along v / |v| by ds (a length) instead of along v by ds (a time) */
+#define SPH_TRACE_PLANAR     2   /* remove v's component along desc.normal before it is used              */
+#define SPH_TRACE_VALUES   (-1)  /* fields[k] / carry: row k (carry: row 3) of values, values[k * n + id]  */
+#define SPH_TRACE_NONE     (-2)  /* carry: nothing carried                                                */
+enum { SPH_TRACE_DONE = 0, SPH_TRACE_LEFT_GAS = 1, SPH_TRACE_LEFT_BOX = 2, SPH_TRACE_STAGNANT = 3, SPH_TRACE_NONFINITE = 4 };
+typedef struct sph_trace_desc {
+    double  clip_lo[3], clip_hi[3];   /* SOURCE clip box, sph_sample's                                   */
+    double  h;                        /* sph_sample's h rule                                             */
+    double  box_lo[3], box_hi[3];     /* tracers stop outside lo < p < hi; -/+INFINITY: none             */
+    double  ds;                       /* finite, != 0; < 0 traces upstream                               */
+    double  omega[3], centre[3];      /* frame: v - omega x (p - centre); zeros: the inertial frame      */
+    double  normal[3];                /* SPH_TRACE_PLANAR: any non-zero vector (normalised on the host)  */
+    int32_t fields[3];                /* the vector's components: SPH_F_* or SPH_TRACE_VALUES            */
+    int32_t carry;                    /* a scalar sampled at every recorded vertex, or SPH_TRACE_NONE    */
+    int32_t weight;                   /* SPH_RENDER_WEIGHT_MASS / _VOLUME                                */
+    int32_t n_steps;                  /* 1 .. 65535                                                      */
+    int32_t stride;                   /* >= 1, divides n_steps: every stride-th vertex is recorded       */
+    int32_t flags;                    /* SPH_TRACE_ARCLENGTH | SPH_TRACE_PLANAR                          */
+    int32_t reserved[2];              /* must be 0                                                       */
+} sph_trace_desc;                     /* 224 bytes */
+int sph_trace(sph_ctx *ctx, const sph_trace_desc *d, int64_t n_seeds, const double *sx, const double *sy, const double *sz,
+              const double *values, double *host_path, int64_t n_path, double *host_carry, int32_t *host_status,
+              int32_t *host_n_done, int64_t *counts);
+int sph_trace_dev(sph_ctx *ctx, const sph_trace_desc *d, int64_t n_seeds, const double *d_sx, const double *d_sy,
+                  const double *d_sz, const double *d_values, double *d_path, int64_t n_path, double *d_carry, int32_t *d_status,
+                  int32_t *d_n_done, int64_t *d_counts);
+
 /* ---- gravitational potential and acceleration at arbitrary points: the Barnes-Hut field of the gas and the field of the
  *      sinks where no particle is (a rotation curve, a potential map, torque maps, the tidal field at a candidate sink
  *      position, tracers) ------------------------------------------------------------------------------------------------

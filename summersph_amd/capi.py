@@ -48,6 +48,7 @@ SYMBOLS = [
     "sph_groups", "sph_groups_dev",
     "sph_gradients", "sph_gradients_dev",
     "sph_sample", "sph_sample_dev",
+    "sph_trace", "sph_trace_dev",
     "sph_gravity_at", "sph_gravity_at_dev",
     "sph_bound", "sph_bound_dev",
     "sph_cube", "sph_cube_dev",
@@ -83,6 +84,13 @@ GRAD_VALUES = -1
 SAMPLE_NORMALISE = 1
 SAMPLE_MAX_FIELDS = 4
 SAMPLE_VALUES = -1
+TRACE_ARCLENGTH = 1
+TRACE_PLANAR = 2
+TRACE_VALUES = -1
+TRACE_NONE = -2
+# sph_trace's status codes (include/summersph.h, "Stops")
+TRACE_DONE, TRACE_LEFT_GAS, TRACE_LEFT_BOX, TRACE_STAGNANT, TRACE_NONFINITE = range(5)
+TRACE_STATUS = ["done", "left_gas", "left_box", "stagnant", "nonfinite"]
 GRAVAT_GAS = 1
 GRAVAT_SINKS = 2
 GRAVAT_SPLIT = 4
@@ -228,6 +236,45 @@ def sample_desc(fields=(), weight="mass", normalise=False, h=None, clip=None) ->
     lo, hi = ((-np.inf,) * 3, (np.inf,) * 3) if clip is None else clip
     d.clip_lo[:] = [float(v) for v in lo]
     d.clip_hi[:] = [float(v) for v in hi]
+    return d
+
+
+class TraceDesc(C.Structure):
+    """sph_trace_desc (include/summersph.h): sph_sample's source clip box and h, the tracers' box, the step ds, the frame
+    (omega, centre), the PLANAR normal, the three component ids and the carry id (SPH_F_*, TRACE_VALUES; carry: TRACE_NONE),
+    weight, n_steps, stride, flags (TRACE_ARCLENGTH | TRACE_PLANAR), reserved"""
+    _fields_ = [("clip_lo", C.c_double * 3), ("clip_hi", C.c_double * 3), ("h", C.c_double),
+                ("box_lo", C.c_double * 3), ("box_hi", C.c_double * 3), ("ds", C.c_double),
+                ("omega", C.c_double * 3), ("centre", C.c_double * 3), ("normal", C.c_double * 3),
+                ("fields", C.c_int32 * 3), ("carry", C.c_int32), ("weight", C.c_int32), ("n_steps", C.c_int32),
+                ("stride", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+def trace_desc(n_steps, ds, fields=("vx", "vy", "vz"), carry=None, arclength=False, omega=None, centre=(0.0, 0.0, 0.0),
+               normal=None, box=None, stride=1, weight="mass", h=None, clip=None) -> TraceDesc:
+    """The descriptor of Context.trace's arguments (see there)."""
+    fields = list(fields)
+    if len(fields) != 3:
+        raise ValueError(f"trace: three component fields, not {len(fields)}")
+
+    def fid(f):
+        return FIELDS.index(f) if isinstance(f, str) else int(f)
+    d = TraceDesc()
+    d.fields[:] = [fid(f) for f in fields]
+    d.carry = TRACE_NONE if carry is None else fid(carry)
+    d.weight = {"mass": RENDER_WEIGHT_MASS, "volume": RENDER_WEIGHT_VOLUME}[weight] if isinstance(weight, str) else int(weight)
+    d.n_steps, d.stride, d.ds = int(n_steps), int(stride), float(ds)
+    d.flags = (TRACE_ARCLENGTH if arclength else 0) | (TRACE_PLANAR if normal is not None else 0)
+    d.h = 0.0 if h is None else float(h)
+    lo, hi = ((-np.inf,) * 3, (np.inf,) * 3) if clip is None else clip
+    d.clip_lo[:] = [float(v) for v in lo]
+    d.clip_hi[:] = [float(v) for v in hi]
+    lo, hi = ((-np.inf,) * 3, (np.inf,) * 3) if box is None else box
+    d.box_lo[:] = [float(v) for v in lo]
+    d.box_hi[:] = [float(v) for v in hi]
+    d.omega[:] = [0.0] * 3 if omega is None else [float(v) for v in omega]
+    d.centre[:] = [float(v) for v in centre]
+    d.normal[:] = [0.0] * 3 if normal is None else [float(v) for v in normal]
     return d
 
 
@@ -578,6 +625,9 @@ def load():
     for fn in (lib.sph_sample, lib.sph_sample_dev):
         fn.argtypes = [C.c_void_p, C.POINTER(SampleDesc), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                        C.c_int64, C.c_void_p, C.c_void_p]
+    for fn in (lib.sph_trace, lib.sph_trace_dev):
+        fn.argtypes = [C.c_void_p, C.POINTER(TraceDesc), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                       C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sph_gradients_dev.argtypes = [C.c_void_p, C.POINTER(GradientsDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                       C.c_void_p]
     for fn in (lib.sph_gravity_at, lib.sph_gravity_at_dev):
@@ -1243,6 +1293,97 @@ class Context:
             return w
         parts = [out] + ([w] if want_w else []) + ([cn] if counts else [])
         return parts[0] if len(parts) == 1 else tuple(parts)
+
+    # ---- field lines of an SPH-interpolated vector field (sph_trace) -------------------------------
+    def trace(self, seeds, n_steps, ds, fields=("vx", "vy", "vz"), values=None, carry=None, arclength=False, omega=None,
+              centre=(0.0, 0.0, 0.0), normal=None, box=None, stride=1, weight="mass", h=None, clip=None, counts=False,
+              device=False):
+        """Field lines of the SPH-interpolated vector field (fields[0], fields[1], fields[2]) of the owned gas (include/
+        summersph.h, sph_trace): n_steps classical RK4 steps of ds per seed through the frozen field, the stage velocity being
+        exactly Context.sample(..., normalise=True) at the stage point.  seeds: as Context.sample takes points.  fields and
+        carry: SPH_F_* names or ids, or TRACE_VALUES for row k (carry: row 3) of values, an (n_rows, sph_count) array in the
+        upload order.  ds: a time, or with arclength=True a length along v / |v|; ds < 0 traces upstream.  omega, centre:
+        the frame v - omega x (p - centre).  normal: remove v's component along it (TRACE_PLANAR).  box: (lo xyz, hi xyz),
+        a line stops outside it.  stride: every stride-th vertex is recorded (divides n_steps).  weight, h, clip: as
+        Context.sample.  Returns (path (n_rec + 1, 3, M), status (M) int32, n_done (M) int32[, carry (n_rec + 1, M)][, counts:
+        the seeds per status code, TRACE_STATUS]); rows after a line's last vertex are NaN.  device=True: torch tensors
+        (sph_trace_dev).  The descriptor used is left in self.trace_desc."""
+        d = trace_desc(n_steps, ds, fields, carry, arclength, omega, centre, normal, box, stride, weight, h, clip)
+        self.trace_desc = d
+        n = self.n
+        if d.stride < 1 or d.n_steps < 1 or d.n_steps % d.stride:
+            raise ValueError("trace: n_steps >= 1 and stride >= 1 dividing n_steps")
+        n_rec = d.n_steps // d.stride
+        has_carry = d.carry != TRACE_NONE
+        rows = 4 if d.carry == TRACE_VALUES else max([k + 1 for k in range(3) if d.fields[k] == TRACE_VALUES], default=0)
+        three = isinstance(seeds, (tuple, list)) and len(seeds) == 3
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+
+            def ok(t):
+                return isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == dev
+            if three:
+                p = list(seeds)
+            elif ok(seeds) and seeds.ndim == 2 and seeds.shape[1] == 3:
+                p = [seeds[:, a].contiguous() for a in range(3)]
+            else:
+                p = [None]
+            if not all(ok(t) and t.ndim == 1 and t.is_contiguous() and t.numel() == p[0].numel() for t in p):
+                raise ValueError("trace: device seeds must be an (M, 3) or three contiguous float64 tensors on the context's GPU")
+            m = p[0].numel()
+            if values is not None:
+                if not (ok(values) and values.is_contiguous()):
+                    raise ValueError("trace: device values must be a contiguous float64 tensor on the context's GPU")
+                if values.numel() < rows * n:
+                    raise ValueError(f"trace: values need {rows} rows of {n}")
+            path = torch.empty((n_rec + 1, 3, m), dtype=torch.float64, device=dev)
+            car = torch.empty((n_rec + 1, m), dtype=torch.float64, device=dev) if has_carry else None
+            status = torch.empty(m, dtype=torch.int32, device=dev)
+            done = torch.empty(m, dtype=torch.int32, device=dev)
+            cnt = torch.empty(5, dtype=torch.int64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
+            self._ck(self.lib.sph_trace_dev(self._h, C.byref(d), m, *(C.c_void_p(t.data_ptr()) for t in p),
+                                            None if values is None else C.c_void_p(values.data_ptr()),
+                                            C.c_void_p(path.data_ptr()), 3 * (n_rec + 1) * m,
+                                            None if car is None else C.c_void_p(car.data_ptr()), C.c_void_p(status.data_ptr()),
+                                            C.c_void_p(done.data_ptr()), C.c_void_p(cnt.data_ptr())))
+            st = self.stream()                                    # torch's later work waits for the trace
+            if st:
+                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
+            else:
+                torch.cuda.synchronize(dev)
+            cn = tuple(int(v) for v in cnt.cpu().tolist()) if counts else None
+        else:
+            if three:
+                p = [np.ascontiguousarray(t, dtype=np.float64).reshape(-1) for t in seeds]
+            else:
+                a = np.asarray(seeds, dtype=np.float64)
+                if a.ndim != 2 or a.shape[1] != 3:
+                    raise ValueError("trace: seeds must be an (M, 3) array or three arrays")
+                p = [np.ascontiguousarray(a[:, k]) for k in range(3)]
+            m = p[0].size
+            if p[1].size != m or p[2].size != m:
+                raise ValueError("trace: the three seed arrays differ in length")
+            v = None
+            if values is not None:
+                v = np.ascontiguousarray(values, dtype=np.float64)
+                if v.ndim == 1:
+                    v = v.reshape(1, -1)
+                if v.shape[1] != n:
+                    raise ValueError(f"trace: values rows of {v.shape[1]} for {n} particles")
+                if v.shape[0] < rows:                             # row k belongs to component k: pad the rows nothing reads
+                    v = np.concatenate([v, np.zeros((rows - v.shape[0], n))])
+            path = np.empty((n_rec + 1, 3, m), dtype=np.float64)
+            car = np.empty((n_rec + 1, m), dtype=np.float64) if has_carry else None
+            status = np.empty(m, dtype=np.int32)
+            done = np.empty(m, dtype=np.int32)
+            cc = (C.c_int64 * 5)(0, 0, 0, 0, 0)
+            self._ck(self.lib.sph_trace(self._h, C.byref(d), m, p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data,
+                                        None if v is None else v.ctypes.data, path.ctypes.data, 3 * (n_rec + 1) * m,
+                                        None if car is None else car.ctypes.data, status.ctypes.data, done.ctypes.data, cc))
+            cn = tuple(int(x) for x in cc) if counts else None
+        return tuple([path, status, done] + ([car] if has_carry else []) + ([cn] if counts else []))
 
     # ---- spectral cubes (sph_cube) -----------------------------------------------------------------
     def cube(self, shape, bounds, v0, dv, n_chan, rot=None, centre=(0.0, 0.0, 0.0), v_ref=(0.0, 0.0, 0.0), sigma_scale=0.0,

@@ -1308,6 +1308,24 @@ int sph_sample_dev(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const
     return sample_run(c, d, n_points, d_px, d_py, d_pz, d_values, d_out, n_out, d_weight, d_counts, false, field_ready);
 }
 
+int sph_trace(sph_ctx *c, const sph_trace_desc *d, int64_t n_seeds, const double *sx, const double *sy, const double *sz,
+              const double *values, double *host_path, int64_t n_path, double *host_carry, int32_t *host_status,
+              int32_t *host_n_done, int64_t *counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return trace_run(c, d, n_seeds, sx, sy, sz, values, host_path, n_path, host_carry, host_status, host_n_done, counts, true,
+                     field_ready);
+}
+
+int sph_trace_dev(sph_ctx *c, const sph_trace_desc *d, int64_t n_seeds, const double *d_sx, const double *d_sy,
+                  const double *d_sz, const double *d_values, double *d_path, int64_t n_path, double *d_carry, int32_t *d_status,
+                  int32_t *d_n_done, int64_t *d_counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return trace_run(c, d, n_seeds, d_sx, d_sy, d_sz, d_values, d_path, n_path, d_carry, d_status, d_n_done, d_counts, false,
+                     field_ready);
+}
+
 int sph_gravity_at(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_points, const double *px, const double *py,
                    const double *pz, const double *ph, double *host_out, int64_t n_out, int64_t *counts) {
     if (!c) return SPH_ERR_ARG;

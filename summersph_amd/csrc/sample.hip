@@ -31,6 +31,9 @@
 //                   nearest face is farther than 2 H_l; each cell's records in id order; den and the K num in registers.
 //                   Epilogue: normalise, store at the point's original index, integer-atomic counts.
 // A point's values depend only on the sources, the descriptor and the point itself: no float atomics anywhere.
+//
+// The steps up to sample_tails are sample_build, which sph_trace (trace.hip) calls too; what its walk shares with sample_walk
+// on the device (Level, Info, kernel_w, add_range, point_sums: the level / cell loop of a point) is in sample_common.hpp.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
@@ -38,10 +41,10 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "cell_table.hpp"
-
 // the per-pair arithmetic is written in one documented order (summersph.h); no contraction into fused multiply-adds
 #pragma clang fp contract(off)
+
+#include "sample_common.hpp"
 
 namespace sph {
 
@@ -50,10 +53,9 @@ namespace {
 constexpr int SB = 256;                    // block of the per-slot, per-point and walk kernels
 constexpr int BOX_BLOCKS = 1024;           // select blocks at most (grid-stride beyond)
 constexpr int NBP = 8;                     // box partials: lo (3), hi (3), sources, bad
-constexpr int HBINS = 8192;                // quarter octaves of a positive double: bits >> 50
+constexpr int HBINS = SAMPLE_HBINS;
 constexpr int HSHIFT = 50;
-constexpr double DBL_BIG = 1.7976931348623157e308;
-constexpr uint64_t POINT_KEY_NONE = (uint64_t)1 << (3 * LEVEL_AXIS_BITS);     // a point without a cell: sorts last
+constexpr double DBL_BIG = SAMPLE_DBL_BIG;
 
 struct Sel {
     double clip_lo[3], clip_hi[3];
@@ -62,35 +64,11 @@ struct Sel {
     int64_t n_owned;
 };
 
-struct Level {
-    double edge, inv_e;                    // cell edge E_l and 1 / E_l
-    double cull2;                          // (2 H_l)^2 (1 + 1e-5): a cell farther than this (squared) holds no reaching source
-    int32_t cmax[3];                       // largest cell index per axis
-    int32_t pad;
-};
-
-// on the device, written by sample_levels (counts by sample_walk)
-struct Info {
-    double lo[3];                          // the source box's minimum: origin of every level's cells
-    int64_t n_src;                         // sources (sorted positions [0, n_src))
-    int64_t counts[2];                     // points with den != 0 (-1: a source has a bad h), points with a non-finite coordinate
-    int32_t bad;
-    int32_t nlev;                          // occupied levels
-    int32_t top;                           // the most populated level (the points are sorted by their cell in it)
-    int32_t g;                             // a level is an aligned group of 2^g quarter octaves
-    Level lv[MAX_LEVELS];
-    uint8_t level_of[HBINS];               // quarter octave -> level
-};
-
 // the fields read: ptr[k] is a context field in slot order (by_id 0) or a row of the caller's values by original id
 struct Vals {
     const double *ptr[SPH_SAMPLE_MAX_FIELDS];
     int32_t by_id[SPH_SAMPLE_MAX_FIELDS];
 };
-
-__device__ __forceinline__ bool finite3(double x, double y, double z) {
-    return fabs(x) <= DBL_BIG && fabs(y) <= DBL_BIG && fabs(z) <= DBL_BIG;
-}
 
 // the renders' selection: owned, strictly inside the clip box (a non-finite position is never inside)
 __device__ __forceinline__ bool source(const Sel &s, int32_t id, double x, double y, double z) {
@@ -101,14 +79,6 @@ __device__ __forceinline__ bool source(const Sel &s, int32_t id, double x, doubl
 __device__ __forceinline__ double h_of(const Sel &s, int64_t i) { return s.h_one > 0.0 ? s.h_one : s.hf[i]; }
 
 __device__ __forceinline__ bool good_h(double h) { return h > 0.0 && h <= DBL_BIG; }
-
-// render.hip's kernel_w: 1 - 1.5 q^2 + 0.75 q^3 (q <= 1), 0.25 (2 - q)^3 (1 < q <= 2), 0 beyond
-__device__ __forceinline__ double kernel_w(double q) {
-    const double t = 2.0 - q;
-    const double w1 = (1.0 - 1.5 * (q * q)) + 0.75 * (q * q * q);
-    const double w2 = 0.25 * (t * t * t);
-    return q <= 1.0 ? w1 : (q <= 2.0 ? w2 : 0.0);
-}
 
 // per-block partials lo (3), hi (3), sources, bad; the h histogram (hist non-null: per-particle h)
 __global__ __launch_bounds__(SB) void sample_select(const double *__restrict__ x, const double *__restrict__ y,
@@ -308,39 +278,8 @@ __global__ __launch_bounds__(SB) void sample_point_keys(const double *__restrict
                                                         uint64_t *__restrict__ keys, uint32_t *__restrict__ vals) {
     const int64_t t = (int64_t)blockIdx.x * SB + threadIdx.x;
     if (t >= m) return;
-    const double x = px[t], y = py[t], z = pz[t];
-    uint64_t key = POINT_KEY_NONE;
-    if (finite3(x, y, z)) {
-        key = 0;
-        if (info->nlev > 0) {
-            const Level &L = info->lv[info->top];
-            key = level_key(0, level_cell_axis(x, info->lo[0], L.inv_e, L.cmax[0]), level_cell_axis(y, info->lo[1], L.inv_e, L.cmax[1]),
-                            level_cell_axis(z, info->lo[2], L.inv_e, L.cmax[2]));
-        }
-    }
-    keys[t] = key;
+    keys[t] = point_sort_key(info, px[t], py[t], pz[t]);
     vals[t] = (uint32_t)t;
-}
-
-// the sources at sorted positions [q0, q1) added to a point's sums, in that order
-template <int K, bool PER_H>
-__device__ __forceinline__ void add_range(const double4 *__restrict__ rec, const double *__restrict__ wsa, int32_t q0, int32_t q1,
-                                          const double (&p)[3], double ih_one, double &den, double (&num)[K > 0 ? K : 1]) {
-    constexpr int S = K + 1;
-    for (int32_t q = q0; q < q1; q++) {
-        const double4 s = rec[q];
-        const double dx = p[0] - s.x, dy = p[1] - s.y, dz = p[2] - s.z;
-        const double d2 = (dx * dx + dy * dy) + dz * dz;
-        const double ih = PER_H ? s.w : ih_one;
-        if (!(d2 * (ih * ih) <= 4.0000001)) continue;      // filter only: q <= 2 decides
-        const double qq = sqrt(d2) * ih;
-        if (!(qq <= 2.0)) continue;
-        const double wn = kernel_w(qq);
-        const double *w = wsa + (int64_t)q * S;
-        den += w[0] * wn;
-#pragma unroll
-        for (int k = 0; k < K; k++) num[k] += w[1 + k] * wn;
-    }
 }
 
 // one lane per point (the t-th in walk order: point pidx[t], or t itself without the point sort)
@@ -363,41 +302,7 @@ __global__ __launch_bounds__(SB) void sample_walk(const double *__restrict__ px,
     for (int k = 0; k < K; k++) num[k] = 0.0;
     const int nlev = (active && fin) ? info->nlev : 0;
     const double ih_one = 1.0 / h_one;                       // one h: the records' 1 / h_j, bitwise
-    for (int l = 0; l < nlev; l++) {
-        const Level &L = info->lv[l];
-        const double e = L.edge, cull2 = L.cull2;
-        // the stencil: the signed, unclamped cell of the point +- 1, intersected with the source box's cells
-        int32_t c0[3], c1[3];
-        bool any = true;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            const double cm = (double)L.cmax[a];
-            const double fc = fmin(fmax(floor((p[a] - info->lo[a]) * L.inv_e), -2.0), cm + 2.0);
-            const int32_t ci = (int32_t)fc;
-            c0[a] = max(ci - 1, 0);
-            c1[a] = min(ci + 1, L.cmax[a]);
-            any = any && c0[a] <= c1[a];
-        }
-        if (!any) continue;
-        for (int32_t n0 = c0[0]; n0 <= c1[0]; n0++) {
-            const double f0 = info->lo[0] + (double)n0 * e;
-            const double g0 = fmax(fmax(f0 - p[0], p[0] - (f0 + e)), 0.0);
-            for (int32_t n1 = c0[1]; n1 <= c1[1]; n1++) {
-                const double f1 = info->lo[1] + (double)n1 * e;
-                const double g1 = fmax(fmax(f1 - p[1], p[1] - (f1 + e)), 0.0);
-                const double g01 = g0 * g0 + g1 * g1;
-                if (g01 > cull2) continue;
-                for (int32_t n2 = c0[2]; n2 <= c1[2]; n2++) {
-                    const double f2 = info->lo[2] + (double)n2 * e;
-                    const double g2 = fmax(fmax(f2 - p[2], p[2] - (f2 + e)), 0.0);
-                    if (g01 + g2 * g2 > cull2) continue;     // no source of this level in the cell reaches the point
-                    const int64_t en = hash_slot(tab, mask, level_key((uint64_t)l, (uint64_t)n0, (uint64_t)n1, (uint64_t)n2));
-                    if (en < 0) continue;
-                    add_range<K, PER_H>(rec, wsa, tab[en].start, tab[en].end, p, ih_one, den, num);
-                }
-            }
-        }
-    }
+    point_sums<K, PER_H>(info, rec, wsa, tab, mask, nlev, p, ih_one, den, num);
     const bool nan = !fin || bad;
     if (active) {
 #pragma unroll
@@ -449,6 +354,93 @@ int env_int(const char *name, int fallback, int lo, int hi) {
 
 }  // namespace
 
+int sample_build(sph_ctx *c, const SampleSources &src, size_t extra_bytes, SampleView *view, char **extra, char **sort_tmp_out) {
+    hipStream_t st = c->stream;
+    const int64_t n = c->n;
+    const int64_t ns = c->cap > 0 ? c->n_slots : 0;
+    const bool held = ns > 0 && n > 0;
+    const bool per_h = src.per_h, host = src.host;
+    const int nf = src.nf;
+    const int g0 = env_int("SPH_SAMPLE_LEVEL_WIDTH", 1, 0, 13);            // 2^g0 quarter octaves per level
+    const int64_t nn = std::max<int64_t>(n, 1);
+    const int nb = (int)std::min<int64_t>((std::max<int64_t>(ns, 1) + SB - 1) / SB, BOX_BLOCKS);
+    int64_t tl = 1;
+    while (tl < 2 * nn) tl <<= 1;                                // hash table: load <= 1/2
+    size_t sort_bytes = 0;
+    SPH_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
+                                      (uint32_t *)nullptr, (size_t)nn, 0u, 64u, st));
+    const size_t n_val = host && src.values ? (size_t)nf * (size_t)nn : 0;
+    uint64_t *keys, *keys_alt;
+    uint32_t *vals, *vals_alt, *hist_buf;
+    char *sort_tmp, *extra_buf;
+    double4 *rec;
+    Ent *tab;
+    Info *info;
+    double *wsa, *box_part, *h_values;
+    auto layout = [&](Carve cv) {
+        keys = cv.take<uint64_t>(nn);
+        keys_alt = cv.take<uint64_t>(nn);
+        vals = cv.take<uint32_t>(nn);
+        vals_alt = cv.take<uint32_t>(nn);
+        sort_tmp = cv.take<char>(std::max(sort_bytes, src.tmp_bytes));
+        rec = cv.take<double4>(nn);
+        wsa = cv.take<double>((size_t)(nf + 1) * (size_t)nn);
+        tab = cv.take<Ent>(tl);
+        box_part = cv.take<double>(NBP * (size_t)nb);
+        hist_buf = cv.take<uint32_t>(per_h ? HBINS : 0);
+        info = cv.take<Info>(1);
+        h_values = cv.take<double>(n_val);                       // the host form's device copy
+        extra_buf = cv.take<char>(extra_bytes);
+        return cv.bytes;
+    };
+    char *buf = nullptr;
+    SPH_TRY(analysis_scratch(c, layout(Carve{}), &buf));
+    layout(Carve{buf});
+    uint32_t *hist = per_h ? hist_buf : nullptr;
+    const double *d_values = host && src.values ? h_values : src.values;
+
+    Sel s{};
+    for (int a = 0; a < 3; a++) { s.clip_lo[a] = src.clip_lo[a]; s.clip_hi[a] = src.clip_hi[a]; }
+    s.h_one = src.h_one;
+    s.hf = per_h ? c->f[SPH_F_H] : nullptr;
+    s.n_owned = c->n_owned;
+    Vals vf{};
+    for (int k = 0; k < nf; k++) {
+        const bool by_id = src.fields[k] == SPH_SAMPLE_VALUES;
+        vf.by_id[k] = by_id ? 1 : 0;
+        vf.ptr[k] = by_id ? d_values + (size_t)k * (size_t)n : c->f[src.fields[k]];
+        if (by_id && host && n > 0)
+            SPH_HIP(hipMemcpyAsync(const_cast<double *>(vf.ptr[k]), src.values + (size_t)k * (size_t)n, (size_t)n * sizeof(double),
+                                   hipMemcpyHostToDevice, st));
+    }
+    const uint64_t mask = (uint64_t)(tl - 1);
+    if (held) {
+        const double *x = c->f[SPH_F_X], *y = c->f[SPH_F_Y], *z = c->f[SPH_F_Z];
+        // selection, box, levels
+        if (hist) SPH_HIP(hipMemsetAsync(hist, 0, sizeof(uint32_t) * (size_t)HBINS, st));
+        sample_select<<<dim3((unsigned)nb), dim3(SB), 0, st>>>(x, y, z, c->orig, ns, s, box_part, hist);
+        sample_levels<<<dim3(1), dim3(WAVE), 0, st>>>(box_part, nb, hist, src.h_one, g0, info);
+        SPH_HIP(hipGetLastError());
+        // (level, cell) keys by original id, sort, records, hash table over the occupied cells
+        SPH_HIP(hipMemsetAsync(keys, 0xff, sizeof(uint64_t) * (size_t)n, st));
+        SPH_HIP(hipMemsetAsync(vals, 0, sizeof(uint32_t) * (size_t)n, st));
+        sample_keys<<<dim3(blocks(ns, SB)), dim3(SB), 0, st>>>(x, y, z, c->orig, ns, s, info, keys, vals);
+        size_t tmp = sort_bytes;
+        SPH_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)n, 0u, 64u, st));
+        SPH_HIP(hipMemsetAsync(tab, 0xff, sizeof(Ent) * (size_t)tl, st));
+        sample_records<<<dim3(blocks(n, SB)), dim3(SB), 0, st>>>(x, y, z, c->f[SPH_F_M], src.volume ? c->f[SPH_F_RHO] : nullptr,
+                                                                 c->orig, s, vf, nf, keys_alt, vals_alt, info, n, rec, wsa, tab, mask);
+        sample_tails<<<dim3(blocks(n, SB)), dim3(SB), 0, st>>>(keys_alt, info, n, tab, mask);
+    } else {
+        sample_no_sources<<<dim3(1), dim3(WAVE), 0, st>>>(info);
+    }
+    SPH_HIP(hipGetLastError());
+    *view = SampleView{info, rec, wsa, tab, mask};
+    *extra = extra_buf;
+    *sort_tmp_out = sort_tmp;
+    return SPH_OK;
+}
+
 int sample_run(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const double *px, const double *py, const double *pz,
                const double *values, double *out, int64_t n_out, double *weight, int64_t *counts, bool host,
                bool (*ready)(const sph_ctx *, int)) {
@@ -497,56 +489,31 @@ int sample_run(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const dou
     }
 
     hipStream_t st = c->stream;
-    const int64_t n = c->n, m = n_points;
-    const int64_t ns = c->cap > 0 ? c->n_slots : 0;
-    const bool held = ns > 0 && n > 0;
+    const int64_t m = n_points;
     const bool sort_points = env_int("SPH_SAMPLE_POINT_SORT", 1, 0, 1) != 0;
-    const int g0 = env_int("SPH_SAMPLE_LEVEL_WIDTH", 1, 0, 13);            // 2^g0 quarter octaves per level
-    const int64_t nn = std::max<int64_t>(n, 1);
-    const int nb = (int)std::min<int64_t>((std::max<int64_t>(ns, 1) + SB - 1) / SB, BOX_BLOCKS);
-    int64_t tl = 1;
-    while (tl < 2 * nn) tl <<= 1;                                // hash table: load <= 1/2
-    size_t sort_bytes = 0, psort_bytes = 0;
-    SPH_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                      (uint32_t *)nullptr, (size_t)nn, 0u, 64u, st));
+    size_t psort_bytes = 0;
     if (sort_points)
         SPH_HIP(rocprim::radix_sort_pairs(nullptr, psort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
                                           (uint32_t *)nullptr, (size_t)m, 0u, (unsigned)(3 * LEVEL_AXIS_BITS + 1), st));
     const size_t mp = sort_points ? (size_t)m : 0;
-    const size_t n_val = host && values ? (size_t)nf * (size_t)nn : 0;
-    uint64_t *keys, *keys_alt, *pkeys, *pkeys_alt;
-    uint32_t *vals, *vals_alt, *pvals, *pvals_alt, *hist_buf;
-    char *sort_tmp;
-    double4 *rec;
-    Ent *tab;
-    Info *info;
-    double *wsa, *box_part, *h_pts, *h_values, *h_out, *h_weight;
+    uint64_t *pkeys, *pkeys_alt;
+    uint32_t *pvals, *pvals_alt;
+    double *h_pts, *h_out, *h_weight;
     auto layout = [&](Carve cv) {
-        keys = cv.take<uint64_t>(nn);
-        keys_alt = cv.take<uint64_t>(nn);
-        vals = cv.take<uint32_t>(nn);
-        vals_alt = cv.take<uint32_t>(nn);
         pkeys = cv.take<uint64_t>(mp);
         pkeys_alt = cv.take<uint64_t>(mp);
         pvals = cv.take<uint32_t>(mp);
         pvals_alt = cv.take<uint32_t>(mp);
-        sort_tmp = cv.take<char>(std::max(sort_bytes, psort_bytes));
-        rec = cv.take<double4>(nn);
-        wsa = cv.take<double>((size_t)(nf + 1) * (size_t)nn);
-        tab = cv.take<Ent>(tl);
-        box_part = cv.take<double>(NBP * (size_t)nb);
-        hist_buf = cv.take<uint32_t>(per_h ? HBINS : 0);
-        info = cv.take<Info>(1);
         h_pts = cv.take<double>(host ? 3 * (size_t)m : 0);       // the host form's device copies
-        h_values = cv.take<double>(n_val);
         h_out = cv.take<double>(host ? n_out : 0);
         h_weight = cv.take<double>(host && weight ? m : 0);
         return cv.bytes;
     };
-    char *buf = nullptr;
-    SPH_TRY(analysis_scratch(c, layout(Carve{}), &buf));
-    layout(Carve{buf});
-    uint32_t *hist = per_h ? hist_buf : nullptr;
+    const SampleSources src{d->clip_lo, d->clip_hi, h_one, per_h, volume, host, nf, d->fields, values, psort_bytes};
+    SampleView v{};
+    char *extra = nullptr, *sort_tmp = nullptr;
+    SPH_TRY(sample_build(c, src, layout(Carve{}), &v, &extra, &sort_tmp));
+    layout(Carve{extra});
     const double *d_px = px, *d_py = py, *d_pz = pz;
     if (host) {
         SPH_TRY(analysis_pinned(c));
@@ -555,46 +522,9 @@ int sample_run(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const dou
         SPH_HIP(hipMemcpyAsync(h_pts + 2 * m, pz, (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
         d_px = h_pts; d_py = h_pts + m; d_pz = h_pts + 2 * m;
     }
-    const double *d_values = host && values ? h_values : values;
     double *d_out = host ? h_out : out;
     double *d_weight = host ? (weight ? h_weight : nullptr) : weight;
-
-    Sel s{};
-    for (int a = 0; a < 3; a++) { s.clip_lo[a] = d->clip_lo[a]; s.clip_hi[a] = d->clip_hi[a]; }
-    s.h_one = h_one;
-    s.hf = per_h ? c->f[SPH_F_H] : nullptr;
-    s.n_owned = c->n_owned;
-    Vals vf{};
-    for (int k = 0; k < nf; k++) {
-        const bool by_id = d->fields[k] == SPH_SAMPLE_VALUES;
-        vf.by_id[k] = by_id ? 1 : 0;
-        vf.ptr[k] = by_id ? d_values + (size_t)k * (size_t)n : c->f[d->fields[k]];
-        if (by_id && host && n > 0)
-            SPH_HIP(hipMemcpyAsync(const_cast<double *>(vf.ptr[k]), values + (size_t)k * (size_t)n, (size_t)n * sizeof(double),
-                                   hipMemcpyHostToDevice, st));
-    }
-    const uint64_t mask = (uint64_t)(tl - 1);
-    if (held) {
-        const double *x = c->f[SPH_F_X], *y = c->f[SPH_F_Y], *z = c->f[SPH_F_Z];
-        // selection, box, levels
-        if (hist) SPH_HIP(hipMemsetAsync(hist, 0, sizeof(uint32_t) * (size_t)HBINS, st));
-        sample_select<<<dim3((unsigned)nb), dim3(SB), 0, st>>>(x, y, z, c->orig, ns, s, box_part, hist);
-        sample_levels<<<dim3(1), dim3(WAVE), 0, st>>>(box_part, nb, hist, h_one, g0, info);
-        SPH_HIP(hipGetLastError());
-        // (level, cell) keys by original id, sort, records, hash table over the occupied cells
-        SPH_HIP(hipMemsetAsync(keys, 0xff, sizeof(uint64_t) * (size_t)n, st));
-        SPH_HIP(hipMemsetAsync(vals, 0, sizeof(uint32_t) * (size_t)n, st));
-        sample_keys<<<dim3(blocks(ns, SB)), dim3(SB), 0, st>>>(x, y, z, c->orig, ns, s, info, keys, vals);
-        size_t tmp = sort_bytes;
-        SPH_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)n, 0u, 64u, st));
-        SPH_HIP(hipMemsetAsync(tab, 0xff, sizeof(Ent) * (size_t)tl, st));
-        sample_records<<<dim3(blocks(n, SB)), dim3(SB), 0, st>>>(x, y, z, c->f[SPH_F_M], volume ? c->f[SPH_F_RHO] : nullptr, c->orig, s,
-                                                                 vf, nf, keys_alt, vals_alt, info, n, rec, wsa, tab, mask);
-        sample_tails<<<dim3(blocks(n, SB)), dim3(SB), 0, st>>>(keys_alt, info, n, tab, mask);
-    } else {
-        sample_no_sources<<<dim3(1), dim3(WAVE), 0, st>>>(info);
-    }
-    SPH_HIP(hipGetLastError());
+    Info *info = v.info;
     // the points in the order of their cells
     if (sort_points) {
         sample_point_keys<<<dim3(blocks(m, SB)), dim3(SB), 0, st>>>(d_px, d_py, d_pz, m, info, pkeys, pvals);
@@ -603,7 +533,7 @@ int sample_run(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const dou
         SPH_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, pkeys, pkeys_alt, pvals, pvals_alt, (size_t)m, 0u,
                                           (unsigned)(3 * LEVEL_AXIS_BITS + 1), st));
     }
-    WalkArgs wa{d_px, d_py, d_pz, sort_points ? pvals_alt : nullptr, m, info, rec, wsa, tab, mask, h_one,
+    WalkArgs wa{d_px, d_py, d_pz, sort_points ? pvals_alt : nullptr, m, info, v.rec, v.wsa, v.tab, v.mask, h_one,
                 (d->flags & SPH_SAMPLE_NORMALISE) ? 1 : 0, d_out, d_weight};
     hipError_t e = hipSuccess;
     switch (nf) {

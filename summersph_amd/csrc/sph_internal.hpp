@@ -259,7 +259,7 @@ struct sph_ctx {
     int64_t timing_seen[32] = {};    // launches of group k since timing was switched on
     sph::TimingSlot tslot[SPH_K_COUNT];
 
-    // the analysis calls (render, profile, energy, groups, gradients, sample): private scratch, never the grid / list buffers above
+    // the analysis calls (render, profile, energy, groups, gradients, sample, trace): private scratch, never the grid / list buffers above
     void *rnd_buf = nullptr; size_t rnd_bytes = 0;
     double *rnd_small = nullptr;     // per-block statistics, their result and the selection cursor
     double *rnd_pinned = nullptr;    // pinned read-back slots
@@ -442,6 +442,12 @@ int gradients_run(sph_ctx *c, const sph_gradients_desc *d, const double *values,
 int sample_run(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const double *px, const double *py, const double *pz,
                const double *values, double *out, int64_t n_out, double *weight, int64_t *counts, bool host,
                bool (*ready)(const sph_ctx *, int));
+// field lines of an SPH-interpolated vector field (trace.hip, over sample.hip's structure: sample_common.hpp): host form
+// (seeds / values / path / carry / status / n_done host memory, counts[5] host, one synchronisation) or device form
+// (counts[5] device memory or null); ready = sph_download_field's rule
+int trace_run(sph_ctx *c, const sph_trace_desc *d, int64_t n_seeds, const double *sx, const double *sy, const double *sz,
+              const double *values, double *path, int64_t n_path, double *carry_out, int32_t *status, int32_t *n_done,
+              int64_t *counts, bool host, bool (*ready)(const sph_ctx *, int));
 // potential and acceleration at arbitrary points (gravity_at.hip): host form (points / ph / out host memory, counts[2]
 // host) or device form (counts[2] device memory or null)
 int gravity_at_run(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_points, const double *px, const double *py,

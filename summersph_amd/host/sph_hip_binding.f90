@@ -44,6 +44,9 @@ module sph_hip_binding
   public :: sph_gradients_desc, sph_gradients, sph_gradients_dev, SPH_GRAD_CORRECTED, SPH_GRAD_MAX_FIELDS, SPH_GRAD_VALUES
   ! SPH interpolation at arbitrary points (density, fields or the caller's values where the caller wants them)
   public :: sph_sample_desc, sph_sample, sph_sample_dev, SPH_SAMPLE_NORMALISE, SPH_SAMPLE_MAX_FIELDS, SPH_SAMPLE_VALUES
+  ! field lines of an SPH-interpolated vector field (streamlines of the velocity, in a rotating frame if wanted)
+  public :: sph_trace_desc, sph_trace, sph_trace_dev, SPH_TRACE_ARCLENGTH, SPH_TRACE_PLANAR, SPH_TRACE_VALUES, SPH_TRACE_NONE
+  public :: SPH_TRACE_DONE, SPH_TRACE_LEFT_GAS, SPH_TRACE_LEFT_BOX, SPH_TRACE_STAGNANT, SPH_TRACE_NONFINITE
   ! gravitational potential and acceleration at arbitrary points (the gas' Barnes-Hut field and the sinks' field)
   public :: sph_gravity_at_desc, sph_gravity_at, sph_gravity_at_dev, SPH_GRAVAT_GAS, SPH_GRAVAT_SINKS, SPH_GRAVAT_SPLIT
   ! binding energies and unbinding of groups (each group's own potential, the members' energies, the bound core)
@@ -163,6 +166,24 @@ module sph_hip_binding
     integer(c_int32_t) :: fields(SPH_SAMPLE_MAX_FIELDS)
     integer(c_int32_t) :: n_fields, weight, flags, reserved
   end type sph_sample_desc
+
+  ! sph_trace: sph_sample's SOURCE clip box and h, the tracers' box (+-infinity: none), the step ds (finite, /= 0), the frame
+  ! v - omega x (p - centre), the SPH_TRACE_PLANAR normal, the three component ids and the carry id (SPH_F_*,
+  ! SPH_TRACE_VALUES: row k, the carry row 4, of values; carry: SPH_TRACE_NONE), weight, n_steps 1 .. 65535, stride (divides
+  ! n_steps), flags, reserved (0).  path holds path(p, a, r) in Fortran order: (n_seeds, 3, n_steps / stride + 1).  224 bytes.
+  integer(c_int32_t), parameter :: SPH_TRACE_ARCLENGTH = 1, SPH_TRACE_PLANAR = 2, SPH_TRACE_VALUES = -1, SPH_TRACE_NONE = -2
+  integer(c_int32_t), parameter :: SPH_TRACE_DONE = 0, SPH_TRACE_LEFT_GAS = 1, SPH_TRACE_LEFT_BOX = 2, SPH_TRACE_STAGNANT = 3, &
+                                   SPH_TRACE_NONFINITE = 4
+  type, bind(C) :: sph_trace_desc
+    real(c_double) :: clip_lo(3), clip_hi(3)
+    real(c_double) :: h
+    real(c_double) :: box_lo(3), box_hi(3)
+    real(c_double) :: ds
+    real(c_double) :: omega(3), centre(3), normal(3)
+    integer(c_int32_t) :: fields(3)
+    integer(c_int32_t) :: carry, weight, n_steps, stride, flags
+    integer(c_int32_t) :: reserved(2)
+  end type sph_trace_desc
 
   ! sph_gravity_at: h (> 0: the softening length of every point; 0: params.h, fixed-h contexts only; unused with ph), soft2
   ! (>= 0, added to d.d; 0.0025 is the force's value), flags (SPH_GRAVAT_GAS, _SINKS, _SPLIT), reserved (0).  out holds
@@ -705,6 +726,23 @@ module sph_hip_binding
       type(c_ptr), value :: ctx, d_px, d_py, d_pz, d_values, d_out, d_weight, d_counts
       type(sph_sample_desc), intent(in) :: d
       integer(c_int64_t), value :: n_points, n_out
+    end function
+    ! ---- field lines: sx, sy, sz (n_seeds doubles each), values (rows of sph_count doubles, download order, or c_null_ptr),
+    !      host_path (3 (n_rec + 1) n_seeds doubles), host_carry ((n_rec + 1) n_seeds doubles, or c_null_ptr without a carry),
+    !      host_status and host_n_done (n_seeds int32 each), counts (5 x int64: the seeds per status code; or c_null_ptr)
+    integer(c_int) function sph_trace(ctx, d, n_seeds, sx, sy, sz, values, host_path, n_path, host_carry, host_status, &
+                                      host_n_done, counts) bind(C, name='sph_trace')
+      import :: c_int, c_int64_t, c_ptr, sph_trace_desc
+      type(c_ptr), value :: ctx, sx, sy, sz, values, host_path, host_carry, host_status, host_n_done, counts
+      type(sph_trace_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_seeds, n_path
+    end function
+    integer(c_int) function sph_trace_dev(ctx, d, n_seeds, d_sx, d_sy, d_sz, d_values, d_path, n_path, d_carry, d_status, &
+                                          d_n_done, d_counts) bind(C, name='sph_trace_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_trace_desc
+      type(c_ptr), value :: ctx, d_sx, d_sy, d_sz, d_values, d_path, d_carry, d_status, d_n_done, d_counts
+      type(sph_trace_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_seeds, n_path
     end function
     ! ---- potential and acceleration at points: px, py, pz (n_points doubles each), ph (n_points softening lengths or
     !      c_null_ptr), host_out (4 n_points doubles, 8 n_points with SPH_GRAVAT_SPLIT), counts (2 x int64: points with a
