@@ -152,9 +152,33 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
 // The lookup in two halves, so that a kernel can put work between the request of the two knots and their use: the knots of
 // a table in LDS come back behind whatever the wave asked of the LDS before them.
 struct Knots { double t0, t1, a; };
+// tab[k] and tab[k + 1] of a table in LDS as TWO 8-byte reads (ds_read_b64, the second at offset:8 of the same address register)
+// and not the one ds_read2_b64 the backend merges two plain loads into: the paired read takes the LDS array 8 cycles per wave and
+// banks 16 lanes at a time over 32 dwords, two single reads take 2 + 2 and bank 32 lanes over 64 (measured on random knots between
+// record reads: tests/tools/micro/knot_reads.hip, DESIGN.md section 4 "Round 5").  volatile is what keeps the two loads apart; it
+// costs no register and no wait, and the compiler still counts lgkmcnt itself.  -DSPH_KNOTS_READ2 restores the paired read
+// everywhere (profiles/knot_reads_ab.sh builds that library beside the product one); PAIRED = true does so for one caller.
+#ifdef SPH_KNOTS_READ2
+constexpr bool KNOTS_PAIRED = true;
+#else
+constexpr bool KNOTS_PAIRED = false;
+#endif
+template <bool PAIRED = KNOTS_PAIRED>
+__device__ __forceinline__ void knot_pair(const double *__restrict__ tab, int k, double &t0, double &t1) {
+    if constexpr (PAIRED) {
+        t0 = tab[k]; t1 = tab[k + 1];
+    } else {
+        typedef const volatile __attribute__((address_space(3))) double *LdsKnot;      // (a generic volatile pointer loads through flat_load)
+        const LdsKnot p = (LdsKnot)(tab + k);
+        t0 = p[0]; t1 = p[1];
+    }
+}
+template <bool PAIRED = KNOTS_PAIRED>
 __device__ __forceinline__ Knots table_knots_at(const double *__restrict__ tab, double t) {      // t = q / dq, 0 <= t <= nq (+ an ulp)
-    const int k = (int)t;
-    return Knots{tab[k], tab[k + 1], __builtin_amdgcn_fract(t)};
+    Knots kn;
+    knot_pair<PAIRED>(tab, (int)t, kn.t0, kn.t1);
+    kn.a = __builtin_amdgcn_fract(t);
+    return kn;
 }
 __device__ __forceinline__ Knots table_knots(const double *__restrict__ tab, double qi, double inv_dq) {
     return table_knots_at(tab, qi * inv_dq);
@@ -212,8 +236,11 @@ __device__ __forceinline__ void table_lerp2(const double *__restrict__ tw, const
     const double t = qi * inv_dq;
     const int k = (int)t;
     const double a = __builtin_amdgcn_fract(t), b = 1.0 - a;
-    w = b * tw[k] + a * tw[k + 1];
-    dw = b * tdw[k] + a * tdw[k + 1];
+    double w0, w1, d0, d1;
+    knot_pair(tw, k, w0, w1);
+    knot_pair(tdw, k, d0, d1);
+    w = b * w0 + a * w1;
+    dw = b * d0 + a * d1;
 }
 
 // ---- the pair terms, written ONCE (pairs.hip, tiled.hip and varh.hip all call these) -----------------------------------

@@ -168,7 +168,9 @@ template <int BS, int U, int UPR, bool SWZ>
 __device__ __forceinline__ void stage_rest(const double2 *__restrict__ src, double2 *dst, const TileMap &tm, int me = threadIdx.x) {
     const int b1 = tm.base[1], b2 = tm.base[2], o0 = tm.lo[0], o1 = tm.lo[1] - b1, o2 = tm.lo[2] - b2;
     const int count = UPR * tm.need;
-    for (int t0 = me + U * BS; t0 < count; t0 += U * BS) {
+    int tid = me;                                                  // opaque, as in stage_commit
+    asm volatile("" : "+v"(tid));
+    for (int t0 = tid + U * BS; t0 < count; t0 += U * BS) {
         double2 v[U];
 #pragma unroll
         for (int u = 0; u < U; u++) {

@@ -442,8 +442,10 @@ __global__ __launch_bounds__(BS) void forces_q(PairConst pc, int32_t tcap, int32
     // workgroups b, b + 8, .. share an XCD (round-robin dispatch, speed only): XCD x works on one contiguous eighth of the
     // groups, so that the up to nine workgroups that stage a record find it in that XCD's L2; its workgroups take the
     // groups of that eighth in turn
+    // (group numbers as 32-bit integers: the scalar unit has no 64-bit ordered compare, so a 64-bit g_hi sat in two vector registers
+    // for the whole kernel -- with the two notes below what forces_q<1024, 8, true> spilled around its pair loop)
     const int nx = min(8, (int)gridDim.x), xcd = blockIdx.x % nx, per = ((int)gridDim.x - xcd + nx - 1) / nx;
-    const int64_t g_hi = (int64_t)ngroups * (xcd + 1) / nx;
+    const int g_hi = (int)((int64_t)ngroups * (xcd + 1) / nx);
     const double inv_h = pc.inv_h, inv_dq = pc.inv_dq;
     auto dw_of = [&](double q) {
         const double t = knot_coord(q, inv_dq);
@@ -466,7 +468,7 @@ __global__ __launch_bounds__(BS) void forces_q(PairConst pc, int32_t tcap, int32
         sp[3] = make_double2(0.0, 1.0); sp[4] = make_double2(0.0, 0.0); sp[5] = make_double2(0.0, 0.0);
     }
     // what does not need the tile is fetched one group ahead: the plan and the dealt target of this thread
-    int64_t group = (int64_t)ngroups * xcd / nx + blockIdx.x / nx;
+    int group = (int)((int64_t)ngroups * xcd / nx) + (int)blockIdx.x / nx;
     TileMap tm_next;
     int2 deal_next = make_int2(0, -1);
     if (group < g_hi) {
@@ -481,7 +483,7 @@ __global__ __launch_bounds__(BS) void forces_q(PairConst pc, int32_t tcap, int32
     unsigned long long ph_last = __builtin_readcyclecounter();
 #endif
     for (; group < g_hi; group += per) {
-        const int64_t base = group * T;
+        const int64_t base = (int64_t)group * T;
         const TileMap tm = tm_next;
         const int2 dl = deal_next;
         if (group + per < g_hi) {
@@ -509,7 +511,9 @@ __global__ __launch_bounds__(BS) void forces_q(PairConst pc, int32_t tcap, int32
         // takes half s >> 2, a row per trip (ent_pos, tile_common.hpp)
         const int ntrip = __builtin_amdgcn_readfirstlane(wave_max_i32((cnt + LPT - 1) / LPT));
         const int nrow = (ntrip + TPR - 1) / TPR;
-        const uint32_t *lp = reinterpret_cast<const uint32_t *>(nlist) + (((size_t)(self >> 6) * (cap >> 3)) * 64 + (self & 63)) * 4 + (sub & 3);
+        // (the lane's part of the address as ONE 32-bit offset: written (.. * 64 + (self & 63)) * 4 + (sub & 3), the thread-constant
+        // (sub & 3) was kept as a 64-bit term of its own across the group loop)
+        const uint32_t *lp = reinterpret_cast<const uint32_t *>(nlist) + ((size_t)(self >> 6) * (cap >> 3)) * 256 + (uint32_t)(((self & 63) << 2) | (sub & 3));
         // the first two list rows are asked for ahead of the tile; the target's record is read from the tile: one round trip to
         // memory for the tile where there were four (tile in two trips, then the record, then the rows)
         uint32_t wa = lp[0];
@@ -600,9 +604,10 @@ __global__ __launch_bounds__(BS) void forces_q(PairConst pc, int32_t tcap, int32
             PairConst pe;
             pe.G = ea.G; pe.alpha_floor = ea.alpha_floor; pe.alpha_decay = ea.alpha_decay; pe.inv_dwnorm = ea.inv_dwnorm; pe.ns = ea.ns;
             double *const out = sub == 0 ? ea.ax : (sub == 1 ? ea.ay : (sub == 2 ? ea.az : ea.du));
-            const double start = (ea.grav && sub < 3) ? out[i] : 0.0;
-            out[i] = force_channel(pe, sk, A, f, start, sub);
-            if (sub == 3) ea.dalpha[i] = alpha_rate(pe, inv_h, B.w, Cc.x, Cc.y, f);
+            // (self == i for a live target: the 32-bit index is what the pair loop keeps anyway)
+            const double start = (ea.grav && sub < 3) ? out[self] : 0.0;
+            out[self] = force_channel(pe, sk, A, f, start, sub);
+            if (sub == 3) ea.dalpha[self] = alpha_rate(pe, inv_h, B.w, Cc.x, Cc.y, f);
         }
 #ifdef SPH_PHASE_CLOCKS
         pa_n++;
