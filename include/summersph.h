@@ -624,6 +624,66 @@ int sph_groups(sph_ctx *ctx, const sph_groups_desc *d, int32_t *host_labels, int
 int sph_groups_dev(sph_ctx *ctx, const sph_groups_desc *d, int32_t *d_labels, int64_t n_labels, double *d_table,
                    int64_t max_groups, int64_t *d_n_groups);
 
+/* ---- density-peak clumps: the basins of the density field of the owned gas, merged across high saddles (a HOP /
+ *      watershed finder: where friends-of-friends percolates through a disc, this separates a fragment from its arm) ------
+ * Select   as sph_groups: the owned gas with rho >= rho_min strictly inside the clip box, finite positions; rho is what
+ *          sph_download_field(SPH_F_RHO) returns (SPH_ERR_STATE when stale).  A non-finite rho is never selected.
+ * Neighbours  selected i and j are neighbours iff sph_groups would link them: d2 < b * b, d2 = (dx dx + dy dy) + dz dz,
+ *          no fused multiply-adds, b = link or, with SPH_PEAKS_LINK_H, link * max(h_i, h_j) (rounded once).  Symmetric.
+ * Order    a is above b iff rho_a > rho_b, or rho_a == rho_b and id_a < id_b (original ids): a strict total order, so
+ *          plateaus and ties need no special case.
+ * Hop      next[i] = the highest of i and its neighbours; next[i] == i: a raw peak.  peak[i] = the end of i's chain
+ *          (chains strictly ascend, so they end).  The particles of one peak are its basin.
+ * Saddles  every neighbour pair (i, j) with peak[i] != peak[j] has the saddle value s = min(rho_i, rho_j); the edge
+ *          {a, b} between two raw peaks carries S(a, b) = the maximum of s over all such pairs.
+ * Merge    components start as single raw peaks; a component's top is its highest peak.  Edges are taken by S descending,
+ *          ties by the key (min id << 32 | max id) ascending.  For an edge whose ends lie in different components A and
+ *          B, top(A) above top(B): B joins A iff rho(top(B)) < contrast * S (the product rounded once).  contrast = 1
+ *          never merges (S <= rho(top(B)) always): the raw basins.  contrast = +INFINITY merges every edge: the
+ *          friends-of-friends components, labels and columns 0 .. 20 bitwise what sph_groups gives for the same link.
+ * Drop, number  components whose top has rho < peak_min (-INFINITY: none) and components with fewer than min_members
+ *          members are dropped; the rest are numbered by N descending, then the smallest original id ascending.
+ * Labels   as sph_groups: int32 per particle in sph_download_field order, -1 for unselected, dropped and ghosts.
+ * Table    table[g * SPH_PEAKS_NCOL + col]: columns 0 .. 20 are sph_groups' columns with the same per-member
+ *          arithmetic, order rule and reduction shape; 21 S_out = the largest S over the edges whose ends lie in different
+ *          final components (before dropping), 0 if there is none; 22 the number of raw peaks in the component.  Column 19
+ *          (id of the densest member) is the component's top and column 15 its rho.
+ * Counts   int64 counts[SPH_PEAKS_NCOUNT] = {n_groups, raw peaks of the selection, distinct peak-peak edges}.
+ * Order    every decision is a comparison, S is an integer maximum over bit patterns and the table follows sph_groups'
+ *          order rule: labels, counts and table are bitwise the same over repeated calls, over the context's sorted order
+ *          and over dense or hashed grids.  No float atomics.
+ * cost     the merge is a sequential union-find over the edge list (about n / 10 edges and n / 10 raw peaks in a disc),
+ *          run on the host.  Both forms therefore wait for the stream three times: for the number of neighbour pairs
+ *          that cross basins and of raw peaks (12 bytes; the pair buffer is sized from the first, the scratch grows
+ *          and the pass starts again when it does not fit, so nothing is ever truncated), for the number of distinct
+ *          edges (8 bytes), and for the sorted edge list and the peaks' rho (16 bytes per edge, 8 per peak), after
+ *          which the top and S_out of every peak are uploaded (12 bytes per peak).  The host form copies counts, table
+ *          rows and labels out in one more wait.  The device form (labels, table, counts in device memory) cannot
+ *          promise zero synchronisations as sph_groups_dev does; a selected h <= 0 or non-finite under LINK_H shows
+ *          there as counts[0] == -1 with every label -1.  No state, field, statistic (other than device_bytes: the
+ *          render's scratch), flag, grid, list or dt of the context changes; a run that calls sph_peaks after every step
+ *          is bitwise the run without it.
+ * SPH_ERR_ARG: as sph_groups (null descriptor or counts, link <= 0 or non-finite, NaN rho_min or clip, min_members < 1,
+ * labels with n_labels != sph_count, max_groups < 0, a table with max_groups == 0, unknown flags, reserved != 0), and
+ * contrast < 1 or NaN, NaN peak_min.  SPH_ERR_STATE: as sph_groups.  An empty selection gives 0 groups. */
+#define SPH_PEAKS_LINK_H   1         /* b = link * max(h_i, h_j)                                                 */
+#define SPH_PEAKS_NCOL     23        /* table columns per group                                                  */
+#define SPH_PEAKS_NCOUNT   3         /* n_groups, raw peaks, edges                                               */
+typedef struct sph_peaks_desc {
+    double  link;                    /* neighbour radius (LINK_H: in units of h), finite, > 0                    */
+    double  rho_min;                 /* rho >= rho_min; -INFINITY: no cut                                        */
+    double  peak_min;                /* components whose top has rho < peak_min are dropped; -INFINITY: none     */
+    double  contrast;                /* >= 1; 1: raw basins, +INFINITY: friends-of-friends                       */
+    double  clip_lo[3], clip_hi[3];  /* strict particle clip box; -INFINITY / +INFINITY = none                   */
+    int64_t min_members;             /* >= 1                                                                     */
+    int32_t flags;                   /* SPH_PEAKS_LINK_H                                                         */
+    int32_t reserved;                /* must be 0                                                                */
+} sph_peaks_desc;                    /* 96 bytes */
+int sph_peaks(sph_ctx *ctx, const sph_peaks_desc *d, int32_t *host_labels, int64_t n_labels, double *host_table,
+              int64_t max_groups, int64_t *counts);
+int sph_peaks_dev(sph_ctx *ctx, const sph_peaks_desc *d, int32_t *d_labels, int64_t n_labels, double *d_table,
+                  int64_t max_groups, int64_t *d_counts);
+
 /* ---- SPH gradients: the gradient of up to four per-particle fields at every owned gas particle (vorticity, divergence,
  *      gradients of rho, u, P or any caller's array), in the standard difference form or the matrix-corrected form -------
  * Kernel   the renders' analytic cubic spline with the DOUBLE-precision pi (not the simulation's REAL(4)-pi table):

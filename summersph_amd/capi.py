@@ -46,6 +46,7 @@ SYMBOLS = [
     "sph_profile", "sph_profile_dev", "sph_profile_finish",
     "sph_energy", "sph_energy_dev",
     "sph_groups", "sph_groups_dev",
+    "sph_peaks", "sph_peaks_dev",
     "sph_gradients", "sph_gradients_dev",
     "sph_sample", "sph_sample_dev",
     "sph_trace", "sph_trace_dev",
@@ -78,6 +79,13 @@ GROUPS_NCOL = 21
 # sph_groups' table columns (include/summersph.h, "Table")
 GROUPS_COLUMNS = ["N", "M", "x", "y", "z", "vx", "vy", "vz", "r_rms", "r_max", "Sx", "Sy", "Sz", "K_int", "U", "rho_max",
                   "x_dense", "y_dense", "z_dense", "id_dense", "id_min"]
+PEAKS_LINK_H = 1
+PEAKS_NCOL = 23
+PEAKS_NCOUNT = 3
+# sph_peaks' table columns (include/summersph.h, "Table"): sph_groups' columns, the highest saddle towards another
+# component and the raw peaks merged into this one; and its counts
+PEAKS_COLUMNS = GROUPS_COLUMNS + ["S_out", "n_peaks"]
+PEAKS_COUNTS = ["n_groups", "n_raw_peaks", "n_edges"]
 GRAD_CORRECTED = 1
 GRAD_MAX_FIELDS = 4
 GRAD_VALUES = -1
@@ -188,6 +196,32 @@ def groups_table(table: np.ndarray) -> np.ndarray:
     """(n, GROUPS_NCOL) float64 -> a structured array of n records with the GROUPS_COLUMNS names"""
     t = np.ascontiguousarray(table, dtype=np.float64).reshape(-1, GROUPS_NCOL)
     return t.view([(c, np.float64) for c in GROUPS_COLUMNS]).reshape(-1)
+
+
+class PeaksDesc(C.Structure):
+    """sph_peaks_desc (include/summersph.h): neighbour radius, rho cut, peak cut, contrast, strict clip box, min_members,
+    flags (PEAKS_LINK_H), reserved"""
+    _fields_ = [("link", C.c_double), ("rho_min", C.c_double), ("peak_min", C.c_double), ("contrast", C.c_double),
+                ("clip_lo", C.c_double * 3), ("clip_hi", C.c_double * 3), ("min_members", C.c_int64), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+def peaks_desc(link, contrast=2.0, rho_min=-np.inf, peak_min=-np.inf, min_members=1, link_h=False, clip=None) -> PeaksDesc:
+    """The descriptor of Context.peaks' arguments (see there)."""
+    d = PeaksDesc()
+    d.link, d.rho_min, d.peak_min, d.contrast = float(link), float(rho_min), float(peak_min), float(contrast)
+    d.min_members = int(min_members)
+    d.flags = PEAKS_LINK_H if link_h else 0
+    lo, hi = ((-np.inf,) * 3, (np.inf,) * 3) if clip is None else clip
+    d.clip_lo[:] = [float(v) for v in lo]
+    d.clip_hi[:] = [float(v) for v in hi]
+    return d
+
+
+def peaks_table(table: np.ndarray) -> np.ndarray:
+    """(n, PEAKS_NCOL) float64 -> a structured array of n records with the PEAKS_COLUMNS names"""
+    t = np.ascontiguousarray(table, dtype=np.float64).reshape(-1, PEAKS_NCOL)
+    return t.view([(c, np.float64) for c in PEAKS_COLUMNS]).reshape(-1)
 
 
 class GradientsDesc(C.Structure):
@@ -620,6 +654,10 @@ def load():
                                C.POINTER(C.c_int64)]
     lib.sph_groups_dev.argtypes = [C.c_void_p, C.POINTER(GroupsDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                    C.c_void_p]
+    lib.sph_peaks.argtypes = [C.c_void_p, C.POINTER(PeaksDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                              C.POINTER(C.c_int64)]
+    lib.sph_peaks_dev.argtypes = [C.c_void_p, C.POINTER(PeaksDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                  C.c_void_p]
     lib.sph_gradients.argtypes = [C.c_void_p, C.POINTER(GradientsDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     for fn in (lib.sph_sample, lib.sph_sample_dev):
@@ -1154,6 +1192,46 @@ class Context:
                                      None if tab is None else tab.ctypes.data, mg, C.byref(ng)))
         ng = int(ng.value)
         return lab, (None if tab is None else groups_table(tab[:min(ng, mg)])), ng
+
+    # ---- density-peak clumps (sph_peaks) ---------------------------------------------------------
+    def peaks(self, link, contrast=2.0, rho_min=-np.inf, peak_min=-np.inf, min_members=1, link_h=False, clip=None,
+              max_groups=None, labels=True, device=False):
+        """The density-peak clumps of the owned gas (include/summersph.h, sph_peaks): among the particles Context.groups
+        would select and link, every particle climbs to its densest neighbour; the basins merge across saddles S with
+        rho(lower top) < contrast * S (1: the raw basins, inf: the friends-of-friends groups); components whose top is below
+        peak_min or with fewer than min_members members are dropped, the rest numbered by N descending, then the smallest id.
+        Returns (labels, table, n_groups, counts): labels and table keyed as Context.groups' are (PEAKS_COLUMNS: the
+        GROUPS_COLUMNS, S_out and n_peaks), counts = (n_groups, n_raw_peaks, n_edges).  device=True: labels, the
+        (max_groups, PEAKS_NCOL) table and the three counts are torch tensors on the context's GPU (sph_peaks_dev; counts[0]
+        == -1 tells of a bad h under link_h); the call still waits for the stream, since the merge runs on the host.  The
+        descriptor used is left in self.peaks_desc."""
+        d = peaks_desc(link, contrast, rho_min, peak_min, min_members, link_h, clip)
+        n = self.n
+        mg = n if max_groups is None else int(max_groups)
+        self.peaks_desc = d
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            lab = torch.empty(n, dtype=torch.int32, device=dev) if labels else None
+            tab = torch.empty((mg, PEAKS_NCOL), dtype=torch.float64, device=dev) if mg > 0 else None
+            cnt = torch.empty(PEAKS_NCOUNT, dtype=torch.int64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
+            self._ck(self.lib.sph_peaks_dev(self._h, C.byref(d), C.c_void_p(lab.data_ptr()) if lab is not None else None, n,
+                                            C.c_void_p(tab.data_ptr()) if tab is not None else None, mg,
+                                            C.c_void_p(cnt.data_ptr())))
+            st = self.stream()                                    # torch's later work waits for the clumps
+            if st:
+                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
+            else:
+                torch.cuda.synchronize(dev)
+            return lab, tab, int(cnt[0].item()), cnt
+        lab = np.empty(n, dtype=np.int32) if labels else None
+        tab = np.empty((mg, PEAKS_NCOL)) if mg > 0 else None
+        cnt = (C.c_int64 * PEAKS_NCOUNT)()
+        self._ck(self.lib.sph_peaks(self._h, C.byref(d), None if lab is None else lab.ctypes.data, n,
+                                    None if tab is None else tab.ctypes.data, mg, cnt))
+        ng = int(cnt[0])
+        return lab, (None if tab is None else peaks_table(tab[:min(ng, mg)])), ng, tuple(int(v) for v in cnt)
 
     # ---- SPH gradients (sph_gradients) ------------------------------------------------------------
     def gradients(self, fields=("vx", "vy", "vz"), values=None, corrected=True, h=None, clip=None, rho=False, device=False):

@@ -1275,6 +1275,20 @@ int sph_groups_dev(sph_ctx *c, const sph_groups_desc *d, int32_t *d_labels, int6
     return groups_run(c, d, d_labels, n_labels, d_table, max_groups, d_n_groups, false, field_ready);
 }
 
+int sph_peaks(sph_ctx *c, const sph_peaks_desc *d, int32_t *host_labels, int64_t n_labels, double *host_table,
+              int64_t max_groups, int64_t *counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return peaks_run(c, d, host_labels, n_labels, host_table, max_groups, counts, true, field_ready);
+}
+
+int sph_peaks_dev(sph_ctx *c, const sph_peaks_desc *d, int32_t *d_labels, int64_t n_labels, double *d_table,
+                  int64_t max_groups, int64_t *d_counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return peaks_run(c, d, d_labels, n_labels, d_table, max_groups, d_counts, false, field_ready);
+}
+
 int sph_gradients(sph_ctx *c, const sph_gradients_desc *d, const double *values, double *host_out, int64_t n_out,
                   double *host_rho, int64_t *n_targets, int64_t *n_singular) {
     if (!c) return SPH_ERR_ARG;

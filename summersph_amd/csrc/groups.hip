@@ -27,6 +27,8 @@
 //                    (pieces of 1024 sorted positions from the group's start, one wavefront each, then one wavefront per
 //                    group); R = sum m r / M and V = sum m v / M stay on the device
 //   groups_pieces<2> / groups_final<2>: the moments about R and V, r_max, rho_max and its member -> the table rows
+// groups_select .. groups_tails are the host function groups_front and groups_count .. groups_final the host function
+// groups_tail (sph_internal.hpp): sph_peaks (peaks.hip) runs the same two around its own partition.
 //
 // Union-find (groups_link).  parent[] is indexed by original id and every link points to a smaller id, so a root is the
 // smallest id of its tree and no cycle can form.  A find follows parent links with plain loads; such a load may return an
@@ -64,24 +66,11 @@ constexpr int NGS = 9;                     // per group after the first pass: N,
 constexpr int JUMP = 16;                   // links a lane follows per jump round
 constexpr int COUNT_RUN = 16;              // consecutive ids per thread of groups_count
 
-struct Sel {
-    double rho_min, clip_lo[3], clip_hi[3];
-    double link, fixed_h;                  // fixed_h: h of every particle when hf is null
-    const double *hf;                      // SPH_F_H (variable h) or null
-    int32_t link_h;
-};
-
-// on the device, written by groups_box (and n_groups by groups_number)
-struct Info {
-    double lo[3];
-    double inv_e;                          // 1 / cell edge
-    int64_t n_sel;                         // selected particles (0 when bad)
-    int64_t n_groups;                      // -1: a selected particle has a bad h under LINK_H
-    int32_t bad;
-};
+using Sel = GroupsSel;                     // sph_internal.hpp: shared with peaks.hip
+using Info = GroupsInfo;
 
 __device__ __forceinline__ bool selected(const Sel &s, double x, double y, double z, double rho) {
-    return rho >= s.rho_min && s.clip_lo[0] < x && x < s.clip_hi[0] && s.clip_lo[1] < y && y < s.clip_hi[1] &&
+    return rho >= s.rho_min && rho <= s.rho_cap && s.clip_lo[0] < x && x < s.clip_hi[0] && s.clip_lo[1] < y && y < s.clip_hi[1] &&
            s.clip_lo[2] < z && z < s.clip_hi[2];
 }
 
@@ -473,6 +462,92 @@ __global__ __launch_bounds__(GB) void groups_final(const int32_t *__restrict__ s
 
 }  // namespace
 
+void groups_sizes(const sph_ctx *c, int64_t min_members, int64_t max_groups, GroupsWork &w) {
+    w.ns = c->cap > 0 ? c->n_slots : 0;
+    w.no = c->n_owned;
+    w.gb = w.no / min_members;                                   // groups there can be at most
+    w.rows = std::min(max_groups, w.gb);                         // table rows written
+    w.n_pieces = w.ns / PIECE + w.gb + 1;
+    w.nb = (int)std::min<int64_t>((w.ns + GB - 1) / GB, BOX_BLOCKS);
+    w.tl = 1;
+    while (w.tl < 2 * w.ns) w.tl <<= 1;                          // hash table: load <= 1/2
+    size_t sort_pairs = 0, sort_keys = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, sort_pairs, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
+                                    (uint32_t *)nullptr, (size_t)w.ns, 0u, 64u, c->stream);
+    (void)rocprim::radix_sort_keys(nullptr, sort_keys, (uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)w.no, 0u, 64u, c->stream);
+    w.sort_bytes = std::max(sort_pairs, sort_keys);
+}
+
+void groups_take(GroupsWork &w, Carve &cv) {
+    const int64_t ns = w.ns, no = w.no;
+    w.keys = cv.take<uint64_t>(ns);
+    w.keys_alt = cv.take<uint64_t>(ns);
+    w.vals = cv.take<uint32_t>(ns);
+    w.vals_alt = cv.take<uint32_t>(ns);
+    w.sort_tmp = cv.take<char>(w.sort_bytes);
+    w.rec = cv.take<double4>(ns);
+    w.sid = cv.take<int32_t>(ns);
+    w.tab = cv.take<Ent>(w.tl);
+    w.parent = cv.take<int32_t>(no);
+    w.cnt = cv.take<int32_t>(no);
+    w.gnum = cv.take<int32_t>(no);
+    w.box_part = cv.take<double>(9 * (size_t)w.nb);
+    w.info = cv.take<Info>(1);
+    w.start = cv.take<int32_t>(w.gb + 1);
+    w.part = cv.take<double>(NP2 * (size_t)w.n_pieces);
+    w.gstat = cv.take<double>(NGS * (size_t)std::max<int64_t>(w.gb, 1));
+}
+
+int groups_front(sph_ctx *c, const GroupsSel &s, GroupsWork &w) {
+    hipStream_t st = c->stream;
+    const int64_t ns = w.ns, no = w.no;
+    const double *x = c->f[SPH_F_X], *y = c->f[SPH_F_Y], *z = c->f[SPH_F_Z], *rho = c->f[SPH_F_RHO];
+    // selection, box, cell edge
+    groups_select<<<dim3((unsigned)w.nb), dim3(GB), 0, st>>>(x, y, z, rho, c->orig, ns, no, s, w.parent, w.cnt, w.gnum, w.box_part);
+    groups_box<<<dim3(1), dim3(WAVE), 0, st>>>(w.box_part, w.nb, s, w.info);
+    SPH_HIP(hipGetLastError());
+    // cell keys, sort, hash table over the occupied cells
+    groups_keys<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(x, y, z, rho, c->orig, ns, no, s, w.info, w.keys, w.vals);
+    size_t tmp = w.sort_bytes;
+    SPH_HIP(rocprim::radix_sort_pairs(w.sort_tmp, tmp, w.keys, w.keys_alt, w.vals, w.vals_alt, (size_t)ns, 0u, 64u, st));
+    SPH_HIP(hipMemsetAsync(w.tab, 0xff, sizeof(Ent) * (size_t)w.tl, st));
+    groups_gather<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(x, y, z, c->orig, s, w.keys_alt, w.vals_alt, w.info, ns, w.rec, w.sid,
+                                                              w.tab, (uint64_t)(w.tl - 1));
+    groups_tails<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(w.keys_alt, w.info, ns, w.tab, (uint64_t)(w.tl - 1));
+    SPH_HIP(hipGetLastError());
+    return SPH_OK;
+}
+
+int groups_tail(sph_ctx *c, GroupsWork &w, int64_t min_members, int32_t *d_labels, double *d_table) {
+    hipStream_t st = c->stream;
+    const int64_t n = c->n, ns = w.ns, no = w.no, gb = w.gb, rows = w.rows, n_pieces = w.n_pieces;
+    const double *x = c->f[SPH_F_X], *y = c->f[SPH_F_Y], *z = c->f[SPH_F_Z], *rho = c->f[SPH_F_RHO];
+    groups_count<<<dim3(blocks((no + COUNT_RUN - 1) / COUNT_RUN, GB)), dim3(GB), 0, st>>>(w.parent, no, w.cnt);
+    // numbering: (N descending, root id)
+    groups_root_keys<<<dim3(blocks(no, GB)), dim3(GB), 0, st>>>(w.parent, w.cnt, no, min_members, w.info, w.keys);
+    size_t tmp = w.sort_bytes;
+    SPH_HIP(rocprim::radix_sort_keys(w.sort_tmp, tmp, w.keys, w.keys_alt, (size_t)no, 0u, 64u, st));
+    groups_number<<<dim3(blocks(no, GB)), dim3(GB), 0, st>>>(w.keys_alt, no, w.gnum, w.info);
+    // members in (group, id) order, labels
+    if (d_labels && n > no) SPH_HIP(hipMemsetAsync(d_labels + no, 0xff, (size_t)(n - no) * sizeof(int32_t), st));   // ghosts
+    groups_members<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(c->orig, ns, no, w.parent, w.gnum, w.keys, w.vals, d_labels);
+    tmp = w.sort_bytes;
+    SPH_HIP(rocprim::radix_sort_pairs(w.sort_tmp, tmp, w.keys, w.keys_alt, w.vals, w.vals_alt, (size_t)ns, 0u, 64u, st));
+    groups_starts<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(w.keys_alt, ns, w.start);
+    SPH_HIP(hipGetLastError());
+    // the two reductions
+    Fields f{x, y, z, c->f[SPH_F_VX], c->f[SPH_F_VY], c->f[SPH_F_VZ], c->f[SPH_F_U], c->f[SPH_F_M], rho, c->orig};
+    const int wpb = GB / WAVE;
+    groups_pieces<1><<<dim3(blocks(n_pieces, wpb)), dim3(GB), 0, st>>>(f, w.vals_alt, w.start, w.info, n_pieces, w.gstat, w.part);
+    groups_final<1><<<dim3(blocks(gb, wpb)), dim3(GB), 0, st>>>(w.start, w.info, gb, w.part, w.keys_alt, f, w.gstat, d_table, rows);
+    if (rows > 0) {
+        groups_pieces<2><<<dim3(blocks(n_pieces, wpb)), dim3(GB), 0, st>>>(f, w.vals_alt, w.start, w.info, n_pieces, w.gstat, w.part);
+        groups_final<2><<<dim3(blocks(rows, wpb)), dim3(GB), 0, st>>>(w.start, w.info, gb, w.part, w.keys_alt, f, w.gstat, d_table, rows);
+    }
+    SPH_HIP(hipGetLastError());
+    return SPH_OK;
+}
+
 int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_labels, double *table, int64_t max_groups,
                int64_t *n_groups, bool host, bool (*ready)(const sph_ctx *, int)) {
     const char *who = "sph_groups";
@@ -509,42 +584,13 @@ int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_
         }
         return SPH_OK;
     }
-    const int64_t gb = no / d->min_members;                      // groups there can be at most
-    const int64_t rows = std::min(max_groups, gb);               // table rows written
-    const int64_t n_pieces = ns / PIECE + gb + 1;
-    const int nb = (int)std::min<int64_t>((ns + GB - 1) / GB, BOX_BLOCKS);
-    int64_t tl = 1;
-    while (tl < 2 * ns) tl <<= 1;                                // hash table: load <= 1/2
-    size_t sort_pairs = 0, sort_keys = 0;
-    SPH_HIP(rocprim::radix_sort_pairs(nullptr, sort_pairs, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                      (uint32_t *)nullptr, (size_t)ns, 0u, 64u, st));
-    SPH_HIP(rocprim::radix_sort_keys(nullptr, sort_keys, (uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)no, 0u, 64u, st));
-    const size_t sort_bytes = std::max(sort_pairs, sort_keys);
-    uint64_t *keys, *keys_alt;
-    uint32_t *vals, *vals_alt;
-    char *sort_tmp;
-    double4 *rec;
-    Ent *tab;
-    Info *info;
-    int32_t *sid, *parent, *cnt, *gnum, *start, *h_labels;
-    double *box_part, *part, *gstat, *h_table;
+    GroupsWork w{};
+    groups_sizes(c, d->min_members, max_groups, w);
+    const int64_t rows = w.rows;
+    int32_t *h_labels;
+    double *h_table;
     auto layout = [&](Carve cv) {
-        keys = cv.take<uint64_t>(ns);
-        keys_alt = cv.take<uint64_t>(ns);
-        vals = cv.take<uint32_t>(ns);
-        vals_alt = cv.take<uint32_t>(ns);
-        sort_tmp = cv.take<char>(sort_bytes);
-        rec = cv.take<double4>(ns);
-        sid = cv.take<int32_t>(ns);
-        tab = cv.take<Ent>(tl);
-        parent = cv.take<int32_t>(no);
-        cnt = cv.take<int32_t>(no);
-        gnum = cv.take<int32_t>(no);
-        box_part = cv.take<double>(9 * (size_t)nb);
-        info = cv.take<Info>(1);
-        start = cv.take<int32_t>(gb + 1);
-        part = cv.take<double>(NP2 * (size_t)n_pieces);
-        gstat = cv.take<double>(NGS * (size_t)std::max<int64_t>(gb, 1));
+        groups_take(w, cv);
         h_labels = cv.take<int32_t>(host && labels ? n : 0);                     // the host form's device copies
         h_table = cv.take<double>(host ? SPH_GROUPS_NCOL * (size_t)rows : 0);
         return cv.bytes;
@@ -558,56 +604,23 @@ int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_
 
     Sel s{};
     s.rho_min = d->rho_min;
+    s.rho_cap = INFINITY;
     for (int a = 0; a < 3; a++) { s.clip_lo[a] = d->clip_lo[a]; s.clip_hi[a] = d->clip_hi[a]; }
     s.link = d->link;
     s.fixed_h = c->p.h;
     s.hf = c->variable ? c->f[SPH_F_H] : nullptr;
     s.link_h = link_h ? 1 : 0;
     const double b2 = d->link * d->link;
-    const double *x = c->f[SPH_F_X], *y = c->f[SPH_F_Y], *z = c->f[SPH_F_Z], *rho = c->f[SPH_F_RHO];
-
-    // selection, box, cell edge
-    groups_select<<<dim3((unsigned)nb), dim3(GB), 0, st>>>(x, y, z, rho, c->orig, ns, no, s, parent, cnt, gnum, box_part);
-    groups_box<<<dim3(1), dim3(WAVE), 0, st>>>(box_part, nb, s, info);
-    SPH_HIP(hipGetLastError());
-    // cell keys, sort, hash table over the occupied cells
-    groups_keys<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(x, y, z, rho, c->orig, ns, no, s, info, keys, vals);
-    size_t tmp = sort_bytes;
-    SPH_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)ns, 0u, 64u, st));
-    SPH_HIP(hipMemsetAsync(tab, 0xff, sizeof(Ent) * (size_t)tl, st));
-    groups_gather<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(x, y, z, c->orig, s, keys_alt, vals_alt, info, ns, rec, sid, tab,
-                                                              (uint64_t)(tl - 1));
-    groups_tails<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(keys_alt, info, ns, tab, (uint64_t)(tl - 1));
+    SPH_TRY(groups_front(c, s, w));
     // links, then the flattening: every round multiplies the links a pointer spans by JUMP (>= 16^rounds >= no)
-    groups_link<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(rec, sid, keys_alt, info, ns, tab, (uint64_t)(tl - 1), d->link, b2,
-                                                            s.link_h, parent);
+    groups_link<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(w.rec, w.sid, w.keys_alt, w.info, ns, w.tab, (uint64_t)(w.tl - 1), d->link,
+                                                            b2, s.link_h, w.parent);
     SPH_HIP(hipGetLastError());
     int rounds = 1;
     for (double span = JUMP; span < (double)no; span *= JUMP) rounds++;
-    for (int r = 0; r < rounds; r++) groups_jump<<<dim3(blocks(no, GB)), dim3(GB), 0, st>>>(parent, no);
-    groups_count<<<dim3(blocks((no + COUNT_RUN - 1) / COUNT_RUN, GB)), dim3(GB), 0, st>>>(parent, no, cnt);
-    // numbering: (N descending, root id)
-    groups_root_keys<<<dim3(blocks(no, GB)), dim3(GB), 0, st>>>(parent, cnt, no, d->min_members, info, keys);
-    tmp = sort_bytes;
-    SPH_HIP(rocprim::radix_sort_keys(sort_tmp, tmp, keys, keys_alt, (size_t)no, 0u, 64u, st));
-    groups_number<<<dim3(blocks(no, GB)), dim3(GB), 0, st>>>(keys_alt, no, gnum, info);
-    // members in (group, id) order, labels
-    if (d_labels && n > no) SPH_HIP(hipMemsetAsync(d_labels + no, 0xff, (size_t)(n - no) * sizeof(int32_t), st));   // ghosts
-    groups_members<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(c->orig, ns, no, parent, gnum, keys, vals, d_labels);
-    tmp = sort_bytes;
-    SPH_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)ns, 0u, 64u, st));
-    groups_starts<<<dim3(blocks(ns, GB)), dim3(GB), 0, st>>>(keys_alt, ns, start);
-    SPH_HIP(hipGetLastError());
-    // the two reductions
-    Fields f{x, y, z, c->f[SPH_F_VX], c->f[SPH_F_VY], c->f[SPH_F_VZ], c->f[SPH_F_U], c->f[SPH_F_M], rho, c->orig};
-    const int wpb = GB / WAVE;
-    groups_pieces<1><<<dim3(blocks(n_pieces, wpb)), dim3(GB), 0, st>>>(f, vals_alt, start, info, n_pieces, gstat, part);
-    groups_final<1><<<dim3(blocks(gb, wpb)), dim3(GB), 0, st>>>(start, info, gb, part, keys_alt, f, gstat, d_table, rows);
-    if (rows > 0) {
-        groups_pieces<2><<<dim3(blocks(n_pieces, wpb)), dim3(GB), 0, st>>>(f, vals_alt, start, info, n_pieces, gstat, part);
-        groups_final<2><<<dim3(blocks(rows, wpb)), dim3(GB), 0, st>>>(start, info, gb, part, keys_alt, f, gstat, d_table, rows);
-    }
-    SPH_HIP(hipGetLastError());
+    for (int r = 0; r < rounds; r++) groups_jump<<<dim3(blocks(no, GB)), dim3(GB), 0, st>>>(w.parent, no);
+    SPH_TRY(groups_tail(c, w, d->min_members, d_labels, d_table));
+    const Info *info = w.info;
     if (!host) {
         SPH_HIP(hipMemcpyAsync(n_groups, &info->n_groups, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
         return SPH_OK;

@@ -433,6 +433,47 @@ int stage_sources(sph_ctx *c, double *rec, double *box_part, double bb[6]);
 // form; ready = sph_download_field's rule
 int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_labels, double *table, int64_t max_groups,
                int64_t *n_groups, bool host, bool (*ready)(const sph_ctx *, int));
+// sph_groups' front end (selection, box, cell keys, sort, records and hashed cell table) and its tail (members per root,
+// numbering, member sort, labels, the two table reductions) as host functions, shared with sph_peaks (peaks.hip), which
+// puts its own partition between them.  Between the two, parent[id] is the root of every selected owned id (a root is
+// the smallest id of its set and its own parent) and -1 for every other; cnt[] is 0 and gnum[] -1.
+struct Ent;                                // cell_table.hpp
+struct GroupsSel {                         // the selection and the link, by value to the kernels
+    double rho_min, rho_cap, clip_lo[3], clip_hi[3];     // rho_min <= rho <= rho_cap (+INFINITY: sph_groups' rule)
+    double link, fixed_h;                  // fixed_h: h of every particle when hf is null
+    const double *hf;                      // SPH_F_H (variable h) or null
+    int32_t link_h;
+};
+struct GroupsInfo {                        // on the device, written by groups_box (and n_groups by groups_number)
+    double lo[3];
+    double inv_e;                          // 1 / cell edge
+    int64_t n_sel;                         // selected particles (0 when bad)
+    int64_t n_groups;                      // -1: a selected particle has a bad h under LINK_H
+    int32_t bad;
+};
+struct GroupsWork {                        // sizes (groups_sizes) and the buffers inside the call's scratch (groups_take)
+    int64_t ns, no, gb, rows, n_pieces, tl;
+    int nb;
+    size_t sort_bytes;
+    uint64_t *keys, *keys_alt;             // after groups_front: keys_alt / vals_alt = the sorted cell keys and their slots
+    uint32_t *vals, *vals_alt;
+    char *sort_tmp;
+    double4 *rec;                          // {x, y, z, h} in sorted order
+    int32_t *sid;                          // original id in sorted order
+    Ent *tab;                              // tl entries
+    GroupsInfo *info;
+    int32_t *parent, *cnt, *gnum, *start;
+    double *box_part, *part, *gstat;
+};
+void groups_sizes(const sph_ctx *c, int64_t min_members, int64_t max_groups, GroupsWork &w);   // max_groups: 0 without a table
+void groups_take(GroupsWork &w, Carve &cv);
+int groups_front(sph_ctx *c, const GroupsSel &s, GroupsWork &w);
+// d_table: w.rows rows of SPH_GROUPS_NCOL doubles (device memory) or null with w.rows == 0; d_labels: c->n int32 or null
+int groups_tail(sph_ctx *c, GroupsWork &w, int64_t min_members, int32_t *d_labels, double *d_table);
+// density-peak clumps (peaks.hip): host form (labels / table / counts[3] host memory) or device form; both wait for the
+// stream (the merge runs on the host); ready = sph_download_field's rule
+int peaks_run(sph_ctx *c, const sph_peaks_desc *d, int32_t *labels, int64_t n_labels, double *table, int64_t max_groups,
+              int64_t *counts, bool host, bool (*ready)(const sph_ctx *, int));
 // SPH gradients (gradients.hip): host form (values / out / rho host memory, counts[2] host, one synchronisation) or device
 // form (counts[2] device memory or null); ready = sph_download_field's rule
 int gradients_run(sph_ctx *c, const sph_gradients_desc *d, const double *values, double *out, int64_t n_out, double *rho_out,

@@ -40,6 +40,8 @@ module sph_hip_binding
   public :: sph_energy, sph_energy_dev, SPH_ENERGY_NSUM
   ! friends-of-friends groups (clumps of the owned gas: labels per particle and a table per group)
   public :: sph_groups_desc, sph_groups, sph_groups_dev, SPH_GROUPS_LINK_H, SPH_GROUPS_NCOL
+  ! density-peak clumps (basins of the density field merged across high saddles: labels, a table per clump, counts)
+  public :: sph_peaks_desc, sph_peaks, sph_peaks_dev, SPH_PEAKS_LINK_H, SPH_PEAKS_NCOL, SPH_PEAKS_NCOUNT
   ! SPH gradients (standard or matrix-corrected) of up to four fields at the owned gas
   public :: sph_gradients_desc, sph_gradients, sph_gradients_dev, SPH_GRAD_CORRECTED, SPH_GRAD_MAX_FIELDS, SPH_GRAD_VALUES
   ! SPH interpolation at arbitrary points (density, fields or the caller's values where the caller wants them)
@@ -76,6 +78,7 @@ module sph_hip_binding
   integer(c_int32_t), parameter :: SPH_PROFILE_LOG = 1, SPH_PROFILE_AUTO_NORMAL = 2, SPH_PROFILE_NSUM = 20, SPH_PROFILE_NCOL = 29
   integer(c_int32_t), parameter :: SPH_ENERGY_NSUM = 28
   integer(c_int32_t), parameter :: SPH_GROUPS_LINK_H = 1, SPH_GROUPS_NCOL = 21
+  integer(c_int32_t), parameter :: SPH_PEAKS_LINK_H = 1, SPH_PEAKS_NCOL = 23, SPH_PEAKS_NCOUNT = 3
 
   type, bind(C) :: sph_params
     real(c_double) :: h, gamma, gamma_m1
@@ -142,6 +145,16 @@ module sph_hip_binding
     integer(c_int64_t) :: min_members
     integer(c_int32_t) :: flags, reserved
   end type sph_groups_desc
+
+  ! neighbour radius (LINK_H: in units of max(h_i, h_j)), rho >= rho_min, components whose top has rho < peak_min are
+  ! dropped (IEEE -infinity: none), contrast >= 1 (1: raw basins, +infinity: friends-of-friends), strict clip box,
+  ! min_members >= 1, flags, reserved (0).  table(SPH_PEAKS_NCOL, max_groups), counts(SPH_PEAKS_NCOUNT).  96 bytes.
+  type, bind(C) :: sph_peaks_desc
+    real(c_double) :: link, rho_min, peak_min, contrast
+    real(c_double) :: clip_lo(3), clip_hi(3)
+    integer(c_int64_t) :: min_members
+    integer(c_int32_t) :: flags, reserved
+  end type sph_peaks_desc
 
   ! sph_gradients: strict target clip box (+-infinity: none), h (> 0: one h for all; 0: each particle's own), fields
   ! (SPH_F_* or SPH_GRAD_VALUES: row k of values), n_fields 1 .. 4, flags (SPH_GRAD_CORRECTED), reserved (0).  out holds
@@ -691,6 +704,23 @@ module sph_hip_binding
       import :: c_int, c_int64_t, c_ptr, sph_groups_desc
       type(c_ptr), value :: ctx, d_labels, d_table, d_n_groups
       type(sph_groups_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_labels, max_groups
+    end function
+    ! ---- density-peak clumps: as sph_groups, with counts (SPH_PEAKS_NCOUNT int64: groups, raw peaks, edges) in place
+    !      of the count and SPH_PEAKS_NCOL doubles per table row
+    integer(c_int) function sph_peaks(ctx, d, host_labels, n_labels, host_table, max_groups, counts) &
+        bind(C, name='sph_peaks')
+      import :: c_int, c_int64_t, c_ptr, sph_peaks_desc
+      type(c_ptr), value :: ctx, host_labels, host_table
+      type(sph_peaks_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_labels, max_groups
+      integer(c_int64_t), intent(out) :: counts(*)
+    end function
+    integer(c_int) function sph_peaks_dev(ctx, d, d_labels, n_labels, d_table, max_groups, d_counts) &
+        bind(C, name='sph_peaks_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_peaks_desc
+      type(c_ptr), value :: ctx, d_labels, d_table, d_counts
+      type(sph_peaks_desc), intent(in) :: d
       integer(c_int64_t), value :: n_labels, max_groups
     end function
     ! ---- SPH gradients: values (n_fields rows of sph_count doubles, download order, or c_null_ptr), host_out
