@@ -143,15 +143,10 @@ def parse_args(argv=None):
 def main(argv=None) -> int:
     a = parse_args(argv)
     from . import capi
-    from .profile import read_save
+    from .cli import read_save, uploaded_context
     gas, sinks = read_save(a.save, a.variable)
-    names = "x y z vx vy vz u m alpha".split() + (["h"] if a.variable else [])
     used = set(a.axes + a.q)
-    ctx = capi.Context(device=a.device, variable=a.variable)
-    try:
-        ctx.upload({k: np.ascontiguousarray(gas[:, i]) for i, k in enumerate(names)})
-        if sinks.shape[0]:
-            ctx.set_sinks({k: sinks[:, i] for i, k in zip((0, 1, 2, 3, 4, 5, 7), "x y z vx vy vz m".split())})
+    with uploaded_context(gas, sinks, a.variable, a.device) as ctx:
         if used & set(DERIVED + RATES) or a.weight == "volume":
             ctx.density()
         if used & set(RATES):
@@ -173,8 +168,6 @@ def main(argv=None) -> int:
         sums, counts = ctx.binned(a.axes, a.bins, ranges=ranges, log=a.log, q=a.q, weight=a.weight, squares=a.squares)
         d = ctx.binned_desc
         edges = [capi.binned_edges(d, None, k) for k in range(len(a.axes))]
-    finally:
-        ctx.close()
     N, W, mean, disp = finish(sums, len(a.q), a.squares)
     out = {"sums": sums, "N": N, "W": W, "mean": mean, "counts": np.array(counts), "q": np.array(a.q, dtype=str),
            "edges_x": edges[0]}

@@ -650,14 +650,10 @@ def load():
     lib.sph_profile_finish.argtypes = [C.POINTER(ProfileDesc), C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_int64]
     lib.sph_energy.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
     lib.sph_energy_dev.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
-    lib.sph_groups.argtypes = [C.c_void_p, C.POINTER(GroupsDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                               C.POINTER(C.c_int64)]
-    lib.sph_groups_dev.argtypes = [C.c_void_p, C.POINTER(GroupsDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                   C.c_void_p]
-    lib.sph_peaks.argtypes = [C.c_void_p, C.POINTER(PeaksDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                              C.POINTER(C.c_int64)]
-    lib.sph_peaks_dev.argtypes = [C.c_void_p, C.POINTER(PeaksDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                  C.c_void_p]
+    for fn in (lib.sph_groups, lib.sph_groups_dev):
+        fn.argtypes = [C.c_void_p, C.POINTER(GroupsDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    for fn in (lib.sph_peaks, lib.sph_peaks_dev):
+        fn.argtypes = [C.c_void_p, C.POINTER(PeaksDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     lib.sph_gradients.argtypes = [C.c_void_p, C.POINTER(GradientsDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     for fn in (lib.sph_sample, lib.sph_sample_dev):
@@ -671,10 +667,9 @@ def load():
     for fn in (lib.sph_gravity_at, lib.sph_gravity_at_dev):
         fn.argtypes = [C.c_void_p, C.POINTER(GravityAtDesc), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                        C.c_int64, C.c_void_p]
-    lib.sph_bound.argtypes = [C.c_void_p, C.POINTER(BoundDesc), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                              C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
-    lib.sph_bound_dev.argtypes = [C.c_void_p, C.POINTER(BoundDesc), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                  C.c_int64, C.c_void_p, C.c_void_p]
+    for fn in (lib.sph_bound, lib.sph_bound_dev):
+        fn.argtypes = [C.c_void_p, C.POINTER(BoundDesc), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                       C.c_void_p, C.c_void_p]
     for fn in (lib.sph_cube, lib.sph_cube_dev):
         fn.argtypes = [C.c_void_p, C.POINTER(CubeDesc), C.c_void_p, C.c_void_p, C.c_int64]
     for fn in (lib.sph_force_terms, lib.sph_force_terms_dev):
@@ -702,6 +697,154 @@ def _hp(a):
     return a.ctypes.data
 
 
+# ---- the marshalling of the analysis calls -----------------------------------------------------------------------------
+# Every analysis call has a host form (numpy in and out, sph_X) and a device form (torch tensors on the context's GPU,
+# sph_X_dev) with the same argument list.  A Context method is written once against a form object: it allocates the
+# outputs, turns arrays into pointer arguments, holds the int64 counts and runs the call.
+def _on_gpu(t, device: int, dtype=np.float64) -> bool:
+    """t is a torch tensor of the dtype on GPU `device`"""
+    import torch
+    return isinstance(t, torch.Tensor) and t.dtype == getattr(torch, np.dtype(dtype).name) and t.device == torch.device("cuda", device)
+
+
+class _HostForm:
+    device = False
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def empty(self, shape, dtype=np.float64):
+        return np.empty(shape, dtype=dtype)
+
+    @staticmethod
+    def ptr(a):
+        return None if a is None else a.ctypes.data
+
+    @staticmethod
+    def counts(k: int):
+        return np.zeros(k, dtype=np.int64)
+
+    @staticmethod
+    def host(a):
+        return a
+
+    def read(self, cnt) -> tuple:
+        return tuple(int(v) for v in self.host(cnt))
+
+    def call(self, name: str, *args):
+        self.ctx._ck(getattr(self.ctx.lib, name)(self.ctx._h, *args))
+
+
+class _DeviceForm(_HostForm):
+    device = True
+
+    def __init__(self, ctx):
+        import torch
+        self.ctx, self.torch, self.dev = ctx, torch, torch.device("cuda", ctx.device)
+
+    def owns(self, t, dtype=np.float64) -> bool:
+        return _on_gpu(t, self.ctx.device, dtype)
+
+    def empty(self, shape, dtype=np.float64):
+        return self.torch.empty(shape, dtype=getattr(self.torch, np.dtype(dtype).name), device=self.dev)
+
+    @staticmethod
+    def ptr(a):
+        return None if a is None else C.c_void_p(a.data_ptr())
+
+    def counts(self, k: int):
+        return self.empty(k, np.int64)
+
+    @staticmethod
+    def host(a):
+        return a.cpu().numpy()
+
+    def call(self, name: str, *args):
+        """sph_X_dev ordered against torch: the call runs on the context's stream, not torch's"""
+        cuda, ctx = self.torch.cuda, self.ctx
+        cuda.current_stream(self.dev).synchronize()               # the blocks may still be in use by torch's queued work
+        ctx._ck(getattr(ctx.lib, name + "_dev")(ctx._h, *args))
+        st = ctx.stream()                                         # torch's later work on the outputs waits for the call
+        if st:
+            cuda.current_stream(self.dev).wait_stream(cuda.ExternalStream(st, device=self.dev))
+        else:
+            cuda.synchronize(self.dev)
+
+
+def _points(who, points, form, extra=None, noun="point"):
+    """The rule "points as an (M, 3) array or three arrays of M": ([x, y, z, *extra], M).  extra: the optional per-point
+    arrays by name (an absent one stays None).  The host form converts to contiguous float64 numpy; the device form takes
+    contiguous float64 tensors on the context's GPU as they are (an (M, 3) tensor is split into three)."""
+    three = isinstance(points, (tuple, list)) and len(points) == 3
+    more = list((extra or {}).items())
+    if form.device:
+        if three:
+            p = list(points)
+        elif form.owns(points) and points.ndim == 2 and points.shape[1] == 3:
+            p = [points[:, a].contiguous() for a in range(3)]
+        else:
+            p = [None]
+        given = p + [t for _, t in more if t is not None]
+        if not all(form.owns(t) and t.ndim == 1 and t.is_contiguous() and t.numel() == p[0].numel() for t in given):
+            what = f"(and {', '.join(extra)}) must be" if extra else "must be an (M, 3) or three"
+            raise ValueError(f"{who}: device {noun}s {what} contiguous float64 tensors on the context's GPU")
+        return p + [t for _, t in more], p[0].numel()
+    if three:
+        p = [np.ascontiguousarray(t, dtype=np.float64).reshape(-1) for t in points]
+    else:
+        a = np.asarray(points, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"{who}: {noun}s must be an (M, 3) array or three arrays")
+        p = [np.ascontiguousarray(a[:, k]) for k in range(3)]
+    m = p[0].size
+    if p[1].size != m or p[2].size != m:
+        raise ValueError(f"{who}: the three {noun} arrays differ in length")
+    for name, t in more:
+        if t is not None:
+            t = np.ascontiguousarray(t, dtype=np.float64).reshape(-1)
+            if t.size != m:
+                raise ValueError(f"{who}: {name} has {t.size} values for {m} points")
+        p.append(t)
+    return p, m
+
+
+def _values_rows(who, values, rows, n, form, exact=False):
+    """The multi-row rule: values is None or an (n_rows, n) array in the upload order of which the call reads `rows` rows.
+    The host form takes 1-D input as one row and zero-pads the rows nothing reads (row k belongs to field k); the device
+    form takes a contiguous float64 tensor on the context's GPU of at least (exact: exactly) rows * n values."""
+    if values is None:
+        return None
+    if form.device:
+        if not (form.owns(values) and values.is_contiguous()):
+            raise ValueError(f"{who}: device values must be a contiguous float64 tensor on the context's GPU")
+        if exact and values.numel() != rows * n:
+            raise ValueError(f"{who}: values rows of {values.numel() // max(rows, 1)} for {n} particles")
+        if values.numel() < rows * n:
+            raise ValueError(f"{who}: values need {rows} rows of {n}")
+        return values
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    if v.ndim != 2:
+        v = v.reshape(1, -1)
+    if v.shape[1] != n:
+        raise ValueError(f"{who}: values rows of {v.shape[1]} for {n} particles")
+    if v.shape[0] < rows:
+        v = np.concatenate([v, np.zeros((rows - v.shape[0], n))])
+    return v
+
+
+def _values_one(who, values, n, form):
+    """The single-row rule: n values in the upload order, float64 numpy (host form) or a contiguous float64 tensor on the
+    context's GPU (device form)."""
+    if form.device:
+        if not (form.owns(values) and values.is_contiguous() and values.numel() == n):
+            raise ValueError(f"{who}: device values must be a contiguous float64 tensor of sph_count() on the context's GPU")
+        return values
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    if v.size != n:
+        raise ValueError(f"{who}: {v.size} values for {n} particles")
+    return v
+
+
 class Context:
     """Thin object wrapper over an sph_ctx*.  Arrays are float64 numpy (host) unless a method says _dev."""
 
@@ -721,6 +864,10 @@ class Context:
     def _ck(self, st):
         if st != 0:
             raise SphError(st, self.lib.sph_strerror(st).decode() + " -- " + self.lib.sph_last_error(self._h).decode())
+
+    def _form(self, device):
+        """the host or device form of an analysis call"""
+        return _DeviceForm(self) if device else _HostForm(self)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1006,21 +1153,9 @@ class Context:
         self.render_bounds."""
         d = self.render_desc(shape, bounds, axis, h, clip, spacing)
         oshape = self.render_shape(d)
-        size = int(np.prod(oshape, dtype=np.int64))
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            out = torch.empty(oshape, dtype=torch.float64, device=dev)
-            torch.cuda.current_stream(dev).synchronize()          # the block may still be in use by torch's queued work
-            self._ck(self.lib.sph_render_density_dev(self._h, C.byref(d), C.c_void_p(out.data_ptr()), size))
-            st = self.stream()                                    # torch's later work on `out` waits for the render
-            if st:
-                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
-            else:
-                torch.cuda.synchronize(dev)
-        else:
-            out = np.empty(oshape, dtype=np.float64)
-            self._ck(self.lib.sph_render_density(self._h, C.byref(d), out.ctypes.data, size))
+        f = self._form(device)
+        out = f.empty(oshape)
+        f.call("sph_render_density", C.byref(d), f.ptr(out), int(np.prod(oshape, dtype=np.int64)))
         self.render_bounds = (np.array(d.lo[:]), np.array(d.hi[:]))
         return out
 
@@ -1043,49 +1178,24 @@ class Context:
         read from the context, or sph_count() values in the upload order -- a float64 numpy array (host form, device must
         be False) or a contiguous float64 torch tensor on the context's GPU (device form, device must be True).  The
         other arguments and self.render_bounds are render_density's."""
+        f = self._form(device)
         values = None
-        if isinstance(field, str):
-            fid = field
-        else:
-            fid = RENDER_FIELD_VALUES
-            values = field
-            if isinstance(values, np.ndarray):
+        if not isinstance(field, str):                            # the values' kind must be the form's
+            if isinstance(field, np.ndarray):
                 if device:
                     raise ValueError("render_field: a numpy values array renders with device=False")
-                values = np.ascontiguousarray(values, dtype=np.float64)
-                n = values.size
-            else:
-                import torch
-                if not (isinstance(values, torch.Tensor) and values.dtype == torch.float64 and values.is_contiguous()
-                        and values.device == torch.device("cuda", self.device)):
-                    raise ValueError("render_field: values must be float64 numpy or a contiguous float64 tensor on the context's GPU")
-                if not device:
-                    raise ValueError("render_field: a device values tensor renders with device=True")
-                n = values.numel()
-            if n != self.n:
-                raise ValueError(f"render_field: {n} values for {self.n} particles")
-        d = self.render_field_desc(fid, shape, bounds, axis, h, clip, spacing, weight, normalise)
+            elif not (_on_gpu(field, self.device) and field.is_contiguous()):
+                raise ValueError("render_field: values must be float64 numpy or a contiguous float64 tensor on the context's GPU")
+            elif not device:
+                raise ValueError("render_field: a device values tensor renders with device=True")
+            elif field.numel() != self.n:
+                raise ValueError(f"render_field: {field.numel()} values for {self.n} particles")
+            values, field = _values_one("render_field", field, self.n, f), RENDER_FIELD_VALUES
+        d = self.render_field_desc(field, shape, bounds, axis, h, clip, spacing, weight, normalise)
         oshape = self.render_shape(d.base)
-        size = int(np.prod(oshape, dtype=np.int64))
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            out = torch.empty(oshape, dtype=torch.float64, device=dev)
-            wout = torch.empty(oshape, dtype=torch.float64, device=dev) if weight_out else None
-            torch.cuda.current_stream(dev).synchronize()          # the blocks and values may still be in use by torch's work
-            self._ck(self.lib.sph_render_field_dev(self._h, C.byref(d), None if values is None else C.c_void_p(values.data_ptr()),
-                                                   C.c_void_p(out.data_ptr()), None if wout is None else C.c_void_p(wout.data_ptr()),
-                                                   size))
-            st = self.stream()                                    # torch's later work on the outputs waits for the render
-            if st:
-                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
-            else:
-                torch.cuda.synchronize(dev)
-        else:
-            out = np.empty(oshape, dtype=np.float64)
-            wout = np.empty(oshape, dtype=np.float64) if weight_out else None
-            self._ck(self.lib.sph_render_field(self._h, C.byref(d), None if values is None else values.ctypes.data,
-                                               out.ctypes.data, None if wout is None else wout.ctypes.data, size))
+        out = f.empty(oshape)
+        wout = f.empty(oshape) if weight_out else None
+        f.call("sph_render_field", C.byref(d), f.ptr(values), f.ptr(out), f.ptr(wout), int(np.prod(oshape, dtype=np.int64)))
         self.render_bounds = (np.array(d.base.lo[:]), np.array(d.base.hi[:]))
         return (out, wout) if weight_out else out
 
@@ -1101,24 +1211,15 @@ class Context:
         descriptor used (normal written back) is left in self.profile_desc."""
         d = profile_desc(r_min, r_max, n_r, n_phi, log, centre, sink, normal, z_max)
         nb = int(n_r) * int(n_phi)
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            out = torch.empty((nb, PROFILE_NSUM), dtype=torch.float64, device=dev)
-            torch.cuda.current_stream(dev).synchronize()          # the block may still be in use by torch's queued work
-            self._ck(self.lib.sph_profile_dev(self._h, C.byref(d), C.c_void_p(out.data_ptr()), nb))
-            st = self.stream()                                    # torch's later work on `out` waits for the profile
-            if st:
-                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
-            else:
-                torch.cuda.synchronize(dev)
-            self.profile_desc = d
-            return out
-        sums = np.empty((nb, PROFILE_NSUM))
-        table = None if sums_only else np.empty((nb, PROFILE_NCOL))
-        self._ck(self.lib.sph_profile(self._h, C.byref(d), sums.ctypes.data, None if table is None else table.ctypes.data, nb))
+        f = self._form(device)
+        sums = f.empty((nb, PROFILE_NSUM))
+        if device:                                                # sph_profile_dev takes no table
+            f.call("sph_profile", C.byref(d), f.ptr(sums), nb)
+        else:
+            table = None if sums_only else f.empty((nb, PROFILE_NCOL))
+            f.call("sph_profile", C.byref(d), f.ptr(sums), f.ptr(table), nb)
         self.profile_desc = d
-        return (None if table is None else profile_table(table)), sums
+        return sums if device else ((None if table is None else profile_table(table)), sums)
 
     # ---- conserved totals and the potential (sph_energy) ---------------------------------------
     def energy(self, phi=False, device=False, src_offset=0):
@@ -1129,31 +1230,27 @@ class Context:
         context's GPU (sph_energy_dev); the named values are read from them.  src_offset: the position of this context's
         owned particles in the external source set (sph_set_gravity_sources_dev), ignored without one."""
         n = self.n
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            sums = torch.empty(ENERGY_NSUM, dtype=torch.float64, device=dev)
-            ph = torch.empty(n, dtype=torch.float64, device=dev) if phi else None
-            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
-            self._ck(self.lib.sph_energy_dev(self._h, int(src_offset), C.c_void_p(sums.data_ptr()),
-                                             C.c_void_p(ph.data_ptr()) if ph is not None else None, n))
-            st = self.stream()                                    # torch's later work waits for the energy
-            if st:
-                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
-            else:
-                torch.cuda.synchronize(dev)
-            out = energy_total(sums.cpu().numpy())
-        else:
-            sums = np.empty(ENERGY_NSUM)
-            ph = np.empty(n) if phi else None
-            self._ck(self.lib.sph_energy(self._h, int(src_offset), sums.ctypes.data, None if ph is None else ph.ctypes.data, n))
-            out = energy_total(sums)
+        f = self._form(device)
+        sums = f.empty(ENERGY_NSUM)
+        ph = f.empty(n) if phi else None
+        f.call("sph_energy", int(src_offset), f.ptr(sums), f.ptr(ph), n)
+        out = energy_total(f.host(sums))
         out["sums"] = sums
         if phi:
             out["phi"] = ph
         return out
 
     # ---- friends-of-friends groups (sph_groups) --------------------------------------------------
+    def _components(self, name, d, n_col, n_count, max_groups, labels, f):
+        """the call groups and peaks share: (labels, the max_groups table rows, max_groups, the counts buffer)"""
+        n = self.n
+        mg = n if max_groups is None else int(max_groups)
+        lab = f.empty(n, np.int32) if labels else None
+        tab = f.empty((mg, n_col)) if mg > 0 else None
+        cnt = f.counts(n_count)
+        f.call(name, C.byref(d), f.ptr(lab), n, f.ptr(tab), mg, f.ptr(cnt))
+        return lab, tab, mg, cnt
+
     def groups(self, link, rho_min=-np.inf, min_members=1, link_h=False, clip=None, max_groups=None, labels=True,
                device=False):
         """The friends-of-friends groups of the owned gas (include/summersph.h, sph_groups): particles with rho >= rho_min
@@ -1165,33 +1262,13 @@ class Context:
         (max_groups of them, the first min(n_groups, max_groups) written) are torch tensors on the context's GPU
         (sph_groups_dev); the table is then an (max_groups, GROUPS_NCOL) float64 tensor.  The descriptor used is left in
         self.groups_desc."""
-        d = groups_desc(link, rho_min, min_members, link_h, clip)
-        n = self.n
-        mg = n if max_groups is None else int(max_groups)
-        self.groups_desc = d
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            lab = torch.empty(n, dtype=torch.int32, device=dev) if labels else None
-            tab = torch.empty((mg, GROUPS_NCOL), dtype=torch.float64, device=dev) if mg > 0 else None
-            cnt = torch.empty(1, dtype=torch.int64, device=dev)
-            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
-            self._ck(self.lib.sph_groups_dev(self._h, C.byref(d), C.c_void_p(lab.data_ptr()) if lab is not None else None, n,
-                                             C.c_void_p(tab.data_ptr()) if tab is not None else None, mg,
-                                             C.c_void_p(cnt.data_ptr())))
-            st = self.stream()                                    # torch's later work waits for the groups
-            if st:
-                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
-            else:
-                torch.cuda.synchronize(dev)
-            return lab, tab, int(cnt.item())
-        lab = np.empty(n, dtype=np.int32) if labels else None
-        tab = np.empty((mg, GROUPS_NCOL)) if mg > 0 else None
-        ng = C.c_int64(0)
-        self._ck(self.lib.sph_groups(self._h, C.byref(d), None if lab is None else lab.ctypes.data, n,
-                                     None if tab is None else tab.ctypes.data, mg, C.byref(ng)))
-        ng = int(ng.value)
-        return lab, (None if tab is None else groups_table(tab[:min(ng, mg)])), ng
+        d = self.groups_desc = groups_desc(link, rho_min, min_members, link_h, clip)
+        f = self._form(device)
+        lab, tab, mg, cnt = self._components("sph_groups", d, GROUPS_NCOL, 1, max_groups, labels, f)
+        ng = f.read(cnt)[0]
+        if tab is not None and not device:
+            tab = groups_table(tab[:min(ng, mg)])
+        return lab, tab, ng
 
     # ---- density-peak clumps (sph_peaks) ---------------------------------------------------------
     def peaks(self, link, contrast=2.0, rho_min=-np.inf, peak_min=-np.inf, min_members=1, link_h=False, clip=None,
@@ -1205,33 +1282,13 @@ class Context:
         (max_groups, PEAKS_NCOL) table and the three counts are torch tensors on the context's GPU (sph_peaks_dev; counts[0]
         == -1 tells of a bad h under link_h); the call still waits for the stream, since the merge runs on the host.  The
         descriptor used is left in self.peaks_desc."""
-        d = peaks_desc(link, contrast, rho_min, peak_min, min_members, link_h, clip)
-        n = self.n
-        mg = n if max_groups is None else int(max_groups)
-        self.peaks_desc = d
+        d = self.peaks_desc = peaks_desc(link, contrast, rho_min, peak_min, min_members, link_h, clip)
+        f = self._form(device)
+        lab, tab, mg, cnt = self._components("sph_peaks", d, PEAKS_NCOL, PEAKS_NCOUNT, max_groups, labels, f)
+        counts = f.read(cnt)
         if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            lab = torch.empty(n, dtype=torch.int32, device=dev) if labels else None
-            tab = torch.empty((mg, PEAKS_NCOL), dtype=torch.float64, device=dev) if mg > 0 else None
-            cnt = torch.empty(PEAKS_NCOUNT, dtype=torch.int64, device=dev)
-            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
-            self._ck(self.lib.sph_peaks_dev(self._h, C.byref(d), C.c_void_p(lab.data_ptr()) if lab is not None else None, n,
-                                            C.c_void_p(tab.data_ptr()) if tab is not None else None, mg,
-                                            C.c_void_p(cnt.data_ptr())))
-            st = self.stream()                                    # torch's later work waits for the clumps
-            if st:
-                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
-            else:
-                torch.cuda.synchronize(dev)
-            return lab, tab, int(cnt[0].item()), cnt
-        lab = np.empty(n, dtype=np.int32) if labels else None
-        tab = np.empty((mg, PEAKS_NCOL)) if mg > 0 else None
-        cnt = (C.c_int64 * PEAKS_NCOUNT)()
-        self._ck(self.lib.sph_peaks(self._h, C.byref(d), None if lab is None else lab.ctypes.data, n,
-                                    None if tab is None else tab.ctypes.data, mg, cnt))
-        ng = int(cnt[0])
-        return lab, (None if tab is None else peaks_table(tab[:min(ng, mg)])), ng, tuple(int(v) for v in cnt)
+            return lab, tab, counts[0], cnt
+        return lab, (None if tab is None else peaks_table(tab[:min(counts[0], mg)])), counts[0], counts
 
     # ---- SPH gradients (sph_gradients) ------------------------------------------------------------
     def gradients(self, fields=("vx", "vy", "vz"), values=None, corrected=True, h=None, clip=None, rho=False, device=False):
@@ -1243,47 +1300,19 @@ class Context:
         grad an (n_fields, 3, n) array (NaN rows for non-targets), rho~ (n,) or None (rho=False), counts = (n_targets,
         n_singular).  device=True: grad and rho~ are torch tensors on the context's GPU (sph_gradients_dev).  The
         descriptor used is left in self.gradients_desc."""
-        d = gradients_desc(fields, corrected, h, clip)
+        d = self.gradients_desc = gradients_desc(fields, corrected, h, clip)
         n, nf = self.n, d.n_fields
-        n_out = 3 * nf * n
-        self.gradients_desc = d
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            if values is not None:
-                if not (isinstance(values, torch.Tensor) and values.dtype == torch.float64 and values.is_contiguous()
-                        and values.device == dev):
-                    raise ValueError("gradients: device values must be a contiguous float64 tensor on the context's GPU")
-                if values.numel() < nf * n and any(d.fields[k] == GRAD_VALUES for k in range(nf)):
-                    raise ValueError(f"gradients: values need {nf} rows of {n}")
-            out = torch.empty((nf, 3, n), dtype=torch.float64, device=dev)
-            r = torch.empty(n, dtype=torch.float64, device=dev) if rho else None
-            cnt = torch.empty(2, dtype=torch.int64, device=dev)
-            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
-            self._ck(self.lib.sph_gradients_dev(self._h, C.byref(d), None if values is None else C.c_void_p(values.data_ptr()),
-                                                C.c_void_p(out.data_ptr()), n_out, None if r is None else C.c_void_p(r.data_ptr()),
-                                                C.c_void_p(cnt.data_ptr())))
-            st = self.stream()                                    # torch's later work waits for the gradients
-            if st:
-                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
-            else:
-                torch.cuda.synchronize(dev)
-            c = cnt.cpu().tolist()
-            return out, r, (int(c[0]), int(c[1]))
-        v = None
-        if values is not None:
-            v = np.ascontiguousarray(values, dtype=np.float64)
-            if v.ndim == 1:
-                v = v.reshape(1, -1)
-            if v.shape[1] != n:
-                raise ValueError(f"gradients: values rows of {v.shape[1]} for {n} particles")
-            if v.shape[0] < nf:                                   # row k belongs to field k: pad the rows no field reads
-                v = np.concatenate([v, np.zeros((nf - v.shape[0], n))])
-        out = np.empty((nf, 3, n), dtype=np.float64)
-        r = np.empty(n, dtype=np.float64) if rho else None
+        f = self._form(device)
+        v = _values_rows("gradients", values, nf if GRAD_VALUES in d.fields[:nf] else 0, n, f)
+        out = f.empty((nf, 3, n))
+        r = f.empty(n) if rho else None
+        args = (C.byref(d), f.ptr(v), f.ptr(out), 3 * nf * n, f.ptr(r))
+        if device:                                                # sph_gradients_dev: one pointer to both counts
+            cnt = f.counts(2)
+            f.call("sph_gradients", *args, f.ptr(cnt))
+            return out, r, f.read(cnt)
         nt, ns = C.c_int64(0), C.c_int64(0)
-        self._ck(self.lib.sph_gradients(self._h, C.byref(d), None if v is None else v.ctypes.data, out.ctypes.data, n_out,
-                                        None if r is None else r.ctypes.data, C.byref(nt), C.byref(ns)))
+        f.call("sph_gradients", *args, C.byref(nt), C.byref(ns))
         return out, r, (int(nt.value), int(ns.value))
 
     # ---- SPH interpolation at arbitrary points (sph_sample) ----------------------------------------
@@ -1300,76 +1329,19 @@ class Context:
         fields=()) and / or counts a tuple (out, den, (n_hit, n_nonfinite)) of the parts asked for -- with fields=() and
         neither flag just den.  device=True: torch tensors (sph_sample_dev).  The descriptor used is left in
         self.sample_desc."""
-        d = sample_desc(fields, weight, normalise, h, clip)
+        d = self.sample_desc = sample_desc(fields, weight, normalise, h, clip)
         n, nf = self.n, d.n_fields
         want_w = weight_out or nf == 0
-        self.sample_desc = d
-        uses_values = any(d.fields[k] == SAMPLE_VALUES for k in range(nf))
-        three = isinstance(points, (tuple, list)) and len(points) == 3
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-
-            def ok(t):
-                return isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == dev
-            if three:
-                p = list(points)
-            elif ok(points) and points.ndim == 2 and points.shape[1] == 3:
-                p = [points[:, a].contiguous() for a in range(3)]
-            else:
-                p = [None]
-            if not all(ok(t) and t.ndim == 1 and t.is_contiguous() and t.numel() == p[0].numel() for t in p):
-                raise ValueError("sample: device points must be an (M, 3) or three contiguous float64 tensors on the context's GPU")
-            m = p[0].numel()
-            if values is not None:
-                if not (ok(values) and values.is_contiguous()):
-                    raise ValueError("sample: device values must be a contiguous float64 tensor on the context's GPU")
-                if uses_values and values.numel() < nf * n:
-                    raise ValueError(f"sample: values need {nf} rows of {n}")
-            out = torch.empty((nf, m), dtype=torch.float64, device=dev)
-            w = torch.empty(m, dtype=torch.float64, device=dev) if want_w else None
-            cnt = torch.empty(2, dtype=torch.int64, device=dev)
-            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
-            self._ck(self.lib.sph_sample_dev(self._h, C.byref(d), m, *(C.c_void_p(t.data_ptr()) for t in p),
-                                             None if values is None else C.c_void_p(values.data_ptr()),
-                                             C.c_void_p(out.data_ptr()) if nf else None, nf * m,
-                                             None if w is None else C.c_void_p(w.data_ptr()), C.c_void_p(cnt.data_ptr())))
-            st = self.stream()                                    # torch's later work waits for the sample
-            if st:
-                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
-            else:
-                torch.cuda.synchronize(dev)
-            cn = tuple(int(v) for v in cnt.cpu().tolist()) if counts else None
-        else:
-            if three:
-                p = [np.ascontiguousarray(t, dtype=np.float64).reshape(-1) for t in points]
-            else:
-                a = np.asarray(points, dtype=np.float64)
-                if a.ndim != 2 or a.shape[1] != 3:
-                    raise ValueError("sample: points must be an (M, 3) array or three arrays")
-                p = [np.ascontiguousarray(a[:, k]) for k in range(3)]
-            m = p[0].size
-            if p[1].size != m or p[2].size != m:
-                raise ValueError("sample: the three point arrays differ in length")
-            v = None
-            if values is not None:
-                v = np.ascontiguousarray(values, dtype=np.float64)
-                if v.ndim == 1:
-                    v = v.reshape(1, -1)
-                if v.shape[1] != n:
-                    raise ValueError(f"sample: values rows of {v.shape[1]} for {n} particles")
-                if v.shape[0] < nf:                               # row k belongs to field k: pad the rows no field reads
-                    v = np.concatenate([v, np.zeros((nf - v.shape[0], n))])
-            out = np.empty((nf, m), dtype=np.float64)
-            w = np.empty(m, dtype=np.float64) if want_w else None
-            cc = (C.c_int64 * 2)(0, 0)
-            self._ck(self.lib.sph_sample(self._h, C.byref(d), m, p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data,
-                                         None if v is None else v.ctypes.data, out.ctypes.data if nf else None, nf * m,
-                                         None if w is None else w.ctypes.data, cc))
-            cn = (int(cc[0]), int(cc[1])) if counts else None
+        f = self._form(device)
+        p, m = _points("sample", points, f)
+        v = _values_rows("sample", values, nf if SAMPLE_VALUES in d.fields[:nf] else 0, n, f)
+        out = f.empty((nf, m))
+        w = f.empty(m) if want_w else None
+        cnt = f.counts(2)
+        f.call("sph_sample", C.byref(d), m, *map(f.ptr, p), f.ptr(v), f.ptr(out) if nf else None, nf * m, f.ptr(w), f.ptr(cnt))
         if nf == 0 and not weight_out and not counts:
             return w
-        parts = [out] + ([w] if want_w else []) + ([cn] if counts else [])
+        parts = [out] + ([w] if want_w else []) + ([f.read(cnt)] if counts else [])
         return parts[0] if len(parts) == 1 else tuple(parts)
 
     # ---- field lines of an SPH-interpolated vector field (sph_trace) -------------------------------
@@ -1386,82 +1358,23 @@ class Context:
         Context.sample.  Returns (path (n_rec + 1, 3, M), status (M) int32, n_done (M) int32[, carry (n_rec + 1, M)][, counts:
         the seeds per status code, TRACE_STATUS]); rows after a line's last vertex are NaN.  device=True: torch tensors
         (sph_trace_dev).  The descriptor used is left in self.trace_desc."""
-        d = trace_desc(n_steps, ds, fields, carry, arclength, omega, centre, normal, box, stride, weight, h, clip)
-        self.trace_desc = d
+        d = self.trace_desc = trace_desc(n_steps, ds, fields, carry, arclength, omega, centre, normal, box, stride, weight, h, clip)
         n = self.n
         if d.stride < 1 or d.n_steps < 1 or d.n_steps % d.stride:
             raise ValueError("trace: n_steps >= 1 and stride >= 1 dividing n_steps")
         n_rec = d.n_steps // d.stride
         has_carry = d.carry != TRACE_NONE
         rows = 4 if d.carry == TRACE_VALUES else max([k + 1 for k in range(3) if d.fields[k] == TRACE_VALUES], default=0)
-        three = isinstance(seeds, (tuple, list)) and len(seeds) == 3
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-
-            def ok(t):
-                return isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == dev
-            if three:
-                p = list(seeds)
-            elif ok(seeds) and seeds.ndim == 2 and seeds.shape[1] == 3:
-                p = [seeds[:, a].contiguous() for a in range(3)]
-            else:
-                p = [None]
-            if not all(ok(t) and t.ndim == 1 and t.is_contiguous() and t.numel() == p[0].numel() for t in p):
-                raise ValueError("trace: device seeds must be an (M, 3) or three contiguous float64 tensors on the context's GPU")
-            m = p[0].numel()
-            if values is not None:
-                if not (ok(values) and values.is_contiguous()):
-                    raise ValueError("trace: device values must be a contiguous float64 tensor on the context's GPU")
-                if values.numel() < rows * n:
-                    raise ValueError(f"trace: values need {rows} rows of {n}")
-            path = torch.empty((n_rec + 1, 3, m), dtype=torch.float64, device=dev)
-            car = torch.empty((n_rec + 1, m), dtype=torch.float64, device=dev) if has_carry else None
-            status = torch.empty(m, dtype=torch.int32, device=dev)
-            done = torch.empty(m, dtype=torch.int32, device=dev)
-            cnt = torch.empty(5, dtype=torch.int64, device=dev)
-            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
-            self._ck(self.lib.sph_trace_dev(self._h, C.byref(d), m, *(C.c_void_p(t.data_ptr()) for t in p),
-                                            None if values is None else C.c_void_p(values.data_ptr()),
-                                            C.c_void_p(path.data_ptr()), 3 * (n_rec + 1) * m,
-                                            None if car is None else C.c_void_p(car.data_ptr()), C.c_void_p(status.data_ptr()),
-                                            C.c_void_p(done.data_ptr()), C.c_void_p(cnt.data_ptr())))
-            st = self.stream()                                    # torch's later work waits for the trace
-            if st:
-                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
-            else:
-                torch.cuda.synchronize(dev)
-            cn = tuple(int(v) for v in cnt.cpu().tolist()) if counts else None
-        else:
-            if three:
-                p = [np.ascontiguousarray(t, dtype=np.float64).reshape(-1) for t in seeds]
-            else:
-                a = np.asarray(seeds, dtype=np.float64)
-                if a.ndim != 2 or a.shape[1] != 3:
-                    raise ValueError("trace: seeds must be an (M, 3) array or three arrays")
-                p = [np.ascontiguousarray(a[:, k]) for k in range(3)]
-            m = p[0].size
-            if p[1].size != m or p[2].size != m:
-                raise ValueError("trace: the three seed arrays differ in length")
-            v = None
-            if values is not None:
-                v = np.ascontiguousarray(values, dtype=np.float64)
-                if v.ndim == 1:
-                    v = v.reshape(1, -1)
-                if v.shape[1] != n:
-                    raise ValueError(f"trace: values rows of {v.shape[1]} for {n} particles")
-                if v.shape[0] < rows:                             # row k belongs to component k: pad the rows nothing reads
-                    v = np.concatenate([v, np.zeros((rows - v.shape[0], n))])
-            path = np.empty((n_rec + 1, 3, m), dtype=np.float64)
-            car = np.empty((n_rec + 1, m), dtype=np.float64) if has_carry else None
-            status = np.empty(m, dtype=np.int32)
-            done = np.empty(m, dtype=np.int32)
-            cc = (C.c_int64 * 5)(0, 0, 0, 0, 0)
-            self._ck(self.lib.sph_trace(self._h, C.byref(d), m, p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data,
-                                        None if v is None else v.ctypes.data, path.ctypes.data, 3 * (n_rec + 1) * m,
-                                        None if car is None else car.ctypes.data, status.ctypes.data, done.ctypes.data, cc))
-            cn = tuple(int(x) for x in cc) if counts else None
-        return tuple([path, status, done] + ([car] if has_carry else []) + ([cn] if counts else []))
+        f = self._form(device)
+        p, m = _points("trace", seeds, f, noun="seed")
+        v = _values_rows("trace", values, rows, n, f)
+        path = f.empty((n_rec + 1, 3, m))
+        car = f.empty((n_rec + 1, m)) if has_carry else None
+        status, done = f.empty(m, np.int32), f.empty(m, np.int32)
+        cnt = f.counts(5)
+        f.call("sph_trace", C.byref(d), m, *map(f.ptr, p), f.ptr(v), f.ptr(path), 3 * (n_rec + 1) * m, f.ptr(car), f.ptr(status),
+               f.ptr(done), f.ptr(cnt))
+        return tuple([path, status, done] + ([car] if has_carry else []) + ([f.read(cnt)] if counts else []))
 
     # ---- spectral cubes (sph_cube) -----------------------------------------------------------------
     def cube(self, shape, bounds, v0, dv, n_chan, rot=None, centre=(0.0, 0.0, 0.0), v_ref=(0.0, 0.0, 0.0), sigma_scale=0.0,
@@ -1474,33 +1387,14 @@ class Context:
         contiguous float64 torch tensor on the context's GPU (device=True); h, clip: as render_density; per_velocity:
         divide by dv.  Returns float64 numpy or, device=True, a torch tensor (sph_cube_dev).  The descriptor used is left
         in self.cube_desc."""
-        d = cube_desc(shape, bounds, v0, dv, n_chan, rot, centre, v_ref, sigma_scale, sigma_floor, h, clip, per_velocity)
-        self.cube_desc = d
+        d = self.cube_desc = cube_desc(shape, bounds, v0, dv, n_chan, rot, centre, v_ref, sigma_scale, sigma_floor, h, clip,
+                                       per_velocity)
         oshape = (d.n_chan, d.n_u, d.n_v)
         size = int(np.prod(oshape, dtype=np.int64)) if min(oshape) > 0 else 0
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            if values is not None and not (isinstance(values, torch.Tensor) and values.dtype == torch.float64 and
-                                           values.is_contiguous() and values.device == dev and values.numel() == self.n):
-                raise ValueError("cube: device values must be a contiguous float64 tensor of sph_count() on the context's GPU")
-            out = torch.empty([max(v, 0) for v in oshape], dtype=torch.float64, device=dev)
-            torch.cuda.current_stream(dev).synchronize()          # the blocks and values may still be in use by torch's work
-            self._ck(self.lib.sph_cube_dev(self._h, C.byref(d), None if values is None else C.c_void_p(values.data_ptr()),
-                                           C.c_void_p(out.data_ptr()), size))
-            st = self.stream()                                    # torch's later work on `out` waits for the cube
-            if st:
-                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
-            else:
-                torch.cuda.synchronize(dev)
-        else:
-            v = None
-            if values is not None:
-                v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
-                if v.size != self.n:
-                    raise ValueError(f"cube: {v.size} values for {self.n} particles")
-            out = np.empty([max(v_, 0) for v_ in oshape], dtype=np.float64)
-            self._ck(self.lib.sph_cube(self._h, C.byref(d), None if v is None else v.ctypes.data, out.ctypes.data, size))
+        f = self._form(device)
+        v = None if values is None else _values_one("cube", values, self.n, f)
+        out = f.empty([max(k, 0) for k in oshape])
+        f.call("sph_cube", C.byref(d), f.ptr(v), f.ptr(out), size)
         return out
 
     # ---- the rates split by physical term (sph_force_terms) -----------------------------------------
@@ -1515,20 +1409,9 @@ class Context:
         d = ForceTermsDesc()
         d.flags = TERMS_SKIP_GAS_GRAVITY if skip_gas_gravity else 0
         n = self.n
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            out = torch.empty((TERMS_NROW, n), dtype=torch.float64, device=dev)
-            torch.cuda.current_stream(dev).synchronize()          # the block may still be in use by torch's queued work
-            self._ck(self.lib.sph_force_terms_dev(self._h, C.byref(d), C.c_void_p(out.data_ptr()), TERMS_NROW * n))
-            st = self.stream()                                    # torch's later work on `out` waits for the pass
-            if st:
-                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
-            else:
-                torch.cuda.synchronize(dev)
-        else:
-            out = np.empty((TERMS_NROW, n), dtype=np.float64)
-            self._ck(self.lib.sph_force_terms(self._h, C.byref(d), out.ctypes.data, TERMS_NROW * n))
+        f = self._form(device)
+        out = f.empty((TERMS_NROW, n))
+        f.call("sph_force_terms", C.byref(d), f.ptr(out), TERMS_NROW * n)
         return out
 
     # ---- binned sums (sph_binned) ---------------------------------------------------------------------
@@ -1543,46 +1426,22 @@ class Context:
         Returns (sums, counts): sums (n0, n1, nsum) float64 with nsum = 2 + n_q (1 + squares), [..., 0] = N, [..., 1] =
         sum w, [..., 2 + k] = sum w A_k, [..., 2 + n_q + k] = sum w A_k A_k (binned.finish turns them into means and
         dispersions); counts = (selected, outside the range, dropped as NaN).  device=True: sums and counts (int64) are torch
-        tensors on the context's GPU (sph_binned_dev), ordered after the call on torch's current stream; nothing waits.  The descriptor used is left in self.binned_desc."""
+        tensors on the context's GPU (sph_binned_dev); as with every device form, torch's current stream is synchronised before
+        the call and made to wait for it afterwards.  The descriptor used is left in self.binned_desc."""
         n = self.n
         n_rows = 0
         if values is not None:
             n_rows = int(values.shape[0]) if values.ndim == 2 else 1
         d, tab = binned_desc(axes, bins, ranges, edges, log, q, weight, n_rows, squares, skip_nan)
         self.binned_desc = d
-        n0, n1, nsum = int(d.n[0]), int(d.n[1]), binned_nsum(d.n_q, squares)
-        size = max(n0, 0) * max(n1, 0) * nsum
-        ep = None if tab is None else tab.ctypes.data
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            if values is not None:
-                if not (isinstance(values, torch.Tensor) and values.dtype == torch.float64 and values.is_contiguous()
-                        and values.device == dev):
-                    raise ValueError("binned: device values must be a contiguous float64 tensor on the context's GPU")
-                if values.numel() != n_rows * n:
-                    raise ValueError(f"binned: values rows of {values.numel() // max(n_rows, 1)} for {n} particles")
-            out = torch.empty((max(n0, 0), max(n1, 0), nsum), dtype=torch.float64, device=dev)
-            cnt = torch.empty(3, dtype=torch.int64, device=dev)
-            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
-            self._ck(self.lib.sph_binned_dev(self._h, C.byref(d), None if values is None else C.c_void_p(values.data_ptr()), ep,
-                                             C.c_void_p(out.data_ptr()), size, C.c_void_p(cnt.data_ptr())))
-            st = self.stream()                                    # torch's later work waits for the sums
-            if st:
-                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
-            else:
-                torch.cuda.synchronize(dev)
-            return out, cnt
-        v = None
-        if values is not None:
-            v = np.ascontiguousarray(values, dtype=np.float64).reshape(n_rows, -1)
-            if v.shape[1] != n:
-                raise ValueError(f"binned: values rows of {v.shape[1]} for {n} particles")
-        out = np.empty((max(n0, 0), max(n1, 0), nsum), dtype=np.float64)
-        cnt = np.zeros(3, dtype=np.int64)
-        self._ck(self.lib.sph_binned(self._h, C.byref(d), None if v is None else v.ctypes.data, ep, out.ctypes.data, size,
-                                     cnt.ctypes.data))
-        return out, tuple(int(c) for c in cnt)
+        shape = (max(int(d.n[0]), 0), max(int(d.n[1]), 0), binned_nsum(d.n_q, squares))
+        f = self._form(device)
+        v = _values_rows("binned", values, n_rows, n, f, exact=True)
+        out = f.empty(shape)
+        cnt = f.counts(3)
+        f.call("sph_binned", C.byref(d), f.ptr(v), None if tab is None else tab.ctypes.data, f.ptr(out),
+               shape[0] * shape[1] * shape[2], f.ptr(cnt))
+        return out, (cnt if device else f.read(cnt))
 
     # ---- potential and acceleration at arbitrary points (sph_gravity_at) ---------------------------
     def gravity_at(self, points, h=None, ph=None, soft2=GRAVAT_REF_SOFT2, gas=True, sinks=True, split=False, counts=False,
@@ -1594,66 +1453,19 @@ class Context:
         and (3, M), the sum of the selected parts; split=True: (2, M) and (2, 3, M), the gas first, then the sinks.
         counts=True: (phi, acc, (n_nonfinite_points, n_bad_h)).  device=True: torch tensors (sph_gravity_at_dev).  The
         descriptor used is left in self.gravity_at_desc."""
-        d = gravity_at_desc(h, soft2, gas, sinks, split)
-        self.gravity_at_desc = d
+        d = self.gravity_at_desc = gravity_at_desc(h, soft2, gas, sinks, split)
         rows = 8 if split else 4
-        three = isinstance(points, (tuple, list)) and len(points) == 3
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-
-            def ok(t):
-                return isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == dev
-            if three:
-                p = list(points)
-            elif ok(points) and points.ndim == 2 and points.shape[1] == 3:
-                p = [points[:, a].contiguous() for a in range(3)]
-            else:
-                p = [None]
-            if ph is not None:
-                p = p + [ph]
-            if not all(ok(t) and t.ndim == 1 and t.is_contiguous() and t.numel() == p[0].numel() for t in p):
-                raise ValueError("gravity_at: device points (and ph) must be contiguous float64 tensors on the context's GPU")
-            m = p[0].numel()
-            out = torch.empty((rows, m), dtype=torch.float64, device=dev)
-            cnt = torch.empty(2, dtype=torch.int64, device=dev)
-            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
-            self._ck(self.lib.sph_gravity_at_dev(self._h, C.byref(d), m, *(C.c_void_p(t.data_ptr()) for t in p[:3]),
-                                                 None if ph is None else C.c_void_p(p[3].data_ptr()),
-                                                 C.c_void_p(out.data_ptr()), rows * m, C.c_void_p(cnt.data_ptr())))
-            st = self.stream()                                    # torch's later work waits for the walk
-            if st:
-                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
-            else:
-                torch.cuda.synchronize(dev)
-            cn = tuple(int(v) for v in cnt.cpu().tolist()) if counts else None
-        else:
-            if three:
-                p = [np.ascontiguousarray(t, dtype=np.float64).reshape(-1) for t in points]
-            else:
-                a = np.asarray(points, dtype=np.float64)
-                if a.ndim != 2 or a.shape[1] != 3:
-                    raise ValueError("gravity_at: points must be an (M, 3) array or three arrays")
-                p = [np.ascontiguousarray(a[:, k]) for k in range(3)]
-            m = p[0].size
-            if p[1].size != m or p[2].size != m:
-                raise ValueError("gravity_at: the three point arrays differ in length")
-            hh = None
-            if ph is not None:
-                hh = np.ascontiguousarray(ph, dtype=np.float64).reshape(-1)
-                if hh.size != m:
-                    raise ValueError(f"gravity_at: ph has {hh.size} values for {m} points")
-            out = np.empty((rows, m), dtype=np.float64)
-            cc = (C.c_int64 * 2)(0, 0)
-            self._ck(self.lib.sph_gravity_at(self._h, C.byref(d), m, p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data,
-                                             None if hh is None else hh.ctypes.data, out.ctypes.data, rows * m, cc))
-            cn = (int(cc[0]), int(cc[1])) if counts else None
+        f = self._form(device)
+        p, m = _points("gravity_at", points, f, {"ph": ph})
+        out = f.empty((rows, m))
+        cnt = f.counts(2)
+        f.call("sph_gravity_at", C.byref(d), m, *map(f.ptr, p), f.ptr(out), rows * m, f.ptr(cnt))
         if split:
             out = out.reshape(2, 4, m)
             phi, acc = out[:, 0], out[:, 1:]
         else:
             phi, acc = out[0], out[1:]
-        return (phi, acc, cn) if counts else (phi, acc)
+        return (phi, acc, f.read(cnt)) if counts else (phi, acc)
 
     # ---- binding energies and unbinding of groups (sph_bound) ----------------------------------------
     def bound(self, labels, n_groups, h=None, soft2=GRAVAT_REF_SOFT2, thermal=False, max_rounds=0, min_members=1,
@@ -1669,37 +1481,20 @@ class Context:
         dissolved, stopped at max_rounds).  device=True: labels is an int32 tensor on the context's GPU and bound_labels,
         e, phi and the (n_groups, BOUND_NCOL) table are torch tensors (sph_bound_dev); counts[0] == -1 then tells of a
         member with an unusable h.  The descriptor used is left in self.bound_desc."""
-        d = bound_desc(h, soft2, thermal, max_rounds, min_members, max_members)
+        d = self.bound_desc = bound_desc(h, soft2, thermal, max_rounds, min_members, max_members)
         n, ng = self.n, int(n_groups)
-        self.bound_desc = d
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            if not (isinstance(labels, torch.Tensor) and labels.dtype == torch.int32 and labels.is_contiguous()
-                    and labels.device == dev and labels.numel() == n):
-                raise ValueError("bound: device labels must be a contiguous int32 tensor of sph_count values on the context's GPU")
-            bl = torch.empty(n, dtype=torch.int32, device=dev)
-            out = torch.empty((2, n), dtype=torch.float64, device=dev)
-            tab = torch.empty((max(ng, 0), BOUND_NCOL), dtype=torch.float64, device=dev)
-            cnt = torch.empty(4, dtype=torch.int64, device=dev)
-            torch.cuda.current_stream(dev).synchronize()          # the blocks may still be in use by torch's queued work
-            self._ck(self.lib.sph_bound_dev(self._h, C.byref(d), C.c_void_p(labels.data_ptr()), n, ng, C.c_void_p(bl.data_ptr()),
-                                            C.c_void_p(out.data_ptr()), 2 * n, C.c_void_p(tab.data_ptr()),
-                                            C.c_void_p(cnt.data_ptr())))
-            st = self.stream()                                    # torch's later work waits for the rounds
-            if st:
-                torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(st, device=dev))
-            else:
-                torch.cuda.synchronize(dev)
-            return bl, out[0], out[1], tab, tuple(int(v) for v in cnt.cpu().tolist())
-        lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
-        bl = np.empty(n, dtype=np.int32)
-        out = np.empty((2, n), dtype=np.float64)
-        tab = np.empty((max(ng, 0), BOUND_NCOL), dtype=np.float64)
-        cc = (C.c_int64 * 4)(0, 0, 0, 0)
-        self._ck(self.lib.sph_bound(self._h, C.byref(d), lab.ctypes.data, lab.size, ng, bl.ctypes.data, out.ctypes.data, 2 * n,
-                                    tab.ctypes.data, cc))
-        return bl, out[0], out[1], bound_table(tab), tuple(int(v) for v in cc)
+        f = self._form(device)
+        if not device:
+            labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        elif not (f.owns(labels, "int32") and labels.is_contiguous() and labels.numel() == n):
+            raise ValueError("bound: device labels must be a contiguous int32 tensor of sph_count values on the context's GPU")
+        bl = f.empty(n, np.int32)
+        out = f.empty((2, n))
+        tab = f.empty((max(ng, 0), BOUND_NCOL))
+        cnt = f.counts(4)
+        f.call("sph_bound", C.byref(d), f.ptr(labels), n if device else labels.size, ng, f.ptr(bl), f.ptr(out), 2 * n, f.ptr(tab),
+               f.ptr(cnt))
+        return bl, out[0], out[1], (tab if device else bound_table(tab)), f.read(cnt)
 
     # ---- diagnostics ---------------------------------------------------------------------
     def stats(self) -> Stats:

@@ -14,7 +14,7 @@ import sys
 
 import numpy as np
 
-STATE = "x y z vx vy vz u m alpha".split()
+from .cli import read_save, uploaded_context
 
 
 def view(inclination, position_angle=0.0, azimuth=0.0):
@@ -224,22 +224,13 @@ def args_desc(a):
 
 def cube_rows(gas, sinks, kw, variable=False, device=0):
     """Uploads the rows into a fresh context and returns its cube (Context.cube(**kw))."""
-    from . import capi
-    ctx = capi.Context(device=device, variable=variable)
-    try:
-        names = STATE + (["h"] if variable else [])
-        ctx.upload({k: gas[:, i] for i, k in enumerate(names)})
-        if sinks.shape[0]:
-            ctx.set_sinks({k: sinks[:, i] for i, k in zip((0, 1, 2, 3, 4, 5, 7), "x y z vx vy vz m".split())})
+    with uploaded_context(gas, sinks, variable, device) as ctx:
         if kw.get("sigma_scale", 0.0) != 0.0:
             ctx.density()                   # the sound speed c
         return ctx.cube(**kw)
-    finally:
-        ctx.close()
 
 
 def main(argv=None) -> int:
-    from .profile import read_save
     ap = build_parser()
     a = ap.parse_args(argv)
     try:

@@ -19,6 +19,8 @@ import sys
 
 import numpy as np
 
+from .cli import read_save, uploaded_context
+
 
 def energy_rows(gas, sinks, variable=False, self_gravity=True, theta=None, phi=False, device=0):
     """Uploads the rows into a fresh context and returns Context.energy's dict"""
@@ -27,15 +29,8 @@ def energy_rows(gas, sinks, variable=False, self_gravity=True, theta=None, phi=F
     kw = {"flags": flags}
     if theta is not None:
         kw["theta"] = float(theta)
-    ctx = capi.Context(device=device, variable=variable, **kw)
-    try:
-        names = "x y z vx vy vz u m alpha".split() + (["h"] if variable else [])
-        ctx.upload({k: gas[:, i] for i, k in enumerate(names)})
-        if sinks.shape[0]:
-            ctx.set_sinks({k: sinks[:, i] for i, k in zip((0, 1, 2, 3, 4, 5, 7), "x y z vx vy vz m".split())})
+    with uploaded_context(gas, sinks, variable, device, **kw) as ctx:
         return ctx.energy(phi=phi)
-    finally:
-        ctx.close()
 
 
 def to_json(e: dict) -> dict:
@@ -44,7 +39,6 @@ def to_json(e: dict) -> dict:
 
 
 def main(argv=None) -> int:
-    from .profile import read_save
     ap = argparse.ArgumentParser(prog="python -m summersph_amd.energy", description=__doc__.split("\n\n")[0])
     ap.add_argument("save", help="save file")
     ap.add_argument("--variable", action="store_true", help="10-value gas records (.. alpha h), variable-h context")

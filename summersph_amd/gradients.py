@@ -22,44 +22,23 @@ import sys
 
 import numpy as np
 
-from .profile import read_save
-
-STATE = "x y z vx vy vz u m alpha".split()
+from . import cli
+from .cli import STATE, desc_arrays, parse_clip, read_save, uploaded_context
 
 
 def parse_fields(spec: str, variable: bool = False):
     """'vx,vy,vz' -> ['vx', 'vy', 'vz']: 1 .. 4 field names of capi.FIELDS (h and omega only with variable h)"""
     from . import capi
-    names = spec.split(",")
-    allowed = [f for f in capi.FIELDS if variable or f not in ("h", "omega")]
-    if not 1 <= len(names) <= capi.GRAD_MAX_FIELDS or any(f not in allowed for f in names):
-        raise ValueError(f"--fields wants 1 .. {capi.GRAD_MAX_FIELDS} comma-separated names of {allowed}, not {spec!r}")
-    return names
-
-
-def parse_clip(spec: str):
-    """'x0,y0,z0,x1,y1,z1' -> ((x0, y0, z0), (x1, y1, z1)), no NaN and lo <= hi on every axis"""
-    v = [float(t) for t in spec.split(",")]
-    if len(v) != 6 or any(np.isnan(v)) or any(v[a] > v[3 + a] for a in range(3)):
-        raise ValueError(f"--clip wants x0,y0,z0,x1,y1,z1 with x0 <= x1 ..., not {spec!r}")
-    return tuple(v[:3]), tuple(v[3:])
+    return cli.parse_fields(spec, 1, capi.GRAD_MAX_FIELDS, variable, blanks=True)
 
 
 def gradients_rows(gas, sinks, fields=("vx", "vy", "vz"), corrected=True, h=None, clip=None, variable=False, device=0):
     """Uploads the rows into a fresh context and evaluates the gradients: (grad (K, 3, n), rho~, counts, descriptor)."""
-    from . import capi
-    ctx = capi.Context(device=device, variable=variable)
-    try:
-        names = STATE + (["h"] if variable else [])
-        ctx.upload({k: gas[:, i] for i, k in enumerate(names)})
-        if sinks.shape[0]:
-            ctx.set_sinks({k: sinks[:, i] for i, k in zip((0, 1, 2, 3, 4, 5, 7), "x y z vx vy vz m".split())})
+    with uploaded_context(gas, sinks, variable, device) as ctx:
         if any(f not in STATE + ["h"] for f in fields):
             ctx.density()                   # rho, P, c (and the rates' fields only after forces: stale otherwise)
         g, rho, counts = ctx.gradients(fields=fields, corrected=corrected, h=h, clip=clip, rho=True)
         return g, rho, counts, ctx.gradients_desc
-    finally:
-        ctx.close()
 
 
 def main(argv=None) -> int:
@@ -94,9 +73,7 @@ def main(argv=None) -> int:
         ok = np.isfinite(v["divv"])
         summary["median_abs_divv"] = float(np.median(np.abs(v["divv"][ok]))) if ok.any() else None
         summary["median_omega_z"] = float(np.median(v["curl"][2][ok])) if ok.any() else None
-    for f, _ in capi.GradientsDesc._fields_:
-        val = getattr(d, f)
-        out["desc_" + f] = np.array(val[:] if hasattr(val, "__len__") else val)
+    out.update(desc_arrays(d))
     np.savez(a.out, **out)
     if a.json:
         print(json.dumps(summary))

@@ -27,7 +27,8 @@ import sys
 
 import numpy as np
 
-from .sample import STATE, frame, parse_vec, points_from_args, ring_radii
+from .cli import desc_arrays, parse_vec, read_save, uploaded_context
+from .sample import frame, points_from_args, ring_radii
 
 
 def cylindrical(acc, points, centre=(0.0, 0.0, 0.0), normal=(0.0, 0.0, 1.0)):
@@ -104,22 +105,13 @@ def gravity_rows(gas, sinks, points, h=None, ph=None, soft2=None, gas_part=True,
                  variable=False, device=0):
     """Uploads the rows into a fresh context and evaluates: (phi, acc, (n_nonfinite, n_bad_h), descriptor)."""
     from . import capi
-    ctx = capi.Context(device=device, variable=variable, **({} if theta is None else {"theta": float(theta)}))
-    try:
-        names = STATE + (["h"] if variable else [])
-        ctx.upload({k: gas[:, i] for i, k in enumerate(names)})
-        if sinks.shape[0]:
-            ctx.set_sinks({k: sinks[:, i] for i, k in zip((0, 1, 2, 3, 4, 5, 7), "x y z vx vy vz m".split())})
+    with uploaded_context(gas, sinks, variable, device, **({} if theta is None else {"theta": float(theta)})) as ctx:
         phi, acc, cnt = ctx.gravity_at(points, h=h, ph=ph, soft2=capi.GRAVAT_REF_SOFT2 if soft2 is None else soft2, gas=gas_part,
                                        sinks=sink_part, split=split, counts=True)
         return phi, acc, cnt, ctx.gravity_at_desc
-    finally:
-        ctx.close()
 
 
 def main(argv=None) -> int:
-    from . import capi
-    from .profile import read_save
     ap = build_parser()
     a = ap.parse_args(argv)
     check_args(ap, a)
@@ -158,9 +150,7 @@ def main(argv=None) -> int:
             res["vc2_sinks" if a.no_gas else "vc2_gas"] = res["vc2"]
     res.update(points=points, shape=np.array(shape, dtype=np.int64), phi=phi, acc=acc, n_nonfinite=np.array(n_nonfin),
                n_bad_h=np.array(n_bad_h))
-    for f, _ in capi.GravityAtDesc._fields_:
-        val = getattr(d, f)
-        res["desc_" + f] = np.array(val[:] if hasattr(val, "__len__") else val)
+    res.update(desc_arrays(d))
     np.savez(a.out, **res)
     ok = np.isfinite(phi)
     summary = {"n_points": int(points.shape[0]), "n_nonfinite": n_nonfin, "n_bad_h": n_bad_h,

@@ -29,35 +29,19 @@ import sys
 
 import numpy as np
 
-from .profile import read_save
-
-
-def parse_clip(spec: str):
-    """'x0,y0,z0,x1,y1,z1' -> ((x0, y0, z0), (x1, y1, z1)), no NaN and lo <= hi on every axis"""
-    v = [float(t) for t in spec.split(",")]
-    if len(v) != 6 or any(np.isnan(v)) or any(v[a] > v[3 + a] for a in range(3)):
-        raise ValueError(f"--clip wants x0,y0,z0,x1,y1,z1 with x0 <= x1 ..., not {spec!r}")
-    return tuple(v[:3]), tuple(v[3:])
+from .cli import desc_arrays, parse_clip, read_save, uploaded_context
 
 
 def groups_rows(gas, sinks, link, rho_min=-np.inf, min_members=1, link_h=False, clip=None, variable=False, device=0,
                 bound=None):
     """Uploads the rows into a fresh context, evaluates rho and finds the groups: (labels, table, n_groups, descriptor);
     with bound (a dict of Context.bound's keyword arguments) a fifth entry, what Context.bound returns for these groups."""
-    from . import capi
-    ctx = capi.Context(device=device, variable=variable)
-    try:
-        names = "x y z vx vy vz u m alpha".split() + (["h"] if variable else [])
-        ctx.upload({k: gas[:, i] for i, k in enumerate(names)})
-        if sinks.shape[0]:
-            ctx.set_sinks({k: sinks[:, i] for i, k in zip((0, 1, 2, 3, 4, 5, 7), "x y z vx vy vz m".split())})
+    with uploaded_context(gas, sinks, variable, device) as ctx:
         ctx.density()
         labels, table, ng = ctx.groups(link, rho_min=rho_min, min_members=min_members, link_h=link_h, clip=clip)
         if bound is None:
             return labels, table, ng, ctx.groups_desc
         return labels, table, ng, ctx.groups_desc, ctx.bound(labels, ng, **bound)
-    finally:
-        ctx.close()
 
 
 def main(argv=None) -> int:
@@ -111,9 +95,7 @@ def main(argv=None) -> int:
         out.update({"bound_labels": bl, "e": e, "phi": phi, "bound_counts": np.array(bcnt, dtype=np.int64),
                     "bound_table": np.ascontiguousarray(btab).view(np.float64).reshape(-1, capi.BOUND_NCOL)})
     out.update({c: np.ascontiguousarray(table[c]) for c in capi.GROUPS_COLUMNS})
-    for f, _ in capi.GroupsDesc._fields_:
-        v = getattr(d, f)
-        out["desc_" + f] = np.array(v[:] if hasattr(v, "__len__") else v)
+    out.update(desc_arrays(d))
     np.savez(a.out, **out)
     if a.csv:
         np.savetxt(a.csv, np.stack([table[c] for c in capi.GROUPS_COLUMNS], axis=1).reshape(-1, capi.GROUPS_NCOL),

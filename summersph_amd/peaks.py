@@ -25,29 +25,20 @@ import sys
 
 import numpy as np
 
-from .groups import parse_clip
-from .profile import read_save
+from .cli import desc_arrays, parse_clip, read_save, uploaded_context
 
 
 def peaks_rows(gas, sinks, link, contrast=2.0, rho_min=-np.inf, peak_min=-np.inf, min_members=1, link_h=False, clip=None,
                variable=False, device=0, bound=None):
     """Uploads the rows into a fresh context, evaluates rho and finds the clumps: (labels, table, n_groups, counts,
     descriptor); with bound (a dict of Context.bound's keyword arguments) a sixth entry, what Context.bound returns."""
-    from . import capi
-    ctx = capi.Context(device=device, variable=variable)
-    try:
-        names = "x y z vx vy vz u m alpha".split() + (["h"] if variable else [])
-        ctx.upload({k: gas[:, i] for i, k in enumerate(names)})
-        if sinks.shape[0]:
-            ctx.set_sinks({k: sinks[:, i] for i, k in zip((0, 1, 2, 3, 4, 5, 7), "x y z vx vy vz m".split())})
+    with uploaded_context(gas, sinks, variable, device) as ctx:
         ctx.density()
         labels, table, ng, counts = ctx.peaks(link, contrast=contrast, rho_min=rho_min, peak_min=peak_min,
                                               min_members=min_members, link_h=link_h, clip=clip)
         if bound is None:
             return labels, table, ng, counts, ctx.peaks_desc
         return labels, table, ng, counts, ctx.peaks_desc, ctx.bound(labels, ng, **bound)
-    finally:
-        ctx.close()
 
 
 def main(argv=None) -> int:
@@ -106,9 +97,7 @@ def main(argv=None) -> int:
         out.update({"bound_labels": bl, "e": e, "phi": phi, "bound_counts": np.array(bcnt, dtype=np.int64),
                     "bound_table": np.ascontiguousarray(btab).view(np.float64).reshape(-1, capi.BOUND_NCOL)})
     out.update({c: np.ascontiguousarray(table[c]) for c in capi.PEAKS_COLUMNS})
-    for f, _ in capi.PeaksDesc._fields_:
-        v = getattr(d, f)
-        out["desc_" + f] = np.array(v[:] if hasattr(v, "__len__") else v)
+    out.update(desc_arrays(d))
     np.savez(a.out, **out)
     if a.csv:
         np.savetxt(a.csv, np.stack([table[c] for c in capi.PEAKS_COLUMNS], axis=1).reshape(-1, capi.PEAKS_NCOL),

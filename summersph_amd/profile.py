@@ -27,6 +27,8 @@ import sys
 
 import numpy as np
 
+from .cli import desc_arrays, read_save, uploaded_context
+
 
 def parse_centre(spec: str):
     """'sink:K' -> ('sink', K); 'x,y,z' -> ('point', (x, y, z)); anything else raises ValueError"""
@@ -51,42 +53,17 @@ def parse_normal(spec: str):
     return tuple(v)
 
 
-def read_save(path: str, variable: bool = False):
-    """(gas rows (n, 9 or 10), sink rows (ns, 8)): records of 9 (10 with variable) values are gas, of 8 sinks"""
-    ng = 10 if variable else 9
-    gas, sinks = [], []
-    with open(path) as f:
-        f.readline()
-        for line in f:
-            tok = line.split()
-            if len(tok) == ng:
-                gas.append([float(t.replace("D", "E")) for t in tok])
-            elif len(tok) == 8:
-                sinks.append([float(t.replace("D", "E")) for t in tok])
-            elif tok:
-                raise ValueError(f"{path}: a record of {len(tok)} values")
-    return np.asarray(gas, dtype=np.float64).reshape(-1, ng), np.asarray(sinks, dtype=np.float64).reshape(-1, 8)
-
-
 def profile_rows(gas, sinks, r_min, r_max, n_r, n_phi=1, log=False, centre=None, normal=(0.0, 0.0, 1.0), z_max=np.inf,
                  variable=False, device=0):
     """Uploads the rows into a fresh context and profiles them: (table, sums, descriptor used)."""
-    from . import capi
-    ctx = capi.Context(device=device, variable=variable)
-    try:
-        names = "x y z vx vy vz u m alpha".split() + (["h"] if variable else [])
-        ctx.upload({k: gas[:, i] for i, k in enumerate(names)})
-        if sinks.shape[0]:
-            ctx.set_sinks({k: sinks[:, i] for i, k in zip((0, 1, 2, 3, 4, 5, 7), "x y z vx vy vz m".split())})
-        kw = {}
-        if centre is not None and centre[0] == "sink":
-            kw["sink"] = centre[1]
-        elif centre is not None:
-            kw["centre"] = (centre[1], (0.0, 0.0, 0.0), 0.0)
+    kw = {}
+    if centre is not None and centre[0] == "sink":
+        kw["sink"] = centre[1]
+    elif centre is not None:
+        kw["centre"] = (centre[1], (0.0, 0.0, 0.0), 0.0)
+    with uploaded_context(gas, sinks, variable, device) as ctx:
         table, sums = ctx.profile(r_min, r_max, n_r, n_phi, log=log, normal=normal, z_max=z_max, **kw)
         return table, sums, ctx.profile_desc
-    finally:
-        ctx.close()
 
 
 def main(argv=None) -> int:
@@ -126,9 +103,7 @@ def main(argv=None) -> int:
     out = {c: np.ascontiguousarray(table[c]) for c in capi.PROFILE_COLUMNS}
     out["edges"] = np.append(table["R_lo"][::a.nphi], table["R_hi"][-1])
     out["sums"] = sums
-    for f, _ in capi.ProfileDesc._fields_:
-        v = getattr(d, f)
-        out["desc_" + f] = np.array(v[:] if hasattr(v, "__len__") else v)
+    out.update(desc_arrays(d))
     np.savez(a.out, **out)
     if a.csv:
         np.savetxt(a.csv, np.stack([table[c] for c in capi.PROFILE_COLUMNS], axis=1), delimiter=",",

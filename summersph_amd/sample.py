@@ -28,7 +28,8 @@ import sys
 
 import numpy as np
 
-STATE = "x y z vx vy vz u m alpha".split()
+from . import cli
+from .cli import STATE, desc_arrays, parse_clip, parse_vec, read_save, uploaded_context
 
 
 # ---- point sets ----------------------------------------------------------------------------------------------------------
@@ -121,26 +122,7 @@ def line_points(a, b, n):
 def parse_fields(spec, variable=False):
     """'rho,u,vy' -> ['rho', 'u', 'vy']: 0 .. 4 field names of capi.FIELDS (h and omega only with variable h); '' -> []"""
     from . import capi
-    names = [t for t in spec.split(",") if t] if spec else []
-    allowed = [f for f in capi.FIELDS if variable or f not in ("h", "omega")]
-    if len(names) > capi.SAMPLE_MAX_FIELDS or any(f not in allowed for f in names):
-        raise ValueError(f"--fields wants 0 .. {capi.SAMPLE_MAX_FIELDS} comma-separated names of {allowed}, not {spec!r}")
-    return names
-
-
-def parse_vec(spec, what="a vector"):
-    v = [float(t) for t in spec.split(",")]
-    if len(v) != 3 or not all(math.isfinite(t) for t in v):
-        raise ValueError(f"{what} wants three finite numbers x,y,z, not {spec!r}")
-    return tuple(v)
-
-
-def parse_clip(spec):
-    """'x0,y0,z0,x1,y1,z1' -> ((x0, y0, z0), (x1, y1, z1)), no NaN and lo <= hi on every axis"""
-    v = [float(t) for t in spec.split(",")]
-    if len(v) != 6 or any(np.isnan(v)) or any(v[a] > v[3 + a] for a in range(3)):
-        raise ValueError(f"--clip wants x0,y0,z0,x1,y1,z1 with x0 <= x1 ..., not {spec!r}")
-    return tuple(v[:3]), tuple(v[3:])
+    return cli.parse_fields(spec, 0, capi.SAMPLE_MAX_FIELDS, variable)
 
 
 def points_from_args(a):
@@ -193,25 +175,15 @@ def build_parser():
 
 def sample_rows(gas, sinks, points, fields=(), volume=False, normalise=False, h=None, clip=None, variable=False, device=0):
     """Uploads the rows into a fresh context and samples: (out (K, M), den (M,), (n_hit, n_nonfinite), descriptor)."""
-    from . import capi
-    ctx = capi.Context(device=device, variable=variable)
-    try:
-        names = STATE + (["h"] if variable else [])
-        ctx.upload({k: gas[:, i] for i, k in enumerate(names)})
-        if sinks.shape[0]:
-            ctx.set_sinks({k: sinks[:, i] for i, k in zip((0, 1, 2, 3, 4, 5, 7), "x y z vx vy vz m".split())})
+    with uploaded_context(gas, sinks, variable, device) as ctx:
         if volume or any(f not in STATE + ["h"] for f in fields):
             ctx.density()                   # rho, P, c (and the rates' fields only after forces: stale otherwise)
         out, den, cnt = ctx.sample(points, fields=fields, weight="volume" if volume else "mass", normalise=normalise, h=h,
                                    clip=clip, weight_out=True, counts=True)
         return out, den, cnt, ctx.sample_desc
-    finally:
-        ctx.close()
 
 
 def main(argv=None) -> int:
-    from . import capi
-    from .profile import read_save
     ap = build_parser()
     a = ap.parse_args(argv)
     try:
@@ -227,9 +199,7 @@ def main(argv=None) -> int:
     out, den, (n_hit, n_bad), d = sample_rows(gas, sinks, points, fields, a.volume, a.normalise, a.h, clip, a.variable, a.device)
     res = {f: out[k] for k, f in enumerate(fields)}
     res.update(points=points, shape=np.array(shape, dtype=np.int64), weight=den, n_hit=np.array(n_hit), n_nonfinite=np.array(n_bad))
-    for f, _ in capi.SampleDesc._fields_:
-        val = getattr(d, f)
-        res["desc_" + f] = np.array(val[:] if hasattr(val, "__len__") else val)
+    res.update(desc_arrays(d))
     np.savez(a.out, **res)
     ok = np.isfinite(den)
     summary = {"n_points": int(points.shape[0]), "n_hit": n_hit, "n_nonfinite": n_bad,

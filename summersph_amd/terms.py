@@ -148,19 +148,13 @@ def parse_args(argv=None):
 def main(argv=None) -> int:
     a = parse_args(argv)
     from . import capi
-    from .profile import read_save
+    from .cli import read_save, uploaded_context
     gas, sinks = read_save(a.save, a.variable)
     names = "x y z vx vy vz u m alpha".split() + (["h"] if a.variable else [])
     state = {k: np.ascontiguousarray(gas[:, i]) for i, k in enumerate(names)}
     flags = (capi.FLAG_VARIABLE_H if a.variable else 0) | (capi.FLAG_SELF_GRAVITY if a.self_gravity else 0)
-    ctx = capi.Context(device=a.device, variable=a.variable, flags=flags)
-    try:
-        ctx.upload(state)
-        if sinks.shape[0]:
-            ctx.set_sinks({k: sinks[:, i] for i, k in zip((0, 1, 2, 3, 4, 5, 7), "x y z vx vy vz m".split())})
+    with uploaded_context(gas, sinks, a.variable, a.device, flags=flags) as ctx:
         rows = ctx.force_terms(skip_gas_gravity=a.no_gravity, refresh=True)
-    finally:
-        ctx.close()
     tot = totals(state, rows, a.centre)
     out = {"rows": rows, "row_names": np.array(capi.TERM_ROWS), "terms": np.array(TERMS), **tot}
     if a.edges is not None:

@@ -28,7 +28,9 @@ import sys
 
 import numpy as np
 
-from .sample import STATE, frame, line_points, parse_clip, parse_vec, plane_points
+from . import cli
+from .cli import STATE, desc_arrays, parse_clip, parse_vec, read_save, uploaded_context
+from .sample import frame, line_points, plane_points
 
 
 # ---- seeds and frames ----------------------------------------------------------------------------------------------------
@@ -94,12 +96,7 @@ def both_ways(ctx, seeds, n_steps, ds, **kw):
 # ---- command line --------------------------------------------------------------------------------------------------------
 def parse_fields(spec, variable=False):
     """'vx,vy,vz' -> ['vx', 'vy', 'vz']: exactly three field names of capi.FIELDS (h and omega only with variable h)"""
-    from . import capi
-    names = [t for t in spec.split(",") if t]
-    allowed = [f for f in capi.FIELDS if variable or f not in ("h", "omega")]
-    if len(names) != 3 or any(f not in allowed for f in names):
-        raise ValueError(f"--fields wants three comma-separated names of {allowed}, not {spec!r}")
-    return names
+    return cli.parse_fields(spec, 3, 3, variable)
 
 
 def seeds_from_args(a):
@@ -185,25 +182,16 @@ def trace_options(a, sinks=None):
 def trace_rows(gas, sinks, seeds, n_steps, ds, both=False, variable=False, device=0, **kw):
     """Uploads the rows into a fresh context and traces: Context.trace's tuple with counts (both: both_ways' tuple) and the
     descriptor."""
-    from . import capi
-    ctx = capi.Context(device=device, variable=variable)
-    try:
-        names = STATE + (["h"] if variable else [])
-        ctx.upload({k: gas[:, i] for i, k in enumerate(names)})
-        if sinks.shape[0]:
-            ctx.set_sinks({k: sinks[:, i] for i, k in zip((0, 1, 2, 3, 4, 5, 7), "x y z vx vy vz m".split())})
+    with uploaded_context(gas, sinks, variable, device) as ctx:
         used = list(kw.get("fields", ())) + ([kw["carry"]] if kw.get("carry") is not None else [])
         if kw.get("weight") == "volume" or any(f not in STATE + ["h"] for f in used):
             ctx.density()                   # rho, P, c (and the rates' fields only after forces: stale otherwise)
         res = both_ways(ctx, seeds, n_steps, ds, counts=True, **kw) if both else ctx.trace(seeds, n_steps, ds, counts=True, **kw)
         return res, ctx.trace_desc
-    finally:
-        ctx.close()
 
 
 def main(argv=None) -> int:
     from . import capi
-    from .profile import read_save
     ap = build_parser()
     a = ap.parse_args(argv)
     gas, sinks = read_save(a.save, a.variable)
@@ -220,9 +208,7 @@ def main(argv=None) -> int:
         out.update(status=res[1], n_done=res[2])
     if a.carry is not None:
         out["carry"] = res[3]
-    for f, _ in capi.TraceDesc._fields_:
-        val = getattr(d, f)
-        out["desc_" + f] = np.array(val[:] if hasattr(val, "__len__") else val)
+    out.update(desc_arrays(d))
     np.savez(a.out, **out)
     summary = {"n_seeds": int(seeds.shape[0]), "n_steps": a.steps, "rows": int(res[0].shape[0]),
                **{k: int(v) for k, v in zip(capi.TRACE_STATUS, res[-1])}}
