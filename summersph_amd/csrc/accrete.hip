@@ -252,6 +252,8 @@ __global__ __launch_bounds__(AB) void acc_compact(CompactArgs a, const int32_t *
 __global__ void sink_cull(int ns, double bound, double *__restrict__ sink, double *__restrict__ srad, int32_t *__restrict__ ns_out);
 int sinks_cull(sph_ctx *c);
 
+static int pack_survivors(sph_ctx *c, bool single, int64_t n_before, int64_t *removed);
+
 // requires a valid grid (bbox, drec, orig/inv of the current positions).  On return the context holds only
 // the survivors, in the caller's order (like a fresh upload); *removed = how many particles left.
 int accrete_and_cull(sph_ctx *c, int64_t *removed, int32_t *d_keep_out) {
@@ -259,7 +261,7 @@ int accrete_and_cull(sph_ctx *c, int64_t *removed, int32_t *d_keep_out) {
     *removed = 0;
     if (n == 0) return sinks_cull(c);
     SPH_HIP(ensure_inv(c));
-    c->keys_early = false;
+    c->early_keys_dropped();
     RootBox rb;
     double size = 0.0;
     for (int a = 0; a < 3; a++) {
@@ -285,7 +287,6 @@ int accrete_and_cull(sph_ctx *c, int64_t *removed, int32_t *d_keep_out) {
         c->path_keys_valid = true;
     }
     int32_t *keep = reinterpret_cast<int32_t *>(c->keys);          // the cell-key buffers are free between grid builds
-    int32_t *pos = reinterpret_cast<int32_t *>(c->keys_alt);
     unsigned long long *accmask = reinterpret_cast<unsigned long long *>(c->scratch);
     acc_mark<<<dim3(gb), dim3(AB), 0, c->stream>>>(rb, c->mkeys_alt, c->mvals_alt, n, drec, c->orig, c->sink, c->sink_radius, c->ns,
                                                    c->variable ? 1 : 0, c->p.bounding_size, keep, accmask);
@@ -299,58 +300,73 @@ int accrete_and_cull(sph_ctx *c, int64_t *removed, int32_t *d_keep_out) {
         }
         SPH_HIP(hipGetLastError());
     }
-    // exclusive scan of keep[] over original ids -> new ids
-    size_t sb = 0;
-    SPH_HIP(rocprim::exclusive_scan(nullptr, sb, keep, pos, 0, (size_t)n, rocprim::plus<int32_t>(), c->stream));
-    if (sb > c->sort_tmp_bytes) { c->err = "accrete: scan scratch too small"; return SPH_ERR_NOMEM; }
-    SPH_HIP(rocprim::exclusive_scan(c->sort_tmp, sb, keep, pos, 0, (size_t)n, rocprim::plus<int32_t>(), c->stream));
-    // ONE read-back per call: how many particles stay (and, variable h, how many sinks: [V]'s check_bounds culls sinks too)
-    if (c->variable && c->ns > 0) {
-        sink_cull<<<dim3(1), dim3(64), 0, c->stream>>>(c->ns, c->p.bounding_size, c->sink, c->sink_radius, c->d_flags + 2);
-        SPH_HIP(hipGetLastError());
-    }
-    int32_t *last = reinterpret_cast<int32_t *>(c->h_pinned + 300);
-    last[2] = c->ns;
-    SPH_HIP(hipMemcpyAsync(&last[0], pos + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    SPH_HIP(hipMemcpyAsync(&last[1], keep + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (c->variable && c->ns > 0) SPH_HIP(hipMemcpyAsync(&last[2], c->d_flags + 2, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    SPH_HIP(hipStreamSynchronize(c->stream));
-    c->host_syncs++;
-    if (last[2] != c->ns) { c->ns = last[2]; c->rates_valid = false; }
-    const int64_t n_new = (int64_t)last[0] + last[1];
-    if (n_new == n) return SPH_OK;                     // nobody left: sorted state stays as it is
-    CompactArgs ca{};
-    for (int k = 0; k < 9; k++) { ca.src[k] = c->f[k]; ca.dst[k] = c->f_alt[k]; }
-    ca.nf = 9;
-    if (c->variable) { ca.src[9] = c->f[SPH_F_H]; ca.dst[9] = c->f_alt[9]; ca.nf = 10; }
-    acc_compact<<<dim3(gb), dim3(AB), 0, c->stream>>>(ca, keep, pos, c->inv, n);
-    SPH_HIP(hipGetLastError());
-    for (int k = 0; k < 9; k++) std::swap(c->f[k], c->f_alt[k]);
-    if (c->variable) std::swap(c->f[SPH_F_H], c->f_alt[9]);
-    // the reference's pack ([F]:481,554) keeps the survivors' density, pressure, accelerations and rates of the last
-    // evaluation: compact those too (one field at a time through the scratch array, whose mask use is over), so that a
-    // download after the last step of a run sees them
-    const bool keep_derived = c->rates_valid;
-    if (keep_derived) {
-        for (int k = SPH_F_RHO; k < SPH_F_COUNT; k++) {
-            if ((k == SPH_F_H) || (k == SPH_F_OMEGA && !c->variable)) continue;
-            CompactArgs cd{};
-            cd.src[0] = c->f[k]; cd.dst[0] = c->scratch; cd.nf = 1;
-            acc_compact<<<dim3(gb), dim3(AB), 0, c->stream>>>(cd, keep, pos, c->inv, n);
-            std::swap(c->f[k], c->scratch);
+    return pack_survivors(c, true, n, removed);
+}
+
+// The tail of both packs.  keep[] (c->keys, by original id) marks the survivors: an exclusive scan gives their new ids, ONE
+// read-back their number, and the state is compacted into the caller's order, like a fresh upload.  single = sph_accrete_and_cull:
+// the variable-h cull of the sinks rides on the read-back ([V]'s check_bounds culls sinks too), nothing is touched when everybody
+// stays, the derived fields of a valid evaluation are compacted as well, and nobody waits for the pack; else (sph_accrete_apply_dev)
+// the ghosts go in any case and the call ends synchronised.  *removed = n_before - survivors (all particles / the owned ones).
+static int pack_survivors(sph_ctx *c, bool single, int64_t n_before, int64_t *removed) {
+    const int64_t n = c->n;
+    const unsigned gb = (unsigned)((n + AB - 1) / AB);
+    int32_t *keep = reinterpret_cast<int32_t *>(c->keys);          // the cell-key buffers are free between grid builds
+    int32_t *pos = reinterpret_cast<int32_t *>(c->keys_alt);
+    const bool cull_sinks = single && c->variable && c->ns > 0;
+    bool keep_derived = c->derived_kept;       // the multi-GPU pack has never touched the flag ("The context's state")
+    int64_t n_new = 0;
+    if (n > 0) {
+        // exclusive scan of keep[] over original ids -> new ids
+        size_t sb = 0;
+        SPH_HIP(rocprim::exclusive_scan(nullptr, sb, keep, pos, 0, (size_t)n, rocprim::plus<int32_t>(), c->stream));
+        if (sb > c->sort_tmp_bytes) { c->err = "accrete: scan scratch too small"; return SPH_ERR_NOMEM; }
+        SPH_HIP(rocprim::exclusive_scan(c->sort_tmp, sb, keep, pos, 0, (size_t)n, rocprim::plus<int32_t>(), c->stream));
+        if (cull_sinks) {
+            sink_cull<<<dim3(1), dim3(64), 0, c->stream>>>(c->ns, c->p.bounding_size, c->sink, c->sink_radius, c->d_flags + 2);
+            SPH_HIP(hipGetLastError());
         }
+        AccWords *last = &c->pin->acc;
+        last->ns = c->ns;
+        SPH_HIP(hipMemcpyAsync(&last->pos_last, pos + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        SPH_HIP(hipMemcpyAsync(&last->keep_last, keep + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (cull_sinks) SPH_HIP(hipMemcpyAsync(&last->ns, c->d_flags + 2, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        SPH_HIP(hipStreamSynchronize(c->stream));
+        if (single) c->host_syncs++;
+        if (last->ns != c->ns) { c->ns = last->ns; c->sinks_changed(); }
+        n_new = (int64_t)last->pos_last + last->keep_last;
+        if (single && n_new == n) return SPH_OK;           // nobody left: sorted state stays as it is
+        CompactArgs ca{};
+        for (int k = 0; k < 9; k++) { ca.src[k] = c->f[k]; ca.dst[k] = c->f_alt[k]; }
+        ca.nf = 9;
+        if (c->variable) { ca.src[9] = c->f[SPH_F_H]; ca.dst[9] = c->f_alt[9]; ca.nf = 10; }
+        acc_compact<<<dim3(gb), dim3(AB), 0, c->stream>>>(ca, keep, pos, c->inv, n);
         SPH_HIP(hipGetLastError());
+        for (int k = 0; k < 9; k++) std::swap(c->f[k], c->f_alt[k]);
+        if (c->variable) std::swap(c->f[SPH_F_H], c->f_alt[9]);
+        // the reference's pack ([F]:481,554) keeps the survivors' density, pressure, accelerations and rates of the last
+        // evaluation: compact those too (one field at a time through the scratch array, whose mask use is over), so that a
+        // download after the last step of a run sees them
+        if (single) keep_derived = c->rates_valid;
+        if (single && keep_derived) {
+            for (int k = SPH_F_RHO; k < SPH_F_COUNT; k++) {
+                if ((k == SPH_F_H) || (k == SPH_F_OMEGA && !c->variable)) continue;
+                CompactArgs cd{};
+                cd.src[0] = c->f[k]; cd.dst[0] = c->scratch; cd.nf = 1;
+                acc_compact<<<dim3(gb), dim3(AB), 0, c->stream>>>(cd, keep, pos, c->inv, n);
+                std::swap(c->f[k], c->scratch);
+            }
+            SPH_HIP(hipGetLastError());
+        }
     }
     c->n = n_new; c->n_slots = n_new; c->dead_below = 0;
     c->n_owned = n_new;
     SPH_HIP(launch_iota(c, c->orig, n_new));
     SPH_HIP(launch_iota(c, c->inv, n_new));
     c->inv_valid = true;
-    c->grid_valid = c->rho_valid = c->eos_valid = c->rates_valid = c->tree_valid = c->order_valid = false;
-    c->h_refresh_ok = false;
-    c->path_keys_valid = false;
-    c->derived_kept = keep_derived;
-    *removed = n - n_new;
+    if (!single) SPH_HIP(hipStreamSynchronize(c->stream));
+    c->slots_repacked(keep_derived);
+    *removed = n_before - n_new;
     return SPH_OK;
 }
 
@@ -378,7 +394,7 @@ int sinks_cull(sph_ctx *c) {
     int32_t ns_new = c->ns;
     SPH_HIP(hipMemcpyAsync(&ns_new, c->d_flags + 2, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     SPH_HIP(hipStreamSynchronize(c->stream));
-    if (ns_new != c->ns) { c->ns = ns_new; c->rates_valid = false; }
+    if (ns_new != c->ns) { c->ns = ns_new; c->sinks_changed(); }
     return SPH_OK;
 }
 
@@ -455,7 +471,7 @@ int sink_add_checked(sph_ctx *c, const double *d_cand, int32_t *created) {
     int32_t flag = 0;
     SPH_HIP(hipMemcpyAsync(&flag, c->d_flags + 2, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     SPH_HIP(hipStreamSynchronize(c->stream));
-    if (flag) { c->ns += 1; *created = 1; c->rates_valid = false; }
+    if (flag) { c->ns += 1; *created = 1; c->sinks_changed(); }
     return SPH_OK;
 }
 
@@ -507,45 +523,16 @@ int accrete_mark_ext(sph_ctx *c, int64_t src_off, double *d_partials) {
 int accrete_apply_ext(sph_ctx *c, const double *d_all, int nranks, int stride, int32_t *d_keep_out, int64_t *removed) {
     *removed = 0;
     if (!c->acc_marked) { c->err = "sph_accrete_apply_dev: call sph_accrete_mark_dev first"; return SPH_ERR_STATE; }
-    c->acc_marked = false;
+    c->marks_applied();
     SPH_HIP(ensure_inv(c));
-    c->keys_early = false;
-    const int64_t n = c->n, no = c->n_owned;
+    c->early_keys_dropped();
+    const int64_t no = c->n_owned;
     if (c->ns > 0)
         acc_sink_update_ranks<<<dim3(1), dim3(64), 0, c->stream>>>(c->ns, d_all, nranks, stride, c->sink);
     SPH_HIP(hipGetLastError());
-    int32_t *keep = reinterpret_cast<int32_t *>(c->keys);
-    int32_t *pos = reinterpret_cast<int32_t *>(c->keys_alt);
-    if (d_keep_out && no > 0) SPH_HIP(hipMemcpyAsync(d_keep_out, keep, sizeof(int32_t) * (size_t)no, hipMemcpyDeviceToDevice, c->stream));
-    int64_t n_new = 0;
-    if (n > 0) {
-        size_t sb = 0;
-        SPH_HIP(rocprim::exclusive_scan(nullptr, sb, keep, pos, 0, (size_t)n, rocprim::plus<int32_t>(), c->stream));
-        if (sb > c->sort_tmp_bytes) { c->err = "accrete: scan scratch too small"; return SPH_ERR_NOMEM; }
-        SPH_HIP(rocprim::exclusive_scan(c->sort_tmp, sb, keep, pos, 0, (size_t)n, rocprim::plus<int32_t>(), c->stream));
-        int32_t last[2];
-        SPH_HIP(hipMemcpyAsync(&last[0], pos + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        SPH_HIP(hipMemcpyAsync(&last[1], keep + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        SPH_HIP(hipStreamSynchronize(c->stream));
-        n_new = (int64_t)last[0] + last[1];
-        CompactArgs ca{};
-        for (int k = 0; k < 9; k++) { ca.src[k] = c->f[k]; ca.dst[k] = c->f_alt[k]; }
-        ca.nf = 9;
-        if (c->variable) { ca.src[9] = c->f[SPH_F_H]; ca.dst[9] = c->f_alt[9]; ca.nf = 10; }
-        acc_compact<<<dim3((unsigned)((n + AB - 1) / AB)), dim3(AB), 0, c->stream>>>(ca, keep, pos, c->inv, n);
-        SPH_HIP(hipGetLastError());
-        for (int k = 0; k < 9; k++) std::swap(c->f[k], c->f_alt[k]);
-        if (c->variable) std::swap(c->f[SPH_F_H], c->f_alt[9]);
-    }
-    c->numbers_set = false;                            // the caller's numbering has changed
-    *removed = no - n_new;                             // owned particles that left; the ghosts are dropped as well
-    c->n = n_new; c->n_slots = n_new; c->dead_below = 0;
-    c->n_owned = n_new;
-    SPH_HIP(launch_iota(c, c->orig, n_new));
-    SPH_HIP(launch_iota(c, c->inv, n_new));
-    c->inv_valid = true;
-    SPH_HIP(hipStreamSynchronize(c->stream));
-    c->grid_valid = c->rho_valid = c->eos_valid = c->rates_valid = c->tree_valid = c->order_valid = false;
+    if (d_keep_out && no > 0)
+        SPH_HIP(hipMemcpyAsync(d_keep_out, c->keys, sizeof(int32_t) * (size_t)no, hipMemcpyDeviceToDevice, c->stream));
+    SPH_TRY(pack_survivors(c, false, no, removed));    // owned particles that left; the ghosts are dropped as well
     return sinks_cull(c);                              // [V]:610-613; the sinks are replicated: every rank drops the same ones
 }
 

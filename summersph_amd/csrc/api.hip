@@ -1,6 +1,6 @@
 // api.hip -- the C ABI of libsummersph_hip.so (declared in include/summersph.h).
-// Owns the context, device memory and the call-order state machine; all arithmetic lives in
-// grid.hip / pairs.hip / integrate.hip.  There is deliberately no CPU path here.
+// Owns the context and its device memory and drives the call-order state machine (the flags and their transitions:
+// ctx_state.hpp); all arithmetic lives in grid.hip / pairs.hip / integrate.hip.  There is deliberately no CPU path here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,14 +30,13 @@ void free_particle_arrays(sph_ctx *c) {
     ctx_free(c, c->nlist); ctx_free(c, c->ncount); ctx_free(c, c->wave_max); ctx_free(c, c->ntail); ctx_free(c, c->wave_class); ctx_free(c, c->leaf_half);
     ctx_free(c, c->plan_d); ctx_free(c, c->plan_f); ctx_free(c, c->plan_h); ctx_free(c, c->deal);
     for (auto &g : c->g_cache) ctx_free(c, g);
-    c->grav_valid = false;
     ctx_free(c, c->sel_ids); c->sel_cap = 0;
     ctx_free(c, c->prec); ctx_free(c, c->lrec); ctx_free(c, c->mkeys); ctx_free(c, c->mkeys_alt);
     ctx_free(c, c->mvals); ctx_free(c, c->mvals_alt); ctx_free(c, c->msort_tmp); ctx_free(c, c->h_new);
     gravity_free(c);                                     // tree arrays are (re)allocated by the next tree build
     c->msort_tmp_bytes = 0;
     c->cap = 0; c->nl_cap = 0; c->nl_waves_cap = 0; c->sort_tmp_bytes = 0;
-    c->h_new_is_build = false; c->list_has_margin = false;
+    c->arrays_freed();
 }
 
 int ensure_capacity(sph_ctx *c, int64_t n) {
@@ -184,16 +183,16 @@ int do_density(sph_ctx *c) {
         // growth of h against the lengths the list was built with -- known only when sph_update_h produced the new h (its
         // swap left the old lengths in h_new); after an upload / scatter of h the list is built, never re-flagged
         SPH_TRY(varh_h_stats(c, c->h_new_is_build));
-        c->h_new_is_build = false;
+        c->h_growth_taken();
         { Timed t(c, SPH_K_LEAF); SPH_TRY(varh_refresh_h(c)); }
         // the list of the new lengths: re-flagged from the list in place when no h outgrew its margin, else built.  The
         // re-flag pass and the density pass that follows it walk the same rows: one kernel does both (SPH_NO_FUSED_REFLAG: A/B)
         static const bool no_fused = getenv("SPH_NO_FUSED_REFLAG") != nullptr;
-        c->rates_valid = false; c->rho_valid = false; c->eos_valid = false;
+        c->h_records_refreshed();
         if (varh_can_reflag(c) && !no_fused) {
             Timed t(c, SPH_K_REFLAG);
             SPH_TRY(varh_reflag_density(c, make_pair_const(c)));
-            c->grid_valid = true; c->h_refresh_ok = false;
+            c->grid_valid = true; c->h_refresh_settled();
             c->density_passes++;
             c->rho_valid = true; c->eos_valid = true;
             return SPH_OK;
@@ -202,17 +201,14 @@ int do_density(sph_ctx *c) {
         else { Timed t(c, SPH_K_NLIST); SPH_TRY(varh_nlist_build(c)); }
         c->grid_valid = true;
     }
-    c->h_refresh_ok = false;
+    c->h_refresh_settled();
     if (!c->grid_valid) {
-        c->h_new_is_build = false;
+        c->h_growth_taken();
         if (c->variable) SPH_TRY(varh_h_stats(c));
         { Timed t(c, SPH_K_GRID); SPH_TRY(grid_rebuild(c)); }
-        c->order_valid = true; c->derived_kept = false; c->grav_valid = false;
-        c->path_keys_valid = false;
-        c->rates_valid = false; c->rho_valid = false; c->eos_valid = false; c->tree_valid = false;
-        c->wave_class_valid = false; c->interior_done = false;
+        c->order_valid = true;
+        c->grid_rebuilt();
         if (c->variable) {
-            c->leaf_valid = false;
             { Timed t(c, SPH_K_LEAF); SPH_TRY(varh_leaf_build(c)); }
             c->leaf_valid = true;
             { Timed t(c, SPH_K_NLIST); SPH_TRY(varh_nlist_build(c)); }
@@ -276,12 +272,12 @@ int do_forces_part(sph_ctx *c, int part) {
         { Timed t(c, SPH_K_SINKACC); SPH_HIP(launch_sink_accel(c, pc)); }
         { Timed t(c, SPH_K_FORCES); SPH_HIP(use_tile_kernel(c, true) ? launch_forces_wt(c, pc, 1) : launch_forces(c, pc, 1)); }
         c->interior_done = true;
-        c->rates_valid = false;
+        c->forces_part_done(1);
         return SPH_OK;
     }
     if (!c->interior_done) { c->err = "sph_forces_part: part 2 before part 1"; return SPH_ERR_STATE; }
     { Timed t(c, SPH_K_FORCES); SPH_HIP(use_tile_kernel(c, true) ? launch_forces_wt(c, pc, 2) : launch_forces(c, pc, 2)); }
-    c->interior_done = false;
+    c->forces_part_done(2);
     c->force_passes++;
     c->rates_valid = true;
     return SPH_OK;
@@ -291,20 +287,20 @@ int do_kick(sph_ctx *c, double dt, bool dev) {
     if (!c->rates_valid) { c->err = "sph_kick: rates are stale, call sph_forces first"; return SPH_ERR_STATE; }
     Timed t(c, SPH_K_KICK);
     SPH_HIP(launch_kick(c, dt, dev));
-    c->eos_valid = false;
+    c->velocities_kicked();
     return SPH_OK;
 }
 
 int do_drift(sph_ctx *c, double dt, bool dev) {
     Timed t(c, SPH_K_DRIFT);
     SPH_HIP(launch_drift(c, dt, dev));
-    c->grid_valid = false; c->rho_valid = false; c->eos_valid = false; c->order_valid = false;
+    c->positions_moved();
     return SPH_OK;
 }
 
 int put_dt(sph_ctx *c, double dt, double t) {
-    c->h_pinned[16] = dt; c->h_pinned[17] = t; c->h_pinned[18] = 0.0;
-    SPH_HIP(hipMemcpyAsync(c->d_dt, c->h_pinned + 16, 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    c->pin->dt_in = {dt, t, 0.0};
+    SPH_HIP(hipMemcpyAsync(c->d_dt, &c->pin->dt_in, sizeof(DtWords), hipMemcpyHostToDevice, c->stream));
     return SPH_OK;
 }
 
@@ -314,27 +310,25 @@ int put_dt(sph_ctx *c, double dt, double t) {
 // after an upload) is an error here, never a silently truncated result.  Requires the stream to be idle.
 int drain_reports(sph_ctx *c) {
     if (c->ring_nl_valid) {
-        const int32_t *rep = reinterpret_cast<const int32_t *>(c->h_pinned + 240 + 8 * (1 - c->ring_nl));
+        const int32_t *rep = c->pin->nl[1 - c->ring_nl].v;
         if (rep[0] > c->nl_cap || (c->tiled && rep[3] >= 65536)) {
             c->err = "neighbour list overflowed in the last build (lists or candidate intervals grew beyond their headroom within one step): results are incomplete";
-            c->ring_nl_valid = false; c->grid_valid = false; c->rho_valid = false; c->eos_valid = false; c->rates_valid = false;
-            c->nl_overflowed = true;
+            c->list_overflow_reported();
             return SPH_ERR_STATE;
         }
     }
     if (c->ring_bbox_valid && !c->bbox_exact) {
-        const double *bb = c->h_pinned + 200 + 16 * (1 - c->ring_bbox);
-        if (*reinterpret_cast<const int32_t *>(bb + 6) != 0) { c->err = "non-finite particle position at grid build"; return SPH_ERR_NONFINITE; }
+        if (c->pin->bbox[1 - c->ring_bbox].nonfinite != 0) { c->err = "non-finite particle position at grid build"; return SPH_ERR_NONFINITE; }
     }
     return SPH_OK;
 }
 
 int get_dt(sph_ctx *c, double *dt, double *t) {
-    SPH_HIP(hipMemcpyAsync(c->h_pinned + 20, c->d_dt, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipMemcpyAsync(&c->pin->dt_out, c->d_dt, sizeof(DtWords), hipMemcpyDeviceToHost, c->stream));
     SPH_HIP(hipStreamSynchronize(c->stream));
     SPH_TRY(drain_reports(c));
-    if (dt) *dt = c->h_pinned[20];
-    if (t) *t = c->h_pinned[21];
+    if (dt) *dt = c->pin->dt_out.dt;
+    if (t) *t = c->pin->dt_out.t;
     return SPH_OK;
 }
 
@@ -345,10 +339,9 @@ int do_update_h(sph_ctx *c) {
     const PairConst pc = make_pair_const(c);
     { Timed t(c, SPH_K_UPDATE_H); SPH_HIP(launch_update_h(c, pc)); }
     // h changed: reaches, neighbour sets, rho all depend on it -- but nothing else does (do_density's short path)
-    c->grid_valid = false; c->rho_valid = false; c->eos_valid = false;
+    c->h_updated();
     c->h_refresh_ok = true;
     c->h_new_is_build = true;                           // launch_update_h swapped: h_new = the lengths of the list in place
-    c->grav_valid = false;                              // the softening length of [V]:296 is the particle's own h
     return SPH_OK;
 }
 
@@ -357,13 +350,11 @@ int do_accrete(sph_ctx *c, int64_t *removed, int32_t *d_keep = nullptr) {
     if (c->n_owned != c->n) { c->err = "sph_accrete_and_cull: not available with ghost particles"; return SPH_ERR_STATE; }
     if (!c->bbox_exact) {       // the octree's root box is the exact bounding box: take it from the last build's read-back slot
         SPH_HIP(hipStreamSynchronize(c->stream));
-        const double *bb = c->h_pinned + 200 + 16 * (1 - c->ring_bbox);
+        const double *bb = c->pin->bbox[1 - c->ring_bbox].box;
         for (int a = 0; a < 6; a++) c->bbox[a] = bb[a];
         c->bbox_exact = true;
     }
-    SPH_TRY(accrete_and_cull(c, removed, d_keep));      // includes [V]'s cull of the sinks (Variable.f90:610-613)
-    if (*removed > 0) c->numbers_set = false;           // the caller's numbering changed with the pack()
-    return SPH_OK;
+    return accrete_and_cull(c, removed, d_keep);        // includes [V]'s cull of the sinks (Variable.f90:610-613)
 }
 
 int one_step_device_dt(sph_ctx *c) {
@@ -376,9 +367,9 @@ int one_step_device_dt(sph_ctx *c) {
         Timed t(c, SPH_K_KICK);
         SPH_TRY(grid_prepare_early(c));
         const hipError_t e = c->keys_early ? launch_kick_drift_keys(c) : launch_kick_drift(c);
-        if (e != hipSuccess) c->keys_early = false;
+        if (e != hipSuccess) c->early_keys_dropped();
         SPH_HIP(e);
-        c->grid_valid = false; c->rho_valid = false; c->eos_valid = false; c->order_valid = false;
+        c->positions_moved();
     }
     SPH_TRY(do_density(c));
     SPH_TRY(do_forces(c));
@@ -386,7 +377,7 @@ int one_step_device_dt(sph_ctx *c) {
         if (!c->rates_valid) { c->err = "sph_step: rates are stale"; return SPH_ERR_STATE; }
         Timed t(c, SPH_K_DT);
         SPH_HIP(launch_kick_next_dt(c, true));
-        c->eos_valid = false;
+        c->velocities_kicked();
     }
     if (c->variable) SPH_TRY(do_update_h(c));          // Variable.f90:1152
     if (c->variable && (c->p.flags & SPH_FLAG_SINK_CREATION)) {      // Variable.f90:1155, before accretion and bounds
@@ -398,38 +389,6 @@ int one_step_device_dt(sph_ctx *c) {
         SPH_TRY(do_accrete(c, &removed));
     }
     return SPH_OK;
-}
-
-// What an overwritten field invalidates -- shared by sph_upload_field*, sph_scatter_field_dev and sph_scatter_fields_dev.
-void field_written(sph_ctx *c, int field) {
-    if (field <= SPH_F_Z || field == SPH_F_M || field == SPH_F_H) {
-        c->h_refresh_ok = field == SPH_F_H && (c->grid_valid || c->h_refresh_ok);     // only h is newer than the grid
-        c->grid_valid = false; c->rho_valid = false;
-    }
-    if (field == SPH_F_H) c->h_new_is_build = false;     // h_new no longer pairs with the new h: the next list is built, not re-flagged
-    if (field <= SPH_F_Z || field == SPH_F_M) {
-        // a new configuration: the one-build-late reports (list overflow, bounding box, non-finite flag) describe the old one,
-        // so the next build waits for its own read-backs instead of trusting them
-        c->ring_nl_valid = false; c->ring_bbox_valid = false;
-    }
-    if (field <= SPH_F_Z) { c->order_valid = false; c->keys_early = false; }     // the keys of launch_kick_drift_keys too
-    if (field <= SPH_F_ALPHA || field == SPH_F_RHO || field == SPH_F_H || field == SPH_F_OMEGA) c->eos_valid = false;
-    c->derived_kept = false;
-    c->grav_valid = false;
-}
-
-bool field_ready(const sph_ctx *c, int field) {
-    if (field <= SPH_F_ALPHA) return true;
-    if (field == SPH_F_H) return c->variable;
-    // accretion / cull compacted the derived arrays along with the state: the survivors keep the values of the last
-    // evaluation, as the reference's pack leaves them ([F]:481,554)
-    if (c->derived_kept) return field != SPH_F_OMEGA || c->variable;
-    // derived arrays are in the current slot order as long as no re-sort happened since they were
-    // written (a re-sort clears rates_valid)
-    if (field == SPH_F_OMEGA) return c->variable && (c->rho_valid || c->rates_valid);
-    if (field == SPH_F_RHO) return c->rho_valid || c->rates_valid;
-    if (field == SPH_F_P || field == SPH_F_C) return c->eos_valid || c->rates_valid;
-    return c->rates_valid;
 }
 
 }  // namespace
@@ -547,8 +506,8 @@ int sph_ctx_create(const sph_params *p, int device, sph_ctx **out) {
         if (hipEventCreateWithFlags(&c->ev_bbox[k], hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&c->ev_nl[k], hipEventDisableTiming) != hipSuccess) return fail(SPH_ERR_HIP);
     c->no_stale = getenv("SPH_SYNC_EVERY_BUILD") != nullptr;
-    if (hipHostMalloc(reinterpret_cast<void **>(&c->h_pinned), 640 * sizeof(double), hipHostMallocDefault) != hipSuccess) return fail(SPH_ERR_NOMEM);
-    std::memset(c->h_pinned, 0, 640 * sizeof(double));
+    if (hipHostMalloc(reinterpret_cast<void **>(&c->pin), sizeof(PinnedSlots), hipHostMallocDefault) != hipSuccess) return fail(SPH_ERR_NOMEM);
+    std::memset(c->pin, 0, sizeof(PinnedSlots));
     if ((st = ctx_alloc(c, &c->bbox_part, BBOX_PART_CLASSIC + (size_t)EARLY_MAX_BLOCKS * 6, "bbox")) != SPH_OK) return fail(st);
     if ((st = ctx_alloc(c, &c->d_flags, 8, "flags")) != SPH_OK) return fail(st);
     if (hipMemset(c->d_flags, 0, 8 * sizeof(int32_t)) != hipSuccess) return fail(SPH_ERR_HIP);
@@ -595,7 +554,7 @@ int sph_ctx_destroy(sph_ctx *c) {
     ctx_free(c, c->grav_tab); ctx_free(c, c->sink_radius);
     ctx_free(c, c->w_tab); ctx_free(c, c->dw_tab); ctx_free(c, c->w_pair); ctx_free(c, c->dw_pair); ctx_free(c, c->sink); ctx_free(c, c->sink_part);
     ctx_free(c, c->dt_part); ctx_free(c, c->d_dt);
-    if (c->h_pinned) (void)hipHostFree(c->h_pinned);
+    if (c->pin) (void)hipHostFree(c->pin);
     for (int k = 0; k < 2; k++) { if (c->ev_bbox[k]) (void)hipEventDestroy(c->ev_bbox[k]); if (c->ev_nl[k]) (void)hipEventDestroy(c->ev_nl[k]); }
     ctx_free(c, c->sel_count); ctx_free_ptr(c, c->sel_tmp); ctx_free(c, c->bnd_boxes);
     render_free(c);
@@ -625,7 +584,6 @@ static int upload_impl(sph_ctx *c, int64_t n, const double *const src[9], hipMem
     DeviceGuard g(c->device);
     SPH_TRY(ensure_capacity(c, n));
     c->n = n; c->n_slots = n; c->dead_below = 0;
-    c->numbers_set = false;
     c->n_owned = n;
     for (int k = 0; k < 9; k++) {
         if (n == 0) break;
@@ -634,14 +592,10 @@ static int upload_impl(sph_ctx *c, int64_t n, const double *const src[9], hipMem
     }
     SPH_HIP(launch_iota(c, c->orig, n));
     SPH_HIP(launch_iota(c, c->inv, n));
-    c->inv_valid = true; c->keys_early = false;
+    c->inv_valid = true;
     if (c->variable) SPH_HIP(launch_fill(c, c->f[SPH_F_H], c->p.h, n));    // until sph_upload_field(SPH_F_H) sets it
     SPH_HIP(hipStreamSynchronize(c->stream));
-    c->grid_valid = c->rho_valid = c->eos_valid = c->rates_valid = c->order_valid = c->tree_valid = false;
-    c->derived_kept = false;
-    c->ring_bbox_valid = c->ring_nl_valid = false;       // a new particle set: the next build waits for its own read-backs
-    c->nl_overflowed = false;
-    c->h_new_is_build = false; c->h_refresh_ok = false;
+    c->particle_set_replaced();
     return SPH_OK;
 }
 
@@ -671,7 +625,7 @@ int sph_set_sinks(sph_ctx *c, int32_t ns, const double *sx, const double *sy, co
     std::vector<double> rad((size_t)MAX_SINKS, c->variable ? 5.0 : 3.5);      // Variable.f90:830 / SUMMER_SPH.f90:694
     SPH_HIP(hipMemcpy(c->sink_radius, rad.data(), rad.size() * sizeof(double), hipMemcpyHostToDevice));
     c->ns = ns;
-    c->rates_valid = false;
+    c->sinks_changed();
     return SPH_OK;
 }
 
@@ -713,7 +667,7 @@ int sph_step(sph_ctx *c, double *dt, double *t) { return sph_run(c, 1, dt, t); }
 
 int sph_download_field_dev(sph_ctx *c, int field, double *d_out, int64_t n) {
     if (!c || field < 0 || field >= SPH_F_COUNT || n != c->n || (n > 0 && !d_out)) return SPH_ERR_ARG;
-    if (!field_ready(c, field)) { c->err = "sph_download_field: field is stale"; return SPH_ERR_STATE; }
+    if (!field_ready(*c, c->variable, field)) { c->err = "sph_download_field: field is stale"; return SPH_ERR_STATE; }
     DeviceGuard g(c->device);
     SPH_HIP(launch_unpermute(c, c->f[field], d_out));
     SPH_HIP(hipStreamSynchronize(c->stream));
@@ -722,7 +676,7 @@ int sph_download_field_dev(sph_ctx *c, int field, double *d_out, int64_t n) {
 
 int sph_download_field(sph_ctx *c, int field, double *host, int64_t n) {
     if (!c || field < 0 || field >= SPH_F_COUNT || n != c->n || (n > 0 && !host)) return SPH_ERR_ARG;
-    if (!field_ready(c, field)) { c->err = "sph_download_field: field is stale"; return SPH_ERR_STATE; }
+    if (!field_ready(*c, c->variable, field)) { c->err = "sph_download_field: field is stale"; return SPH_ERR_STATE; }
     if (n == 0) return SPH_OK;
     DeviceGuard g(c->device);
     SPH_HIP(launch_unpermute(c, c->f[field], c->scratch));
@@ -792,7 +746,7 @@ static int upload_field_impl(sph_ctx *c, int field, const double *src, int64_t n
     const int f = field;
     SPH_HIP(launch_scatter_fields(c, 1, &f, 0, n, dsrc));
     SPH_HIP(hipStreamSynchronize(c->stream));
-    field_written(c, field);
+    c->field_written(field);
     return SPH_OK;
 }
 
@@ -838,8 +792,7 @@ int sph_update_h(sph_ctx *c) { if (!c) return SPH_ERR_ARG; DeviceGuard g(c->devi
 int sph_set_owned(sph_ctx *c, int64_t n_owned) {
     if (!c || n_owned < 0 || n_owned > c->n) return SPH_ERR_ARG;
     c->n_owned = n_owned;
-    c->h_refresh_ok = false; c->keys_early = false;
-    c->grid_valid = c->rho_valid = c->eos_valid = c->rates_valid = false;
+    c->owned_count_changed();
     return SPH_OK;
 }
 
@@ -855,7 +808,7 @@ int sph_scatter_field_dev(sph_ctx *c, int field, int64_t first, int64_t count, c
     DeviceGuard g(c->device);
     SPH_HIP(launch_scatter_field(c, c->f[field], first, count, d_vals));
     if ((field == SPH_F_H || field == SPH_F_OMEGA) && !c->variable) { c->err = "field needs SPH_FLAG_VARIABLE_H"; return SPH_ERR_ARG; }
-    field_written(c, field);
+    c->field_written(field);
     return SPH_OK;
 }
 
@@ -863,7 +816,7 @@ static bool fields_ok(const sph_ctx *c, int nf, const int *fields, bool for_read
     if (nf < 1 || nf > SPH_F_COUNT || !fields) return false;
     for (int f = 0; f < nf; f++) {
         if (fields[f] < 0 || fields[f] >= SPH_F_COUNT) return false;
-        if (for_read && !field_ready(c, fields[f])) return false;
+        if (for_read && !field_ready(*c, c->variable, fields[f])) return false;
     }
     return true;
 }
@@ -882,7 +835,7 @@ int sph_scatter_fields_dev(sph_ctx *c, int32_t nf, const int32_t *fields, int64_
     if (!fields_ok(c, nf, fields, false)) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
     SPH_HIP(launch_scatter_fields(c, nf, fields, first, count, d_vals));
-    for (int f = 0; f < nf; f++) field_written(c, fields[f]);
+    for (int f = 0; f < nf; f++) c->field_written(fields[f]);
     return SPH_OK;
 }
 
@@ -906,9 +859,9 @@ int sph_dt_candidate(sph_ctx *c, double *cand) {
     if (!c->rates_valid) { c->err = "sph_dt_candidate: rates are stale"; return SPH_ERR_STATE; }
     DeviceGuard g(c->device);
     { Timed t(c, SPH_K_DT); SPH_HIP(launch_dt_partial_only(c)); }
-    SPH_HIP(hipMemcpyAsync(c->h_pinned + 24, c->d_dt + 2, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipMemcpyAsync(&c->pin->dt_cand, c->d_dt + 2, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     SPH_HIP(hipStreamSynchronize(c->stream));
-    *cand = c->h_pinned[24];
+    *cand = c->pin->dt_cand;
     return SPH_OK;
 }
 
@@ -999,7 +952,7 @@ int sph_replace_ghosts_dev(sph_ctx *c, int64_t count, const double *d_state) {
     DeviceGuard g(c->device);
     SPH_TRY(domain_replace_ghosts(c, count, d_state));
     if (c->own_stream) SPH_HIP(hipStreamSynchronize(c->stream));
-    c->grid_valid = c->rho_valid = c->eos_valid = c->rates_valid = c->order_valid = c->tree_valid = false;
+    c->ghosts_replaced();
     return SPH_OK;
 }
 
@@ -1007,10 +960,10 @@ int sph_set_boundary_boxes(sph_ctx *c, int32_t nbox, const double *boxes) {
     if (!c || nbox < 0 || nbox > MAX_SEL_BOXES || (nbox > 0 && !boxes)) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
     if (!c->bnd_boxes) SPH_TRY(ctx_alloc(c, &c->bnd_boxes, (size_t)6 * MAX_SEL_BOXES, "boundary boxes"));
-    for (int k = 0; k < 6 * nbox; k++) c->h_pinned[128 + k] = boxes[k];      // pinned staging: no host synchronisation
-    if (nbox > 0) SPH_HIP(hipMemcpyAsync(c->bnd_boxes, c->h_pinned + 128, (size_t)6 * nbox * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    for (int k = 0; k < 6 * nbox; k++) c->pin->bnd_boxes[k] = boxes[k];      // pinned staging: no host synchronisation
+    if (nbox > 0) SPH_HIP(hipMemcpyAsync(c->bnd_boxes, c->pin->bnd_boxes, (size_t)6 * nbox * sizeof(double), hipMemcpyHostToDevice, c->stream));
     c->n_bnd_boxes = nbox;
-    c->wave_class_valid = false;
+    c->wave_classes_stale();
     return SPH_OK;
 }
 
@@ -1026,11 +979,7 @@ int sph_set_gravity_sources_dev(sph_ctx *c, int64_t n_src, const double *d_xyzm,
     c->gx_src = n_src > 0 ? d_xyzm : nullptr;
     c->gx_n = n_src;
     for (int a = 0; a < 6; a++) c->gx_box[a] = n_src > 0 ? lo_hi[a] : 0.0;
-    c->gx_keys_valid = false;
-    c->tree_valid = false; c->grav_valid = false;
-    c->leaf_valid = false;
-    c->rates_valid = false;
-    if (c->variable) { c->grid_valid = false; c->rho_valid = false; c->eos_valid = false; }      // the leaf boxes change
+    c->gravity_sources_changed(c->variable);
     return SPH_OK;
 }
 
@@ -1054,7 +1003,7 @@ int sph_set_numbers_dev(sph_ctx *c, int64_t first, int64_t count, const int64_t 
     DeviceGuard g(c->device);
     SPH_HIP(launch_set_numbers(c, first, count, d_numbers));
     c->numbers_set = true;
-    if (c->variable) { c->grid_valid = false; c->rho_valid = false; c->eos_valid = false; }
+    c->numbers_changed(c->variable);
     return SPH_OK;
 }
 
@@ -1095,7 +1044,7 @@ int sph_kick_drift_devdt(sph_ctx *c) {
     DeviceGuard g(c->device);
     Timed t(c, SPH_K_KICK);
     SPH_HIP(launch_kick_drift(c));
-    c->grid_valid = false; c->rho_valid = false; c->eos_valid = false; c->order_valid = false;
+    c->positions_moved();
     return SPH_OK;
 }
 
@@ -1106,7 +1055,7 @@ int sph_kick_dt_candidate_dev(sph_ctx *c) {
     DeviceGuard g(c->device);
     Timed t(c, SPH_K_DT);
     SPH_HIP(launch_kick_dt_candidate(c));
-    c->eos_valid = false;
+    c->velocities_kicked();
     return SPH_OK;
 }
 
@@ -1118,7 +1067,7 @@ int sph_kick_dt_candidate_gas_dev(sph_ctx *c) {
     DeviceGuard g(c->device);
     Timed t(c, SPH_K_DT);
     SPH_HIP(launch_kick_dt_candidate(c, false));
-    c->eos_valid = false;
+    c->velocities_kicked();
     return SPH_OK;
 }
 
@@ -1176,7 +1125,7 @@ int sph_get_bbox(sph_ctx *c, double *lo, double *hi) {
     if (!c->grid_valid) { c->err = "sph_get_bbox: no grid built for the current positions"; return SPH_ERR_STATE; }
     DeviceGuard g(c->device);
     SPH_HIP(hipStreamSynchronize(c->stream));             // the exact box of the last build sits in its read-back slot
-    const double *bb = c->h_pinned + 200 + 16 * (1 - c->ring_bbox);
+    const double *bb = c->pin->bbox[1 - c->ring_bbox].box;
     for (int a = 0; a < 3; a++) { lo[a] = bb[a]; hi[a] = bb[3 + a]; }
     return SPH_OK;
 }
@@ -1227,14 +1176,14 @@ int sph_render_field(sph_ctx *c, sph_render_field_desc *d, const double *values,
                      int64_t out_len) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    return render_field(c, d, values, host_out, host_weight, out_len, true, field_ready);
+    return render_field(c, d, values, host_out, host_weight, out_len, true);
 }
 
 int sph_render_field_dev(sph_ctx *c, sph_render_field_desc *d, const double *d_values, double *d_out, double *d_weight,
                          int64_t out_len) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    return render_field(c, d, d_values, d_out, d_weight, out_len, false, field_ready);
+    return render_field(c, d, d_values, d_out, d_weight, out_len, false);
 }
 
 int sph_profile(sph_ctx *c, sph_profile_desc *d, double *host_sums, double *host_table, int64_t n_bins) {
@@ -1265,28 +1214,28 @@ int sph_groups(sph_ctx *c, const sph_groups_desc *d, int32_t *host_labels, int64
                int64_t max_groups, int64_t *n_groups) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    return groups_run(c, d, host_labels, n_labels, host_table, max_groups, n_groups, true, field_ready);
+    return groups_run(c, d, host_labels, n_labels, host_table, max_groups, n_groups, true);
 }
 
 int sph_groups_dev(sph_ctx *c, const sph_groups_desc *d, int32_t *d_labels, int64_t n_labels, double *d_table,
                    int64_t max_groups, int64_t *d_n_groups) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    return groups_run(c, d, d_labels, n_labels, d_table, max_groups, d_n_groups, false, field_ready);
+    return groups_run(c, d, d_labels, n_labels, d_table, max_groups, d_n_groups, false);
 }
 
 int sph_peaks(sph_ctx *c, const sph_peaks_desc *d, int32_t *host_labels, int64_t n_labels, double *host_table,
               int64_t max_groups, int64_t *counts) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    return peaks_run(c, d, host_labels, n_labels, host_table, max_groups, counts, true, field_ready);
+    return peaks_run(c, d, host_labels, n_labels, host_table, max_groups, counts, true);
 }
 
 int sph_peaks_dev(sph_ctx *c, const sph_peaks_desc *d, int32_t *d_labels, int64_t n_labels, double *d_table,
                   int64_t max_groups, int64_t *d_counts) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    return peaks_run(c, d, d_labels, n_labels, d_table, max_groups, d_counts, false, field_ready);
+    return peaks_run(c, d, d_labels, n_labels, d_table, max_groups, d_counts, false);
 }
 
 int sph_gradients(sph_ctx *c, const sph_gradients_desc *d, const double *values, double *host_out, int64_t n_out,
@@ -1294,7 +1243,7 @@ int sph_gradients(sph_ctx *c, const sph_gradients_desc *d, const double *values,
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
     int64_t counts[2] = {0, 0};
-    const int st = gradients_run(c, d, values, host_out, n_out, host_rho, counts, true, field_ready);
+    const int st = gradients_run(c, d, values, host_out, n_out, host_rho, counts, true);
     if (st != SPH_OK) return st;
     if (n_targets) *n_targets = counts[0];
     if (n_singular) *n_singular = counts[1];
@@ -1305,21 +1254,21 @@ int sph_gradients_dev(sph_ctx *c, const sph_gradients_desc *d, const double *d_v
                       double *d_rho, int64_t *d_counts) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    return gradients_run(c, d, d_values, d_out, n_out, d_rho, d_counts, false, field_ready);
+    return gradients_run(c, d, d_values, d_out, n_out, d_rho, d_counts, false);
 }
 
 int sph_sample(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const double *px, const double *py, const double *pz,
                const double *values, double *host_out, int64_t n_out, double *host_weight, int64_t *counts) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    return sample_run(c, d, n_points, px, py, pz, values, host_out, n_out, host_weight, counts, true, field_ready);
+    return sample_run(c, d, n_points, px, py, pz, values, host_out, n_out, host_weight, counts, true);
 }
 
 int sph_sample_dev(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const double *d_px, const double *d_py,
                    const double *d_pz, const double *d_values, double *d_out, int64_t n_out, double *d_weight, int64_t *d_counts) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    return sample_run(c, d, n_points, d_px, d_py, d_pz, d_values, d_out, n_out, d_weight, d_counts, false, field_ready);
+    return sample_run(c, d, n_points, d_px, d_py, d_pz, d_values, d_out, n_out, d_weight, d_counts, false);
 }
 
 int sph_trace(sph_ctx *c, const sph_trace_desc *d, int64_t n_seeds, const double *sx, const double *sy, const double *sz,
@@ -1327,8 +1276,7 @@ int sph_trace(sph_ctx *c, const sph_trace_desc *d, int64_t n_seeds, const double
               int32_t *host_n_done, int64_t *counts) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    return trace_run(c, d, n_seeds, sx, sy, sz, values, host_path, n_path, host_carry, host_status, host_n_done, counts, true,
-                     field_ready);
+    return trace_run(c, d, n_seeds, sx, sy, sz, values, host_path, n_path, host_carry, host_status, host_n_done, counts, true);
 }
 
 int sph_trace_dev(sph_ctx *c, const sph_trace_desc *d, int64_t n_seeds, const double *d_sx, const double *d_sy,
@@ -1336,8 +1284,7 @@ int sph_trace_dev(sph_ctx *c, const sph_trace_desc *d, int64_t n_seeds, const do
                   int32_t *d_n_done, int64_t *d_counts) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    return trace_run(c, d, n_seeds, d_sx, d_sy, d_sz, d_values, d_path, n_path, d_carry, d_status, d_n_done, d_counts, false,
-                     field_ready);
+    return trace_run(c, d, n_seeds, d_sx, d_sy, d_sz, d_values, d_path, n_path, d_carry, d_status, d_n_done, d_counts, false);
 }
 
 int sph_gravity_at(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_points, const double *px, const double *py,
@@ -1371,13 +1318,13 @@ int sph_bound_dev(sph_ctx *c, const sph_bound_desc *d, const int32_t *d_labels, 
 int sph_cube(sph_ctx *c, const sph_cube_desc *d, const double *values, double *host_out, int64_t out_len) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    return cube_run(c, d, values, host_out, out_len, true, field_ready);
+    return cube_run(c, d, values, host_out, out_len, true);
 }
 
 int sph_cube_dev(sph_ctx *c, const sph_cube_desc *d, const double *d_values, double *d_out, int64_t out_len) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    return cube_run(c, d, d_values, d_out, out_len, false, field_ready);
+    return cube_run(c, d, d_values, d_out, out_len, false);
 }
 
 int sph_force_terms(sph_ctx *c, const sph_force_terms_desc *d, double *host_out, int64_t n_out) {
@@ -1396,14 +1343,14 @@ int sph_binned(sph_ctx *c, const sph_binned_desc *d, const double *values, const
                int64_t n_sums, int64_t *counts) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    return binned_run(c, d, values, edges, host_sums, n_sums, counts, true, field_ready);
+    return binned_run(c, d, values, edges, host_sums, n_sums, counts, true);
 }
 
 int sph_binned_dev(sph_ctx *c, const sph_binned_desc *d, const double *d_values, const double *edges, double *d_sums,
                    int64_t n_sums, int64_t *d_counts) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
-    return binned_run(c, d, d_values, edges, d_sums, n_sums, d_counts, false, field_ready);
+    return binned_run(c, d, d_values, edges, d_sums, n_sums, d_counts, false);
 }
 
 int sph_synchronize(sph_ctx *c) {

@@ -290,7 +290,7 @@ const char *axis_edges(const sph_binned_desc *d, const double *edges, int a, dou
 }  // namespace
 
 int binned_run(sph_ctx *c, const sph_binned_desc *d, const double *values, const double *edges, double *sums, int64_t n_sums,
-               int64_t *counts, bool host, bool (*ready)(const sph_ctx *, int)) {
+               int64_t *counts, bool host) {
     const char *who = "sph_binned";
     if (!d) return arg_error(c, who, "null descriptor");
     if (!sums) return arg_error(c, who, "null output");
@@ -320,12 +320,12 @@ int binned_run(sph_ctx *c, const sph_binned_desc *d, const double *values, const
     uint32_t rows_used = 0;                              // the rows some source reads
     auto use = [&](int32_t id) {
         if (id < 0) { rows_used |= 1u << (-1 - id); return true; }
-        return ready(c, id);
+        return field_ready(*c, c->variable, id);
     };
     bool fresh = true;
     for (int a = 0; a < d->n_axes; a++) fresh = use(d->axis[a]) && fresh;
     for (int k = 0; k < nq; k++) fresh = use(d->q[k]) && fresh;
-    if (d->weight == SPH_BINNED_W_VOLUME) fresh = ready(c, SPH_F_RHO) && fresh;
+    if (d->weight == SPH_BINNED_W_VOLUME) fresh = field_ready(*c, c->variable, SPH_F_RHO) && fresh;
     if (!fresh) {
         c->err = "sph_binned: a field is stale (as sph_download_field would refuse it)";
         return SPH_ERR_STATE;

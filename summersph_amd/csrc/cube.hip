@@ -388,8 +388,7 @@ __global__ __launch_bounds__(GT) void cube_gather(GatherArgs A) {
 
 }  // namespace
 
-int cube_run(sph_ctx *c, const sph_cube_desc *d, const double *values, double *out, int64_t out_len, bool host,
-             bool (*ready)(const sph_ctx *, int)) {
+int cube_run(sph_ctx *c, const sph_cube_desc *d, const double *values, double *out, int64_t out_len, bool host) {
     const char *who = "sph_cube";
     if (!d || !out) return arg_error(c, who, "null descriptor or output");
     if (d->reserved != 0) return arg_error(c, who, "reserved must be 0");
@@ -420,7 +419,7 @@ int cube_run(sph_ctx *c, const sph_cube_desc *d, const double *values, double *o
         const double det = r[0] * (r[4] * r[8] - r[5] * r[7]) - r[1] * (r[3] * r[8] - r[5] * r[6]) + r[2] * (r[3] * r[7] - r[4] * r[6]);
         if (!(ok && std::fabs(det - 1.0) <= 1e-12)) return arg_error(c, who, "rot must be orthonormal and right-handed within 1e-12");
     }
-    if (d->sigma_scale != 0.0 && !ready(c, SPH_F_C)) {
+    if (d->sigma_scale != 0.0 && !field_ready(*c, c->variable, SPH_F_C)) {
         c->err = "sph_cube: c is stale (sph_download_field would refuse it) and sigma_scale > 0";
         return SPH_ERR_STATE;
     }

@@ -139,7 +139,7 @@ __global__ void apply_partials(const double *__restrict__ all, int nranks, int s
 int domain_select_boxes_enqueue(sph_ctx *c, int nbox, const double *boxes) {
     const int64_t no = c->n_owned;
     c->sel_stride = no;
-    int64_t *h = reinterpret_cast<int64_t *>(c->h_pinned + 64);
+    int64_t *h = c->pin->sel_counts;
     for (int b = 0; b < nbox; b++) h[b] = 0;
     if (!c->sel_count) {
         if (ctx_alloc(c, &c->sel_count, (size_t)MAX_SEL_BOXES, "selection counts") != SPH_OK) return SPH_ERR_NOMEM;
@@ -175,7 +175,7 @@ int domain_select_boxes_enqueue(sph_ctx *c, int nbox, const double *boxes) {
 }
 
 void domain_selected_counts(sph_ctx *c, int nbox, int64_t *counts) {
-    const int64_t *h = reinterpret_cast<const int64_t *>(c->h_pinned + 64);
+    const int64_t *h = c->pin->sel_counts;
     for (int b = 0; b < nbox; b++) counts[b] = h[b];
 }
 
@@ -194,7 +194,6 @@ int domain_replace_ghosts(sph_ctx *c, int64_t count, const double *d_vals) {
         return SPH_ERR_NOMEM;
     }
     SPH_HIP(ensure_inv(c));            // from the reorder's orig, before ghosts are appended to it
-    c->keys_early = false;
     if (count > 0) {
         FieldPtrs9 fp{};
         for (int f = 0; f < 9; f++) fp.p[f] = c->f[f];

@@ -251,7 +251,7 @@ int energy_sums(sph_ctx *c, int64_t src_offset, double *sums, double *phi, int64
                 for (int a = 0; a < 4; a++) rb[a] = c->root_box[a];
                 SPH_TRY(gravity_tree_build(c));
                 for (int a = 0; a < 4; a++) c->root_box[a] = rb[a];
-                c->grav_valid = false;
+                c->tree_rebuilt_for_analysis();
             }
         }
         SPH_HIP(launch_potential(c, n_src, src_offset, phi_self));

@@ -348,7 +348,7 @@ hipError_t launch_walk(bool corrected, unsigned nb, hipStream_t st, const double
 }  // namespace
 
 int gradients_run(sph_ctx *c, const sph_gradients_desc *d, const double *values, double *out, int64_t n_out, double *rho_out,
-                  int64_t *counts, bool host, bool (*ready)(const sph_ctx *, int)) {
+                  int64_t *counts, bool host) {
     const char *who = "sph_gradients";
     if (!d) return arg_error(c, who, "null descriptor");
     if (d->reserved[0] != 0 || d->reserved[1] != 0) return arg_error(c, who, "reserved must be 0");
@@ -369,7 +369,7 @@ int gradients_run(sph_ctx *c, const sph_gradients_desc *d, const double *values,
     for (int a = 0; a < 3; a++)
         if (std::isnan(d->clip_lo[a]) || std::isnan(d->clip_hi[a])) return arg_error(c, who, "the clip box has a NaN");
     for (int k = 0; k < nf; k++)
-        if (d->fields[k] >= 0 && !ready(c, d->fields[k])) {
+        if (d->fields[k] >= 0 && !field_ready(*c, c->variable, d->fields[k])) {
             c->err = "sph_gradients: a field is stale (as sph_download_field would refuse it)";
             return SPH_ERR_STATE;
         }

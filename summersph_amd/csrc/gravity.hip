@@ -576,7 +576,7 @@ void gravity_free(sph_ctx *c) {
     ctx_free(c, c->g_leafA); ctx_free(c, c->g_walkB); ctx_free(c, c->g_leafB);
     ctx_free(c, c->g_keys); ctx_free(c, c->g_keys_alt); ctx_free(c, c->g_vals); ctx_free(c, c->g_vals_alt);
     ctx_free_ptr(c, c->g_sort_tmp); c->g_sort_tmp = nullptr; c->g_sort_tmp_bytes = 0;
-    c->g_cap = 0; c->gx_keys_valid = false;
+    c->g_cap = 0; c->tree_arrays_freed();
 }
 
 // tree arrays for `need` leaves (the context's slots, or an external source set that may be much larger)
@@ -697,7 +697,7 @@ int gravity_tree_build(sph_ctx *c) {
 // sort, the same kernels).  Built into the context's tree arrays: the context's own tree, the sorted external keys
 // and the cached self-gravity term are no longer there, so they are marked stale (the next sph_forces rebuilds them).
 int gravity_tree_build_records(sph_ctx *c, const double *rec, int64_t n, const double box[6]) {
-    c->tree_valid = false; c->grav_valid = false; c->gx_keys_valid = false;
+    c->tree_arrays_taken();
     if (n == 0) return SPH_OK;
     if (n > 2000000000LL) { c->err = "gravity: more than 2e9 sources"; return SPH_ERR_ARG; }
     { const int st = gravity_reserve(c, std::max(c->cap, n)); if (st != SPH_OK) return st; }

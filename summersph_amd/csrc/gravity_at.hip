@@ -227,7 +227,7 @@ int gravity_at_run(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_points, c
             for (int a = 0; a < 4; a++) keep[a] = c->root_box[a];
             SPH_TRY(gravity_tree_build(c));
             for (int a = 0; a < 4; a++) c->root_box[a] = keep[a];
-            c->grav_valid = false;
+            c->tree_rebuilt_for_analysis();
         }
         rb.size = 0.0;
         for (int a = 0; a < 3; a++) {                                  // the root box of the tree ([F]:803-808)

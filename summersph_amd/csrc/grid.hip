@@ -633,9 +633,9 @@ int owned_bbox(sph_ctx *c, double *d_out6, double *h_out6) {
     SPH_HIP(hipGetLastError());
     if (d_out6) SPH_HIP(hipMemcpyAsync(d_out6, res, 6 * sizeof(double), hipMemcpyDeviceToDevice, st));
     if (h_out6) {
-        SPH_HIP(hipMemcpyAsync(c->h_pinned + 48, res, 6 * sizeof(double), hipMemcpyDeviceToHost, st));
+        SPH_HIP(hipMemcpyAsync(c->pin->owned_box, res, 6 * sizeof(double), hipMemcpyDeviceToHost, st));
         SPH_HIP(hipStreamSynchronize(st));
-        for (int a = 0; a < 6; a++) h_out6[a] = c->h_pinned[48 + a];
+        for (int a = 0; a < 6; a++) h_out6[a] = c->pin->owned_box[a];
     }
     return SPH_OK;
 }
@@ -772,8 +772,8 @@ int grid_prepare_early(sph_ctx *c) {
         return SPH_OK;
     const int q = 1 - c->ring_bbox;
     SPH_HIP(hipEventSynchronize(c->ev_bbox[q]));
-    const double *bb = c->h_pinned + 200 + 16 * q;
-    if (*reinterpret_cast<const int32_t *>(bb + 6) != 0) return SPH_OK;         // grid_rebuild reports it
+    const double *bb = c->pin->bbox[q].box;
+    if (c->pin->bbox[q].nonfinite != 0) return SPH_OK;         // grid_rebuild reports it
     const double guard = 2.0 * c->p.h * (1.0 + 1e-6);
     double box[6];
     for (int a = 0; a < 3; a++) { box[a] = bb[a] - guard; box[3 + a] = bb[3 + a] + guard; }
@@ -819,7 +819,7 @@ int grid_rebuild(sph_ctx *c) {
     // ---- bounding box ---------------------------------------------------------------
     int nb = (int)std::min<int64_t>((ns + BB_BLOCK - 1) / BB_BLOCK, BB_MAX_BLOCKS);
     const int p = c->ring_bbox;
-    double *slot = c->h_pinned + 200 + 16 * p;
+    double *slot = c->pin->bbox[p].box;      // bbox_final writes the whole BoxReport through it
     const bool stale = c->ring_bbox_valid && !c->no_stale && !c->variable && !c->gravity && !(c->p.flags & SPH_FLAG_ACCRETE_CULL);
     early = early && stale && !swap && ns == n;
     auto box_launches = [&]() -> int {
@@ -837,16 +837,17 @@ int grid_rebuild(sph_ctx *c) {
     // boundary cells and still meet all their neighbours there, so the box only has to be roughly right.
     // With the partials of launch_kick_drift_keys in place the box is finished further down, on cell_scatter.
     if (!early) SPH_TRY(box_launches());
-    const double *bb = slot;
+    const BoxReport *rep = &c->pin->bbox[p];
     if (stale) {
         SPH_HIP(hipEventSynchronize(c->ev_bbox[1 - p]));
-        bb = c->h_pinned + 200 + 16 * (1 - p);
+        rep = &c->pin->bbox[1 - p];
     } else {
         SPH_HIP(hipStreamSynchronize(st));
         c->host_syncs++;
     }
     c->ring_bbox = 1 - p; c->ring_bbox_valid = true; c->bbox_exact = !stale;
-    if (*reinterpret_cast<const int32_t *>(bb + 6) != 0) {
+    const double *bb = rep->box;
+    if (rep->nonfinite != 0) {
         c->err = "non-finite particle position at grid build";
         return SPH_ERR_NONFINITE;
     }
@@ -899,10 +900,10 @@ int grid_rebuild(sph_ctx *c) {
                                                                 (int32_t)c->n_owned, c->dead_below);
             moment_final<<<dim3(1), dim3(448), 0, st>>>(mpart, nb, mpart + (size_t)BB_MAX_BLOCKS * 7);
             SPH_HIP(hipGetLastError());
-            SPH_HIP(hipMemcpyAsync(c->h_pinned + 280, mpart + (size_t)BB_MAX_BLOCKS * 7, 7 * sizeof(double), hipMemcpyDeviceToHost, st));
+            SPH_HIP(hipMemcpyAsync(c->pin->trim, mpart + (size_t)BB_MAX_BLOCKS * 7, 7 * sizeof(double), hipMemcpyDeviceToHost, st));
             SPH_HIP(hipStreamSynchronize(st));
             c->host_syncs++;
-            const double *mo = c->h_pinned + 280;
+            const double *mo = c->pin->trim;
             if (!(mo[0] >= 1.0)) break;
             bool shrunk = false;
             for (int a = 0; a < 3; a++) {

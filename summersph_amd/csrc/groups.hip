@@ -549,7 +549,7 @@ int groups_tail(sph_ctx *c, GroupsWork &w, int64_t min_members, int32_t *d_label
 }
 
 int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_labels, double *table, int64_t max_groups,
-               int64_t *n_groups, bool host, bool (*ready)(const sph_ctx *, int)) {
+               int64_t *n_groups, bool host) {
     const char *who = "sph_groups";
     if (!d) return arg_error(c, who, "null descriptor");
     if (!n_groups) return arg_error(c, who, "null count pointer");
@@ -563,7 +563,7 @@ int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_
     if (labels && n_labels != c->n) return arg_error(c, who, "n_labels != sph_count");
     if (max_groups < 0) return arg_error(c, who, "max_groups < 0");
     if (table && max_groups == 0) return arg_error(c, who, "a table needs max_groups > 0");
-    if (!ready(c, SPH_F_RHO)) { c->err = "sph_groups: rho is stale (call sph_density)"; return SPH_ERR_STATE; }
+    if (!field_ready(*c, c->variable, SPH_F_RHO)) { c->err = "sph_groups: rho is stale (call sph_density)"; return SPH_ERR_STATE; }
     const bool link_h = (d->flags & SPH_GROUPS_LINK_H) != 0;
     if (link_h && !c->variable && !(c->p.h > 0.0 && std::isfinite(c->p.h))) {
         c->err = "sph_groups: SPH_GROUPS_LINK_H needs h > 0";

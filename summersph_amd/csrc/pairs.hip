@@ -344,11 +344,11 @@ int nlist_build(sph_ctx *c) {
         nl<<<dim3(pair_blocks(n)), dim3(PAIR_BLOCK), 0, c->stream>>>(
             c->grid, reinterpret_cast<const double4 *>(c->drec), c->cell_start, n, pc.rcut2, c->nl_cap, c->nlist,
             c->ncount, c->wave_max, c->wave_class, c->orig, (int32_t)c->n_owned, c->hv);
-        max_to_host<<<dim3(1), dim3(1024), 0, c->stream>>>(c->wave_class, (n + 63) / 64, reinterpret_cast<int32_t *>(c->h_pinned + 9));
+        max_to_host<<<dim3(1), dim3(1024), 0, c->stream>>>(c->wave_class, (n + 63) / 64, &c->pin->wave_max);
         SPH_HIP(hipGetLastError());
         SPH_HIP(hipStreamSynchronize(c->stream));
-        c->wave_class_valid = false;
-        const int32_t mx = *reinterpret_cast<int32_t *>(c->h_pinned + 9);
+        c->wave_classes_stale();
+        const int32_t mx = c->pin->wave_max;
         c->nl_max = mx;
         if (mx <= c->nl_cap) { c->nlist_builds++; return SPH_OK; }
         // grow: the list is sized for the densest wave; 288 GB of HBM make this cheap

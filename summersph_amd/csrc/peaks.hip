@@ -342,7 +342,7 @@ void merge_edges(const std::vector<int32_t> &ea, const std::vector<int32_t> &eb,
 }  // namespace
 
 int peaks_run(sph_ctx *c, const sph_peaks_desc *d, int32_t *labels, int64_t n_labels, double *table, int64_t max_groups,
-              int64_t *counts, bool host, bool (*ready)(const sph_ctx *, int)) {
+              int64_t *counts, bool host) {
     const char *who = "sph_peaks";
     if (!d) return arg_error(c, who, "null descriptor");
     if (!counts) return arg_error(c, who, "null counts pointer");
@@ -358,7 +358,7 @@ int peaks_run(sph_ctx *c, const sph_peaks_desc *d, int32_t *labels, int64_t n_la
     if (labels && n_labels != c->n) return arg_error(c, who, "n_labels != sph_count");
     if (max_groups < 0) return arg_error(c, who, "max_groups < 0");
     if (table && max_groups == 0) return arg_error(c, who, "a table needs max_groups > 0");
-    if (!ready(c, SPH_F_RHO)) { c->err = "sph_peaks: rho is stale (call sph_density)"; return SPH_ERR_STATE; }
+    if (!field_ready(*c, c->variable, SPH_F_RHO)) { c->err = "sph_peaks: rho is stale (call sph_density)"; return SPH_ERR_STATE; }
     const bool link_h = (d->flags & SPH_PEAKS_LINK_H) != 0;
     if (link_h && !c->variable && !(c->p.h > 0.0 && std::isfinite(c->p.h))) {
         c->err = "sph_peaks: SPH_PEAKS_LINK_H needs h > 0";

@@ -622,7 +622,7 @@ int render_density(sph_ctx *c, sph_render_desc *d, double *out, int64_t out_len,
 }
 
 int render_field(sph_ctx *c, sph_render_field_desc *d, const double *values, double *out, double *wout, int64_t out_len,
-                 bool host, bool (*ready)(const sph_ctx *, int)) {
+                 bool host) {
     const char *who = "sph_render_field";
     if (!d) return arg_error(c, who, "null descriptor");
     if (d->reserved != 0) return arg_error(c, who, "reserved must be 0");
@@ -639,7 +639,7 @@ int render_field(sph_ctx *c, sph_render_field_desc *d, const double *values, dou
     fs.rho = volume ? c->f[SPH_F_RHO] : nullptr;
     fs.normalise = d->normalise != 0;
     fs.wout = wout;
-    fs.stale = (d->field >= 0 && !ready(c, d->field)) || (volume && !ready(c, SPH_F_RHO));
+    fs.stale = (d->field >= 0 && !field_ready(*c, c->variable, d->field)) || (volume && !field_ready(*c, c->variable, SPH_F_RHO));
     return render_impl(c, &d->base, &fs, out, out_len, host);
 }
 

@@ -442,8 +442,7 @@ int sample_build(sph_ctx *c, const SampleSources &src, size_t extra_bytes, Sampl
 }
 
 int sample_run(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const double *px, const double *py, const double *pz,
-               const double *values, double *out, int64_t n_out, double *weight, int64_t *counts, bool host,
-               bool (*ready)(const sph_ctx *, int)) {
+               const double *values, double *out, int64_t n_out, double *weight, int64_t *counts, bool host) {
     const char *who = "sph_sample";
     if (!d) return arg_error(c, who, "null descriptor");
     if (d->reserved != 0) return arg_error(c, who, "reserved must be 0");
@@ -467,8 +466,8 @@ int sample_run(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const dou
     for (int a = 0; a < 3; a++)
         if (std::isnan(d->clip_lo[a]) || std::isnan(d->clip_hi[a])) return arg_error(c, who, "the clip box has a NaN");
     const bool volume = d->weight == SPH_RENDER_WEIGHT_VOLUME;
-    bool stale = volume && !ready(c, SPH_F_RHO);
-    for (int k = 0; k < nf; k++) stale = stale || (d->fields[k] >= 0 && !ready(c, d->fields[k]));
+    bool stale = volume && !field_ready(*c, c->variable, SPH_F_RHO);
+    for (int k = 0; k < nf; k++) stale = stale || (d->fields[k] >= 0 && !field_ready(*c, c->variable, d->fields[k]));
     if (stale) {
         c->err = "sph_sample: a field or rho is stale (sph_download_field would refuse it)";
         return SPH_ERR_STATE;

@@ -4,12 +4,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/summersph.h"
+#include "ctx_state.hpp"
 
 namespace sph {
 
@@ -82,14 +84,40 @@ struct TimingSlot {
     double total_ms = 0.0;
     int64_t launches = 0;
 };
-// potential and acceleration at arbitrary points (gravity_at.hip): host form (points / ph / out host memory, counts[2]
-// host) or device form (counts[2] device memory or null)
-int gravity_at_run(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_points, const double *px, const double *py,
-                   const double *pz, const double *ph, double *out, int64_t n_out, int64_t *counts, bool host);
+
+// The pinned host block of the build and step paths (c->pin, zeroed at creation): one member per use, so that no two uses
+// can share a word.  Every member is the target of an asynchronous copy, the source of one, or is written by a kernel
+// through its address (pinned memory is mapped into the device's address space); a report keeps the element layout of
+// the kernel that writes it.  (The analysis calls have their own 32 doubles, rnd_pinned.)
+struct DtWords { double dt, t, cand; };                      // the layout of d_dt
+struct HStats { double h_max, h_sum, growth, shrink; };      // h_stats_final
+struct BoxReport { double box[6]; int32_t nonfinite; };      // bbox_final: min xyz, max xyz, then the flag as an int at double 6
+struct ListReport { int32_t v[8]; };                         // plan_reduce_kernel: longest list, misfits, largest tile need (tiled.hip)
+struct AccWords { int32_t pos_last, keep_last, ns; };        // the packs: scan and mark of the last particle, sinks after the cull
+struct PinnedSlots {
+    int32_t wave_max;                              // max_to_host: the longest list of the untiled builds
+    DtWords dt_in, dt_out;                         // sph_set_dt's source, sph_get_dt's target
+    double dt_cand;                                // sph_dt_candidate
+    HStats h_stats;                                // varh_h_stats
+    double owned_box[6];                           // owned_bbox
+    int64_t sel_counts[MAX_SEL_BOXES];             // sph_select_boxes*
+    double bnd_boxes[6 * MAX_SEL_BOXES];           // sph_set_boundary_boxes' staging
+    BoxReport bbox[2];                             // the bounding-box reports of the last two builds (ring_bbox)
+    ListReport nl[2];                              // the list reports of the last two tiled builds (ring_nl)
+    double trim[7];                                // grid_rebuild's trim moments
+    AccWords acc;                                  // the accretion packs' read-back
+};
+static_assert(offsetof(BoxReport, nonfinite) == 6 * sizeof(double) && sizeof(BoxReport) % 8 == 0, "bbox_final's layout");
+static_assert(sizeof(DtWords) == 3 * sizeof(double) && sizeof(HStats) == 4 * sizeof(double), "copied as arrays of doubles");
+#define SPH_PIN_ALIGNED(m, a) static_assert(offsetof(PinnedSlots, m) % (a) == 0, #m " is misaligned for its writer")
+SPH_PIN_ALIGNED(wave_max, 4); SPH_PIN_ALIGNED(dt_in, 8); SPH_PIN_ALIGNED(dt_out, 8); SPH_PIN_ALIGNED(dt_cand, 8);
+SPH_PIN_ALIGNED(h_stats, 8); SPH_PIN_ALIGNED(owned_box, 8); SPH_PIN_ALIGNED(sel_counts, 8); SPH_PIN_ALIGNED(bnd_boxes, 8);
+SPH_PIN_ALIGNED(bbox, 8); SPH_PIN_ALIGNED(nl, 4); SPH_PIN_ALIGNED(trim, 8); SPH_PIN_ALIGNED(acc, 4);
+#undef SPH_PIN_ALIGNED
 
 }  // namespace sph
 
-struct sph_ctx {
+struct sph_ctx : sph::CtxState {
     sph_params p;
     int device = 0;
     int num_cus = 256;
@@ -111,7 +139,6 @@ struct sph_ctx {
     int64_t sel_stride = 0;                              // ids of box b start at sel_ids + b * sel_stride (n_owned at select time)
     // split force evaluation (sph_forces_part): waves near the other GPUs' boxes wait for the ghost fields
     int32_t *wave_class = nullptr; double *bnd_boxes = nullptr; int32_t n_bnd_boxes = 0;
-    bool wave_class_valid = false, interior_done = false;
     bool own_stream = true;                              // false: the caller's stream (sph_set_stream), *_dev calls do not synchronise
 
     // cell-sorted struct-of-arrays state + derived + rates (SPH_F_* order)
@@ -119,7 +146,6 @@ struct sph_ctx {
     double *f_alt[10] = {};          // ping-pong targets for the state fields on reorder (9, +h when variable)
     int32_t *orig = nullptr, *orig_alt = nullptr;   // sorted slot -> original index
     int32_t *inv = nullptr;                         // original index -> sorted slot
-    bool inv_valid = true;           // false: the last reorder left inv alone (one rank, no ghosts); ensure_inv rebuilds it from orig
     double *scratch = nullptr;       // n doubles (un-permute on download)
 
     // gather records (array-of-structs: one particle = one or few cache lines)
@@ -143,19 +169,13 @@ struct sph_ctx {
     double *cell_hmax = nullptr;     // per cell: largest h of its particles
     double *h_new = nullptr;         // scratch for calc_smoothing
     double *leaf_half = nullptr;     // half edge of every slot's leaf cell (reach = 2 h + this)
-    bool path_keys_valid = false;    // mkeys_alt / mvals_alt hold the sorted octree path keys of the current grid build (root box: c->bbox)
-    bool h_refresh_ok = false;       // the only thing newer than the grid is h (sph_update_h / an upload of h)
-    bool h_new_is_build = false;     // h_new holds the lengths the list in place was built with (set by sph_update_h's swap; an
-                                     // upload / scatter of h, a new particle set or a reallocation clears it: no re-flag then)
-    bool leaf_valid = false;         // leaf cells match the current sorted order and (external) octree
     double h_max_glob = 0.0, h_mean = 0.0;
     double root_box[4] = {0, 0, 0, 0};   // octree root centre + edge ([V]:1007-1012)
 
     // Barnes-Hut gas self-gravity (gravity.hip): binary radix tree over the octree path keys
     bool gravity = false;
-    bool tree_valid = false;
     double *g_cache[3] = {nullptr, nullptr, nullptr};   // SPH_FLAG_REUSE_GRAVITY: the self-gravity term of the last walk (sorted order)
-    bool grav_valid = false;                            // ... still that of the current positions, masses, h, tree and sorted order
+                                                        // (grav_valid: still that of the current positions, masses, h, tree and order)
     int32_t *g_left = nullptr, *g_right = nullptr, *g_parent = nullptr, *g_leaf_parent = nullptr, *g_prefix = nullptr;
     int32_t *g_flag = nullptr, *g_slot = nullptr, *g_lvl = nullptr, *g_rope = nullptr, *g_leaf_rope = nullptr;
     double *g_sum = nullptr, *g_leafA = nullptr;     // 4 doubles per node / leaf
@@ -166,12 +186,10 @@ struct sph_ctx {
     double *grav_tab = nullptr;                      // softening table, [F]:81-101
     uint64_t *g_keys = nullptr, *g_keys_alt = nullptr; uint32_t *g_vals = nullptr, *g_vals_alt = nullptr;
     void *g_sort_tmp = nullptr; size_t g_sort_tmp_bytes = 0;
-    bool acc_marked = false, acc_any_mass = false;  // multi-GPU accretion: between sph_accrete_mark_dev and _apply_dev
     int64_t g_cap = 0;                               // leaves the tree arrays hold
     // external gravity sources (multi-GPU: the particles of every GPU), caller-owned {x,y,z,m} records + their bounding box
     const double *gx_src = nullptr; int64_t gx_n = 0; double gx_box[6] = {0, 0, 0, 0, 0, 0};
-    bool gx_keys_valid = false;                      // g_keys_alt / g_vals_alt hold the sorted path keys of gx_src
-    int32_t *number = nullptr; bool numbers_set = false;   // variable h: the reference's particle numbers by original id
+    int32_t *number = nullptr;                       // variable h: the reference's particle numbers by original id (numbers_set)
 
     // grid
     sph::GridDesc grid{};
@@ -182,22 +200,19 @@ struct sph_ctx {
     int32_t *cell_fill = nullptr;    // counting sort of the grid build: per-cell cursor (inside the cell_start allocation, behind the table)
     double *bbox_part = nullptr;     // per-block partial min/max
     // fixed-h steps (sph_run / sph_step): the opening kick + drift also wrote the cell keys, the histogram and the box
-    // partials of the new positions for the grid grid_early (grid.hip: grid_prepare_early); the next grid build takes them
-    bool keys_early = false;
+    // partials of the new positions for the grid grid_early (grid.hip: grid_prepare_early; keys_early); the next grid build takes them
     sph::GridDesc grid_early{};
     int early_blocks = 0;            // ... and the number of box partials it left behind the classic ones in bbox_part
-    double *h_pinned = nullptr;      // pinned host scratch (bbox[6], flags, dt, ...)
+    sph::PinnedSlots *pin = nullptr; // pinned host memory: staging and read-back slots of the build and step paths
     int32_t *d_flags = nullptr;      // [0] nonfinite, [1] nlist max count
     // Read-backs one build stale (no host wait on the step that is being enqueued): the fixed-h path sizes its grid from
     // the bounding box of the PREVIOUS build plus one cell (a particle outside the box is clamped into a boundary cell and
     // still finds every neighbour: the box is a matter of speed, not of correctness) and checks the list overflow of the
-    // previous build.  Two pinned slots and two events each, used alternately.
+    // previous build.  Two pinned slots (pin->bbox, pin->nl) and two events each, used alternately; ring_*_valid: the other
+    // slot holds the previous build's report.  A reported overflow (nl_overflowed) means the state may carry a kick from
+    // truncated sums: every evaluation is refused until sph_upload.
     hipEvent_t ev_bbox[2] = {nullptr, nullptr}, ev_nl[2] = {nullptr, nullptr};
     int ring_bbox = 0, ring_nl = 0;
-    bool ring_bbox_valid = false, ring_nl_valid = false;
-    // a list overflow was reported: the state may carry a kick from truncated sums.  Every evaluation is refused until sph_upload
-    bool nl_overflowed = false;
-    bool bbox_exact = true;          // c->bbox is the exact box of the last build (not the previous one widened)
     bool no_stale = false;           // SPH_SYNC_EVERY_BUILD: wait for every read-back (A/B switch)
     int64_t host_syncs = 0;          // stream synchronisations inside the build path (statistics)
     // hashed cell table (grid.hip): used instead of cell_start when the current grid is hashed
@@ -223,7 +238,6 @@ struct sph_ctx {
     int32_t *ntail = nullptr;        // variable h: entries of the margin shell, stored from the end of the lane's column
     // variable h, re-flag pass (varh.hip): the growth of h the list in place was built to survive, the growth measured
     double vl_grow = 1.0, h_growth = 0.0, h_shrink = 0.0;    // h_shrink: largest h_build / h_now
-    bool list_has_margin = false;    // the list in place carries the margin shell calc_smoothing reads
     int64_t nlist_reflags = 0;
     int32_t nl_max = 0; double nl_mean = 0.0;
 
@@ -242,12 +256,7 @@ struct sph_ctx {
     double *d_dt = nullptr;
     double *dt_part = nullptr; int32_t dt_blocks = 0;
 
-    bool order_valid = false;    // sorted order, drec, bbox, orig/inv match the current positions
-    bool grid_valid = false;     // sorted order + cell table + neighbour list match positions
-    bool rho_valid = false;      // rho matches positions and masses
-    bool eos_valid = false;      // P, c, frec match rho, u, alpha, v
-    bool rates_valid = false;
-    bool derived_kept = false;   // after an accretion / cull: rho .. dalpha of the survivors, compacted with the state (downloads only)
+    // (what is valid and what is pending: the flags of sph::CtxState, ctx_state.hpp)
 
     // statistics and timing
     int64_t grid_builds = 0, nlist_builds = 0, density_passes = 0, force_passes = 0;
@@ -412,9 +421,9 @@ hipError_t launch_update_h(sph_ctx *c, const PairConst &pc);   // leaves the loc
 PairConst make_pair_const(const sph_ctx *c);
 // density rendering (render.hip): out is host memory (host_out) or device memory; two read-backs (+ the host copy)
 int render_density(sph_ctx *c, sph_render_desc *d, double *out, int64_t out_len, bool host_out);
-// field rendering (render.hip): host (values, out and wout host memory) or device form; ready = sph_download_field's rule
+// field rendering (render.hip): host (values, out and wout host memory) or device form
 int render_field(sph_ctx *c, sph_render_field_desc *d, const double *values, double *out, double *wout, int64_t out_len,
-                 bool host, bool (*ready)(const sph_ctx *, int));
+                 bool host);
 void render_free(sph_ctx *c);
 // what the analysis calls share (render.hip; freed by render_free): their scratch, which grows and never shrinks, and the
 // 32 pinned doubles of their read-backs, allocated at the first call that needs them
@@ -430,9 +439,9 @@ int energy_sums(sph_ctx *c, int64_t src_offset, double *sums, double *phi, int64
 int stage_blocks(int64_t n_owned);
 int stage_sources(sph_ctx *c, double *rec, double *box_part, double bb[6]);
 // friends-of-friends groups (groups.hip): host form (labels / table / count host memory, one synchronisation) or device
-// form; ready = sph_download_field's rule
+// form
 int groups_run(sph_ctx *c, const sph_groups_desc *d, int32_t *labels, int64_t n_labels, double *table, int64_t max_groups,
-               int64_t *n_groups, bool host, bool (*ready)(const sph_ctx *, int));
+               int64_t *n_groups, bool host);
 // sph_groups' front end (selection, box, cell keys, sort, records and hashed cell table) and its tail (members per root,
 // numbering, member sort, labels, the two table reductions) as host functions, shared with sph_peaks (peaks.hip), which
 // puts its own partition between them.  Between the two, parent[id] is the root of every selected owned id (a root is
@@ -471,24 +480,23 @@ int groups_front(sph_ctx *c, const GroupsSel &s, GroupsWork &w);
 // d_table: w.rows rows of SPH_GROUPS_NCOL doubles (device memory) or null with w.rows == 0; d_labels: c->n int32 or null
 int groups_tail(sph_ctx *c, GroupsWork &w, int64_t min_members, int32_t *d_labels, double *d_table);
 // density-peak clumps (peaks.hip): host form (labels / table / counts[3] host memory) or device form; both wait for the
-// stream (the merge runs on the host); ready = sph_download_field's rule
+// stream (the merge runs on the host)
 int peaks_run(sph_ctx *c, const sph_peaks_desc *d, int32_t *labels, int64_t n_labels, double *table, int64_t max_groups,
-              int64_t *counts, bool host, bool (*ready)(const sph_ctx *, int));
+              int64_t *counts, bool host);
 // SPH gradients (gradients.hip): host form (values / out / rho host memory, counts[2] host, one synchronisation) or device
-// form (counts[2] device memory or null); ready = sph_download_field's rule
+// form (counts[2] device memory or null)
 int gradients_run(sph_ctx *c, const sph_gradients_desc *d, const double *values, double *out, int64_t n_out, double *rho_out,
-                  int64_t *counts, bool host, bool (*ready)(const sph_ctx *, int));
+                  int64_t *counts, bool host);
 // SPH interpolation at arbitrary points (sample.hip): host form (points / values / out / weight host memory, counts[2] host,
-// one synchronisation) or device form (counts[2] device memory or null); ready = sph_download_field's rule
+// one synchronisation) or device form (counts[2] device memory or null)
 int sample_run(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const double *px, const double *py, const double *pz,
-               const double *values, double *out, int64_t n_out, double *weight, int64_t *counts, bool host,
-               bool (*ready)(const sph_ctx *, int));
+               const double *values, double *out, int64_t n_out, double *weight, int64_t *counts, bool host);
 // field lines of an SPH-interpolated vector field (trace.hip, over sample.hip's structure: sample_common.hpp): host form
 // (seeds / values / path / carry / status / n_done host memory, counts[5] host, one synchronisation) or device form
-// (counts[5] device memory or null); ready = sph_download_field's rule
+// (counts[5] device memory or null)
 int trace_run(sph_ctx *c, const sph_trace_desc *d, int64_t n_seeds, const double *sx, const double *sy, const double *sz,
               const double *values, double *path, int64_t n_path, double *carry_out, int32_t *status, int32_t *n_done,
-              int64_t *counts, bool host, bool (*ready)(const sph_ctx *, int));
+              int64_t *counts, bool host);
 // potential and acceleration at arbitrary points (gravity_at.hip): host form (points / ph / out host memory, counts[2]
 // host) or device form (counts[2] device memory or null)
 int gravity_at_run(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_points, const double *px, const double *py,
@@ -498,14 +506,13 @@ int gravity_at_run(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_points, c
 int bound_run(sph_ctx *c, const sph_bound_desc *d, const int32_t *labels, int64_t n_labels, int64_t n_groups,
               int32_t *bound_labels, double *out, int64_t n_out, double *table, int64_t *counts, bool host);
 // position-position-velocity cubes (cube.hip): host form (values / out host memory, two read-backs + the copy out) or device
-// form; ready = sph_download_field's rule
-int cube_run(sph_ctx *c, const sph_cube_desc *d, const double *values, double *out, int64_t out_len, bool host,
-             bool (*ready)(const sph_ctx *, int));
+// form
+int cube_run(sph_ctx *c, const sph_cube_desc *d, const double *values, double *out, int64_t out_len, bool host);
 // the rates of sph_forces split by term (terms.hip): host form (out host memory, one synchronisation) or device form
 int force_terms_run(sph_ctx *c, const sph_force_terms_desc *d, double *out, int64_t n_out, bool host);
 // binned sums (binned.hip): host form (values / sums / counts[3] host memory, one read-back) or device form (counts[3] device
-// memory or null); edges is host memory in both; ready = sph_download_field's rule
+// memory or null); edges is host memory in both
 int binned_run(sph_ctx *c, const sph_binned_desc *d, const double *values, const double *edges, double *sums, int64_t n_sums,
-               int64_t *counts, bool host, bool (*ready)(const sph_ctx *, int));
+               int64_t *counts, bool host);
 
 }  // namespace sph

@@ -783,10 +783,10 @@ int nlist_build_tiled(sph_ctx *c) {
     // tiled path when a group's intervals reach HALF of what an entry can address.
     const bool trusted = c->ring_nl_valid && !c->no_stale;
     const int p = c->ring_nl;
-    int32_t *slot = reinterpret_cast<int32_t *>(c->h_pinned + 240 + 8 * p);
+    int32_t *slot = c->pin->nl[p].v;
     if (trusted) {
         SPH_HIP(hipEventSynchronize(c->ev_nl[1 - p]));
-        const int32_t *prev = reinterpret_cast<const int32_t *>(c->h_pinned + 240 + 8 * (1 - p));
+        const int32_t *prev = c->pin->nl[1 - p].v;
         // either way the context refuses every evaluation from here on (nl_overflowed, do_density)
         if (prev[0] > c->nl_cap) { c->nl_overflowed = true; c->err = "neighbour list overflowed in the previous build (lists grew by more than a third within one step)"; return SPH_ERR_STATE; }
         if (prev[3] >= LIST16_MAX_NEED) { c->nl_overflowed = true; c->err = "neighbour list: a group's candidate intervals outgrew the 16-bit entries within one step"; return SPH_ERR_STATE; }

@@ -192,7 +192,7 @@ bool field_id_ok(int32_t f) { return f == SPH_TRACE_VALUES || (f >= 0 && f < SPH
 
 int trace_run(sph_ctx *c, const sph_trace_desc *d, int64_t n_seeds, const double *sx, const double *sy, const double *sz,
               const double *values, double *path, int64_t n_path, double *carry_out, int32_t *status, int32_t *n_done,
-              int64_t *counts, bool host, bool (*ready)(const sph_ctx *, int)) {
+              int64_t *counts, bool host) {
     const char *who = "sph_trace";
     if (!d) return arg_error(c, who, "null descriptor");
     if (d->reserved[0] != 0 || d->reserved[1] != 0) return arg_error(c, who, "reserved must be 0");
@@ -232,8 +232,8 @@ int trace_run(sph_ctx *c, const sph_trace_desc *d, int64_t n_seeds, const double
     const bool volume = d->weight == SPH_RENDER_WEIGHT_VOLUME;
     const int nf = carry ? 4 : 3;
     const int32_t fields[4] = {d->fields[0], d->fields[1], d->fields[2], carry ? d->carry : 0};
-    bool stale = volume && !ready(c, SPH_F_RHO);
-    for (int k = 0; k < nf; k++) stale = stale || (fields[k] >= 0 && !ready(c, fields[k]));
+    bool stale = volume && !field_ready(*c, c->variable, SPH_F_RHO);
+    for (int k = 0; k < nf; k++) stale = stale || (fields[k] >= 0 && !field_ready(*c, c->variable, fields[k]));
     if (stale) {
         c->err = "sph_trace: a field or rho is stale (sph_download_field would refuse it)";
         return SPH_ERR_STATE;

@@ -1111,12 +1111,13 @@ int varh_h_stats(sph_ctx *c, bool with_growth) {
     h_stats_partial<<<dim3(nb), dim3(VBLOCK), 0, c->stream>>>(c->f[SPH_F_H], with_growth ? c->h_new : nullptr, n, part);
     h_stats_final<<<dim3(1), dim3(64), 0, c->stream>>>(part, nb, part + 2048);
     SPH_HIP(hipGetLastError());
-    SPH_HIP(hipMemcpyAsync(c->h_pinned + 28, part + 2048, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    const HStats &hs = c->pin->h_stats;
+    SPH_HIP(hipMemcpyAsync(&c->pin->h_stats, part + 2048, sizeof(HStats), hipMemcpyDeviceToHost, c->stream));
     SPH_HIP(hipStreamSynchronize(c->stream));
-    c->h_max_glob = c->h_pinned[28];
-    c->h_mean = c->h_pinned[29] / (double)n;
+    c->h_max_glob = hs.h_max;
+    c->h_mean = hs.h_sum / (double)n;
     c->h_shrink = INFINITY;
-    if (with_growth) { c->h_growth = c->h_pinned[30]; c->h_shrink = c->h_pinned[31]; }
+    if (with_growth) { c->h_growth = hs.growth; c->h_shrink = hs.shrink; }
     if (!(c->h_max_glob > 0.0) || !std::isfinite(c->h_max_glob)) { c->err = "variable h: non-positive or non-finite smoothing length"; return SPH_ERR_ARG; }
     return SPH_OK;
 }
@@ -1198,10 +1199,10 @@ int varh_nlist_build(sph_ctx *c) {
             c->grid, R, c->h_max_glob, grow * grow, reinterpret_cast<const double4 *>(c->prec), reinterpret_cast<const double4 *>(c->lrec), c->orig,
             c->cell_start, c->hv, c->cell_hmax, n, (int32_t)c->n_owned, c->nl_cap, c->nlist, c->ncount, c->ntail, c->wave_max, c->wave_class,
             c->numbers_set ? c->number : nullptr);
-        max_to_host<<<dim3(1), dim3(1024), 0, c->stream>>>(c->wave_class, (n + 63) / 64, reinterpret_cast<int32_t *>(c->h_pinned + 9));
+        max_to_host<<<dim3(1), dim3(1024), 0, c->stream>>>(c->wave_class, (n + 63) / 64, &c->pin->wave_max);
         SPH_HIP(hipGetLastError());
         SPH_HIP(hipStreamSynchronize(c->stream));
-        const int32_t mx = *reinterpret_cast<int32_t *>(c->h_pinned + 9);
+        const int32_t mx = c->pin->wave_max;
         c->nl_max = mx;
         if (mx <= c->nl_cap) {
             c->nlist_builds++;
@@ -1232,7 +1233,7 @@ int varh_nlist_reflag(sph_ctx *c) {
         reinterpret_cast<const double4 *>(c->prec), reinterpret_cast<const double4 *>(c->lrec), c->orig, n, (int32_t)c->n_owned, c->nl_cap,
         c->nlist, c->ncount, c->ntail, c->wave_max, c->numbers_set ? c->number : nullptr);
     SPH_HIP(hipGetLastError());
-    c->list_has_margin = false;        // the margin rows may be overwritten: calc_smoothing falls back to its cell walk on this list
+    c->list_reflagged();               // the margin rows may be overwritten: calc_smoothing falls back to its cell walk on this list
     c->nlist_reflags++;
     return SPH_OK;
 }
@@ -1248,7 +1249,7 @@ int varh_reflag_density(sph_ctx *c, const PairConst &pc) {
         c->numbers_set ? c->number : nullptr, c->w_tab, c->dw_tab, c->f[SPH_F_U], c->f[SPH_F_ALPHA], c->f[SPH_F_VX], c->f[SPH_F_VY],
         c->f[SPH_F_VZ], c->f[SPH_F_RHO], c->f[SPH_F_OMEGA], c->f[SPH_F_P], c->f[SPH_F_C], c->frec);
     SPH_HIP(hipGetLastError());
-    c->list_has_margin = false;
+    c->list_reflagged();
     c->nlist_reflags++;
     return SPH_OK;
 }
