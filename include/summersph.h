@@ -381,6 +381,9 @@ int sph_set_sink_accel(sph_ctx *ctx, int32_t ns, const double *sax, const double
  *               column sums along that axis, the two other axes in order.  A column sum adds the 3-D mode's node values
  *               in increasing node index (bitwise the sequential sum of the 3-D output).  SPH_RENDER_SPACING multiplies
  *               the sums by that axis's node spacing (hi - lo) / (n - 1): a column density
+ *   flat axes   lo[a] == hi[a] with n[a] > 1 (SPH_RENDER_AUTO_BOUNDS over a coplanar selection gives it) is valid: the n[a]
+ *               nodes of that axis coincide, the 3-D output repeats one plane, a column sum along the axis adds it n[a]
+ *               times, and the node spacing is 0: with SPH_RENDER_SPACING that column image is all zeros
  *   order       every node adds its terms in the (cell, particle id) order of the render's own binning, which depends
  *               only on the node box, n, h and the clip: results are bitwise reproducible, independent of the context's
  *               sorted order and of axis / flags
