@@ -1075,6 +1075,74 @@ typedef struct sph_cube_desc {
 int sph_cube(sph_ctx *ctx, const sph_cube_desc *d, const double *values, double *host_out, int64_t out_len);
 int sph_cube_dev(sph_ctx *ctx, const sph_cube_desc *d, const double *d_values, double *d_out, int64_t out_len);
 
+/* ---- emission-absorption images: what an observer sees of the owned gas when it is not optically thin -- intensity,
+ *      optical depth, transmission and the depth of the tau = tau_surface surface (summersph_amd/transfer.py) -----------
+ * Frame, Select, Nodes  exactly sph_cube's: rot[9] with rows u^, v^, w^ (orthonormal and right-handed within 1e-12, else
+ *          SPH_ERR_ARG), w^ pointing away from the observer; P_j = rot (r_j - centre), every row evaluated as
+ *          ((a0 dx + a1 dy) + a2 dz) with no fused multiply-adds; the owned gas particles with clip_lo < r < clip_hi on
+ *          every axis of the SIMULATION frame (strict); h > 0: one h for every particle, 0: each particle's own; node i on
+ *          image axis a is lo[a] + i (hi[a] - lo[a]) / (n - 1), the last one exactly hi[a] (np.linspace), n == 1: the
+ *          single node lo[a].  The depth of a particle is D_j = P_j,w.
+ * Inputs   the opacity kappa_j = kappa_scale K_j and the source function S_j.  K and S each come from the place their
+ *          selector (kappa, source) names: an SPH_F_* field of the context (SPH_ERR_STATE exactly where sph_download_field
+ *          would refuse it as stale), SPH_TRANSFER_VALUES (the caller's array of sph_count doubles in sph_download_field's
+ *          order; host memory for sph_transfer, device memory for _dev) or SPH_TRANSFER_ONE (the constant 1).  A pointer
+ *          must be non-NULL exactly when its selector is SPH_TRANSFER_VALUES.  A selected K_j that is negative or
+ *          non-finite, or a selected non-finite S_j, gives SPH_ERR_ARG (found in the statistics pass, before anything is
+ *          written).  S_j may have either sign.
+ * Slab     for node g, b = |g - P_j,uv| and p = b / h_j: dtau_j = y0_j F(p), y0_j = m_j kappa_j / (pi h_j^2), pi in double
+ *          precision, F the line-integrated spline of sph_cube ("Footprint" above): F(0) = 1.5, F = 0 for p >= 2.
+ * Order    the selected particles are taken in ascending (D_j, id), nearest the observer first; equal depths are ordered by
+ *          id (a flat sheet seen face-on); the order is total over the doubles, -0.0 and +0.0 compare equal and fall to
+ *          the id.
+ * Compositing  per node start with tau = 0, T = 1, I = 0, surf = NaN and the node running.  For each particle in order
+ *          while the node runs, a particle with p >= 2 being skipped, with no fused multiply-adds:
+ *            a = -expm1(-dtau)
+ *            I <- I + (S_j T) a
+ *            T <- T - T a
+ *            tau <- tau + dtau
+ *            if surf is NaN and tau >= tau_surface: surf <- D_j
+ *            if tau >= tau_max: the node stops (deeper particles add nothing)
+ *          tau_max = +INFINITY never stops a node.  The stop is part of the definition, as the 8.5 sigma truncation is of
+ *          sph_cube's; it is what lets the pass leave an opaque tile early.
+ * Output   four planes of n_u n_v doubles in C order [plane][iu][iv], out_len == 4 n_u n_v: 0: I + T background; 1: tau
+ *          as accumulated until the node stopped; 2: T; 3: surf, NaN where tau never reached tau_surface.  sph_transfer
+ *          copies them to host memory; sph_transfer_dev leaves them in device memory, ordered on the context's stream.
+ * Reproducibility  the result depends only on the descriptor, the selected particles and their ids: a repeated call, the
+ *          host and the device form, and the same state in a context with another sorted order are bitwise equal.
+ * Cost     two stream synchronisations (selection statistics, list sizes) + the copies of the host form.  Every particle
+ *          is entered into the list of each tile of 8 x 8 nodes that holds a node within 2 h_j (1 + 1e-6) of P_j,uv on both
+ *          axes; the lists hold sum_j (tiles touched) entries of 8 bytes (twice, for the sort).  SPH_ERR_NOMEM when the
+ *          scratch does not fit or that count reaches 2^31: the bad case is a large fixed h over a tiny image extent, where
+ *          every particle touches every tile.  No state, statistic (other than device_bytes: the analysis scratch) or flag
+ *          of the context changes.  One context: compositing across contexts is only valid for depth-disjoint sets.
+ * SPH_ERR_ARG: null descriptor or output, n_u or n_v < 1, out_len != 4 n_u n_v, lo > hi or non-finite, h < 0 or
+ * non-finite, a NaN clip, a non-finite centre, kappa_scale < 0 or non-finite, tau_surface <= 0 or NaN, tau_max <= 0 or NaN,
+ * a non-finite background, a bad rot, a selector that is neither a field id nor SPH_TRANSFER_VALUES / _ONE, a pointer given
+ * without SPH_TRANSFER_VALUES or missing with it, flags != 0, reserved != 0, a bad selected K or S (above).  SPH_ERR_STATE:
+ * a stale field named by source or kappa; a selected h <= 0 or non-finite.  SPH_ERR_NOMEM: see Cost. */
+#define SPH_TRANSFER_VALUES (-1)    /* K or S from the caller's array */
+#define SPH_TRANSFER_ONE (-2)       /* K or S = 1                     */
+typedef struct sph_transfer_desc {
+    double  rot[9];                 /* rows u^, v^, w^ (row-major)                                   */
+    double  centre[3];              /* origin of the image plane                                     */
+    double  lo[2], hi[2];           /* node box on the image axes u, v                               */
+    double  clip_lo[3], clip_hi[3]; /* strict particle clip box (simulation axes); -/+INFINITY = none */
+    double  h;                      /* > 0: one h for all; 0: each particle's own h                  */
+    double  kappa_scale;            /* kappa_j = kappa_scale K_j; >= 0, finite                       */
+    double  tau_surface;            /* plane 3 is the depth at which tau reaches it; > 0             */
+    double  tau_max;                /* a node stops at tau >= tau_max; > 0, may be +INFINITY         */
+    double  background;             /* intensity behind the gas; finite                              */
+    int32_t n_u, n_v;               /* image nodes per axis, each >= 1                               */
+    int32_t source, kappa;          /* where S and K come from: SPH_F_*, SPH_TRANSFER_VALUES, _ONE   */
+    int32_t flags;                  /* must be 0                                                     */
+    int32_t reserved;               /* must be 0                                                     */
+} sph_transfer_desc;                /* 240 bytes */
+int sph_transfer(sph_ctx *ctx, const sph_transfer_desc *d, const double *source, const double *kappa, double *host_out,
+                 int64_t out_len);
+int sph_transfer_dev(sph_ctx *ctx, const sph_transfer_desc *d, const double *d_source, const double *d_kappa, double *d_out,
+                     int64_t out_len);
+
 /* ---- the rates of sph_forces split by physical term: which term moves angular momentum at a radius (torque by term per
  *      ring), where the artificial viscosity heats the gas (a shock-heating map through sph_render_field), how large the
  *      numerical dissipation is beside the PdV work ----------------------------------------------------------------------

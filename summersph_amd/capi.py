@@ -53,6 +53,7 @@ SYMBOLS = [
     "sph_gravity_at", "sph_gravity_at_dev",
     "sph_bound", "sph_bound_dev",
     "sph_cube", "sph_cube_dev",
+    "sph_transfer", "sph_transfer_dev",
     "sph_force_terms", "sph_force_terms_dev",
     "sph_binned", "sph_binned_dev", "sph_binned_edges",
 ]
@@ -105,6 +106,10 @@ GRAVAT_SPLIT = 4
 GRAVAT_REF_SOFT2 = 0.001 * 2.5      # the force walk's softening term (0.001_dp * smoothing)
 CUBE_PER_VELOCITY = 1
 CUBE_CHUNK = 32               # channels per workgroup of cube_gather (csrc/cube.hip, CUBE_CHUNK): more run in several chunks
+TRANSFER_VALUES = -1
+TRANSFER_ONE = -2
+# sph_transfer's planes (include/summersph.h, "Output")
+TRANSFER_PLANES = ["intensity", "tau", "transmission", "surface"]
 TERMS_NROW = 16
 TERMS_SKIP_GAS_GRAVITY = 1
 # sph_force_terms' rows (include/summersph.h, "Rows"): pressure gradient, artificial viscosity, sink gravity, gas
@@ -463,6 +468,47 @@ def cube_desc(shape, bounds, v0, dv, n_chan, rot=None, centre=(0.0, 0.0, 0.0), v
     return d
 
 
+class TransferDesc(C.Structure):
+    """sph_transfer_desc (include/summersph.h): rot (rows u^, v^, w^), centre, image node box, strict clip box, h, kappa_scale,
+    tau_surface, tau_max, background, image nodes, the selectors of S and K (a field id, TRANSFER_VALUES, TRANSFER_ONE),
+    flags, reserved"""
+    _fields_ = [("rot", C.c_double * 9), ("centre", C.c_double * 3), ("lo", C.c_double * 2), ("hi", C.c_double * 2),
+                ("clip_lo", C.c_double * 3), ("clip_hi", C.c_double * 3), ("h", C.c_double), ("kappa_scale", C.c_double),
+                ("tau_surface", C.c_double), ("tau_max", C.c_double), ("background", C.c_double), ("n_u", C.c_int32),
+                ("n_v", C.c_int32), ("source", C.c_int32), ("kappa", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+def _transfer_selector(v) -> int:
+    """None: the constant 1; a field name or id; anything else: the caller's array"""
+    if v is None:
+        return TRANSFER_ONE
+    if isinstance(v, str):
+        return FIELDS.index(v)
+    if isinstance(v, (int, np.integer)):
+        return int(v)
+    return TRANSFER_VALUES
+
+
+def transfer_desc(shape, bounds, rot=None, centre=(0.0, 0.0, 0.0), source="u", kappa=None, kappa_scale=1.0, tau_surface=1.0,
+                  tau_max=np.inf, background=0.0, h=None, clip=None) -> TransferDesc:
+    """The descriptor of Context.transfer's arguments (see there); source and kappa arrays only set their selectors."""
+    n = (int(shape),) * 2 if np.isscalar(shape) else tuple(int(v) for v in shape)
+    if len(n) != 2:
+        raise ValueError("shape: one node count or (n_u, n_v)")
+    d = TransferDesc()
+    d.rot[:] = np.asarray(np.eye(3) if rot is None else rot, dtype=np.float64).reshape(9).tolist()
+    d.centre[:] = [float(v) for v in centre]
+    b = np.asarray(bounds, dtype=np.float64).reshape(2, 2)
+    d.lo[:] = b[0].tolist(); d.hi[:] = b[1].tolist()
+    cb = np.array([[-np.inf] * 3, [np.inf] * 3]) if clip is None else np.asarray(clip, dtype=np.float64).reshape(2, 3)
+    d.clip_lo[:] = cb[0].tolist(); d.clip_hi[:] = cb[1].tolist()
+    d.h = 0.0 if h is None else float(h)
+    d.kappa_scale, d.tau_surface, d.tau_max, d.background = float(kappa_scale), float(tau_surface), float(tau_max), float(background)
+    d.n_u, d.n_v = n
+    d.source, d.kappa = _transfer_selector(source), _transfer_selector(kappa)
+    return d
+
+
 def bound_table(table: np.ndarray) -> np.ndarray:
     """(n, BOUND_NCOL) float64 -> a structured array of n records with the BOUND_COLUMNS names"""
     t = np.ascontiguousarray(table, dtype=np.float64).reshape(-1, BOUND_NCOL)
@@ -672,6 +718,8 @@ def load():
                        C.c_void_p, C.c_void_p]
     for fn in (lib.sph_cube, lib.sph_cube_dev):
         fn.argtypes = [C.c_void_p, C.POINTER(CubeDesc), C.c_void_p, C.c_void_p, C.c_int64]
+    for fn in (lib.sph_transfer, lib.sph_transfer_dev):
+        fn.argtypes = [C.c_void_p, C.POINTER(TransferDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     for fn in (lib.sph_force_terms, lib.sph_force_terms_dev):
         fn.argtypes = [C.c_void_p, C.POINTER(ForceTermsDesc), C.c_void_p, C.c_int64]
     for fn in (lib.sph_binned, lib.sph_binned_dev):
@@ -1395,6 +1443,27 @@ class Context:
         v = None if values is None else _values_one("cube", values, self.n, f)
         out = f.empty([max(k, 0) for k in oshape])
         f.call("sph_cube", C.byref(d), f.ptr(v), f.ptr(out), size)
+        return out
+
+    # ---- emission-absorption images (sph_transfer) -------------------------------------------------
+    def transfer(self, shape, bounds, rot=None, centre=(0.0, 0.0, 0.0), source="u", kappa=None, kappa_scale=1.0, tau_surface=1.0,
+                 tau_max=np.inf, background=0.0, h=None, clip=None, device=False):
+        """The emission-absorption image of the owned gas (include/summersph.h, sph_transfer), shape (4, n_u, n_v): the planes
+        TRANSFER_PLANES -- I + T background, the optical depth, the transmission T and the depth of the tau = tau_surface
+        surface (NaN where tau never reaches it).  shape, bounds, rot, centre, h, clip: as cube.  source (S_j) and kappa (K_j,
+        the opacity is kappa_scale K_j): a field name or id, None (the constant 1) or sph_count() numbers in the upload
+        order -- float64 numpy (device=False) or a contiguous float64 torch tensor on the context's GPU (device=True).  The
+        particles are composited front to back; a node stops at tau >= tau_max.  Returns float64 numpy or, device=True, a
+        torch tensor (sph_transfer_dev).  The descriptor used is left in self.transfer_desc."""
+        d = self.transfer_desc = transfer_desc(shape, bounds, rot, centre, source, kappa, kappa_scale, tau_surface, tau_max,
+                                               background, h, clip)
+        oshape = (4, d.n_u, d.n_v)
+        size = int(np.prod(oshape, dtype=np.int64)) if min(oshape) > 0 else 0
+        f = self._form(device)
+        sv = _values_one("transfer", source, self.n, f) if d.source == TRANSFER_VALUES else None
+        kv = _values_one("transfer", kappa, self.n, f) if d.kappa == TRANSFER_VALUES else None
+        out = f.empty([max(k, 0) for k in oshape])
+        f.call("sph_transfer", C.byref(d), f.ptr(sv), f.ptr(kv), f.ptr(out), size)
         return out
 
     # ---- the rates split by physical term (sph_force_terms) -----------------------------------------

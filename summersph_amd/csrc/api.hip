@@ -1327,6 +1327,20 @@ int sph_cube_dev(sph_ctx *c, const sph_cube_desc *d, const double *d_values, dou
     return cube_run(c, d, d_values, d_out, out_len, false);
 }
 
+int sph_transfer(sph_ctx *c, const sph_transfer_desc *d, const double *source, const double *kappa, double *host_out,
+                 int64_t out_len) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return transfer_run(c, d, source, kappa, host_out, out_len, true);
+}
+
+int sph_transfer_dev(sph_ctx *c, const sph_transfer_desc *d, const double *d_source, const double *d_kappa, double *d_out,
+                     int64_t out_len) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return transfer_run(c, d, d_source, d_kappa, d_out, out_len, false);
+}
+
 int sph_force_terms(sph_ctx *c, const sph_force_terms_desc *d, double *host_out, int64_t n_out) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);

@@ -508,6 +508,10 @@ int bound_run(sph_ctx *c, const sph_bound_desc *d, const int32_t *labels, int64_
 // position-position-velocity cubes (cube.hip): host form (values / out host memory, two read-backs + the copy out) or device
 // form
 int cube_run(sph_ctx *c, const sph_cube_desc *d, const double *values, double *out, int64_t out_len, bool host);
+// emission-absorption images (transfer.hip): host form (source / kappa / out host memory, two read-backs + the copy out) or
+// device form
+int transfer_run(sph_ctx *c, const sph_transfer_desc *d, const double *source, const double *kappa, double *out,
+                 int64_t out_len, bool host);
 // the rates of sph_forces split by term (terms.hip): host form (out host memory, one synchronisation) or device form
 int force_terms_run(sph_ctx *c, const sph_force_terms_desc *d, double *out, int64_t n_out, bool host);
 // binned sums (binned.hip): host form (values / sums / counts[3] host memory, one read-back) or device form (counts[3] device

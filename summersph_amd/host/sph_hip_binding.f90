@@ -55,6 +55,8 @@ module sph_hip_binding
   public :: sph_bound_desc, sph_bound, sph_bound_dev, SPH_BOUND_THERMAL, SPH_BOUND_NCOL
   ! spectral cubes (the optically thin position-position-velocity cube of the owned gas seen along any direction)
   public :: sph_cube_desc, sph_cube, sph_cube_dev, SPH_CUBE_PER_VELOCITY
+  ! emission-absorption images (intensity, optical depth, transmission and the tau surface of the gas seen along any direction)
+  public :: sph_transfer_desc, sph_transfer, sph_transfer_dev, SPH_TRANSFER_VALUES, SPH_TRANSFER_ONE
   ! the rates of sph_forces split by physical term (pressure, viscosity, sink gravity, self-gravity, PdV, heating, alpha)
   public :: sph_force_terms_desc, sph_force_terms, sph_force_terms_dev, SPH_TERMS_NROW, SPH_TERMS_SKIP_GAS_GRAVITY
   ! binned sums (weighted 1-D and 2-D sums of any fields or caller rows; the generic form of sph_profile's reduction)
@@ -238,6 +240,23 @@ module sph_hip_binding
     integer(c_int32_t) :: n_u, n_v, n_chan, flags
     integer(c_int64_t) :: reserved
   end type sph_cube_desc
+
+  ! sph_transfer: rot, centre, image node box, strict clip box and h as sph_cube's; kappa_scale (kappa_j = kappa_scale K_j),
+  ! tau_surface (> 0), tau_max (> 0, may be +infinity), background, n_u, n_v, source and kappa (where S and K come from: a
+  ! field id, SPH_TRANSFER_VALUES or SPH_TRANSFER_ONE), flags (0), reserved (0).  out holds out(iv, iu, plane) in Fortran
+  ! order: (n_v, n_u, 4), planes I + T background, tau, T, depth of the tau_surface surface.  240 bytes.
+  integer(c_int32_t), parameter :: SPH_TRANSFER_VALUES = -1
+  integer(c_int32_t), parameter :: SPH_TRANSFER_ONE = -2
+  type, bind(C) :: sph_transfer_desc
+    real(c_double) :: rot(9)
+    real(c_double) :: centre(3)
+    real(c_double) :: lo(2), hi(2)
+    real(c_double) :: clip_lo(3), clip_hi(3)
+    real(c_double) :: h
+    real(c_double) :: kappa_scale, tau_surface, tau_max, background
+    integer(c_int32_t) :: n_u, n_v, source, kappa
+    integer(c_int32_t) :: flags, reserved
+  end type sph_transfer_desc
 
   ! sph_force_terms: flags (SPH_TERMS_SKIP_GAS_GRAVITY: rows 9-11 are NaN, no tree walk), reserved (0).  out holds
   ! out(id, row) in Fortran order: (sph_count, SPH_TERMS_NROW), rows a_P(3) a_V(3) a_S(3) a_G(3) du_P du_V and the source and
@@ -821,6 +840,20 @@ module sph_hip_binding
       import :: c_int, c_int64_t, c_ptr, sph_cube_desc
       type(c_ptr), value :: ctx, d_values, d_out
       type(sph_cube_desc), intent(in) :: d
+      integer(c_int64_t), value :: out_len
+    end function
+    ! ---- emission-absorption images: source, kappa (sph_count doubles in the download order with SPH_TRANSFER_VALUES, else
+    !      c_null_ptr), host_out (4 n_u n_v doubles, C order [plane][iu][iv]), out_len = 4 n_u n_v
+    integer(c_int) function sph_transfer(ctx, d, source, kappa, host_out, out_len) bind(C, name='sph_transfer')
+      import :: c_int, c_int64_t, c_ptr, sph_transfer_desc
+      type(c_ptr), value :: ctx, source, kappa, host_out
+      type(sph_transfer_desc), intent(in) :: d
+      integer(c_int64_t), value :: out_len
+    end function
+    integer(c_int) function sph_transfer_dev(ctx, d, d_source, d_kappa, d_out, out_len) bind(C, name='sph_transfer_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_transfer_desc
+      type(c_ptr), value :: ctx, d_source, d_kappa, d_out
+      type(sph_transfer_desc), intent(in) :: d
       integer(c_int64_t), value :: out_len
     end function
     ! ---- the rates split by term: host_out / d_out (SPH_TERMS_NROW sph_count doubles, C order [row][id]), n_out = their number;
