@@ -6,11 +6,11 @@
 // nothing here reads or writes the context's grid, cell table, neighbour list, statistics or flags.
 //
 // Pipeline (all on ctx->stream, the analysis calls' scratch), the density render's front end in the image plane:
-//   cube_stats_partial/_final  owned gas particles inside the clip box: max h, min h, count                (read-back 1)
+//   cube_stats_partial, stats_final  owned gas particles inside the clip box: max h, min h, count          (read-back 1)
 //   cube_select                P_j = rot (r_j - centre); the selected particles within 2 h_j of the node box -> 64-bit key
 //                              (image-plane cell << 32 | id) and slot, compacted with an atomic cursor     (read-back 2)
 //   rocprim radix sort         (cell, particle id): the order every voxel adds its terms in
-//   cube_cells / cube_records  cell table; SoA records {P_u, P_v, V, m A / (pi h^2), 1 / h, sigma} and the particle's
+//   start_table / cube_records cell table; SoA records {P_u, P_v, V, m A / (pi h^2), 1 / h, sigma} and the particle's
 //                              channel range [klo, khi] (outside it every weight is an exact +0.0), in sorted order
 //   cube_gather                one wavefront per tile of 8 x 8 image nodes and per chunk of CC channels.  Every lane keeps
 //                              its node's CC-channel spectrum in LDS (slot [channel][lane]: lanes own disjoint slots, no
@@ -21,12 +21,14 @@
 //                              evaluate F once and add Y w_k into their own slots, w_k read from the lane that holds it.
 // A voxel's value is therefore the sum of its terms in the (cell, id) order of a binning that depends only on the
 // descriptor and the selected particles' h range: bitwise reproducible and independent of the context's sorted order.
+// The selection, the h rule, the reach, the nodes, the frame and start_table are image_common.hpp's, shared with render.hip
+// and transfer.hip.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
 #include <cmath>
 
-#include "reduce_common.hpp"
+#include "image_common.hpp"
 #include "spline_column.hpp"
 
 // the definition fixes the order of the frame's sums; no contraction into fused multiply-adds
@@ -38,7 +40,7 @@ namespace {
 
 constexpr int RB = 256;            // reduction / select block
 constexpr int RB_MAX = 1024;       // blocks of the reduction
-constexpr int NSTAT = 3;           // max h, max(-h), count
+constexpr int NSTAT = 3, NMIN = 0, NMAX = 2;       // max h, max(-h); count
 constexpr int TU = 8, TV = 8;      // image nodes per workgroup (v fastest)
 constexpr int GT = TU * TV;        // threads per gather workgroup: one wavefront
 static_assert(GT == WAVE, "cube_gather passes the channel weights between the lanes of one wavefront");
@@ -51,17 +53,8 @@ constexpr int CH = 2 * GT;         // records per LDS stage (6 planes of doubles
 constexpr int64_t MAX_CELLS = (int64_t)1 << 22;
 constexpr double XCUT = 8.5;       // the line profile's truncation, in sigma
 
-struct Frame {
-    double rot[9], centre[3], v_ref[3];
-};
-
-struct Sel {
-    double clip_lo[3], clip_hi[3];
-    double h;                      // > 0: one h for every particle; else per particle from hf
-    const double *hf;
-    const int32_t *orig;
-    int64_t n_slots;
-    int32_t n_owned;
+struct VFrame : Frame {            // the frame and its velocity zero (a kernel argument: sph_transfer's frame has none)
+    double v_ref[3];
 };
 
 struct PGrid {                     // image-plane cell grid
@@ -70,80 +63,34 @@ struct PGrid {                     // image-plane cell grid
     int32_t dim[2];
 };
 
-struct Nodes {
-    double lo[2], hi[2], step[2];  // hi = lo where n == 1
-    int32_t n[2];
-};
-
 struct Chan {
     double v0, dv;
     double sigma_scale, sigma_floor;
     int32_t n;
 };
 
-__device__ __forceinline__ bool selected(const Sel &s, int64_t i, double px, double py, double pz) {
-    return s.orig[i] < s.n_owned && px > s.clip_lo[0] && px < s.clip_hi[0] && py > s.clip_lo[1] && py < s.clip_hi[1] &&
-           pz > s.clip_lo[2] && pz < s.clip_hi[2];
-}
-
 __device__ __forceinline__ int32_t cell_1d(const PGrid &g, int a, double p) {
     const double t = floor((p - g.org[a]) * g.inv_edge);
     return (int32_t)fmin(fmax(t, 0.0), (double)(g.dim[a] - 1));     // monotone in p; NaN -> 0
 }
 
-// np.linspace: i * step + lo, the last node exactly hi
-__device__ __forceinline__ double node_coord(const Nodes &nd, int a, int i) {
-    return i >= nd.n[a] - 1 ? nd.hi[a] : (double)i * nd.step[a] + nd.lo[a];
-}
-
-// row a of rot applied to d, in the definition's order
-__device__ __forceinline__ double row_dot(const double *r, int a, double dx, double dy, double dz) {
-    return (r[3 * a] * dx + r[3 * a + 1] * dy) + r[3 * a + 2] * dz;
-}
-
 // partial[b * NSTAT + k]: max h, max -h, count over block b's grid-stride share of the selection
 __global__ __launch_bounds__(RB) void cube_stats_partial(const double *__restrict__ x, const double *__restrict__ y,
                                                          const double *__restrict__ z, Sel s, double *__restrict__ partial) {
-    __shared__ double sm[NSTAT][RB / WAVE];
     double v[NSTAT] = {-INFINITY, -INFINITY, 0.0};
     for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < s.n_slots; i += (int64_t)gridDim.x * RB) {
         if (!selected(s, i, x[i], y[i], z[i])) continue;
-        const double h = s.h > 0.0 ? s.h : s.hf[i];
+        const double h = sel_h(s, i);
         v[0] = fmax(v[0], h);
         v[1] = fmax(v[1], -h);
         v[2] += 1.0;
     }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NSTAT; k++) {
-        const double r = k < 2 ? wave_max(v[k]) : wave_sum(v[k]);
-        if (lane == 0) sm[k][wv] = r;
-    }
-    __syncthreads();
-    if (threadIdx.x < NSTAT) {
-        const int k = threadIdx.x;
-        double r = sm[k][0];
-        for (int w = 1; w < RB / WAVE; w++) r = k < 2 ? fmax(r, sm[k][w]) : r + sm[k][w];
-        partial[(int64_t)blockIdx.x * NSTAT + k] = r;
-    }
-}
-
-// one wave per statistic
-__global__ __launch_bounds__(NSTAT * 64) void cube_stats_final(const double *__restrict__ partial, int nblocks,
-                                                               double *__restrict__ out) {
-    const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    double r = k < 2 ? -INFINITY : 0.0;
-    for (int b = lane; b < nblocks; b += 64) {
-        const double v = partial[b * NSTAT + k];
-        r = k < 2 ? fmax(r, v) : r + v;
-    }
-    r = k < 2 ? wave_max(r) : wave_sum(r);
-    if (lane == 0) out[k] = r;
+    stats_block_partial<NMIN, NMAX, RB>(v, partial);
 }
 
 // the selected particles within 2 h_j (1 + 1e-6) of the node box in the image plane -> key (cell << 32 | original id), slot
 __global__ __launch_bounds__(RB) void cube_select(const double *__restrict__ x, const double *__restrict__ y,
-                                                  const double *__restrict__ z, Sel s, Frame fr, Nodes nd, PGrid g,
+                                                  const double *__restrict__ z, Sel s, VFrame fr, Nodes<2> nd, PGrid g,
                                                   uint64_t *__restrict__ keys, uint32_t *__restrict__ vals,
                                                   uint32_t *__restrict__ cursor, int64_t cap) {
     for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < s.n_slots; i += (int64_t)gridDim.x * RB) {
@@ -151,7 +98,7 @@ __global__ __launch_bounds__(RB) void cube_select(const double *__restrict__ x, 
         if (!selected(s, i, px, py, pz)) continue;
         const double dx = px - fr.centre[0], dy = py - fr.centre[1], dz = pz - fr.centre[2];
         const double P[2] = {row_dot(fr.rot, 0, dx, dy, dz), row_dot(fr.rot, 1, dx, dy, dz)};
-        const double reach = 2.0 * (s.h > 0.0 ? s.h : s.hf[i]) * (1.0 + 1e-6);
+        const double reach = sel_reach(s, i);
         bool near = true;
 #pragma unroll
         for (int a = 0; a < 2; a++) near = near && P[a] >= nd.lo[a] - reach && P[a] <= nd.hi[a] + reach;
@@ -165,19 +112,6 @@ __global__ __launch_bounds__(RB) void cube_select(const double *__restrict__ x, 
     }
 }
 
-// cell_start[c] = first sorted record of cell c (c in [0, ncells])
-__global__ __launch_bounds__(256) void cube_cells(const uint64_t *__restrict__ keys, int64_t n, int64_t ncells,
-                                                  int32_t *__restrict__ cell_start) {
-    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (c > ncells) return;
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)(keys[mid] >> 32) < c) lo = mid + 1; else hi = mid;
-    }
-    cell_start[c] = (int32_t)lo;
-}
-
 struct Fields {
     const double *x, *y, *z, *vx, *vy, *vz, *m, *cs;
     const double *values;          // the caller's A in the original order, or null (A = 1)
@@ -189,13 +123,13 @@ __device__ __forceinline__ double chan_edge(const Chan &ch, int k) { return ((do
 // records in sorted order: P_u, P_v, V, y0 = m A / (pi h^2), 1 / h, sigma; klo .. khi: the channels whose weight can be
 // non-zero (one channel of margin on either side: the skipped ones have both edges beyond the truncation, or on one side of
 // V where sigma == 0, an exact +0.0)
-__global__ __launch_bounds__(256) void cube_records(Fields f, Sel s, Frame fr, Chan ch, const uint32_t *__restrict__ vals,
+__global__ __launch_bounds__(256) void cube_records(Fields f, Sel s, VFrame fr, Chan ch, const uint32_t *__restrict__ vals,
                                                     int64_t n, double *__restrict__ rec, int32_t *__restrict__ krange,
                                                     int64_t stride) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int64_t j = vals[i];
-    const double h = s.h > 0.0 ? s.h : s.hf[j];
+    const double h = sel_h(s, j);
     const double dx = f.x[j] - fr.centre[0], dy = f.y[j] - fr.centre[1], dz = f.z[j] - fr.centre[2];
     const double V = row_dot(fr.rot, 2, f.vx[j] - fr.v_ref[0], f.vy[j] - fr.v_ref[1], f.vz[j] - fr.v_ref[2]);
     double sg = ch.sigma_floor;
@@ -240,7 +174,7 @@ __device__ __forceinline__ double lane_value(double v, int l) {
 #endif
 
 struct GatherArgs {
-    Nodes nd;
+    Nodes<2> nd;
     PGrid g;
     Chan ch;
     const double *pu, *pv, *vl, *y0, *ih, *sg;
@@ -259,7 +193,7 @@ __global__ __launch_bounds__(GT) void cube_gather(GatherArgs A) {
     __shared__ int32_t sklo[CH], skhi[CH];
     __shared__ int32_t s_start[GT], s_off[GT];
 
-    const Nodes &nd = A.nd;
+    const Nodes<2> &nd = A.nd;
     const int t = threadIdx.x;
     const int tu = blockIdx.x / A.tiles_v, tv = blockIdx.x % A.tiles_v;
     const int iu = tu * TU + t / TV, iv = tv * TV + t % TV;
@@ -378,32 +312,17 @@ int cube_run(sph_ctx *c, const sph_cube_desc *d, const double *values, double *o
     if (!(d->dv > 0.0) || !std::isfinite(d->dv) || !std::isfinite(d->v0)) return arg_error(c, who, "dv must be finite and > 0, v0 finite");
     if (!(d->sigma_scale >= 0.0) || !(d->sigma_floor >= 0.0) || !std::isfinite(d->sigma_scale) || !std::isfinite(d->sigma_floor))
         return arg_error(c, who, "sigma_scale and sigma_floor must be finite and >= 0");
-    {   // rows orthonormal, right-handed
-        const double *r = d->rot;
-        bool ok = true;
-        for (int a = 0; a < 3; a++)
-            for (int b = a; b < 3; b++) {
-                const double dot = (r[3 * a] * r[3 * b] + r[3 * a + 1] * r[3 * b + 1]) + r[3 * a + 2] * r[3 * b + 2];
-                ok = ok && std::fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-12;
-            }
-        const double det = r[0] * (r[4] * r[8] - r[5] * r[7]) - r[1] * (r[3] * r[8] - r[5] * r[6]) + r[2] * (r[3] * r[7] - r[4] * r[6]);
-        if (!(ok && std::fabs(det - 1.0) <= 1e-12)) return arg_error(c, who, "rot must be orthonormal and right-handed within 1e-12");
-    }
+    if (!check_rot(d->rot)) return arg_error(c, who, "rot must be orthonormal and right-handed within 1e-12");
     if (d->sigma_scale != 0.0 && !field_ready(*c, c->variable, SPH_F_C)) {
         c->err = "sph_cube: c is stale (sph_download_field would refuse it) and sigma_scale > 0";
         return SPH_ERR_STATE;
     }
 
     hipStream_t st = c->stream;
-    Sel s{};
-    Frame fr{};
-    for (int a = 0; a < 3; a++) { s.clip_lo[a] = d->clip_lo[a]; s.clip_hi[a] = d->clip_hi[a]; fr.centre[a] = d->centre[a]; fr.v_ref[a] = d->v_ref[a]; }
+    const Sel s = make_sel(c, d->clip_lo, d->clip_hi, d->h);
+    VFrame fr{};
+    for (int a = 0; a < 3; a++) { fr.centre[a] = d->centre[a]; fr.v_ref[a] = d->v_ref[a]; }
     for (int a = 0; a < 9; a++) fr.rot[a] = d->rot[a];
-    s.h = d->h > 0.0 ? d->h : (c->variable ? 0.0 : c->p.h);
-    s.hf = c->variable ? c->f[SPH_F_H] : nullptr;
-    s.orig = c->orig;
-    s.n_slots = c->cap > 0 ? c->n_slots : 0;
-    s.n_owned = (int32_t)c->n_owned;
     Chan ch{d->v0, d->dv, d->sigma_scale, d->sigma_floor, d->n_chan};
 
     SPH_TRY(analysis_pinned(c));
@@ -429,25 +348,13 @@ int cube_run(sph_ctx *c, const sph_cube_desc *d, const double *values, double *o
     if (s.n_slots > 0) {
         const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((s.n_slots + RB - 1) / RB, RB_MAX));
         cube_stats_partial<<<dim3(nb), dim3(RB), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], s, partial);
-        cube_stats_final<<<dim3(1), dim3(NSTAT * 64), 0, st>>>(partial, nb, stats);
-        SPH_HIP(hipGetLastError());
-        SPH_HIP(hipMemcpyAsync(c->rnd_pinned, stats, NSTAT * sizeof(double), hipMemcpyDeviceToHost, st));
-        SPH_HIP(hipStreamSynchronize(st));
-        for (int k = 0; k < NSTAT; k++) hs[k] = c->rnd_pinned[k];
+        SPH_TRY((stats_read_back<NSTAT, NMIN, NMAX>(c, partial, nb, stats, hs)));
     }
     const int64_t count = (int64_t)hs[2];
     const double h_max = hs[0], h_min = -hs[1];
-    if (count > 0 && !(h_min > 0.0 && std::isfinite(h_max))) {
-        c->err = "sph_cube: a selected particle has h <= 0 or a non-finite h";
-        return SPH_ERR_STATE;
-    }
-    Nodes nd{};
-    nd.n[0] = d->n_u; nd.n[1] = d->n_v;
-    for (int a = 0; a < 2; a++) {
-        nd.lo[a] = d->lo[a];
-        nd.hi[a] = nd.n[a] == 1 ? d->lo[a] : d->hi[a];             // a single node sits at lo
-        if (nd.n[a] > 1) nd.step[a] = (nd.hi[a] - nd.lo[a]) / (double)(nd.n[a] - 1);
-    }
+    SPH_TRY(check_h_range(c, who, count, h_max, h_min));
+    const int32_t n_uv[2] = {d->n_u, d->n_v};
+    const Nodes<2> nd = make_nodes<2>(d->lo, d->hi, n_uv);
 
     // ---- image-plane grid over the node box + the reach: edge 2 h_max, halved while a cell still spans a tile of nodes and
     //      an eighth of the reach (finer cells only trim the candidates of a tile) and the table stays within MAX_CELLS ------
@@ -455,7 +362,7 @@ int cube_run(sph_ctx *c, const sph_cube_desc *d, const double *values, double *o
     double reach = 0.0;
     int64_t ncells = 1;
     if (count > 0) {
-        reach = 2.0 * h_max * (1.0 + 1e-6);
+        reach = reach_of(h_max);
         double ext[2], edge = 2.0 * h_max;
         for (int a = 0; a < 2; a++) { g.org[a] = nd.lo[a] - reach; ext[a] = (nd.hi[a] + reach) - g.org[a]; }
         auto cells = [&](double e) { return std::max(1.0, std::ceil(ext[0] / e)) * std::max(1.0, std::ceil(ext[1] / e)); };
@@ -516,7 +423,7 @@ int cube_run(sph_ctx *c, const sph_cube_desc *d, const double *values, double *o
         while (cbits < 32 && ((int64_t)1 << cbits) < ncells) cbits++;
         size_t tmp = sort_bytes;
         SPH_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)nsel, 0u, 32u + cbits, st));
-        cube_cells<<<dim3((unsigned)((ncells + 1 + 255) / 256)), dim3(256), 0, st>>>(keys_alt, nsel, ncells, cell_start);
+        start_table<<<dim3((unsigned)((ncells + 1 + 255) / 256)), dim3(256), 0, st>>>(keys_alt, nsel, ncells, cell_start);
         if (host_v) SPH_HIP(hipMemcpyAsync(values_copy, values, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, st));
         Fields f{c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], c->f[SPH_F_VX], c->f[SPH_F_VY], c->f[SPH_F_VZ], c->f[SPH_F_M],
                  c->f[SPH_F_C], d_values};

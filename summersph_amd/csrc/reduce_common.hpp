@@ -2,6 +2,7 @@
 // groups.hip): a run of sorted positions is cut into pieces of PIECE positions from its own start, one wavefront reduces
 // each piece (lane l adds positions l, l + 64, ... in turn, then the butterfly) and a second kernel adds a run's pieces in
 // the same shape.  A sum's shape then depends on its run's start and length alone, never on the launch.
+// Also the min / max / count statistics of the image passes' selections (render.hip, cube.hip, transfer.hip).
 #pragma once
 #include "sph_internal.hpp"
 
@@ -19,6 +20,50 @@ __device__ __forceinline__ double wave_min(double v) {
 __device__ __forceinline__ double wave_max(double v) {
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
     return v;
+}
+
+// The image passes' selection statistics (render.hip, cube.hip, transfer.hip): N values of which the first NMIN are
+// minima, the next NMAX maxima and the rest counts (sums of small integers).  All three are exact in any order, so the
+// values do not depend on the launch.
+template <int NMIN, int NMAX>
+__device__ __forceinline__ double stat_identity(int k) { return k < NMIN ? INFINITY : (k < NMIN + NMAX ? -INFINITY : 0.0); }
+template <int NMIN, int NMAX>
+__device__ __forceinline__ double stat_join(int k, double a, double b) {
+    return k < NMIN ? fmin(a, b) : (k < NMIN + NMAX ? fmax(a, b) : a + b);
+}
+template <int NMIN, int NMAX>
+__device__ __forceinline__ double stat_wave(int k, double v) {
+    return k < NMIN ? wave_min(v) : (k < NMIN + NMAX ? wave_max(v) : wave_sum(v));
+}
+
+// the tail of a statistics kernel of B threads: joins every thread's v over the block into partial[blockIdx.x * N + k]
+template <int NMIN, int NMAX, int B, int N>
+__device__ __forceinline__ void stats_block_partial(const double (&v)[N], double *__restrict__ partial) {
+    __shared__ double sm[N][B / WAVE];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const double r = stat_wave<NMIN, NMAX>(k, v[k]);
+        if (lane == 0) sm[k][wv] = r;
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        const int k = threadIdx.x;
+        double r = sm[k][0];
+        for (int w = 1; w < B / WAVE; w++) r = stat_join<NMIN, NMAX>(k, r, sm[k][w]);
+        partial[(int64_t)blockIdx.x * N + k] = r;
+    }
+}
+
+// joins the nblocks rows of partial: one wave per statistic
+template <int N, int NMIN, int NMAX>
+__global__ __launch_bounds__(N * WAVE) void stats_final(const double *__restrict__ partial, int nblocks,
+                                                        double *__restrict__ out) {
+    const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double r = stat_identity<NMIN, NMAX>(k);
+    for (int b = lane; b < nblocks; b += 64) r = stat_join<NMIN, NMAX>(k, r, partial[b * N + k]);
+    r = stat_wave<NMIN, NMAX>(k, r);
+    if (lane == 0) out[k] = r;
 }
 
 constexpr int PIECE = 16 * WAVE;   // positions per piece: 16 per lane

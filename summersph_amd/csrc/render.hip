@@ -5,11 +5,11 @@
 // step loop: nothing here reads or writes the context's grid, cell table, neighbour list, statistics or flags.
 //
 // Pipeline (all on ctx->stream, render-private scratch):
-//   render_stats_partial/_final  owned gas particles inside the clip box: min/max xyz, max/min h, count  (read-back 1)
+//   render_stats_partial, stats_final  owned gas particles inside the clip box: min/max xyz, max/min h, count  (read-back 1)
 //   render_select                the selected particles within 2 h_j of the node box -> 64-bit key (cell << 32 | id)
 //                                and slot, compacted with an atomic cursor                            (read-back 2)
 //   rocprim radix sort           (cell, particle id): the order every node adds its terms in
-//   render_cells / render_records  cell table; SoA records {x, y, z, m sigma_j, 1/h_j} in sorted order
+//   start_table / render_records   cell table; SoA records {x, y, z, m sigma_j, 1/h_j} in sorted order
 //   render_field_records         (sph_render_field) SoA records {x, y, z, w_j sigma_j, w_j sigma_j A_j, 1/h_j} in sorted order
 //   render_gather<W>             one workgroup per tile of 8 x 8 node columns; lanes walk axis W in segments of KW nodes.
 //                                The records of the cells that overlap a segment's brick (+ the reach) are staged into LDS
@@ -21,12 +21,13 @@
 // A node's value is therefore the sum of its contributing terms in the global (cell, id) order of a binning that depends
 // only on the node box, n, h and the clip: independent of the context's sorted order, of the launch geometry and of the
 // output mode (terms of particles beyond 2h are skipped or are exact +0.0, which changes no sum).
+// The selection, the h rule, the reach, the nodes and start_table are image_common.hpp's, shared with cube.hip and transfer.hip.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
 #include <cmath>
 
-#include "reduce_common.hpp"
+#include "image_common.hpp"
 
 // the 3-D values and the column sums must be bitwise the same per node: no contraction into fused multiply-adds that
 // the compiler might choose differently in the three instantiations of the gather
@@ -38,7 +39,7 @@ namespace {
 
 constexpr int RB = 256;            // reduction / select block
 constexpr int RB_MAX = 1024;       // blocks of the reduction
-constexpr int NSTAT = 9;           // min xyz, max xyz, max h, max(-h), count
+constexpr int NSTAT = 9, NMIN = 3, NMAX = 5;       // min xyz; max xyz, max h, max(-h); count
 #ifndef RENDER_TILE
 #define RENDER_TILE 8              // A/B switch ("Density rendering"): 16 = workgroups of 16 x 16 columns
 #endif
@@ -49,24 +50,10 @@ constexpr int CH = 4 * GT;         // records per LDS chunk (5 planes of doubles
                                    // render's 6 planes: 12 KB)
 constexpr int64_t MAX_CELLS = (int64_t)1 << 26;
 
-struct Sel {
-    double clip_lo[3], clip_hi[3];
-    double h;                      // > 0: one h for every particle; else per particle from hf
-    const double *hf;
-    const int32_t *orig;
-    int64_t n_slots;
-    int32_t n_owned;
-};
-
 struct RGrid {                     // render-private cell grid
     double org[3];
     double inv_edge;
     int32_t dim[3];
-};
-
-struct Nodes {
-    double lo[3], hi[3], step[3];  // hi = lo where n == 1
-    int32_t n[3];
 };
 
 struct Recs {
@@ -75,73 +62,37 @@ struct Recs {
     const double *wa;              // the field render's w sigma A plane (unused by the density render)
 };
 
-__device__ __forceinline__ bool selected(const Sel &s, int64_t i, double px, double py, double pz) {
-    return s.orig[i] < s.n_owned && px > s.clip_lo[0] && px < s.clip_hi[0] && py > s.clip_lo[1] && py < s.clip_hi[1] &&
-           pz > s.clip_lo[2] && pz < s.clip_hi[2];
-}
-
 __device__ __forceinline__ int32_t cell_1d(const RGrid &g, int a, double p) {
     const double t = floor((p - g.org[a]) * g.inv_edge);
     return (int32_t)fmin(fmax(t, 0.0), (double)(g.dim[a] - 1));     // monotone in p; NaN -> 0
 }
 
-// np.linspace: i * step + lo, the last node exactly hi
-__device__ __forceinline__ double node_coord(const Nodes &nd, int a, int i) {
-    return i >= nd.n[a] - 1 ? nd.hi[a] : (double)i * nd.step[a] + nd.lo[a];
-}
-
 // partial[b * NSTAT + k]: min x y z, max x y z, max h, max -h, count over block b's grid-stride share of the selection
 __global__ __launch_bounds__(RB) void render_stats_partial(const double *__restrict__ x, const double *__restrict__ y,
                                                            const double *__restrict__ z, Sel s, double *__restrict__ partial) {
-    __shared__ double sm[NSTAT][RB / WAVE];
     double v[NSTAT] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY, -INFINITY, -INFINITY, 0.0};
     for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < s.n_slots; i += (int64_t)gridDim.x * RB) {
         const double p[3] = {x[i], y[i], z[i]};
         if (!selected(s, i, p[0], p[1], p[2])) continue;
 #pragma unroll
         for (int a = 0; a < 3; a++) { v[a] = fmin(v[a], p[a]); v[3 + a] = fmax(v[3 + a], p[a]); }
-        const double h = s.h > 0.0 ? s.h : s.hf[i];
+        const double h = sel_h(s, i);
         v[6] = fmax(v[6], h);
         v[7] = fmax(v[7], -h);
         v[8] += 1.0;
     }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NSTAT; k++) {
-        const double r = k < 3 ? wave_min(v[k]) : (k < 8 ? wave_max(v[k]) : wave_sum(v[k]));
-        if (lane == 0) sm[k][wv] = r;
-    }
-    __syncthreads();
-    if (threadIdx.x < NSTAT) {
-        const int k = threadIdx.x;
-        double r = sm[k][0];
-        for (int w = 1; w < RB / WAVE; w++) r = k < 3 ? fmin(r, sm[k][w]) : (k < 8 ? fmax(r, sm[k][w]) : r + sm[k][w]);
-        partial[(int64_t)blockIdx.x * NSTAT + k] = r;
-    }
-}
-
-// one wave per statistic
-__global__ __launch_bounds__(NSTAT * 64) void render_stats_final(const double *__restrict__ partial, int nblocks,
-                                                                 double *__restrict__ out) {
-    const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    double r = k < 3 ? INFINITY : (k < 8 ? -INFINITY : 0.0);
-    for (int b = lane; b < nblocks; b += 64) {
-        const double v = partial[b * NSTAT + k];
-        r = k < 3 ? fmin(r, v) : (k < 8 ? fmax(r, v) : r + v);
-    }
-    r = k < 3 ? wave_min(r) : (k < 8 ? wave_max(r) : wave_sum(r));
-    if (lane == 0) out[k] = r;
+    stats_block_partial<NMIN, NMAX, RB>(v, partial);
 }
 
 // the selected particles within 2 h_j (1 + 1e-6) of the node box -> key (cell << 32 | original id), slot
 __global__ __launch_bounds__(RB) void render_select(const double *__restrict__ x, const double *__restrict__ y,
-                                                    const double *__restrict__ z, Sel s, Nodes nd, RGrid g,
+                                                    const double *__restrict__ z, Sel s, Nodes<3> nd, RGrid g,
                                                     uint64_t *__restrict__ keys, uint32_t *__restrict__ vals,
                                                     uint32_t *__restrict__ cursor, int64_t cap) {
     for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < s.n_slots; i += (int64_t)gridDim.x * RB) {
         const double p[3] = {x[i], y[i], z[i]};
         if (!selected(s, i, p[0], p[1], p[2])) continue;
-        const double reach = 2.0 * (s.h > 0.0 ? s.h : s.hf[i]) * (1.0 + 1e-6);
+        const double reach = sel_reach(s, i);
         bool near = true;
 #pragma unroll
         for (int a = 0; a < 3; a++) near = near && p[a] >= nd.lo[a] - reach && p[a] <= nd.hi[a] + reach;
@@ -156,19 +107,6 @@ __global__ __launch_bounds__(RB) void render_select(const double *__restrict__ x
     }
 }
 
-// cell_start[c] = first sorted record of cell c (c in [0, ncells])
-__global__ __launch_bounds__(256) void render_cells(const uint64_t *__restrict__ keys, int64_t n, int64_t ncells,
-                                                    int32_t *__restrict__ cell_start) {
-    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (c > ncells) return;
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)(keys[mid] >> 32) < c) lo = mid + 1; else hi = mid;
-    }
-    cell_start[c] = (int32_t)lo;
-}
-
 // records in sorted order: x, y, z, m sigma_j = m / (pi h_j^3), 1 / h_j   (double-precision pi: the script's kernel)
 __global__ __launch_bounds__(256) void render_records(const double *__restrict__ x, const double *__restrict__ y,
                                                       const double *__restrict__ z, const double *__restrict__ m, Sel s,
@@ -177,7 +115,7 @@ __global__ __launch_bounds__(256) void render_records(const double *__restrict__
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int64_t j = vals[i];
-    const double h = s.h > 0.0 ? s.h : s.hf[j];
+    const double h = sel_h(s, j);
     rec[i] = x[j];
     rec[stride + i] = y[j];
     rec[2 * stride + i] = z[j];
@@ -197,7 +135,7 @@ __global__ __launch_bounds__(256) void render_field_records(const double *__rest
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int64_t j = vals[i];
-    const double h = s.h > 0.0 ? s.h : s.hf[j];
+    const double h = sel_h(s, j);
     const double sigma = 1.0 / (M_PI * (h * h * h));
     const double ws = (rho ? m[j] / rho[j] : m[j]) * sigma;
     const double av = values ? values[s.orig[j]] : a[j];
@@ -219,7 +157,7 @@ __device__ __forceinline__ double kernel_w(double q) {
 }
 
 struct GatherArgs {
-    Nodes nd;
+    Nodes<3> nd;
     RGrid g;
     Recs r;
     double reach;      // 2 h_max (1 + 1e-6): the brick's box is widened by this to find its candidate cells
@@ -244,7 +182,7 @@ __device__ __forceinline__ void gather_body(const GatherArgs &A) {
     __shared__ int32_t s_start[GT], s_off[GT];
     __shared__ int32_t s_wsum[GT / WAVE];
 
-    const Nodes &nd = A.nd;
+    const Nodes<3> &nd = A.nd;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const int tu = blockIdx.x / A.tiles_v, tv = blockIdx.x % A.tiles_v;
     const int iu = tu * TU + t / TV, iv = tv * TV + t % TV;
@@ -433,13 +371,7 @@ int render_impl(sph_ctx *c, sph_render_desc *d, const FieldSpec *fs, double *out
     }
 
     hipStream_t st = c->stream;
-    Sel s{};
-    for (int a = 0; a < 3; a++) { s.clip_lo[a] = d->clip_lo[a]; s.clip_hi[a] = d->clip_hi[a]; }
-    s.h = d->h > 0.0 ? d->h : (c->variable ? 0.0 : c->p.h);
-    s.hf = c->variable ? c->f[SPH_F_H] : nullptr;
-    s.orig = c->orig;
-    s.n_slots = c->cap > 0 ? c->n_slots : 0;
-    s.n_owned = (int32_t)c->n_owned;
+    const Sel s = make_sel(c, d->clip_lo, d->clip_hi, d->h);
 
     if (!c->rnd_small) SPH_TRY(ctx_alloc(c, &c->rnd_small, (size_t)RB_MAX * NSTAT + 16, "render statistics"));
     SPH_TRY(analysis_pinned(c));
@@ -451,37 +383,23 @@ int render_impl(sph_ctx *c, sph_render_desc *d, const FieldSpec *fs, double *out
     if (s.n_slots > 0) {
         const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((s.n_slots + RB - 1) / RB, RB_MAX));
         render_stats_partial<<<dim3(nb), dim3(RB), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], s, c->rnd_small);
-        render_stats_final<<<dim3(1), dim3(NSTAT * 64), 0, st>>>(c->rnd_small, nb, stats);
-        SPH_HIP(hipGetLastError());
-        SPH_HIP(hipMemcpyAsync(c->rnd_pinned, stats, NSTAT * sizeof(double), hipMemcpyDeviceToHost, st));
-        SPH_HIP(hipStreamSynchronize(st));
-        for (int k = 0; k < NSTAT; k++) hs[k] = c->rnd_pinned[k];
+        SPH_TRY((stats_read_back<NSTAT, NMIN, NMAX>(c, c->rnd_small, nb, stats, hs)));
     }
     const int64_t count = (int64_t)hs[8];
     if (count == 0 && autob) return arg_error(c, who, "SPH_RENDER_AUTO_BOUNDS over an empty selection");
     const double h_max = hs[6], h_min = -hs[7];
-    if (count > 0 && !(h_min > 0.0 && std::isfinite(h_max))) {
-        c->err = std::string(who) + ": a selected particle has h <= 0 or a non-finite h";
-        return SPH_ERR_STATE;
-    }
-    Nodes nd{};
-    for (int a = 0; a < 3; a++) {
-        nd.lo[a] = autob ? hs[a] : d->lo[a];
-        nd.hi[a] = autob ? hs[3 + a] : d->hi[a];
-        nd.n[a] = d->n[a];
-        if (nd.n[a] > 1) nd.step[a] = (nd.hi[a] - nd.lo[a]) / (double)(nd.n[a] - 1);
-    }
-    Nodes ndk = nd;                                     // the kernels' copy: a single node sits at lo
-    for (int a = 0; a < 3; a++) if (ndk.n[a] == 1) ndk.hi[a] = ndk.lo[a];
+    SPH_TRY(check_h_range(c, who, count, h_max, h_min));
+    const double *lo = autob ? hs : d->lo, *hi = autob ? hs + 3 : d->hi;
+    const Nodes<3> nd = make_nodes<3>(lo, hi, d->n);
 
     // ---- render grid: edge max(2 h_max, what keeps the table within MAX_CELLS) over the node box + the reach -----------
     RGrid g{};
     double reach = 0.0;
     int64_t ncells = 1;
     if (count > 0) {
-        reach = 2.0 * h_max * (1.0 + 1e-6);
+        reach = reach_of(h_max);
         double ext[3], edge = 2.0 * h_max;
-        for (int a = 0; a < 3; a++) { g.org[a] = ndk.lo[a] - reach; ext[a] = (ndk.hi[a] + reach) - g.org[a]; }
+        for (int a = 0; a < 3; a++) { g.org[a] = nd.lo[a] - reach; ext[a] = (nd.hi[a] + reach) - g.org[a]; }
         for (;;) {
             double prod = 1.0;
             for (int a = 0; a < 3; a++) prod *= std::max(1.0, std::ceil(ext[a] / edge));
@@ -530,7 +448,7 @@ int render_impl(sph_ctx *c, sph_render_desc *d, const FieldSpec *fs, double *out
     if (count > 0) {
         SPH_HIP(hipMemsetAsync(cursor, 0, sizeof(uint32_t), st));
         const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((s.n_slots + RB - 1) / RB, 4 * RB_MAX));
-        render_select<<<dim3(nb), dim3(RB), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], s, ndk, g, keys, vals, cursor, cap);
+        render_select<<<dim3(nb), dim3(RB), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], s, nd, g, keys, vals, cursor, cap);
         SPH_HIP(hipGetLastError());
         SPH_HIP(hipMemcpyAsync(c->rnd_pinned + 16, cursor, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         SPH_HIP(hipStreamSynchronize(st));
@@ -545,7 +463,7 @@ int render_impl(sph_ctx *c, sph_render_desc *d, const FieldSpec *fs, double *out
         while (cbits < 32 && ((int64_t)1 << cbits) < ncells) cbits++;
         size_t tmp = sort_bytes;
         SPH_HIP(rocprim::radix_sort_pairs(sort_tmp, tmp, keys, keys_alt, vals, vals_alt, (size_t)nsel, 0u, 32u + cbits, st));
-        render_cells<<<dim3((unsigned)((ncells + 1 + 255) / 256)), dim3(256), 0, st>>>(keys_alt, nsel, ncells, cell_start);
+        start_table<<<dim3((unsigned)((ncells + 1 + 255) / 256)), dim3(256), 0, st>>>(keys_alt, nsel, ncells, cell_start);
         if (!fs) {
             render_records<<<dim3((unsigned)((nsel + 255) / 256)), dim3(256), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z],
                                                                                        c->f[SPH_F_M], s, vals_alt, nsel, rec, cap);
@@ -556,7 +474,7 @@ int render_impl(sph_ctx *c, sph_render_desc *d, const FieldSpec *fs, double *out
         }
         SPH_HIP(hipGetLastError());
         GatherArgs a{};
-        a.nd = ndk; a.g = g; a.reach = reach;
+        a.nd = nd; a.g = g; a.reach = reach;
         if (!fs) a.r = Recs{rec, rec + cap, rec + 2 * cap, rec + 3 * cap, rec + 4 * cap, cell_start, nullptr};
         else a.r = Recs{rec, rec + cap, rec + 2 * cap, rec + 3 * cap, rec + 5 * cap, cell_start, rec + 4 * cap};
         a.project = d->axis >= 0;
@@ -586,7 +504,7 @@ int render_impl(sph_ctx *c, sph_render_desc *d, const FieldSpec *fs, double *out
         SPH_HIP(hipStreamSynchronize(st));
     }
     if (autob)
-        for (int a = 0; a < 3; a++) { d->lo[a] = nd.lo[a]; d->hi[a] = nd.hi[a]; }
+        for (int a = 0; a < 3; a++) { d->lo[a] = hs[a]; d->hi[a] = hs[3 + a]; }
     return SPH_OK;
 }
 

@@ -7,7 +7,7 @@
 // table, neighbour list, statistics or flags.
 //
 // Pipeline (all on ctx->stream, the analysis calls' scratch):
-//   transfer_stats_partial/_final  owned gas inside the clip box: max h, min h, count, bad K or S             (read-back 1)
+//   transfer_stats_partial, stats_final  owned gas inside the clip box: max h, min h, count, bad K or S       (read-back 1)
 //   transfer_count                 the selected particles that reach a node and the tiles they touch: sizes   (read-back 2)
 //   transfer_select                the same particles -> (id, slot), compacted with an atomic cursor
 //   rocprim radix sort             by id, then transfer_depth_keys and a stable sort by the sortable image of D_j: (D, id)
@@ -15,7 +15,7 @@
 //                                  number of tiles of 8 x 8 nodes the particle touches (the nodes within its reach, a box)
 //   rocprim exclusive scan, transfer_emit   one entry (tile << 32 | depth rank) per particle and tile, in rank order
 //   rocprim radix sort             stable, on the tile bits alone: every tile's entries stay in depth order
-//   transfer_tiles                 tile start table
+//   start_table                    tile start table
 //   transfer_gather                one wavefront per tile, lane = node.  The tile's records are staged into LDS 128 at a
 //                                  time in list order.  Per record a ballot gives the nodes inside its footprint; the
 //                                  (record, node) pairs of a segment are then evaluated 64 at a time (F, one expm1: the
@@ -23,13 +23,15 @@
 //                                  applied per node in list order.  The loop ends with the list or when no lane runs.
 // A node's value is therefore a function of the descriptor, the selected particles and their ids alone: bitwise
 // reproducible and independent of the context's sorted order.
+// The selection, the h rule, the reach, the nodes, the frame and start_table are image_common.hpp's, shared with render.hip
+// and cube.hip.
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <cmath>
 
-#include "reduce_common.hpp"
+#include "image_common.hpp"
 #include "spline_column.hpp"
 
 // the definition fixes the order of the frame's sums and of the compositing; no contraction into fused multiply-adds
@@ -41,7 +43,7 @@ namespace {
 
 constexpr int RB = 256;            // reduction / select block
 constexpr int RB_MAX = 1024;       // blocks of the reduction
-constexpr int NSTAT = 4;           // max h, max(-h), count, particles with a bad K or S
+constexpr int NSTAT = 4, NMIN = 0, NMAX = 2;       // max h, max(-h); count, particles with a bad K or S
 constexpr int TU = 8, TV = 8;      // image nodes per tile (v fastest)
 constexpr int GT = TU * TV;        // threads per gather workgroup: one wavefront, lane = node
 static_assert(GT == WAVE, "transfer_gather ballots over the nodes of one wavefront");
@@ -57,24 +59,6 @@ constexpr int PSKIP = 0x8000;
 static_assert(PC >= GT && CH * GT <= PSKIP, "a record's 64 pairs fit a segment; (record << 6 | lane) stays below the skip bit");
 constexpr int64_t MAX_ENTRIES = (int64_t)1 << 31;
 
-struct Frame {
-    double rot[9], centre[3];
-};
-
-struct Sel {
-    double clip_lo[3], clip_hi[3];
-    double h;                      // > 0: one h for every particle; else per particle from hf
-    const double *hf;
-    const int32_t *orig;
-    int64_t n_slots;
-    int32_t n_owned;
-};
-
-struct Nodes {
-    double lo[2], hi[2], step[2];  // hi = lo where n == 1
-    int32_t n[2];
-};
-
 // where K or S of a slot comes from: a field of the context (slot order), the caller's array (original order) or 1
 struct Src {
     const double *field, *values;
@@ -84,24 +68,9 @@ __device__ __forceinline__ double src_at(const Src &s, const int32_t *orig, int6
     return s.field ? s.field[i] : (s.values ? s.values[orig[i]] : 1.0);
 }
 
-__device__ __forceinline__ bool selected(const Sel &s, int64_t i, double px, double py, double pz) {
-    return s.orig[i] < s.n_owned && px > s.clip_lo[0] && px < s.clip_hi[0] && py > s.clip_lo[1] && py < s.clip_hi[1] &&
-           pz > s.clip_lo[2] && pz < s.clip_hi[2];
-}
-
-// np.linspace: i * step + lo, the last node exactly hi
-__device__ __forceinline__ double node_coord(const Nodes &nd, int a, int i) {
-    return i >= nd.n[a] - 1 ? nd.hi[a] : (double)i * nd.step[a] + nd.lo[a];
-}
-
-// row a of rot applied to d, in the definition's order
-__device__ __forceinline__ double row_dot(const double *r, int a, double dx, double dy, double dz) {
-    return (r[3 * a] * dx + r[3 * a + 1] * dy) + r[3 * a + 2] * dz;
-}
-
 // the nodes i0 .. i1 of axis a with p - reach <= node <= p + reach, decided on the node coordinates themselves (the
 // division only gives the first guess); false when there is none (or p is NaN)
-__device__ __forceinline__ bool node_range(const Nodes &nd, int a, double p, double reach, int &i0, int &i1) {
+__device__ __forceinline__ bool node_range(const Nodes<2> &nd, int a, double p, double reach, int &i0, int &i1) {
     const double a0 = p - reach, a1 = p + reach;
     const int n = nd.n[a];
     if (!(a1 >= nd.lo[a] && a0 <= nd.hi[a])) return false;
@@ -119,7 +88,7 @@ __device__ __forceinline__ bool node_range(const Nodes &nd, int a, double p, dou
 }
 
 // the tiles [t0[a], t1[a]] that hold the nodes within the reach of P; false: none
-__device__ __forceinline__ bool tile_range(const Nodes &nd, double pu, double pv, double reach, int t0[2], int t1[2]) {
+__device__ __forceinline__ bool tile_range(const Nodes<2> &nd, double pu, double pv, double reach, int t0[2], int t1[2]) {
     int i0, i1;
     if (!node_range(nd, 0, pu, reach, i0, i1)) return false;
     t0[0] = i0 / TU; t1[0] = i1 / TU;
@@ -132,57 +101,31 @@ __device__ __forceinline__ bool tile_range(const Nodes &nd, double pu, double pv
 __global__ __launch_bounds__(RB) void transfer_stats_partial(const double *__restrict__ x, const double *__restrict__ y,
                                                              const double *__restrict__ z, Sel s, Src K, Src S,
                                                              double *__restrict__ partial) {
-    __shared__ double sm[NSTAT][RB / WAVE];
     double v[NSTAT] = {-INFINITY, -INFINITY, 0.0, 0.0};
     for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < s.n_slots; i += (int64_t)gridDim.x * RB) {
         if (!selected(s, i, x[i], y[i], z[i])) continue;
-        const double h = s.h > 0.0 ? s.h : s.hf[i];
+        const double h = sel_h(s, i);
         v[0] = fmax(v[0], h);
         v[1] = fmax(v[1], -h);
         v[2] += 1.0;
         const double k = src_at(K, s.orig, i), sj = src_at(S, s.orig, i);
         if (!(k >= 0.0 && k < INFINITY) || !(fabs(sj) < INFINITY)) v[3] += 1.0;
     }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NSTAT; k++) {
-        const double r = k < 2 ? wave_max(v[k]) : wave_sum(v[k]);
-        if (lane == 0) sm[k][wv] = r;
-    }
-    __syncthreads();
-    if (threadIdx.x < NSTAT) {
-        const int k = threadIdx.x;
-        double r = sm[k][0];
-        for (int w = 1; w < RB / WAVE; w++) r = k < 2 ? fmax(r, sm[k][w]) : r + sm[k][w];
-        partial[(int64_t)blockIdx.x * NSTAT + k] = r;
-    }
-}
-
-// one wave per statistic (the counts are sums of small integers: exact in any order)
-__global__ __launch_bounds__(NSTAT * 64) void transfer_stats_final(const double *__restrict__ partial, int nblocks,
-                                                                   double *__restrict__ out) {
-    const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    double r = k < 2 ? -INFINITY : 0.0;
-    for (int b = lane; b < nblocks; b += 64) {
-        const double v = partial[b * NSTAT + k];
-        r = k < 2 ? fmax(r, v) : r + v;
-    }
-    r = k < 2 ? wave_max(r) : wave_sum(r);
-    if (lane == 0) out[k] = r;
+    stats_block_partial<NMIN, NMAX, RB>(v, partial);
 }
 
 // the selected particles that reach a node: P_uv and the tiles; false for every other slot
-__device__ __forceinline__ bool reaches(const Sel &s, const Frame &fr, const Nodes &nd, int64_t i, double px, double py,
+__device__ __forceinline__ bool reaches(const Sel &s, const Frame &fr, const Nodes<2> &nd, int64_t i, double px, double py,
                                         double pz, int t0[2], int t1[2]) {
     if (!selected(s, i, px, py, pz)) return false;
     const double dx = px - fr.centre[0], dy = py - fr.centre[1], dz = pz - fr.centre[2];
-    const double reach = 2.0 * (s.h > 0.0 ? s.h : s.hf[i]) * (1.0 + 1e-6);
+    const double reach = sel_reach(s, i);
     return tile_range(nd, row_dot(fr.rot, 0, dx, dy, dz), row_dot(fr.rot, 1, dx, dy, dz), reach, t0, t1);
 }
 
 // sizes[0]: particles that reach a node, sizes[1]: entries (particle, tile)
 __global__ __launch_bounds__(RB) void transfer_count(const double *__restrict__ x, const double *__restrict__ y,
-                                                     const double *__restrict__ z, Sel s, Frame fr, Nodes nd,
+                                                     const double *__restrict__ z, Sel s, Frame fr, Nodes<2> nd,
                                                      unsigned long long *__restrict__ sizes) {
     unsigned long long np = 0, ne = 0;
     for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < s.n_slots; i += (int64_t)gridDim.x * RB) {
@@ -207,7 +150,7 @@ __global__ __launch_bounds__(RB) void transfer_count(const double *__restrict__ 
 
 // the same particles -> (original id, slot)
 __global__ __launch_bounds__(RB) void transfer_select(const double *__restrict__ x, const double *__restrict__ y,
-                                                      const double *__restrict__ z, Sel s, Frame fr, Nodes nd,
+                                                      const double *__restrict__ z, Sel s, Frame fr, Nodes<2> nd,
                                                       uint32_t *__restrict__ ids, uint32_t *__restrict__ slots,
                                                       uint32_t *__restrict__ cursor, int64_t cap) {
     for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < s.n_slots; i += (int64_t)gridDim.x * RB) {
@@ -239,14 +182,14 @@ struct Fields {
 };
 
 // records in depth order: P_u, P_v, D, y0 = m kappa / (pi h^2), 1 / h, S; cnt[i]: the tiles particle i touches
-__global__ __launch_bounds__(256) void transfer_records(Fields f, Sel s, Frame fr, Nodes nd, Src K, Src S, double kappa_scale,
+__global__ __launch_bounds__(256) void transfer_records(Fields f, Sel s, Frame fr, Nodes<2> nd, Src K, Src S, double kappa_scale,
                                                         const uint32_t *__restrict__ slots, int64_t n,
                                                         double *__restrict__ rec, int64_t stride, uint32_t *__restrict__ cnt) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i > n) return;
     if (i == n) { cnt[i] = 0; return; }                                // the scan's last element: the total
     const int64_t j = slots[i];
-    const double h = s.h > 0.0 ? s.h : s.hf[j];
+    const double h = sel_h(s, j);
     const double dx = f.x[j] - fr.centre[0], dy = f.y[j] - fr.centre[1], dz = f.z[j] - fr.centre[2];
     const double pu = row_dot(fr.rot, 0, dx, dy, dz), pv = row_dot(fr.rot, 1, dx, dy, dz);
     const double kappa = kappa_scale * src_at(K, s.orig, j);
@@ -257,20 +200,20 @@ __global__ __launch_bounds__(256) void transfer_records(Fields f, Sel s, Frame f
     rec[4 * stride + i] = 1.0 / h;
     rec[5 * stride + i] = src_at(S, s.orig, j);
     int t0[2], t1[2];
-    const bool any = tile_range(nd, pu, pv, 2.0 * h * (1.0 + 1e-6), t0, t1);
+    const bool any = tile_range(nd, pu, pv, reach_of(h), t0, t1);
     cnt[i] = any ? (uint32_t)(t1[0] - t0[0] + 1) * (uint32_t)(t1[1] - t0[1] + 1) : 0u;
 }
 
 // entries (tile << 32 | depth rank) of particle i at off[i] ..: rank order, a particle's tiles ascending
-__global__ __launch_bounds__(256) void transfer_emit(const double *__restrict__ rec, int64_t stride, Sel s, Nodes nd,
+__global__ __launch_bounds__(256) void transfer_emit(const double *__restrict__ rec, int64_t stride, Sel s, Nodes<2> nd,
                                                      int32_t tiles_v, const uint32_t *__restrict__ slots,
                                                      const uint32_t *__restrict__ off, int64_t n, int64_t cap,
                                                      uint64_t *__restrict__ keys) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double h = s.h > 0.0 ? s.h : s.hf[slots[i]];
+    const double reach = sel_reach(s, slots[i]);
     int t0[2], t1[2];
-    if (!tile_range(nd, rec[i], rec[stride + i], 2.0 * h * (1.0 + 1e-6), t0, t1)) return;     // transfer_records' test
+    if (!tile_range(nd, rec[i], rec[stride + i], reach, t0, t1)) return;     // transfer_records' test
     int64_t o = off[i];
     const int64_t end = min((int64_t)off[i + 1], cap);
     for (int tu = t0[0]; tu <= t1[0]; tu++)
@@ -278,21 +221,8 @@ __global__ __launch_bounds__(256) void transfer_emit(const double *__restrict__ 
             if (o < end) keys[o] = ((uint64_t)((int64_t)tu * tiles_v + tv) << 32) | (uint64_t)i;
 }
 
-// tile_start[t] = first sorted entry of tile t (t in [0, ntiles])
-__global__ __launch_bounds__(256) void transfer_tiles(const uint64_t *__restrict__ keys, int64_t n, int64_t ntiles,
-                                                      int32_t *__restrict__ tile_start) {
-    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (c > ntiles) return;
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)(keys[mid] >> 32) < c) lo = mid + 1; else hi = mid;
-    }
-    tile_start[c] = (int32_t)lo;
-}
-
 struct GatherArgs {
-    Nodes nd;
+    Nodes<2> nd;
     const double *pu, *pv, *dp, *y0, *ih, *sf;
     const uint64_t *entries;       // (tile << 32 | depth rank), tile-major, a tile's in depth order
     const int32_t *tile_start;     // null: no particle reaches a node
@@ -317,7 +247,7 @@ __global__ __launch_bounds__(GT) void transfer_gather(GatherArgs A) {
     __shared__ double pdt[PC], pa[PC];
     __shared__ uint16_t ppair[PC];                             // record of the stage << 6 | lane; PSKIP: p >= 2
 
-    const Nodes &nd = A.nd;
+    const Nodes<2> &nd = A.nd;
     const int t = threadIdx.x;
     const int tu = blockIdx.x / A.tiles_v, tv = blockIdx.x % A.tiles_v;
     const int iu = tu * TU + t / TV, iv = tv * TV + t % TV;
@@ -428,17 +358,7 @@ int transfer_run(sph_ctx *c, const sph_transfer_desc *d, const double *source, c
         return arg_error(c, who, "source must be given with SPH_TRANSFER_VALUES and only then");
     if ((d->kappa == SPH_TRANSFER_VALUES) != (kappa != nullptr))
         return arg_error(c, who, "kappa must be given with SPH_TRANSFER_VALUES and only then");
-    {   // rows orthonormal, right-handed
-        const double *r = d->rot;
-        bool ok = true;
-        for (int a = 0; a < 3; a++)
-            for (int b = a; b < 3; b++) {
-                const double dot = (r[3 * a] * r[3 * b] + r[3 * a + 1] * r[3 * b + 1]) + r[3 * a + 2] * r[3 * b + 2];
-                ok = ok && std::fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-12;
-            }
-        const double det = r[0] * (r[4] * r[8] - r[5] * r[7]) - r[1] * (r[3] * r[8] - r[5] * r[6]) + r[2] * (r[3] * r[7] - r[4] * r[6]);
-        if (!(ok && std::fabs(det - 1.0) <= 1e-12)) return arg_error(c, who, "rot must be orthonormal and right-handed within 1e-12");
-    }
+    if (!check_rot(d->rot)) return arg_error(c, who, "rot must be orthonormal and right-handed within 1e-12");
     for (int32_t id : {d->source, d->kappa})
         if (id >= 0 && !field_ready(*c, c->variable, id)) {
             c->err = "sph_transfer: a field named by source or kappa is stale (sph_download_field would refuse it)";
@@ -449,22 +369,12 @@ int transfer_run(sph_ctx *c, const sph_transfer_desc *d, const double *source, c
     if (ntiles > 0x7fffffff) return arg_error(c, who, "too many image nodes");
 
     hipStream_t st = c->stream;
-    Sel s{};
+    const Sel s = make_sel(c, d->clip_lo, d->clip_hi, d->h);
     Frame fr{};
-    for (int a = 0; a < 3; a++) { s.clip_lo[a] = d->clip_lo[a]; s.clip_hi[a] = d->clip_hi[a]; fr.centre[a] = d->centre[a]; }
+    for (int a = 0; a < 3; a++) fr.centre[a] = d->centre[a];
     for (int a = 0; a < 9; a++) fr.rot[a] = d->rot[a];
-    s.h = d->h > 0.0 ? d->h : (c->variable ? 0.0 : c->p.h);
-    s.hf = c->variable ? c->f[SPH_F_H] : nullptr;
-    s.orig = c->orig;
-    s.n_slots = c->cap > 0 ? c->n_slots : 0;
-    s.n_owned = (int32_t)c->n_owned;
-    Nodes nd{};
-    nd.n[0] = d->n_u; nd.n[1] = d->n_v;
-    for (int a = 0; a < 2; a++) {
-        nd.lo[a] = d->lo[a];
-        nd.hi[a] = nd.n[a] == 1 ? d->lo[a] : d->hi[a];             // a single node sits at lo
-        if (nd.n[a] > 1) nd.step[a] = (nd.hi[a] - nd.lo[a]) / (double)(nd.n[a] - 1);
-    }
+    const int32_t n_uv[2] = {d->n_u, d->n_v};
+    const Nodes<2> nd = make_nodes<2>(d->lo, d->hi, n_uv);
 
     SPH_TRY(analysis_pinned(c));
     // ---- scratch.  It is sized three times (the statistics; the particles; the entries) and may move when it grows: what
@@ -510,18 +420,11 @@ int transfer_run(sph_ctx *c, const sph_transfer_desc *d, const double *source, c
     if (s.n_slots > 0) {
         const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((s.n_slots + RB - 1) / RB, RB_MAX));
         transfer_stats_partial<<<dim3(nb), dim3(RB), 0, st>>>(c->f[SPH_F_X], c->f[SPH_F_Y], c->f[SPH_F_Z], s, K, S, partial);
-        transfer_stats_final<<<dim3(1), dim3(NSTAT * 64), 0, st>>>(partial, nb, stats);
-        SPH_HIP(hipGetLastError());
-        SPH_HIP(hipMemcpyAsync(c->rnd_pinned, stats, NSTAT * sizeof(double), hipMemcpyDeviceToHost, st));
-        SPH_HIP(hipStreamSynchronize(st));
-        for (int k = 0; k < NSTAT; k++) hs[k] = c->rnd_pinned[k];
+        SPH_TRY((stats_read_back<NSTAT, NMIN, NMAX>(c, partial, nb, stats, hs)));
     }
     const int64_t count = (int64_t)hs[2];
     const double h_max = hs[0], h_min = -hs[1];
-    if (count > 0 && !(h_min > 0.0 && std::isfinite(h_max))) {
-        c->err = "sph_transfer: a selected particle has h <= 0 or a non-finite h";
-        return SPH_ERR_STATE;
-    }
+    SPH_TRY(check_h_range(c, who, count, h_max, h_min));
     if (hs[3] > 0.0) return arg_error(c, who, "a selected particle has a negative or non-finite K or a non-finite S");
 
     // ---- read-back 2: the particles that reach a node and the entries of the tile lists -----------------------------------
@@ -618,7 +521,7 @@ int transfer_run(sph_ctx *c, const sph_transfer_desc *d, const double *source, c
             tb = tmp_bytes;
             SPH_HIP(rocprim::radix_sort_keys(tmp, tb, ent, ent_alt, (size_t)nent, 32u, 32u + tbits, st));
         }
-        transfer_tiles<<<dim3((unsigned)((ntiles + 1 + 255) / 256)), dim3(256), 0, st>>>(ent_alt, nent, ntiles, tile_start);
+        start_table<<<dim3((unsigned)((ntiles + 1 + 255) / 256)), dim3(256), 0, st>>>(ent_alt, nent, ntiles, tile_start);
         SPH_HIP(hipGetLastError());
         a.pu = rec; a.pv = rec + cap; a.dp = rec + 2 * cap; a.y0 = rec + 3 * cap; a.ih = rec + 4 * cap; a.sf = rec + 5 * cap;
         a.entries = ent_alt;

@@ -113,7 +113,7 @@ def _resource_usage():
     for line in out.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
         if m:
-            cur = m.group(1) if "transfer_" in m.group(1) else None
+            cur = m.group(1) if any(s in m.group(1) for s in ("transfer_", "stats_final", "start_table")) else None
             if cur:
                 kernels[cur] = {}
             continue
@@ -126,8 +126,8 @@ def _resource_usage():
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 def test_transfer_kernels_fit_the_register_budget():
     k = _resource_usage()
-    names = ("transfer_stats_partial", "transfer_stats_final", "transfer_count", "transfer_select", "transfer_depth_keys",
-             "transfer_records", "transfer_emit", "transfer_tiles", "transfer_gather")
+    names = ("transfer_stats_partial", "stats_final", "transfer_count", "transfer_select", "transfer_depth_keys",
+             "transfer_records", "transfer_emit", "start_table", "transfer_gather")
     for name in names:
         assert sum(name in n for n in k) == 1, name
     assert len(k) == len(names), sorted(k)
