@@ -5,33 +5,22 @@ header, the register budget of the binned kernels, binned.finish, the command li
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_support import c_layout, containing, fortran_links, library, needs_fc, needs_hipcc, resource_usage
 import binned_ref
 from conftest import ROOT
 
-FC = shutil.which("amdflang") or "/opt/rocm/bin/amdflang"
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "summersph_amd", "csrc")
 FIELDS = ["lo", "hi", "axis", "n", "n_axes", "n_q", "q", "weight", "n_rows", "flags", "reserved"]
 SPH_ERR_ARG = 1
-
-
-def _library():
-    from summersph_amd import capi
-    if not os.path.exists(capi.LIB_PATH):
-        subprocess.run(["make", "-C", CSRC], check=True, stdout=subprocess.DEVNULL)
-    return capi.LIB_PATH
 
 
 @pytest.fixture(scope="module")
 def capi():
     from summersph_amd import capi as m
-    _library()
+    library()
     m.load()
     return m
 
@@ -150,18 +139,11 @@ def test_python_descriptor_helper(capi):
 
 # ---- 3. the ABI mirrors ----------------------------------------------------------------------------------------------------
 def test_descriptor_layout_and_symbols(capi, tmp_path):
-    src = tmp_path / "layout.c"
     consts = ["SPH_BINNED_MAX_Q", "SPH_BINNED_ROW(0)", "SPH_BINNED_ROW(15)", "SPH_BINNED_W_ONE", "SPH_BINNED_W_MASS",
               "SPH_BINNED_W_VOLUME", "SPH_BINNED_LOG0", "SPH_BINNED_LOG1", "SPH_BINNED_EDGES0", "SPH_BINNED_EDGES1",
               "SPH_BINNED_SQUARES", "SPH_BINNED_SKIP_NAN"]
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "summersph.h"\nint main(void) {\n'
-                   '  printf("size %zu\\n", sizeof(sph_binned_desc));\n' +
-                   "".join(f'  printf("{f} %zu\\n", offsetof(sph_binned_desc, {f}));\n' for f in FIELDS) +
-                   '  printf("consts' + " %d" * len(consts) + '\\n", ' + ", ".join(consts) + ');\n'
-                   '  printf("abi %d\\n", SPH_ABI_VERSION);\n  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = c_layout(tmp_path, "sph_binned_desc", FIELDS,
+                   ['printf("consts' + " %d" * len(consts) + '\\n", ' + ", ".join(consts) + ');', 'printf("abi %d\\n", SPH_ABI_VERSION);'])
     assert int(got["size"]) == C.sizeof(capi.BinnedDesc) == 112
     for f in FIELDS:
         assert int(got[f]) == getattr(capi.BinnedDesc, f).offset, f
@@ -169,7 +151,7 @@ def test_descriptor_layout_and_symbols(capi, tmp_path):
             capi.BINNED_LOG0, capi.BINNED_LOG1, capi.BINNED_EDGES0, capi.BINNED_EDGES1, capi.BINNED_SQUARES, capi.BINNED_SKIP_NAN]
     assert got["consts"] == " ".join(str(v) for v in mine) == "8 -1 -16 0 1 2 1 2 4 8 16 32"
     assert got["abi"] == "1"                                        # the change is additive
-    lib = C.CDLL(_library())
+    lib = C.CDLL(library())
     for s in ("sph_binned", "sph_binned_dev", "sph_binned_edges"):
         assert s in capi.SYMBOLS and hasattr(lib, s), s
     binding = open(os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")).read()
@@ -177,11 +159,9 @@ def test_descriptor_layout_and_symbols(capi, tmp_path):
     assert re.search(r"SPH_BINNED_LOG0 = 1, SPH_BINNED_LOG1 = 2, SPH_BINNED_EDGES0 = 4, SPH_BINNED_EDGES1 = 8", binding)
 
 
-@pytest.mark.skipif(not os.path.exists(FC), reason="needs amdflang")
+@needs_fc
 def test_fortran_binding_compiles_and_links(tmp_path):
-    lib = _library()
-    caller = tmp_path / "binned_caller.f90"
-    caller.write_text("""program binned_caller
+    fortran_links(tmp_path, "binned_caller", """program binned_caller
   use, intrinsic :: iso_c_binding
   use sph_hip_binding
   implicit none
@@ -214,34 +194,12 @@ def test_fortran_binding_compiles_and_links(tmp_path):
   print *, st, edge
 end program binned_caller
 """)
-    binding = os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")
-    exe = tmp_path / "binned_caller"
-    subprocess.run([FC, "-O1", binding, str(caller), "-L" + os.path.dirname(lib), "-lsummersph_hip",
-                    "-Wl,-rpath," + os.path.dirname(lib), "-o", str(exe)], check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
-    assert exe.exists()
 
 
 # ---- 4. the kernels' resources ---------------------------------------------------------------------------------------------
-def _resource_usage():
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "binned.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, check=True, capture_output=True, text=True).stderr
-    kernels, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1) if "binned_" in m.group(1) else None
-            if cur:
-                kernels[cur] = {}
-            continue
-        m = re.search(r"remark: +([^:\[]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if cur and m:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_binned_kernels_fit_the_register_budget():
-    k = _resource_usage()
+    k = resource_usage("binned.hip", containing("binned_"))
     for name, count in (("binned_keys", 1), ("binned_starts", 1), ("binned_pieces", 6), ("binned_final", 1)):
         assert sum(name in n for n in k) == count, (name, sorted(k))
     for name, r in k.items():

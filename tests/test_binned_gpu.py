@@ -17,19 +17,13 @@ import pytest
 import binned_ref
 import profile_ref
 from conftest import ROOT, rel_err
+from gpu_support import capi, make_context
 from summersph_amd import ic, txtio
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
 SPH_ERR_ARG, SPH_ERR_STATE = 1, 5
 STATE = "x y z vx vy vz u m alpha".split()
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
 
 
 def _disc(n, seed, variable=False):
@@ -42,13 +36,6 @@ def _disc(n, seed, variable=False):
     gas["vz"] = rng.normal(0.0, 0.05, gas["x"].size)
     gas["vx"] = gas["vx"] + rng.normal(0.0, 0.02, gas["x"].size)
     return gas, sinks
-
-
-def _ctx(capi, gas, sinks, variable=False, flags=0):
-    ctx = capi.Context(device=0, variable=variable, **({"flags": flags} if flags else {}))
-    ctx.upload(gas)
-    ctx.set_sinks(sinks)
-    return ctx
 
 
 def _counts(c):
@@ -100,7 +87,7 @@ def _check(capi, ctx, axes, bins, values=None, exact=False, owned=None, **kw):
 @pytest.fixture(scope="module")
 def disc(capi):
     gas, sinks = _disc(20000, 5)
-    ctx = _ctx(capi, gas, sinks)
+    ctx = make_context(capi, gas, sinks)
     ctx.density()
     R = np.sqrt(gas["x"] * gas["x"] + gas["y"] * gas["y"])
     yield ctx, gas, R
@@ -135,7 +122,7 @@ def test_parity_two_axes(capi, disc, weight, q, squares):
 
 def test_parity_variable_h(capi):
     gas, sinks = _disc(6000, 9, variable=True)
-    ctx = _ctx(capi, gas, sinks, variable=True)
+    ctx = make_context(capi, gas, sinks, variable=True)
     h = gas["h"]
     _check(capi, ctx, "h", 10, ranges=(float(h.min()), float(np.nextafter(h.max(), np.inf))), q=("u", "h"), squares=True)
     ctx.density()
@@ -158,7 +145,7 @@ def integer_set(capi):
     gas["m"] = np.full(n, 2.0)                                            # w A and w A A are exact
     label = rng.permutation(np.repeat(np.arange(len(POPULATIONS)), POPULATIONS)).astype(np.float64)
     values = np.stack([label, rng.integers(-50, 51, n).astype(np.float64), rng.integers(0, 100, n).astype(np.float64)])
-    ctx = _ctx(capi, gas, sinks)
+    ctx = make_context(capi, gas, sinks)
     yield ctx, values
     ctx.close()
 
@@ -197,12 +184,12 @@ def test_order_rule_bitwise(capi):
     R = np.sqrt(gas["x"] * gas["x"] + gas["y"] * gas["y"])[None, :]
     args = dict(axes=(capi.binned_row(0), "u"), bins=(16, 3), ranges=((5.0, 70.0), (0.1, 0.5)), log=(0,), q=("u", "alpha", "vz"),
                 squares=True)
-    a = _ctx(capi, gas, sinks)
+    a = make_context(capi, gas, sinks)
     s0, c0 = a.binned(values=R, **args)                        # upload order
     a.density()                                                # cell-sorted
     s1, c1 = a.binned(values=R, **args)
     s2, c2 = a.binned(values=R, **args)
-    b = _ctx(capi, gas, sinks, flags=capi.FLAG_HASHED_GRID)
+    b = make_context(capi, gas, sinks, flags=capi.FLAG_HASHED_GRID)
     b.density()
     s3, c3 = b.binned(values=R, **args)
     s4, c4 = a.binned(values=torch.from_numpy(R).to("cuda:0"), device=True, **args)
@@ -221,7 +208,7 @@ def test_ring_sums_are_bitwise_sph_profile(capi, log):
     r0, r1, nr = 10.0, 60.0, 12
     keep = ~profile_ref.edge_margin(gas, r0, r1, nr, 1, log)
     gas = {k: (v[keep] if isinstance(v, np.ndarray) and v.shape == keep.shape else v) for k, v in gas.items()}
-    ctx = _ctx(capi, gas, sinks)
+    ctx = make_context(capi, gas, sinks)
     _, prof = ctx.profile(r0, r1, nr, log=log, sums_only=True)          # about the origin, normal z^
     R = np.sqrt(gas["x"] * gas["x"] + gas["y"] * gas["y"])[None, :]
     got, counts = ctx.binned(capi.binned_row(0), nr, edges=terms.ring_edges(r0, r1, nr, log), q=("u", "alpha"), weight="mass",
@@ -241,7 +228,7 @@ def test_force_terms_rows_reduce_to_ring_heating(capi):
     R = np.sqrt(gas["x"] * gas["x"] + gas["y"] * gas["y"])
     near = np.min(np.abs(R[:, None] - edges[None, :]), axis=1) <= 1e-10 * R      # the device's R may round the other way
     gas = {k: (v[~near] if isinstance(v, np.ndarray) and v.shape == near.shape else v) for k, v in gas.items()}
-    ctx = _ctx(capi, gas, sinks)
+    ctx = make_context(capi, gas, sinks)
     ctx.density()
     rows = ctx.force_terms(device=True)
     assert isinstance(rows, torch.Tensor)
@@ -265,7 +252,7 @@ def test_force_terms_rows_reduce_to_ring_heating(capi):
 def test_gradients_rows_on_a_clipped_target_set(capi):
     import torch
     gas, sinks = _disc(20000, 21)
-    ctx = _ctx(capi, gas, sinks)
+    ctx = make_context(capi, gas, sinks)
     clip = ((-40.0, -40.0, -np.inf), (40.0, 25.0, np.inf))
     grad, _, (n_targets, _) = ctx.gradients(("vx", "vy", "vz"), clip=clip, device=True)
     div = (grad[0, 0] + grad[1, 1]) + grad[2, 2]
@@ -290,7 +277,7 @@ def test_gradients_rows_on_a_clipped_target_set(capi):
 # ---- the selection rule -------------------------------------------------------------------------------------------------------------
 def test_ghosts_are_excluded(capi):
     gas, sinks = _disc(20000, 23)
-    ctx = _ctx(capi, gas, sinks)
+    ctx = make_context(capi, gas, sinks)
     ctx.set_owned(15000)
     owned = np.arange(gas["x"].size) < 15000
     got, counts = _check(capi, ctx, "u", 7, ranges=(0.15, 0.45), q=("alpha",), owned=owned)
@@ -301,7 +288,7 @@ def test_ghosts_are_excluded(capi):
 def test_full_coverage_and_cull(capi):
     gas, sinks = _disc(20000, 23)
     sinks = dict(sinks); sinks["radius"] = np.array([15.0])   # accretes the inner edge
-    ctx = _ctx(capi, gas, sinks)
+    ctx = make_context(capi, gas, sinks)
     for step in range(2):
         got, counts = _check(capi, ctx, ("u", "alpha"), (5, 4), ranges=((0.0, 1.0), (0.0, 2.0)), q=("m",), weight="one")
         assert counts == (ctx.n, 0, 0) and got[..., 0].sum() == ctx.n
@@ -346,7 +333,7 @@ def test_empty_context_empty_selection_and_stale_rho(capi):
     assert not got.cpu().numpy().any() and _counts(counts) == (0, 0, 0)
     ctx.close()
     gas, sinks = _disc(3000, 37)
-    ctx = _ctx(capi, gas, sinks)
+    ctx = make_context(capi, gas, sinks)
     got, counts = ctx.binned("u", 4, ranges=(5.0, 6.0), q=("alpha",))
     assert not got.any() and counts == (0, ctx.n, 0)
     for kw in (dict(axes="rho", bins=4, ranges=(1e-9, 1.0)), dict(axes="u", bins=4, ranges=(0.0, 1.0), q=("P",)),
@@ -361,7 +348,7 @@ def test_empty_context_empty_selection_and_stale_rho(capi):
 
 def test_errors_that_need_a_context(capi):
     gas, sinks = _disc(3000, 37)
-    ctx = _ctx(capi, gas, sinks)
+    ctx = make_context(capi, gas, sinks)
     lib, n = ctx.lib, ctx.n
     d, _ = capi.binned_desc("u", 4, (0.0, 1.0), q=("alpha",))
     buf, vals = np.full(4 * 3, -7.0), np.zeros((2, n))
@@ -391,7 +378,7 @@ def test_no_side_effects(capi):
     gas, sinks = _disc(8000, 29)
     runs = []
     for with_binned in (False, True):
-        ctx = _ctx(capi, gas, sinks)
+        ctx = make_context(capi, gas, sinks)
         dt, t = 1e-3, 0.0
         statsl = []
         for _ in range(10):
@@ -431,7 +418,7 @@ def test_cli_round_trip(capi, tmp_path):
     z = np.load(out)
     g2, s2 = ic.split_rows(np.concatenate([rows[:, :8], srows], axis=0))
     g2["alpha"] = rows[:, 8]
-    ctx = _ctx(capi, g2, s2)
+    ctx = make_context(capi, g2, s2)
     ctx.density()
     s, c = ctx.binned(("rho", "u"), (16, 12), ranges=[tuple(v) for v in info["ranges"]], log=(0, 1), q=("alpha",), squares=True)
     assert np.array_equal(z["sums"], s) and tuple(z["counts"]) == c == (3000, 0, 0)

@@ -4,31 +4,21 @@ command line's parsing."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_support import c_layout, containing, fortran_links, needs_fc, needs_hipcc, resource_usage
 from conftest import ROOT
 import bound_ref
 
-FC = shutil.which("amdflang") or "/opt/rocm/bin/amdflang"
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "summersph_amd", "csrc")
 FIELDS = ["h", "soft2", "min_members", "max_members", "max_rounds", "flags", "reserved"]
 
 
 def test_bound_desc_layout_matches_header(tmp_path):
     from summersph_amd import capi
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "summersph.h"\nint main(void) {\n'
-                   '  printf("size %zu\\n", sizeof(sph_bound_desc));\n' +
-                   "".join(f'  printf("{f} %zu\\n", offsetof(sph_bound_desc, {f}));\n' for f in FIELDS) +
-                   '  printf("consts %d %d %d\\n", SPH_BOUND_THERMAL, SPH_BOUND_NCOL, SPH_ABI_VERSION);\n  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = c_layout(tmp_path, "sph_bound_desc", FIELDS,
+                   ['printf("consts %d %d %d\\n", SPH_BOUND_THERMAL, SPH_BOUND_NCOL, SPH_ABI_VERSION);'])
     assert int(got["size"]) == ctypes.sizeof(capi.BoundDesc) == 48
     for f in FIELDS:
         assert int(got[f]) == getattr(capi.BoundDesc, f).offset, f
@@ -46,13 +36,9 @@ def test_bound_desc_layout_matches_header(tmp_path):
     assert t["N0"].tolist() == [0.0, 24.0] and t["e_most_bound"].tolist() == [23.0, 47.0]
 
 
-@pytest.mark.skipif(not os.path.exists(FC), reason="needs amdflang")
+@needs_fc
 def test_fortran_binding_compiles_and_links(tmp_path):
-    lib = os.path.join(ROOT, "summersph_amd", "libsummersph_hip.so")
-    if not os.path.exists(lib):
-        subprocess.run(["make", "-C", CSRC], check=True, stdout=subprocess.DEVNULL)
-    caller = tmp_path / "bound_caller.f90"
-    caller.write_text("""program bound_caller
+    fortran_links(tmp_path, "bound_caller", """program bound_caller
   use, intrinsic :: iso_c_binding
   use sph_hip_binding
   implicit none
@@ -79,33 +65,11 @@ def test_fortran_binding_compiles_and_links(tmp_path):
   print *, st
 end program bound_caller
 """)
-    binding = os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")
-    exe = tmp_path / "bound_caller"
-    subprocess.run([FC, "-O1", binding, str(caller), "-L" + os.path.dirname(lib), "-lsummersph_hip",
-                    "-Wl,-rpath," + os.path.dirname(lib), "-o", str(exe)], check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
-    assert exe.exists()
 
 
-def _resource_usage():
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "bound.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, check=True, capture_output=True, text=True).stderr
-    kernels, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1) if "bound_" in m.group(1) else None
-            if cur:
-                kernels[cur] = {}
-            continue
-        m = re.search(r"remark: +([^:\[]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if cur and m:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_bound_kernels_fit_the_register_budget():
-    k = _resource_usage()
+    k = resource_usage("bound.hip", containing("bound_"))
     for name in ("bound_fill", "bound_keys", "bound_starts", "bound_gather", "bound_init", "bound_momE", "bound_mom_final",
                  "bound_plan", "bound_pairs", "bound_sumsE", "bound_sums_final", "bound_scatter", "bound_counts"):
         assert sum(name in n for n in k) == 1, name

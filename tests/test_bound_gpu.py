@@ -20,6 +20,7 @@ import pytest
 
 from conftest import ROOT
 import bound_ref
+from gpu_support import capi, make_context
 from summersph_amd import ic, txtio
 
 pytestmark = pytest.mark.gpu
@@ -28,13 +29,6 @@ SPH_ERR_ARG = 1
 SPH_ERR_STATE = 5
 H_FIXED = 0.3
 FIELDS = "x y z vx vy vz u m".split()
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
 
 
 @functools.lru_cache(maxsize=None)
@@ -52,15 +46,8 @@ def _ref(variable, kw):
 
 
 def _ctx(capi, gas, sinks, n_owned, variable=False, flags=0):
-    kw = {} if variable else {"h": H_FIXED}
-    if flags:
-        kw["flags"] = flags
-    ctx = capi.Context(device=0, variable=variable, **kw)
-    ctx.upload(gas)
-    ctx.set_sinks(sinks)
-    if n_owned != gas["x"].size:
-        ctx.set_owned(n_owned)
-    return ctx
+    return make_context(capi, gas, sinks, variable=variable, flags=flags, n_owned=None if n_owned == gas["x"].size else n_owned,
+                        **({} if variable else {"h": H_FIXED}))
 
 
 def _blob_ctx(capi, variable=False, flags=0):

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, rel_err
+from gpu_support import capi
 from summersph_amd import ic
 from test_parity_gpu import EVAL_TOL
 
@@ -27,13 +28,6 @@ DERIVED = ["rho", "P", "c", "ax", "ay", "az", "du", "dalpha"]
 PROBES = ["forces", "kick", "next_dt", "refresh_eos", "update_h", "forces_part2"]
 COUNTERS = ["grid_builds", "nlist_builds", "nlist_reflags", "density_passes", "force_passes"]
 DT = 1e-3
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
 
 
 def case_kw(capi, case):

@@ -10,18 +10,12 @@ terms are added in sequence).  Nodes with no particle within 2 h (1 + 1e-12) mus
 import numpy as np
 import pytest
 
+from gpu_support import capi
 import image_ref
 import image_sets as S
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
 
 
 def _run(ctx, c, a):

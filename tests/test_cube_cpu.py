@@ -5,34 +5,23 @@ the command line's parsing."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_support import CSRC, c_layout, containing, fortran_links, needs_fc, needs_hipcc, resource_usage
 from conftest import ROOT
 import cube_ref
 from summersph_amd import cube as cb
 
-FC = shutil.which("amdflang") or "/opt/rocm/bin/amdflang"
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "summersph_amd", "csrc")
 FIELDS = ["rot", "centre", "v_ref", "lo", "hi", "clip_lo", "clip_hi", "h", "v0", "dv", "sigma_scale", "sigma_floor", "n_u", "n_v",
           "n_chan", "flags", "reserved"]
 
 
 def test_cube_desc_layout_matches_header(tmp_path):
     from summersph_amd import capi
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "summersph.h"\nint main(void) {\n'
-                   '  printf("size %zu\\n", sizeof(sph_cube_desc));\n' +
-                   "".join(f'  printf("{f} %zu\\n", offsetof(sph_cube_desc, {f}));\n' for f in FIELDS) +
-                   '  printf("consts %d\\n", SPH_CUBE_PER_VELOCITY);\n  printf("abi %d\\n", SPH_ABI_VERSION);\n'
-                   '  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = c_layout(tmp_path, "sph_cube_desc", FIELDS,
+                   ['printf("consts %d\\n", SPH_CUBE_PER_VELOCITY);', 'printf("abi %d\\n", SPH_ABI_VERSION);'])
     assert int(got["size"]) == ctypes.sizeof(capi.CubeDesc) == 264
     for f in FIELDS:
         assert int(got[f]) == getattr(capi.CubeDesc, f).offset, f
@@ -58,13 +47,9 @@ def test_cube_desc_layout_matches_header(tmp_path):
         capi.cube_desc((1, 2, 3), ((0, 0), (1, 1)), 0.0, 1.0, 1)
 
 
-@pytest.mark.skipif(not os.path.exists(FC), reason="needs amdflang")
+@needs_fc
 def test_fortran_binding_compiles_and_links(tmp_path):
-    lib = os.path.join(ROOT, "summersph_amd", "libsummersph_hip.so")
-    if not os.path.exists(lib):
-        subprocess.run(["make", "-C", CSRC], check=True, stdout=subprocess.DEVNULL)
-    caller = tmp_path / "cube_caller.f90"
-    caller.write_text("""program cube_caller
+    fortran_links(tmp_path, "cube_caller", """program cube_caller
   use, intrinsic :: iso_c_binding
   use, intrinsic :: ieee_arithmetic
   use sph_hip_binding
@@ -99,33 +84,11 @@ def test_fortran_binding_compiles_and_links(tmp_path):
   print *, st
 end program cube_caller
 """)
-    binding = os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")
-    exe = tmp_path / "cube_caller"
-    subprocess.run([FC, "-O1", binding, str(caller), "-L" + os.path.dirname(lib), "-lsummersph_hip",
-                    "-Wl,-rpath," + os.path.dirname(lib), "-o", str(exe)], check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
-    assert exe.exists()
 
 
-def _resource_usage():
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "cube.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, check=True, capture_output=True, text=True).stderr
-    kernels, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1) if any(s in m.group(1) for s in ("cube_", "stats_final", "start_table")) else None
-            if cur:
-                kernels[cur] = {}
-            continue
-        m = re.search(r"remark: +([^:\[]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if cur and m:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_cube_kernels_fit_the_register_budget():
-    k = _resource_usage()
+    k = resource_usage("cube.hip", containing("cube_", "stats_final", "start_table"))
     for name in ("cube_stats_partial", "stats_final", "cube_select", "start_table", "cube_records", "cube_gather"):
         assert sum(name in n for n in k) == 1, name
     assert len(k) == 6, sorted(k)

@@ -6,6 +6,7 @@ with a physical check; and the command line.
 Bound: every voxel within 1e-12 of the cube's largest magnitude (global, not per channel: a difference of erf values
 carries an absolute error of about 1e-16 of the column term, which is arbitrarily large relative to a far-wing channel)."""
 import ctypes as C
+import functools
 import json
 import subprocess
 import sys
@@ -13,8 +14,9 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_golden
+from conftest import ROOT
 import cube_ref
+from gpu_support import capi, golden_gas, make_context
 from summersph_amd import cube as cb
 from summersph_amd import ic, txtio
 
@@ -25,25 +27,7 @@ TOL = 1e-12
 ALONG_X = np.array([[0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [1.0, 0.0, 0.0]])       # u^ = y^, v^ = z^, w^ = x^
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
-def _ctx(capi, gas, sinks=None, variable=False, density=True):
-    ctx = capi.Context(device=0, variable=variable)
-    ctx.upload(gas)
-    if sinks is not None:
-        ctx.set_sinks(sinks)
-    if density:
-        ctx.density()
-    return ctx
-
-
-def _golden_gas(name):
-    return ic.split_rows(load_golden(name)["ic"])
+_ctx = functools.partial(make_context, density=True)      # every call here reads rho unless it says density=False
 
 
 def _set(capi, name, density=True):
@@ -53,7 +37,7 @@ def _set(capi, name, density=True):
     if name == "discvar20000":
         gas, sinks = ic.split_rows(ic.keplerian_disc_var(20000))
         return _ctx(capi, gas, sinks, variable=True, density=density)
-    gas, sinks = _golden_gas(name)
+    gas, sinks = golden_gas(name)
     return _ctx(capi, gas, sinks, variable="discv" in name, density=density)
 
 
@@ -144,7 +128,7 @@ def test_parity_with_the_restatement(capi, name):
 
 
 def test_line_profile_regimes(capi):
-    gas, sinks = _golden_gas("disc3000_eval")
+    gas, sinks = golden_gas("disc3000_eval")
     gas = {k: v.copy() for k, v in gas.items()}
     n_chan, v0, dv = 16, -1.0, 0.125
     e = cube_ref.edges(v0, dv, n_chan)
@@ -211,7 +195,7 @@ def test_mass_in_velocity(capi):
 
 
 def test_footprint_edges(capi):
-    gas, sinks = _golden_gas("disc3000_eval")
+    gas, sinks = golden_gas("disc3000_eval")
     gas = {k: v.copy() for k, v in gas.items()}
     hh = 0.5
     # nodes on the integers of [0, 8] x [0, 6]; the first particles are placed by hand

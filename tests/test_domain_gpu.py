@@ -5,17 +5,11 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
+from gpu_support import capi
 from summersph_amd import ic
 
 pytestmark = pytest.mark.gpu
 STATE = "x y z vx vy vz u m alpha".split()
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
 
 
 @pytest.fixture(scope="module")

@@ -3,18 +3,14 @@ the softening potential against the force's grav_table polynomial, the numpy res
 reference's own trajectory fixture, and the command line's parsing."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from abi_support import containing, fortran_links, needs_fc, needs_hipcc, resource_usage
 from conftest import ROOT, load_golden
 import energy_ref
-
-FC = shutil.which("amdflang") or "/opt/rocm/bin/amdflang"
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "summersph_amd", "csrc")
 
 
 def test_header_constant_and_prototypes_match_capi(tmp_path):
@@ -37,13 +33,9 @@ def test_header_constant_and_prototypes_match_capi(tmp_path):
     assert re.search(r"SPH_ENERGY_NSUM = 28", binding)
 
 
-@pytest.mark.skipif(not os.path.exists(FC), reason="needs amdflang")
+@needs_fc
 def test_fortran_binding_compiles_and_links(tmp_path):
-    lib = os.path.join(ROOT, "summersph_amd", "libsummersph_hip.so")
-    if not os.path.exists(lib):
-        subprocess.run(["make", "-C", CSRC], check=True, stdout=subprocess.DEVNULL)
-    caller = tmp_path / "energy_caller.f90"
-    caller.write_text("""program energy_caller
+    fortran_links(tmp_path, "energy_caller", """program energy_caller
   use, intrinsic :: iso_c_binding
   use sph_hip_binding
   implicit none
@@ -59,34 +51,12 @@ def test_fortran_binding_compiles_and_links(tmp_path):
   print *, 'E = ', sums(12) + sums(13) + sums(14) + sums(15) + sums(27) + sums(28)
 end program energy_caller
 """)
-    binding = os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")
-    exe = tmp_path / "energy_caller"
-    subprocess.run([FC, "-O1", binding, str(caller), "-L" + os.path.dirname(lib), "-lsummersph_hip",
-                    "-Wl,-rpath," + os.path.dirname(lib), "-o", str(exe)], check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
-    assert exe.exists()
 
 
-def _resource_usage(src, pattern):
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", src, "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, check=True, capture_output=True, text=True).stderr
-    kernels, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1) if re.search(pattern, m.group(1)) else None
-            if cur:
-                kernels[cur] = {}
-            continue
-        m = re.search(r"remark: +([^:\[]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if cur and m:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_energy_kernels_fit_the_register_budget():
-    k = _resource_usage("energy.hip", "energy_")
-    k.update(_resource_usage("gravity.hip", "grav_potential_wave"))
+    k = resource_usage("energy.hip", containing("energy_"))
+    k.update(resource_usage("gravity.hip", containing("grav_potential_wave")))
     for name in ("energy_stage", "energy_box", "energy_pieces", "energy_final", "grav_potential_wave"):
         assert sum(name in n for n in k) == 1, name
     for name, r in k.items():

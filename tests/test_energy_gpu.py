@@ -12,6 +12,7 @@ import pytest
 
 from conftest import ROOT, load_golden
 import energy_ref
+from gpu_support import capi, make_context, var_params, with_variable_h
 from summersph_amd import ic, txtio
 
 pytestmark = pytest.mark.gpu
@@ -23,26 +24,8 @@ BH_TOL = 1e-2
 TINY_THETA = 1e-9
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
 def _ctx(capi, gas, sinks, variable=False, flags=0, **kw):
-    if variable:
-        flags |= capi.FLAG_VARIABLE_H
-    ctx = capi.Context(device=0, variable=variable, **({"flags": flags} if flags else {}), **kw)
-    ctx.upload(gas)
-    if sinks is not None:
-        ctx.set_sinks(sinks)
-    return ctx
-
-
-def _var_kw(g):
-    gamma, eta, tol, maxlen, scale = g["params"]
-    return dict(gamma=gamma, gamma_m1=gamma - 1.0, eta=eta, h_tol=tol, h_max_length=maxlen, dt_scale=scale)
+    return make_context(capi, gas, sinks, variable=variable, flags=with_variable_h(capi, flags, variable), **kw)
 
 
 def _cmp_sums(got, want, scale, tol, which=range(energy_ref.NSUM)):
@@ -67,7 +50,7 @@ def test_sink_terms_without_self_gravity(capi, name):
     g = load_golden(name)
     variable = name.startswith("discv")
     gas, sinks = (ic.split_rows_var if variable else ic.split_rows)(g["ic"])
-    ctx = _ctx(capi, gas, sinks, variable, **(_var_kw(g) if variable else {}))
+    ctx = _ctx(capi, gas, sinks, variable, **(var_params(g) if variable else {}))
     e = ctx.energy(phi=True)
     h = gas["h"] if variable else ctx.params.h
     want, phi, sc = energy_ref.energy_sums(gas, sinks, ctx.params.G, h, self_gravity=False, scales=True)
@@ -86,7 +69,7 @@ def test_exact_self_potential_is_the_direct_sum(capi, case):
     variable = case.startswith("sinkcv")
     g = load_golden("sinkcv1500_traj" if variable else "disc3000_traj")
     gas, sinks = energy_ref.rows_to_dicts(g, "full_s3_" if variable else "full_s5_", variable)
-    ctx = _ctx(capi, gas, sinks, variable, flags=capi.FLAG_SELF_GRAVITY, theta=TINY_THETA, **(_var_kw(g) if variable else {}))
+    ctx = _ctx(capi, gas, sinks, variable, flags=capi.FLAG_SELF_GRAVITY, theta=TINY_THETA, **(var_params(g) if variable else {}))
     e = ctx.energy(phi=True)
     h = gas["h"] if variable else ctx.params.h
     want, phi, sc = energy_ref.energy_sums(gas, sinks, ctx.params.G, h, self_gravity=True, scales=True)
@@ -246,7 +229,7 @@ def test_no_side_effects_on_a_run(capi, case):
     if case == "variable":
         g = load_golden("discv3000_traj")
         gas, sinks = ic.split_rows_var(g["ic"])
-        flags, variable, kw = capi.FLAG_SELF_GRAVITY, True, _var_kw(g)
+        flags, variable, kw = capi.FLAG_SELF_GRAVITY, True, var_params(g)
     else:
         g = load_golden("acc2000_traj" if case == "sg_acc" else "disc3000_traj")
         gas, sinks = ic.split_rows(g["ic"])

@@ -8,18 +8,15 @@ references; the shares of that bar they use are printed (measured: fixed-h sets 
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_support import c_layout, fortran_links, library, needs_fc
 import force_terms_ref as FR
 import force_terms_sets as TS
 import varh_ref as VR
 from conftest import ROOT, load_golden
-
-FC = shutil.which("amdflang") or "/opt/rocm/bin/amdflang"
 
 TOTALS = ("ax", "ay", "az", "du", "dalpha")
 
@@ -193,25 +190,10 @@ def test_command_line_arguments():
 
 
 # ---- 4. the binding ---------------------------------------------------------------------------------------------------------
-def _library():
-    from summersph_amd import capi
-    if not os.path.exists(capi.LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "summersph_amd", "csrc")], check=True, stdout=subprocess.DEVNULL)
-    return capi.LIB_PATH
-
-
 def test_descriptor_layout_rows_and_symbols(tmp_path):
     from summersph_amd import capi
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "summersph.h"\nint main(void) {\n'
-                   '  printf("size %zu\\n", sizeof(sph_force_terms_desc));\n'
-                   '  printf("flags %zu\\n", offsetof(sph_force_terms_desc, flags));\n'
-                   '  printf("reserved %zu\\n", offsetof(sph_force_terms_desc, reserved));\n'
-                   '  printf("consts %d %d\\n", SPH_TERMS_NROW, SPH_TERMS_SKIP_GAS_GRAVITY);\n'
-                   '  printf("abi %d\\n", SPH_ABI_VERSION);\n  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = c_layout(tmp_path, "sph_force_terms_desc", ["flags", "reserved"],
+                   ['printf("consts %d %d\\n", SPH_TERMS_NROW, SPH_TERMS_SKIP_GAS_GRAVITY);', 'printf("abi %d\\n", SPH_ABI_VERSION);'])
     assert int(got["size"]) == C.sizeof(capi.ForceTermsDesc) == 16
     assert int(got["flags"]) == capi.ForceTermsDesc.flags.offset == 0
     assert int(got["reserved"]) == capi.ForceTermsDesc.reserved.offset == 4
@@ -219,7 +201,7 @@ def test_descriptor_layout_rows_and_symbols(tmp_path):
     assert got["abi"] == "1"                                        # the change is additive
     assert len(capi.TERM_ROWS) == 16 == FR.NROW and capi.TERM_ROWS[12:] == ["du_P", "du_V", "dalpha_source", "dalpha_decay"]
     assert "sph_force_terms" in capi.SYMBOLS and "sph_force_terms_dev" in capi.SYMBOLS
-    lib = C.CDLL(_library())
+    lib = C.CDLL(library())
     for s in ("sph_force_terms", "sph_force_terms_dev"):
         assert hasattr(lib, s), s
     assert lib.sph_abi_version() == 1
@@ -227,11 +209,9 @@ def test_descriptor_layout_rows_and_symbols(tmp_path):
     assert re.search(r"SPH_TERMS_NROW = 16, SPH_TERMS_SKIP_GAS_GRAVITY = 1", binding)
 
 
-@pytest.mark.skipif(not os.path.exists(FC), reason="needs amdflang")
+@needs_fc
 def test_fortran_binding_compiles_and_links(tmp_path):
-    lib = _library()
-    caller = tmp_path / "terms_caller.f90"
-    caller.write_text("""program terms_caller
+    fortran_links(tmp_path, "terms_caller", """program terms_caller
   use, intrinsic :: iso_c_binding
   use sph_hip_binding
   implicit none
@@ -249,8 +229,3 @@ def test_fortran_binding_compiles_and_links(tmp_path):
   print *, st
 end program terms_caller
 """)
-    binding = os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")
-    exe = tmp_path / "terms_caller"
-    subprocess.run([FC, "-O1", binding, str(caller), "-L" + os.path.dirname(lib), "-lsummersph_hip",
-                    "-Wl,-rpath," + os.path.dirname(lib), "-o", str(exe)], check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
-    assert exe.exists()

@@ -22,6 +22,7 @@ import force_terms_ref as FR
 import force_terms_sets as TS
 import varh_ref as VR
 from conftest import rel_err
+from gpu_support import capi
 
 pytestmark = pytest.mark.gpu
 
@@ -29,13 +30,6 @@ SPH_ERR_ARG, SPH_ERR_STATE = 1, 5
 RATES = ("ax", "ay", "az", "du", "dalpha")
 STATE = "x y z vx vy vz u alpha".split()
 PAIR_ROWS = list(range(0, 9)) + [12, 13, 14, 15]          # every row the restatement states (9-11: the gravity term)
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
 
 
 @pytest.fixture(scope="module")

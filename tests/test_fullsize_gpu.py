@@ -13,18 +13,12 @@ import numpy as np
 import pytest
 from scipy.spatial import cKDTree
 
+from gpu_support import capi
 from summersph_amd import ic
 
 pytestmark = pytest.mark.gpu
 N = 1_000_000
 H = 2.5
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
 
 
 @pytest.fixture(scope="module")

@@ -7,6 +7,7 @@ tests/test_gradients_gpu.py's _cmp holds rho~ to: the project's rule is used unc
 import numpy as np
 import pytest
 
+from gpu_support import capi, make_context
 import gradients_ref
 import search_sets as S
 from test_gradients_gpu import _cmp
@@ -15,19 +16,8 @@ pytestmark = pytest.mark.gpu
 FIXED_H_DENSITY = [n for n in S.GRADIENT_SETS if n in S.DENSITY_SETS]
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
 def _ctx(capi, s, density=False):
-    ctx = capi.Context(device=0, **s.context_kw())
-    ctx.upload(s.gas)
-    if density:
-        ctx.density()
-    return ctx
+    return make_context(capi, s.gas, density=density, **s.context_kw())
 
 
 WORST = [0.0]

@@ -5,32 +5,22 @@ parsing."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_support import c_layout, containing, fortran_links, needs_fc, needs_hipcc, resource_usage
 from conftest import ROOT, load_golden
 import gradients_ref
 from summersph_amd import ic
 
-FC = shutil.which("amdflang") or "/opt/rocm/bin/amdflang"
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "summersph_amd", "csrc")
 FIELDS = ["clip_lo", "clip_hi", "h", "fields", "n_fields", "flags", "reserved"]
 
 
 def test_gradients_desc_layout_matches_header(tmp_path):
     from summersph_amd import capi
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "summersph.h"\nint main(void) {\n'
-                   '  printf("size %zu\\n", sizeof(sph_gradients_desc));\n' +
-                   "".join(f'  printf("{f} %zu\\n", offsetof(sph_gradients_desc, {f}));\n' for f in FIELDS) +
-                   '  printf("consts %d %d %d\\n", SPH_GRAD_CORRECTED, SPH_GRAD_MAX_FIELDS, SPH_GRAD_VALUES);\n  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = c_layout(tmp_path, "sph_gradients_desc", FIELDS,
+                   ['printf("consts %d %d %d\\n", SPH_GRAD_CORRECTED, SPH_GRAD_MAX_FIELDS, SPH_GRAD_VALUES);'])
     assert int(got["size"]) == ctypes.sizeof(capi.GradientsDesc) == 88
     for f in FIELDS:
         assert int(got[f]) == getattr(capi.GradientsDesc, f).offset, f
@@ -61,13 +51,9 @@ def test_velocity_derivatives_of_a_linear_flow():
     assert np.allclose(v["curl_mag"], np.linalg.norm(v["curl"][:, 0]))
 
 
-@pytest.mark.skipif(not os.path.exists(FC), reason="needs amdflang")
+@needs_fc
 def test_fortran_binding_compiles_and_links(tmp_path):
-    lib = os.path.join(ROOT, "summersph_amd", "libsummersph_hip.so")
-    if not os.path.exists(lib):
-        subprocess.run(["make", "-C", CSRC], check=True, stdout=subprocess.DEVNULL)
-    caller = tmp_path / "grad_caller.f90"
-    caller.write_text("""program grad_caller
+    fortran_links(tmp_path, "grad_caller", """program grad_caller
   use, intrinsic :: iso_c_binding
   use, intrinsic :: ieee_arithmetic
   use sph_hip_binding
@@ -92,33 +78,11 @@ def test_fortran_binding_compiles_and_links(tmp_path):
   print *, st, nt, ns
 end program grad_caller
 """)
-    binding = os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")
-    exe = tmp_path / "grad_caller"
-    subprocess.run([FC, "-O1", binding, str(caller), "-L" + os.path.dirname(lib), "-lsummersph_hip",
-                    "-Wl,-rpath," + os.path.dirname(lib), "-o", str(exe)], check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
-    assert exe.exists()
 
 
-def _resource_usage():
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "gradients.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, check=True, capture_output=True, text=True).stderr
-    kernels, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1) if "grad_" in m.group(1) else None
-            if cur:
-                kernels[cur] = {}
-            continue
-        m = re.search(r"remark: +([^:\[]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if cur and m:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_gradient_kernels_fit_the_register_budget():
-    k = _resource_usage()
+    k = resource_usage("gradients.hip", containing("grad_"))
     for name in ("grad_select", "grad_box", "grad_keys", "grad_gather", "grad_tails"):
         assert sum(name in n for n in k) == 1, name
     walks = [n for n in k if "grad_walk" in n]

@@ -11,7 +11,8 @@ import time
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_golden
+from conftest import ROOT
+from gpu_support import capi, field_positions, golden_gas, make_context, over_defaults, ref_h
 import gradients_ref
 from summersph_amd import ic, txtio
 
@@ -20,36 +21,8 @@ SPH_ERR_ARG = 1
 SPH_ERR_STATE = 5
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
 def _ctx(capi, gas, sinks=None, variable=False, flags=0, density=True):
-    if flags:
-        flags |= capi.default_params(variable).flags
-    ctx = capi.Context(device=0, variable=variable, **({"flags": flags} if flags else {}))
-    ctx.upload(gas)
-    if sinks is not None:
-        ctx.set_sinks(sinks)
-    if density:
-        ctx.density()
-    return ctx
-
-
-def _golden_gas(name):
-    e = load_golden(name)
-    return ic.split_rows(e["ic"])
-
-
-def _pos(ctx):
-    return np.stack([ctx.field("x"), ctx.field("y"), ctx.field("z")], axis=1)
-
-
-def _ref_h(ctx, capi):
-    return ctx.field("h") if ctx.params.flags & capi.FLAG_VARIABLE_H else float(ctx.params.h)
+    return make_context(capi, gas, sinks, variable=variable, flags=over_defaults(capi, flags, variable), density=density)
 
 
 def _cmp(g, rg, rho=None, rrho=None, tol=1e-12, ratio=None):
@@ -83,7 +56,7 @@ def _set(capi, name):
     if name == "discvar20000":
         gas, sinks = ic.split_rows(ic.keplerian_disc_var(20000))
         return _ctx(capi, gas, sinks, variable=True)
-    gas, sinks = _golden_gas(name)
+    gas, sinks = golden_gas(name)
     return _ctx(capi, gas, sinks, variable="discv" in name)
 
 
@@ -91,11 +64,11 @@ def _set(capi, name):
 def test_parity_with_the_restatement(capi, name):
     ctx = _set(capi, name)
     n = ctx.n
-    pos, m = _pos(ctx), ctx.field("m")
+    pos, m = field_positions(ctx), ctx.field("m")
     rng = np.random.default_rng(3)
     vals = np.stack([rng.normal(size=n), pos[:, 0] * pos[:, 1]])
     A = np.stack([ctx.field("vx"), ctx.field("vy"), ctx.field("u"), ctx.field("rho")])
-    h = _ref_h(ctx, capi)
+    h = ref_h(ctx, capi)
     for corrected in (True, False):
         inf = {}
         rg, rr, nt, ns = gradients_ref.gradients(pos, m, np.concatenate([A, vals]), h, corrected=corrected, info=inf)
@@ -120,7 +93,7 @@ def test_million_particle_disc(capi):
     ctx = _ctx(capi, gas, sinks, density=False)
     g, rho, (nt, ns) = ctx.gradients(rho=True)
     assert nt == ctx.n and ns < 0.01 * nt                         # the thin outskirts of the disc
-    pos, m = _pos(ctx), ctx.field("m")
+    pos, m = field_positions(ctx), ctx.field("m")
     A = np.stack([ctx.field("vx"), ctx.field("vy"), ctx.field("vz")])
     ids = np.sort(np.random.default_rng(7).choice(ctx.n, 2000, replace=False))
     inf = {}
@@ -151,7 +124,7 @@ def test_linear_fields_are_exact(capi, which):
         gas, sinks = ic.split_rows(ic.keplerian_disc_var(20000, seed=4))
         ctx = _ctx(capi, gas, sinks, variable=True, density=False)
         hs = [None]
-    pos = _pos(ctx)
+    pos = field_positions(ctx)
     G = np.random.default_rng(5).normal(size=(4, 3))
     vals = 1.0 + G @ pos.T
     for h in hs:
@@ -202,7 +175,7 @@ def test_order_rule_bitwise(capi, variable):
     # clip: the common targets bitwise
     clip = ((-40.0, -30.0, -2.0), (35.0, 30.0, 3.0))
     g, rho, (nt, _) = a.gradients(clip=clip, **kw)
-    t = gradients_ref.targets_mask(_pos(a), a.n, clip)
+    t = gradients_ref.targets_mask(field_positions(a), a.n, clip)
     assert nt == int(t.sum()) > 0
     assert np.all(np.isnan(g[:, :, ~t])) and np.all(np.isnan(rho[~t]))
     assert np.array_equal(g[:, :, t], r0[0][:, :, t], equal_nan=True) and np.array_equal(rho[t], r0[1][t])
@@ -256,7 +229,7 @@ def test_after_accrete_and_cull(capi):
     assert g.shape == (3, 3, ctx.n) and nt == ctx.n
     A = np.stack([ctx.field("vx"), ctx.field("vy"), ctx.field("rho")])
     inf = {}
-    rg, rr, rnt, rns = gradients_ref.gradients(_pos(ctx), ctx.field("m"), A, 2.5, info=inf)
+    rg, rr, rnt, rns = gradients_ref.gradients(field_positions(ctx), ctx.field("m"), A, 2.5, info=inf)
     assert (nt, ns) == (rnt, rns)
     _cmp(g, rg, rho, rr, ratio=inf["ratio"])
     ctx.close()
@@ -382,7 +355,7 @@ def test_a_target_whose_h_spans_the_box(capi):
     dt = time.perf_counter() - t0
     print(f"h spanning the box: host form {dt * 1e3:.1f} ms for {nt} targets")
     inf = {}
-    rg, rr, rnt, rns = gradients_ref.gradients(_pos(ctx), ctx.field("m"), vals, ctx.field("h"), info=inf)
+    rg, rr, rnt, rns = gradients_ref.gradients(field_positions(ctx), ctx.field("m"), vals, ctx.field("h"), info=inf)
     assert (nt, ns) == (rnt, rns)
     _cmp(g, rg, rho, rr, ratio=inf["ratio"])
     assert np.allclose(g[1, :, 123], [2.0, 0.0, -1.0], rtol=0, atol=1e-11)

@@ -4,19 +4,15 @@ line's parsing."""
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from abi_support import containing, fortran_links, needs_fc, needs_hipcc, resource_usage
 from conftest import ROOT
 import energy_ref
 import gravity_at_ref as ref
-
-FC = shutil.which("amdflang") or "/opt/rocm/bin/amdflang"
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "summersph_amd", "csrc")
 
 
 def test_header_constants_and_prototypes_match_capi(tmp_path):
@@ -52,13 +48,9 @@ def test_header_constants_and_prototypes_match_capi(tmp_path):
     assert re.search(r"SPH_GRAVAT_GAS = 1, SPH_GRAVAT_SINKS = 2, SPH_GRAVAT_SPLIT = 4", binding)
 
 
-@pytest.mark.skipif(not os.path.exists(FC), reason="needs amdflang")
+@needs_fc
 def test_fortran_binding_compiles_and_links(tmp_path):
-    lib = os.path.join(ROOT, "summersph_amd", "libsummersph_hip.so")
-    if not os.path.exists(lib):
-        subprocess.run(["make", "-C", CSRC], check=True, stdout=subprocess.DEVNULL)
-    caller = tmp_path / "gravity_at_caller.f90"
-    caller.write_text("""program gravity_at_caller
+    exe = fortran_links(tmp_path, "gravity_at_caller", """program gravity_at_caller
   use, intrinsic :: iso_c_binding
   use sph_hip_binding
   implicit none
@@ -82,35 +74,13 @@ def test_fortran_binding_compiles_and_links(tmp_path):
   if (st /= 1) stop 2
 end program gravity_at_caller
 """)
-    binding = os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")
-    exe = tmp_path / "gravity_at_caller"
-    subprocess.run([FC, "-O1", binding, str(caller), "-L" + os.path.dirname(lib), "-lsummersph_hip",
-                    "-Wl,-rpath," + os.path.dirname(lib), "-o", str(exe)], check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
-    assert exe.exists()
     assert subprocess.run([str(exe)]).returncode == 0        # a null context is SPH_ERR_ARG before any device is touched
 
 
-def _resource_usage(src, pattern):
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", src, "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, check=True, capture_output=True, text=True).stderr
-    kernels, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1) if re.search(pattern, m.group(1)) else None
-            if cur:
-                kernels[cur] = {}
-            continue
-        m = re.search(r"remark: +([^:\[]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if cur and m:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_gravity_at_kernels_fit_the_register_budget():
-    k = _resource_usage("gravity_at.hip", "gravat_")
-    k.update(_resource_usage("gravity.hip", "grav_field_points"))
+    k = resource_usage("gravity_at.hip", containing("gravat_"))
+    k.update(resource_usage("gravity.hip", containing("grav_field_points")))
     for name in ("gravat_point_keys", "gravat_finish", "grav_field_points"):
         assert sum(name in n for n in k) == 1, name
     for name, r in k.items():

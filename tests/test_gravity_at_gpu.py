@@ -16,6 +16,7 @@ import pytest
 
 from conftest import ROOT, load_golden
 import energy_ref
+from gpu_support import capi, make_context, over_defaults, var_params, with_variable_h
 import gravity_at_ref as ref
 import octree_ref
 from summersph_amd import ic, txtio
@@ -39,28 +40,9 @@ BH_TOL_ACC = 0.112
 BH_TOL_PHI = 1.33e-2
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
 def _ctx(capi, gas, sinks=None, variable=False, flags=0, **kw):
-    if variable:
-        flags |= capi.FLAG_VARIABLE_H
-    if flags:
-        flags |= capi.default_params(variable).flags
-    ctx = capi.Context(device=0, variable=variable, **({"flags": flags} if flags else {}), **kw)
-    ctx.upload(gas)
-    if sinks is not None:
-        ctx.set_sinks(sinks)
-    return ctx
-
-
-def _var_kw(g):
-    gamma, eta, tol, maxlen, scale = g["params"]
-    return dict(gamma=gamma, gamma_m1=gamma - 1.0, eta=eta, h_tol=tol, h_max_length=maxlen, dt_scale=scale)
+    flags = over_defaults(capi, with_variable_h(capi, flags, variable), variable)
+    return make_context(capi, gas, sinks, variable=variable, flags=flags, **kw)
 
 
 def _rows(phi, acc):
@@ -84,7 +66,7 @@ def _fixture(capi, case, **kw):
     variable = case.startswith("sinkcv")
     g = load_golden("sinkcv1500_traj" if variable else "disc3000_traj")
     gas, sinks = energy_ref.rows_to_dicts(g, "full_s3_" if variable else "full_s5_", variable)
-    ctx = _ctx(capi, gas, sinks, variable, **kw, **(_var_kw(g) if variable else {}))
+    ctx = _ctx(capi, gas, sinks, variable, **kw, **(var_params(g) if variable else {}))
     return ctx, gas, sinks, variable
 
 

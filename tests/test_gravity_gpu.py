@@ -4,23 +4,15 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, rel_err
+from gpu_support import capi, make_context
 from summersph_amd import ic
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
 def make_ctx(capi, rows, **kw):
     gas, sinks = ic.split_rows(rows)
-    ctx = capi.Context(device=0, **kw)
-    ctx.upload(gas); ctx.set_sinks(sinks)
-    return ctx, gas, sinks
+    return make_context(capi, gas, sinks, **kw), gas, sinks
 
 
 @pytest.mark.parametrize("name", ["sod1000_eval", "disc3000_eval", "disc3000ns_eval", "bin2000_eval"])

@@ -4,31 +4,20 @@ pair search, its order rule, and the command line's parsing."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_support import c_layout, containing, fortran_links, needs_fc, needs_hipcc, resource_usage
 from conftest import ROOT
 import groups_ref
 
-FC = shutil.which("amdflang") or "/opt/rocm/bin/amdflang"
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "summersph_amd", "csrc")
 FIELDS = ["link", "rho_min", "clip_lo", "clip_hi", "min_members", "flags", "reserved"]
 
 
 def test_groups_desc_layout_matches_header(tmp_path):
     from summersph_amd import capi
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "summersph.h"\nint main(void) {\n'
-                   '  printf("size %zu\\n", sizeof(sph_groups_desc));\n' +
-                   "".join(f'  printf("{f} %zu\\n", offsetof(sph_groups_desc, {f}));\n' for f in FIELDS) +
-                   '  printf("consts %d %d\\n", SPH_GROUPS_LINK_H, SPH_GROUPS_NCOL);\n  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = c_layout(tmp_path, "sph_groups_desc", FIELDS, ['printf("consts %d %d\\n", SPH_GROUPS_LINK_H, SPH_GROUPS_NCOL);'])
     assert int(got["size"]) == ctypes.sizeof(capi.GroupsDesc) == 80
     for f in FIELDS:
         assert int(got[f]) == getattr(capi.GroupsDesc, f).offset, f
@@ -44,13 +33,9 @@ def test_groups_desc_layout_matches_header(tmp_path):
     assert d.rho_min == -np.inf and list(d.clip_lo) == [-np.inf] * 3 and list(d.clip_hi) == [np.inf] * 3
 
 
-@pytest.mark.skipif(not os.path.exists(FC), reason="needs amdflang")
+@needs_fc
 def test_fortran_binding_compiles_and_links(tmp_path):
-    lib = os.path.join(ROOT, "summersph_amd", "libsummersph_hip.so")
-    if not os.path.exists(lib):
-        subprocess.run(["make", "-C", CSRC], check=True, stdout=subprocess.DEVNULL)
-    caller = tmp_path / "groups_caller.f90"
-    caller.write_text("""program groups_caller
+    fortran_links(tmp_path, "groups_caller", """program groups_caller
   use, intrinsic :: iso_c_binding
   use, intrinsic :: ieee_arithmetic
   use sph_hip_binding
@@ -76,33 +61,11 @@ def test_fortran_binding_compiles_and_links(tmp_path):
   print *, st, ng
 end program groups_caller
 """)
-    binding = os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")
-    exe = tmp_path / "groups_caller"
-    subprocess.run([FC, "-O1", binding, str(caller), "-L" + os.path.dirname(lib), "-lsummersph_hip",
-                    "-Wl,-rpath," + os.path.dirname(lib), "-o", str(exe)], check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
-    assert exe.exists()
 
 
-def _resource_usage():
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "groups.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, check=True, capture_output=True, text=True).stderr
-    kernels, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1) if "groups_" in m.group(1) else None
-            if cur:
-                kernels[cur] = {}
-            continue
-        m = re.search(r"remark: +([^:\[]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if cur and m:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_groups_kernels_fit_the_register_budget():
-    k = _resource_usage()
+    k = resource_usage("groups.hip", containing("groups_"))
     for name in ("groups_select", "groups_box", "groups_keys", "groups_gather", "groups_tails", "groups_link", "groups_jump",
                  "groups_count", "groups_root_keys", "groups_number", "groups_members", "groups_starts"):
         assert sum(name in n for n in k) == 1, name

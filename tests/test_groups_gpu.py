@@ -4,6 +4,7 @@ adversarial sets (a long helix chain, pairs at exactly b and one ulp either side
 the box, clumps 10^7 apart, ghosts, a cull, clip / min_members / max_groups, an empty selection), the order rule, no
 side effects on a running simulation, the device form, the argument errors and the command line."""
 import ctypes as C
+import functools
 import os
 import subprocess
 import sys
@@ -12,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_golden
+from gpu_support import capi, clumped_disc, make_context
 import groups_ref
 from summersph_amd import ic, txtio
 
@@ -23,21 +25,7 @@ EXACT = ("N", "r_max", "rho_max", "x_dense", "y_dense", "z_dense", "id_dense", "
 FIELDS = "x y z vx vy vz u m rho".split()
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
-def _ctx(capi, gas, sinks=None, variable=False, flags=0, density=True):
-    ctx = capi.Context(device=0, variable=variable, **({"flags": flags} if flags else {}))
-    ctx.upload(gas)
-    if sinks is not None:
-        ctx.set_sinks(sinks)
-    if density:
-        ctx.density()
-    return ctx
+_ctx = functools.partial(make_context, density=True)      # every call here reads rho unless it says density=False
 
 
 def _fields(ctx, h=False):
@@ -82,46 +70,9 @@ def _gas(pos, seed=0, m=1e-6):
             "m": rng.uniform(0.5, 1.5, n) * m, "alpha": np.ones(n)}
 
 
-def _clumped_disc(n_disc, k, per, seed):
-    gas, sinks = ic.split_rows(ic.keplerian_disc(n_disc, seed=seed))
-    gas = dict(gas)
-    rng = np.random.default_rng(seed + 1)
-    r = np.sqrt(gas["x"] ** 2 + gas["y"] ** 2)
-    rmax = float(np.max(r))
-    centres = []
-    for j in range(k):
-        ang = 2 * np.pi * j / k
-        rc = 15.0 + (rmax - 25.0) * (j + 0.5) / k
-        centres.append((rc * np.cos(ang), rc * np.sin(ang), 0.0))
-    centres = np.array(centres)
-    far = np.ones(gas["x"].size, bool)
-    for c in centres:
-        far &= (gas["x"] - c[0]) ** 2 + (gas["y"] - c[1]) ** 2 + (gas["z"] - c[2]) ** 2 > 9.0
-    gas = {kk: v[far] for kk, v in gas.items()}
-    blobs = []
-    for c in centres:
-        # Plummer (a = 0.2) truncated at 0.8: every member within 1.6 of every other
-        u = rng.uniform(0, 0.95, 3 * per)
-        rr = 0.2 / np.sqrt(u ** (-2.0 / 3.0) - 1.0)
-        rr = rr[rr < 0.8][:per]
-        d = rng.normal(size=(rr.size, 3))
-        d /= np.linalg.norm(d, axis=1)[:, None]
-        blobs.append(c + d * rr[:, None])
-    bl = np.concatenate(blobs)
-    nb = len(bl)
-    vk = np.sqrt(1.0 / np.hypot(bl[:, 0], bl[:, 1]))
-    ph = np.arctan2(bl[:, 1], bl[:, 0])
-    add = {"x": bl[:, 0], "y": bl[:, 1], "z": bl[:, 2], "vx": -vk * np.sin(ph) + rng.normal(0, 0.01, nb),
-           "vy": vk * np.cos(ph) + rng.normal(0, 0.01, nb), "vz": rng.normal(0, 0.01, nb),
-           "u": rng.uniform(0.1, 0.3, nb), "m": np.full(nb, gas["m"][0]), "alpha": np.ones(nb)}
-    n0 = gas["x"].size
-    gas = {kk: np.concatenate([gas[kk], add[kk]]) for kk in add}
-    return gas, sinks, n0, [len(b) for b in blobs]
-
-
 # ---- parity ------------------------------------------------------------------------------------------------------------
 def test_parity_embedded_clumps(capi):
-    gas, sinks, n0, sizes = _clumped_disc(20000, 4, 400, 3)
+    gas, sinks, n0, sizes = clumped_disc(20000, 4, 400, 3)
     ctx = _ctx(capi, gas, sinks)
     rho = ctx.field("rho")
     rho_min = 0.5 * float(np.min(rho[n0:]))

@@ -180,7 +180,7 @@ def test_existing_brute_force_cases_never_run_a_second_batch():
             "clustered": (existing._clustered(), np.array([-18.0, -16.0, -14.0]), np.array([17.0, 15.0, 16.0]), (21, 19, 17), 64)}
     for name, (rows, lo, hi, n, want) in sets.items():
         gas, _ = ic.split_rows(existing._edge_set(rows, h, lo, hi))
-        got = _max_n_int(existing._pos(gas), h, lo, hi, n)
+        got = _max_n_int(existing.positions(gas), h, lo, hi, n)
         assert got == want <= S.GT, (name, got)
     # per-particle h (test_per_particle_h_variable_context): n_int depends on the largest h alone; the disc's h is at least
     # its midplane value and at most h_max_length = 10

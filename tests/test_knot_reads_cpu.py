@@ -16,6 +16,8 @@ import subprocess
 
 import pytest
 
+from abi_support import REMARKS, hipcc_flags
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "summersph_amd", "csrc")
 HIPCC = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
@@ -30,8 +32,7 @@ VARIANTS = ["density_wtILi1024ELb1E", "density_wtILi1024ELb0E", "forces_qILi1024
 def compiled(tmp_path_factory):
     """(assembly per kernel, resource report per kernel) of tiled.hip"""
     out = tmp_path_factory.mktemp("knots_cpu") / "tiled.s"
-    r = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "--cuda-device-only", "-S",
-                        "-Rpass-analysis=kernel-resource-usage", os.path.join(CSRC, "tiled.hip"), "-o", str(out)],
+    r = subprocess.run([HIPCC, *hipcc_flags(), "--cuda-device-only", "-S", REMARKS, os.path.join(CSRC, "tiled.hip"), "-o", str(out)],
                        check=True, capture_output=True, text=True, timeout=900)
     asm, name = {}, None
     for line in out.read_text().splitlines():
@@ -50,7 +51,7 @@ def compiled(tmp_path_factory):
             name = m.group(1)
             usage[name] = {}
             continue
-        m = re.search(r"remark: .*?\s+([A-Za-z][A-Za-z \[\]/]*?): (\S+) \[-Rpass-analysis", line)
+        m = re.search(r"remark: .*?\s+([A-Za-z][A-Za-z \[\]/]*?): (\S+) " + re.escape("[" + REMARKS.split("=")[0]), line)
         if m and name is not None:
             usage[name][m.group(1).strip()] = m.group(2)
     return asm, usage

@@ -13,6 +13,7 @@ import sys
 import numpy as np
 import pytest
 
+from gpu_support import capi, make_context, with_variable_h
 import octree_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -22,13 +23,6 @@ ROOT = os.path.dirname(HERE)
 NAMES = list(R.FAMILIES)
 MODES = ("fixed", "var")
 KEY_TIES = {"shared_keys", "coincident"}       # sets with coinciding path keys (their tie order is the slot order)
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
 
 
 _CASES = {}
@@ -45,9 +39,7 @@ def case(name, mode):
 
 def make_ctx(capi, gas, h, flags=0):
     var = h is not None
-    ctx = capi.Context(device=0, variable=var, flags=flags | (capi.FLAG_VARIABLE_H if var else 0))
-    ctx.upload(dict(gas, h=h) if var else gas)
-    return ctx
+    return make_context(capi, dict(gas, h=h) if var else gas, variable=var, flags=with_variable_h(capi, flags, var))
 
 
 def accel(ctx):

@@ -8,27 +8,16 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, rel_err
+from gpu_support import capi, make_context, var_params
 from summersph_amd import ic
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-13
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
 def make_ctx(capi, g, **kw):
     gas, sinks = ic.split_rows(g["ic"])
-    gamma, eta, tol, maxlen, scale = g["params"]
-    ctx = capi.Context(device=0, variable=True, gamma=gamma, gamma_m1=gamma - 1.0, eta=eta, h_tol=tol,
-                       h_max_length=maxlen, dt_scale=scale, **kw)
-    ctx.upload(gas)
-    ctx.set_sinks(sinks)
-    return ctx, gas, sinks
+    return make_context(capi, gas, sinks, variable=True, **var_params(g), **kw), gas, sinks
 
 
 @pytest.mark.parametrize("name", ["discv3000_eval", "discv2000r_eval"])

@@ -5,32 +5,22 @@ cannot separate, and the command line's parsing."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_support import CSRC, c_layout, containing, fortran_links, needs_fc, needs_hipcc, resource_usage
 from conftest import ROOT
 import groups_ref
 import peaks_ref
 
-FC = shutil.which("amdflang") or "/opt/rocm/bin/amdflang"
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "summersph_amd", "csrc")
 FIELDS = ["link", "rho_min", "peak_min", "contrast", "clip_lo", "clip_hi", "min_members", "flags", "reserved"]
 
 
 def test_peaks_desc_layout_matches_header(tmp_path):
     from summersph_amd import capi
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "summersph.h"\nint main(void) {\n'
-                   '  printf("size %zu\\n", sizeof(sph_peaks_desc));\n' +
-                   "".join(f'  printf("{f} %zu\\n", offsetof(sph_peaks_desc, {f}));\n' for f in FIELDS) +
-                   '  printf("consts %d %d %d\\n", SPH_PEAKS_LINK_H, SPH_PEAKS_NCOL, SPH_PEAKS_NCOUNT);\n  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = c_layout(tmp_path, "sph_peaks_desc", FIELDS,
+                   ['printf("consts %d %d %d\\n", SPH_PEAKS_LINK_H, SPH_PEAKS_NCOL, SPH_PEAKS_NCOUNT);'])
     assert int(got["size"]) == ctypes.sizeof(capi.PeaksDesc) == 96
     assert [f for f, _ in capi.PeaksDesc._fields_] == FIELDS
     for f in FIELDS:
@@ -51,13 +41,9 @@ def test_peaks_desc_layout_matches_header(tmp_path):
     assert list(d.clip_lo) == [-np.inf] * 3 and list(d.clip_hi) == [np.inf] * 3
 
 
-@pytest.mark.skipif(not os.path.exists(FC), reason="needs amdflang")
+@needs_fc
 def test_fortran_binding_compiles_and_links(tmp_path):
-    lib = os.path.join(ROOT, "summersph_amd", "libsummersph_hip.so")
-    if not os.path.exists(lib):
-        subprocess.run(["make", "-C", CSRC], check=True, stdout=subprocess.DEVNULL)
-    caller = tmp_path / "peaks_caller.f90"
-    caller.write_text("""program peaks_caller
+    fortran_links(tmp_path, "peaks_caller", """program peaks_caller
   use, intrinsic :: iso_c_binding
   use, intrinsic :: ieee_arithmetic
   use sph_hip_binding
@@ -85,28 +71,11 @@ def test_fortran_binding_compiles_and_links(tmp_path):
   print *, st, counts
 end program peaks_caller
 """)
-    binding = os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")
-    exe = tmp_path / "peaks_caller"
-    subprocess.run([FC, "-O1", binding, str(caller), "-L" + os.path.dirname(lib), "-lsummersph_hip",
-                    "-Wl,-rpath," + os.path.dirname(lib), "-o", str(exe)], check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
-    assert exe.exists()
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_peaks_kernels_fit_the_register_budget():
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "peaks.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, check=True, capture_output=True, text=True).stderr
-    k, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1) if "peaks_" in m.group(1) else None
-            if cur:
-                k[cur] = {}
-            continue
-        m = re.search(r"remark: +([^:\[]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if cur and m:
-            k[cur][m.group(1).strip()] = int(m.group(2))
+    k = resource_usage("peaks.hip", containing("peaks_"))
     for name in ("peaks_gather", "peaks_slots", "peaks_hop", "peaks_jump", "peaks_flags", "peaks_compact", "peaks_edge_keys",
                  "peaks_edge_idx", "peaks_scatter", "peaks_assign", "peaks_minid", "peaks_root", "peaks_table"):
         assert sum(name in n for n in k) == 1, name

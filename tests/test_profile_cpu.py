@@ -5,32 +5,22 @@ import ctypes
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_support import c_layout, containing, fortran_links, needs_fc, needs_hipcc, resource_usage
 from conftest import ROOT
 import profile_ref
 
-FC = shutil.which("amdflang") or "/opt/rocm/bin/amdflang"
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "summersph_amd", "csrc")
 FIELDS = ["centre", "centre_v", "central_mass", "normal", "r_min", "r_max", "z_max", "n_r", "n_phi", "sink", "flags", "reserved"]
 
 
 def test_profile_desc_layout_matches_header(tmp_path):
     from summersph_amd import capi
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "summersph.h"\nint main(void) {\n'
-                   '  printf("size %zu\\n", sizeof(sph_profile_desc));\n' +
-                   "".join(f'  printf("{f} %zu\\n", offsetof(sph_profile_desc, {f}));\n' for f in FIELDS) +
-                   '  printf("consts %d %d %d %d\\n", SPH_PROFILE_LOG, SPH_PROFILE_AUTO_NORMAL, SPH_PROFILE_NSUM, '
-                   'SPH_PROFILE_NCOL);\n  printf("abi %d\\n", SPH_ABI_VERSION);\n  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = c_layout(tmp_path, "sph_profile_desc", FIELDS,
+                   ['printf("consts %d %d %d %d\\n", SPH_PROFILE_LOG, SPH_PROFILE_AUTO_NORMAL, SPH_PROFILE_NSUM, SPH_PROFILE_NCOL);',
+                    'printf("abi %d\\n", SPH_ABI_VERSION);'])
     assert int(got["size"]) == ctypes.sizeof(capi.ProfileDesc) == 128
     for f in FIELDS:
         assert int(got[f]) == getattr(capi.ProfileDesc, f).offset, f
@@ -42,13 +32,9 @@ def test_profile_desc_layout_matches_header(tmp_path):
     assert re.search(r"SPH_PROFILE_LOG = 1, SPH_PROFILE_AUTO_NORMAL = 2, SPH_PROFILE_NSUM = 20, SPH_PROFILE_NCOL = 29", binding)
 
 
-@pytest.mark.skipif(not os.path.exists(FC), reason="needs amdflang")
+@needs_fc
 def test_fortran_binding_compiles_and_links(tmp_path):
-    lib = os.path.join(ROOT, "summersph_amd", "libsummersph_hip.so")
-    if not os.path.exists(lib):
-        subprocess.run(["make", "-C", CSRC], check=True, stdout=subprocess.DEVNULL)
-    caller = tmp_path / "profile_caller.f90"
-    caller.write_text("""program profile_caller
+    fortran_links(tmp_path, "profile_caller", """program profile_caller
   use, intrinsic :: iso_c_binding
   use, intrinsic :: ieee_arithmetic
   use sph_hip_binding
@@ -82,33 +68,11 @@ def test_fortran_binding_compiles_and_links(tmp_path):
   print *, st, table(1, 1)
 end program profile_caller
 """)
-    binding = os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")
-    exe = tmp_path / "profile_caller"
-    subprocess.run([FC, "-O1", binding, str(caller), "-L" + os.path.dirname(lib), "-lsummersph_hip",
-                    "-Wl,-rpath," + os.path.dirname(lib), "-o", str(exe)], check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
-    assert exe.exists()
 
 
-def _resource_usage():
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "profile.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, check=True, capture_output=True, text=True).stderr
-    kernels, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1) if "profile_" in m.group(1) else None
-            if cur:
-                kernels[cur] = {}
-            continue
-        m = re.search(r"remark: +([^:\[]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if cur and m:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_profile_kernels_fit_the_register_budget():
-    k = _resource_usage()
+    k = resource_usage("profile.hip", containing("profile_"))
     for name in ("profile_keys", "profile_starts", "profile_pieces", "profile_final"):
         assert sum(name in n for n in k) == 1, name
     for name, r in k.items():

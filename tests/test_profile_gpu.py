@@ -13,19 +13,13 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_golden, rel_err
+from gpu_support import capi, make_context
 import profile_ref
 from summersph_amd import ic, txtio
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
 SPH_ERR_ARG = 1
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
 
 
 def _disc(n, seed, variable=False):
@@ -45,13 +39,6 @@ def _drop_edges(gas, cases, centre=(0, 0, 0), normal=(0, 0, 1)):
     for (r0, r1, nr, nphi, log) in cases:
         keep &= ~profile_ref.edge_margin(gas, r0, r1, nr, nphi, log, centre, normal)
     return {k: (v[keep] if isinstance(v, np.ndarray) and v.shape == keep.shape else v) for k, v in gas.items()}
-
-
-def _ctx(capi, gas, sinks, variable=False, flags=0):
-    ctx = capi.Context(device=0, variable=variable, **({"flags": flags} if flags else {}))
-    ctx.upload(gas)
-    ctx.set_sinks(sinks)
-    return ctx
 
 
 def _ref(capi, ctx, gas, sinks, r0, r1, nr, nphi=1, log=False, z_max=np.inf, sink=0, normal=(0, 0, 1), h=None):
@@ -98,7 +85,7 @@ CASES = [(10.0, 60.0, 12, 1, False, np.inf), (10.0, 60.0, 12, 1, True, np.inf), 
 def test_parity_fixed_h(capi):
     gas, sinks = _disc(20000, 5)
     gas = _drop_edges(gas, [c[:5] for c in CASES])
-    ctx = _ctx(capi, gas, sinks)
+    ctx = make_context(capi, gas, sinks)
     for (r0, r1, nr, nphi, log, zm) in CASES:
         t, s = ctx.profile(r0, r1, nr, nphi, log=log, sink=0, z_max=zm)
         rs, rt = _ref(capi, ctx, gas, sinks, r0, r1, nr, nphi, log, zm)
@@ -111,7 +98,7 @@ def test_parity_fixed_h(capi):
 def test_parity_variable_h(capi):
     gas, sinks = _disc(6000, 9, variable=True)
     gas = _drop_edges(gas, [(10.0, 40.0, 8, 1, False)])
-    ctx = _ctx(capi, gas, sinks, variable=True)
+    ctx = make_context(capi, gas, sinks, variable=True)
     t, s = ctx.profile(10.0, 40.0, 8, sink=0)
     rs, rt = _ref(capi, ctx, gas, sinks, 10.0, 40.0, 8, h=gas["h"])
     _cmp_sums(s, rs)
@@ -126,7 +113,7 @@ def test_parity_1e6(capi):
     # than the tolerance by itself)
     r1 = 1.001 * float(np.max(np.hypot(gas["x"], gas["y"])))
     gas = _drop_edges(gas, [(10.0, r1, 100, 1, False)])
-    ctx = _ctx(capi, gas, sinks)
+    ctx = make_context(capi, gas, sinks)
     t, s = ctx.profile(10.0, r1, 100, sink=0)
     rs, rt = _ref(capi, ctx, gas, sinks, 10.0, r1, 100, 1, False)
     _cmp_sums(s, rs)
@@ -138,12 +125,12 @@ def test_parity_1e6(capi):
 def test_order_rule_bitwise(capi):
     gas, sinks = _disc(20000, 13)
     args = dict(r_min=5.0, r_max=70.0, n_r=16, n_phi=4, sink=0, z_max=3.0)
-    a = _ctx(capi, gas, sinks)
+    a = make_context(capi, gas, sinks)
     s0 = a.profile(**args)[1]                                 # upload order
     a.density()                                               # cell-sorted
     s1 = a.profile(**args)[1]
     s2 = a.profile(**args)[1]
-    b = _ctx(capi, gas, sinks, flags=capi.FLAG_HASHED_GRID)
+    b = make_context(capi, gas, sinks, flags=capi.FLAG_HASHED_GRID)
     b.density()
     s3 = b.profile(**args)[1]
     for s in (s1, s2, s3):
@@ -170,12 +157,12 @@ def _transform(gas, sinks, rot, shift=(0, 0, 0), boost=(0, 0, 0)):
 def test_frames(capi):
     gas, sinks = _disc(20000, 17)
     gas = _drop_edges(gas, [(10.0, 60.0, 10, 1, False)])
-    base = _ctx(capi, gas, sinks)
+    base = make_context(capi, gas, sinks)
     t0, _ = base.profile(10.0, 60.0, 10, sink=0)
     rot = _rot_x(30.0)
     nz = rot @ np.array([0.0, 0.0, 1.0])
     g, s = _transform(gas, sinks, rot)
-    ctx = _ctx(capi, g, s)
+    ctx = make_context(capi, g, s)
     t1, _ = ctx.profile(10.0, 60.0, 10, sink=0, normal=tuple(nz))
     assert np.array_equal(t1["N"], t0["N"])
     for c in ("Sigma", "R_mean", "H", "vphi_mean", "vR_mean", "sigma_z", "Omega", "kappa", "Q", "Mdot", "j", "ecc", "tilt"):
@@ -191,7 +178,7 @@ def test_frames(capi):
     assert np.allclose(n1, nz, atol=1e-2, rtol=0)             # which is z^ up to the sampling noise of L
     # translated and boosted, centred on the sink
     g2, s2 = _transform(gas, sinks, np.eye(3), shift=(123.0, -45.0, 7.0), boost=(3.0, -2.0, 0.5))
-    ctx2 = _ctx(capi, g2, s2)
+    ctx2 = make_context(capi, g2, s2)
     t2, _ = ctx2.profile(10.0, 60.0, 10, sink=0)
     assert np.array_equal(t2["N"], t0["N"])
     for c in capi.PROFILE_COLUMNS:
@@ -210,7 +197,7 @@ def test_circumbinary_fixture(capi):
     R = np.hypot(gas["x"] - com[0], gas["y"] - com[1])
     r0, r1 = 0.5 * float(np.min(R)), 1.01 * float(np.max(R))
     gas = _drop_edges(gas, [(r0, r1, 12, 1, False)], centre=com)
-    ctx = _ctx(capi, gas, sinks)
+    ctx = make_context(capi, gas, sinks)
     t, s = ctx.profile(r0, r1, 12, centre=(com, comv, mb))
     p = ctx.params
     rs, _ = profile_ref.profile_sums(gas, p.h, p.G, r0, r1, 12, 1, False, np.inf, com, comv, mb)
@@ -225,14 +212,14 @@ def test_circumbinary_fixture(capi):
 def test_additivity_over_contexts(capi):
     gas, sinks = _disc(20000, 19)
     args = dict(r_min=10.0, r_max=60.0, n_r=10, n_phi=3, sink=0)
-    whole = _ctx(capi, gas, sinks)
+    whole = make_context(capi, gas, sinks)
     tw, sw = whole.profile(**args)
     half = gas["x"].size // 2
     parts = [{k: (v[sl] if isinstance(v, np.ndarray) and v.shape == gas["x"].shape else v) for k, v in gas.items()}
              for sl in (slice(0, half), slice(half, None))]
     sp = []
     for p in parts:
-        c = _ctx(capi, p, sinks)
+        c = make_context(capi, p, sinks)
         sp.append(c.profile(**args)[1])
         c.close()
     tot = sp[0] + sp[1]
@@ -247,7 +234,7 @@ def test_additivity_over_contexts(capi):
 def test_full_coverage_and_cull(capi):
     gas, sinks = _disc(20000, 23)
     sinks = dict(sinks); sinks["radius"] = np.array([15.0])   # accretes the inner edge
-    ctx = _ctx(capi, gas, sinks)
+    ctx = make_context(capi, gas, sinks)
     for step in range(2):
         _, s = ctx.profile(0.0, 1e4, 7, n_phi=2, sink=0)
         assert s[:, 0].sum() == ctx.n
@@ -262,7 +249,7 @@ def test_no_side_effects(capi):
     gas, sinks = _disc(8000, 29)
     runs = []
     for with_profile in (False, True):
-        ctx = _ctx(capi, gas, sinks)
+        ctx = make_context(capi, gas, sinks)
         dt, t = 1e-3, 0.0
         statsl = []
         for _ in range(5):
@@ -286,7 +273,7 @@ def test_no_side_effects(capi):
 def test_device_form_is_bitwise_the_host_form(capi):
     import torch
     gas, sinks = _disc(20000, 31)
-    ctx = _ctx(capi, gas, sinks)
+    ctx = make_context(capi, gas, sinks)
     _, s = ctx.profile(10.0, 60.0, 10, n_phi=4, log=True, sink=0, z_max=4.0)
     d = ctx.profile(10.0, 60.0, 10, n_phi=4, log=True, sink=0, z_max=4.0, device=True)
     assert isinstance(d, torch.Tensor) and np.array_equal(d.cpu().numpy(), s)
@@ -295,7 +282,7 @@ def test_device_form_is_bitwise_the_host_form(capi):
 
 def test_errors(capi):
     gas, sinks = _disc(3000, 37)
-    ctx = _ctx(capi, gas, sinks)
+    ctx = make_context(capi, gas, sinks)
     lib = ctx.lib
     good = dict(r_min=10.0, r_max=40.0, n_r=4, n_phi=2, sink=0)
     buf = np.zeros((8, capi.PROFILE_NSUM))
@@ -342,7 +329,7 @@ def test_cli_matches_context_profile(capi, tmp_path):
     z = np.load(out)
     g2, s2 = ic.split_rows(np.concatenate([rows[:, :8], srows], axis=0))
     g2["alpha"] = rows[:, 8]
-    ctx = _ctx(capi, g2, s2)
+    ctx = make_context(capi, g2, s2)
     t, s = ctx.profile(10.0, 50.0, 8, n_phi=2, log=True, sink=0, normal="auto", z_max=5.0)
     for c in capi.PROFILE_COLUMNS:
         assert np.array_equal(z[c], t[c], equal_nan=True), c

@@ -17,25 +17,13 @@ import functools
 import numpy as np
 import pytest
 
+from gpu_support import capi, make_context
 import image_ref
 import image_sets as S
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
 WORST = {}
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
-def _ctx(capi, case):
-    ctx = capi.Context(device=0, variable=case["variable"])
-    ctx.upload(case["gas"])
-    return ctx
 
 
 def _nodes(case):
@@ -98,7 +86,7 @@ def test_density_every_node(capi, name):
     n = case["n"]
     sel, lo, hi, g = _nodes(case)
     _, den, _, s_den, near = _mass_ref(name)
-    ctx = _ctx(capi, case)
+    ctx = make_context(capi, case["gas"], variable=case["variable"])
     kw = _kw(case, lo, hi)
     grid = ctx.render_density(n, **kw)
     if case["lo"] is None:
@@ -137,7 +125,7 @@ def test_density_every_node(capi, name):
 def _field_case(capi, name, weight):
     case = S.render_case(name)
     sel, lo, hi, g = _nodes(case)
-    ctx = _ctx(capi, case)
+    ctx = make_context(capi, case["gas"], variable=case["variable"])
     a = S.field_values(ctx.n)
     if weight == "mass":
         ref = _mass_ref(name)

@@ -1,34 +1,20 @@
 """CPU tests of the density rendering (sph_render_density): the ABI mirrors (ctypes, Fortran) against the C header, the
 numpy restatement against the reference script's own image, the CLI's save-file parsing and row selection, and the
 gather kernels' register budget (no spills, no scratch)."""
-import os
-import re
-import shutil
-import subprocess
-
 import numpy as np
-import pytest
 
-from conftest import ROOT, load_golden
+from abi_support import c_layout, containing, fortran_links, needs_fc, needs_hipcc, resource_usage
+from conftest import load_golden
 import render_ref
 from summersph_amd import render, txtio
 
-FC = shutil.which("amdflang") or "/opt/rocm/bin/amdflang"
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "summersph_amd", "csrc")
 FIELDS = ["lo", "hi", "clip_lo", "clip_hi", "h", "n", "axis", "flags", "reserved"]
 
 
 def test_render_desc_layout_matches_header(tmp_path):
     from summersph_amd.capi import RenderDesc
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "summersph.h"\nint main(void) {\n'
-                   '  printf("size %zu\\n", sizeof(sph_render_desc));\n' +
-                   "".join(f'  printf("{f} %zu\\n", offsetof(sph_render_desc, {f}));\n' for f in FIELDS) +
-                   '  printf("auto %d spacing %d\\n", SPH_RENDER_AUTO_BOUNDS, SPH_RENDER_SPACING);\n  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = c_layout(tmp_path, "sph_render_desc", FIELDS,
+                   ['printf("auto %d spacing %d\\n", SPH_RENDER_AUTO_BOUNDS, SPH_RENDER_SPACING);'])
     assert int(got["size"]) == __import__("ctypes").sizeof(RenderDesc) == 128
     for f in FIELDS:
         assert int(got[f]) == getattr(RenderDesc, f).offset, f
@@ -36,13 +22,9 @@ def test_render_desc_layout_matches_header(tmp_path):
     assert got["auto"] == f"{capi.RENDER_AUTO_BOUNDS} spacing {capi.RENDER_SPACING}"
 
 
-@pytest.mark.skipif(not os.path.exists(FC), reason="needs amdflang")
+@needs_fc
 def test_fortran_binding_compiles_and_links(tmp_path):
-    lib = os.path.join(ROOT, "summersph_amd", "libsummersph_hip.so")
-    if not os.path.exists(lib):
-        subprocess.run(["make", "-C", CSRC], check=True, stdout=subprocess.DEVNULL)
-    caller = tmp_path / "render_caller.f90"
-    caller.write_text("""program render_caller
+    fortran_links(tmp_path, "render_caller", """program render_caller
   use, intrinsic :: iso_c_binding
   use, intrinsic :: ieee_arithmetic
   use sph_hip_binding
@@ -66,11 +48,6 @@ def test_fortran_binding_compiles_and_links(tmp_path):
   print *, st
 end program render_caller
 """)
-    binding = os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")
-    subprocess.run([FC, "-O1", binding, str(caller), "-L" + os.path.dirname(lib), "-lsummersph_hip",
-                    "-Wl,-rpath," + os.path.dirname(lib), "-o", str(tmp_path / "render_caller")],
-                   check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
-    assert (tmp_path / "render_caller").exists()
 
 
 def test_numpy_restatement_reproduces_the_script():
@@ -115,26 +92,9 @@ def test_save_parsing_and_script_row_selection(tmp_path):
     assert np.array_equal(sel, gas2[:26])              # rows 27..29 clipped, row 26 (the last survivor) dropped
 
 
-def _resource_usage():
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "render.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, check=True, capture_output=True, text=True).stderr
-    kernels, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1) if any(s in m.group(1) for s in ("render_", "stats_final", "start_table")) else None
-            if cur:
-                kernels[cur] = {}
-            continue
-        m = re.search(r"remark: +([^:\[]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if cur and m:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_render_kernels_do_not_spill():
-    k = _resource_usage()
+    k = resource_usage("render.hip", containing("render_", "stats_final", "start_table"))
     names = " ".join(k)
     for want in ("render_gather", "render_select", "render_stats_partial", "stats_final", "render_records", "start_table"):
         assert want in names, want

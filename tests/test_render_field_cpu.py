@@ -5,33 +5,23 @@ import ctypes
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_support import c_layout, containing, fortran_links, needs_fc, needs_hipcc, resource_usage
 from conftest import ROOT
 import render_field_ref
 import render_ref
 
-FC = shutil.which("amdflang") or "/opt/rocm/bin/amdflang"
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "summersph_amd", "csrc")
 FIELDS = ["base", "field", "weight", "normalise", "reserved"]
 
 
 def test_render_field_desc_layout_matches_header(tmp_path):
     from summersph_amd import capi
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "summersph.h"\nint main(void) {\n'
-                   '  printf("size %zu\\n", sizeof(sph_render_field_desc));\n' +
-                   "".join(f'  printf("{f} %zu\\n", offsetof(sph_render_field_desc, {f}));\n' for f in FIELDS) +
-                   '  printf("consts %d %d %d\\n", SPH_RENDER_FIELD_VALUES, SPH_RENDER_WEIGHT_MASS, SPH_RENDER_WEIGHT_VOLUME);\n'
-                   '  printf("base_size %zu\\n", sizeof(sph_render_desc));\n  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = c_layout(tmp_path, "sph_render_field_desc", FIELDS,
+                   ['printf("consts %d %d %d\\n", SPH_RENDER_FIELD_VALUES, SPH_RENDER_WEIGHT_MASS, SPH_RENDER_WEIGHT_VOLUME);',
+                    'printf("base_size %zu\\n", sizeof(sph_render_desc));'])
     assert int(got["size"]) == ctypes.sizeof(capi.RenderFieldDesc) == 144
     assert int(got["base_size"]) == 128
     for f in FIELDS:
@@ -41,13 +31,9 @@ def test_render_field_desc_layout_matches_header(tmp_path):
     assert re.search(r"SPH_RENDER_FIELD_VALUES = -1, SPH_RENDER_WEIGHT_MASS = 0, SPH_RENDER_WEIGHT_VOLUME = 1", binding)
 
 
-@pytest.mark.skipif(not os.path.exists(FC), reason="needs amdflang")
+@needs_fc
 def test_fortran_binding_compiles_and_links(tmp_path):
-    lib = os.path.join(ROOT, "summersph_amd", "libsummersph_hip.so")
-    if not os.path.exists(lib):
-        subprocess.run(["make", "-C", CSRC], check=True, stdout=subprocess.DEVNULL)
-    caller = tmp_path / "field_caller.f90"
-    caller.write_text("""program field_caller
+    fortran_links(tmp_path, "field_caller", """program field_caller
   use, intrinsic :: iso_c_binding
   use, intrinsic :: ieee_arithmetic
   use sph_hip_binding
@@ -78,33 +64,11 @@ def test_fortran_binding_compiles_and_links(tmp_path):
   print *, st
 end program field_caller
 """)
-    binding = os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")
-    subprocess.run([FC, "-O1", binding, str(caller), "-L" + os.path.dirname(lib), "-lsummersph_hip",
-                    "-Wl,-rpath," + os.path.dirname(lib), "-o", str(tmp_path / "field_caller")],
-                   check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
-    assert (tmp_path / "field_caller").exists()
 
 
-def _resource_usage():
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "render.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, check=True, capture_output=True, text=True).stderr
-    kernels, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1) if ("render_" in m.group(1) or "field_gather" in m.group(1)) else None
-            if cur:
-                kernels[cur] = {}
-            continue
-        m = re.search(r"remark: +([^:\[]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if cur and m:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_field_kernels_fit_the_register_budget():
-    k = _resource_usage()
+    k = resource_usage("render.hip", containing("render_", "field_gather"))
     field = {n: r for n, r in k.items() if "field_gather" in n or "render_field_records" in n}
     assert sum("field_gather" in n for n in field) == 6             # walk axis 0 / 1 / 2, with and without den
     assert sum("render_field_records" in n for n in field) == 1

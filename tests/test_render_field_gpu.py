@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_golden, rel_err
+from gpu_support import capi, field_positions, make_context
 import render_field_ref
 import render_ref
 from summersph_amd import ic, txtio
@@ -20,26 +21,12 @@ TOL = 1e-12
 SPH_ERR_ARG, SPH_ERR_STATE = 1, 5
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
 def _ctx(capi, rows, variable=False, u_seed=None):
     gas, sinks = ic.split_rows(rows)
     if u_seed is not None:                                # a non-uniform u, so that a field render has something to show
         gas = dict(gas)
         gas["u"] = np.random.default_rng(u_seed).uniform(0.1, 0.5, gas["x"].size)
-    ctx = capi.Context(device=0, variable=variable)
-    ctx.upload(gas)
-    ctx.set_sinks(sinks)
-    return ctx, gas
-
-
-def _pos(ctx):
-    return np.stack([ctx.field(k) for k in "xyz"], axis=1)
+    return make_context(capi, gas, sinks, variable=variable), gas
 
 
 def _seq_sum(grid, axis):
@@ -92,7 +79,7 @@ def _brute_case(capi, variable):
 @pytest.mark.parametrize("variable", [False, True])
 def test_brute_force(capi, variable):
     ctx, h, hr, lo, hi, n = _brute_case(capi, variable)
-    pos, m, rho = _pos(ctx), ctx.field("m"), ctx.field("rho")
+    pos, m, rho = field_positions(ctx), ctx.field("m"), ctx.field("rho")
     a = np.random.default_rng(8).normal(0.3, 1.0, ctx.n)
     ref3 = {wt: render_field_ref.grid_brute(pos, w, a, h, lo, hi, n) for wt, w in (("mass", m), ("volume", m / rho))}
     for weight in ("mass", "volume"):
@@ -343,7 +330,7 @@ def test_scale_1e6_edge_on_velocity_map(capi):
     img, w = ctx.render_field("vy", n, axis="y", normalise=True, weight_out=True)
     assert img.shape == (512, 64)
     lo, hi = ctx.render_bounds
-    pos = _pos(ctx)
+    pos = field_positions(ctx)
     m, hv, vy = ctx.field("m"), ctx.field("h"), ctx.field("vy")
     ax = render_ref.axes(lo, hi, n)
     rng = np.random.default_rng(2)

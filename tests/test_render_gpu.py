@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_golden
+from gpu_support import capi, make_context, positions
 import render_ref
 from summersph_amd import ic, txtio
 
@@ -18,23 +19,9 @@ TOL = 1e-12
 SPH_ERR_ARG = 1
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
 def _ctx(capi, rows, variable=False):
     gas, sinks = ic.split_rows(rows)
-    ctx = capi.Context(device=0, variable=variable)
-    ctx.upload(gas)
-    ctx.set_sinks(sinks)
-    return ctx, gas, sinks
-
-
-def _pos(gas):
-    return np.stack([gas["x"], gas["y"], gas["z"]], axis=1)
+    return make_context(capi, gas, sinks, variable=variable), gas, sinks
 
 
 def _check_field(got, ref, pos, m, h, lo, hi, n):
@@ -102,7 +89,7 @@ def test_grid_fixed_h_vs_brute_force(capi, case):
     ctx, gas, _ = _ctx(capi, rows)
     got = ctx.render_density(n, bounds=(lo, hi), h=h)
     assert got.shape == n
-    pos, m = _pos(gas), gas["m"]
+    pos, m = positions(gas), gas["m"]
     ref = render_ref.grid_brute(pos, m, h, lo, hi, n)
     _check_field(got, ref, pos, m, h, lo, hi, n)
     ctx.close()
@@ -232,7 +219,7 @@ def test_selection_sinks_ghosts_clip_and_auto_bounds(capi):
     g = {k: v.copy() for k, v in gas.items()}
     g["x"][:3] = cl[0]; g["y"][3:6] = ch[1]
     c5 = capi.Context(device=0); c5.upload(g)
-    p5 = _pos(g)
+    p5 = positions(g)
     keep = np.all((p5 > cl) & (p5 < ch), axis=1)
     img = c5.render_density((20, 18, 6), clip=(cl, ch), h=1.25)
     lo5, hi5 = c5.render_bounds

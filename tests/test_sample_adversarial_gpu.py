@@ -12,6 +12,7 @@ reference's: a source that grazes a point at q = 2 - 2^-19 adds 2^-59 of its wei
 import numpy as np
 import pytest
 
+from gpu_support import capi, make_context
 import sample_ref
 import search_sets as S
 import trace_ref
@@ -19,19 +20,8 @@ import trace_ref
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
 def _ctx(capi, s, density=False):
-    ctx = capi.Context(device=0, **s.context_kw())
-    ctx.upload(s.gas)
-    if density:
-        ctx.density()
-    return ctx
+    return make_context(capi, s.gas, density=density, **s.context_kw())
 
 
 def _ratio(err, bound):

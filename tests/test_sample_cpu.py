@@ -4,36 +4,25 @@ selection, zeros and NaN rules, the point-set helpers' geometry, and the command
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_support import c_layout, containing, fortran_links, needs_fc, needs_hipcc, resource_usage
 from conftest import ROOT
 import profile_ref
 import render_field_ref
 import sample_ref
 from summersph_amd import sample as smp
 
-FC = shutil.which("amdflang") or "/opt/rocm/bin/amdflang"
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "summersph_amd", "csrc")
 FIELDS = ["clip_lo", "clip_hi", "h", "fields", "n_fields", "weight", "flags", "reserved"]
 
 
 def test_sample_desc_layout_matches_header(tmp_path):
     from summersph_amd import capi
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "summersph.h"\nint main(void) {\n'
-                   '  printf("size %zu\\n", sizeof(sph_sample_desc));\n' +
-                   "".join(f'  printf("{f} %zu\\n", offsetof(sph_sample_desc, {f}));\n' for f in FIELDS) +
-                   '  printf("consts %d %d %d %d %d\\n", SPH_SAMPLE_NORMALISE, SPH_SAMPLE_MAX_FIELDS, SPH_SAMPLE_VALUES,\n'
-                   '         SPH_RENDER_WEIGHT_MASS, SPH_RENDER_WEIGHT_VOLUME);\n  printf("abi %d\\n", SPH_ABI_VERSION);\n'
-                   '  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = c_layout(tmp_path, "sph_sample_desc", FIELDS,
+                   ['printf("consts %d %d %d %d %d\\n", SPH_SAMPLE_NORMALISE, SPH_SAMPLE_MAX_FIELDS, SPH_SAMPLE_VALUES,\n'
+                    '         SPH_RENDER_WEIGHT_MASS, SPH_RENDER_WEIGHT_VOLUME);', 'printf("abi %d\\n", SPH_ABI_VERSION);'])
     assert int(got["size"]) == ctypes.sizeof(capi.SampleDesc) == 88
     for f in FIELDS:
         assert int(got[f]) == getattr(capi.SampleDesc, f).offset, f
@@ -56,13 +45,9 @@ def test_sample_desc_layout_matches_header(tmp_path):
         capi.sample_desc(("u",), weight="number")
 
 
-@pytest.mark.skipif(not os.path.exists(FC), reason="needs amdflang")
+@needs_fc
 def test_fortran_binding_compiles_and_links(tmp_path):
-    lib = os.path.join(ROOT, "summersph_amd", "libsummersph_hip.so")
-    if not os.path.exists(lib):
-        subprocess.run(["make", "-C", CSRC], check=True, stdout=subprocess.DEVNULL)
-    caller = tmp_path / "sample_caller.f90"
-    caller.write_text("""program sample_caller
+    fortran_links(tmp_path, "sample_caller", """program sample_caller
   use, intrinsic :: iso_c_binding
   use, intrinsic :: ieee_arithmetic
   use sph_hip_binding
@@ -90,33 +75,11 @@ def test_fortran_binding_compiles_and_links(tmp_path):
   print *, st, counts
 end program sample_caller
 """)
-    binding = os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")
-    exe = tmp_path / "sample_caller"
-    subprocess.run([FC, "-O1", binding, str(caller), "-L" + os.path.dirname(lib), "-lsummersph_hip",
-                    "-Wl,-rpath," + os.path.dirname(lib), "-o", str(exe)], check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
-    assert exe.exists()
 
 
-def _resource_usage():
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "sample.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, check=True, capture_output=True, text=True).stderr
-    kernels, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1) if "sample_" in m.group(1) else None
-            if cur:
-                kernels[cur] = {}
-            continue
-        m = re.search(r"remark: +([^:\[]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if cur and m:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_sample_kernels_fit_the_register_budget():
-    k = _resource_usage()
+    k = resource_usage("sample.hip", containing("sample_"))
     for name in ("sample_select", "sample_levels", "sample_no_sources", "sample_keys", "sample_records", "sample_tails",
                  "sample_point_keys"):
         assert sum(name in n for n in k) == 1, name

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_golden
+from gpu_support import capi, field_positions, golden_gas, make_context, over_defaults, ref_h
 import render_field_ref
 import sample_ref
 from summersph_amd import ic, txtio
@@ -28,36 +29,8 @@ TOL_NUM = 1e-12
 TOL_DEN = 1e-13
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
 def _ctx(capi, gas, sinks=None, variable=False, flags=0, density=True):
-    if flags:
-        flags |= capi.default_params(variable).flags
-    ctx = capi.Context(device=0, variable=variable, **({"flags": flags} if flags else {}))
-    ctx.upload(gas)
-    if sinks is not None:
-        ctx.set_sinks(sinks)
-    if density:
-        ctx.density()
-    return ctx
-
-
-def _golden_gas(name):
-    e = load_golden(name)
-    return ic.split_rows(e["ic"])
-
-
-def _pos(ctx):
-    return np.stack([ctx.field("x"), ctx.field("y"), ctx.field("z")], axis=1)
-
-
-def _ref_h(ctx, capi):
-    return ctx.field("h") if ctx.params.flags & capi.FLAG_VARIABLE_H else float(ctx.params.h)
+    return make_context(capi, gas, sinks, variable=variable, flags=over_defaults(capi, flags, variable), density=density)
 
 
 def _close(got, want, tol, what=""):
@@ -97,7 +70,7 @@ def _set(capi, name):
     if name == "discvar20000":
         gas, sinks = ic.split_rows(ic.keplerian_disc_var(20000))
         return _ctx(capi, gas, sinks, variable=True)
-    gas, sinks = _golden_gas(name)
+    gas, sinks = golden_gas(name)
     return _ctx(capi, gas, sinks, variable="discv" in name)
 
 
@@ -105,8 +78,8 @@ def _set(capi, name):
 def test_parity_with_the_restatement(capi, name):
     ctx = _set(capi, name)
     n = ctx.n
-    pos, m, rho = _pos(ctx), ctx.field("m"), ctx.field("rho")
-    h = _ref_h(ctx, capi)
+    pos, m, rho = field_positions(ctx), ctx.field("m"), ctx.field("rho")
+    h = ref_h(ctx, capi)
     pts, n_far = _points(pos, h)
     rng = np.random.default_rng(3)
     vals = np.stack([rng.normal(size=n), pos[:, 0] * pos[:, 1]])
@@ -188,7 +161,7 @@ def test_order_rule_bitwise(capi, variable):
     import torch
     gas, sinks = ic.split_rows(ic.keplerian_disc_var(40000, seed=15) if variable else ic.keplerian_disc(40000, seed=15))
     a = _ctx(capi, gas, sinks, variable=variable, density=False)
-    pos = _pos(a)
+    pos = field_positions(a)
     pts, _ = _points(pos[::7], gas["h"] if variable else 2.5, seed=9)
     pts[11] = [np.nan, 0.0, 0.0]
     pts[12] = [0.0, np.inf, 0.0]
@@ -242,7 +215,7 @@ def test_smoothing_lengths_over_ten_octaves(capi):
     ctx = _ctx(capi, gas, sinks, variable=True, density=False)
     h = ctx.field("h")
     assert np.array_equal(h, gas["h"]) and np.log2(h.max() / h.min()) >= 10.0
-    pos, m = _pos(ctx), ctx.field("m")
+    pos, m = field_positions(ctx), ctx.field("m")
     pts = np.concatenate([rng.uniform(pos.min(axis=0) - 2.0, pos.max(axis=0) + 2.0, (2000, 3)), pos[:1000]])
     vals = np.stack([np.sin(pos[:, 0]), pos[:, 1] - pos[:, 2]])
     levels = np.unique(h.view(np.uint64) >> np.uint64(51)).size    # occupied half octaves
@@ -267,7 +240,7 @@ def test_smoothing_lengths_over_ten_octaves(capi):
 def test_constant_field(capi, variable):
     gas, sinks = ic.split_rows(ic.keplerian_disc_var(20000, seed=6) if variable else ic.keplerian_disc(20000, seed=6))
     ctx = _ctx(capi, gas, sinks, variable=variable)
-    pts, n_far = _points(_pos(ctx), _ref_h(ctx, capi))
+    pts, n_far = _points(field_positions(ctx), ref_h(ctx, capi))
     for weight in ("mass", "volume"):
         out, den = ctx.sample(pts, fields=(capi.SAMPLE_VALUES,), values=np.full(ctx.n, 3.0), weight=weight, normalise=True,
                               weight_out=True)
@@ -282,7 +255,7 @@ def test_ranks_add_up(capi):
     gas, sinks = ic.split_rows(ic.keplerian_disc_var(30000, seed=17))
     n = gas["x"].size
     one = _ctx(capi, gas, sinks, variable=True, density=False)
-    pts, _ = _points(_pos(one), gas["h"])
+    pts, _ = _points(field_positions(one), gas["h"])
     kw = {"fields": ("vx", "u"), "weight_out": True, "counts": True}
     o1, d1, c1 = one.sample(pts, **kw)
     one.close()
@@ -314,7 +287,7 @@ def test_after_accrete_and_cull(capi):
     ctx = _ctx(capi, gas, sinks)
     ctx.forces()
     assert ctx.accrete_and_cull() > 0 and ctx.n < 20000
-    pos = _pos(ctx)
+    pos = field_positions(ctx)
     vals = np.stack([pos[:, 0] + 2.0 * pos[:, 1], np.arange(ctx.n, dtype=np.float64)])
     pts, _ = _points(pos, 2.5)
     out, den, cnt = ctx.sample(pts, fields=(capi.SAMPLE_VALUES, capi.SAMPLE_VALUES, "rho"), values=vals, weight_out=True, counts=True)
@@ -459,7 +432,7 @@ def _smoothed_midplane_density(sigma, h, H):
 def test_million_particles_million_points(capi):
     gas, sinks = ic.split_rows(ic.keplerian_disc(1_000_000, seed=5))
     ctx = _ctx(capi, gas, sinks, density=False)
-    pos, m = _pos(ctx), ctx.field("m")
+    pos, m = field_positions(ctx), ctx.field("m")
     R = np.hypot(pos[:, 0], pos[:, 1])
     r_in, r_out = 10.0, float(R.max())
     polar, shape = smp.polar_points(30.0, r_out - 30.0, 512, 2048)

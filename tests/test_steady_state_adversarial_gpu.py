@@ -70,6 +70,7 @@ import pytest
 import steady_sets as S
 import varh_ref as VR
 from conftest import rel_err
+from gpu_support import capi, make_context
 
 pytestmark = pytest.mark.gpu
 
@@ -78,21 +79,8 @@ FLAGSETS = ("default", "no_whole_tile", "no_lds_tiles")
 STATE8 = "x y z vx vy vz u alpha".split()
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
 def flags_of(capi, flagset):
     return {"default": 0, "no_whole_tile": capi.FLAG_NO_WHOLE_TILE, "no_lds_tiles": capi.FLAG_NO_LDS_TILES}[flagset]
-
-
-def make_ctx(capi, gas, flags=0):
-    ctx = capi.Context(device=0, flags=flags)
-    ctx.upload(gas)
-    return ctx
 
 
 def download(ctx, names):
@@ -106,7 +94,7 @@ def steady_run(capi, name, flagset, checks=True):
     s = S.build(name)
     gas, clump = s["gas"], s["clump"]
     n = gas["x"].size
-    ctx = make_ctx(capi, gas, flags_of(capi, flagset))
+    ctx = make_context(capi, gas, flags=flags_of(capi, flagset))
     rec = dict(dts=[], pos=[S.positions(gas)], stats=[], kind=[], bytes=[], worst=dict(rho=0.0, rates=0.0, oracle=0.0),
                untiled=flagset == "no_lds_tiles")
     if checks:
@@ -278,7 +266,7 @@ def test_contraction_as_one_run_chains_its_own_dt_without_waiting(capi):
     states, dts, t_ref = S.run_trajectory(name)
     caps = S.capacity_replay([S.pair_stats(S.positions(st))["longest"] for st in states])
     assert sum(c["regrown"] for c in caps) >= 2
-    ctx = make_ctx(capi, s["gas"])
+    ctx = make_context(capi, s["gas"])
     ctx.density(); ctx.forces()                      # the first build, with its own waits (the run starts with the same calls)
     before = ctx.stats()
     assert before.nlist_builds == 1 and before.nlist_capacity == S.NL_CAP0
@@ -426,7 +414,7 @@ def sheet_run(capi, flagset):
     from test_whole_tile_gpu import FIELDS
     name = "sheet_puffing_up"
     s = S.build(name)
-    ctx = make_ctx(capi, s["gas"], flags_of(capi, flagset))
+    ctx = make_context(capi, s["gas"], flags=flags_of(capi, flagset))
     ctx.density(); ctx.forces()
     st0 = ctx.stats()
     rec = dict(first=download(ctx, FIELDS), fits=[st0.tile_fit_pct_forces], syncs=[st0.host_syncs], pos=[S.positions(s["gas"])],
@@ -541,7 +529,7 @@ def test_too_fast_mid_run_raises_at_the_next_build(capi, flagset):
     """the overflowing build is followed by more steps within the same call: the next build reads its report and refuses"""
     name = "contraction_too_fast_mid"
     s = S.build(name)
-    ctx = make_ctx(capi, s["gas"], flags_of(capi, flagset))
+    ctx = make_context(capi, s["gas"], flags=flags_of(capi, flagset))
     with pytest.raises(capi.SphError) as err:
         ctx.run(len(s["dts"]), s["dts"][0], 0.0)
     # ctx.step along the schedule could not reach this check: every call that returns drains the reports, so step 1 itself
@@ -560,7 +548,7 @@ def test_too_fast_last_build_raises_from_the_call_that_returns(capi, flagset):
     """the overflowing build is the last of the call: drain_reports, at the end of that very call"""
     name = "contraction_too_fast_last"
     s = S.build(name)
-    ctx = make_ctx(capi, s["gas"], flags_of(capi, flagset))
+    ctx = make_context(capi, s["gas"], flags=flags_of(capi, flagset))
     ctx.density(); ctx.forces()
     assert ctx.stats().nlist_capacity == S.NL_CAP0 and ctx.stats().nlist_max <= 72
     with pytest.raises(capi.SphError) as err:

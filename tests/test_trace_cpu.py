@@ -5,36 +5,26 @@ status of every seed: no stage evaluation of its seed sets has a den that roundi
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_support import c_layout, containing, fortran_links, needs_fc, needs_hipcc, resource_usage
 from conftest import ROOT, load_golden
 import trace_ref
 from summersph_amd import ic
 from summersph_amd import trace as trc
 
-FC = shutil.which("amdflang") or "/opt/rocm/bin/amdflang"
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "summersph_amd", "csrc")
 FIELDS = ["clip_lo", "clip_hi", "h", "box_lo", "box_hi", "ds", "omega", "centre", "normal", "fields", "carry", "weight", "n_steps",
           "stride", "flags", "reserved"]
 
 
 def test_trace_desc_layout_matches_header(tmp_path):
     from summersph_amd import capi
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "summersph.h"\nint main(void) {\n'
-                   '  printf("size %zu\\n", sizeof(sph_trace_desc));\n' +
-                   "".join(f'  printf("{f} %zu\\n", offsetof(sph_trace_desc, {f}));\n' for f in FIELDS) +
-                   '  printf("consts %d %d %d %d\\n", SPH_TRACE_ARCLENGTH, SPH_TRACE_PLANAR, SPH_TRACE_VALUES, SPH_TRACE_NONE);\n'
-                   '  printf("codes %d %d %d %d %d\\n", SPH_TRACE_DONE, SPH_TRACE_LEFT_GAS, SPH_TRACE_LEFT_BOX, SPH_TRACE_STAGNANT,\n'
-                   '         SPH_TRACE_NONFINITE);\n  printf("abi %d\\n", SPH_ABI_VERSION);\n  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = c_layout(tmp_path, "sph_trace_desc", FIELDS,
+                   ['printf("consts %d %d %d %d\\n", SPH_TRACE_ARCLENGTH, SPH_TRACE_PLANAR, SPH_TRACE_VALUES, SPH_TRACE_NONE);',
+                    'printf("codes %d %d %d %d %d\\n", SPH_TRACE_DONE, SPH_TRACE_LEFT_GAS, SPH_TRACE_LEFT_BOX, SPH_TRACE_STAGNANT,\n'
+                    '         SPH_TRACE_NONFINITE);', 'printf("abi %d\\n", SPH_ABI_VERSION);'])
     assert int(got["size"]) == ctypes.sizeof(capi.TraceDesc) == 224
     for f in FIELDS:
         assert int(got[f]) == getattr(capi.TraceDesc, f).offset, f
@@ -64,13 +54,9 @@ def test_trace_desc_layout_matches_header(tmp_path):
         capi.trace_desc(3, 1.0, weight="number")
 
 
-@pytest.mark.skipif(not os.path.exists(FC), reason="needs amdflang")
+@needs_fc
 def test_fortran_binding_compiles_and_links(tmp_path):
-    lib = os.path.join(ROOT, "summersph_amd", "libsummersph_hip.so")
-    if not os.path.exists(lib):
-        subprocess.run(["make", "-C", CSRC], check=True, stdout=subprocess.DEVNULL)
-    caller = tmp_path / "trace_caller.f90"
-    caller.write_text("""program trace_caller
+    fortran_links(tmp_path, "trace_caller", """program trace_caller
   use, intrinsic :: iso_c_binding
   use, intrinsic :: ieee_arithmetic
   use sph_hip_binding
@@ -108,33 +94,11 @@ def test_fortran_binding_compiles_and_links(tmp_path):
   print *, st, counts
 end program trace_caller
 """)
-    binding = os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")
-    exe = tmp_path / "trace_caller"
-    subprocess.run([FC, "-O1", binding, str(caller), "-L" + os.path.dirname(lib), "-lsummersph_hip",
-                    "-Wl,-rpath," + os.path.dirname(lib), "-o", str(exe)], check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
-    assert exe.exists()
 
 
-def _resource_usage():
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "trace.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, check=True, capture_output=True, text=True).stderr
-    kernels, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1) if "trace_" in m.group(1) else None
-            if cur:
-                kernels[cur] = {}
-            continue
-        m = re.search(r"remark: +([^:\[]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if cur and m:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_trace_kernels_fit_the_register_budget():
-    k = _resource_usage()
+    k = resource_usage("trace.hip", containing("trace_"))
     assert sum("trace_seed_keys" in n for n in k) == 1
     walks = [n for n in k if "trace_walk" in n]
     assert len(walks) == 4, walks

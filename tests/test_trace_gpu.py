@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_golden
+from gpu_support import capi, make_context, over_defaults, positions
 import trace_ref
 from summersph_amd import ic, txtio
 from summersph_amd import trace as trc
@@ -25,32 +26,13 @@ SPH_ERR_STATE = 5
 TOL_NUM = 1e-12
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
 def _ctx(capi, gas, sinks=None, variable=False, flags=0, density=True):
-    if flags:
-        flags |= capi.default_params(variable).flags
-    ctx = capi.Context(device=0, variable=variable, **({"flags": flags} if flags else {}))
-    ctx.upload(gas)
-    if sinks is not None:
-        ctx.set_sinks(sinks)
-    if density:
-        ctx.density()
-    return ctx
+    return make_context(capi, gas, sinks, variable=variable, flags=over_defaults(capi, flags, variable), density=density)
 
 
 def _golden(capi, name, density=True):
     gas, sinks = ic.split_rows(load_golden(name)["ic"])
     return _ctx(capi, gas, sinks, variable="discv" in name, density=density), gas, sinks
-
-
-def _pos(gas):
-    return np.stack([gas["x"], gas["y"], gas["z"]], axis=1)
 
 
 def _same(a, b):
@@ -71,7 +53,7 @@ def _sampler(ctx, fields, values=None, carry=None, **kw):
 @pytest.mark.parametrize("name", ["disc3000_eval", "discv3000_eval", "bin2000_eval"])
 def test_bitwise_against_the_composition(capi, name):
     ctx, gas, sinks = _golden(capi, name)
-    pos = _pos(gas)
+    pos = positions(gas)
     n = ctx.n
     h = gas["h"] if "h" in gas else float(ctx.params.h)
     seeds = trace_ref.parity_seeds(pos, h, 11, n=257, n_far=16)
@@ -135,7 +117,7 @@ def test_order_rule_bitwise(capi, variable):
     name = "discv3000_eval" if variable else "disc3000_eval"
     a, gas, sinks = _golden(capi, name, density=False)
     h0 = gas["h"] if variable else 2.5
-    seeds = trace_ref.parity_seeds(_pos(gas), h0, 21, n=65, n_far=6)
+    seeds = trace_ref.parity_seeds(positions(gas), h0, 21, n=65, n_far=6)
     seeds[7] = [0.0, np.inf, 0.0]
     kw = dict(arclength=True, carry="u", omega=(0.0, 0.0, 0.004), normal=(0.0, 0.1, 1.0), stride=2, counts=True)
     r0 = a.trace(seeds, 8, 0.6, **kw)
@@ -174,7 +156,7 @@ def test_order_rule_bitwise(capi, variable):
 
 def test_stride(capi):
     ctx, gas, _ = _golden(capi, "discv3000_eval", density=False)
-    seeds = trace_ref.parity_seeds(_pos(gas), gas["h"], 31, n=100, n_far=10)
+    seeds = trace_ref.parity_seeds(positions(gas), gas["h"], 31, n=100, n_far=10)
     kw = dict(carry="u", box=((-30.0, -30.0, -6.0), (30.0, 30.0, 6.0)))
     full = ctx.trace(seeds, 12, 8.0, **kw)
     assert len(set(full[2].tolist())) > 3                            # lines that stop at different vertices
@@ -187,7 +169,7 @@ def test_stride(capi):
 
 def test_stops(capi):
     ctx, gas, _ = _golden(capi, "disc3000_eval", density=False)
-    pos, n = _pos(gas), ctx.n
+    pos, n = positions(gas), ctx.n
     lo, hi = pos.min(axis=0), pos.max(axis=0)
     mid = 0.5 * (lo + hi)
     h = float(ctx.params.h)
@@ -238,7 +220,7 @@ def test_stops(capi):
 def test_constant_field(capi, variable):
     """independent of the restatement: in a constant field c every RK4 step adds ds c, with ARCLENGTH ds c / |c|"""
     ctx, gas, _ = _golden(capi, "discv3000_eval" if variable else "disc3000_eval", density=False)
-    pos, n, S, ds = _pos(gas), ctx.n, 16, 0.25
+    pos, n, S, ds = positions(gas), ctx.n, 16, 0.25
     seeds = pos[::30] + 0.1
     cvec = np.array([0.3, -0.2, 0.1])
     V = capi.TRACE_VALUES

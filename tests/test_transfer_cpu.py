@@ -5,19 +5,15 @@ command line's parsing."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_support import c_layout, containing, fortran_links, needs_fc, needs_hipcc, resource_usage
 from conftest import ROOT
 import transfer_ref
 from summersph_amd import cube as cb
 
-FC = shutil.which("amdflang") or "/opt/rocm/bin/amdflang"
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "summersph_amd", "csrc")
 FIELDS = ["rot", "centre", "lo", "hi", "clip_lo", "clip_hi", "h", "kappa_scale", "tau_surface", "tau_max", "background", "n_u",
           "n_v", "source", "kappa", "flags", "reserved"]
 FLIP = np.diag([-1.0, 1.0, -1.0])                    # (u^, v^, w^) -> (-u^, v^, -w^): the view from behind
@@ -25,15 +21,8 @@ FLIP = np.diag([-1.0, 1.0, -1.0])                    # (u^, v^, w^) -> (-u^, v^,
 
 def test_transfer_desc_layout_matches_header(tmp_path):
     from summersph_amd import capi
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "summersph.h"\nint main(void) {\n'
-                   '  printf("size %zu\\n", sizeof(sph_transfer_desc));\n' +
-                   "".join(f'  printf("{f} %zu\\n", offsetof(sph_transfer_desc, {f}));\n' for f in FIELDS) +
-                   '  printf("consts %d %d\\n", SPH_TRANSFER_VALUES, SPH_TRANSFER_ONE);\n  printf("abi %d\\n", SPH_ABI_VERSION);\n'
-                   '  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = c_layout(tmp_path, "sph_transfer_desc", FIELDS,
+                   ['printf("consts %d %d\\n", SPH_TRANSFER_VALUES, SPH_TRANSFER_ONE);', 'printf("abi %d\\n", SPH_ABI_VERSION);'])
     assert int(got["size"]) == ctypes.sizeof(capi.TransferDesc) == 240
     for f in FIELDS:
         assert int(got[f]) == getattr(capi.TransferDesc, f).offset, f
@@ -58,13 +47,9 @@ def test_transfer_desc_layout_matches_header(tmp_path):
         capi.transfer_desc((1, 2, 3), ((0, 0), (1, 1)))
 
 
-@pytest.mark.skipif(not os.path.exists(FC), reason="needs amdflang")
+@needs_fc
 def test_fortran_binding_compiles_and_links(tmp_path):
-    lib = os.path.join(ROOT, "summersph_amd", "libsummersph_hip.so")
-    if not os.path.exists(lib):
-        subprocess.run(["make", "-C", CSRC], check=True, stdout=subprocess.DEVNULL)
-    caller = tmp_path / "transfer_caller.f90"
-    caller.write_text("""program transfer_caller
+    fortran_links(tmp_path, "transfer_caller", """program transfer_caller
   use, intrinsic :: iso_c_binding
   use, intrinsic :: ieee_arithmetic
   use sph_hip_binding
@@ -99,33 +84,11 @@ def test_fortran_binding_compiles_and_links(tmp_path):
   print *, st
 end program transfer_caller
 """)
-    binding = os.path.join(ROOT, "summersph_amd", "host", "sph_hip_binding.f90")
-    exe = tmp_path / "transfer_caller"
-    subprocess.run([FC, "-O1", binding, str(caller), "-L" + os.path.dirname(lib), "-lsummersph_hip",
-                    "-Wl,-rpath," + os.path.dirname(lib), "-o", str(exe)], check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
-    assert exe.exists()
 
 
-def _resource_usage():
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "transfer.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, check=True, capture_output=True, text=True).stderr
-    kernels, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1) if any(s in m.group(1) for s in ("transfer_", "stats_final", "start_table")) else None
-            if cur:
-                kernels[cur] = {}
-            continue
-        m = re.search(r"remark: +([^:\[]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if cur and m:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_transfer_kernels_fit_the_register_budget():
-    k = _resource_usage()
+    k = resource_usage("transfer.hip", containing("transfer_", "stats_final", "start_table"))
     names = ("transfer_stats_partial", "stats_final", "transfer_count", "transfer_select", "transfer_depth_keys",
              "transfer_records", "transfer_emit", "start_table", "transfer_gather")
     for name in names:

@@ -10,6 +10,7 @@ tau_surface (plane 3) or tau_max (every plane: the node stops one particle earli
 that threshold; such nodes must be at most 1 % of the nodes the reference lights, which is asserted on the reference
 alone."""
 import ctypes as C
+import functools
 import json
 import subprocess
 import sys
@@ -19,6 +20,7 @@ import pytest
 
 from conftest import ROOT, load_golden
 import cube_ref
+from gpu_support import capi, make_context
 import transfer_ref
 from summersph_amd import cube as cb
 from summersph_amd import ic, txtio
@@ -31,21 +33,7 @@ ALONG_X = np.array([[0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [1.0, 0.0, 0.0]])       # 
 FLIP = np.diag([-1.0, 1.0, -1.0])                                              # (u^, v^, w^) -> (-u^, v^, -w^)
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
-def _ctx(capi, gas, sinks=None, variable=False, density=True):
-    ctx = capi.Context(device=0, variable=variable)
-    ctx.upload(gas)
-    if sinks is not None:
-        ctx.set_sinks(sinks)
-    if density:
-        ctx.density()
-    return ctx
+_ctx = functools.partial(make_context, density=True)      # every call here reads rho unless it says density=False
 
 
 def _set(capi, name):

@@ -25,6 +25,7 @@ import pytest
 import varh_ref as VR
 import varh_sets as S
 from conftest import rel_err
+from gpu_support import capi, make_context
 
 pytestmark = pytest.mark.gpu
 
@@ -36,21 +37,12 @@ BIG = ["lattice17", "lattice33", "lattice_ties", "sheet", "plummer", "sparse_cub
 FLAGSETS = ("default", "no_reflag", "hashed")
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
-
-
 def flags_of(capi, flagset):
     return {"default": 0, "no_reflag": capi.FLAG_NO_REFLAG, "hashed": capi.FLAG_HASHED_GRID}[flagset]
 
 
 def make_ctx(capi, gas, flags=0):
-    ctx = capi.Context(device=0, variable=True, flags=capi.FLAG_VARIABLE_H | flags)
-    ctx.upload(gas)
-    return ctx
+    return make_context(capi, gas, variable=True, flags=capi.FLAG_VARIABLE_H | flags)
 
 
 def mode_of(name):

@@ -7,6 +7,7 @@ test_parity_gpu.py checks (it runs whichever kernels the context picks)."""
 import numpy as np
 import pytest
 
+from gpu_support import capi
 from summersph_amd import ic
 
 pytestmark = pytest.mark.gpu
@@ -18,13 +19,6 @@ def same(a, b, f, tol=1e-14):
     if f in BITWISE:
         return np.array_equal(a, b)
     return float(np.max(np.abs(a - b))) <= tol * float(np.max(np.abs(b)))
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from summersph_amd import capi as m
-    m.load()
-    return m
 
 
 def evaluate(capi, gas, sinks, flags, steps=0):
