@@ -1275,6 +1275,103 @@ int sph_binned_dev(sph_ctx *ctx, const sph_binned_desc *d, const double *d_value
                    int64_t n_sums, int64_t *d_counts);
 int sph_binned_edges(const sph_binned_desc *d, const double *edges, int32_t axis, double *out);
 
+/* ---- pair sums: per bin of the separation r (or of r / h_i), the count of the ordered pairs (i, j), j != i, of the owned gas
+ *      and exact sums over them -- the pair distribution g(r / h) (the pairing instability, particle noise), the mean pairwise
+ *      radial velocity, the second- and third-order structure functions of the velocity and the variogram of any scalar ----
+ * Sources  j: the owned gas (ghosts and sinks excluded) that is usable: finite x, y, z and finite every requested quantity --
+ *          the A_k, m with SPH_PAIRS_W_MASS, vx vy vz with SPH_PAIRS_VELOCITY, h (also > 0) with SPH_PAIRS_SCALE_H.  An owned
+ *          gas particle that is not usable is neither source nor target and is counted in counts[2].
+ * Targets  i: the sources strictly inside the clip box (clip_lo < r < clip_hi on every axis, the renders' rule; -inf / +inf
+ *          for no clip) whose original id (sph_download_field's order) has id % target_stride == target_phase.  Sources
+ *          outside the clip box still act as sources.  The phases 0 .. stride - 1 partition the targets: a single phase is an
+ *          unbiased sample at 1 / stride of the cost.
+ * A_k      up to SPH_PAIRS_MAX_Q quantities, each an SPH_F_* id, read as sph_download_field reads it (SPH_ERR_STATE exactly
+ *          when that call would refuse the field as stale), or SPH_PAIRS_ROW(k): row k of values, values[k * n + id], n =
+ *          sph_count -- sph_binned's sources.  values is host memory in the host form and device memory in the device form;
+ *          NULL if and only if n_rows == 0.
+ * Pair     dx = x_j - x_i (dy, dz alike), d2 = (dx * dx + dy * dy) + dz * dz, r = sqrt(d2); the binned variable is r, or with
+ *          SPH_PAIRS_SCALE_H r / h_i (an IEEE division; h_i the target's h, params.h on the fixed-h path).  No fused
+ *          multiply-adds anywhere.  The pair is selected when the variable lies in [edge[0], edge[n_bins]); its bin b has
+ *          edge[b] <= variable < edge[b + 1] against the table, never by a formula alone.
+ * Edges    sph_binned's: edge[k] = lo + (k (hi - lo)) / n_bins, or with SPH_PAIRS_LOG lo pow(hi / lo, k / n_bins);
+ *          edge[n_bins] = hi exactly.  With SPH_PAIRS_EDGES the table is the caller's: n_bins + 1 strictly increasing finite
+ *          doubles in edges (host memory in both forms), lo / hi ignored.  sph_pairs_edges returns the table the call will
+ *          use (pure host code: no context, no device) and refuses what the call refuses of the descriptor and the table.
+ * Weight   w = w_i * w_j with w_p = 1 (SPH_PAIRS_W_ONE) or m_p (SPH_PAIRS_W_MASS).
+ * Sums     sums[b * nsum + s], nsum = 2 + 2 n_q + (4 with SPH_PAIRS_VELOCITY), n_out == n_bins nsum:
+ *            s = 0                N, the count
+ *            s = 1                sum w
+ *            s = 2 + k            sum w * dA_k,           dA_k = A_k(j) - A_k(i)
+ *            s = 2 + n_q + k      sum w * (dA_k * dA_k)
+ *          and with SPH_PAIRS_VELOCITY, s0 = 2 + 2 n_q, dv = v_j - v_i per component,
+ *          u = ((dvx * dx + dvy * dy) + dvz * dz) / r, u = 0 where r == 0, u2 = u * u:
+ *            s = s0               sum w * u
+ *            s = s0 + 1           sum w * u2
+ *            s = s0 + 2           sum w * (u2 * u)
+ *            s = s0 + 3           sum w * ((dvx * dvx + dvy * dvy) + dvz * dvz)
+ * Exact    every float sum is accumulated exactly in 128-bit fixed point.  A first pass takes order-free maxima over the
+ *          sources: w_max = max |w_p|, A_k,max = max |A_k|, v_max = the largest |v| component.  With W2 = w_max * w_max,
+ *          D_k = 2 * A_k,max and V = 4 * v_max the bounds B_s are ("Bounds"):
+ *            s = 1  W2;   s = 2 + k  W2 * D_k;   s = 2 + n_q + k  W2 * (D_k * D_k);
+ *            s = s0  W2 * V;   s = s0 + 1  W2 * (V * V);   s = s0 + 2  W2 * ((V * V) * V);   s = s0 + 3  W2 * (V * V)
+ *          (|u| <= sqrt(3) * 2 v_max < V, |dv|^2 <= 12 v_max^2 < V * V; rounding is monotone, so no term exceeds its bound).
+ *          e_s is the binary exponent with B_s < 2^e_s: the exponent frexp returns (0 for B_s = 0); e_0 = 62.  A term is
+ *          formed in double as written above, multiplied by 2^(62 - e_s) (exact), rounded half-even to a 64-bit integer (its
+ *          magnitude is < 2^62) and added into a 128-bit two's-complement integer: an error of at most half a quantum
+ *          2^(e_s - 62) per term, none from the addition; B_s = 0 gives the sum 0.  N is a plain 64-bit count.  A bin's
+ *          accumulator overflows only beyond 2^65 terms.  The bounds must be finite.
+ *          raw[2 (b * nsum + s)] is the low and raw[2 (b * nsum + s) + 1] the high 64-bit limb, exps[s] = e_s; sums[..] is
+ *          limb value * 2^(e_s - 62), correctly rounded (once).  Raw results with equal exps add exactly as 128-bit integers
+ *          (phases, clip boxes, ranks); sph_pairs_finish(d, exps, raw, sums) turns limbs into the same doubles (pure host
+ *          code; it reads n_bins, n_q and flags of the descriptor).
+ * Counts   counts[3] (may be NULL; device memory in the device form): targets, sources, owned gas not usable.  sources +
+ *          not usable = the owned gas.
+ * Order    none: integer addition is associative.  sums, raw, exps and counts are bitwise independent of the context's
+ *          sorted order, of the dense or hashed grid, of the launch shape, of the host or device form and of repeated calls.
+ *          No float atomics.
+ * Search   groups' hashed cell table at cell edge r_max (1 + 1e-6), r_max = edge[n_bins] (times the targets' largest h with
+ *          SPH_PAIRS_SCALE_H), enlarged on the device where an axis would need more than 2^21 - 8 cells; the cost is that of
+ *          the 27 cells around every target.
+ * cost     host form: one read-back (limbs, exponents, counts; raw and exps may be NULL); device form: ordered on the
+ *          context's stream, no synchronisation (but one when the scratch has to grow); d_raw, d_exps, d_counts may be NULL.
+ *          The scratch is the analysis calls' shared buffer.  No state, field, statistic (other than device_bytes), flag,
+ *          grid, list or dt of the context changes.
+ * SPH_ERR_ARG: null descriptor or output, n_bins outside 1 .. SPH_PAIRS_MAX_BINS, n_out != n_bins nsum, n_q outside 0 ..
+ * SPH_PAIRS_MAX_Q, a source that is neither an SPH_F_* id nor a row below n_rows, n_rows outside 0 .. 16, values NULL with
+ * n_rows > 0 or given with n_rows == 0, edges NULL with SPH_PAIRS_EDGES or given without, a caller's table that is not strictly
+ * increasing or not finite, a non-finite lo or hi, lo >= hi, LOG with lo <= 0, LOG with EDGES, computed edges that coincide,
+ * target_stride < 1, target_phase outside 0 .. target_stride - 1, a NaN in the clip box, an unknown weight, unknown flags,
+ * reserved != 0; nothing is written then.  SPH_ERR_STATE: a stale field.  SPH_ERR_NOMEM: the scratch does not fit.  An empty
+ * context or an empty selection gives zero sums. */
+#define SPH_PAIRS_MAX_Q      4
+#define SPH_PAIRS_MAX_BINS   1024
+#define SPH_PAIRS_ROW(k)     (-1 - (k))   /* a quantity: row k of values, k < n_rows <= 16 */
+#define SPH_PAIRS_W_ONE      0            /* w_p = 1 */
+#define SPH_PAIRS_W_MASS     1            /* w_p = m_p */
+#define SPH_PAIRS_LOG        1            /* logarithmic edges (lo > 0) */
+#define SPH_PAIRS_EDGES      2            /* the caller's edge table */
+#define SPH_PAIRS_SCALE_H    4            /* bin r / h_i instead of r */
+#define SPH_PAIRS_VELOCITY   8            /* also the four velocity sums */
+typedef struct sph_pairs_desc {
+    double  lo, hi;                 /* range [lo, hi) of the binned variable; ignored with SPH_PAIRS_EDGES */
+    double  clip_lo[3], clip_hi[3]; /* the targets' strict clip box; -inf / +inf: none                     */
+    int32_t n_bins;                 /* 1 .. SPH_PAIRS_MAX_BINS                                             */
+    int32_t n_q;                    /* quantities, 0 .. SPH_PAIRS_MAX_Q                                    */
+    int32_t q[SPH_PAIRS_MAX_Q];     /* their sources: SPH_F_* or SPH_PAIRS_ROW(k)                          */
+    int32_t weight;                 /* SPH_PAIRS_W_*                                                       */
+    int32_t n_rows;                 /* rows of values, 0 .. 16                                             */
+    int32_t flags;                  /* SPH_PAIRS_LOG | EDGES | SCALE_H | VELOCITY                          */
+    int32_t target_stride;          /* >= 1                                                                */
+    int32_t target_phase;           /* 0 .. target_stride - 1                                              */
+    int32_t reserved[3];            /* must be 0                                                           */
+} sph_pairs_desc;                   /* 120 bytes */
+int sph_pairs(sph_ctx *ctx, const sph_pairs_desc *d, const double *values, const double *edges, double *host_sums, int64_t n_out,
+              uint64_t *host_raw, int32_t *exps, int64_t *counts);
+int sph_pairs_dev(sph_ctx *ctx, const sph_pairs_desc *d, const double *d_values, const double *edges, double *d_sums,
+                  int64_t n_out, uint64_t *d_raw, int32_t *d_exps, int64_t *d_counts);
+int sph_pairs_edges(const sph_pairs_desc *d, const double *edges, double *out);
+int sph_pairs_finish(const sph_pairs_desc *d, const int32_t *exps, const uint64_t *raw, double *sums);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too

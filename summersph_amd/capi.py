@@ -56,6 +56,7 @@ SYMBOLS = [
     "sph_transfer", "sph_transfer_dev",
     "sph_force_terms", "sph_force_terms_dev",
     "sph_binned", "sph_binned_dev", "sph_binned_edges",
+    "sph_pairs", "sph_pairs_dev", "sph_pairs_edges", "sph_pairs_finish",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
@@ -121,6 +122,11 @@ BINNED_MAX_ROWS = 16
 BINNED_W_ONE, BINNED_W_MASS, BINNED_W_VOLUME = 0, 1, 2
 BINNED_WEIGHTS = {"one": BINNED_W_ONE, "mass": BINNED_W_MASS, "volume": BINNED_W_VOLUME}
 BINNED_LOG0, BINNED_LOG1, BINNED_EDGES0, BINNED_EDGES1, BINNED_SQUARES, BINNED_SKIP_NAN = 1, 2, 4, 8, 16, 32
+PAIRS_MAX_Q = 4
+PAIRS_MAX_BINS = 1024
+PAIRS_W_ONE, PAIRS_W_MASS = 0, 1
+PAIRS_WEIGHTS = {"one": PAIRS_W_ONE, "mass": PAIRS_W_MASS}
+PAIRS_LOG, PAIRS_EDGES, PAIRS_SCALE_H, PAIRS_VELOCITY = 1, 2, 4, 8
 BOUND_THERMAL = 1
 BOUND_NCOL = 24
 # sph_bound's table columns (include/summersph.h, "Outputs"): S_0's, the last evaluated set's, the outcome
@@ -427,6 +433,78 @@ def binned_edges(desc: BinnedDesc, edges=None, axis: int = 0) -> np.ndarray:
     return out
 
 
+class PairsDesc(C.Structure):
+    """sph_pairs_desc (include/summersph.h)"""
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("clip_lo", C.c_double * 3), ("clip_hi", C.c_double * 3),
+                ("n_bins", C.c_int32), ("n_q", C.c_int32), ("q", C.c_int32 * PAIRS_MAX_Q), ("weight", C.c_int32),
+                ("n_rows", C.c_int32), ("flags", C.c_int32), ("target_stride", C.c_int32), ("target_phase", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+def pairs_row(k: int) -> int:
+    """the source id of row k of values (SPH_PAIRS_ROW)"""
+    return -1 - int(k)
+
+
+def pairs_nsum(n_q: int, velocity: bool) -> int:
+    return 2 + 2 * int(n_q) + (4 if velocity else 0)
+
+
+def pairs_desc(r_range, bins, log=False, edges=None, scale_h=False, q=(), weight="one", velocity=False, clip=None, stride=1,
+               phase=0, n_rows=0):
+    """(PairsDesc, edge table or None) of a sph_pairs call (include/summersph.h).  r_range: (lo, hi) of the binned variable,
+    None with edges (bins + 1 values); q: up to PAIRS_MAX_Q field names, SPH_F_* ids or pairs_row(k); clip: None or
+    ((x0, y0, z0), (x1, y1, z1)), the targets' strict box."""
+    q = (q,) if isinstance(q, (str, int, np.integer)) else tuple(q)
+    if len(q) > PAIRS_MAX_Q:
+        raise ValueError(f"pairs: at most {PAIRS_MAX_Q} quantities")
+    d = PairsDesc()
+    d.n_bins, d.n_q, d.n_rows = int(bins), len(q), int(n_rows)
+    d.weight = PAIRS_WEIGHTS[weight] if isinstance(weight, str) else int(weight)
+    d.target_stride, d.target_phase = int(stride), int(phase)
+    flags = (PAIRS_LOG if log else 0) | (PAIRS_SCALE_H if scale_h else 0) | (PAIRS_VELOCITY if velocity else 0)
+    tab = None
+    if edges is not None:
+        tab = np.ascontiguousarray(edges, dtype=np.float64)
+        if tab.shape != (int(bins) + 1,):
+            raise ValueError(f"pairs: {int(bins)} bins want {int(bins) + 1} edges")
+        flags |= PAIRS_EDGES
+    else:
+        if r_range is None:
+            raise ValueError("pairs: a range or edges")
+        d.lo, d.hi = float(r_range[0]), float(r_range[1])
+    lo, hi = ((-np.inf,) * 3, (np.inf,) * 3) if clip is None else clip
+    d.clip_lo[:] = [float(v) for v in lo]
+    d.clip_hi[:] = [float(v) for v in hi]
+    for k, s in enumerate(q):
+        d.q[k] = _binned_source(s)
+    d.flags = flags
+    return d, tab
+
+
+def pairs_edges(desc: PairsDesc, edges=None) -> np.ndarray:
+    """the edge table sph_pairs uses (pure host code: no context, no device)"""
+    out = np.empty(min(max(int(desc.n_bins), 0), PAIRS_MAX_BINS) + 1, dtype=np.float64)
+    e = None if edges is None else np.ascontiguousarray(edges, dtype=np.float64)
+    st = load().sph_pairs_edges(C.byref(desc), None if e is None else e.ctypes.data, out.ctypes.data)
+    if st != 0:
+        raise SphError(st, load().sph_strerror(st).decode() + " -- sph_pairs_edges")
+    return out
+
+
+def pairs_finish(desc: PairsDesc, exps, raw) -> np.ndarray:
+    """sph_pairs_finish: raw limbs (n_bins, nsum, 2) uint64 -- e.g. those of several calls added with pairs.add_raw -- and
+    their exponents -> the (n_bins, nsum) doubles, correctly rounded.  Host code only: no context, no device."""
+    nsum = pairs_nsum(desc.n_q, bool(desc.flags & PAIRS_VELOCITY))
+    r = np.ascontiguousarray(raw, dtype=np.uint64).reshape(int(desc.n_bins), nsum, 2)
+    e = np.ascontiguousarray(exps, dtype=np.int32).reshape(nsum)
+    out = np.empty((int(desc.n_bins), nsum))
+    st = load().sph_pairs_finish(C.byref(desc), e.ctypes.data, r.ctypes.data, out.ctypes.data)
+    if st != 0:
+        raise SphError(st, load().sph_strerror(st).decode() + " -- sph_pairs_finish")
+    return out
+
+
 def bound_desc(h=None, soft2=GRAVAT_REF_SOFT2, thermal=False, max_rounds=0, min_members=1, max_members=2**31 - 1) -> BoundDesc:
     """The descriptor of Context.bound's arguments (see there)."""
     d = BoundDesc()
@@ -725,6 +803,11 @@ def load():
     for fn in (lib.sph_binned, lib.sph_binned_dev):
         fn.argtypes = [C.c_void_p, C.POINTER(BinnedDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.sph_binned_edges.argtypes = [C.POINTER(BinnedDesc), C.c_void_p, C.c_int32, C.c_void_p]
+    for fn in (lib.sph_pairs, lib.sph_pairs_dev):
+        fn.argtypes = [C.c_void_p, C.POINTER(PairsDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                       C.c_void_p]
+    lib.sph_pairs_edges.argtypes = [C.POINTER(PairsDesc), C.c_void_p, C.c_void_p]
+    lib.sph_pairs_finish.argtypes = [C.POINTER(PairsDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -1511,6 +1594,42 @@ class Context:
         f.call("sph_binned", C.byref(d), f.ptr(v), None if tab is None else tab.ctypes.data, f.ptr(out),
                shape[0] * shape[1] * shape[2], f.ptr(cnt))
         return out, (cnt if device else f.read(cnt))
+
+    # ---- pair sums (sph_pairs) --------------------------------------------------------------------------
+    def pairs(self, r_range, bins, *, log=False, edges=None, scale_h=False, q=(), weight="one", velocity=False, clip=None,
+              stride=1, phase=0, values=None, raw=False, device=False):
+        """Per bin of the pair separation r (scale_h: of r / h_i), the count of the ordered pairs (i, j), j != i, of the
+        owned gas and exact sums over them (include/summersph.h, sph_pairs).  r_range: (lo, hi), or None with edges (bins + 1
+        values); log: logarithmic bins.  q: up to PAIRS_MAX_Q quantities A_k, each a field name, an SPH_F_* id or
+        pairs_row(k): row k of values, an (n_rows, sph_count) array in the upload order (float64 numpy; device=True: a
+        contiguous float64 torch tensor on the context's GPU).  weight: "one" or "mass" (w = m_i m_j).  velocity: also the
+        sums of w u, w u^2, w u^3 and w |dv|^2, u the pairwise radial velocity.  The targets i are the usable owned gas
+        strictly inside clip (None: everywhere) whose upload index has index % stride == phase; every usable owned gas
+        particle is a source.
+        Returns (sums, counts, exps) and, with raw=True, also the limbs: sums (n_bins, nsum) float64, nsum = 2 + 2 n_q +
+        (4 with velocity), [:, 0] = N, [:, 1] = sum w, [:, 2 + k] = sum w dA_k, [:, 2 + n_q + k] = sum w dA_k^2, then the
+        velocity sums (pairs.finish turns them into means); counts = (targets, sources, not usable); exps (nsum,) int32, the
+        sums' binary exponents; raw (n_bins, nsum, 2) uint64, the exact 128-bit sums as {low, high} limbs in units of
+        2^(exps - 62), which add exactly across calls (pairs.add_raw, then pairs_finish).  device=True: sums, counts
+        (int64), exps and raw (as int64, the same bits) are torch tensors on the context's GPU (sph_pairs_dev).  The descriptor
+        used is left in self.pairs_desc."""
+        n = self.n
+        n_rows = 0
+        if values is not None:
+            n_rows = int(values.shape[0]) if values.ndim == 2 else 1
+        d, tab = pairs_desc(r_range, bins, log, edges, scale_h, q, weight, velocity, clip, stride, phase, n_rows)
+        self.pairs_desc = d
+        nb, nsum = max(int(d.n_bins), 0), pairs_nsum(d.n_q, velocity)
+        f = self._form(device)
+        v = _values_rows("pairs", values, n_rows, n, f, exact=True)
+        out = f.empty((nb, nsum))
+        lim = f.empty((nb, nsum, 2), np.int64 if device else np.uint64) if raw else None
+        ex = f.empty((nsum,), np.int32)
+        cnt = f.counts(3)
+        f.call("sph_pairs", C.byref(d), f.ptr(v), None if tab is None else tab.ctypes.data, f.ptr(out), nb * nsum, f.ptr(lim),
+               f.ptr(ex), f.ptr(cnt))
+        res = (out, cnt if device else f.read(cnt), ex)
+        return res + (lim,) if raw else res
 
     # ---- potential and acceleration at arbitrary points (sph_gravity_at) ---------------------------
     def gravity_at(self, points, h=None, ph=None, soft2=GRAVAT_REF_SOFT2, gas=True, sinks=True, split=False, counts=False,

@@ -1367,6 +1367,20 @@ int sph_binned_dev(sph_ctx *c, const sph_binned_desc *d, const double *d_values,
     return binned_run(c, d, d_values, edges, d_sums, n_sums, d_counts, false);
 }
 
+int sph_pairs(sph_ctx *c, const sph_pairs_desc *d, const double *values, const double *edges, double *host_sums, int64_t n_out,
+              uint64_t *host_raw, int32_t *exps, int64_t *counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return pairs_run(c, d, values, edges, host_sums, n_out, host_raw, exps, counts, true);
+}
+
+int sph_pairs_dev(sph_ctx *c, const sph_pairs_desc *d, const double *d_values, const double *edges, double *d_sums, int64_t n_out,
+                  uint64_t *d_raw, int32_t *d_exps, int64_t *d_counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return pairs_run(c, d, d_values, edges, d_sums, n_out, d_raw, d_exps, d_counts, false);
+}
+
 int sph_synchronize(sph_ctx *c) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);

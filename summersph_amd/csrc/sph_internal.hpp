@@ -518,5 +518,9 @@ int force_terms_run(sph_ctx *c, const sph_force_terms_desc *d, double *out, int6
 // memory or null); edges is host memory in both
 int binned_run(sph_ctx *c, const sph_binned_desc *d, const double *values, const double *edges, double *sums, int64_t n_sums,
                int64_t *counts, bool host);
+// pair-separation sums (pair_stats.hip): host form (values / sums / raw / exps / counts[3] host memory, one read-back) or
+// device form (raw, exps, counts device memory or null); edges is host memory in both
+int pairs_run(sph_ctx *c, const sph_pairs_desc *d, const double *values, const double *edges, double *sums, int64_t n_out,
+              uint64_t *raw, int32_t *exps, int64_t *counts, bool host);
 
 }  // namespace sph

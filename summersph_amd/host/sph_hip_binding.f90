@@ -63,6 +63,9 @@ module sph_hip_binding
   public :: sph_binned_desc, sph_binned, sph_binned_dev, sph_binned_edges, SPH_BINNED_MAX_Q
   public :: SPH_BINNED_W_ONE, SPH_BINNED_W_MASS, SPH_BINNED_W_VOLUME, SPH_BINNED_LOG0, SPH_BINNED_LOG1
   public :: SPH_BINNED_EDGES0, SPH_BINNED_EDGES1, SPH_BINNED_SQUARES, SPH_BINNED_SKIP_NAN
+  ! pair sums (pair-separation histograms and structure functions, accumulated exactly in 128-bit fixed point)
+  public :: sph_pairs_desc, sph_pairs, sph_pairs_dev, sph_pairs_edges, sph_pairs_finish, SPH_PAIRS_MAX_Q, SPH_PAIRS_MAX_BINS
+  public :: SPH_PAIRS_W_ONE, SPH_PAIRS_W_MASS, SPH_PAIRS_LOG, SPH_PAIRS_CALLER_EDGES, SPH_PAIRS_SCALE_H, SPH_PAIRS_VELOCITY
   public :: c_message
 
   integer(c_int), parameter :: SPH_OK = 0
@@ -283,6 +286,23 @@ module sph_hip_binding
     integer(c_int32_t) :: weight, n_rows, flags
     integer(c_int32_t) :: reserved(3)
   end type sph_binned_desc
+
+  ! sph_pairs: a quantity q is an SPH_F_* id or -1 - k: row k of values (C: SPH_PAIRS_ROW(k)), values(id, row) in Fortran
+  ! order: (sph_count, n_rows).  sums(s, b) in Fortran order: (nsum, n_bins), nsum = 2 + 2 n_q + (4 with VELOCITY); raw(limb,
+  ! s, b): (2, nsum, n_bins) 64-bit limbs, low first; exps(nsum).  120 bytes.
+  integer(c_int32_t), parameter :: SPH_PAIRS_MAX_Q = 4, SPH_PAIRS_MAX_BINS = 1024
+  integer(c_int32_t), parameter :: SPH_PAIRS_W_ONE = 0, SPH_PAIRS_W_MASS = 1
+  ! SPH_PAIRS_CALLER_EDGES is C's SPH_PAIRS_EDGES: Fortran names ignore case, and sph_pairs_edges is the function
+  integer(c_int32_t), parameter :: SPH_PAIRS_LOG = 1, SPH_PAIRS_CALLER_EDGES = 2, SPH_PAIRS_SCALE_H = 4, SPH_PAIRS_VELOCITY = 8
+  type, bind(C) :: sph_pairs_desc
+    real(c_double) :: lo, hi
+    real(c_double) :: clip_lo(3), clip_hi(3)
+    integer(c_int32_t) :: n_bins, n_q
+    integer(c_int32_t) :: q(SPH_PAIRS_MAX_Q)
+    integer(c_int32_t) :: weight, n_rows, flags
+    integer(c_int32_t) :: target_stride, target_phase
+    integer(c_int32_t) :: reserved(3)
+  end type sph_pairs_desc
 
   interface
     integer(c_int) function sph_abi_version() bind(C, name='sph_abi_version')
@@ -891,6 +911,37 @@ module sph_hip_binding
       type(c_ptr), value :: edges
       integer(c_int32_t), value :: axis
       real(c_double), intent(out) :: out(*)
+    end function
+    ! ---- pair sums: values / d_values (n_rows sph_count doubles or c_null_ptr), edges (host memory in both forms, or
+    !      c_null_ptr), sums (n_out doubles), raw (2 n_out 64-bit limbs or c_null_ptr), exps (nsum int32 or c_null_ptr),
+    !      counts (3 int64 or c_null_ptr: targets, sources, not usable)
+    integer(c_int) function sph_pairs(ctx, d, values, edges, host_sums, n_out, host_raw, exps, counts) bind(C, name='sph_pairs')
+      import :: c_int, c_int64_t, c_ptr, sph_pairs_desc
+      type(c_ptr), value :: ctx, values, edges, host_sums, host_raw, exps, counts
+      type(sph_pairs_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_out
+    end function
+    integer(c_int) function sph_pairs_dev(ctx, d, d_values, edges, d_sums, n_out, d_raw, d_exps, d_counts) &
+        bind(C, name='sph_pairs_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_pairs_desc
+      type(c_ptr), value :: ctx, d_values, edges, d_sums, d_raw, d_exps, d_counts
+      type(sph_pairs_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_out
+    end function
+    ! the edge table the call uses: out holds n_bins + 1 doubles; host only, no context
+    integer(c_int) function sph_pairs_edges(d, edges, out) bind(C, name='sph_pairs_edges')
+      import :: c_int, c_double, c_ptr, sph_pairs_desc
+      type(sph_pairs_desc), intent(in) :: d
+      type(c_ptr), value :: edges
+      real(c_double), intent(out) :: out(*)
+    end function
+    ! raw limbs (2, nsum, n_bins) and their exponents -> the correctly rounded doubles (nsum, n_bins); host only, no context
+    integer(c_int) function sph_pairs_finish(d, exps, raw, sums) bind(C, name='sph_pairs_finish')
+      import :: c_int, c_int32_t, c_int64_t, c_double, sph_pairs_desc
+      type(sph_pairs_desc), intent(in) :: d
+      integer(c_int32_t), intent(in) :: exps(*)
+      integer(c_int64_t), intent(in) :: raw(*)
+      real(c_double), intent(out) :: sums(*)
     end function
   end interface
 
