@@ -142,6 +142,8 @@ struct Timed {
     }
 };
 
+// (A rider's time -- rider_common.hpp: the sinks' sums inside density_wt / forces_q on the plain fixed-h step -- is
+// booked with its host kernel's group; SPH_K_SINKACC then reports no launches, or the sink-sink pairs' alone.)
 void resolve_timing(sph_ctx *c) {
     for (auto &s : c->tslot) {
         for (auto &pr : s.pending) {
@@ -168,7 +170,21 @@ bool use_tile_kernel(const sph_ctx *c, bool forces) {
     return 100 * groups >= (int64_t)(forces ? thr_f : thr_d) * c->num_cus;
 }
 
-int do_density(sph_ctx *c) {
+// Riders (rider_common.hpp, DESIGN section 4 "Round 6"): on the plain fixed-h step -- no variable h, no self-gravity, no accretion, no
+// ghosts, one rank; dense or hashed table -- the sinks' sums between the pair kernels run as extra workgroups in the tails of
+// density_wt / forces_q.  Wherever the tile kernels are not chosen for a launch the stand-alone kernels run as before.
+// A/B switches: SPH_NO_SINK_RIDE (here: the step does not ask for sink_accel_partial / _final to ride, the one item that does) and
+// SPH_NO_RIDERS (tiled.hip: the launchers carry no rider workgroup whatever they are asked).
+bool riders_allowed(const sph_ctx *c) {
+    static const bool off = getenv("SPH_NO_SINK_RIDE") != nullptr;
+    return !(off || c->variable || c->gravity || (c->p.flags & SPH_FLAG_ACCRETE_CULL) || c->n_slots != c->n || c->dead_below != 0 ||
+             c->n_owned != c->n || c->nranks != 1);
+}
+
+// in_step: called by a step (one_step_device_dt), which evaluates the forces on the same positions right behind and hands
+// *rode -- the blocks of sink_accel_partial that rode on this density pass, 0 for none -- on to do_forces
+int do_density(sph_ctx *c, bool in_step = false, int32_t *rode = nullptr) {
+    if (rode) *rode = 0;
     static const bool no_refresh = getenv("SPH_NO_H_REFRESH") != nullptr;      // A/B switch
     if (c->nl_overflowed) {
         // drain_reports cleared the stale report along with the validity flags, so the next build would wait for its own, regrow
@@ -222,14 +238,15 @@ int do_density(sph_ctx *c) {
     if ((c->p.flags & SPH_FLAG_REUSE_DENSITY) && c->rho_valid) {
         SPH_HIP(c->variable ? launch_eos_only_v(c, pc) : launch_eos_only(c, pc));
     } else {
-        SPH_HIP(c->variable ? launch_density_v(c, pc) : (use_tile_kernel(c, false) ? launch_density_wt(c, pc) : launch_density(c, pc)));
+        SPH_HIP(c->variable ? launch_density_v(c, pc)
+                            : (use_tile_kernel(c, false) ? launch_density_wt(c, pc, in_step && rode && riders_allowed(c), rode) : launch_density(c, pc)));
         c->density_passes++;
     }
     c->rho_valid = true; c->eos_valid = true;
     return SPH_OK;
 }
 
-int do_forces(sph_ctx *c) {
+int do_forces(sph_ctx *c, int32_t rode = 0) {
     if (!c->eos_valid || !c->grid_valid) { c->err = "sph_forces: call sph_density first"; return SPH_ERR_STATE; }
     const PairConst pc = make_pair_const(c);
     if (c->gravity) {                                   // particle_gravforces, [F]:825 -- before the sink and SPH terms
@@ -254,8 +271,15 @@ int do_forces(sph_ctx *c) {
             }
         }
     }
-    { Timed t(c, SPH_K_SINKACC); SPH_HIP(launch_sink_accel(c, pc)); }
-    { Timed t(c, SPH_K_FORCES); SPH_HIP(c->variable ? launch_forces_v(c, pc) : (use_tile_kernel(c, true) ? launch_forces_wt(c, pc, 0) : launch_forces(c, pc))); }
+    // The sinks' sums: where their partials rode on this evaluation's density_wt launch, the final sums ride on forces_q -- they go
+    // to rows 7-9 of c->sink, forces_q reads rows 0-2 and 6 -- and only the sink-sink pairs, which add to rows 7-9, keep a launch
+    // (two sinks or more), now behind forces_q.  The timing group SPH_K_SINKACC then holds that launch or none; the riders' time is
+    // their host kernels'.
+    const bool tile_f = !c->variable && use_tile_kernel(c, true);
+    const bool ride_final = rode > 0 && tile_f && !c->wt_half_f;      // (the half-group variants of forces_q take no rider)
+    if (!ride_final) { Timed t(c, SPH_K_SINKACC); SPH_HIP(launch_sink_accel(c, pc, rode > 0 ? 1 : 0)); }
+    { Timed t(c, SPH_K_FORCES); SPH_HIP(c->variable ? launch_forces_v(c, pc) : (tile_f ? launch_forces_wt(c, pc, 0, ride_final ? rode : 0) : launch_forces(c, pc))); }
+    if (ride_final && pc.ns >= 2) { Timed t(c, SPH_K_SINKACC); SPH_HIP(launch_sink_accel(c, pc, 2)); }
     c->force_passes++;
     c->rates_valid = true;
     return SPH_OK;
@@ -359,8 +383,9 @@ int do_accrete(sph_ctx *c, int64_t *removed, int32_t *d_keep = nullptr) {
 
 int one_step_device_dt(sph_ctx *c) {
     // SUMMER_SPH.f90:889-916
-    SPH_TRY(do_density(c));
-    SPH_TRY(do_forces(c));
+    int32_t rode = 0;                                  // what a density pass tells the force pass behind it (riders, do_density)
+    SPH_TRY(do_density(c, true, &rode));
+    SPH_TRY(do_forces(c, rode));
     {   // kick + drift, one pass over the state (bitwise what sph_kick + sph_drift give)
         if (!c->rates_valid) { c->err = "sph_step: rates are stale"; return SPH_ERR_STATE; }
         // ... and, where the next grid build is the plain one, the keys, the histogram and the box partials of that build
@@ -371,8 +396,8 @@ int one_step_device_dt(sph_ctx *c) {
         SPH_HIP(e);
         c->positions_moved();
     }
-    SPH_TRY(do_density(c));
-    SPH_TRY(do_forces(c));
+    SPH_TRY(do_density(c, true, &rode));
+    SPH_TRY(do_forces(c, rode));
     {   // closing kick + get_next_timestep, one pass (bitwise what sph_kick + sph_next_dt give)
         if (!c->rates_valid) { c->err = "sph_step: rates are stale"; return SPH_ERR_STATE; }
         Timed t(c, SPH_K_DT);
@@ -553,7 +578,7 @@ int sph_ctx_destroy(sph_ctx *c) {
     grid_hash_free(c);
     ctx_free(c, c->grav_tab); ctx_free(c, c->sink_radius);
     ctx_free(c, c->w_tab); ctx_free(c, c->dw_tab); ctx_free(c, c->w_pair); ctx_free(c, c->dw_pair); ctx_free(c, c->sink); ctx_free(c, c->sink_part);
-    ctx_free(c, c->dt_part); ctx_free(c, c->d_dt);
+    ctx_free(c, c->dt_part); ctx_free(c, c->d_dt); ctx_free(c, c->d_dens_riders); ctx_free(c, c->d_force_riders);
     if (c->pin) (void)hipHostFree(c->pin);
     for (int k = 0; k < 2; k++) { if (c->ev_bbox[k]) (void)hipEventDestroy(c->ev_bbox[k]); if (c->ev_nl[k]) (void)hipEventDestroy(c->ev_nl[k]); }
     ctx_free(c, c->sel_count); ctx_free_ptr(c, c->sel_tmp); ctx_free(c, c->bnd_boxes);

@@ -28,6 +28,7 @@
 
 #include "pair_common.hpp"
 #include "reduce_common.hpp"
+#include "rider_common.hpp"
 #include "tile_common.hpp"
 
 namespace sph {
@@ -250,44 +251,18 @@ __global__ __launch_bounds__(BLOCK) void forces_kernel(PairConst pc, const doubl
 // acceleration of the sinks: sum over all gas particles, then sink-sink pairs ([F]:567-591)
 // two stages, fixed order -> bitwise reproducible
 // ------------------------------------------------------------------------------------------
-constexpr int SA_BLOCK = 256;
-
+// (the bodies are rider_common.hpp's: the same code rides on density_wt / forces_q where a step runs the tile kernels)
 __global__ __launch_bounds__(SA_BLOCK) void sink_accel_partial(PairConst pc, const double4 *__restrict__ drec, int64_t n,
                                                                const double *__restrict__ sink, double *__restrict__ part,
                                                                const int32_t *__restrict__ orig, int32_t n_owned) {
     __shared__ double sm[3][SA_BLOCK / WAVE];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int s = 0; s < pc.ns; s++) {
-        const double sx = sink[0 * MAX_SINKS + s], sy = sink[1 * MAX_SINKS + s], sz = sink[2 * MAX_SINKS + s];
-        double b0 = 0.0, b1 = 0.0, b2 = 0.0;
-        for (int64_t j = (int64_t)blockIdx.x * SA_BLOCK + threadIdx.x; j < n; j += (int64_t)gridDim.x * SA_BLOCK) {
-            if (orig[j] >= n_owned) continue;                                       // ghosts are summed by their owners
-            const double4 p = drec[j];
-            const double v0 = p.x - sx, v1 = p.y - sy, v2 = p.z - sz;              // [F]:569
-            const double dr = sqrt(v0 * v0 + v1 * v1 + v2 * v2);                   // [F]:570
-            const double d3 = dr * dr * dr;
-            b0 = b0 + (p.w * (pc.G * v0 / d3)); b1 = b1 + (p.w * (pc.G * v1 / d3)); b2 = b2 + (p.w * (pc.G * v2 / d3));  // [F]:572-573
-        }
-        b0 = wave_sum(b0); b1 = wave_sum(b1); b2 = wave_sum(b2);
-        if (lane == 0) { sm[0][wv] = b0; sm[1][wv] = b1; sm[2][wv] = b2; }
-        __syncthreads();
-        if (threadIdx.x < 3) {
-            double r = 0.0;
-            for (int k = 0; k < SA_BLOCK / WAVE; k++) r += sm[threadIdx.x][k];
-            part[((size_t)blockIdx.x * MAX_SINKS + s) * 3 + threadIdx.x] = r;
-        }
-        __syncthreads();
-    }
+    sink_partial_block(pc.G, pc.ns, drec, n, sink, part, orig, n_owned, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x, sm);
 }
 
 // one block per sink, one wave per component: lanes stride over the per-block partials, then a
 // fixed-order wave reduction (bitwise reproducible)
 __global__ __launch_bounds__(192) void sink_accel_final(const double *__restrict__ part, int nblocks, double *__restrict__ sink) {
-    const int s = blockIdx.x, comp = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    double b = 0.0;
-    for (int k = lane; k < nblocks; k += 64) b += part[((size_t)k * MAX_SINKS + s) * 3 + comp];
-    b = wave_sum(b);
-    if (lane == 0) sink[(7 + comp) * MAX_SINKS + s] = b;
+    sink_final_wave(part, nblocks, sink, (int)blockIdx.x, (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63));
 }
 
 // sink-sink pairs, [F]:578-590: serial, as in the reference (ns is tiny)
@@ -443,13 +418,20 @@ hipError_t launch_classify_waves(sph_ctx *c) {
     return hipGetLastError();
 }
 
-hipError_t launch_sink_accel(sph_ctx *c, const PairConst &pc) {
+// blocks of sink_accel_partial (launch or riders): what sink_accel_final adds up
+int sink_accel_blocks(const sph_ctx *c) {
+    return (int)std::max<int64_t>(std::min<int64_t>((c->n + SA_BLOCK - 1) / SA_BLOCK, c->sink_blocks), 1);
+}
+
+// from 0: everything.  Where the tile kernels carry the sums as riders (rider_common.hpp) -- from 1: the partials are there
+// (density_wt's riders), from 2: the sums too (forces_q's rider), only the sink-sink pairs are left
+hipError_t launch_sink_accel(sph_ctx *c, const PairConst &pc, int from) {
     if (pc.ns == 0) return hipSuccess;
-    int nb = (int)std::min<int64_t>((c->n + SA_BLOCK - 1) / SA_BLOCK, c->sink_blocks);
-    if (nb < 1) nb = 1;
-    sink_accel_partial<<<dim3(nb), dim3(SA_BLOCK), 0, c->stream>>>(pc, reinterpret_cast<const double4 *>(c->drec), c->n,
-                                                                    c->sink, c->sink_part, c->orig, (int32_t)c->n_owned);
-    sink_accel_final<<<dim3(pc.ns), dim3(192), 0, c->stream>>>(c->sink_part, nb, c->sink);
+    const int nb = sink_accel_blocks(c);
+    if (from < 1)
+        sink_accel_partial<<<dim3(nb), dim3(SA_BLOCK), 0, c->stream>>>(pc, reinterpret_cast<const double4 *>(c->drec), c->n,
+                                                                        c->sink, c->sink_part, c->orig, (int32_t)c->n_owned);
+    if (from < 2) sink_accel_final<<<dim3(pc.ns), dim3(192), 0, c->stream>>>(c->sink_part, nb, c->sink);
     if (pc.ns >= 2 && c->rank == 0) sink_sink_kernel<<<dim3(1), dim3(64), 0, c->stream>>>(pc, c->sink);
     return hipGetLastError();
 }

@@ -256,6 +256,10 @@ struct sph_ctx : sph::CtxState {
     double *d_dt = nullptr;
     double *dt_part = nullptr; int32_t dt_blocks = 0;
 
+    // Riders of the persistent pair kernels on the plain fixed-h step (rider_common.hpp, DESIGN section 4 "Round 6"): their arguments
+    void *d_dens_riders = nullptr, *d_force_riders = nullptr;   // DensRiders / ForceRiders on the device
+    std::vector<unsigned char> dens_riders_host, force_riders_host;   // ... and what they hold (rewritten only on a change)
+
     // (what is valid and what is pending: the flags of sph::CtxState, ctx_state.hpp)
 
     // statistics and timing
@@ -346,7 +350,8 @@ hipError_t launch_density(sph_ctx *c, const PairConst &pc);
 hipError_t launch_eos_only(sph_ctx *c, const PairConst &pc, bool ghosts_only = false);
 hipError_t launch_forces(sph_ctx *c, const PairConst &pc, int part = 0);
 hipError_t launch_classify_waves(sph_ctx *c);
-hipError_t launch_sink_accel(sph_ctx *c, const PairConst &pc);
+hipError_t launch_sink_accel(sph_ctx *c, const PairConst &pc, int from = 0);
+int sink_accel_blocks(const sph_ctx *c);
 hipError_t launch_kick(sph_ctx *c, double dt, bool dt_from_device);
 hipError_t launch_drift(sph_ctx *c, double dt, bool dt_from_device);
 hipError_t launch_next_dt(sph_ctx *c, bool advance_t);
@@ -381,8 +386,10 @@ hipError_t launch_apply_partials(sph_ctx *c, const double *d_all, int nranks, in
 // LDS-tiled fixed-h kernels (tiled.hip; default)
 int nlist_build_tiled(sph_ctx *c);
 constexpr int WT_TILE_RECORDS = 3712;     // whole-tile kernels: {x,y,z,m} records per LDS tile (116 KB; + the kernel table <= 160 KB)
-hipError_t launch_density_wt(sph_ctx *c, const PairConst &pc);
-hipError_t launch_forces_wt(sph_ctx *c, const PairConst &pc, int part);
+// ride_sink: the launch may carry sink_accel_partial as riders; *rode = the blocks it did carry (0: none).  rode > 0 for the
+// forces: that many partials are there, and forces_q<., 4, .> carries sink_accel_final as a rider
+hipError_t launch_density_wt(sph_ctx *c, const PairConst &pc, bool ride_sink = false, int32_t *rode = nullptr);
+hipError_t launch_forces_wt(sph_ctx *c, const PairConst &pc, int part, int32_t rode = 0);
 double forces_lane_efficiency(const std::vector<int32_t> &cnt);   // list entries / lane-trips of the forces kernel in use (host, statistics)
 // self-gravity (gravity.hip)
 hipError_t grav_sort_tmp_bytes(int64_t n, size_t *bytes);

@@ -20,10 +20,12 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 
 #include "pair_common.hpp"
 #include "tile_common.hpp"
+#include "rider_common.hpp"
 
 namespace sph {
 
@@ -274,14 +276,19 @@ __global__ __launch_bounds__(BS) void density_wt(PairConst pc, int32_t tcap, int
                                                  const double *__restrict__ alpha, const double *__restrict__ vx,
                                                  const double *__restrict__ vy, const double *__restrict__ vz,
                                                  double *__restrict__ rho, double *__restrict__ P, double *__restrict__ cs,
-                                                 double *__restrict__ frec, const int32_t *__restrict__ orig, int32_t n_owned) {
+                                                 double *__restrict__ frec, const int32_t *__restrict__ orig, int32_t n_owned,
+                                                 const DensRiders *__restrict__ riders, int32_t nriders) {
     extern __shared__ __align__(16) double lds_dyn[];      // (16: the tile is read 16 bytes at a time; static LDS in front of it must not shift it by 8)
+    // the last nriders workgroups of the grid are riders (rider_common.hpp): they start where a persistent workgroup has finished,
+    // run a small reduction of the step out of earlier launches' results and leave; the persistent grid is what is in front of them
+    const int pgrid = (int)gridDim.x - nriders;
+    if ((int)blockIdx.x >= pgrid) { density_riders(riders, (int)blockIdx.x - pgrid, lds_dyn, pc.G, pc.ns, drec, n, orig, n_owned); return; }
     double *lds_w = lds_dyn;                                               // TAB_LEN(nq) doubles (padded to even)
     double4 *tile = reinterpret_cast<double4 *>(lds_dyn + (TAB ? (TAB_LDS(pc.nq)) : 0));
     // persistent, as forces_q: one workgroup per CU walks over groups of BS targets; the table once, the plan one group ahead;
     // XCD x works on one contiguous eighth of the groups (its L2 then holds what neighbouring groups stage twice)
     if (TAB) for (int k = threadIdx.x; k < TAB_LEN(pc.nq); k += BS) lds_w[k] = w_tab[k];
-    const int nx = min(8, (int)gridDim.x), xcd = blockIdx.x % nx, per = ((int)gridDim.x - xcd + nx - 1) / nx;
+    const int nx = min(8, pgrid), xcd = blockIdx.x % nx, per = (pgrid - xcd + nx - 1) / nx;
     const int64_t g_hi = (int64_t)ngroups * (xcd + 1) / nx;
     const int lane = threadIdx.x & 63;
     const double inv_h = pc.inv_h, inv_dq = pc.inv_dq;
@@ -409,7 +416,8 @@ __global__ __launch_bounds__(BS) void forces_q(PairConst pc, int32_t tcap, int32
                                                double *__restrict__ ax, double *__restrict__ ay, double *__restrict__ az,
                                                double *__restrict__ du, double *__restrict__ dalpha,
                                                const int32_t *__restrict__ orig, int32_t n_owned,
-                                               const int32_t *__restrict__ wave_class, int32_t want, const int32_t *__restrict__ plan256) {
+                                               const int32_t *__restrict__ wave_class, int32_t want, const int32_t *__restrict__ plan256,
+                                               const ForceRiders *__restrict__ riders, int32_t nriders) {
     // LPT = 4: groups of 256 targets, `plan` = plan_f (the groups the list entries are slots of), targets dealt by list length.
     // LPT = 8: groups of 128 targets (half the tile need: neighbourhoods of ~200 that do not fit otherwise), `plan` = the
     // half-group plans, plan256 = plan_f: an entry becomes a slot of the half group's tile with one constant per interval;
@@ -418,6 +426,11 @@ __global__ __launch_bounds__(BS) void forces_q(PairConst pc, int32_t tcap, int32
     constexpr int T = BS / LPT;
     constexpr int TPR = 8 / LPT;                           // trips per list row
     extern __shared__ __align__(16) double lds_dyn[];      // (16: the tile is read 16 bytes at a time; static LDS in front of it must not shift it by 8)
+    // a rider workgroup behind the persistent grid (rider_common.hpp): sink_accel_final.  It writes the sinks' accelerations, rows
+    // 7-9 of `sink`; the persistent workgroups stage rows 0-2 and 6 (x, y, z, m; s_sink below) and read no other row.
+    // (LPT = 4 only: the half-group variants sit at the register limit and spill with anything added; they take no rider)
+    const int pgrid = LPT == 4 ? (int)gridDim.x - nriders : (int)gridDim.x;
+    if (LPT == 4 && (int)blockIdx.x >= pgrid) { forces_rider(riders); return; }
     double *lds_dw = lds_dyn;
     double2 *tile = reinterpret_cast<double2 *>(lds_dyn + (TAB ? (TAB_LDS(pc.nq)) : 0));      // !TAB: dW knots recomputed (density_wt)
     __shared__ double s_sink[4][MAX_SINKS];              // x, y, z, m of the sinks: the epilogue reads them here, not through serial scalar loads
@@ -444,7 +457,7 @@ __global__ __launch_bounds__(BS) void forces_q(PairConst pc, int32_t tcap, int32
     // groups of that eighth in turn
     // (group numbers as 32-bit integers: the scalar unit has no 64-bit ordered compare, so a 64-bit g_hi sat in two vector registers
     // for the whole kernel -- with the two notes below what forces_q<1024, 8, true> spilled around its pair loop)
-    const int nx = min(8, (int)gridDim.x), xcd = blockIdx.x % nx, per = ((int)gridDim.x - xcd + nx - 1) / nx;
+    const int nx = min(8, pgrid), xcd = blockIdx.x % nx, per = (pgrid - xcd + nx - 1) / nx;
     const int g_hi = (int)((int64_t)ngroups * (xcd + 1) / nx);
     const double inv_h = pc.inv_h, inv_dq = pc.inv_dq;
     auto dw_of = [&](double q) {
@@ -850,28 +863,67 @@ static unsigned persistent_grid(const sph_ctx *c, int64_t ngroups) {
     return (unsigned)std::min<int64_t>(ngroups, cus);
 }
 
+// The riders' arguments live in device memory and are rewritten -- by a one-thread kernel that takes them by value, so in
+// stream order and with nothing for the host to keep alive -- only when a value differs from what the device holds: in the
+// steady state of a run, never.
+template <class T>
+__global__ void set_rider_args(T *dst, T v) { *dst = v; }
+
+template <class T>
+static hipError_t sync_rider_args(sph_ctx *c, void *&dev, std::vector<unsigned char> &host, const T &v) {
+    if (!dev) {
+        if (ctx_alloc_bytes(c, &dev, sizeof(T), "rider arguments") != SPH_OK) return hipErrorOutOfMemory;
+        host.clear();
+    }
+    if (host.size() == sizeof(T) && std::memcmp(host.data(), &v, sizeof(T)) == 0) return hipSuccess;
+    set_rider_args<T><<<dim3(1), dim3(1), 0, c->stream>>>(static_cast<T *>(dev), v);
+    host.assign(reinterpret_cast<const unsigned char *>(&v), reinterpret_cast<const unsigned char *>(&v) + sizeof(T));
+    return hipGetLastError();
+}
+
+// SPH_NO_RIDERS (A/B switch): no launch of the two kernels carries a rider workgroup, whatever its caller asks for; the caller
+// learns it from what the launcher reports back and takes the stand-alone launches
+static bool riders_off() {
+    static const bool off = getenv("SPH_NO_RIDERS") != nullptr;
+    return off;
+}
+
+// rode: the blocks of sink_accel_partial that this launch carried as riders (0: none)
 template <bool TAB>
-static hipError_t density_wt_launch(sph_ctx *c, const PairConst &pc) {
+static hipError_t density_wt_launch(sph_ctx *c, const PairConst &pc, bool ride_sink, int32_t *rode) {
     const int32_t tcap = tile_cap(pc.nq, 4, TAB);
     const size_t lds = (TAB ? (size_t)(TAB_LDS(pc.nq)) * sizeof(double) : 0) + ((size_t)tcap + 1) * sizeof(double4);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&density_wt<WT_BS, TAB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     const int64_t ngroups = (c->n + WT_BS - 1) / WT_BS;
     const unsigned grid = persistent_grid(c, ngroups);
-    density_wt<WT_BS, TAB><<<dim3(grid), dim3(WT_BS), lds, c->stream>>>(
+    // riders (rider_common.hpp): sink_accel_partial, four of its blocks a workgroup
+    const int nriders = ride_sink && !riders_off() && pc.ns > 0 ? (sink_accel_blocks(c) + RIDER_BS / SA_BLOCK - 1) / (RIDER_BS / SA_BLOCK) : 0;
+    if (nriders > 0) {
+        DensRiders ra;
+        std::memset(&ra, 0, sizeof(ra));
+        ra.sink = c->sink; ra.sink_part = c->sink_part; ra.sa_blocks = sink_accel_blocks(c);
+        e = sync_rider_args(c, c->d_dens_riders, c->dens_riders_host, ra);
+        if (e != hipSuccess) return e;
+    }
+    density_wt<WT_BS, TAB><<<dim3(grid + (unsigned)nriders), dim3(WT_BS), lds, c->stream>>>(
         pc, tcap, (int32_t)ngroups, c->plan_d, c->plan_f, reinterpret_cast<const double4 *>(c->drec), c->nlist, c->nl_cap, c->ncount, c->wave_max,
         c->w_tab, c->n, c->f[SPH_F_U], c->f[SPH_F_ALPHA], c->f[SPH_F_VX],
-        c->f[SPH_F_VY], c->f[SPH_F_VZ], c->f[SPH_F_RHO], c->f[SPH_F_P], c->f[SPH_F_C], c->frec, c->orig, (int32_t)c->n_owned);
-    return hipGetLastError();
+        c->f[SPH_F_VY], c->f[SPH_F_VZ], c->f[SPH_F_RHO], c->f[SPH_F_P], c->f[SPH_F_C], c->frec, c->orig, (int32_t)c->n_owned,
+        static_cast<const DensRiders *>(c->d_dens_riders), nriders);
+    e = hipGetLastError();
+    if (rode) *rode = e == hipSuccess && nriders > 0 ? sink_accel_blocks(c) : 0;
+    return e;
 }
 
-hipError_t launch_density_wt(sph_ctx *c, const PairConst &pc) {
+hipError_t launch_density_wt(sph_ctx *c, const PairConst &pc, bool ride_sink, int32_t *rode) {
+    if (rode) *rode = 0;
     if (c->n == 0) return hipSuccess;
-    return c->wt_big ? density_wt_launch<false>(c, pc) : density_wt_launch<true>(c, pc);
+    return c->wt_big ? density_wt_launch<false>(c, pc, ride_sink, rode) : density_wt_launch<true>(c, pc, ride_sink, rode);
 }
 
 template <int LPT, bool TAB>
-static hipError_t forces_q_launch(sph_ctx *c, const PairConst &pc, int part) {
+static hipError_t forces_q_launch(sph_ctx *c, const PairConst &pc, int part, int32_t rode) {
     constexpr int BS = 1024;
     const int32_t tcap = tile_cap_q(pc.nq, TAB);
     const size_t lds = (TAB ? (size_t)(TAB_LDS(pc.nq)) * sizeof(double) : 0) + ((size_t)tcap * 6 + (tcap >> 3) + 8) * sizeof(double2);
@@ -880,19 +932,28 @@ static hipError_t forces_q_launch(sph_ctx *c, const PairConst &pc, int part) {
     constexpr int T = BS / LPT;
     const int64_t ngroups = (c->n + T - 1) / T;
     const unsigned grid = persistent_grid(c, ngroups);
-    forces_q<BS, LPT, TAB><<<dim3(grid), dim3(BS), lds, c->stream>>>(
+    // the rider (rider_common.hpp): sink_accel_final over the partials that rode on the density_wt launch before, one workgroup
+    const int nriders = LPT == 4 && !riders_off() && pc.ns > 0 && rode > 0 ? 1 : 0;
+    if (nriders > 0) {
+        ForceRiders ra;
+        std::memset(&ra, 0, sizeof(ra));
+        ra.sink_part = c->sink_part; ra.sink = c->sink; ra.sa_blocks = rode; ra.ns = pc.ns;
+        e = sync_rider_args(c, c->d_force_riders, c->force_riders_host, ra);
+        if (e != hipSuccess) return e;
+    }
+    forces_q<BS, LPT, TAB><<<dim3(grid + (unsigned)nriders), dim3(BS), lds, c->stream>>>(
         pc, tcap, (int32_t)ngroups, LPT == 4 ? c->plan_f : c->plan_h, LPT == 4 ? reinterpret_cast<const int2 *>(c->deal) : nullptr, c->frec, c->nlist, c->nl_cap,
         c->ncount, c->dw_tab, c->sink, c->n, c->f[SPH_F_AX],
         c->f[SPH_F_AY], c->f[SPH_F_AZ], c->f[SPH_F_DU], c->f[SPH_F_DALPHA], c->orig, (int32_t)c->n_owned,
-        part ? c->wave_class : nullptr, part == 2 ? 1 : 0, c->plan_f);
+        part ? c->wave_class : nullptr, part == 2 ? 1 : 0, c->plan_f, static_cast<const ForceRiders *>(c->d_force_riders), nriders);
     return hipGetLastError();
 }
 
 // part 0: every wave.  part 1 / 2: only the waves of class 0 (interior) / class 1, as launch_forces
-hipError_t launch_forces_wt(sph_ctx *c, const PairConst &pc, int part) {
+hipError_t launch_forces_wt(sph_ctx *c, const PairConst &pc, int part, int32_t rode) {
     if (c->n == 0) return hipSuccess;
-    if (c->wt_half_f) return c->wt_big_f ? forces_q_launch<8, false>(c, pc, part) : forces_q_launch<8, true>(c, pc, part);
-    return c->wt_big_f ? forces_q_launch<4, false>(c, pc, part) : forces_q_launch<4, true>(c, pc, part);
+    if (c->wt_half_f) return c->wt_big_f ? forces_q_launch<8, false>(c, pc, part, rode) : forces_q_launch<8, true>(c, pc, part, rode);
+    return c->wt_big_f ? forces_q_launch<4, false>(c, pc, part, rode) : forces_q_launch<4, true>(c, pc, part, rode);
 }
 
 }  // namespace sph
