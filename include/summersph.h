@@ -1372,6 +1372,65 @@ int sph_pairs_dev(sph_ctx *ctx, const sph_pairs_desc *d, const double *d_values,
 int sph_pairs_edges(const sph_pairs_desc *d, const double *edges, double *out);
 int sph_pairs_finish(const sph_pairs_desc *d, const int32_t *exps, const uint64_t *raw, double *sums);
 
+/* ---- history: a per-step time series recorded on the device (the dt every step chose, the accreted counts, the sinks'
+ *      orbits and masses, the peak density, the conserved totals) ---------------------------------------------------------
+ * A device-resident log of `capacity` rows of doubles.  Between sph_history_begin and sph_history_end every step of
+ * sph_step / sph_run whose running number is a multiple of `every` appends one row, at the very end of the step (after the
+ * h update, sink creation and accretion / cull): the row describes what sph_download_state would return after that step.
+ * The rows are written by kernels on the context's stream; a recorded step adds no stream synchronisation and no host
+ * read-back.  The row index, the step number and the dropped count are kept on the host.  A full log drops further rows
+ * and counts them (no wrap-around).  Without a history the step is exactly what it is without this section: no kernel, no
+ * argument and no allocation differ.  The native multi-rank loop (summersph_halo.h) does not record.
+ * Step     steps are counted since sph_history_begin, the unrecorded ones included.  sph_history_record appends a row for
+ *          the state as it is now without advancing the number: the t = 0 row, or a row after explicit sph_density /
+ *          sph_forces / sph_kick / sph_drift calls; sph_upload keeps the history and its numbers.
+ * Row      width = SPH_HISTORY_NHEAD + 7 max_sinks doubles:
+ *           0      the step number
+ *           1-3    the device's time words after the step: t, the next dt, the dt candidate
+ *           4, 5   owned gas particles (original ids < n_owned), sinks
+ *           6-33   sph_energy's sums[0..28), same indices, same per-term arithmetic in the same order, no fused
+ *                  multiply-adds: capi.energy_total(row[6:34]) works.  Entry 6 + 13 (W_self) is 0: the history walks no
+ *                  tree; take sph_energy at snapshots for it.
+ *           34     rho_max over the owned gas (NaN densities are passed over); NaN where the context's density is not
+ *                  current (sph_download_field would refuse rho, e.g. sph_history_record after a drift) or no gas is held
+ *           35-38  the densest particle: its index in sph_download_field order, and x, y, z; ties go to the lowest index;
+ *                  NaN where 34 is
+ *           39     max |v| = sqrt(max((vx vx + vy vy) + vz vz)); 0 without gas, NaN where a velocity is NaN
+ *           40 + 7 s ..  sink s < min(ns, max_sinks): x, y, z, vx, vy, vz, m; NaN for s >= ns
+ * Exact    the gas sums 1 .. 12 and 14 (row 7 .. 18 and 20) are exact sums of sph_energy's fp64 terms: with B = max |term|
+ *          of a sum and e the exponent with B < 2^e (0 for B = 0), every term is rounded half-even to a multiple of
+ *          2^(e - 62), the integers are added in 128 bits and the total is rounded to a double once (sph_pairs' arithmetic).
+ *          The result is defined by these rules alone: it does not depend on the sorted order, the grid kind, the block
+ *          count or the launch, and it differs from the real sum by at most N 2^(e - 63) plus the final rounding.  A sum
+ *          with a non-finite term is NaN; the other sums are unaffected.  N (row 6) is a plain count.
+ *          Rows 4 and 6 (n and N) are the host's owned count (sph_set_owned; sph_count without ghosts), not a count of the
+ *          slots the passes ran over: the passes take the slots whose original id is in [0, n_owned), which are exactly
+ *          that many between steps.
+ * Sinks    row 21 .. 33: sph_energy's sink part, the same arithmetic bit for bit, on rank 0 only (sph_set_rank).
+ * read     sph_history_read copies rows [first, first + count) to the host: it synchronises the stream and then reports
+ *          what sph_get_dt reports (a list overflow or a non-finite position of the last build).  sph_history_read_dev
+ *          copies to device memory in the stream's order without waiting.  The host form's wait is not counted in
+ *          sph_stats.host_syncs, which counts the waits inside the build path only (sph_get_dt's and the downloads' are
+ *          not counted either).  sph_history_info: the rows held, the rows
+ *          dropped, the steps counted and the row width (null outputs are skipped).
+ * cost     four launches per recorded row: two coalesced passes over the sorted state and two single blocks.  The log
+ *          and about 0.4 MB of partials are counted in device_bytes from begin to end.
+ * SPH_ERR_STATE: record, info, read or end without begin.  SPH_ERR_ARG: a null descriptor, capacity < 1, every < 1, max_sinks
+ * outside 0 .. 64, flags != 0, a null output of a read of count > 0 rows, first or count outside [0, rows]. */
+typedef struct sph_history_desc {
+    int32_t capacity;   /* rows the log holds (>= 1)                                           */
+    int32_t every;      /* record the steps whose running number is a multiple of this (>= 1)  */
+    int32_t max_sinks;  /* per-sink columns kept per row (0 .. 64)                             */
+    int32_t flags;      /* 0; reserved                                                         */
+} sph_history_desc;     /* 16 bytes */
+#define SPH_HISTORY_NHEAD 40                    /* row width = NHEAD + 7 * max_sinks doubles   */
+int sph_history_begin(sph_ctx *ctx, const sph_history_desc *d);   /* allocate, rows = 0, step number = 0; a second begin replaces the first */
+int sph_history_end(sph_ctx *ctx);                                /* free; steps record nothing again */
+int sph_history_record(sph_ctx *ctx);
+int sph_history_info(sph_ctx *ctx, int64_t *rows, int64_t *dropped, int64_t *steps, int32_t *width);
+int sph_history_read(sph_ctx *ctx, int64_t first, int64_t count, double *host_out);
+int sph_history_read_dev(sph_ctx *ctx, int64_t first, int64_t count, double *d_out);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too

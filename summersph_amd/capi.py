@@ -57,6 +57,7 @@ SYMBOLS = [
     "sph_force_terms", "sph_force_terms_dev",
     "sph_binned", "sph_binned_dev", "sph_binned_edges",
     "sph_pairs", "sph_pairs_dev", "sph_pairs_edges", "sph_pairs_finish",
+    "sph_history_begin", "sph_history_end", "sph_history_record", "sph_history_info", "sph_history_read", "sph_history_read_dev",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
@@ -76,6 +77,12 @@ ENERGY_NSUM = 28
 # (rank 0 only)
 ENERGY_SUMS = ["N", "M", "mx", "my", "mz", "px", "py", "pz", "lx", "ly", "lz", "K", "U", "W_self", "W_gs",
                "Ns", "Ms", "Mx_s", "My_s", "Mz_s", "Px_s", "Py_s", "Pz_s", "Lx_s", "Ly_s", "Lz_s", "K_s", "W_ss"]
+HISTORY_NHEAD = 40
+HISTORY_MAX_SINKS = 64
+# a row of sph_history (include/summersph.h, "Row"): the head's HISTORY_NHEAD columns, then 7 per kept sink
+HISTORY_SINK_COLUMNS = ["x", "y", "z", "vx", "vy", "vz", "m"]
+HISTORY_COLUMNS = (["step", "t", "dt_next", "dt_cand", "n", "ns"] + ENERGY_SUMS +
+                   ["rho_max", "densest", "densest_x", "densest_y", "densest_z", "v_max"])
 GROUPS_LINK_H = 1
 GROUPS_NCOL = 21
 # sph_groups' table columns (include/summersph.h, "Table")
@@ -505,6 +512,54 @@ def pairs_finish(desc: PairsDesc, exps, raw) -> np.ndarray:
     return out
 
 
+class HistoryDesc(C.Structure):
+    """sph_history_desc (include/summersph.h)"""
+    _fields_ = [("capacity", C.c_int32), ("every", C.c_int32), ("max_sinks", C.c_int32), ("flags", C.c_int32)]
+
+
+def history_desc(capacity, every=1, max_sinks=0) -> HistoryDesc:
+    """The HistoryDesc of a sph_history_begin call: capacity rows, every every-th step, max_sinks per-sink column groups."""
+    capacity, every, max_sinks = int(capacity), int(every), int(max_sinks)
+    if not 1 <= capacity < 2**31:
+        raise ValueError("history: capacity must be 1 .. 2^31 - 1")
+    if not 1 <= every < 2**31:
+        raise ValueError("history: every must be 1 .. 2^31 - 1")
+    if not 0 <= max_sinks <= HISTORY_MAX_SINKS:
+        raise ValueError(f"history: max_sinks must be 0 .. {HISTORY_MAX_SINKS}")
+    d = HistoryDesc()
+    d.capacity, d.every, d.max_sinks, d.flags = capacity, every, max_sinks, 0
+    return d
+
+
+def history_width(max_sinks: int) -> int:
+    return HISTORY_NHEAD + 7 * int(max_sinks)
+
+
+def history_columns(rows, dropped=0) -> dict:
+    """Raw history rows (R, HISTORY_NHEAD + 7 max_sinks) -> the dict Context.history returns: the head's columns by name
+    (step, n, ns and densest as int64; densest is -1 where the row has none), the energy_total keys per row (E without
+    W_self, P, L and com as (R, 3)), densest_pos (R, 3), sinks (R, max_sinks, 7), dropped and "rows", the raw array."""
+    r = np.asarray(rows, dtype=np.float64)
+    if r.ndim != 2 or r.shape[1] < HISTORY_NHEAD or (r.shape[1] - HISTORY_NHEAD) % 7:
+        raise ValueError("history: rows must be (R, HISTORY_NHEAD + 7 max_sinks)")
+    out = {k: r[:, i] for i, k in enumerate(HISTORY_COLUMNS)}
+    for k in ("step", "n", "ns"):
+        out[k] = out[k].astype(np.int64)
+    out["densest"] = np.where(np.isnan(out["densest"]), -1.0, out["densest"]).astype(np.int64)
+    out["densest_pos"] = np.stack([out.pop("densest_x"), out.pop("densest_y"), out.pop("densest_z")], axis=1)
+    s = r[:, 6:6 + ENERGY_NSUM]
+    out["E"] = ((((s[:, 11] + s[:, 12]) + s[:, 13]) + s[:, 14]) + s[:, 26]) + s[:, 27]
+    out["P"] = s[:, 5:8] + s[:, 20:23]
+    out["L"] = s[:, 8:11] + s[:, 23:26]
+    mt = s[:, 1] + s[:, 16]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["com"] = np.where((mt > 0)[:, None], (s[:, 2:5] + s[:, 17:20]) / mt[:, None], 0.0)
+    out["sinks"] = r[:, HISTORY_NHEAD:].reshape(r.shape[0], (r.shape[1] - HISTORY_NHEAD) // 7, 7)
+    out["dropped"] = int(dropped)
+    out["rows"] = r
+    return out
+
+
 def bound_desc(h=None, soft2=GRAVAT_REF_SOFT2, thermal=False, max_rounds=0, min_members=1, max_members=2**31 - 1) -> BoundDesc:
     """The descriptor of Context.bound's arguments (see there)."""
     d = BoundDesc()
@@ -808,6 +863,13 @@ def load():
                        C.c_void_p]
     lib.sph_pairs_edges.argtypes = [C.POINTER(PairsDesc), C.c_void_p, C.c_void_p]
     lib.sph_pairs_finish.argtypes = [C.POINTER(PairsDesc), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sph_history_begin.argtypes = [C.c_void_p, C.POINTER(HistoryDesc)]
+    lib.sph_history_end.argtypes = [C.c_void_p]
+    lib.sph_history_record.argtypes = [C.c_void_p]
+    lib.sph_history_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int32)]
+    for fn in (lib.sph_history_read, lib.sph_history_read_dev):
+        fn.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
     _lib = lib
     return lib
 
@@ -1369,6 +1431,42 @@ class Context:
         out["sums"] = sums
         if phi:
             out["phi"] = ph
+        return out
+
+    # ---- the per-step time series (sph_history) ---------------------------------------------------
+    def history_begin(self, capacity, every=1, max_sinks=None):
+        """Starts (or restarts) the device-resident log of one row per every-th step of step / run (include/summersph.h,
+        sph_history): capacity rows, the per-sink columns of max_sinks sinks (None: the current sink count)."""
+        ms = int(self.lib.sph_sink_count(self._h)) if max_sinks is None else max_sinks
+        d = history_desc(capacity, every, ms)
+        self._ck(self.lib.sph_history_begin(self._h, C.byref(d)))
+        self.history_desc = d
+
+    def history_record(self):
+        """Appends a row for the state as it is now (the step number is not advanced)."""
+        self._ck(self.lib.sph_history_record(self._h))
+
+    def history_end(self):
+        self._ck(self.lib.sph_history_end(self._h))
+
+    def history_info(self) -> dict:
+        """rows held, rows dropped, steps counted since history_begin and the row width"""
+        r, d, s, w = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        self._ck(self.lib.sph_history_info(self._h, C.byref(r), C.byref(d), C.byref(s), C.byref(w)))
+        return {"rows": r.value, "dropped": d.value, "steps": s.value, "width": w.value}
+
+    def history(self, first=0, count=None, device=False):
+        """Rows [first, first + count) of the log (count None: all from first) as history_columns' dict of named columns.
+        device=True: the rows are copied on the context's GPU in the stream's order (sph_history_read_dev) and "rows" is
+        that torch tensor; the named columns are read from it."""
+        info = self.history_info()
+        first = int(first)
+        cnt = info["rows"] - first if count is None else int(count)
+        f = self._form(device)
+        rows = f.empty((max(cnt, 0), info["width"]))
+        f.call("sph_history_read", first, cnt, f.ptr(rows))
+        out = history_columns(f.host(rows), info["dropped"])
+        out["rows"] = rows
         return out
 
     # ---- friends-of-friends groups (sph_groups) --------------------------------------------------

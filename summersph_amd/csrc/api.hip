@@ -413,7 +413,7 @@ int one_step_device_dt(sph_ctx *c) {
         int64_t removed = 0;
         SPH_TRY(do_accrete(c, &removed));
     }
-    return SPH_OK;
+    return history_step(c);                            // sph_history: a row of the state sph_download_state would return now
 }
 
 }  // namespace
@@ -584,6 +584,7 @@ int sph_ctx_destroy(sph_ctx *c) {
     ctx_free(c, c->sel_count); ctx_free_ptr(c, c->sel_tmp); ctx_free(c, c->bnd_boxes);
     render_free(c);
     profile_free(c);
+    history_free(c);
     if (c->stream && c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return SPH_OK;
@@ -1404,6 +1405,43 @@ int sph_pairs_dev(sph_ctx *c, const sph_pairs_desc *d, const double *d_values, c
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
     return pairs_run(c, d, d_values, edges, d_sums, n_out, d_raw, d_exps, d_counts, false);
+}
+
+int sph_history_begin(sph_ctx *c, const sph_history_desc *d) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return history_begin(c, d);
+}
+
+int sph_history_end(sph_ctx *c) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return history_end(c);
+}
+
+int sph_history_record(sph_ctx *c) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return history_record(c);
+}
+
+int sph_history_info(sph_ctx *c, int64_t *rows, int64_t *dropped, int64_t *steps, int32_t *width) {
+    if (!c) return SPH_ERR_ARG;
+    return history_info(c, rows, dropped, steps, width);
+}
+
+int sph_history_read(sph_ctx *c, int64_t first, int64_t count, double *host_out) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    SPH_TRY(history_read(c, first, count, host_out, true));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    return drain_reports(c);
+}
+
+int sph_history_read_dev(sph_ctx *c, int64_t first, int64_t count, double *d_out) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return history_read(c, first, count, d_out, false);
 }
 
 int sph_synchronize(sph_ctx *c) {

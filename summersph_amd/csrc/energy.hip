@@ -21,6 +21,7 @@
 #include <cmath>
 #include <vector>
 
+#include "energy_terms.hpp"
 #include "reduce_common.hpp"
 
 // the per-particle arithmetic is written in one documented order (summersph.h); no contraction into fused multiply-adds
@@ -30,7 +31,7 @@ namespace sph {
 
 namespace {
 
-constexpr int NG = 15;                 // gas sums
+constexpr int NG = ENERGY_NG;          // gas sums (the terms: energy_terms.hpp)
 constexpr int EB = 256;                // stage block
 constexpr int BOX_BLOCKS = 1024;       // stage blocks at most (grid-stride beyond)
 
@@ -98,25 +99,11 @@ __global__ __launch_bounds__(256) void energy_pieces(GasFields f, const int32_t 
     for (int64_t k = g * PIECE + lane; k < p1; k += WAVE) {
         const int32_t i = inv[k];
         const double x = f.x[i], y = f.y[i], z = f.z[i], vx = f.vx[i], vy = f.vy[i], vz = f.vz[i], m = f.m[i];
-        // Phi_sink = -sum_s G M_s / |r - R_s| in sink order, unsoftened; massless sinks add 0
-        double ps = 0.0;
-        for (int s = 0; s < ns; s++) {
-            const double sm = sink[6 * MAX_SINKS + s];
-            if (sm == 0.0) continue;
-            const double dx = x - sink[s], dy = y - sink[MAX_SINKS + s], dz = z - sink[2 * MAX_SINKS + s];
-            ps = ps - (G * sm) / sqrt((dx * dx + dy * dy) + dz * dz);
-        }
+        const double ps = phi_sink(x, y, z, sink, ns, G);
         const double pg = phi_self ? phi_self[k] : 0.0;
         if (phi_out) phi_out[k] = pg + ps;
-        const double q[NG] = {1.0,
-                              m,
-                              m * x, m * y, m * z,
-                              m * vx, m * vy, m * vz,
-                              m * (y * vz - z * vy), m * (z * vx - x * vz), m * (x * vy - y * vx),
-                              (0.5 * m) * ((vx * vx + vy * vy) + vz * vz),
-                              m * f.u[i],
-                              (0.5 * m) * pg,
-                              m * ps};
+        double q[NG];
+        gas_terms(x, y, z, vx, vy, vz, f.u[i], m, pg, ps, q);
 #pragma unroll
         for (int s = 0; s < NG; s++) acc[s] += q[s];
     }
@@ -143,34 +130,9 @@ __global__ __launch_bounds__(WAVE) void energy_final(const double *__restrict__ 
     }
 #pragma unroll
     for (int s = 0; s < NG; s++) acc[s] = wave_sum(acc[s]);
-    constexpr int NK = SPH_ENERGY_NSUM - NG;
+    constexpr int NK = ENERGY_NK;
     double sk[NK];
-#pragma unroll
-    for (int s = 0; s < NK; s++) sk[s] = 0.0;
-    if (rank0 && lane < ns) {
-        const double x = sink[lane], y = sink[MAX_SINKS + lane], z = sink[2 * MAX_SINKS + lane];
-        const double vx = sink[3 * MAX_SINKS + lane], vy = sink[4 * MAX_SINKS + lane], vz = sink[5 * MAX_SINKS + lane];
-        const double m = sink[6 * MAX_SINKS + lane];
-        double w = 0.0;
-        for (int t = lane + 1; t < ns; t++) {
-            const double mt = sink[6 * MAX_SINKS + t];
-            const double mm = m * mt;
-            if (mm == 0.0) continue;
-            const double dx = x - sink[t], dy = y - sink[MAX_SINKS + t], dz = z - sink[2 * MAX_SINKS + t];
-            w = w - (G * mm) / sqrt((dx * dx + dy * dy) + dz * dz);
-        }
-        const double q[NK] = {1.0,
-                              m,
-                              m * x, m * y, m * z,
-                              m * vx, m * vy, m * vz,
-                              m * (y * vz - z * vy), m * (z * vx - x * vz), m * (x * vy - y * vx),
-                              (0.5 * m) * ((vx * vx + vy * vy) + vz * vz),
-                              w};
-#pragma unroll
-        for (int s = 0; s < NK; s++) sk[s] = q[s];
-    }
-#pragma unroll
-    for (int s = 0; s < NK; s++) sk[s] = wave_sum(sk[s]);
+    sink_sums(lane, sink, ns, rank0, G, sk);
     if (lane == 0) {
 #pragma unroll
         for (int s = 0; s < NG; s++) sums[s] = acc[s];

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "cell_table.hpp"
+#include "exact_sum.hpp"
 #include "reduce_common.hpp"
 
 // every term in one documented order (summersph.h); no contraction into fused multiply-adds
@@ -126,13 +127,6 @@ __global__ __launch_bounds__(KB) void pairs_select(const int32_t *__restrict__ o
         cls[i] = c;
     }
     stats_block_partial<3, 10, KB, NST>(v, part);
-}
-
-// the exponent e with b < 2^e (b >= 0 and finite; 0 for b = 0)
-__device__ __forceinline__ int32_t exp_above(double b) {
-    int e = 0;
-    (void)frexp(b, &e);
-    return (int32_t)e;
 }
 
 // one wavefront: the partials -> Info
@@ -231,10 +225,10 @@ __global__ __launch_bounds__(KB) void pairs_tails(const uint64_t *__restrict__ s
     cell_close(skey, (int64_t)blockIdx.x * KB + threadIdx.x, n_slots, info->n_src, tab, mask);
 }
 
-// term 2^sh, rounded half-even to an integer (|.| <= 2^62 by the bounds), added into the 128-bit accumulator {lo, hi}: the
+// term 2^sh, rounded half-even to an integer (exact_sum.hpp: |.| <= 2^62 by the bounds), added into the 128-bit accumulator {lo, hi}: the
 // low word with a returning add, the high word gets the term's sign word plus the carry the returned value shows
 __device__ __forceinline__ void add_term(unsigned long long *h, double term, int sh) {
-    const long long t = (long long)rint(ldexp(term, sh));
+    const long long t = to_fixed(term, sh);
     const unsigned long long tu = (unsigned long long)t;
     const unsigned long long old = atomicAdd(h, tu);
     const long long up = (t >> 63) + (long long)(old + tu < old);
@@ -376,32 +370,6 @@ __global__ __launch_bounds__(KB) void pairs_sum(const unsigned long long *__rest
     raw[2 * g + 1] = hi;
 }
 
-// {lo, hi} 2^(e - 62), correctly rounded: the magnitude normalised to its top 64 bits with the rest as a sticky bit (the
-// bits below a double's rounding position), then u64 -> f64 rounds half-even once, then an exact scaling
-__device__ __forceinline__ double limbs_to_double(unsigned long long lo, unsigned long long hi, int e) {
-    const bool neg = (long long)hi < 0;
-    if (neg) {
-        lo = ~lo + 1ull;
-        hi = ~hi + (lo == 0ull);
-    }
-    if ((lo | hi) == 0ull) return 0.0;
-    const int lz = hi ? __clzll((long long)hi) : 64 + __clzll((long long)lo);
-    unsigned long long top, rest;
-    if (lz >= 64) {
-        top = lo << (lz - 64);
-        rest = 0ull;
-    } else if (lz == 0) {
-        top = hi;
-        rest = lo;
-    } else {
-        top = (hi << lz) | (lo >> (64 - lz));
-        rest = lo << lz;
-    }
-    if (rest) top |= 1ull;
-    const double d = ldexp((double)top, 64 - lz + e - 62);
-    return neg ? -d : d;
-}
-
 __global__ __launch_bounds__(KB) void pairs_convert(const unsigned long long *__restrict__ raw, const Info *__restrict__ info,
                                                     int nsum, int64_t n_acc, double *__restrict__ sums, int32_t *__restrict__ exps) {
     const int64_t g = (int64_t)blockIdx.x * KB + threadIdx.x;
@@ -456,11 +424,6 @@ const char *make_edges(const sph_pairs_desc *d, const double *edges, double *edg
     for (int k = 0; k < n; k++)
         if (!(edge[k] < edge[k + 1])) return "the edges are not strictly increasing (bins too narrow)";
     return nullptr;
-}
-
-double finish_one(uint64_t lo, uint64_t hi, int e) {
-    const __int128 v = (__int128)(((unsigned __int128)hi << 64) | (unsigned __int128)lo);
-    return std::ldexp((double)v, e - 62);                // int128 -> double rounds half-even once; the scaling is exact
 }
 
 template <bool VEL, bool HASQ>

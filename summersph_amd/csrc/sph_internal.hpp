@@ -107,6 +107,7 @@ struct PinnedSlots {
     double trim[7];                                // grid_rebuild's trim moments
     AccWords acc;                                  // the accretion packs' read-back
 };
+struct History;                                              // the per-step time series (history.hip); null: none begun
 static_assert(offsetof(BoxReport, nonfinite) == 6 * sizeof(double) && sizeof(BoxReport) % 8 == 0, "bbox_final's layout");
 static_assert(sizeof(DtWords) == 3 * sizeof(double) && sizeof(HStats) == 4 * sizeof(double), "copied as arrays of doubles");
 #define SPH_PIN_ALIGNED(m, a) static_assert(offsetof(PinnedSlots, m) % (a) == 0, #m " is misaligned for its writer")
@@ -279,6 +280,8 @@ struct sph_ctx : sph::CtxState {
     // sph_profile and sph_binned (profile.hip, binned.hip): the edge table's pinned staging copy and the event of its last upload
     double *prf_edge = nullptr; size_t prf_edge_cap = 0;
     hipEvent_t prf_evt = nullptr;
+    // sph_history (history.hip): the log, its partial buffers and the host-side row / step / dropped counts
+    sph::History *hist = nullptr;
 };
 
 // Host scaffolding of every launcher that has the context as `c` and returns a status.
@@ -529,5 +532,15 @@ int binned_run(sph_ctx *c, const sph_binned_desc *d, const double *values, const
 // device form (raw, exps, counts device memory or null); edges is host memory in both
 int pairs_run(sph_ctx *c, const sph_pairs_desc *d, const double *values, const double *edges, double *sums, int64_t n_out,
               uint64_t *raw, int32_t *exps, int64_t *counts, bool host);
+
+// the per-step time series (history.hip).  history_step is the step's hook (a no-op without a history); history_read only
+// enqueues the copy (the host form's caller synchronises)
+int history_begin(sph_ctx *c, const sph_history_desc *d);
+int history_end(sph_ctx *c);
+void history_free(sph_ctx *c);
+int history_record(sph_ctx *c);
+int history_step(sph_ctx *c);
+int history_info(sph_ctx *c, int64_t *rows, int64_t *dropped, int64_t *steps, int32_t *width);
+int history_read(sph_ctx *c, int64_t first, int64_t count, double *out, bool host);
 
 }  // namespace sph

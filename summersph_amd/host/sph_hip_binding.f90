@@ -65,6 +65,8 @@ module sph_hip_binding
   public :: SPH_BINNED_EDGES0, SPH_BINNED_EDGES1, SPH_BINNED_SQUARES, SPH_BINNED_SKIP_NAN
   ! pair sums (pair-separation histograms and structure functions, accumulated exactly in 128-bit fixed point)
   public :: sph_pairs_desc, sph_pairs, sph_pairs_dev, sph_pairs_edges, sph_pairs_finish, SPH_PAIRS_MAX_Q, SPH_PAIRS_MAX_BINS
+  public :: sph_history_desc, sph_history_begin, sph_history_end, sph_history_record, sph_history_info, sph_history_read
+  public :: sph_history_read_dev, SPH_HISTORY_NHEAD, sph_history_begin_env, sph_history_write
   public :: SPH_PAIRS_W_ONE, SPH_PAIRS_W_MASS, SPH_PAIRS_LOG, SPH_PAIRS_CALLER_EDGES, SPH_PAIRS_SCALE_H, SPH_PAIRS_VELOCITY
   public :: c_message
 
@@ -303,6 +305,12 @@ module sph_hip_binding
     integer(c_int32_t) :: target_stride, target_phase
     integer(c_int32_t) :: reserved(3)
   end type sph_pairs_desc
+
+  ! sph_history: a row is SPH_HISTORY_NHEAD + 7 max_sinks doubles; rows(width, count) in Fortran order.  16 bytes.
+  integer(c_int32_t), parameter :: SPH_HISTORY_NHEAD = 40
+  type, bind(C) :: sph_history_desc
+    integer(c_int32_t) :: capacity, every, max_sinks, flags
+  end type sph_history_desc
 
   interface
     integer(c_int) function sph_abi_version() bind(C, name='sph_abi_version')
@@ -943,6 +951,35 @@ module sph_hip_binding
       integer(c_int64_t), intent(in) :: raw(*)
       real(c_double), intent(out) :: sums(*)
     end function
+    ! ---- the per-step time series: begin / end / record; info's outputs and read's host_out (count rows of the width info
+    !      returns) are c_loc(...) (info's may be c_null_ptr); d_out is device memory
+    integer(c_int) function sph_history_begin(ctx, d) bind(C, name='sph_history_begin')
+      import :: c_int, c_ptr, sph_history_desc
+      type(c_ptr), value :: ctx
+      type(sph_history_desc), intent(in) :: d
+    end function
+    integer(c_int) function sph_history_end(ctx) bind(C, name='sph_history_end')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function sph_history_record(ctx) bind(C, name='sph_history_record')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function sph_history_info(ctx, rows, dropped, steps, width) bind(C, name='sph_history_info')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, rows, dropped, steps, width
+    end function
+    integer(c_int) function sph_history_read(ctx, first, count, host_out) bind(C, name='sph_history_read')
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: ctx, host_out
+      integer(c_int64_t), value :: first, count
+    end function
+    integer(c_int) function sph_history_read_dev(ctx, first, count, d_out) bind(C, name='sph_history_read_dev')
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: ctx, d_out
+      integer(c_int64_t), value :: first, count
+    end function
   end interface
 
 contains
@@ -961,4 +998,50 @@ contains
       s = s // chars(k)
     end do
   end function c_message
+
+  ! The hosts' optional history file: where the environment variable SPH_HISTORY_FILE names a file, begins a history of
+  ! max_rows rows (every step, the per-sink columns of n_sinks sinks) and returns the name in path; on = .false. and no
+  ! call otherwise, so that a run without the variable is exactly the run it was.  The hosts pass max_rows = the step limit,
+  ! at most 100000 (a run without a step limit holds 100000 rows, 38 MB with one sink): the rows of later steps are dropped
+  ! and counted in the file's '#' line.  A name that does not fit path is refused (status 1, SPH_ERR_ARG), not cut short.
+  integer(c_int) function sph_history_begin_env(ctx, max_rows, n_sinks, path, on) result(st)
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in) :: max_rows, n_sinks
+    character(len=*), intent(out) :: path
+    logical, intent(out) :: on
+    type(sph_history_desc) :: d
+    integer :: stat
+    st = SPH_OK
+    call get_environment_variable('SPH_HISTORY_FILE', path, status=stat)
+    on = stat == 0 .and. len_trim(path) > 0
+    if (stat == -1) st = 1_c_int
+    if (.not. on) return
+    d%capacity = int(max(1, max_rows), c_int32_t)
+    d%every = 1_c_int32_t
+    d%max_sinks = int(max(0, min(n_sinks, 64)), c_int32_t)
+    d%flags = 0_c_int32_t
+    st = sph_history_begin(ctx, d)
+  end function sph_history_begin_env
+
+  ! writes the rows recorded so far as text, one line per row (a '#' line with the counts first), and ends the history
+  integer(c_int) function sph_history_write(ctx, path) result(st)
+    type(c_ptr), intent(in) :: ctx
+    character(len=*), intent(in) :: path
+    integer(c_int64_t), target :: rows, dropped, steps
+    integer(c_int32_t), target :: width
+    real(c_double), allocatable, target :: buf(:, :)
+    integer :: u, k
+    st = sph_history_info(ctx, c_loc(rows), c_loc(dropped), c_loc(steps), c_loc(width))
+    if (st /= SPH_OK) return
+    allocate(buf(width, max(rows, 1_c_int64_t)))
+    st = sph_history_read(ctx, 0_c_int64_t, rows, c_loc(buf))
+    if (st /= SPH_OK) return                             ! nothing is written and the history stays begun
+    open(newunit=u, file=trim(path), status='replace', action='write')
+    write(u, '(A,I0,A,I0,A,I0,A,I0)') '# sph_history rows ', rows, ' dropped ', dropped, ' steps ', steps, ' width ', width
+    do k = 1, int(rows)
+      write(u, '(*(ES25.17E3,1X))') buf(:, k)
+    end do
+    close(u)
+    st = sph_history_end(ctx)
+  end function sph_history_write
 end module sph_hip_binding

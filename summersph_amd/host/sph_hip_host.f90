@@ -296,7 +296,8 @@ contains
     real(dp) :: end_time, next_save
     real(dp), allocatable :: dts(:)
     integer :: step, save_no, step_limit, dev, i
-    logical :: talk, do_saves
+    logical :: talk, do_saves, with_history
+    character(len=4096) :: history_file
 
     end_time = 1000.0_dp
     if (present(end_time_in)) end_time = end_time_in
@@ -319,6 +320,9 @@ contains
     prm%bounding_size = bounding_size
     call check(c_null_ptr, sph_ctx_create(prm, int(dev, c_int), ctx), 'sph_ctx_create')
     call push_state(ctx, bodies, sinks)
+    ! optional time series (SPH_HISTORY_FILE): one row per step, recorded on the device, written when the run ends; the log
+    ! holds the step limit's rows, at most 100000: later steps are dropped and counted in the file's first line
+    call check(ctx, sph_history_begin_env(ctx, min(step_limit, 100000), size(sinks), history_file, with_history), 'sph_history_begin')
 
     t = 0.0_c_double
     dt = 1.0e-2_c_double
@@ -360,6 +364,7 @@ contains
       allocate(dt_log(0:min(step, ubound(dts, 1))))
       dt_log = dts(0:ubound(dt_log, 1))
     end if
+    if (with_history) call check(ctx, sph_history_write(ctx, history_file), 'sph_history_write')
     call check(ctx, sph_ctx_destroy(ctx), 'sph_ctx_destroy')
   end subroutine simulate
 
