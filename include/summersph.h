@@ -1431,6 +1431,70 @@ int sph_history_info(sph_ctx *ctx, int64_t *rows, int64_t *dropped, int64_t *ste
 int sph_history_read(sph_ctx *ctx, int64_t first, int64_t count, double *host_out);
 int sph_history_read_dev(sph_ctx *ctx, int64_t first, int64_t count, double *d_out);
 
+/* ---- track: trajectories and fates of chosen particles, recorded on the device (where the gas of a fragment came from, the
+ *      thermal history of gas that passes a shock, which particles a sink swallowed and when) --------------------------------
+ * A tracking set is n_ids caller-order ids (indices of sph_download_* at the time of sph_track_begin).  Each id names one
+ * particle for the lifetime of the tracker, whatever happens to the numbering afterwards: the sorted order changes at every
+ * grid build, and the caller's numbering at every accretion or cull (the survivors are renumbered by rank).  Between
+ * sph_track_begin and sph_track_end every step of sph_step / sph_run whose running number is a multiple of `every` appends
+ * one row at the very end of the step, beside sph_history's row and independent of it: one launch on the context's stream,
+ * no stream synchronisation, no host read-back; the live count stays on the device.  A full log drops further rows and counts
+ * them.  Without a tracker the step and the accretion pack are exactly what they are without this section: no kernel, no
+ * argument, no allocation and no synchronisation differ.
+ * Row      head: SPH_TRACK_NHEAD doubles: the step number (steps are counted since begin, the unrecorded ones included),
+ *          t (the device's time word, as sph_history's column 1), the owned gas count, the tracked particles still alive.
+ *          body: SPH_TRACK_NCOL values per tracked particle, x y z vx vy vz u rho h alpha, laid out [column][k] with k the
+ *          index into the ids as given at begin: body is (rows, SPH_TRACK_NCOL, n_ids) in C order, sph_trace's path shape,
+ *          and one quantity of all tracked particles is contiguous.  A value is bit for bit what sph_download_state /
+ *          sph_download_field would return for that particle at that moment; rho is NaN where sph_download_field would
+ *          refuse SPH_F_RHO (sph_history's rule), h is the context's smoothing length with fixed h.
+ *          A particle that has been removed is NaN in every later row (the log is filled with NaN once, at begin).
+ * Fates    four int32 per tracked particle, {fate, step, sink, current_id}: fate 0 alive, 1 accreted, 2 culled (outside the
+ *          bound); step the tracker's count of completed steps at the moment of removal, so that the particle is finite
+ *          only in rows whose step number is <= it; sink the index of the sink whose sums took its mass (the lowest
+ *          index where the accretion marked it for several, which all take it), -1 unless accreted; current_id its index
+ *          in today's caller order (sph_download_* at that index is this particle), -1 once it is gone.  A particle both
+ *          marked by a sink and outside the bound counts as accreted.
+ * record   sph_track_record appends a row of the state as it is now without advancing the step number (the t = 0 row, or a
+ *          row after an explicit sph_accrete_and_cull).
+ * Scope    one rank, no ghosts: begin returns SPH_ERR_STATE where nranks > 1 or n_owned != n.  sph_upload, sph_upload_dev,
+ *          sph_set_owned, sph_replace_ghosts_dev, sph_set_rank with nranks > 1 and sph_accrete_apply_dev *close* the
+ *          tracker: the ids mean nothing in a new state, and a silently wrong trajectory is worse than a short one.  A
+ *          closed tracker records nothing more (steps go on and are not counted; sph_track_record returns SPH_ERR_STATE);
+ *          its rows and fates stay readable until sph_track_end.  sph_upload_field keeps the numbering and the tracker.
+ * read     sph_track_read copies rows [first, first + count) to the host, the heads to head (count x SPH_TRACK_NHEAD) and
+ *          the bodies to body (count x SPH_TRACK_NCOL x n_ids); either pointer may be null.  It synchronises the stream and
+ *          then reports what sph_get_dt reports.  sph_track_fates copies 4 n_ids int32 and synchronises.  The _dev forms
+ *          copy to device memory in the stream's order without waiting.  sph_track_begin_dev takes the ids from device
+ *          memory; both forms of begin check the ids on the host and may wait for the stream.  sph_track_info: the rows held
+ *          and dropped, the steps counted, n_ids, the live count and whether the tracker is closed (null outputs are
+ *          skipped); asking for n_live reads the device's count and synchronises.  None of these waits is counted in
+ *          sph_stats.host_syncs.
+ * cost     one launch per recorded row: a pass over the sorted order's 4-byte ids with a bit test, ten gathers per hit.  A
+ *          pack that removed particles adds five small launches (the fates, and the bitmap, prefix and tags rebuilt); a pack
+ *          that removed nobody adds none.  The log (capacity x (4 + 10 n_ids) doubles), n / 8 bytes of bitmap, n / 16 of
+ *          prefix and 20 n_ids bytes are counted in device_bytes from begin to end.
+ * SPH_ERR_STATE: record, info, read, fates or end without begin; begin with several ranks or ghosts; record on a closed
+ * tracker.  SPH_ERR_ARG: a null descriptor, capacity < 1, every < 1, flags != 0, n_ids < 1, null ids, an id outside [0, n),
+ * an id given twice, first or count outside [0, rows], a null fates output.  SPH_ERR_NOMEM: the log does not fit. */
+typedef struct sph_track_desc {
+    int64_t capacity;   /* rows the log holds (>= 1)                                           */
+    int32_t every;      /* record the steps whose running number is a multiple of this (>= 1)  */
+    int32_t flags;      /* 0; reserved                                                         */
+} sph_track_desc;       /* 16 bytes */
+#define SPH_TRACK_NHEAD 4                       /* step, t, owned gas count, tracked particles alive */
+#define SPH_TRACK_NCOL 10                       /* x y z vx vy vz u rho h alpha                      */
+int sph_track_begin(sph_ctx *ctx, const sph_track_desc *d, int64_t n_ids, const int64_t *ids);   /* a second begin replaces the first */
+int sph_track_begin_dev(sph_ctx *ctx, const sph_track_desc *d, int64_t n_ids, const int64_t *d_ids);
+int sph_track_end(sph_ctx *ctx);
+int sph_track_record(sph_ctx *ctx);
+int sph_track_info(sph_ctx *ctx, int64_t *rows, int64_t *dropped, int64_t *steps, int64_t *n_tracked, int64_t *n_live,
+                   int32_t *closed);
+int sph_track_read(sph_ctx *ctx, int64_t first, int64_t count, double *host_head, double *host_body);
+int sph_track_read_dev(sph_ctx *ctx, int64_t first, int64_t count, double *d_head, double *d_body);
+int sph_track_fates(sph_ctx *ctx, int32_t *host_fates);
+int sph_track_fates_dev(sph_ctx *ctx, int32_t *d_fates);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too

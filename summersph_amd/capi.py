@@ -58,6 +58,8 @@ SYMBOLS = [
     "sph_binned", "sph_binned_dev", "sph_binned_edges",
     "sph_pairs", "sph_pairs_dev", "sph_pairs_edges", "sph_pairs_finish",
     "sph_history_begin", "sph_history_end", "sph_history_record", "sph_history_info", "sph_history_read", "sph_history_read_dev",
+    "sph_track_begin", "sph_track_begin_dev", "sph_track_end", "sph_track_record", "sph_track_info", "sph_track_read",
+    "sph_track_read_dev", "sph_track_fates", "sph_track_fates_dev",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
@@ -83,6 +85,13 @@ HISTORY_MAX_SINKS = 64
 HISTORY_SINK_COLUMNS = ["x", "y", "z", "vx", "vy", "vz", "m"]
 HISTORY_COLUMNS = (["step", "t", "dt_next", "dt_cand", "n", "ns"] + ENERGY_SUMS +
                    ["rho_max", "densest", "densest_x", "densest_y", "densest_z", "v_max"])
+TRACK_NHEAD = 4
+TRACK_NCOL = 10
+# a row of sph_track (include/summersph.h, "Row"): the head's columns, the per-particle columns of the body, the fates' entries
+TRACK_HEAD = ["step", "t", "n", "n_live"]
+TRACK_COLUMNS = ["x", "y", "z", "vx", "vy", "vz", "u", "rho", "h", "alpha"]
+TRACK_FATES = ["fate", "step", "sink", "current_id"]
+TRACK_ALIVE, TRACK_ACCRETED, TRACK_CULLED = 0, 1, 2
 GROUPS_LINK_H = 1
 GROUPS_NCOL = 21
 # sph_groups' table columns (include/summersph.h, "Table")
@@ -560,6 +569,54 @@ def history_columns(rows, dropped=0) -> dict:
     return out
 
 
+class TrackDesc(C.Structure):
+    """sph_track_desc (include/summersph.h)"""
+    _fields_ = [("capacity", C.c_int64), ("every", C.c_int32), ("flags", C.c_int32)]
+
+
+def track_desc(capacity, every=1) -> TrackDesc:
+    """The TrackDesc of a sph_track_begin call: capacity rows, every every-th step."""
+    capacity, every = int(capacity), int(every)
+    if not 1 <= capacity < 2**63:
+        raise ValueError("track: capacity must be 1 .. 2^63 - 1")
+    if not 1 <= every < 2**31:
+        raise ValueError("track: every must be 1 .. 2^31 - 1")
+    d = TrackDesc()
+    d.capacity, d.every, d.flags = capacity, every, 0
+    return d
+
+
+def track_ids(ids) -> np.ndarray:
+    """The ids of a tracking set as a contiguous 1-D int64 array (at least one; integers only)"""
+    a = np.asarray(ids)
+    if a.ndim != 1 or a.size < 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("track: ids must be a 1-D array of at least one integer")
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def track_columns(head, body, dropped=0) -> dict:
+    """Raw tracker rows, head (R, TRACK_NHEAD) and body (R, TRACK_NCOL, K), -> the dict Context.track returns: step, n and
+    n_live as int64 (R,), t (R,), one (R, K) view per name of TRACK_COLUMNS, body, head and dropped."""
+    hd, bd = np.asarray(head, dtype=np.float64), np.asarray(body, dtype=np.float64)
+    if hd.ndim != 2 or hd.shape[1] != TRACK_NHEAD or bd.ndim != 3 or bd.shape[1] != TRACK_NCOL or bd.shape[0] != hd.shape[0]:
+        raise ValueError("track: head must be (R, TRACK_NHEAD) and body (R, TRACK_NCOL, K)")
+    out = {k: hd[:, i] for i, k in enumerate(TRACK_HEAD)}
+    for k in ("step", "n", "n_live"):
+        out[k] = out[k].astype(np.int64)
+    for i, k in enumerate(TRACK_COLUMNS):
+        out[k] = bd[:, i, :]
+    out["body"], out["head"], out["dropped"] = bd, hd, int(dropped)
+    return out
+
+
+def track_fates_columns(fates) -> dict:
+    """Raw fates (K, 4) int32 -> {"fate", "step", "sink", "current_id"}: four (K,) arrays"""
+    f = np.asarray(fates, dtype=np.int32)
+    if f.ndim != 2 or f.shape[1] != len(TRACK_FATES):
+        raise ValueError("track: fates must be (K, 4)")
+    return {k: f[:, i] for i, k in enumerate(TRACK_FATES)}
+
+
 def bound_desc(h=None, soft2=GRAVAT_REF_SOFT2, thermal=False, max_rounds=0, min_members=1, max_members=2**31 - 1) -> BoundDesc:
     """The descriptor of Context.bound's arguments (see there)."""
     d = BoundDesc()
@@ -870,6 +927,15 @@ def load():
                                      C.POINTER(C.c_int32)]
     for fn in (lib.sph_history_read, lib.sph_history_read_dev):
         fn.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    for fn in (lib.sph_track_begin, lib.sph_track_begin_dev):
+        fn.argtypes = [C.c_void_p, C.POINTER(TrackDesc), C.c_int64, C.c_void_p]
+    lib.sph_track_end.argtypes = [C.c_void_p]
+    lib.sph_track_record.argtypes = [C.c_void_p]
+    lib.sph_track_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 5 + [C.POINTER(C.c_int32)]
+    for fn in (lib.sph_track_read, lib.sph_track_read_dev):
+        fn.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    for fn in (lib.sph_track_fates, lib.sph_track_fates_dev):
+        fn.argtypes = [C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -1468,6 +1534,73 @@ class Context:
         out = history_columns(f.host(rows), info["dropped"])
         out["rows"] = rows
         return out
+
+    # ---- trajectories and fates of chosen particles (sph_track) ------------------------------------
+    def track_begin(self, ids, capacity, every=1):
+        """Starts (or restarts) the device-resident log of the particles that are ids[k] in today's caller order
+        (include/summersph.h, sph_track): one row per every-th step of step / run, capacity rows.  ids: integers (numpy, a
+        list) or an int64 torch tensor on the context's GPU (sph_track_begin_dev)."""
+        d = track_desc(capacity, every)
+        if _on_gpu(ids, self.device, np.int64):
+            f = self._form(True)
+            if ids.dim() != 1 or ids.numel() < 1:
+                raise ValueError("track: ids must be a 1-D tensor of at least one id")
+            ids = ids.contiguous()
+            f.call("sph_track_begin", C.byref(d), ids.numel(), f.ptr(ids))
+        else:
+            a = track_ids(ids)
+            self._ck(self.lib.sph_track_begin(self._h, C.byref(d), a.size, a.ctypes.data))
+        self.track_desc = d
+
+    def track_record(self):
+        """Appends a row for the state as it is now (the step number is not advanced)."""
+        self._ck(self.lib.sph_track_record(self._h))
+
+    def track_end(self):
+        self._ck(self.lib.sph_track_end(self._h))
+
+    def track_info(self, live=True) -> dict:
+        """rows held, rows dropped, steps counted since track_begin, the tracked particles, whether the tracker is closed and
+        (live=True: one read-back, waits for the stream) how many of them are still alive"""
+        v = [C.c_int64(0) for _ in range(5)]
+        closed = C.c_int32(0)
+        self._ck(self.lib.sph_track_info(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(v[3]),
+                                         C.byref(v[4]) if live else None, C.byref(closed)))
+        out = {"rows": v[0].value, "dropped": v[1].value, "steps": v[2].value, "n_tracked": v[3].value, "closed": bool(closed.value)}
+        if live:
+            out["n_live"] = v[4].value
+        return out
+
+    def track(self, first=0, count=None, device=False):
+        """Rows [first, first + count) of the log (count None: all from first) as track_columns' dict: step, t, n, n_live
+        per row, one (rows, K) array per name of TRACK_COLUMNS (column k is the particle that was ids[k] at track_begin;
+        NaN once it is gone) and body (rows, 10, K).  device=True: the rows are copied on the context's GPU in the stream's
+        order (sph_track_read_dev); body, head and the named columns are torch tensors, the head's columns are read from it."""
+        info = self.track_info(live=False)
+        first = int(first)
+        cnt = info["rows"] - first if count is None else int(count)
+        f = self._form(device)
+        head = f.empty((max(cnt, 0), TRACK_NHEAD))
+        body = f.empty((max(cnt, 0), TRACK_NCOL, info["n_tracked"]))
+        f.call("sph_track_read", first, cnt, f.ptr(head), f.ptr(body))
+        if not device:
+            return track_columns(head, body, info["dropped"])
+        out = track_columns(f.host(head), np.empty((head.shape[0], TRACK_NCOL, 0)), info["dropped"])
+        for i, k in enumerate(TRACK_COLUMNS):
+            out[k] = body[:, i, :]
+        out["body"], out["head"] = body, head
+        return out
+
+    def track_fates(self, device=False) -> dict:
+        """The fates of the tracked particles: {"fate", "step", "sink", "current_id"}, four (K,) int32 arrays (torch tensors
+        with device=True).  fate: TRACK_ALIVE, TRACK_ACCRETED, TRACK_CULLED."""
+        k = self.track_info(live=False)["n_tracked"]
+        f = self._form(device)
+        fates = f.empty((k, len(TRACK_FATES)), np.int32)
+        f.call("sph_track_fates", f.ptr(fates))
+        if not device:
+            return track_fates_columns(fates)
+        return {name: fates[:, i] for i, name in enumerate(TRACK_FATES)}
 
     # ---- friends-of-friends groups (sph_groups) --------------------------------------------------
     def _components(self, name, d, n_col, n_count, max_groups, labels, f):

@@ -336,6 +336,8 @@ static int pack_survivors(sph_ctx *c, bool single, int64_t n_before, int64_t *re
         if (last->ns != c->ns) { c->ns = last->ns; c->sinks_changed(); }
         n_new = (int64_t)last->pos_last + last->keep_last;
         if (single && n_new == n) return SPH_OK;           // nobody left: sorted state stays as it is
+        // sph_track: the tracked ids follow the scan and the removed get their fates, while keep, pos and the masks still stand
+        if (single && c->track) SPH_TRY(track_packed(c, keep, pos, reinterpret_cast<const unsigned long long *>(c->scratch)));
         CompactArgs ca{};
         for (int k = 0; k < 9; k++) { ca.src[k] = c->f[k]; ca.dst[k] = c->f_alt[k]; }
         ca.nf = 9;
@@ -365,6 +367,7 @@ static int pack_survivors(sph_ctx *c, bool single, int64_t n_before, int64_t *re
     SPH_HIP(launch_iota(c, c->inv, n_new));
     c->inv_valid = true;
     if (!single) SPH_HIP(hipStreamSynchronize(c->stream));
+    if (!single && c->track) track_close(c);           // the multi-rank pack renumbers without the tracker
     c->slots_repacked(keep_derived);
     *removed = n_before - n_new;
     return SPH_OK;

@@ -413,7 +413,8 @@ int one_step_device_dt(sph_ctx *c) {
         int64_t removed = 0;
         SPH_TRY(do_accrete(c, &removed));
     }
-    return history_step(c);                            // sph_history: a row of the state sph_download_state would return now
+    SPH_TRY(history_step(c));                          // sph_history: a row of the state sph_download_state would return now
+    return c->track ? track_step(c) : SPH_OK;          // sph_track: the tracked particles' row of the same state
 }
 
 }  // namespace
@@ -585,6 +586,7 @@ int sph_ctx_destroy(sph_ctx *c) {
     render_free(c);
     profile_free(c);
     history_free(c);
+    track_free(c);
     if (c->stream && c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return SPH_OK;
@@ -622,6 +624,7 @@ static int upload_impl(sph_ctx *c, int64_t n, const double *const src[9], hipMem
     if (c->variable) SPH_HIP(launch_fill(c, c->f[SPH_F_H], c->p.h, n));    // until sph_upload_field(SPH_F_H) sets it
     SPH_HIP(hipStreamSynchronize(c->stream));
     c->particle_set_replaced();
+    if (c->track) track_close(c);                      // the tracked ids named particles of the set that is gone
     return SPH_OK;
 }
 
@@ -819,12 +822,14 @@ int sph_set_owned(sph_ctx *c, int64_t n_owned) {
     if (!c || n_owned < 0 || n_owned > c->n) return SPH_ERR_ARG;
     c->n_owned = n_owned;
     c->owned_count_changed();
+    if (c->track) track_close(c);
     return SPH_OK;
 }
 
 int sph_set_rank(sph_ctx *c, int32_t rank, int32_t nranks) {
     if (!c || nranks < 1 || rank < 0 || rank >= nranks) return SPH_ERR_ARG;
     c->rank = rank; c->nranks = nranks;
+    if (c->track && nranks > 1) track_close(c);
     return SPH_OK;
 }
 
@@ -979,6 +984,7 @@ int sph_replace_ghosts_dev(sph_ctx *c, int64_t count, const double *d_state) {
     SPH_TRY(domain_replace_ghosts(c, count, d_state));
     if (c->own_stream) SPH_HIP(hipStreamSynchronize(c->stream));
     c->ghosts_replaced();
+    if (c->track) track_close(c);
     return SPH_OK;
 }
 
@@ -1442,6 +1448,64 @@ int sph_history_read_dev(sph_ctx *c, int64_t first, int64_t count, double *d_out
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
     return history_read(c, first, count, d_out, false);
+}
+
+int sph_track_begin(sph_ctx *c, const sph_track_desc *d, int64_t n_ids, const int64_t *ids) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return track_begin(c, d, n_ids, ids, true);
+}
+
+int sph_track_begin_dev(sph_ctx *c, const sph_track_desc *d, int64_t n_ids, const int64_t *d_ids) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return track_begin(c, d, n_ids, d_ids, false);
+}
+
+int sph_track_end(sph_ctx *c) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return track_end(c);
+}
+
+int sph_track_record(sph_ctx *c) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return track_record(c);
+}
+
+int sph_track_info(sph_ctx *c, int64_t *rows, int64_t *dropped, int64_t *steps, int64_t *n_tracked, int64_t *n_live, int32_t *closed) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return track_info(c, rows, dropped, steps, n_tracked, n_live, closed);
+}
+
+int sph_track_read(sph_ctx *c, int64_t first, int64_t count, double *host_head, double *host_body) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    SPH_TRY(track_read(c, first, count, host_head, host_body, true));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    return drain_reports(c);
+}
+
+int sph_track_read_dev(sph_ctx *c, int64_t first, int64_t count, double *d_head, double *d_body) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return track_read(c, first, count, d_head, d_body, false);
+}
+
+int sph_track_fates(sph_ctx *c, int32_t *host_fates) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    SPH_TRY(track_fates(c, host_fates, true));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    return SPH_OK;
+}
+
+int sph_track_fates_dev(sph_ctx *c, int32_t *d_fates) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return track_fates(c, d_fates, false);
 }
 
 int sph_synchronize(sph_ctx *c) {

@@ -108,6 +108,7 @@ struct PinnedSlots {
     AccWords acc;                                  // the accretion packs' read-back
 };
 struct History;                                              // the per-step time series (history.hip); null: none begun
+struct Track;                                                // the tracked particles' log (track.hip); null: none begun
 static_assert(offsetof(BoxReport, nonfinite) == 6 * sizeof(double) && sizeof(BoxReport) % 8 == 0, "bbox_final's layout");
 static_assert(sizeof(DtWords) == 3 * sizeof(double) && sizeof(HStats) == 4 * sizeof(double), "copied as arrays of doubles");
 #define SPH_PIN_ALIGNED(m, a) static_assert(offsetof(PinnedSlots, m) % (a) == 0, #m " is misaligned for its writer")
@@ -282,6 +283,8 @@ struct sph_ctx : sph::CtxState {
     hipEvent_t prf_evt = nullptr;
     // sph_history (history.hip): the log, its partial buffers and the host-side row / step / dropped counts
     sph::History *hist = nullptr;
+    // sph_track (track.hip): the log, the membership bitmap with its prefix and tags, the fates and the host-side counts
+    sph::Track *track = nullptr;
 };
 
 // Host scaffolding of every launcher that has the context as `c` and returns a status.
@@ -542,5 +545,20 @@ int history_record(sph_ctx *c);
 int history_step(sph_ctx *c);
 int history_info(sph_ctx *c, int64_t *rows, int64_t *dropped, int64_t *steps, int32_t *width);
 int history_read(sph_ctx *c, int64_t first, int64_t count, double *out, bool host);
+
+// trajectories and fates of chosen particles (track.hip).  track_step is the step's hook and track_packed the accretion
+// pack's (keep / pos by caller id, accmask by sorted slot; before any of them is reused); both are no-ops without a tracker
+// or with a closed one.  track_close: the particle set was replaced, the ids mean nothing any more.  track_read and
+// track_fates only enqueue the copies (the host forms' callers synchronise)
+int track_begin(sph_ctx *c, const sph_track_desc *d, int64_t n_ids, const int64_t *ids, bool host);
+int track_end(sph_ctx *c);
+void track_free(sph_ctx *c);
+void track_close(sph_ctx *c);
+int track_record(sph_ctx *c);
+int track_step(sph_ctx *c);
+int track_packed(sph_ctx *c, const int32_t *keep, const int32_t *pos, const unsigned long long *accmask);
+int track_info(sph_ctx *c, int64_t *rows, int64_t *dropped, int64_t *steps, int64_t *n_tracked, int64_t *n_live, int32_t *closed);
+int track_read(sph_ctx *c, int64_t first, int64_t count, double *head, double *body, bool host);
+int track_fates(sph_ctx *c, int32_t *fates, bool host);
 
 }  // namespace sph

@@ -67,6 +67,10 @@ module sph_hip_binding
   public :: sph_pairs_desc, sph_pairs, sph_pairs_dev, sph_pairs_edges, sph_pairs_finish, SPH_PAIRS_MAX_Q, SPH_PAIRS_MAX_BINS
   public :: sph_history_desc, sph_history_begin, sph_history_end, sph_history_record, sph_history_info, sph_history_read
   public :: sph_history_read_dev, SPH_HISTORY_NHEAD, sph_history_begin_env, sph_history_write
+  ! trajectories and fates of chosen particles
+  public :: sph_track_desc, sph_track_begin, sph_track_begin_dev, sph_track_end, sph_track_record, sph_track_info, sph_track_read
+  public :: sph_track_read_dev, sph_track_fates, sph_track_fates_dev, SPH_TRACK_NHEAD, SPH_TRACK_NCOL, sph_track_begin_env
+  public :: sph_track_write
   public :: SPH_PAIRS_W_ONE, SPH_PAIRS_W_MASS, SPH_PAIRS_LOG, SPH_PAIRS_CALLER_EDGES, SPH_PAIRS_SCALE_H, SPH_PAIRS_VELOCITY
   public :: c_message
 
@@ -311,6 +315,14 @@ module sph_hip_binding
   type, bind(C) :: sph_history_desc
     integer(c_int32_t) :: capacity, every, max_sinks, flags
   end type sph_history_desc
+
+  ! sph_track: a row is a head of SPH_TRACK_NHEAD doubles and a body of SPH_TRACK_NCOL values per tracked particle,
+  ! body(n_ids, SPH_TRACK_NCOL, count) in Fortran order; fates(4, n_ids).  16 bytes.
+  integer(c_int32_t), parameter :: SPH_TRACK_NHEAD = 4, SPH_TRACK_NCOL = 10
+  type, bind(C) :: sph_track_desc
+    integer(c_int64_t) :: capacity
+    integer(c_int32_t) :: every, flags
+  end type sph_track_desc
 
   interface
     integer(c_int) function sph_abi_version() bind(C, name='sph_abi_version')
@@ -980,6 +992,51 @@ module sph_hip_binding
       type(c_ptr), value :: ctx, d_out
       integer(c_int64_t), value :: first, count
     end function
+    ! ---- tracked particles: ids are 0-based indices in the upload order; info's outputs, read's head and body and the fates
+    !      are c_loc(...) (info's and either of read's may be c_null_ptr); the d_ arguments are device memory
+    integer(c_int) function sph_track_begin(ctx, d, n_ids, ids) bind(C, name='sph_track_begin')
+      import :: c_int, c_int64_t, c_ptr, sph_track_desc
+      type(c_ptr), value :: ctx
+      type(sph_track_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_ids
+      integer(c_int64_t), intent(in) :: ids(*)
+    end function
+    integer(c_int) function sph_track_begin_dev(ctx, d, n_ids, d_ids) bind(C, name='sph_track_begin_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_track_desc
+      type(c_ptr), value :: ctx, d_ids
+      type(sph_track_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_ids
+    end function
+    integer(c_int) function sph_track_end(ctx) bind(C, name='sph_track_end')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function sph_track_record(ctx) bind(C, name='sph_track_record')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function sph_track_info(ctx, rows, dropped, steps, n_tracked, n_live, closed) bind(C, name='sph_track_info')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, rows, dropped, steps, n_tracked, n_live, closed
+    end function
+    integer(c_int) function sph_track_read(ctx, first, count, host_head, host_body) bind(C, name='sph_track_read')
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: ctx, host_head, host_body
+      integer(c_int64_t), value :: first, count
+    end function
+    integer(c_int) function sph_track_read_dev(ctx, first, count, d_head, d_body) bind(C, name='sph_track_read_dev')
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: ctx, d_head, d_body
+      integer(c_int64_t), value :: first, count
+    end function
+    integer(c_int) function sph_track_fates(ctx, host_fates) bind(C, name='sph_track_fates')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, host_fates
+    end function
+    integer(c_int) function sph_track_fates_dev(ctx, d_fates) bind(C, name='sph_track_fates_dev')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, d_fates
+    end function
   end interface
 
 contains
@@ -1044,4 +1101,77 @@ contains
     close(u)
     st = sph_history_end(ctx)
   end function sph_history_write
+
+  ! The hosts' optional trajectory file: where the environment variable SPH_TRACK_FILE names a file, begins a tracker of every
+  ! SPH_TRACK_STRIDE-th of the n particles (default 100; 0-based ids 0, stride, 2 stride ...) with max_rows rows, records the
+  ! state as it is and returns the name in path; on = .false. and no call otherwise, so that a run without the variable is
+  ! exactly the run it was.  The hosts pass max_rows = the step limit + 1; the log holds at most 1000000 / the tracked count
+  ! + 1 rows (80 MB of row-particles), later rows are dropped and counted in the file's first line.
+  integer(c_int) function sph_track_begin_env(ctx, n, max_rows, path, on) result(st)
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in) :: n, max_rows
+    character(len=*), intent(out) :: path
+    logical, intent(out) :: on
+    type(sph_track_desc) :: d
+    integer(c_int64_t), allocatable :: ids(:)
+    character(len=32) :: word
+    integer :: stat, stride, k, nk, ios
+    st = SPH_OK
+    call get_environment_variable('SPH_TRACK_FILE', path, status=stat)
+    on = stat == 0 .and. len_trim(path) > 0 .and. n > 0
+    if (stat == -1) st = 1_c_int
+    if (.not. on) return
+    stride = 100
+    call get_environment_variable('SPH_TRACK_STRIDE', word, status=stat)
+    if (stat == 0 .and. len_trim(word) > 0) then
+      read(word, *, iostat=ios) stride
+      if (ios /= 0 .or. stride < 1) then
+        st = 1_c_int
+        return
+      end if
+    end if
+    nk = (n + stride - 1) / stride
+    allocate(ids(nk))
+    do k = 1, nk
+      ids(k) = int(k - 1, c_int64_t) * int(stride, c_int64_t)
+    end do
+    d%capacity = int(max(1, min(max_rows, 1000000 / nk + 1)), c_int64_t)
+    d%every = 1_c_int32_t
+    d%flags = 0_c_int32_t
+    st = sph_track_begin(ctx, d, int(nk, c_int64_t), ids)
+    if (st == SPH_OK) st = sph_track_record(ctx)
+  end function sph_track_begin_env
+
+  ! writes the rows recorded so far as text: a '#' line with the counts, one line per row and tracked particle (the row's
+  ! step and t, the tracked index k from 0, then x y z vx vy vz u rho h alpha), a '# fates' line and one line per tracked
+  ! particle (k, fate, step, sink, current id); ends the tracker
+  integer(c_int) function sph_track_write(ctx, path) result(st)
+    type(c_ptr), intent(in) :: ctx
+    character(len=*), intent(in) :: path
+    integer(c_int64_t), target :: rows, dropped, steps, nk, live
+    integer(c_int32_t), target :: closed
+    real(c_double), allocatable, target :: head(:, :), body(:, :, :)
+    integer(c_int32_t), allocatable, target :: fates(:, :)
+    integer :: u, r, k
+    st = sph_track_info(ctx, c_loc(rows), c_loc(dropped), c_loc(steps), c_loc(nk), c_loc(live), c_loc(closed))
+    if (st /= SPH_OK) return
+    allocate(head(SPH_TRACK_NHEAD, max(rows, 1_c_int64_t)), body(nk, SPH_TRACK_NCOL, max(rows, 1_c_int64_t)), fates(4, nk))
+    st = sph_track_read(ctx, 0_c_int64_t, rows, c_loc(head), c_loc(body))
+    if (st == SPH_OK) st = sph_track_fates(ctx, c_loc(fates))
+    if (st /= SPH_OK) return                             ! nothing is written and the tracker stays begun
+    open(newunit=u, file=trim(path), status='replace', action='write')
+    write(u, '(A,I0,A,I0,A,I0,A,I0,A,I0,A,I0)') '# sph_track rows ', rows, ' dropped ', dropped, ' steps ', steps, &
+      ' tracked ', nk, ' live ', live, ' closed ', closed
+    do r = 1, int(rows)
+      do k = 1, int(nk)
+        write(u, '(I0,1X,ES25.17E3,1X,I0,10(1X,ES25.17E3))') int(head(1, r), c_int64_t), head(2, r), k - 1, body(k, :, r)
+      end do
+    end do
+    write(u, '(A)') '# fates: k fate step sink current_id'
+    do k = 1, int(nk)
+      write(u, '(I0,4(1X,I0))') k - 1, fates(:, k)
+    end do
+    close(u)
+    st = sph_track_end(ctx)
+  end function sph_track_write
 end module sph_hip_binding

@@ -296,8 +296,8 @@ contains
     real(dp) :: end_time, next_save
     real(dp), allocatable :: dts(:)
     integer :: step, save_no, step_limit, dev, i
-    logical :: talk, do_saves, with_history
-    character(len=4096) :: history_file
+    logical :: talk, do_saves, with_history, with_track
+    character(len=4096) :: history_file, track_file
 
     end_time = 1000.0_dp
     if (present(end_time_in)) end_time = end_time_in
@@ -323,6 +323,8 @@ contains
     ! optional time series (SPH_HISTORY_FILE): one row per step, recorded on the device, written when the run ends; the log
     ! holds the step limit's rows, at most 100000: later steps are dropped and counted in the file's first line
     call check(ctx, sph_history_begin_env(ctx, min(step_limit, 100000), size(sinks), history_file, with_history), 'sph_history_begin')
+    ! optional trajectories (SPH_TRACK_FILE): every SPH_TRACK_STRIDE-th particle, one row per step, written when the run ends
+    call check(ctx, sph_track_begin_env(ctx, size(bodies), min(step_limit, 100000) + 1, track_file, with_track), 'sph_track_begin')
 
     t = 0.0_c_double
     dt = 1.0e-2_c_double
@@ -365,6 +367,7 @@ contains
       dt_log = dts(0:ubound(dt_log, 1))
     end if
     if (with_history) call check(ctx, sph_history_write(ctx, history_file), 'sph_history_write')
+    if (with_track) call check(ctx, sph_track_write(ctx, track_file), 'sph_track_write')
     call check(ctx, sph_ctx_destroy(ctx), 'sph_ctx_destroy')
   end subroutine simulate
 
