@@ -1,6 +1,7 @@
 """numpy restatement of sph_profile / sph_profile_finish (include/summersph.h, "disc profiles"), written from the header's
-definitions: the frame, the edge-table binning, the raw sums as sequential float64 sums in (bin, id) order, and the
-finish step.  numpy evaluates every elementwise expression below without fused multiply-adds."""
+definitions: the frame, the edge-table binning, the raw sums as sequential float64 sums in (bin, id) order -- or, with
+shape="pieces", in the shape the header's "Order" gives the library's reduction (piece_sum) -- and the finish step.  numpy
+evaluates every elementwise expression below without fused multiply-adds."""
 import math
 
 import numpy as np
@@ -81,10 +82,43 @@ def moments(fr, m, u, alpha, h, G, central_mass):
     return np.stack(q, axis=1)
 
 
+PIECE, WAVE = 1024, 64
+
+
+def _wave_sum(q):
+    """(n, 20) -> (20,): lane l adds rows l, l + 64, ... one after the other from 0.0, then the xor butterfly over the 64
+    lanes (o = 32, 16, ..., 1: every lane adds its partner's value), lane 0's result"""
+    n = q.shape[0]
+    rows = -(-n // WAVE)
+    pad = np.zeros((rows * WAVE, q.shape[1]))          # a lane past the end adds nothing; acc + 0.0 is acc (acc is never -0.0)
+    pad[:n] = q
+    acc = np.zeros((WAVE, q.shape[1]))
+    for r in range(rows):
+        acc = acc + pad[r * WAVE:(r + 1) * WAVE]
+    lane = np.arange(WAVE)
+    o = WAVE // 2
+    while o > 0:
+        acc = acc + acc[lane ^ o]
+        o >>= 1
+    return acc[0]
+
+
+def piece_sum(q):
+    """One bin's terms (n, 20), in id order, reduced in the shape of the header's "Order": pieces of 1024 positions from the
+    run's start, each by _wave_sum; then the pieces, in piece order, by _wave_sum again."""
+    q = np.asarray(q, dtype=np.float64)
+    if q.shape[0] == 0:
+        return np.zeros(q.shape[1])
+    parts = np.stack([_wave_sum(q[p:p + PIECE]) for p in range(0, q.shape[0], PIECE)])
+    return _wave_sum(parts)
+
+
 def profile_sums(gas, h, G, r_min, r_max, n_r, n_phi=1, log=False, z_max=np.inf, centre=(0, 0, 0), centre_v=(0, 0, 0),
-                 central_mass=0.0, normal=(0, 0, 1)):
-    """raw sums (n_r n_phi, 20): sequential float64 sums in (bin, id) order; gas: dict of x y z vx vy vz u m alpha arrays in
-    id order; h: one value or per particle.  Returns (sums, bin per particle)."""
+                 central_mass=0.0, normal=(0, 0, 1), shape="sequential", only_bins=None, n_owned=None):
+    """raw sums (n_r n_phi, 20) in (bin, id) order; gas: dict of x y z vx vy vz u m alpha arrays in id order; h: one value or
+    per particle.  shape: "sequential" (one term after the other) or "pieces" (piece_sum: the library's own shape).
+    only_bins: the bins to evaluate (the others must be empty: asserted); n_owned: ids from there on are ghosts, never
+    selected.  Returns (sums, bin per particle)."""
     pos = np.stack([gas[k] for k in "xyz"], axis=1)
     vel = np.stack([gas[k] for k in ("vx", "vy", "vz")], axis=1)
     fr = frame(pos, vel, np.asarray(centre, float), np.asarray(centre_v, float), normal)
@@ -92,12 +126,17 @@ def profile_sums(gas, h, G, r_min, r_max, n_r, n_phi=1, log=False, z_max=np.inf,
     al = gas.get("alpha")
     al = np.zeros_like(gas["m"]) if al is None else al
     q = moments(fr, gas["m"], gas["u"], al, h, G, central_mass)
+    if n_owned is not None:
+        b = np.where(np.arange(b.size) < n_owned, b, -1)
     nb = n_r * n_phi
     sums = np.zeros((nb, NSUM))
-    for bi in range(nb):
+    if only_bins is not None:
+        assert np.all(np.isin(b[b >= 0], only_bins)), "a selected particle outside only_bins"
+    for bi in (range(nb) if only_bins is None else only_bins):
         idx = np.nonzero(b == bi)[0]                   # ascending id
         if idx.size:
-            sums[bi] = np.add.accumulate(q[idx], axis=0)[-1]      # left to right, one term after the other
+            # sequential: left to right, one term after the other
+            sums[bi] = piece_sum(q[idx]) if shape == "pieces" else np.add.accumulate(q[idx], axis=0)[-1]
     return sums, b
 
 
