@@ -1372,6 +1372,99 @@ int sph_pairs_dev(sph_ctx *ctx, const sph_pairs_desc *d, const double *d_values,
 int sph_pairs_edges(const sph_pairs_desc *d, const double *edges, double *out);
 int sph_pairs_finish(const sph_pairs_desc *d, const int32_t *exps, const uint64_t *raw, double *sums);
 
+/* ---- mode sums: the azimuthal Fourier sums C_m, S_m of a weight per ring, m = 0 .. m_max, and the logarithmic-spiral sums
+ *      over (m, p) of the whole annulus -- which spiral modes a disc carries, how strong they are (A_m(R) = |C_m + i S_m| /
+ *      C_0) and how tightly wound (the peak of |A(m, p)| gives the arm number m and the pitch angle tan i = m / p) ----------
+ * Frame    sph_profile's, by the same code: n^ = normal / |normal| and e1, e2 as there; centre c: centre (centre_v is
+ *          checked and otherwise unused), or sink `sink`'s position on the device.  Per particle r' = r - c, X = r'.e1,
+ *          Y = r'.e2, z' = r'.n^ (a.b = (a0 b0 + a1 b1) + a2 b2), R = sqrt(X X + Y Y).  There is no AUTO_NORMAL: pass the
+ *          normal sph_profile wrote back.  No fused multiply-adds anywhere.
+ * Select   the owned gas particles (ghosts and sinks excluded) with r_min <= R < r_max and |z'| < z_max (strict;
+ *          INFINITY: no cut).  A selected particle is usable when base and A (below) are both finite; an owned gas particle
+ *          whose x, y or z is not finite counts as selected and not usable.  What is not usable is dropped and counted.
+ * Weight   w = base * A: base = 1 (SPH_MODES_W_ONE) or m_j (SPH_MODES_W_MASS); A = 1 (n_q == 0; then w = base) or one
+ *          quantity (n_q == 1): q is an SPH_F_* id, read as sph_download_field reads it (SPH_ERR_STATE exactly when that
+ *          call would refuse the field as stale), or SPH_MODES_ROW(k): row k of values, values[k * n + id], n = sph_count
+ *          -- sph_binned's sources.  values is host memory in the host form and device memory in the device form; NULL if
+ *          and only if n_rows == 0.  Only the row q names is read.
+ * Angle    c = X / R, s = Y / R (c = 1, s = 0 where R == 0); no trigonometric function.  The powers (c + i s)^m by the
+ *          recurrence c_0 = 1, s_0 = 0, c_{m+1} = c_m * c - s_m * s, s_{m+1} = s_m * c + c_m * s: each product and each sum
+ *          rounded separately.
+ * Rings    sph_profile's edges, computed once on the host: edge[k] = r_min + (k (r_max - r_min)) / n_r, or with
+ *          SPH_MODES_LOG r_min pow(r_max / r_min, k / n_r); edge[n_r] = r_max exactly.  Ring k: edge[k] <= R < edge[k + 1]
+ *          against that table.  For ring k and m = 0 .. m_max:  C[k][m] = sum w * c_m,  S[k][m] = sum w * s_m;
+ *          ring_counts[k] = the usable selected particles of ring k.
+ * Spiral   with n_p > 0: p[l] = p_min + (l (p_max - p_min)) / (n_p - 1) (p[0] = p_min when n_p == 1), computed once on the
+ *          host; per particle u = log(R / r_ref), and per l: theta = p[l] * u, (cp, sp) = (cos theta, sin theta) (the device
+ *          library's sincos).  For every m, l:  CS[m][l] = sum w * (c_m * cp - s_m * sp),  SN[m][l] = sum w * (s_m * cp +
+ *          c_m * sp) -- the cosine and sine sums of m phi + p ln(R / r_ref).  A selected particle with R == 0 enters the ring
+ *          sums but not these, and is counted in counts[3].
+ * Tables   sph_modes_tables returns the two tables the call will use (pure host code: no context, no device; edges_out n_r +
+ *          1, p_out n_p doubles, either may be NULL) and refuses what the call refuses of the descriptor.
+ * Exact    every sum is accumulated exactly in 128-bit fixed point (sph_pairs' scheme).  A first pass takes the order-free
+ *          maximum W_max = max |w| over the usable selected particles.  One bound for all sums: B = 2 * W_max (|c_m|, |s_m|
+ *          and |c_m cp - s_m sp| are <= 1 + O(m eps) < 2; rounding is monotone, so no term exceeds B); e is the binary
+ *          exponent with B < 2^e: the exponent frexp returns (0 for B = 0).  A term is formed in double as written above,
+ *          multiplied by 2^(62 - e) (exact), rounded half-even to a 64-bit integer (its magnitude is < 2^62) and added into
+ *          a 128-bit two's-complement integer: an error of at most half a quantum 2^(e - 62) per term, none from the
+ *          addition.  An accumulator overflows only beyond 2^65 terms.  B must be finite.
+ * Outputs  sums[n_out], n_out == 2 (m_max + 1) (n_r + n_p): the ring block, ((k (m_max + 1)) + m) 2 + {0: C, 1: S}, then
+ *          the spiral block at 2 n_r (m_max + 1) + ((m n_p) + l) 2 + {0: CS, 1: SN}; every double is limb value * 2^(e -
+ *          62), correctly rounded (once).  raw: the same layout with two uint64 limbs each, raw[2 g] the low and raw[2 g +
+ *          1] the high one.  exp: e, one int32.  ring_counts: n_r int64.  counts[4]: selected and usable, owned gas outside
+ *          the selection, owned gas selected but not usable, usable selected with R == 0 (part of the first); the first
+ *          three add up to the owned gas.  raw, exp, ring_counts and counts may be NULL (device memory in the device form).
+ *          Raw results with equal e add exactly as 128-bit integers (ranks, clip pieces); sph_modes_finish(d, exp, raw,
+ *          sums) turns limbs into the same doubles (pure host code; it reads n_r, m_max and n_p of the descriptor).
+ * Order    none: integer addition is associative.  sums, raw, exp, ring_counts and counts are bitwise independent of the
+ *          context's sorted order, of the dense or hashed grid, of the launch shape, of the host or device form and of
+ *          repeated calls.  No float atomics.
+ * cost     host form: one read-back (limbs, ring counts, exponent, counts); device form: ordered on the context's stream, no
+ *          synchronisation of the stream (but one when the scratch has to grow).  Both forms first wait, on the host, for
+ *          the event of the last upload of the context's pinned table copy (the edges and p of the previous sph_modes,
+ *          sph_pairs, sph_binned or sph_profile call) before they rewrite it: a device-form call that follows another waits until the
+ *          stream has run the earlier call's table copy and all that was queued before it, not that call's kernels.  The scratch is the analysis calls' shared buffer.  No
+ *          state, field, statistic (other than device_bytes), flag, grid, list or dt of the context changes.
+ * SPH_ERR_ARG: null descriptor or output, n_r outside 1 .. SPH_MODES_MAX_RINGS, m_max outside 0 .. SPH_MODES_MAX_M, n_p
+ * outside 0 .. SPH_MODES_MAX_P, n_out != 2 (m_max + 1) (n_r + n_p), r_min < 0, r_min >= r_max, a non-finite r_min / r_max, LOG
+ * with r_min == 0, rings so narrow that two edges coincide, NaN z_max, a zero or non-finite normal, a non-finite centre or
+ * centre_v (sink < 0), sink < -1 or >= sph_sink_count, with n_p > 0: r_ref <= 0 or not finite, a non-finite p_min or p_max,
+ * p_min > p_max; n_q outside 0 .. 1, a source that is neither an SPH_F_* id nor a row below n_rows, n_rows outside 0 .. 16,
+ * values NULL with n_rows > 0 or given with n_rows == 0, an unknown weight, unknown flags, reserved != 0; nothing is written
+ * then.  SPH_ERR_STATE: a stale field.  SPH_ERR_NOMEM: the scratch does not fit.  An empty context or an empty selection
+ * gives zero sums and e = 0. */
+#define SPH_MODES_MAX_M      8
+#define SPH_MODES_MAX_RINGS  1024
+#define SPH_MODES_MAX_P      256
+#define SPH_MODES_ROW(k)     (-1 - (k))   /* the quantity: row k of values, k < n_rows <= 16 */
+#define SPH_MODES_W_ONE      0            /* base = 1 */
+#define SPH_MODES_W_MASS     1            /* base = m */
+#define SPH_MODES_LOG        1            /* logarithmic ring edges (r_min > 0) */
+typedef struct sph_modes_desc {
+    double  centre[3], centre_v[3]; /* frame origin and its velocity (ignored when sink >= 0)                  */
+    double  normal[3];              /* disc normal, any length > 0                                             */
+    double  r_min, r_max;           /* ring range [r_min, r_max)                                               */
+    double  z_max;                  /* strict |z'| < z_max; INFINITY = none                                    */
+    double  p_min, p_max;           /* the spiral wavenumbers' range (n_p > 0)                                 */
+    double  r_ref;                  /* u = log(R / r_ref), > 0 (n_p > 0)                                       */
+    int32_t n_r;                    /* rings, 1 .. SPH_MODES_MAX_RINGS                                         */
+    int32_t m_max;                  /* 0 .. SPH_MODES_MAX_M                                                    */
+    int32_t n_p;                    /* spiral wavenumbers, 0 (no spiral sums) .. SPH_MODES_MAX_P               */
+    int32_t sink;                   /* >= 0: the centre is that sink's position; -1: none                      */
+    int32_t weight;                 /* SPH_MODES_W_*                                                           */
+    int32_t n_q;                    /* 0: A = 1; 1: A = the quantity q                                         */
+    int32_t q;                      /* its source: SPH_F_* or SPH_MODES_ROW(k)                                 */
+    int32_t n_rows;                 /* rows of values, 0 .. 16                                                 */
+    int32_t flags;                  /* SPH_MODES_LOG                                                           */
+    int32_t reserved[3];            /* must be 0                                                               */
+} sph_modes_desc;                   /* 168 bytes */
+int sph_modes(sph_ctx *ctx, const sph_modes_desc *d, const double *values, double *host_sums, int64_t n_out, uint64_t *host_raw,
+              int32_t *exp, int64_t *ring_counts, int64_t *counts);
+int sph_modes_dev(sph_ctx *ctx, const sph_modes_desc *d, const double *d_values, double *d_sums, int64_t n_out, uint64_t *d_raw,
+                  int32_t *d_exp, int64_t *d_ring_counts, int64_t *d_counts);
+int sph_modes_tables(const sph_modes_desc *d, double *edges_out, double *p_out);
+int sph_modes_finish(const sph_modes_desc *d, const int32_t *exp, const uint64_t *raw, double *sums);
+
 /* ---- history: a per-step time series recorded on the device (the dt every step chose, the accreted counts, the sinks'
  *      orbits and masses, the peak density, the conserved totals) ---------------------------------------------------------
  * A device-resident log of `capacity` rows of doubles.  Between sph_history_begin and sph_history_end every step of

@@ -57,6 +57,7 @@ SYMBOLS = [
     "sph_force_terms", "sph_force_terms_dev",
     "sph_binned", "sph_binned_dev", "sph_binned_edges",
     "sph_pairs", "sph_pairs_dev", "sph_pairs_edges", "sph_pairs_finish",
+    "sph_modes", "sph_modes_dev", "sph_modes_tables", "sph_modes_finish",
     "sph_history_begin", "sph_history_end", "sph_history_record", "sph_history_info", "sph_history_read", "sph_history_read_dev",
     "sph_track_begin", "sph_track_begin_dev", "sph_track_end", "sph_track_record", "sph_track_info", "sph_track_read",
     "sph_track_read_dev", "sph_track_fates", "sph_track_fates_dev",
@@ -143,6 +144,14 @@ PAIRS_MAX_BINS = 1024
 PAIRS_W_ONE, PAIRS_W_MASS = 0, 1
 PAIRS_WEIGHTS = {"one": PAIRS_W_ONE, "mass": PAIRS_W_MASS}
 PAIRS_LOG, PAIRS_EDGES, PAIRS_SCALE_H, PAIRS_VELOCITY = 1, 2, 4, 8
+MODES_MAX_M = 8
+MODES_MAX_RINGS = 1024
+MODES_MAX_P = 256
+MODES_W_ONE, MODES_W_MASS = 0, 1
+MODES_WEIGHTS = {"one": MODES_W_ONE, "mass": MODES_W_MASS}
+MODES_LOG = 1
+# sph_modes' counts (include/summersph.h, "Outputs")
+MODES_COUNTS = ["selected", "outside", "not_usable", "at_centre"]
 BOUND_THERMAL = 1
 BOUND_NCOL = 24
 # sph_bound's table columns (include/summersph.h, "Outputs"): S_0's, the last evaluated set's, the outcome
@@ -519,6 +528,92 @@ def pairs_finish(desc: PairsDesc, exps, raw) -> np.ndarray:
     if st != 0:
         raise SphError(st, load().sph_strerror(st).decode() + " -- sph_pairs_finish")
     return out
+
+
+class ModesDesc(C.Structure):
+    """sph_modes_desc (include/summersph.h)"""
+    _fields_ = [("centre", C.c_double * 3), ("centre_v", C.c_double * 3), ("normal", C.c_double * 3), ("r_min", C.c_double),
+                ("r_max", C.c_double), ("z_max", C.c_double), ("p_min", C.c_double), ("p_max", C.c_double), ("r_ref", C.c_double),
+                ("n_r", C.c_int32), ("m_max", C.c_int32), ("n_p", C.c_int32), ("sink", C.c_int32), ("weight", C.c_int32),
+                ("n_q", C.c_int32), ("q", C.c_int32), ("n_rows", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+def modes_row(k: int) -> int:
+    """the source id of row k of values (SPH_MODES_ROW)"""
+    return -1 - int(k)
+
+
+def modes_desc(r_range, n_r, m_max, log=False, z_max=np.inf, centre=None, centre_v=None, sink=None, normal=(0.0, 0.0, 1.0),
+               weight="mass", q=None, spiral=None, r_ref=1.0, n_rows=0) -> ModesDesc:
+    """The descriptor of a sph_modes call (include/summersph.h).  r_range: (r_min, r_max); centre / centre_v: three numbers
+    each (default 0), or sink: the index of the sink the frame is centred on; q: None (A = 1), a field name, an SPH_F_* id
+    or modes_row(k); spiral: None or (p_min, p_max, n_p)."""
+    d = ModesDesc()
+    d.r_min, d.r_max, d.z_max = float(r_range[0]), float(r_range[1]), float(z_max)
+    d.n_r, d.m_max, d.n_rows = int(n_r), int(m_max), int(n_rows)
+    d.flags = MODES_LOG if log else 0
+    d.weight = MODES_WEIGHTS[weight] if isinstance(weight, str) else int(weight)
+    if sink is not None:
+        if centre is not None or centre_v is not None:
+            raise ValueError("modes: give centre / centre_v or sink, not both")
+        d.sink = int(sink)
+    else:
+        d.sink = -1
+        if centre is not None:
+            d.centre[:] = [float(v) for v in centre]
+        if centre_v is not None:
+            d.centre_v[:] = [float(v) for v in centre_v]
+    d.normal[:] = [float(v) for v in normal]
+    if q is not None:
+        d.n_q, d.q = 1, _binned_source(q)
+    if spiral is not None:
+        p_min, p_max, n_p = spiral
+        d.p_min, d.p_max, d.n_p, d.r_ref = float(p_min), float(p_max), int(n_p), float(r_ref)
+    return d
+
+
+def _modes_sizes(desc: ModesDesc):
+    """(n_r, m_max + 1, n_p) of a descriptor, clamped to what an array can be made for"""
+    return (min(max(int(desc.n_r), 0), MODES_MAX_RINGS), min(max(int(desc.m_max), -1), MODES_MAX_M) + 1,
+            min(max(int(desc.n_p), 0), MODES_MAX_P))
+
+
+def modes_split(desc: ModesDesc, flat):
+    """the flat output of sph_modes (sums, or raw with a last axis of 2 limbs) as (ring[n_r, m_max + 1, 2(, 2)],
+    spiral[m_max + 1, n_p, 2(, 2)] or None): views, numpy or torch"""
+    n_r, m1, n_p = _modes_sizes(desc)
+    tail = tuple(flat.shape[1:])
+    ring = flat[:n_r * m1 * 2].reshape((n_r, m1, 2) + tail)
+    spiral = flat[n_r * m1 * 2:].reshape((m1, n_p, 2) + tail) if n_p > 0 else None
+    return ring, spiral
+
+
+def modes_tables(desc: ModesDesc):
+    """(ring edges (n_r + 1,), p table (n_p,)) as sph_modes uses them (pure host code: no context, no device)"""
+    n_r, _, n_p = _modes_sizes(desc)
+    edges, p = np.empty(n_r + 1), np.empty(n_p)
+    st = load().sph_modes_tables(C.byref(desc), edges.ctypes.data, p.ctypes.data)
+    if st != 0:
+        raise SphError(st, load().sph_strerror(st).decode() + " -- sph_modes_tables")
+    return edges, p
+
+
+def modes_finish(desc: ModesDesc, exp, raw):
+    """sph_modes_finish: raw limbs -- the flat (n_out, 2) uint64 block, or the (ring, spiral) pair Context.modes returns,
+    e.g. those of several calls added with modes.add_raw -- and their exponent -> (ring[n_r, m_max + 1, 2],
+    spiral[m_max + 1, n_p, 2] or None) doubles, correctly rounded.  Host code only: no context, no device."""
+    n_r, m1, n_p = _modes_sizes(desc)
+    n_out = 2 * m1 * (n_r + n_p)
+    if isinstance(raw, (tuple, list)):
+        raw = np.concatenate([np.asarray(r).reshape(-1, 2) for r in raw if r is not None])
+    r = np.asarray(raw)
+    r = np.ascontiguousarray(r.view(np.uint64) if r.dtype == np.int64 else r, dtype=np.uint64).reshape(n_out, 2)
+    e = np.array([int(np.asarray(exp).reshape(-1)[0])], dtype=np.int32)
+    out = np.empty(n_out)
+    st = load().sph_modes_finish(C.byref(desc), e.ctypes.data, r.ctypes.data, out.ctypes.data)
+    if st != 0:
+        raise SphError(st, load().sph_strerror(st).decode() + " -- sph_modes_finish")
+    return modes_split(desc, out)
 
 
 class HistoryDesc(C.Structure):
@@ -920,6 +1015,11 @@ def load():
                        C.c_void_p]
     lib.sph_pairs_edges.argtypes = [C.POINTER(PairsDesc), C.c_void_p, C.c_void_p]
     lib.sph_pairs_finish.argtypes = [C.POINTER(PairsDesc), C.c_void_p, C.c_void_p, C.c_void_p]
+    for fn in (lib.sph_modes, lib.sph_modes_dev):
+        fn.argtypes = [C.c_void_p, C.POINTER(ModesDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                       C.c_void_p]
+    lib.sph_modes_tables.argtypes = [C.POINTER(ModesDesc), C.c_void_p, C.c_void_p]
+    lib.sph_modes_finish.argtypes = [C.POINTER(ModesDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sph_history_begin.argtypes = [C.c_void_p, C.POINTER(HistoryDesc)]
     lib.sph_history_end.argtypes = [C.c_void_p]
     lib.sph_history_record.argtypes = [C.c_void_p]
@@ -1861,6 +1961,45 @@ class Context:
                f.ptr(ex), f.ptr(cnt))
         res = (out, cnt if device else f.read(cnt), ex)
         return res + (lim,) if raw else res
+
+    # ---- mode sums (sph_modes) --------------------------------------------------------------------------
+    def modes(self, r_range, n_r, m_max, *, log=False, z_max=np.inf, centre=None, centre_v=None, sink=None,
+              normal=(0.0, 0.0, 1.0), weight="mass", q=None, values=None, spiral=None, r_ref=1.0, raw=False, device=False):
+        """The azimuthal Fourier sums of a weight per ring and the logarithmic-spiral sums of the annulus, exact
+        (include/summersph.h, sph_modes).  r_range: (r_min, r_max), n_r rings (log: logarithmic), m = 0 .. m_max; the frame
+        as in profile(): centre (and centre_v) or sink, and the normal profile() wrote back; |z'| < z_max.  weight: "one"
+        or "mass", times q: None, a field name, an SPH_F_* id or modes_row(k): row k of values, an (n_rows, sph_count) array
+        in the upload order (float64 numpy; device=True: a contiguous float64 torch tensor on the context's GPU).  spiral:
+        None or (p_min, p_max, n_p), the wavenumbers of the spiral sums of m phi + p ln(R / r_ref).
+        Returns (ring, spiral, ring_counts, counts, exp) and, with raw=True, also the limbs: ring (n_r, m_max + 1, 2) float64,
+        [k, m, 0] = C = sum w cos m phi, [k, m, 1] = S = sum w sin m phi; spiral (m_max + 1, n_p, 2), [m, l, 0] = CS and
+        [m, l, 1] = SN, or None without spiral (modes.finish turns both into amplitudes, phases and pitch angles);
+        ring_counts (n_r,) int64; counts = (selected and usable, outside, not usable, at R == 0); exp: the sums' binary
+        exponent; raw = (ring limbs (n_r, m_max + 1, 2, 2), spiral limbs or None) uint64, the exact 128-bit sums as {low,
+        high} in units of 2^(exp - 62), which add exactly across calls of equal exp (modes.add_raw, then modes_finish).
+        device=True: ring, spiral, ring_counts, counts (int64), exp (int32, one element) and raw (as int64, the same bits)
+        are torch tensors on the context's GPU (sph_modes_dev).  The descriptor used is left in self.modes_desc."""
+        n = self.n
+        n_rows = 0
+        if values is not None:
+            if not device:                                # any array-like of rows; the device form wants its tensor as it is
+                values = np.asarray(values, dtype=np.float64)
+            n_rows = int(values.shape[0]) if getattr(values, "ndim", 1) == 2 else 1      # not a tensor: _values_rows says so
+        d = self.modes_desc = modes_desc(r_range, n_r, m_max, log, z_max, centre, centre_v, sink, normal, weight, q, spiral, r_ref,
+                                         n_rows)
+        nr, m1, n_p = _modes_sizes(d)
+        n_out = 2 * m1 * (nr + n_p)
+        f = self._form(device)
+        v = _values_rows("modes", values, n_rows, n, f, exact=True)
+        out = f.empty((n_out,))
+        lim = f.empty((n_out, 2), np.int64 if device else np.uint64) if raw else None
+        ex = f.empty((1,), np.int32)
+        rc = f.empty((nr,), np.int64)
+        cnt = f.counts(4)
+        f.call("sph_modes", C.byref(d), f.ptr(v), f.ptr(out), n_out, f.ptr(lim), f.ptr(ex), f.ptr(rc), f.ptr(cnt))
+        ring, sp = modes_split(d, out)
+        res = (ring, sp, rc, cnt if device else f.read(cnt), ex if device else int(ex[0]))
+        return res + (modes_split(d, lim),) if raw else res
 
     # ---- potential and acceleration at arbitrary points (sph_gravity_at) ---------------------------
     def gravity_at(self, points, h=None, ph=None, soft2=GRAVAT_REF_SOFT2, gas=True, sinks=True, split=False, counts=False,

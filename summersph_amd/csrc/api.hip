@@ -1413,6 +1413,20 @@ int sph_pairs_dev(sph_ctx *c, const sph_pairs_desc *d, const double *d_values, c
     return pairs_run(c, d, d_values, edges, d_sums, n_out, d_raw, d_exps, d_counts, false);
 }
 
+int sph_modes(sph_ctx *c, const sph_modes_desc *d, const double *values, double *host_sums, int64_t n_out, uint64_t *host_raw,
+              int32_t *exp, int64_t *ring_counts, int64_t *counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return modes_run(c, d, values, host_sums, n_out, host_raw, exp, ring_counts, counts, true);
+}
+
+int sph_modes_dev(sph_ctx *c, const sph_modes_desc *d, const double *d_values, double *d_sums, int64_t n_out, uint64_t *d_raw,
+                  int32_t *d_exp, int64_t *d_ring_counts, int64_t *d_counts) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return modes_run(c, d, d_values, d_sums, n_out, d_raw, d_exp, d_ring_counts, d_counts, false);
+}
+
 int sph_history_begin(sph_ctx *c, const sph_history_desc *d) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);

@@ -305,15 +305,8 @@ int binned_run(sph_ctx *c, const sph_binned_desc *d, const double *values, const
     // last upload is done
     hipStream_t st = c->stream;
     const size_t ne0 = (size_t)d->n[0] + 1, ne = ne0 + (d->n_axes == 2 ? (size_t)d->n[1] + 1 : 0);
-    if (!c->prf_evt) SPH_HIP(hipEventCreateWithFlags(&c->prf_evt, hipEventDisableTiming));
-    SPH_HIP(hipEventSynchronize(c->prf_evt));
-    if (ne > c->prf_edge_cap) {
-        if (c->prf_edge) SPH_HIP(hipHostFree(c->prf_edge));
-        c->prf_edge = nullptr; c->prf_edge_cap = 0;
-        SPH_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->prf_edge), ne * sizeof(double), hipHostMallocDefault));
-        c->prf_edge_cap = ne;
-    }
-    double *edge = c->prf_edge;
+    double *edge = nullptr;
+    SPH_TRY(table_staging(c, ne, &edge));
     for (int a = 0; a < d->n_axes; a++)
         if (const char *why = axis_edges(d, edges, a, edge + (a ? ne0 : 0))) return arg_error(c, who, why);
 

@@ -1,7 +1,7 @@
-// exact_sum.hpp -- the exact sums of pair_stats.hip (sph_pairs) and history.hip (sph_history): a term is formed in double,
-// scaled by a power of two that a bound on the terms fixes, rounded half-even to a 64-bit integer and added into a 128-bit
-// integer {lo, hi}; the total is converted to a double once.  Integer addition is associative, so a sum does not depend on
-// the order, the launch or the shape of its reduction (DESIGN sections 26 and 27).
+// exact_sum.hpp -- the exact sums of pair_stats.hip (sph_pairs), history.hip (sph_history) and modes.hip (sph_modes): a
+// term is formed in double, scaled by a power of two that a bound on the terms fixes, rounded half-even to a 64-bit integer
+// and added into a 128-bit integer {lo, hi}; the total is converted to a double once.  Integer addition is associative, so
+// a sum does not depend on the order, the launch or the shape of its reduction (DESIGN sections 26, 27 and 29).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -25,6 +25,17 @@ __device__ __forceinline__ void add_fixed(unsigned long long &lo, unsigned long 
     const unsigned long long tu = (unsigned long long)t;
     lo += tu;
     hi += (unsigned long long)(t >> 63) + (unsigned long long)(lo < tu);
+}
+
+// term 2^sh, rounded half-even to an integer, added into the 128-bit accumulator {h[0], h[1]} that other lanes add to as
+// well (an LDS histogram): the low word with a returning add, the high word gets the term's sign word plus the carry the
+// returned value shows
+__device__ __forceinline__ void add_term(unsigned long long *h, double term, int sh) {
+    const long long t = to_fixed(term, sh);
+    const unsigned long long tu = (unsigned long long)t;
+    const unsigned long long old = atomicAdd(h, tu);
+    const long long up = (t >> 63) + (long long)(old + tu < old);
+    if (up != 0) atomicAdd(h + 1, (unsigned long long)up);
 }
 
 // {lo, hi} += {l, h}

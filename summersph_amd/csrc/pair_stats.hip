@@ -225,16 +225,6 @@ __global__ __launch_bounds__(KB) void pairs_tails(const uint64_t *__restrict__ s
     cell_close(skey, (int64_t)blockIdx.x * KB + threadIdx.x, n_slots, info->n_src, tab, mask);
 }
 
-// term 2^sh, rounded half-even to an integer (exact_sum.hpp: |.| <= 2^62 by the bounds), added into the 128-bit accumulator {lo, hi}: the
-// low word with a returning add, the high word gets the term's sign word plus the carry the returned value shows
-__device__ __forceinline__ void add_term(unsigned long long *h, double term, int sh) {
-    const long long t = to_fixed(term, sh);
-    const unsigned long long tu = (unsigned long long)t;
-    const unsigned long long old = atomicAdd(h, tu);
-    const long long up = (t >> 63) + (long long)(old + tu < old);
-    if (up != 0) atomicAdd(h + 1, (unsigned long long)up);
-}
-
 struct BinArgs {
     const double *rec;
     const uint64_t *skey;
@@ -449,15 +439,8 @@ int pairs_run(sph_ctx *c, const sph_pairs_desc *d, const double *values, const d
     // last upload is done
     hipStream_t st = c->stream;
     const size_t ne = (size_t)n_bins + 1;
-    if (!c->prf_evt) SPH_HIP(hipEventCreateWithFlags(&c->prf_evt, hipEventDisableTiming));
-    SPH_HIP(hipEventSynchronize(c->prf_evt));
-    if (ne > c->prf_edge_cap) {
-        if (c->prf_edge) SPH_HIP(hipHostFree(c->prf_edge));
-        c->prf_edge = nullptr; c->prf_edge_cap = 0;
-        SPH_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->prf_edge), ne * sizeof(double), hipHostMallocDefault));
-        c->prf_edge_cap = ne;
-    }
-    double *edge = c->prf_edge;
+    double *edge = nullptr;
+    SPH_TRY(table_staging(c, ne, &edge));
     if (const char *why = make_edges(d, edges, edge)) return arg_error(c, who, why);
 
     uint32_t rows_used = 0;                              // the rows some quantity reads

@@ -21,6 +21,7 @@
 #include <cmath>
 #include <vector>
 
+#include "disc_frame.hpp"
 #include "reduce_common.hpp"
 
 // the per-particle arithmetic is written in one documented order (summersph.h); no contraction into fused multiply-adds,
@@ -34,17 +35,6 @@ namespace {
 constexpr int NS = SPH_PROFILE_NSUM;
 constexpr int KB = 256;            // key / starts block
 
-struct Frame {
-    double c[3], cv[3];            // centre and its velocity (sink < 0)
-    double e1[3], e2[3], n[3];     // frame axes, lab components
-    double cm;                     // central mass (sink < 0)
-    double G;
-    double fixed_h;                // h of every particle when hf is null
-    const double *sink;            // the context's sink arrays (x y z vx vy vz m, MAX_SINKS each)
-    const double *hf;              // per-particle h (variable h) or null
-    int32_t sink_k;                // >= 0: centre, centre velocity and central mass are this sink's
-};
-
 struct Bins {
     const double *edge;            // n_r + 1 ring edges
     double r_min, r_max, z_max;
@@ -52,32 +42,9 @@ struct Bins {
     int32_t n_r, n_phi, log, shell;   // shell: AUTO_NORMAL pass, r_min <= |r'| < r_max as bin 0
 };
 
-__device__ __forceinline__ void centre_of(const Frame &f, double c[3], double cv[3], double &cm) {
-    if (f.sink_k >= 0) {
-        for (int a = 0; a < 3; a++) { c[a] = f.sink[a * MAX_SINKS + f.sink_k]; cv[a] = f.sink[(3 + a) * MAX_SINKS + f.sink_k]; }
-        cm = f.sink[6 * MAX_SINKS + f.sink_k];
-    } else {
-        for (int a = 0; a < 3; a++) { c[a] = f.c[a]; cv[a] = f.cv[a]; }
-        cm = f.cm;
-    }
-}
-
-__device__ __forceinline__ double dot3(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
-// r' = r - c, X = r'.e1, Y = r'.e2, z' = r'.n, R = sqrt(X^2 + Y^2)
-struct Pos { double r[3], X, Y, Z, R; };
-
-__device__ __forceinline__ Pos frame_pos(const Frame &f, const double c[3], double x, double y, double z) {
-    Pos p;
-    p.r[0] = x - c[0]; p.r[1] = y - c[1]; p.r[2] = z - c[2];
-    p.X = dot3(p.r, f.e1); p.Y = dot3(p.r, f.e2); p.Z = dot3(p.r, f.n);
-    p.R = sqrt(p.X * p.X + p.Y * p.Y);
-    return p;
-}
-
 __global__ __launch_bounds__(KB) void profile_keys(const double *__restrict__ x, const double *__restrict__ y,
                                                    const double *__restrict__ z, const int32_t *__restrict__ orig,
-                                                   int64_t n_slots, int64_t n_owned, Frame f, Bins b, uint32_t n_bins,
+                                                   int64_t n_slots, int64_t n_owned, DiscFrame f, Bins b, uint32_t n_bins,
                                                    uint64_t *__restrict__ keys, uint32_t *__restrict__ vals) {
     const int64_t i = (int64_t)blockIdx.x * KB + threadIdx.x;
     if (i >= n_slots) return;
@@ -128,7 +95,7 @@ __global__ __launch_bounds__(KB) void profile_starts(const uint64_t *__restrict_
 }
 
 // the 20 moments of one particle (summersph.h, "Raw sums"), added to acc in index order
-__device__ __forceinline__ void add_moments(const Frame &f, const double c[3], const double cv[3], double gm,
+__device__ __forceinline__ void add_moments(const DiscFrame &f, const double c[3], const double cv[3], double gm,
                                             const double *const *fld, int64_t i, double acc[NS]) {
     const Pos p = frame_pos(f, c, fld[0][i], fld[1][i], fld[2][i]);
     double v[3];
@@ -155,7 +122,7 @@ __device__ __forceinline__ void add_moments(const Frame &f, const double c[3], c
 struct Fields { const double *p[10]; };    // x y z vx vy vz u m alpha, [9] unused
 
 // one wavefront per piece slot g; gaps (slots no (bin, piece) maps to) return at once
-__global__ __launch_bounds__(KB) void profile_pieces(Fields fl, Frame f, const uint32_t *__restrict__ vals, const int32_t *__restrict__ start,
+__global__ __launch_bounds__(KB) void profile_pieces(Fields fl, DiscFrame f, const uint32_t *__restrict__ vals, const int32_t *__restrict__ start,
                                                      uint32_t n_bins, int64_t n_pieces, double *__restrict__ part) {
     const int64_t g = (int64_t)blockIdx.x * (KB / WAVE) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -219,31 +186,9 @@ const char *check_desc(const sph_profile_desc *d, int64_t n_bins, bool need_norm
     return nullptr;
 }
 
-// n^ = n / |n|; a = x^ if |n^_x| <= 0.9 else y^; e1 = normalise(a - (a.n^) n^); e2 = n^ x e1
-bool frame_axes(const double nin[3], double n[3], double e1[3], double e2[3]) {
-    const double len = std::sqrt((nin[0] * nin[0] + nin[1] * nin[1]) + nin[2] * nin[2]);
-    if (!(len > 0.0) || !std::isfinite(len)) return false;
-    for (int a = 0; a < 3; a++) n[a] = nin[a] / len;
-    double av[3] = {0.0, 0.0, 0.0};
-    av[std::fabs(n[0]) <= 0.9 ? 0 : 1] = 1.0;
-    const double an = (av[0] * n[0] + av[1] * n[1]) + av[2] * n[2];
-    double t[3];
-    for (int a = 0; a < 3; a++) t[a] = av[a] - an * n[a];
-    const double tl = std::sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
-    for (int a = 0; a < 3; a++) e1[a] = t[a] / tl;
-    e2[0] = n[1] * e1[2] - n[2] * e1[1];
-    e2[1] = n[2] * e1[0] - n[0] * e1[2];
-    e2[2] = n[0] * e1[1] - n[1] * e1[0];
-    return true;
-}
-
-// edge[k], k in [0, n_r]: linear r_min + k (r_max - r_min) / n_r, log r_min (r_max / r_min)^(k / n_r); edge[n_r] = r_max
+// edge[k], k in [0, n_r]: the frame header's table for the descriptor
 void ring_edges(const sph_profile_desc *d, double *edge) {
-    const int nr = d->n_r;
-    for (int k = 0; k < nr; k++)
-        edge[k] = (d->flags & SPH_PROFILE_LOG) ? d->r_min * std::pow(d->r_max / d->r_min, (double)k / (double)nr)
-                                               : d->r_min + ((double)k * (d->r_max - d->r_min)) / (double)nr;
-    edge[nr] = d->r_max;
+    ring_edge_table(d->r_min, d->r_max, d->n_r, (d->flags & SPH_PROFILE_LOG) != 0, edge);
 }
 
 // the scratch of a pass (both passes of a call use the same)
@@ -256,7 +201,7 @@ struct PassBufs {
 };
 
 // one pass of the pipeline: the sums of n_bins bins into d_sums (device)
-int run_pass(sph_ctx *c, const Frame &f, const Bins &b, uint32_t n_bins, const PassBufs &pb, size_t sort_bytes, int64_t n_slots,
+int run_pass(sph_ctx *c, const DiscFrame &f, const Bins &b, uint32_t n_bins, const PassBufs &pb, size_t sort_bytes, int64_t n_slots,
              double *d_sums) {
     hipStream_t st = c->stream;
     uint64_t *keys = pb.keys, *keys_alt = pb.keys_alt;
@@ -329,7 +274,7 @@ int profile_sums(sph_ctx *c, sph_profile_desc *d, double *sums, double *table, i
     double *d_out = host ? h_sums : sums;
     SPH_TRY(analysis_pinned(c));
 
-    Frame f{};
+    DiscFrame f{};
     for (int a = 0; a < 3; a++) { f.c[a] = d->centre[a]; f.cv[a] = d->centre_v[a]; }
     f.cm = d->central_mass;
     f.G = c->p.G;
@@ -366,15 +311,8 @@ int profile_sums(sph_ctx *c, sph_profile_desc *d, double *sums, double *table, i
 
     // the edge table travels in the stream's order from a pinned staging copy, rewritten only once its last upload is done
     const size_t ne = (size_t)d->n_r + 1;
-    if (!c->prf_evt) SPH_HIP(hipEventCreateWithFlags(&c->prf_evt, hipEventDisableTiming));
-    SPH_HIP(hipEventSynchronize(c->prf_evt));
-    if (ne > c->prf_edge_cap) {
-        if (c->prf_edge) SPH_HIP(hipHostFree(c->prf_edge));
-        c->prf_edge = nullptr; c->prf_edge_cap = 0;
-        SPH_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->prf_edge), ne * sizeof(double), hipHostMallocDefault));
-        c->prf_edge_cap = ne;
-    }
-    double *edge = c->prf_edge;
+    double *edge = nullptr;
+    SPH_TRY(table_staging(c, ne, &edge));
     ring_edges(d, edge);
     for (int k = 0; k < d->n_r; k++)
         if (!(edge[k] < edge[k + 1])) return arg_error(c, who, "ring edges are not strictly increasing (rings too narrow)");

@@ -442,6 +442,23 @@ void render_free(sph_ctx *c);
 // 32 pinned doubles of their read-backs, allocated at the first call that needs them
 int analysis_scratch(sph_ctx *c, size_t bytes, char **out);
 int analysis_pinned(sph_ctx *c);
+// The small host tables of sph_profile, sph_binned, sph_pairs and sph_modes (edges, wavenumbers) travel to the device in the
+// stream's order from one pinned staging copy of the context (freed by profile_free).  table_staging returns it with room
+// for `count` doubles, after the host has waited for the copy's last upload (c->prf_evt): the one host wait of the device
+// forms, which ends when the previous call's table copy has run.  The caller fills it, enqueues the copy and records
+// c->prf_evt on the stream.
+inline int table_staging(sph_ctx *c, size_t count, double **out) {
+    if (!c->prf_evt) SPH_HIP(hipEventCreateWithFlags(&c->prf_evt, hipEventDisableTiming));
+    SPH_HIP(hipEventSynchronize(c->prf_evt));
+    if (count > c->prf_edge_cap) {
+        if (c->prf_edge) SPH_HIP(hipHostFree(c->prf_edge));
+        c->prf_edge = nullptr; c->prf_edge_cap = 0;
+        SPH_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->prf_edge), count * sizeof(double), hipHostMallocDefault));
+        c->prf_edge_cap = count;
+    }
+    *out = c->prf_edge;
+    return SPH_OK;
+}
 // disc profiles (profile.hip): host form (sums and / or table host memory, one read-back) or device form (sums only)
 int profile_sums(sph_ctx *c, sph_profile_desc *d, double *sums, double *table, int64_t n_bins, bool host);
 void profile_free(sph_ctx *c);
@@ -535,6 +552,10 @@ int binned_run(sph_ctx *c, const sph_binned_desc *d, const double *values, const
 // device form (raw, exps, counts device memory or null); edges is host memory in both
 int pairs_run(sph_ctx *c, const sph_pairs_desc *d, const double *values, const double *edges, double *sums, int64_t n_out,
               uint64_t *raw, int32_t *exps, int64_t *counts, bool host);
+// azimuthal and logarithmic-spiral mode sums (modes.hip): host form (values / sums / raw / exp / ring_counts / counts[4] host
+// memory, one read-back) or device form (raw, exp, ring_counts, counts device memory or null)
+int modes_run(sph_ctx *c, const sph_modes_desc *d, const double *values, double *sums, int64_t n_out, uint64_t *raw, int32_t *exp,
+              int64_t *ring_counts, int64_t *counts, bool host);
 
 // the per-step time series (history.hip).  history_step is the step's hook (a no-op without a history); history_read only
 // enqueues the copy (the host form's caller synchronises)

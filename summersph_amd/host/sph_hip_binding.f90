@@ -65,6 +65,8 @@ module sph_hip_binding
   public :: SPH_BINNED_EDGES0, SPH_BINNED_EDGES1, SPH_BINNED_SQUARES, SPH_BINNED_SKIP_NAN
   ! pair sums (pair-separation histograms and structure functions, accumulated exactly in 128-bit fixed point)
   public :: sph_pairs_desc, sph_pairs, sph_pairs_dev, sph_pairs_edges, sph_pairs_finish, SPH_PAIRS_MAX_Q, SPH_PAIRS_MAX_BINS
+  public :: sph_modes_desc, sph_modes, sph_modes_dev, sph_modes_tables, sph_modes_finish, SPH_MODES_MAX_M, SPH_MODES_MAX_RINGS
+  public :: SPH_MODES_MAX_P, SPH_MODES_W_ONE, SPH_MODES_W_MASS, SPH_MODES_LOG
   public :: sph_history_desc, sph_history_begin, sph_history_end, sph_history_record, sph_history_info, sph_history_read
   public :: sph_history_read_dev, SPH_HISTORY_NHEAD, sph_history_begin_env, sph_history_write
   ! trajectories and fates of chosen particles
@@ -309,6 +311,22 @@ module sph_hip_binding
     integer(c_int32_t) :: target_stride, target_phase
     integer(c_int32_t) :: reserved(3)
   end type sph_pairs_desc
+
+  ! sph_modes: q is an SPH_F_* id or -1 - k: row k of values (C: SPH_MODES_ROW(k)), values(id, row) in Fortran order.  The
+  ! output is flat, n_out = 2 (m_max + 1) (n_r + n_p): the ring block as ring(2, m_max + 1, n_r) in Fortran order (C, S), then
+  ! the spiral block as spiral(2, n_p, m_max + 1) (CS, SN); raw the same with a leading axis of 2 limbs, low first.  168 bytes.
+  integer(c_int32_t), parameter :: SPH_MODES_MAX_M = 8, SPH_MODES_MAX_RINGS = 1024, SPH_MODES_MAX_P = 256
+  integer(c_int32_t), parameter :: SPH_MODES_W_ONE = 0, SPH_MODES_W_MASS = 1, SPH_MODES_LOG = 1
+  type, bind(C) :: sph_modes_desc
+    real(c_double) :: centre(3), centre_v(3)
+    real(c_double) :: normal(3)
+    real(c_double) :: r_min, r_max, z_max
+    real(c_double) :: p_min, p_max, r_ref
+    integer(c_int32_t) :: n_r, m_max, n_p, sink
+    integer(c_int32_t) :: weight, n_q, q, n_rows
+    integer(c_int32_t) :: flags
+    integer(c_int32_t) :: reserved(3)
+  end type sph_modes_desc
 
   ! sph_history: a row is SPH_HISTORY_NHEAD + 7 max_sinks doubles; rows(width, count) in Fortran order.  16 bytes.
   integer(c_int32_t), parameter :: SPH_HISTORY_NHEAD = 40
@@ -960,6 +978,35 @@ module sph_hip_binding
       import :: c_int, c_int32_t, c_int64_t, c_double, sph_pairs_desc
       type(sph_pairs_desc), intent(in) :: d
       integer(c_int32_t), intent(in) :: exps(*)
+      integer(c_int64_t), intent(in) :: raw(*)
+      real(c_double), intent(out) :: sums(*)
+    end function
+    ! ---- mode sums: values, host_sums, host_raw, exp, ring_counts and counts are c_loc(...) (c_null_ptr where the header
+    !      allows NULL); the _dev form takes device memory
+    integer(c_int) function sph_modes(ctx, d, values, host_sums, n_out, host_raw, exp, ring_counts, counts) bind(C, name='sph_modes')
+      import :: c_int, c_int64_t, c_ptr, sph_modes_desc
+      type(c_ptr), value :: ctx, values, host_sums, host_raw, exp, ring_counts, counts
+      type(sph_modes_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_out
+    end function
+    integer(c_int) function sph_modes_dev(ctx, d, d_values, d_sums, n_out, d_raw, d_exp, d_ring_counts, d_counts) &
+        bind(C, name='sph_modes_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_modes_desc
+      type(c_ptr), value :: ctx, d_values, d_sums, d_raw, d_exp, d_ring_counts, d_counts
+      type(sph_modes_desc), intent(in) :: d
+      integer(c_int64_t), value :: n_out
+    end function
+    ! the tables the call uses: edges_out holds n_r + 1 doubles, p_out n_p (at least 1); host only, no context
+    integer(c_int) function sph_modes_tables(d, edges_out, p_out) bind(C, name='sph_modes_tables')
+      import :: c_int, c_double, sph_modes_desc
+      type(sph_modes_desc), intent(in) :: d
+      real(c_double), intent(out) :: edges_out(*), p_out(*)
+    end function
+    ! raw limbs (2, n_out) and their exponent -> the correctly rounded doubles (n_out); host only, no context
+    integer(c_int) function sph_modes_finish(d, exp, raw, sums) bind(C, name='sph_modes_finish')
+      import :: c_int, c_int32_t, c_int64_t, c_double, sph_modes_desc
+      type(sph_modes_desc), intent(in) :: d
+      integer(c_int32_t), intent(in) :: exp
       integer(c_int64_t), intent(in) :: raw(*)
       real(c_double), intent(out) :: sums(*)
     end function
