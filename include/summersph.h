@@ -1588,6 +1588,96 @@ int sph_track_read_dev(sph_ctx *ctx, int64_t first, int64_t count, double *d_hea
 int sph_track_fates(sph_ctx *ctx, int32_t *host_fates);
 int sph_track_fates_dev(sph_ctx *ctx, int32_t *d_fates);
 
+/* ---- frames: a device-resident movie of a run -- line-of-sight-integrated maps of the owned gas appended from the end of
+ *      the step, and the same map as a one-shot call (summersph_amd/frames.py) ------------------------------------------
+ * Between sph_frames_begin and sph_frames_end the steps of sph_step / sph_run append frames to a log of `capacity` rows, at
+ * the very end of the step, after sph_history's and sph_track's rows and independent of them.  The frame's kernels run on
+ * the context's stream; a recorded step adds no stream synchronisation and no host read-back.  Without frames begun the
+ * step is exactly what it is without this section: no kernel, no argument and no allocation differ.  The recorder only
+ * reads the state and names no particle: it survives accretion, culls and a new upload.  One context (several ranks'
+ * frames are not combined here).
+ * Frame, Select, Nodes  exactly sph_cube's: rot[9] with rows u^, v^, w^ (orthonormal and right-handed within 1e-12, else
+ *          SPH_ERR_ARG); P_j = rot (r_j - C), every row evaluated as ((a0 dx + a1 dy) + a2 dz) with no fused multiply-adds;
+ *          the owned gas particles with clip_lo < r < clip_hi on every axis of the SIMULATION frame (strict); h > 0: one h
+ *          for every particle, 0: each particle's own; node i on image axis a is lo[a] + i (hi[a] - lo[a]) / (n - 1), the
+ *          last one exactly hi[a] (np.linspace), n == 1: the single node lo[a]; nodes are point-sampled.
+ * Centre   C = centre, or with centre_sink >= 0 centre[a] + the position of that sink at the time of the frame, read on the
+ *          device.  A sink index >= the current sink count: every plane of that frame is NaN and the head's status is
+ *          SPH_FRAMES_SINK_GONE.
+ * Planes   plane 0 is the column density, planes 1 .. nq (nq <= SPH_FRAMES_MAX_FIELDS) the same sum weighted by the context's
+ *          field fields[k - 1] (an SPH_F_* id).  The term of particle j at node g, with p = sqrt(du du + dv dv) / h_j, du and
+ *          dv the node's coordinates minus P_j,u and P_j,v, is (y0_j A_j) F(p) for p < 2 and nothing otherwise:
+ *          y0_j = m_j / (pi (h_j h_j)), pi in double precision (sph_transfer's y0 with kappa = 1); A_j = 1 for plane 0 and
+ *          the field's value otherwise; F the line-integrated spline of sph_cube ("Footprint" above), F <= F(0) = 1.5.  No
+ *          fused multiply-adds.  A field that sph_download_field would refuse at that moment makes its plane NaN for that
+ *          frame and leaves the others alone (sph_history's rule for rho).
+ * Sum      per plane, B = max |y0_j A_j| over the SELECTED particles (whether or not they reach a node) and e the exponent
+ *          with 1.5 B < 2^e (0 for B = 0).  Every term is rounded half-even to a multiple of 2^(e - 62), the integers are
+ *          added in 128 bits and each node is rounded to a double once (sph_pairs' arithmetic).  A selected particle whose
+ *          1.5 y0 A is not finite makes that plane of that frame NaN.  A frame is therefore a function of the descriptor
+ *          and the selected particles' values alone: bitwise the same for any slot order, upload order, grid kind, launch
+ *          shape, binning and repetition, and it differs from the real-number sum of the fp64 terms by at most
+ *          (terms on that node) 2^(e - 63) plus the final rounding.
+ * Head     SPH_FRAMES_NHEAD doubles per frame: 0 the step number (steps are counted since begin, the unrecorded ones
+ *          included; sph_frame: the count of the log that is begun, else 0); 1 t, the device's time word; 2 the owned gas
+ *          count; 3 the selected count; 4-6 C; 7-10 the planes' exponents e (NaN for a plane that is unused or NaN);
+ *          11 the status (SPH_FRAMES_OK, SPH_FRAMES_SINK_GONE); 12-15 zero.
+ * Log      planes: capacity x (1 + nq) x n_u x n_v doubles in C order [row][plane][iu][iv]; heads: capacity x 16.  A full
+ *          log drops further frames and counts them.  sph_frames_rewind sets the row count to 0 and keeps the allocation,
+ *          the step number, the cadence counter and the dropped count: a long movie is drained between sph_run chunks.
+ * Cadence  every >= 1 with dt_frame == 0: the steps whose running number is a multiple of `every`, decided on the host as
+ *          sph_history does.  dt_frame > 0 with every == 0: uniform in simulation time, the reference's save rule, decided
+ *          on the device, where t lives during sph_run: with t0 the context's t at begin and k starting at 1, a step that
+ *          ends at time t records a frame iff t >= t0 + k dt_frame (product, then sum, in double), and afterwards
+ *          k = floor((t - t0) / dt_frame) + 1 -- at most one frame per step, missed thresholds are skipped.  In this mode
+ *          the frame's launches are enqueued every step and return at once when no frame is due.  The due decision, the row
+ *          index and the dropped count are device words in both modes; sph_frames_info is the only call that reads them
+ *          back (it synchronises; null outputs are skipped, and asking for steps alone does not wait).
+ * record   sph_frames_record appends a frame of the state as it is now, whatever the cadence, without advancing the step
+ *          number or the cadence counter.
+ * read     sph_frames_read copies rows [first, first + count) to the host (either pointer may be null): it reads the row
+ *          count, synchronises and reports what sph_get_dt reports.  sph_frames_read_dev copies to device memory in the
+ *          stream's order without waiting; it cannot know the row count, so its range is checked against the capacity.
+ * One-shot sph_frame / sph_frame_dev: the frame of the state as it is now into head (16 doubles) and planes (out_len ==
+ *          (1 + nq) n_u n_v doubles), by the same kernels on the analysis scratch; capacity, every and dt_frame are not
+ *          read.  sph_frame_dev makes no stream synchronisation and no read-back; sph_frame synchronises once, for its
+ *          copies.  Neither of them touches a log that is begun.
+ * cost     five launches per frame: two passes over the sorted state, the clear and the conversion of the image, one
+ *          block.  The log, 32 (1 + nq) n_u n_v bytes of limbs and about 50 kB are counted in device_bytes from begin to end.
+ * SPH_ERR_ARG: a null descriptor or output, reserved != 0, n_u or n_v < 1, nq outside 0 .. 3, an unknown field id, h < 0 or
+ * non-finite, lo > hi or non-finite, a NaN clip, a non-finite centre, a bad rot, centre_sink >= 64, capacity < 1, neither
+ * cadence or both (every < 0 and a negative or non-finite dt_frame included), out_len != (1 + nq) n_u n_v, first or count
+ * outside the rows.  SPH_ERR_STATE: record, rewind, info, read or end without begin.  SPH_ERR_NOMEM: (1 + nq) n_u n_v above
+ * 2^28, or the log does not fit. */
+#define SPH_FRAMES_MAX_FIELDS 3
+#define SPH_FRAMES_NHEAD 16
+#define SPH_FRAMES_OK 0
+#define SPH_FRAMES_SINK_GONE 1
+typedef struct sph_frames_desc {
+    double  rot[9];                 /* rows u^, v^, w^ (row-major)                                   */
+    double  centre[3];              /* origin of the image plane (added to the sink's position)      */
+    double  lo[2], hi[2];           /* node box on the image axes u, v                               */
+    double  clip_lo[3], clip_hi[3]; /* strict particle clip box (simulation axes); -/+INFINITY = none */
+    double  h;                      /* > 0: one h for all; 0: each particle's own h                  */
+    double  dt_frame;               /* > 0: a frame every dt_frame of simulation time; 0: `every`    */
+    int64_t capacity;               /* frames the log holds (>= 1)                                   */
+    int32_t n_u, n_v;               /* image nodes per axis, each >= 1                               */
+    int32_t every;                  /* >= 1: every every-th step; 0 with dt_frame > 0                */
+    int32_t centre_sink;            /* >= 0: the frame follows this sink; < 0: none                  */
+    int32_t nq;                     /* weighted planes, 0 .. 3                                       */
+    int32_t fields[SPH_FRAMES_MAX_FIELDS]; /* their SPH_F_* ids                                      */
+    int64_t reserved;               /* must be 0                                                     */
+} sph_frames_desc;                  /* 240 bytes */
+int sph_frames_begin(sph_ctx *ctx, const sph_frames_desc *d);     /* allocate, rows = 0, step number = 0, t0 = t; a second begin replaces the first */
+int sph_frames_end(sph_ctx *ctx);
+int sph_frames_record(sph_ctx *ctx);
+int sph_frames_rewind(sph_ctx *ctx);
+int sph_frames_info(sph_ctx *ctx, int64_t *rows, int64_t *dropped, int64_t *steps);
+int sph_frames_read(sph_ctx *ctx, int64_t first, int64_t count, double *host_head, double *host_planes);
+int sph_frames_read_dev(sph_ctx *ctx, int64_t first, int64_t count, double *d_head, double *d_planes);
+int sph_frame(sph_ctx *ctx, const sph_frames_desc *d, double *host_head, double *host_planes, int64_t out_len);
+int sph_frame_dev(sph_ctx *ctx, const sph_frames_desc *d, double *d_head, double *d_planes, int64_t out_len);
+
 /* ---- diagnostics / measurement -------------------------------------------------------- */
 int sph_get_stats(sph_ctx *ctx, sph_stats *out);
 /* the cell grid of the last build: dense (one table entry per cell of the box) or hashed (SPH_FLAG_HASHED_GRID, or a box too

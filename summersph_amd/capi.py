@@ -61,6 +61,8 @@ SYMBOLS = [
     "sph_history_begin", "sph_history_end", "sph_history_record", "sph_history_info", "sph_history_read", "sph_history_read_dev",
     "sph_track_begin", "sph_track_begin_dev", "sph_track_end", "sph_track_record", "sph_track_info", "sph_track_read",
     "sph_track_read_dev", "sph_track_fates", "sph_track_fates_dev",
+    "sph_frames_begin", "sph_frames_end", "sph_frames_record", "sph_frames_rewind", "sph_frames_info", "sph_frames_read",
+    "sph_frames_read_dev", "sph_frame", "sph_frame_dev",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
@@ -93,6 +95,10 @@ TRACK_HEAD = ["step", "t", "n", "n_live"]
 TRACK_COLUMNS = ["x", "y", "z", "vx", "vy", "vz", "u", "rho", "h", "alpha"]
 TRACK_FATES = ["fate", "step", "sink", "current_id"]
 TRACK_ALIVE, TRACK_ACCRETED, TRACK_CULLED = 0, 1, 2
+FRAMES_NHEAD = 16
+FRAMES_MAX_FIELDS = 3
+FRAMES_MAX_SINKS = 64
+FRAMES_OK, FRAMES_SINK_GONE = 0, 1
 GROUPS_LINK_H = 1
 GROUPS_NCOL = 21
 # sph_groups' table columns (include/summersph.h, "Table")
@@ -664,6 +670,56 @@ def history_columns(rows, dropped=0) -> dict:
     return out
 
 
+class FramesDesc(C.Structure):
+    """sph_frames_desc (include/summersph.h): rot (rows u^, v^, w^), centre, image node box, strict clip box, h, dt_frame,
+    capacity, image nodes, every, centre_sink, nq, fields, reserved"""
+    _fields_ = [("rot", C.c_double * 9), ("centre", C.c_double * 3), ("lo", C.c_double * 2), ("hi", C.c_double * 2),
+                ("clip_lo", C.c_double * 3), ("clip_hi", C.c_double * 3), ("h", C.c_double), ("dt_frame", C.c_double),
+                ("capacity", C.c_int64), ("n_u", C.c_int32), ("n_v", C.c_int32), ("every", C.c_int32),
+                ("centre_sink", C.c_int32), ("nq", C.c_int32), ("fields", C.c_int32 * 3), ("reserved", C.c_int64)]
+
+
+def frames_desc(shape, bounds, capacity=1, every=1, dt_frame=None, rot=None, centre=None, centre_sink=None, fields=(), h=None,
+                clip=None) -> FramesDesc:
+    """The descriptor of Context.frames_begin's and Context.frame's arguments (see there).  dt_frame given and every left at
+    1: the cadence is dt_frame's (every = 0 in the descriptor); both given: both are passed on, which the library refuses."""
+    n = (int(shape),) * 2 if np.isscalar(shape) else tuple(int(v) for v in shape)
+    if len(n) != 2:
+        raise ValueError("shape: one node count or (n_u, n_v)")
+    fields = (fields,) if isinstance(fields, (str, int, np.integer)) else tuple(fields)
+    if len(fields) > FRAMES_MAX_FIELDS:
+        raise ValueError(f"frames: at most {FRAMES_MAX_FIELDS} fields")
+    d = FramesDesc()
+    d.rot[:] = np.asarray(np.eye(3) if rot is None else rot, dtype=np.float64).reshape(9).tolist()
+    d.centre[:] = [float(v) for v in ((0.0, 0.0, 0.0) if centre is None else centre)]
+    b = np.asarray(bounds, dtype=np.float64).reshape(2, 2)
+    d.lo[:] = b[0].tolist(); d.hi[:] = b[1].tolist()
+    cb = np.array([[-np.inf] * 3, [np.inf] * 3]) if clip is None else np.asarray(clip, dtype=np.float64).reshape(2, 3)
+    d.clip_lo[:] = cb[0].tolist(); d.clip_hi[:] = cb[1].tolist()
+    d.h = 0.0 if h is None else float(h)
+    d.dt_frame = 0.0 if dt_frame is None else float(dt_frame)
+    d.capacity = int(capacity)
+    d.n_u, d.n_v = n
+    d.every = 0 if (dt_frame is not None and int(every) == 1) else int(every)
+    d.centre_sink = -1 if centre_sink is None else int(centre_sink)
+    d.nq = len(fields)
+    for k, f in enumerate(fields):
+        d.fields[k] = FIELDS.index(f) if isinstance(f, str) else int(f)
+    return d
+
+
+def frames_columns(head, planes, dropped=0) -> dict:
+    """Raw frames, head (R, FRAMES_NHEAD) and planes (R, 1 + nq, n_u, n_v), -> the dict Context.frames returns: step, n,
+    n_sel and status as int64 (R,), t (R,), centre (R, 3), exp (R, 4; NaN where a plane is unused or NaN), planes, head and
+    dropped."""
+    hd = np.asarray(head, dtype=np.float64)
+    if hd.ndim != 2 or hd.shape[1] != FRAMES_NHEAD:
+        raise ValueError("frames: head must be (R, FRAMES_NHEAD)")
+    return {"step": hd[:, 0].astype(np.int64), "t": hd[:, 1], "n": hd[:, 2].astype(np.int64), "n_sel": hd[:, 3].astype(np.int64),
+            "centre": hd[:, 4:7], "exp": hd[:, 7:11], "status": hd[:, 11].astype(np.int64), "planes": planes, "head": hd,
+            "dropped": int(dropped)}
+
+
 class TrackDesc(C.Structure):
     """sph_track_desc (include/summersph.h)"""
     _fields_ = [("capacity", C.c_int64), ("every", C.c_int32), ("flags", C.c_int32)]
@@ -1036,6 +1092,14 @@ def load():
         fn.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
     for fn in (lib.sph_track_fates, lib.sph_track_fates_dev):
         fn.argtypes = [C.c_void_p, C.c_void_p]
+    lib.sph_frames_begin.argtypes = [C.c_void_p, C.POINTER(FramesDesc)]
+    for fn in (lib.sph_frames_end, lib.sph_frames_record, lib.sph_frames_rewind):
+        fn.argtypes = [C.c_void_p]
+    lib.sph_frames_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3
+    for fn in (lib.sph_frames_read, lib.sph_frames_read_dev):
+        fn.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    for fn in (lib.sph_frame, lib.sph_frame_dev):
+        fn.argtypes = [C.c_void_p, C.POINTER(FramesDesc), C.c_void_p, C.c_void_p, C.c_int64]
     _lib = lib
     return lib
 
@@ -1703,6 +1767,69 @@ class Context:
         return {name: fates[:, i] for i, name in enumerate(TRACK_FATES)}
 
     # ---- friends-of-friends groups (sph_groups) --------------------------------------------------
+    # ---- the movie of a run (sph_frames) -------------------------------------------------------------
+    def frames_begin(self, shape, bounds, capacity, every=1, dt_frame=None, rot=None, centre=None, centre_sink=None, fields=(),
+                     h=None, clip=None):
+        """Starts (or restarts) the device-resident log of frames (include/summersph.h, sph_frames): column-density maps of
+        the owned gas on shape nodes over bounds = ((lo_u, lo_v), (hi_u, hi_v)), plus one plane per field weighted by it,
+        appended every every-th step of step / run or, with dt_frame, whenever t passes the next multiple of dt_frame since
+        now.  rot, centre, h, clip: as cube; centre_sink: the frame follows that sink.  The descriptor is left in
+        self.frames_desc."""
+        d = frames_desc(shape, bounds, capacity, every, dt_frame, rot, centre, centre_sink, fields, h, clip)
+        self._ck(self.lib.sph_frames_begin(self._h, C.byref(d)))
+        self.frames_desc = d
+
+    def frames_record(self):
+        """Appends a frame of the state as it is now, whatever the cadence (the step number is not advanced)."""
+        self._ck(self.lib.sph_frames_record(self._h))
+
+    def frames_rewind(self):
+        """Sets the row count to 0 and keeps the allocation: drain a long movie between runs."""
+        self._ck(self.lib.sph_frames_rewind(self._h))
+
+    def frames_end(self):
+        self._ck(self.lib.sph_frames_end(self._h))
+
+    def frames_info(self) -> dict:
+        """rows held, frames dropped and steps counted since frames_begin (reads the device's counts: waits for the stream)"""
+        r, d, s = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._ck(self.lib.sph_frames_info(self._h, C.byref(r), C.byref(d), C.byref(s)))
+        return {"rows": r.value, "dropped": d.value, "steps": s.value}
+
+    def frames(self, first=0, count=None, device=False):
+        """Frames [first, first + count) of the log (count None: all from first) as frames_columns' dict: step, t, n, n_sel,
+        centre, exp, status per frame, planes (rows, 1 + nq, n_u, n_v) and dropped.  device=True: planes and head are torch
+        tensors copied on the context's GPU in the stream's order (sph_frames_read_dev); the named columns are read from
+        the head."""
+        info = self.frames_info()
+        d = self.frames_desc
+        first = int(first)
+        cnt = info["rows"] - first if count is None else int(count)
+        f = self._form(device)
+        head = f.empty((max(cnt, 0), FRAMES_NHEAD))
+        planes = f.empty((max(cnt, 0), 1 + d.nq, d.n_u, d.n_v))
+        if device and not 0 <= first <= first + cnt <= info["rows"]:
+            raise SphError(-1, "sph_frames_read_dev: first / count outside [0, rows]")
+        f.call("sph_frames_read", first, cnt, f.ptr(head), f.ptr(planes))
+        out = frames_columns(f.host(head), planes, info["dropped"])
+        if device:
+            out["head"] = head
+        return out
+
+    def frame(self, shape, bounds, rot=None, centre=None, centre_sink=None, fields=(), h=None, clip=None, device=False):
+        """One frame of the state as it is now (sph_frame): (head, planes) with head the FRAMES_NHEAD doubles of a log's head
+        and planes (1 + nq, n_u, n_v); frames_columns(head[None], planes[None]) names the head's entries.  device=True:
+        torch tensors, no stream synchronisation and no read-back (sph_frame_dev).  The descriptor is left in
+        self.frame_desc."""
+        d = self.frame_desc = frames_desc(shape, bounds, 1, 1, None, rot, centre, centre_sink, fields, h, clip)
+        oshape = (1 + d.nq, d.n_u, d.n_v)
+        size = int(np.prod(oshape, dtype=np.int64)) if min(oshape) > 0 else 0
+        f = self._form(device)
+        head = f.empty(FRAMES_NHEAD)
+        planes = f.empty([max(k, 0) for k in oshape])
+        f.call("sph_frame", C.byref(d), f.ptr(head), f.ptr(planes), size)
+        return head, planes
+
     def _components(self, name, d, n_col, n_count, max_groups, labels, f):
         """the call groups and peaks share: (labels, the max_groups table rows, max_groups, the counts buffer)"""
         n = self.n

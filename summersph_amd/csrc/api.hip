@@ -414,7 +414,8 @@ int one_step_device_dt(sph_ctx *c) {
         SPH_TRY(do_accrete(c, &removed));
     }
     SPH_TRY(history_step(c));                          // sph_history: a row of the state sph_download_state would return now
-    return c->track ? track_step(c) : SPH_OK;          // sph_track: the tracked particles' row of the same state
+    if (c->track) SPH_TRY(track_step(c));              // sph_track: the tracked particles' row of the same state
+    return c->frames ? frames_step(c) : SPH_OK;        // sph_frames: the maps of the same state
 }
 
 }  // namespace
@@ -587,6 +588,7 @@ int sph_ctx_destroy(sph_ctx *c) {
     profile_free(c);
     history_free(c);
     track_free(c);
+    frames_free(c);
     if (c->stream && c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return SPH_OK;
@@ -1520,6 +1522,64 @@ int sph_track_fates_dev(sph_ctx *c, int32_t *d_fates) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
     return track_fates(c, d_fates, false);
+}
+
+int sph_frames_begin(sph_ctx *c, const sph_frames_desc *d) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return frames_begin(c, d);
+}
+
+int sph_frames_end(sph_ctx *c) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return frames_end(c);
+}
+
+int sph_frames_record(sph_ctx *c) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return frames_record(c);
+}
+
+int sph_frames_rewind(sph_ctx *c) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return frames_rewind(c);
+}
+
+int sph_frames_info(sph_ctx *c, int64_t *rows, int64_t *dropped, int64_t *steps) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return frames_info(c, rows, dropped, steps);
+}
+
+int sph_frames_read(sph_ctx *c, int64_t first, int64_t count, double *host_head, double *host_planes) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    SPH_TRY(frames_read(c, first, count, host_head, host_planes, true));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    return drain_reports(c);
+}
+
+int sph_frames_read_dev(sph_ctx *c, int64_t first, int64_t count, double *d_head, double *d_planes) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return frames_read(c, first, count, d_head, d_planes, false);
+}
+
+int sph_frame(sph_ctx *c, const sph_frames_desc *d, double *host_head, double *host_planes, int64_t out_len) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    SPH_TRY(frame_run(c, d, host_head, host_planes, out_len, true));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    return SPH_OK;
+}
+
+int sph_frame_dev(sph_ctx *c, const sph_frames_desc *d, double *d_head, double *d_planes, int64_t out_len) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return frame_run(c, d, d_head, d_planes, out_len, false);
 }
 
 int sph_synchronize(sph_ctx *c) {

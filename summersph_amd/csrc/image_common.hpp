@@ -1,6 +1,7 @@
-// image_common.hpp -- what the image passes (render.hip, cube.hip, transfer.hip) define in common: which particles a call
-// selects and with which h, how far a particle reaches, where the np.linspace nodes sit, the viewing frame, the start
-// table of a sorted key array and the host checks that go with them.  The order-rule and determinism tests and the
+// image_common.hpp -- what the image passes (render.hip, cube.hip, transfer.hip, frames.hip) define in common: which
+// particles a call selects and with which h, how far a particle reaches, where the np.linspace nodes sit and which of them
+// lie within a reach (node_range: transfer.hip's tiles, frames.hip's footprints), the viewing frame, the start table of a
+// sorted key array and the host checks that go with them.  The order-rule and determinism tests and the
 // comparison of sph_transfer against sph_cube rely on these being one function in every pass.  The binning itself
 // (3-D cells, image-plane cells, depth-sorted tile lists) differs per pass and stays in its file.
 #pragma once
@@ -45,6 +46,25 @@ struct Nodes {
 template <int D>
 __device__ __forceinline__ double node_coord(const Nodes<D> &nd, int a, int i) {
     return i >= nd.n[a] - 1 ? nd.hi[a] : (double)i * nd.step[a] + nd.lo[a];
+}
+
+// the nodes i0 .. i1 of axis a with p - reach <= node <= p + reach, decided on the node coordinates themselves (the
+// division only gives the first guess); false when there is none (or p is NaN)
+__device__ __forceinline__ bool node_range(const Nodes<2> &nd, int a, double p, double reach, int &i0, int &i1) {
+    const double a0 = p - reach, a1 = p + reach;
+    const int n = nd.n[a];
+    if (!(a1 >= nd.lo[a] && a0 <= nd.hi[a])) return false;
+    i0 = 0;
+    i1 = n - 1;
+    if (n == 1 || !(nd.step[a] > 0.0) || !(nd.step[a] < INFINITY)) return true;     // every node sits on lo (or the step overflowed)
+    const double last = (double)(n - 1);
+    i0 = (int)fmin(fmax(ceil((a0 - nd.lo[a]) / nd.step[a]), 0.0), last);
+    i1 = (int)fmin(fmax(floor((a1 - nd.lo[a]) / nd.step[a]), 0.0), last);
+    while (i0 > 0 && node_coord(nd, a, i0 - 1) >= a0) i0--;
+    while (node_coord(nd, a, i0) < a0) i0++;               // stops at n - 1 at the latest: hi >= a0
+    while (i1 < n - 1 && node_coord(nd, a, i1 + 1) <= a1) i1++;
+    while (node_coord(nd, a, i1) > a1) i1--;               // stops at 0 at the latest: lo <= a1
+    return i0 <= i1;
 }
 
 struct Frame {

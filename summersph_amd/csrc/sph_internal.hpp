@@ -109,6 +109,7 @@ struct PinnedSlots {
 };
 struct History;                                              // the per-step time series (history.hip); null: none begun
 struct Track;                                                // the tracked particles' log (track.hip); null: none begun
+struct Frames;                                               // the movie's log (frames.hip); null: none begun
 static_assert(offsetof(BoxReport, nonfinite) == 6 * sizeof(double) && sizeof(BoxReport) % 8 == 0, "bbox_final's layout");
 static_assert(sizeof(DtWords) == 3 * sizeof(double) && sizeof(HStats) == 4 * sizeof(double), "copied as arrays of doubles");
 #define SPH_PIN_ALIGNED(m, a) static_assert(offsetof(PinnedSlots, m) % (a) == 0, #m " is misaligned for its writer")
@@ -285,6 +286,8 @@ struct sph_ctx : sph::CtxState {
     sph::History *hist = nullptr;
     // sph_track (track.hip): the log, the membership bitmap with its prefix and tags, the fates and the host-side counts
     sph::Track *track = nullptr;
+    // sph_frames (frames.hip): the log, the limb image, the partials, the device words and the host-side step count
+    sph::Frames *frames = nullptr;
 };
 
 // Host scaffolding of every launcher that has the context as `c` and returns a status.
@@ -581,5 +584,17 @@ int track_packed(sph_ctx *c, const int32_t *keep, const int32_t *pos, const unsi
 int track_info(sph_ctx *c, int64_t *rows, int64_t *dropped, int64_t *steps, int64_t *n_tracked, int64_t *n_live, int32_t *closed);
 int track_read(sph_ctx *c, int64_t first, int64_t count, double *head, double *body, bool host);
 int track_fates(sph_ctx *c, int32_t *fates, bool host);
+
+// the movie of a run (frames.hip).  frames_step is the step's hook (called where c->frames is set); frames_read and frame_run
+// only enqueue the copies (the host forms' callers synchronise); frames_info reads the device's counts and synchronises
+int frames_begin(sph_ctx *c, const sph_frames_desc *d);
+int frames_end(sph_ctx *c);
+void frames_free(sph_ctx *c);
+int frames_record(sph_ctx *c);
+int frames_step(sph_ctx *c);
+int frames_rewind(sph_ctx *c);
+int frames_info(sph_ctx *c, int64_t *rows, int64_t *dropped, int64_t *steps);
+int frames_read(sph_ctx *c, int64_t first, int64_t count, double *head, double *planes, bool host);
+int frame_run(sph_ctx *c, const sph_frames_desc *d, double *head, double *planes, int64_t out_len, bool host);
 
 }  // namespace sph

@@ -68,25 +68,6 @@ __device__ __forceinline__ double src_at(const Src &s, const int32_t *orig, int6
     return s.field ? s.field[i] : (s.values ? s.values[orig[i]] : 1.0);
 }
 
-// the nodes i0 .. i1 of axis a with p - reach <= node <= p + reach, decided on the node coordinates themselves (the
-// division only gives the first guess); false when there is none (or p is NaN)
-__device__ __forceinline__ bool node_range(const Nodes<2> &nd, int a, double p, double reach, int &i0, int &i1) {
-    const double a0 = p - reach, a1 = p + reach;
-    const int n = nd.n[a];
-    if (!(a1 >= nd.lo[a] && a0 <= nd.hi[a])) return false;
-    i0 = 0;
-    i1 = n - 1;
-    if (n == 1 || !(nd.step[a] > 0.0) || !(nd.step[a] < INFINITY)) return true;     // every node sits on lo (or the step overflowed)
-    const double last = (double)(n - 1);
-    i0 = (int)fmin(fmax(ceil((a0 - nd.lo[a]) / nd.step[a]), 0.0), last);
-    i1 = (int)fmin(fmax(floor((a1 - nd.lo[a]) / nd.step[a]), 0.0), last);
-    while (i0 > 0 && node_coord(nd, a, i0 - 1) >= a0) i0--;
-    while (node_coord(nd, a, i0) < a0) i0++;               // stops at n - 1 at the latest: hi >= a0
-    while (i1 < n - 1 && node_coord(nd, a, i1 + 1) <= a1) i1++;
-    while (node_coord(nd, a, i1) > a1) i1--;               // stops at 0 at the latest: lo <= a1
-    return i0 <= i1;
-}
-
 // the tiles [t0[a], t1[a]] that hold the nodes within the reach of P; false: none
 __device__ __forceinline__ bool tile_range(const Nodes<2> &nd, double pu, double pv, double reach, int t0[2], int t1[2]) {
     int i0, i1;

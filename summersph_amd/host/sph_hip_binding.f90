@@ -73,6 +73,10 @@ module sph_hip_binding
   public :: sph_track_desc, sph_track_begin, sph_track_begin_dev, sph_track_end, sph_track_record, sph_track_info, sph_track_read
   public :: sph_track_read_dev, sph_track_fates, sph_track_fates_dev, SPH_TRACK_NHEAD, SPH_TRACK_NCOL, sph_track_begin_env
   public :: sph_track_write
+  ! the movie of a run: line-of-sight-integrated maps of the owned gas appended on the device, and the one-shot frame
+  public :: sph_frames_desc, sph_frames_begin, sph_frames_end, sph_frames_record, sph_frames_rewind, sph_frames_info
+  public :: sph_frames_read, sph_frames_read_dev, sph_frame, sph_frame_dev, SPH_FRAMES_NHEAD, SPH_FRAMES_MAX_FIELDS
+  public :: SPH_FRAMES_OK, SPH_FRAMES_SINK_GONE, sph_frames_begin_env, sph_frames_write
   public :: SPH_PAIRS_W_ONE, SPH_PAIRS_W_MASS, SPH_PAIRS_LOG, SPH_PAIRS_CALLER_EDGES, SPH_PAIRS_SCALE_H, SPH_PAIRS_VELOCITY
   public :: c_message
 
@@ -341,6 +345,23 @@ module sph_hip_binding
     integer(c_int64_t) :: capacity
     integer(c_int32_t) :: every, flags
   end type sph_track_desc
+
+  ! sph_frames: a frame is a head of SPH_FRAMES_NHEAD doubles and 1 + nq planes, planes(n_v, n_u, 1 + nq, count) in Fortran
+  ! order; rot(9) holds the rows u^, v^, w^ one after the other.  240 bytes.
+  integer(c_int32_t), parameter :: SPH_FRAMES_NHEAD = 16, SPH_FRAMES_MAX_FIELDS = 3
+  integer(c_int32_t), parameter :: SPH_FRAMES_OK = 0, SPH_FRAMES_SINK_GONE = 1
+  type, bind(C) :: sph_frames_desc
+    real(c_double) :: rot(9)
+    real(c_double) :: centre(3)
+    real(c_double) :: lo(2), hi(2)
+    real(c_double) :: clip_lo(3), clip_hi(3)
+    real(c_double) :: h, dt_frame
+    integer(c_int64_t) :: capacity
+    integer(c_int32_t) :: n_u, n_v
+    integer(c_int32_t) :: every, centre_sink, nq
+    integer(c_int32_t) :: fields(SPH_FRAMES_MAX_FIELDS)
+    integer(c_int64_t) :: reserved
+  end type sph_frames_desc
 
   interface
     integer(c_int) function sph_abi_version() bind(C, name='sph_abi_version')
@@ -1084,6 +1105,51 @@ module sph_hip_binding
       import :: c_int, c_ptr
       type(c_ptr), value :: ctx, d_fates
     end function
+    ! ---- frames: info's outputs and read's head and planes are c_loc(...) (any of them may be c_null_ptr); the d_ arguments
+    !      are device memory
+    integer(c_int) function sph_frames_begin(ctx, d) bind(C, name='sph_frames_begin')
+      import :: c_int, c_ptr, sph_frames_desc
+      type(c_ptr), value :: ctx
+      type(sph_frames_desc), intent(in) :: d
+    end function
+    integer(c_int) function sph_frames_end(ctx) bind(C, name='sph_frames_end')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function sph_frames_record(ctx) bind(C, name='sph_frames_record')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function sph_frames_rewind(ctx) bind(C, name='sph_frames_rewind')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function sph_frames_info(ctx, rows, dropped, steps) bind(C, name='sph_frames_info')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, rows, dropped, steps
+    end function
+    integer(c_int) function sph_frames_read(ctx, first, count, host_head, host_planes) bind(C, name='sph_frames_read')
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: ctx, host_head, host_planes
+      integer(c_int64_t), value :: first, count
+    end function
+    integer(c_int) function sph_frames_read_dev(ctx, first, count, d_head, d_planes) bind(C, name='sph_frames_read_dev')
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: ctx, d_head, d_planes
+      integer(c_int64_t), value :: first, count
+    end function
+    integer(c_int) function sph_frame(ctx, d, host_head, host_planes, out_len) bind(C, name='sph_frame')
+      import :: c_int, c_int64_t, c_ptr, sph_frames_desc
+      type(c_ptr), value :: ctx, host_head, host_planes
+      type(sph_frames_desc), intent(in) :: d
+      integer(c_int64_t), value :: out_len
+    end function
+    integer(c_int) function sph_frame_dev(ctx, d, d_head, d_planes, out_len) bind(C, name='sph_frame_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_frames_desc
+      type(c_ptr), value :: ctx, d_head, d_planes
+      type(sph_frames_desc), intent(in) :: d
+      integer(c_int64_t), value :: out_len
+    end function
   end interface
 
 contains
@@ -1221,4 +1287,91 @@ contains
     close(u)
     st = sph_track_end(ctx)
   end function sph_track_write
+
+  ! The hosts' optional movie file: where the environment variable SPH_FRAMES_FILE names a file, begins a log of face-on
+  ! column-density maps (looking down z) over the node box lo .. hi -- the hosts pass the initial bounding box of the gas in x
+  ! and y -- on SPH_FRAMES_SIZE x SPH_FRAMES_SIZE nodes (default 256), a frame every SPH_FRAMES_DT of simulation time or,
+  ! without that variable, every SPH_FRAMES_EVERY-th step (default 10), and returns the name in path; on = .false. and no
+  ! call otherwise, so that a run without the variable is exactly the run it was.  The log holds max_rows frames, at most
+  ! 2^27 doubles (1 GB): later frames are dropped and counted in the file's header.  nodes: the image size chosen.
+  integer(c_int) function sph_frames_begin_env(ctx, lo, hi, max_rows, path, on, nodes) result(st)
+    type(c_ptr), intent(in) :: ctx
+    real(c_double), intent(in) :: lo(2), hi(2)
+    integer, intent(in) :: max_rows
+    character(len=*), intent(out) :: path
+    logical, intent(out) :: on
+    integer, intent(out) :: nodes                         ! the image is nodes x nodes (sph_frames_write wants it)
+    type(sph_frames_desc) :: d
+    character(len=64) :: word
+    integer :: stat, ios, n, every
+    real(c_double) :: dtf
+    st = SPH_OK
+    call get_environment_variable('SPH_FRAMES_FILE', path, status=stat)
+    on = stat == 0 .and. len_trim(path) > 0
+    if (stat == -1) st = 1_c_int
+    nodes = 0
+    if (.not. on) return
+    n = 256
+    every = 10
+    dtf = 0.0_c_double
+    call get_environment_variable('SPH_FRAMES_SIZE', word, status=stat)
+    if (stat == 0 .and. len_trim(word) > 0) then
+      read(word, *, iostat=ios) n
+      if (ios /= 0 .or. n < 1 .or. n > 8192) st = 1_c_int
+    end if
+    call get_environment_variable('SPH_FRAMES_EVERY', word, status=stat)
+    if (stat == 0 .and. len_trim(word) > 0) then
+      read(word, *, iostat=ios) every
+      if (ios /= 0 .or. every < 1) st = 1_c_int
+    end if
+    call get_environment_variable('SPH_FRAMES_DT', word, status=stat)
+    if (stat == 0 .and. len_trim(word) > 0) then
+      read(word, *, iostat=ios) dtf
+      if (ios /= 0 .or. .not. dtf > 0.0_c_double) st = 1_c_int
+      every = 0
+    end if
+    if (st /= SPH_OK) return
+    nodes = n
+    d%rot = [1.0_c_double, 0.0_c_double, 0.0_c_double, 0.0_c_double, 1.0_c_double, 0.0_c_double, 0.0_c_double, 0.0_c_double, &
+             1.0_c_double]
+    d%centre = 0.0_c_double
+    d%lo = lo
+    d%hi = hi
+    d%clip_lo = -huge(1.0_c_double)
+    d%clip_hi = huge(1.0_c_double)
+    d%h = 0.0_c_double
+    d%dt_frame = dtf
+    d%capacity = int(max(1, min(max_rows, 2**27 / (n * n))), c_int64_t)
+    d%n_u = int(n, c_int32_t)
+    d%n_v = int(n, c_int32_t)
+    d%every = int(every, c_int32_t)
+    d%centre_sink = -1_c_int32_t
+    d%nq = 0_c_int32_t
+    d%fields = 0_c_int32_t
+    d%reserved = 0_c_int64_t
+    st = sph_frames_begin(ctx, d)
+  end function sph_frames_begin_env
+
+  ! writes the frames recorded so far as one unformatted stream -- four int64 (rows, dropped, steps, n: the image is n x n,
+  ! one plane), then the heads (16 doubles per frame), then the planes (n n doubles per frame, [row][iu][iv] as C has
+  ! them) -- and ends the log
+  integer(c_int) function sph_frames_write(ctx, path, n) result(st)
+    type(c_ptr), intent(in) :: ctx
+    character(len=*), intent(in) :: path
+    integer, intent(in) :: n
+    integer(c_int64_t), target :: rows, dropped, steps
+    real(c_double), allocatable, target :: head(:, :), planes(:, :, :)
+    integer :: u
+    st = sph_frames_info(ctx, c_loc(rows), c_loc(dropped), c_loc(steps))
+    if (st /= SPH_OK) return
+    allocate(head(SPH_FRAMES_NHEAD, max(rows, 1_c_int64_t)), planes(n, n, max(rows, 1_c_int64_t)))
+    st = sph_frames_read(ctx, 0_c_int64_t, rows, c_loc(head), c_loc(planes))
+    if (st /= SPH_OK) return                             ! nothing is written and the log stays begun
+    open(newunit=u, file=trim(path), status='replace', action='write', access='stream', form='unformatted')
+    write(u) rows, dropped, steps, int(n, c_int64_t)
+    write(u) head(:, 1:rows)
+    write(u) planes(:, :, 1:rows)
+    close(u)
+    st = sph_frames_end(ctx)
+  end function sph_frames_write
 end module sph_hip_binding

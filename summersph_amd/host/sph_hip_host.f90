@@ -296,8 +296,9 @@ contains
     real(dp) :: end_time, next_save
     real(dp), allocatable :: dts(:)
     integer :: step, save_no, step_limit, dev, i
-    logical :: talk, do_saves, with_history, with_track
-    character(len=4096) :: history_file, track_file
+    logical :: talk, do_saves, with_history, with_track, with_frames
+    character(len=4096) :: history_file, track_file, frames_file
+    integer :: frames_size
 
     end_time = 1000.0_dp
     if (present(end_time_in)) end_time = end_time_in
@@ -325,6 +326,10 @@ contains
     call check(ctx, sph_history_begin_env(ctx, min(step_limit, 100000), size(sinks), history_file, with_history), 'sph_history_begin')
     ! optional trajectories (SPH_TRACK_FILE): every SPH_TRACK_STRIDE-th particle, one row per step, written when the run ends
     call check(ctx, sph_track_begin_env(ctx, size(bodies), min(step_limit, 100000) + 1, track_file, with_track), 'sph_track_begin')
+    ! optional movie (SPH_FRAMES_FILE): face-on column-density maps of the initial bounding box, recorded on the device every
+    ! SPH_FRAMES_DT of simulation time or every SPH_FRAMES_EVERY-th step, written when the run ends
+    call check(ctx, sph_frames_begin_env(ctx, [minval(bodies%position(1)), minval(bodies%position(2))], &
+      [maxval(bodies%position(1)), maxval(bodies%position(2))], min(step_limit, 100000), frames_file, with_frames, frames_size), 'sph_frames_begin')
 
     t = 0.0_c_double
     dt = 1.0e-2_c_double
@@ -368,6 +373,7 @@ contains
     end if
     if (with_history) call check(ctx, sph_history_write(ctx, history_file), 'sph_history_write')
     if (with_track) call check(ctx, sph_track_write(ctx, track_file), 'sph_track_write')
+    if (with_frames) call check(ctx, sph_frames_write(ctx, frames_file, frames_size), 'sph_frames_write')
     call check(ctx, sph_ctx_destroy(ctx), 'sph_ctx_destroy')
   end subroutine simulate
 
