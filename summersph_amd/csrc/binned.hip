@@ -36,7 +36,6 @@ namespace {
 
 constexpr int KB = 256;            // block of every kernel here
 constexpr int MAXQ = SPH_BINNED_MAX_Q;
-constexpr int MAX_ROWS = 16;
 constexpr int ALL_FLAGS = SPH_BINNED_LOG0 | SPH_BINNED_LOG1 | SPH_BINNED_EDGES0 | SPH_BINNED_EDGES1 | SPH_BINNED_SQUARES |
                           SPH_BINNED_SKIP_NAN;
 
@@ -230,8 +229,6 @@ void launch_pieces(bool sq, unsigned nblk, hipStream_t st, const double *rec, in
     else binned_pieces<MQ, false><<<dim3(nblk), dim3(KB), 0, st>>>(rec, n_q, vals, start, n_bins, n_pieces, part);
 }
 
-bool source_ok(int32_t id, int32_t n_rows) { return id >= 0 ? id < SPH_F_COUNT : -1 - (int64_t)id < n_rows; }
-
 // the checks that need no context and no table; null: fine
 const char *check_desc(const sph_binned_desc *d, const double *edges) {
     for (int k = 0; k < 3; k++)
@@ -326,13 +323,8 @@ int binned_run(sph_ctx *c, const sph_binned_desc *d, const double *values, const
 
     const int64_t n = c->n, n_slots = c->cap > 0 ? c->n_slots : 0;
     if (n_slots == 0 || n == 0) {                        // nothing held: zero sums
-        if (host) {
-            std::memset(sums, 0, (size_t)n_sums * sizeof(double));
-            if (counts) counts[0] = counts[1] = counts[2] = 0;
-        } else {
-            SPH_HIP(hipMemsetAsync(sums, 0, (size_t)n_sums * sizeof(double), st));
-            if (counts) SPH_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(int64_t), st));
-        }
+        SPH_HIP(zero_output(sums, (size_t)n_sums, host, st));
+        SPH_HIP(zero_output(counts, 3, host, st));
         return SPH_OK;
     }
 
@@ -369,10 +361,7 @@ int binned_run(sph_ctx *c, const sph_binned_desc *d, const double *values, const
     const double *d_values = host ? h_values : values;
     if (host) {
         SPH_TRY(analysis_pinned(c));
-        for (int k = 0; k < d->n_rows; k++)
-            if (rows_used >> k & 1u)
-                SPH_HIP(hipMemcpyAsync(h_values + (size_t)k * (size_t)n, values + (size_t)k * (size_t)n, (size_t)n * sizeof(double),
-                                       hipMemcpyHostToDevice, st));
+        SPH_HIP(upload_rows(h_values, values, d->n_rows, rows_used, (size_t)n, st));
     }
     SPH_HIP(hipMemcpyAsync(d_edge, edge, ne * sizeof(double), hipMemcpyHostToDevice, st));
     SPH_HIP(hipEventRecord(c->prf_evt, st));

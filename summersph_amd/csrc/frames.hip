@@ -78,8 +78,6 @@ struct Args {
     int32_t win;                               // the splat's LDS window: win x win nodes (0: none)
 };
 
-__device__ __forceinline__ bool finite(double a) { return fabs(a) <= 1.7976931348623157e308; }
-
 // t has reached the next threshold (product, then sum, in double)
 __device__ __forceinline__ bool threshold_passed(const Args &a) {
     return a.dt_frame > 0.0 && a.d_dt[1] >= a.ctl->t0 + (double)a.ctl->k * a.dt_frame;
@@ -112,7 +110,7 @@ __global__ __launch_bounds__(MB) void frames_maxima(Args a) {
         }
         v[NP] += 1.0;
     }
-    for (int o = 32; o > 0; o >>= 1) bad |= (uint32_t)__shfl_xor((int)bad, o, 64);
+    bad = wave_or(bad);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) s_bad[wv] = bad;
     __syncthreads();
@@ -138,7 +136,7 @@ __global__ __launch_bounds__(NMX * WAVE) void frames_head(Args a, int nb) {
             bad |= a.bad_part[b];
         }
     v = stat_wave<0, NP>(q, v);
-    for (int o = 32; o > 0; o >>= 1) bad |= (uint32_t)__shfl_xor((int)bad, o, 64);
+    bad = wave_or(bad);
     __syncthreads();                                       // every wave has read rows, k and t0
     if (lane != 0) return;
     if (q < NP) {
@@ -172,15 +170,6 @@ __global__ __launch_bounds__(NMX * WAVE) void frames_head(Args a, int nb) {
 __global__ __launch_bounds__(256) void frames_clear(const Ctl *__restrict__ ctl, unsigned long long *__restrict__ limbs, int64_t n) {
     if (!ctl->due) return;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) limbs[i] = 0ull;
-}
-
-// the 64-bit fixed-point t added into the 128-bit accumulator {*lo, *hi} that other lanes add to as well (LDS or global):
-// the low word with a returning add, the high word gets t's sign word plus the carry the returned value shows
-__device__ __forceinline__ void add_fixed_shared(unsigned long long *lo, unsigned long long *hi, unsigned long long tu,
-                                                 unsigned long long sign) {
-    const unsigned long long old = atomicAdd(lo, tu);
-    const unsigned long long up = sign + (unsigned long long)(old + tu < old);
-    if (up != 0ull) atomicAdd(hi, up);
 }
 
 // WIN: with the LDS window.  Dynamic LDS: 2 nplanes win^2 words
@@ -270,10 +259,10 @@ __global__ __launch_bounds__(SB) void frames_splat(Args a) {
                 const unsigned long long tu = (unsigned long long)f, sign = (unsigned long long)(f >> 63);
                 if (inside) {
                     unsigned long long *wl = s_win + (size_t)(2 * pl) * wsz + wu * W + wvv;
-                    add_fixed_shared(wl, wl + wsz, tu, sign);
+                    add_limbs_shared(wl, wl + wsz, tu, sign);
                 } else {
                     unsigned long long *gl = a.limbs + (size_t)(2 * pl) * pixels + node;
-                    add_fixed_shared(gl, gl + pixels, tu, sign);
+                    add_limbs_shared(gl, gl + pixels, tu, sign);
                 }
             }
         }
@@ -286,7 +275,7 @@ __global__ __launch_bounds__(SB) void frames_splat(Args a) {
                 const unsigned long long l = s_win[(size_t)(2 * pl) * wsz + rem], h = s_win[(size_t)(2 * pl + 1) * wsz + rem];
                 if ((l | h) == 0ull) continue;             // only nodes inside the image were added to
                 unsigned long long *gl = a.limbs + (size_t)(2 * pl) * pixels + ((int64_t)iu * nd.n[1] + iv);
-                add_fixed_shared(gl, gl + pixels, l, h);
+                add_limbs_shared(gl, gl + pixels, l, h);
             }
             __syncthreads();
         }

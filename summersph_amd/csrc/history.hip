@@ -58,8 +58,6 @@ struct Head {
     int32_t id, slot;                      // the densest particle (slot < 0: none)
 };
 
-__device__ __forceinline__ bool finite(double a) { return fabs(a) <= 1.7976931348623157e308; }
-
 // is the particle {r, id} denser than {rb, idb} (ties: the lower id)?  NaN is never denser
 __device__ __forceinline__ bool denser(double r, int32_t id, double rb, int32_t idb) { return r > rb || (r == rb && id < idb); }
 
@@ -104,8 +102,8 @@ __global__ __launch_bounds__(HB) void history_maxima(Fields f, int64_t n_slots, 
             if (denser(r, id, rb, idb)) { rb = r; idb = id; slotb = (int32_t)i; }
         }
     }
+    bad = wave_or(bad);
     for (int o = 32; o > 0; o >>= 1) {
-        bad |= (uint32_t)__shfl_xor((int)bad, o, 64);
         const double r = __shfl_xor(rb, o, 64);
         const int32_t id = __shfl_xor(idb, o, 64), sl = __shfl_xor(slotb, o, 64);
         if (denser(r, id, rb, idb)) { rb = r; idb = id; slotb = sl; }
@@ -145,7 +143,7 @@ __global__ __launch_bounds__(FW * WAVE) void history_head(const double *__restri
             if (b < nb) { v = fmax(v, part[b * NMX + k]); bad |= bad_part[b]; }
         }
         v = wave_max(v);
-        for (int o = 32; o > 0; o >>= 1) bad |= (uint32_t)__shfl_xor((int)bad, o, 64);
+        bad = wave_or(bad);
         if (lane != 0) return;
         if (k < NX) {
             head->exps[k] = (bad >> k & 1u) ? 0 : exp_above(fmax(v, 0.0));    // no gas: the maxima are 0

@@ -44,13 +44,9 @@ constexpr int SEL_BLOCKS = 1024;           // select blocks at most (grid-stride
 constexpr int MAX_M = SPH_MODES_MAX_M;
 constexpr int MAX_RINGS = SPH_MODES_MAX_RINGS;
 constexpr int MAX_P = SPH_MODES_MAX_P;
-constexpr int MAX_ROWS = 16;
-constexpr int HIST = 3072;                 // (ring, sum) accumulators of a block's LDS histogram (48 KB)
-constexpr int MAX_COPIES = 8;              // copies of a chunk's histogram in LDS at most, dealt by lane
 constexpr int RING_BLOCKS = 512;           // persistent blocks of modes_rings at most
 constexpr int SPIRAL_BLOCKS = 1024;        // ... of modes_spiral
 constexpr int TILE = 256;                  // records of modes_spiral's LDS tile (8 KB)
-constexpr size_t SLAB_BYTES = (size_t)64 << 20;   // each pass's slabs' budget
 constexpr int NST = 5;                     // statistics of modes_select: max |w|, then counts[4]
 
 struct Sel {
@@ -70,8 +66,6 @@ struct Info {
     int32_t exp;                           // e
     int32_t n_list;                        // records appended (modes_select); zeroed before the launch
 };
-
-__device__ __forceinline__ bool finite(double a) { return fabs(a) <= 1.7976931348623157e308; }
 
 // A wavefront's records take consecutive list entries through one integer atomic.  (One atomic per block and round brings
 // the kernel from 186 to 26 us at 10^6 particles, but the block's rendezvous costs scalar registers the kernel does not
@@ -179,9 +173,9 @@ __global__ __launch_bounds__(KB) void modes_rings(RingArgs a) {
     for (int k0 = 0; k0 < n_r; k0 += a.chunk) {
         const int k1 = min(n_r, k0 + a.chunk);
         const int acc = (k1 - k0) * na;                  // accumulators of one copy: acc copies <= HIST
-        unsigned long long *mine = hist + 2 * (threadIdx.x % a.copies) * acc;
+        unsigned long long *mine = hist_mine(hist, a.copies, acc);
         __syncthreads();                                 // the last chunk's flush is done
-        for (int k = threadIdx.x; k < 2 * acc * a.copies; k += KB) hist[k] = 0ull;
+        hist_zero(hist, a.copies, acc, KB);
         __syncthreads();
         for (int64_t j = (int64_t)blockIdx.x * KB + threadIdx.x; j < n; j += (int64_t)gridDim.x * KB) {
             const int k = a.rec.k[j];
@@ -199,13 +193,7 @@ __global__ __launch_bounds__(KB) void modes_rings(RingArgs a) {
             }
         }
         __syncthreads();
-        unsigned long long *out = a.slab + 2 * ((size_t)blockIdx.x * n_r + k0) * na;
-        for (int k = threadIdx.x; k < acc; k += KB) {    // the copies add up as 128-bit integers
-            unsigned long long lo = 0, up = 0;
-            for (int cp = 0; cp < a.copies; cp++) add_limbs(lo, up, hist[2 * (cp * acc + k)], hist[2 * (cp * acc + k) + 1]);
-            out[2 * k] = lo;
-            out[2 * k + 1] = up;
-        }
+        hist_flush(hist, a.copies, acc, KB, a.slab + 2 * ((size_t)blockIdx.x * n_r + k0) * na);
     }
 }
 
@@ -270,17 +258,16 @@ __global__ __launch_bounds__(KB) void modes_spiral(SpiralArgs a) {
     }
 }
 
-// the sum of the slabs' accumulators g, g in [0, n_acc): one wavefront per accumulator, lane l adds the slabs l, l + 64, ...,
-// then the butterfly.  na == 0: raw[g] (the spiral block).  na > 0: the ring slabs' layout, accumulator 0 of every na the
-// ring's count and the others the ring block's sums in order
+// the sum of the slabs' accumulators g, g in [0, n_acc): one wavefront per accumulator (slab_sum).  na == 0: raw[g] (the
+// spiral block).  na > 0: the ring slabs' layout, accumulator 0 of every na the ring's count and the others the ring block's
+// sums in order
 __global__ __launch_bounds__(KB) void modes_sum(const unsigned long long *__restrict__ slab, int nslab, int64_t n_acc, int na,
                                                 unsigned long long *__restrict__ raw, int64_t *__restrict__ ring_counts) {
     const int64_t g = (int64_t)blockIdx.x * (KB / WAVE) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (g >= n_acc) return;
-    unsigned long long lo = 0, hi = 0;
-    for (int b = lane; b < nslab; b += WAVE) add_limbs(lo, hi, slab[2 * ((size_t)b * n_acc + g)], slab[2 * ((size_t)b * n_acc + g) + 1]);
-    wave_add_limbs(lo, hi);
+    unsigned long long lo, hi;
+    slab_sum(slab, nslab, n_acc, g, lane, lo, hi);
     if (lane != 0) return;
     int64_t o = g;
     if (na > 0) {
@@ -307,8 +294,6 @@ __global__ __launch_bounds__(KB) void modes_convert(const unsigned long long *__
     if (g >= n_acc) return;
     sums[g] = limbs_to_double(raw[2 * g], raw[2 * g + 1], info->exp);
 }
-
-bool source_ok(int32_t id, int32_t n_rows) { return id >= 0 ? id < SPH_F_COUNT : -1 - (int64_t)id < n_rows; }
 
 int64_t n_acc_of(const sph_modes_desc *d) { return 2 * (int64_t)(d->m_max + 1) * ((int64_t)d->n_r + d->n_p); }
 
@@ -397,29 +382,19 @@ int modes_run(sph_ctx *c, const sph_modes_desc *d, const double *values, double 
 
     const int64_t n = c->n, n_slots = c->cap > 0 ? c->n_slots : 0;
     if (n_slots == 0 || n == 0) {                        // nothing held: zero sums, e = 0
-        if (host) {
-            std::memset(sums, 0, (size_t)n_acc * sizeof(double));
-            if (raw) std::memset(raw, 0, (size_t)n_acc * 2 * sizeof(uint64_t));
-            if (exp) exp[0] = 0;
-            if (ring_counts) std::memset(ring_counts, 0, (size_t)n_r * sizeof(int64_t));
-            if (counts) std::memset(counts, 0, 4 * sizeof(int64_t));
-        } else {
-            SPH_HIP(hipMemsetAsync(sums, 0, (size_t)n_acc * sizeof(double), st));
-            if (raw) SPH_HIP(hipMemsetAsync(raw, 0, (size_t)n_acc * 2 * sizeof(uint64_t), st));
-            if (exp) SPH_HIP(hipMemsetAsync(exp, 0, sizeof(int32_t), st));
-            if (ring_counts) SPH_HIP(hipMemsetAsync(ring_counts, 0, (size_t)n_r * sizeof(int64_t), st));
-            if (counts) SPH_HIP(hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), st));
-        }
+        SPH_HIP(zero_output(sums, (size_t)n_acc, host, st));
+        SPH_HIP(zero_output(raw, (size_t)n_acc * 2, host, st));
+        SPH_HIP(zero_output(exp, 1, host, st));
+        SPH_HIP(zero_output(ring_counts, (size_t)n_r, host, st));
+        SPH_HIP(zero_output(counts, 4, host, st));
         return SPH_OK;
     }
 
     // modes_rings: the histogram's chunking and the slabs
     const int na = 2 * m1 + 1;
     const int64_t n_acc_r = (int64_t)n_r * na;
-    const int chunk = std::min(n_r, HIST / na);
-    const int copies = std::max(1, std::min(MAX_COPIES, HIST / (chunk * na)));
-    const int nblk_r = (int)std::max<int64_t>(
-        1, std::min<int64_t>({(int64_t)RING_BLOCKS, (int64_t)(SLAB_BYTES / ((size_t)n_acc_r * 16)), (n_slots + KB - 1) / KB}));
+    const HistPlan hp = hist_plan<2 * (MAX_M + 1) + 1>(n_r, na, std::min<int64_t>(RING_BLOCKS, (n_slots + KB - 1) / KB));
+    const int nblk_r = hp.nslab;
     // modes_spiral: ng wavefronts cover the p table, the other wavefronts of a block share a tile's records
     const int ng = n_p > 0 ? (n_p + WAVE - 1) / WAVE : 1;
     const int nsub = std::max(1, (KB / WAVE) / ng);
@@ -488,7 +463,7 @@ int modes_run(sph_ctx *c, const sph_modes_desc *d, const double *values, double 
 
     modes_select<<<dim3((unsigned)nb), dim3(KB), 0, st>>>(c->orig, n_slots, c->n_owned, f, s, rec, info, part);
     modes_head<<<dim3(1), dim3(WAVE), 0, st>>>(part, nb, info);
-    RingArgs ra{rec, info, slab_ring, n_r, d->m_max, chunk, copies};
+    RingArgs ra{rec, info, slab_ring, n_r, d->m_max, hp.chunk, hp.copies};
     modes_rings<<<dim3((unsigned)nblk_r), dim3(KB), 0, st>>>(ra);
     modes_sum<<<dim3(blocks(n_acc_r, KB / WAVE)), dim3(KB), 0, st>>>(slab_ring, nblk_r, n_acc_r, na, d_raw, d_rc);
     SPH_HIP(hipGetLastError());
@@ -521,7 +496,7 @@ int modes_run(sph_ctx *c, const sph_modes_desc *d, const double *values, double 
     SPH_HIP(hipStreamSynchronize(st));
     Info hi;
     std::memcpy(&hi, h.data() + (size_t)n_acc * 2 + (size_t)n_r, sizeof(Info));
-    for (int64_t g = 0; g < n_acc; g++) sums[g] = finish_one(h[2 * g], h[2 * g + 1], hi.exp);
+    finish_all(h.data(), n_acc, &hi.exp, 1, sums);
     if (raw) std::memcpy(raw, h.data(), (size_t)n_acc * 2 * sizeof(uint64_t));
     if (exp) exp[0] = hi.exp;
     if (ring_counts) std::memcpy(ring_counts, h.data() + (size_t)n_acc * 2, (size_t)n_r * sizeof(int64_t));
@@ -548,7 +523,6 @@ extern "C" int sph_modes_finish(const sph_modes_desc *d, const int32_t *exp, con
     using namespace sph;
     if (!d || !exp || !raw || !sums) return SPH_ERR_ARG;
     if (d->n_r < 1 || d->n_r > MAX_RINGS || d->m_max < 0 || d->m_max > MAX_M || d->n_p < 0 || d->n_p > MAX_P) return SPH_ERR_ARG;
-    const int64_t n_acc = n_acc_of(d);
-    for (int64_t g = 0; g < n_acc; g++) sums[g] = finish_one(raw[2 * g], raw[2 * g + 1], exp[0]);
+    finish_all(raw, n_acc_of(d), exp, 1, sums);
     return SPH_OK;
 }

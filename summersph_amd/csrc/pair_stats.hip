@@ -47,14 +47,10 @@ constexpr int KB = 256;                    // block of every kernel here
 constexpr int BOX_BLOCKS = 1024;           // select blocks at most (grid-stride beyond)
 constexpr int MAXQ = SPH_PAIRS_MAX_Q;
 constexpr int MAXS = 2 + 2 * MAXQ + 4;     // sums per bin at most
-constexpr int MAX_ROWS = 16;
 constexpr int MAX_BINS = SPH_PAIRS_MAX_BINS;
 constexpr int RS = 12;                     // doubles per sorted record: x y z vx vy vz w A0 A1 A2 A3 h
 constexpr int GL = 8;                      // lanes per target
-constexpr int HIST = 3072;                 // (bin, sum) accumulators of a block's LDS histogram (48 KB)
-constexpr int MAX_COPIES = 8;              // copies of a chunk's histogram in LDS at most, dealt by lane: fewer same-address adds
 constexpr int BIN_BLOCKS = 512;            // persistent blocks of pairs_bin at most
-constexpr size_t SLAB_BYTES = (size_t)64 << 20;   // the slabs' budget
 constexpr int NST = 16;                    // statistics of pairs_select: 3 minima, 10 maxima, 3 counts
 constexpr int ALL_FLAGS = SPH_PAIRS_LOG | SPH_PAIRS_EDGES | SPH_PAIRS_SCALE_H | SPH_PAIRS_VELOCITY;
 
@@ -73,8 +69,6 @@ struct Info {
     int32_t exps[MAXS + 2];                // e_s per sum (exps[0] = 62: N is a plain count)
     int32_t n_list, pad;                   // targets appended so far (pairs_gather)
 };
-
-__device__ __forceinline__ bool finite(double a) { return fabs(a) <= 1.7976931348623157e308; }
 
 // class of every slot (0 none, 1 source, 3 source and target), its weight, the per-block partials
 __global__ __launch_bounds__(KB) void pairs_select(const int32_t *__restrict__ orig, int64_t n_slots, int64_t n_owned, Spec s,
@@ -255,9 +249,9 @@ __global__ __launch_bounds__(KB) void pairs_bin(BinArgs a) {
     for (int b0 = 0; b0 < n_bins; b0 += a.chunk) {
         const int b1 = min(n_bins, b0 + a.chunk);
         const int acc = (b1 - b0) * nsum;                // accumulators of one copy
-        unsigned long long *mine = hist + 2 * (threadIdx.x % a.copies) * acc;
+        unsigned long long *mine = hist_mine(hist, a.copies, acc);
         __syncthreads();                                 // the edges are in; the last chunk's flush is done
-        for (int k = threadIdx.x; k < 2 * acc * a.copies; k += KB) hist[k] = 0ull;
+        hist_zero(hist, a.copies, acc, KB);
         __syncthreads();
         const double e_lo = edge[b0], e_hi = edge[b1];
         for (int64_t t = g0; t < n_tgt; t += groups) {
@@ -323,38 +317,18 @@ __global__ __launch_bounds__(KB) void pairs_bin(BinArgs a) {
             }
         }
         __syncthreads();
-        unsigned long long *out = a.slab + 2 * ((size_t)blockIdx.x * n_bins + b0) * nsum;
-        for (int k = threadIdx.x; k < acc; k += KB) {    // the copies add up as 128-bit integers
-            unsigned long long lo = 0, up = 0;
-            for (int c = 0; c < a.copies; c++) {
-                const unsigned long long l = hist[2 * (c * acc + k)];
-                lo += l;
-                up += hist[2 * (c * acc + k) + 1] + (lo < l);
-            }
-            out[2 * k] = lo;
-            out[2 * k + 1] = up;
-        }
+        hist_flush(hist, a.copies, acc, KB, a.slab + 2 * ((size_t)blockIdx.x * n_bins + b0) * nsum);
     }
 }
 
-// raw[g] = the sum of the slabs' accumulators g, g in [0, n_bins nsum): one wavefront per accumulator, lane l adds the slabs
-// l, l + 64, ..., then a butterfly of 128-bit additions
+// raw[g] = the sum of the slabs' accumulators g, g in [0, n_bins nsum): one wavefront per accumulator (slab_sum)
 __global__ __launch_bounds__(KB) void pairs_sum(const unsigned long long *__restrict__ slab, int nblk, int64_t n_acc,
                                                 unsigned long long *__restrict__ raw) {
     const int64_t g = (int64_t)blockIdx.x * (KB / WAVE) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (g >= n_acc) return;
-    unsigned long long lo = 0, hi = 0;
-    for (int b = lane; b < nblk; b += WAVE) {
-        const unsigned long long l = slab[2 * ((size_t)b * n_acc + g)], h = slab[2 * ((size_t)b * n_acc + g) + 1];
-        lo += l;
-        hi += h + (lo < l);
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long l = __shfl_xor(lo, o, 64), h = __shfl_xor(hi, o, 64);
-        lo += l;
-        hi += h + (lo < l);
-    }
+    unsigned long long lo, hi;
+    slab_sum(slab, nblk, n_acc, g, lane, lo, hi);
     if (lane != 0) return;
     raw[2 * g] = lo;
     raw[2 * g + 1] = hi;
@@ -367,8 +341,6 @@ __global__ __launch_bounds__(KB) void pairs_convert(const unsigned long long *__
     if (g >= n_acc) return;
     sums[g] = limbs_to_double(raw[2 * g], raw[2 * g + 1], info->exps[g % nsum]);
 }
-
-bool source_ok(int32_t id, int32_t n_rows) { return id >= 0 ? id < SPH_F_COUNT : -1 - (int64_t)id < n_rows; }
 
 int nsum_of(const sph_pairs_desc *d) { return 2 + 2 * d->n_q + ((d->flags & SPH_PAIRS_VELOCITY) ? 4 : 0); }
 
@@ -456,26 +428,17 @@ int pairs_run(sph_ctx *c, const sph_pairs_desc *d, const double *values, const d
 
     const int64_t n = c->n, n_slots = c->cap > 0 ? c->n_slots : 0;
     if (n_slots == 0 || n == 0) {                        // nothing held: zero sums
-        if (host) {
-            std::memset(sums, 0, (size_t)n_acc * sizeof(double));
-            if (raw) std::memset(raw, 0, (size_t)n_acc * 2 * sizeof(uint64_t));
-            if (exps) { std::memset(exps, 0, (size_t)nsum * sizeof(int32_t)); exps[0] = 62; }
-            if (counts) counts[0] = counts[1] = counts[2] = 0;
-        } else {
-            SPH_HIP(hipMemsetAsync(sums, 0, (size_t)n_acc * sizeof(double), st));
-            if (raw) SPH_HIP(hipMemsetAsync(raw, 0, (size_t)n_acc * 2 * sizeof(uint64_t), st));
-            if (exps) {
-                SPH_HIP(hipMemsetAsync(exps, 0, (size_t)nsum * sizeof(int32_t), st));
-                SPH_HIP(hipMemsetAsync(exps, 62, 1, st));          // little endian: the int32 62
-            }
-            if (counts) SPH_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(int64_t), st));
-        }
+        SPH_HIP(zero_output(sums, (size_t)n_acc, host, st));
+        SPH_HIP(zero_output(raw, (size_t)n_acc * 2, host, st));
+        SPH_HIP(zero_output(exps, (size_t)nsum, host, st));
+        SPH_HIP(zero_output(counts, 3, host, st));
+        if (exps && host) exps[0] = 62;
+        else if (exps) SPH_HIP(hipMemsetAsync(exps, 62, 1, st));            // little endian: the int32 62
         return SPH_OK;
     }
 
-    const int chunk = std::min(n_bins, HIST / nsum);
-    const int copies = std::max(1, std::min(MAX_COPIES, HIST / (chunk * nsum)));
-    const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(BIN_BLOCKS, (int64_t)(SLAB_BYTES / ((size_t)n_acc * 16))));
+    const HistPlan hp = hist_plan<MAXS>(n_bins, nsum, BIN_BLOCKS);
+    const int nblk = hp.nslab;
     const int nb = (int)std::min<int64_t>((n_slots + KB - 1) / KB, BOX_BLOCKS);
     int64_t tl = 1;
     while (tl < 2 * n_slots) tl <<= 1;                   // hash table: load <= 1/2
@@ -518,10 +481,7 @@ int pairs_run(sph_ctx *c, const sph_pairs_desc *d, const double *values, const d
     const double *d_values = host ? h_values : values;
     if (host) {
         SPH_TRY(analysis_pinned(c));
-        for (int k = 0; k < d->n_rows; k++)
-            if (rows_used >> k & 1u)
-                SPH_HIP(hipMemcpyAsync(h_values + (size_t)k * (size_t)n, values + (size_t)k * (size_t)n, (size_t)n * sizeof(double),
-                                       hipMemcpyHostToDevice, st));
+        SPH_HIP(upload_rows(h_values, values, d->n_rows, rows_used, (size_t)n, st));
     }
     SPH_HIP(hipMemcpyAsync(d_edge, edge, ne * sizeof(double), hipMemcpyHostToDevice, st));
     SPH_HIP(hipEventRecord(c->prf_evt, st));
@@ -555,7 +515,7 @@ int pairs_run(sph_ctx *c, const sph_pairs_desc *d, const double *values, const d
     pairs_gather<<<dim3(blocks(n_slots, KB)), dim3(KB), 0, st>>>(c->orig, cls, s, keys_alt, vals_alt, info, n_slots, rec, tlist, tab,
                                                                  (uint64_t)(tl - 1));
     pairs_tails<<<dim3(blocks(n_slots, KB)), dim3(KB), 0, st>>>(keys_alt, info, n_slots, tab, (uint64_t)(tl - 1));
-    BinArgs a{rec, keys_alt, tlist, info, tab, d_edge, slab, (uint64_t)(tl - 1), n_bins, nq, nsum, scale_h ? 1 : 0, chunk, copies};
+    BinArgs a{rec, keys_alt, tlist, info, tab, d_edge, slab, (uint64_t)(tl - 1), n_bins, nq, nsum, scale_h ? 1 : 0, hp.chunk, hp.copies};
     if (velocity) { if (nq) launch_bin<true, true>(nblk, st, a); else launch_bin<true, false>(nblk, st, a); }
     else { if (nq) launch_bin<false, true>(nblk, st, a); else launch_bin<false, false>(nblk, st, a); }
     pairs_sum<<<dim3(blocks(n_acc, KB / WAVE)), dim3(KB), 0, st>>>(slab, nblk, n_acc, d_raw);
@@ -573,7 +533,7 @@ int pairs_run(sph_ctx *c, const sph_pairs_desc *d, const double *values, const d
     SPH_HIP(hipMemcpyAsync(h_info, info, sizeof(Info), hipMemcpyDeviceToHost, st));
     SPH_HIP(hipMemcpyAsync(h_raw.data(), d_raw, h_raw.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     SPH_HIP(hipStreamSynchronize(st));
-    for (int64_t g = 0; g < n_acc; g++) sums[g] = finish_one(h_raw[2 * g], h_raw[2 * g + 1], h_info->exps[g % nsum]);
+    finish_all(h_raw.data(), n_acc, h_info->exps, nsum, sums);
     if (raw) std::memcpy(raw, h_raw.data(), h_raw.size() * sizeof(uint64_t));
     if (exps) std::memcpy(exps, h_info->exps, (size_t)nsum * sizeof(int32_t));
     if (counts) { counts[0] = h_info->n_tgt; counts[1] = h_info->n_src; counts[2] = h_info->n_bad; }
@@ -597,6 +557,6 @@ extern "C" int sph_pairs_finish(const sph_pairs_desc *d, const int32_t *exps, co
     if (!d || !exps || !raw || !sums) return SPH_ERR_ARG;
     if (d->n_bins < 1 || d->n_bins > MAX_BINS || d->n_q < 0 || d->n_q > MAXQ || (d->flags & ~ALL_FLAGS)) return SPH_ERR_ARG;
     const int nsum = nsum_of(d);
-    for (int64_t g = 0; g < (int64_t)d->n_bins * nsum; g++) sums[g] = finish_one(raw[2 * g], raw[2 * g + 1], exps[g % nsum]);
+    finish_all(raw, (int64_t)d->n_bins * nsum, exps, nsum, sums);
     return SPH_OK;
 }

@@ -21,6 +21,10 @@ __device__ __forceinline__ double wave_max(double v) {
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
     return v;
 }
+__device__ __forceinline__ uint32_t wave_or(uint32_t bad) {
+    for (int o = 32; o > 0; o >>= 1) bad |= (uint32_t)__shfl_xor((int)bad, o, 64);
+    return bad;
+}
 
 // The image passes' selection statistics (render.hip, cube.hip, transfer.hip): N values of which the first NMIN are
 // minima, the next NMAX maxima and the rest counts (sums of small integers).  All three are exact in any order, so the

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -461,6 +462,25 @@ inline int table_staging(sph_ctx *c, size_t count, double **out) {
     }
     *out = c->prf_edge;
     return SPH_OK;
+}
+// What sph_binned, sph_pairs and sph_modes share around the caller's values block: n_rows <= MAX_ROWS rows of c->n doubles by
+// original id.  A source is an SPH_F_* id (>= 0) or -1 - row.
+constexpr int MAX_ROWS = 16;
+inline bool source_ok(int32_t id, int32_t n_rows) { return id >= 0 ? id < SPH_F_COUNT : -1 - (int64_t)id < n_rows; }
+// the host forms' device copies of the rows that rows_used names (bit k: row k), in the stream's order
+inline hipError_t upload_rows(double *dst, const double *src, int n_rows, uint32_t rows_used, size_t n, hipStream_t st) {
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < n_rows && e == hipSuccess; k++)
+        if (rows_used >> k & 1u) e = hipMemcpyAsync(dst + k * n, src + k * n, n * sizeof(double), hipMemcpyHostToDevice, st);
+    return e;
+}
+// zeroes n elements of an output: host memory (host form) or device memory in the stream's order; null: nothing to do
+template <class T>
+inline hipError_t zero_output(T *p, size_t n, bool host, hipStream_t st) {
+    if (!p) return hipSuccess;
+    if (!host) return hipMemsetAsync(p, 0, n * sizeof(T), st);
+    std::memset(p, 0, n * sizeof(T));
+    return hipSuccess;
 }
 // disc profiles (profile.hip): host form (sums and / or table host memory, one read-back) or device form (sums only)
 int profile_sums(sph_ctx *c, sph_profile_desc *d, double *sums, double *table, int64_t n_bins, bool host);
