@@ -331,7 +331,8 @@ int put_dt(sph_ctx *c, double dt, double t) {
 // The fixed-h build path reads its reports (longest list, non-finite positions) one build late so that the steady state never
 // waits for the host.  Every entry point that synchronises anyway and hands results to the caller calls this afterwards: the
 // reports of the LAST build have arrived by then, so a list that overflowed in the final build of a run (or in the only build
-// after an upload) is an error here, never a silently truncated result.  Requires the stream to be idle.
+// after an upload) is an error here, never a silently truncated result.  The same for a tile need that reached 65536 in that
+// build (rep[3]): its entries were truncated to 16 bits.  Requires the stream to be idle.
 int drain_reports(sph_ctx *c) {
     if (c->ring_nl_valid) {
         const int32_t *rep = c->pin->nl[1 - c->ring_nl].v;

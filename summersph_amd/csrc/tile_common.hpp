@@ -19,7 +19,9 @@ namespace sph {
 constexpr int LIST16_MAX_NEED = 65536;
 constexpr double SENTINEL_POS = 1.0e30;       // coordinates of the sentinel record of the whole-tile kernels (tiled.hip): q is astronomically > 2
 __device__ __host__ __forceinline__ int ent_pos(int k) { return ((k & 3) << 1) | ((k >> 2) & 1); }
-// halfword p (compile-time in the unrolled loops) of a row
+// halfword p (compile-time in the unrolled loops) of a row.  NOT CALLED by any kernel at present (the kernels decode through
+// ListColumn below, half_entry of density_wt and ent_of of forces_q, tiled.hip): no test can reach it, the entries with
+// bit 15 set of tests/test_list16_edges_gpu.py included.  The decode is unsigned, like theirs.
 __device__ __forceinline__ int row_entry(const int4 &q, int p) {
     const unsigned wd = (unsigned)((p >> 1) == 0 ? q.x : ((p >> 1) == 1 ? q.y : ((p >> 1) == 2 ? q.z : q.w)));
     return (int)((p & 1) ? (wd >> 16) : (wd & 0xffffu));

@@ -550,6 +550,8 @@ __global__ __launch_bounds__(BS) void forces_q(PairConst pc, int32_t tcap, int32
         }
         PH_MARK(5);      // own record out of the tile
         ForceSums f;
+        // (entries at or above 32768 reach this decode in tests/test_list16_edges_gpu.py with LPT == 4 only: the LPT == 8 shift,
+        // (sub >> 2) << 4, has not seen one in any test -- no set there puts such a knot into a sheet that runs half groups)
         auto ent_of = [&](uint32_t wd, int hf) { return (int)((wd >> ((LPT == 4 ? hf : (sub >> 2)) << 4)) & 0xffffu); };
         if (ntrip > 0) {
             // entries are slots of the 256-group's tile (LPT = 4: this tile) or, plus a constant per interval, of this half group's
@@ -740,6 +742,7 @@ int32_t tile_cap_q(int nq, bool tablds = true) {
 }  // namespace
 
 // a context whose groups outgrow the 16-bit entries leaves the tiled path for good: the untiled 32-bit list of pairs.hip
+// (for good: c->tiled is set at sph_create only, a later sph_upload of a small set stays untiled)
 static int leave_tiled_path(sph_ctx *c) {
     c->tiled = false; c->whole_tile = false; c->packed_list = false;
     c->wt_ok = c->wt_ok_f = false; c->wt_fit_pct = c->wt_fit_pct_f = -1;
@@ -793,7 +796,9 @@ int nlist_build_tiled(sph_ctx *c) {
     // Steady state: the report of the PREVIOUS build (it arrived long ago) is read instead of waiting for this one's.  The
     // list keeps a third of headroom, so a list that overflows within one step (which the dt control all but excludes) is
     // an error reported one build late, not a silent truncation.  The same for the 16-bit entries: the context leaves the
-    // tiled path when a group's intervals reach HALF of what an entry can address.
+    // tiled path when a group's intervals reach HALF of what an entry can address.  So entries with bit 15 set are written
+    // by one build only -- the one whose need has grown into [32768, 65535] -- and decoded in that step alone.  The four
+    // branches (the two guards, the error below, drain_reports' term) and that step are pinned by tests/test_list16_edges_gpu.py.
     const bool trusted = c->ring_nl_valid && !c->no_stale;
     const int p = c->ring_nl;
     int32_t *slot = c->pin->nl[p].v;

@@ -85,27 +85,41 @@ def _alpha_rows(out, dal, dal_scale, rho, alpha, c, h):
     out.scale[AL_DECAY] = np.abs(out.rows[AL_DECAY])
 
 
-def fixed_terms(gas, sinks, h=H_FIXED, nq=5000):
-    """the sixteen rows of a fixed-h evaluation.  Also leaves rho, P, c (the oracle's) on the result."""
+def fixed_terms(gas, sinks, h=H_FIXED, nq=5000, targets=None):
+    """the sixteen rows of a fixed-h evaluation.  Also leaves rho, P, c (the oracle's) on the result.
+    targets: an index array -- the rows, scales and list_len of these particles only (the others stay 0): O(len(targets) n),
+    for the sets too large for the whole matrix.  With targets, n_pairs, n_coincident, n_approaching and n_receding are NOT
+    counts of the set: they count the ordered pairs (i, j) with i a target, halved like the full counts -- use them with the
+    whole set only.
+    Cost: the distances are formed in blocks of 16e6 elements; len(targets) n (n^2 without targets) may be 1.28e8 at the most,
+    which is n = 11300 for a full restatement."""
     from oracle import orc
     o = orc.Oracle(gas, sinks, h=h, nq=nq, nthreads=orc.max_threads())
     n = o.n
-    assert n <= 4000, "O(n^2) restatement"
+    rows = np.arange(n) if targets is None else np.asarray(targets, dtype=np.int64)
+    assert rows.size * n <= 4000 * 4000 * 8, "O(len(targets) n) restatement: at most 1.28e8 target-particle pairs"
     o.density()
     out = TermRef(n)
     out.rho, out.P, out.c = o.rho.copy(), o.P.copy(), o.c.copy()
     pos = np.stack([o.x, o.y, o.z], axis=1)
     vel = np.stack([o.vx, o.vy, o.vz], axis=1)
-    d = pos[:, None, :] - pos[None, :, :]
-    r = np.sqrt(d[:, :, 0] * d[:, :, 0] + d[:, :, 1] * d[:, :, 1] + d[:, :, 2] * d[:, :, 2])       # [F]:356-357
-    del d
-    I, J = np.nonzero((r > 0.0) & (r <= 2.0 * h))
+    I, J, dr, zero = [], [], [], 0
+    for a in range(0, rows.size, 4000):                 # (the whole matrix of a set of <= 4000 in one block, as before)
+        blk = rows[a:a + 4000]
+        step = max(1, 16_000_000 // n)
+        for b in range(0, blk.size, step):
+            d = pos[blk[b:b + step], None, :] - pos[None, :, :]
+            r = np.sqrt(d[:, :, 0] * d[:, :, 0] + d[:, :, 1] * d[:, :, 1] + d[:, :, 2] * d[:, :, 2])       # [F]:356-357
+            del d
+            i, j = np.nonzero((r > 0.0) & (r <= 2.0 * h))
+            dr.append(r[i, j]); I.append(blk[b:b + step][i]); J.append(j)
+            zero += int(np.count_nonzero(r == 0.0))
+            del r
+    I, J, dr = np.concatenate(I), np.concatenate(J), np.concatenate(dr)
     out.n_pairs = I.size // 2
     out.list_len = np.bincount(I, minlength=n)
-    out.n_coincident = (int(np.count_nonzero(r == 0.0)) - n) // 2
+    out.n_coincident = (zero - rows.size) // 2
     nv = pos[I] - pos[J]
-    dr = r[I, J]
-    del r
     v = vel[I] - vel[J]                                                            # [F]:358
     vdotr = v[:, 0] * nv[:, 0] + v[:, 1] * nv[:, 1] + v[:, 2] * nv[:, 2]
     out.n_approaching = int(np.count_nonzero(vdotr < 0.0)) // 2

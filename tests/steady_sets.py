@@ -17,6 +17,12 @@ dt values handed to ctx.step one by one (the dt a step returns is compared, not 
   sheet_puffing_up          (8000 particles) a thin sheet whose vertical velocity dispersion thickens it until the forces
                             tiles no longer fit
   clumps_together           8 such clumps that start 6600 apart (2^31 cells: hashed and sticky), fly inward, meet and pass
+and, for the 16-bit entries of the tiled list at their limits (tests/test_list16_edges_gpu.py; 33000 to 754000 particles with
+thousands of neighbours each: the references are the cell-binned pair count, the threaded oracle and the restatement on sampled targets):
+  dense_cube_32767 / _32768 a static cube of exactly 3 x 3 x 3 cells, one tile: the largest tile need is n
+  dense_cube_window         36000 in 4 x 4 x 4 cells, contracting: the need grows into [32768, 65535] for exactly one build
+  sheet_with_knot           such a knot inside a sheet of 700000 whose groups fit their tiles: the whole-tile kernels run
+  rows_aligned_*            three blobs that move into the same cell rows in one step: the need passes 65536 while no list grows
 
 What makes each set adversarial is asserted, from the CPU oracle's trajectory, in tests/test_steady_sets_cpu.py."""
 from __future__ import annotations
@@ -144,6 +150,115 @@ def sheet_puffing_up():
     return dict(gas=_gas(rng, pos, bulk, 0.2), dts=[0.07] * 8, run=None, clump=None)
 
 
+# ---- the 16-bit list entries at their limits (tests/test_list16_edges_gpu.py) -----------------------------------------------------
+# A tiled list entry is the neighbour's slot among the records of its group's three candidate intervals: the group's tile
+# NEED (tile_fit_replay(...)["need"]).  The context leaves the tiled path when a need reaches HALF of 65536, on a report that
+# is one build old in the steady state; so entries with bit 15 set exist only in the one build whose need has grown into
+# [32768, 65535], and a need that reaches 65536 within one step is an error.  These sets hold tens of thousands of particles with
+# thousands of neighbours each -- a cube of 3 x 3 x 3 cells is ONE tile: max need = n.
+LIST16_HALF, LIST16_FULL = 32768, 65536
+
+
+def _cube(rng, n, side):
+    return rng.uniform(-0.5 * side, 0.5 * side, (n, 3))
+
+
+DENSE_CUBE = dict(side=2.9 * EDGE, seed=60, sigma=0.05)
+
+
+def dense_cube(n):
+    """static (no schedule): n uniform points in a cube of 2.9 cell edges -- exactly 3 cells per axis, a tenth of an edge
+    of slack to the fourth -- so that the group which holds a particle of the central cell needs all n records: max need =
+    n, an integer count that no rounding moves.  n = 32767 is the last value a first build keeps tiled, 32768 the first
+    it leaves with."""
+    c = DENSE_CUBE
+    rng = np.random.default_rng(c["seed"])
+    pos = _cube(rng, n, c["side"])
+    return dict(gas=_gas(rng, pos, np.zeros((n, 3)), c["sigma"]), dts=[], run=None, clump=None)
+
+
+WINDOW = dict(n=36000, side=3.30 * EDGE, seed=61, sigma=0.05, k=0.5, shrink=0.95, steps=4)
+
+
+def _window_cube():
+    c = WINDOW
+    rng = np.random.default_rng(c["seed"])
+    pos = _cube(rng, c["n"], c["side"])
+    return rng, pos, -c["k"] * pos
+
+
+def dense_cube_window():
+    """36000 points in a cube of 4 x 4 x 4 cells with the homologous inflow v = -k x of `contraction`, every step (dt = 0.1)
+    shrinking it to 0.95 of its size (the lists grow by 1 / 0.95^3 = 1.17 per step, 1.16 to 1.19 on the oracle's
+    trajectory): the largest tile need starts below 32768, is
+    still below it at build 1, lies inside [32768, 65535] at build 2 -- the only build that writes entries with bit 15 set,
+    and the step that decodes them -- and build 3 learns it from the stale report and leaves the tiled path."""
+    c = WINDOW
+    rng, pos, bulk = _window_cube()
+    dt = (1.0 - c["shrink"]) / c["k"]
+    return dict(gas=_gas(rng, pos, bulk, c["sigma"]), dts=[dt] * c["steps"], run=None, clump=None)
+
+
+KNOT = dict(sheet=700000, side=530.0, sigma_z=0.3, knot=54000, xy=3.37 * EDGE, z=8.55 * EDGE, seed=63, sigma=0.05, k=0.5, shrink=0.95,
+            steps=3)
+
+
+def sheet_with_knot():
+    """the only way to bring entries at or above 32768 into the whole-tile kernels: a thin sheet (700000 particles on 530 x
+    530, 62 per cell column: the tiles of its groups fit, so density_wt and forces_q run) with a dense knot at its centre
+    -- 54000 particles in a box of 3.4 x 3.4 x 8.55 cell edges, tall so that its lists stay at a few thousand, contracting
+    like dense_cube_window.  z keeps the fewest cells and is the fastest axis of the cell key, so a group of the knot needs
+    the columns around its own over the knot's whole height: its need grows through 32768 as the knot shrinks from four
+    columns a side towards three.  The knot's groups misfit and take the fall-back loops of the two kernels; they are fewer
+    than one group in ten of either geometry (the 1024-target density groups, the 256-target forces groups)."""
+    c = KNOT
+    rng = np.random.default_rng(c["seed"])
+    ns, nk = c["sheet"], c["knot"]
+    sheet = np.stack([rng.uniform(-0.5 * c["side"], 0.5 * c["side"], ns), rng.uniform(-0.5 * c["side"], 0.5 * c["side"], ns),
+                      rng.normal(0.0, c["sigma_z"], ns)], axis=1)
+    knot = rng.uniform(-0.5, 0.5, (nk, 3)) * np.array([c["xy"], c["xy"], c["z"]])
+    pos = np.concatenate([sheet, knot])
+    bulk = np.concatenate([np.zeros((ns, 3)), -c["k"] * knot])
+    dt = (1.0 - c["shrink"]) / c["k"]
+    return dict(gas=_gas(rng, pos, bulk, c["sigma"]), dts=[dt] * c["steps"], run=None,
+                clump=np.concatenate([np.zeros(ns, dtype=np.int64), np.ones(nk, dtype=np.int64)]))
+
+
+ROWS = dict(per=28000, blobs=3, side=2.8 * EDGE, seed=62, sigma=0.05, dt=0.1)
+N_MARKERS = 2
+
+
+def rows_aligned(where):
+    """three dense blobs (cubes of 2.8 edges: 3 x 3 x 3 cells each, need = 28000 + the odd marker) side by side along x -- 1.2
+    edges of empty space between them, more than 2 h, before and after -- that start four cell rows apart in y and move rigidly,
+    in ONE step, into the same rows.  Two markers pin the box's corners and stretch y and z to more cells than x, so that x
+    stays the fastest axis of the cell key: a row of cells then runs through all three blobs, and a group's middle
+    intervals -- from its first candidate row to its last -- span them all.  No list grows (no pair of different blobs
+    comes within 2 h), but the largest need goes from below 32768 to above 65536 within one build.
+    What the kernels of that step do with the truncated entries: an entry is e mod 65536 < 65536 <= need, and EntryMap adds
+    the offset of the interval that e mod 65536 falls into, so every decoded index is a record of the group's own three intervals --
+    a WRONG neighbour, never an address outside the arrays.  The sums of that step are wrong and must be refused.
+    where = "mid": two more (short) steps follow within the same call; "last": none."""
+    c = ROWS
+    rng = np.random.default_rng(c["seed"])
+    e = EDGE
+    pos, bulk, ids = [], [], []
+    for b in range(c["blobs"]):
+        corner = np.array([(0.1 + 4.0 * b) * e, (0.1 + 4.0 * b) * e, 0.1 * e])
+        pos.append(corner + rng.uniform(0.0, c["side"], (c["per"], 3)))
+        bulk.append(np.broadcast_to(np.array([0.0, -4.0 * b * e / c["dt"], 0.0]), (c["per"], 3)))
+        ids.append(np.full(c["per"], b))
+    nx = 4.0 * (c["blobs"] - 1) + 3.0                          # cells along x
+    pos.append(np.array([[0.0, 0.0, 0.0], [(nx - 0.05) * e, (nx + 1.5) * e, (nx + 2.5) * e]]))     # nx, nx + 2, nx + 3 cells
+    bulk.append(np.zeros((N_MARKERS, 3)))
+    ids.append(np.array([c["blobs"], c["blobs"] + 1]))
+    pos, bulk = np.concatenate(pos), np.concatenate(bulk)
+    gas = _gas(rng, pos, bulk, c["sigma"])
+    for f, a in zip(("vx", "vy", "vz"), bulk[-N_MARKERS:].T):            # the markers stay where they are
+        gas[f][-N_MARKERS:] = a
+    return dict(gas=gas, dts=[c["dt"]] if where == "last" else [c["dt"], 0.01, 0.01], run=None, clump=np.concatenate(ids))
+
+
 # t = 1 - 2^-k for the approach (the cube halves per step); then the meeting, each dt found by bisection on the oracle so
 # that the longest list grows by a little over a fifth (and written here with three digits); then three steps apart again.
 # The clumps close at 1e4 length units per time unit -- they have to cross 3300 within the time a clump of this size takes
@@ -158,7 +273,15 @@ BUILDERS = {"contraction": contraction,
             "clumps_apart": clumps_apart,
             "clumps_drift": clumps_drift,
             "clumps_together": clumps_together,
-            "sheet_puffing_up": sheet_puffing_up}
+            "sheet_puffing_up": sheet_puffing_up,
+            "dense_cube_32767": lambda: dense_cube(32767),
+            "dense_cube_32768": lambda: dense_cube(32768),
+            "dense_cube_window": dense_cube_window,
+            "sheet_with_knot": sheet_with_knot,
+            "rows_aligned_mid": lambda: rows_aligned("mid"),
+            "rows_aligned_last": lambda: rows_aligned("last")}
+DENSE_STATIC = ["dense_cube_32767", "dense_cube_32768"]
+ROWS_ALIGNED = ["rows_aligned_mid", "rows_aligned_last"]
 SMALL = ["contraction", "clumps_apart", "clumps_drift", "clumps_together"]
 TOO_FAST = ["contraction_too_fast_mid", "contraction_too_fast_last"]
 _BUILT = {}
@@ -204,6 +327,109 @@ def pair_stats(pos, tie=1e-12, chunk=512):
     entries = int(per.sum())
     return dict(longest=int(per.max()) if n else 0, entries=entries, entries_lo=entries + lo, entries_hi=entries + hi,
                 near=near, per=per)
+
+
+def host_threads():
+    """the threads a numpy reference may use: what the process is granted, at most 16"""
+    import os
+    return max(1, min(16, len(os.sched_getaffinity(0))))
+
+
+def pair_stats_binned(pos, tie=1e-12):
+    """pair_stats for the sets too large for it (O(n^2) at 36000 and more): the same counts -- r^2 formed by the very same
+    expression on the very same numbers, so bit for bit the same comparisons -- over the candidates of a cell grid only.
+    Cells of the list's edge (a hair more than 2 h, which also covers the `near` band): a pair is at most one cell apart per
+    axis; the cells of one row are consecutive in the cell-sorted order, so a cell's candidates are 9 ranges of it (found by
+    bisection on the sorted keys: no table of cells, the box may hold 2^31 of them and more).  One task per occupied cell,
+    on host_threads() threads (numpy releases the interpreter lock in its loops).  Equal to pair_stats on the small sets:
+    tests/test_steady_sets_cpu.py."""
+    from concurrent.futures import ThreadPoolExecutor
+    n = pos.shape[0]
+    r2cut = RCUT * RCUT
+    lo = pos.min(axis=0)
+    cell = np.floor((pos - lo) * (1.0 / EDGE)).astype(np.int64)
+    dim = cell.max(axis=0) + 1
+    key = (cell[:, 2] * dim[1] + cell[:, 1]) * dim[0] + cell[:, 0]
+    order = np.argsort(key, kind="stable")
+    x, y, z = (np.ascontiguousarray(pos[order, a]) for a in range(3))
+    skey = key[order]
+    occupied, first = np.unique(skey, return_index=True)
+    last = np.r_[first[1:], n]
+
+    def one(t):
+        k, a, b = int(occupied[t]), int(first[t]), int(last[t])
+        c0, c1, c2 = k % dim[0], (k // dim[0]) % dim[1], k // (dim[0] * dim[1])
+        cand = []
+        for o2 in range(max(c2 - 1, 0), min(c2 + 1, dim[2] - 1) + 1):
+            for o1 in range(max(c1 - 1, 0), min(c1 + 1, dim[1] - 1) + 1):
+                row = (o2 * dim[1] + o1) * dim[0]
+                ja = int(np.searchsorted(skey, row + max(c0 - 1, 0), side="left"))
+                jb = int(np.searchsorted(skey, row + min(c0 + 1, dim[0] - 1), side="right"))
+                if jb > ja:
+                    cand.append(np.arange(ja, jb))
+        cand = np.concatenate(cand)
+        cnt, nr, tl, th = np.zeros(b - a, dtype=np.int64), 0, 0, 0
+        step = max(1, 4_000_000 // cand.size)
+        for a0 in range(a, b, step):                     # (blocks of targets: a dense cell has hundreds, with 20000 candidates)
+            b0 = min(b, a0 + step)
+            d = x[a0:b0, None] - x[None, cand]
+            r2 = d * d
+            d = y[a0:b0, None] - y[None, cand]
+            r2 += d * d
+            d = z[a0:b0, None] - z[None, cand]
+            r2 += d * d
+            r2[cand[None, :] == np.arange(a0, b0)[:, None]] = np.inf
+            band = r2[np.abs(r2 - r2cut) <= r2cut * 2.0e-9]
+            tied = np.abs(band - r2cut) <= r2cut * 2.0 * tie
+            cnt[a0 - a:b0 - a] = np.count_nonzero(r2 <= r2cut, axis=1)
+            nr, tl, th = nr + int(band.size), tl + int(np.count_nonzero(tied & (band <= r2cut))), th + int(np.count_nonzero(tied & (band > r2cut)))
+        return a, b, cnt, nr, tl, th
+    per_sorted = np.zeros(n, dtype=np.int64)
+    lo_ = hi_ = near = 0
+    with ThreadPoolExecutor(max_workers=host_threads()) as pool:
+        for a, b, cnt, nr, tl, th in pool.map(one, range(occupied.size)):
+            per_sorted[a:b] = cnt
+            near, lo_, hi_ = near + nr, lo_ - tl, hi_ + th
+    per = np.empty(n, dtype=np.int64)
+    per[order] = per_sorted
+    entries = int(per.sum())
+    return dict(longest=int(per.max()) if n else 0, entries=entries, entries_lo=entries + lo_, entries_hi=entries + hi_,
+                near=near, per=per)
+
+
+def build_boxes(pos_list):
+    """the box of each build of one upload: the exact box at build 0, then the previous build's, one guard cell wider"""
+    return [exact_box(pos_list[0])] + [stale_box(p) for p in pos_list[:-1]]
+
+
+def need_replay(pos_list):
+    """tile_fit_replay of every build: the per-group needs, and their largest"""
+    fits = [tile_fit_replay(p, *b) for p, b in zip(pos_list, build_boxes(pos_list))]
+    return fits, [int(f["need"].max()) for f in fits]
+
+
+def list16_replay(needs):
+    """csrc/tiled.hip nlist_build_tiled, csrc/api.hip drain_reports over the builds of one upload: needs[k] = the largest tile
+    need of build k.  Per build: "tiled" (the build wrote 16-bit entries), "leaves" (it left the tiled path: at build 0 on
+    its own report, later on the previous build's), "error" (the previous build's need had reached 65536: refused).  A last
+    build whose own need reaches 65536 is "drained": the call that returns reports it."""
+    out, tiled = [], True
+    for k, need in enumerate(needs):
+        if not tiled:
+            out.append("untiled")
+            continue
+        seen = need if k == 0 else needs[k - 1]
+        if k > 0 and seen >= LIST16_FULL:
+            out.append("error")
+            break
+        if 2 * seen >= LIST16_FULL:
+            tiled = False
+            out.append("leaves")
+            continue
+        out.append("tiled")
+    if out and out[-1] == "tiled" and needs[len(out) - 1] >= LIST16_FULL and len(out) == len(needs):
+        out[-1] = "drained"
+    return out
 
 
 def exact_box(pos):
@@ -416,17 +642,73 @@ def oracle_eval(state, clump=None):
     return out
 
 
-def terms_ref(state, clump=None):
+def terms_ref(state, clump=None, targets=None):
     """tests/force_terms_ref.fixed_terms(...).recomposed() on `state`: the five rates and the summed magnitudes of their
-    terms (the scale of the project's per-element bar), each of shape (5, n)"""
+    terms (the scale of the project's per-element bar), each of shape (5, n).  targets: an index array -- only these
+    particles' elements mean anything (the whole set in one piece: O(len(targets) n))"""
     import force_terms_ref as FT
     n = state["x"].size
+    if targets is not None:
+        got, sc = FT.fixed_terms({k: state[k] for k in STATE}, NO_SINKS, h=H, targets=targets).recomposed()
+        return np.array(got), np.array(sc)
     rates, scales = np.empty((5, n)), np.empty((5, n))
     for idx in static_pieces(state, clump):
         got, sc = FT.fixed_terms({k: state[k][idx] for k in STATE}, NO_SINKS, h=H).recomposed()
         for k in range(5):
             rates[k][idx], scales[k][idx] = got[k], sc[k]
     return rates, scales
+
+
+def rho_ref(state, targets):
+    """the density sum of `targets` restated in extended precision: rho_i = sum over r_ij <= 2 h, self included, of
+    m_j W(r_ij) with the oracle's table lookup (oracle.orc.lookup_kernel) and r as the oracle forms it.  Returns (rho as
+    long double, the number of terms per target)"""
+    from oracle import orc
+    pos, m = positions(state), state["m"]
+    rho, terms = np.empty(len(targets), dtype=np.longdouble), np.empty(len(targets), dtype=np.int64)
+    for a, i in enumerate(targets):
+        d = pos[i] - pos
+        r = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2])
+        j = np.flatnonzero(r <= RCUT)
+        W, _ = orc.lookup_kernel(r[j], H)
+        rho[a], terms[a] = np.sum((m[j] * W).astype(np.longdouble)), j.size
+    return rho, terms
+
+
+def rho_bar(rho, list_len):
+    """the per-element bar of a density sum of list_len + 1 positive terms: (k + 8) 2^-53 rho.  A sum of k + 1 positive fp64
+    terms in ANY order is within k 2^-53 of its exact value (each of the k additions rounds a partial sum <= rho by half an
+    ulp); the 8 covers the roundings inside a term (the separation, the table's interpolation, the mass), which the two sides
+    form alike"""
+    return (list_len + 8.0) * 2.0 ** -53 * rho
+
+
+def near_cell_faces(pos, lo, tol=1e-9):
+    """how many coordinates lie within tol cell edges of an inner face of the grid that starts at lo: the particles that the
+    ~1e-12 between the oracle's and the GPU's trajectory could put into another cell.  None of them: the two trajectories
+    sort every particle into the same cell, and every replayed need is the same integer on both."""
+    t = (pos - np.asarray(lo)) * (1.0 / EDGE)
+    return int(np.count_nonzero((np.abs(t - np.round(t)) < tol) & (np.round(t) >= 1.0)))
+
+
+def edge_targets(pos, lo, hi, fit, count=512, seed=0, least=LIST16_HALF, among=None):
+    """the targets of the sampled restatement on a build over the box (lo, hi) (fit = tile_fit_replay(pos, lo, hi)): the
+    particles in the first and the last 64 slots of the tile of every group whose need is >= `least` (32768; the cell-sorted
+    neighbours of the lowest and the highest entries), every fourth target of those groups, and a seeded sample of the rest
+    (of the particles `among`, an index array, where given) up to `count` (at least 128 of them)"""
+    order = fit["order"]
+    pick = []
+    for g in np.flatnonzero(fit["need"] >= least):
+        pick.append(order[256 * g:256 * (g + 1):4])
+        first = next(q for q in range(3) if fit["len"][q][g] > 0)
+        last = next(q for q in (2, 1, 0) if fit["len"][q][g] > 0)
+        pick.append(order[fit["lo"][first][g]:fit["lo"][first][g] + 64])
+        end = fit["lo"][last][g] + fit["len"][last][g]
+        pick.append(order[max(end - 64, 0):end])
+    pick = np.unique(np.concatenate(pick)) if pick else np.zeros(0, dtype=np.int64)
+    rest = np.setdiff1d(np.arange(pos.shape[0]) if among is None else among, pick)
+    extra = np.random.default_rng(seed).choice(rest, size=min(rest.size, max(count - pick.size, 128)), replace=False)
+    return np.sort(np.concatenate([pick, extra]))
 
 
 def early_replay(grid, tables=None):
@@ -449,6 +731,7 @@ def early_replay(grid, tables=None):
 
 
 # ---- the tile fit of the forces kernel, replayed ---------------------------------------------------------------------------
+TILE_CAP_D = (3836, 5087)         # csrc/tiled.hip tile_cap(5000, 4, .): records of a density tile beside the kernel table / without it
 TILE_CAP_Q = (1220, 1628)         # csrc/tiled.hip tile_cap_q(5000): records of a forces tile beside the kernel table / without it
 
 
@@ -458,7 +741,11 @@ def tile_fit_replay(pos, lo, hi):
     a group's tile need is the summed length of its three candidate intervals of the sorted order (one per offset along the
     slowest axis: from the first candidate row of any of its targets to the last).  Returns need (per group), misfits
     (groups of 256 beside the table, without it, half groups beside the table, without it), fit_pct_forces, half (the half-group
-    kernel is chosen) and ok (the whole-tile forces kernel runs)."""
+    kernel is chosen) and ok (the whole-tile forces kernel runs).  Also: order (the cell-sorted order: order[s] = the
+    particle in sorted slot s; group g holds slots 256 g .. 256 g + 255), lo and len (per interval 0, 1, 2 an array over the
+    groups of 256: the interval's first sorted slot and its length; a group's tile is the three intervals one after the
+    other, so entry e of a group points into them), and the density geometry: need_d (per group of 1024 targets),
+    misfits_d (groups beside the table, without it), fit_pct (what stats().tile_fit_pct reports) and ok_d (density_wt runs)."""
     n = pos.shape[0]
     dim = cells_of(lo, hi)[0].astype(np.int64)
     c = np.clip(np.floor((pos - np.asarray(lo)) * (1.0 / EDGE)).astype(np.int64), 0, dim - 1)
@@ -479,6 +766,7 @@ def tile_fit_replay(pos, lo, hi):
     lo0, hi0 = np.maximum(c0 - 1, 0), np.minimum(c0 + 1, d0 - 1)
     big = np.iinfo(np.int64).max
     need = {256: 0, 128: 0}
+    ivl_lo, ivl_len = [], []                             # per interval (offset -1, 0, 1 along the slowest axis) and group of 256
     for o2 in (-1, 0, 1):
         mn, mx = np.full(n, big), np.zeros(n, dtype=np.int64)
         for o1 in (-1, 0, 1):
@@ -493,6 +781,8 @@ def tile_fit_replay(pos, lo, hi):
             edges = np.arange(0, n, g)
             glo, ghi = np.minimum.reduceat(mn, edges), np.maximum.reduceat(mx, edges)
             need[g] = need[g] + np.where(ghi > glo, ghi - glo, 0)
+            if g == 256:
+                ivl_lo.append(np.where(ghi > glo, glo, 0)); ivl_len.append(np.where(ghi > glo, ghi - glo, 0))
     f_blocks = (n + 255) // 256
     half = need[128]
     if half.size < 2 * f_blocks:
@@ -507,4 +797,17 @@ def tile_fit_replay(pos, lo, hi):
     else:
         bigt = not ok_f and ok_fb
         ok, pct = (ok_fb if bigt else ok_f), 100 - (100 * mis[1 if bigt else 0]) // max(f_blocks, 1)
-    return dict(need=need[256], misfits=mis, fit_pct_forces=int(pct), half=use_half, ok=bool(ok))
+    # the density geometry (tiled.hip plan_reduce_kernel): a group of 1024 targets takes, per interval, the span of its four
+    # forces groups; its tile holds TILE_CAP_D records beside the kernel table / without it
+    edges, need_d = np.arange(0, f_blocks, 4), 0
+    for q in range(3):
+        has = ivl_len[q] > 0
+        glo = np.minimum.reduceat(np.where(has, ivl_lo[q], big), edges)
+        ghi = np.maximum.reduceat(np.where(has, ivl_lo[q] + ivl_len[q], 0), edges)
+        need_d = need_d + np.where(ghi > glo, ghi - glo, 0)
+    d_blocks = (n + 1023) // 1024
+    mis_d = [int(np.count_nonzero(need_d > TILE_CAP_D[0])), int(np.count_nonzero(need_d > TILE_CAP_D[1]))]
+    big_d = not mis_d[0] * 10 <= d_blocks and mis_d[1] * 10 <= d_blocks
+    return dict(need=need[256], misfits=mis, fit_pct_forces=int(pct), half=use_half, ok=bool(ok), order=order, lo=ivl_lo, len=ivl_len,
+                need_d=need_d, misfits_d=mis_d, fit_pct=int(100 - (100 * mis_d[1 if big_d else 0]) // max(d_blocks, 1)),
+                ok_d=bool(mis_d[1 if big_d else 0] * 10 <= d_blocks))

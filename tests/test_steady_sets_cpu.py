@@ -210,3 +210,228 @@ def test_sheet_puffing_up_loses_its_forces_tile_fit():
     # nothing else moves: one dense untrimmed grid, lists that only shrink (the first build regrows the 96 slots at once)
     assert all(g["kind"] == 0 and g["rounds"] == 0 for g in grid)
     assert stats[0]["longest"] > S.NL_CAP0 and not any(c["regrown"] or c["overflow"] for c in caps)
+
+
+# ---- the 16-bit list entries at their limits (tests/test_list16_edges_gpu.py) -------------------------------------------------
+# Measured here (8 host threads; 2.5 minutes for these tests, 67 s of them the oracle's three steps on the 754000 particles of
+# sheet_with_knot): the oracle's rho against the extended-precision restatement on 300
+# sampled targets of each set -- sums of 1000 to 5800 positive terms -- differs by <= 6.8e-15 per element (static cube 5.9e-15,
+# window build 6.2e-15, rows 6.8e-15): within a tenth of 1e-13, so the GPU file keeps the project's 1e-13 per element and
+# does not need the derived bound steady_sets.rho_bar ((k + 8) 2^-53 rho: the measured spread is 1.9 % of it).  The oracle's
+# rates against the sampled restatement use 1.9 % of the per-element rate bar and 2e-15 of the field's scale (EVAL_TOL: 1e-13).
+_BIG = {}
+
+
+def big_case(name):
+    """(set, states, positions per build, binned pair statistics per build, capacity replay, tile fits, largest needs)"""
+    if name not in _BIG:
+        s = S.build(name)
+        states = S.trajectory(name)[0] if s["dts"] else [dict(s["gas"])]
+        pos = [S.positions(st) for st in states]
+        stats = [S.pair_stats_binned(p) for p in pos]
+        fits, needs = S.need_replay(pos)
+        _BIG[name] = (s, states, pos, stats, S.capacity_replay([p["longest"] for p in stats]), fits, needs)
+    return _BIG[name]
+
+
+@pytest.mark.parametrize("name", ["contraction", "clumps_apart", "clumps_together"])
+def test_binned_pair_count_is_the_brute_force_count(name):
+    """the cell-binned count forms r^2 with the same expression on the same numbers: every figure of pair_stats, per
+    particle, on sets small enough for both (clumps_together: 2^31 list cells, a sparse box)"""
+    pos = S.positions(S.build(name)["gas"])
+    a, b = S.pair_stats(pos), S.pair_stats_binned(pos)
+    assert set(a) == set(b)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), (name, k)
+    if name == "contraction":
+        shrunk = 0.3 * pos                                                    # dense: lists of hundreds, few cells
+        a, b = S.pair_stats(shrunk), S.pair_stats_binned(shrunk)
+        assert a["longest"] > 200 and all(np.array_equal(a[k], b[k]) for k in a), name
+
+
+def test_sampled_restatement_is_the_full_one_on_its_targets():
+    """force_terms_ref.fixed_terms(targets=...) on a small set: bitwise the rows of the full restatement"""
+    import force_terms_ref as FT
+    gas = S.build("contraction")["gas"]
+    tg = np.sort(np.random.default_rng(3).choice(gas["x"].size, 200, replace=False))
+    full, part = FT.fixed_terms(gas, S.NO_SINKS, h=S.H), FT.fixed_terms(gas, S.NO_SINKS, h=S.H, targets=tg)
+    assert np.array_equal(full.rows[:, tg], part.rows[:, tg]) and np.array_equal(full.scale[:, tg], part.scale[:, tg])
+    assert np.array_equal(full.list_len[tg], part.list_len[tg])
+    rates, scales = S.terms_ref(gas, targets=tg)
+    ref = S.terms_ref(gas)
+    assert np.array_equal(rates[:, tg], ref[0][:, tg]) and np.array_equal(scales[:, tg], ref[1][:, tg])
+
+
+def _common_conditions(name, s, states, pos, stats):
+    gas = s["gas"]
+    n = gas["x"].size
+    assert all(gas[k].shape == (n,) and gas[k].dtype == np.float64 for k in S.STATE) and np.all(gas["m"] == S.MASS)
+    assert 0.05 <= gas["alpha"].min() and gas["alpha"].max() <= 1.0 and 0.5 <= gas["u"].min() and gas["u"].max() <= 2.0
+    again = S.BUILDERS[name]()["gas"]
+    assert all(np.array_equal(gas[k], again[k]) for k in S.STATE)                       # seeded
+    for k, st in enumerate(states):
+        assert all(np.all(np.isfinite(a)) for a in st.values()), (name, k)
+        # no pair ties with r = 2 h at 1e-12: the exact count of the GPU file (taken on the positions the GPU run itself
+        # went through) is well defined.  (Among 1e8 pairs a few lie within 1e-9 of 2 h; that is why `near` is not asked for)
+        assert stats[k]["entries_lo"] == stats[k]["entries"] == stats[k]["entries_hi"], (name, k)
+        assert stats[k]["near"] <= 8, (name, k, stats[k]["near"])
+
+
+def _spread(name, state, targets=300):
+    """the bar question of the GPU file, decided CPU against CPU: the oracle's rho against the extended-precision
+    restatement on sampled targets, per element; and the oracle's rates against the sampled O(n) restatement"""
+    import varh_ref as VR
+    st = {k: state[k] for k in S.STATE}
+    tg = np.sort(np.random.default_rng(1).choice(st["x"].size, targets, replace=False))
+    ev = S.oracle_eval(st)
+    rho, terms = S.rho_ref(st, tg)
+    e = np.abs(ev["rho"][tg].astype(np.longdouble) - rho) / rho
+    share = float(np.max(e * rho / S.rho_bar(rho, terms - 1)))
+    rates, scales = S.terms_ref(st, targets=tg)
+    rate = max(float(np.max(VR.rate_excess(np.abs(ev[f][tg] - rates[i][tg]), np.abs(rates[i][tg]), scales[i][tg])))
+               for i, f in enumerate(S.RATES))
+    scale = max(float(np.max(np.abs(ev[f][tg] - rates[i][tg])) / np.max(np.abs(ev[f]))) for i, f in enumerate(S.RATES))
+    print(f"{name}: oracle against the restatement on {targets} targets of {int(terms.min())} to {int(terms.max())} terms: rho "
+          f"{float(e.max()):.2e} per element ({share:.1%} of (k + 8) 2^-53 rho), rates {rate:.1%} of the per-element bar, "
+          f"{scale:.1e} of the field's scale")
+    # at most a tenth of each bar: the GPU file keeps 1e-13 per element on rho, the rate bar and EVAL_TOL
+    assert float(e.max()) <= 1e-14 and rate <= 0.1 and scale <= 1e-14
+
+
+@pytest.mark.parametrize("name", S.DENSE_STATIC)
+def test_dense_cubes_sit_on_either_side_of_the_first_build_guard(name):
+    s, states, pos, stats, caps, fits, needs = big_case(name)
+    _common_conditions(name, s, states, pos, stats)
+    n = pos[0].shape[0]
+    lo, hi = S.exact_box(pos[0])
+    cells = (hi - lo) / S.EDGE
+    print(name, "n", n, "box in cell edges", cells, "largest need", needs, "longest list", stats[0]["longest"],
+          "mean", stats[0]["entries"] / n)
+    # exactly 3 cells per axis, and at least a twentieth of an edge from 2 or 4
+    assert list(S.cells_of(lo, hi)[0]) == [3.0, 3.0, 3.0] and np.all(cells > 2.05) and np.all(cells < 2.95)
+    # one tile: the largest need is n, an integer count
+    assert needs == [n] and n == (32767 if name.endswith("32767") else 32768)
+    assert S.list16_replay(needs) == (["tiled"] if n == 32767 else ["leaves"])
+    assert 2 * (n - 1) < S.LIST16_FULL <= 2 * 32768
+    assert 3000 <= stats[0]["entries"] / n <= 6000 and not caps[0]["overflow"]
+    if n == 32768:
+        _spread(name, states[0])
+
+
+def test_dense_cube_window_passes_through_the_one_build_window():
+    name = "dense_cube_window"
+    s, states, pos, stats, caps, fits, needs = big_case(name)
+    _common_conditions(name, s, states, pos, stats)
+    boxes = S.build_boxes(pos)
+    dims = [list(S.cells_of(*b)[0]) for b in boxes]
+    plan = S.list16_replay(needs)
+    longest = [p["longest"] for p in stats]
+    over = [int(np.count_nonzero(f["need"] >= S.LIST16_HALF)) for f in fits]
+    print(name, "needs", needs, "groups at or above 32768", over, "of", fits[0]["need"].size, plan, "longest", longest,
+          [(c["cap"], c["regrown"]) for c in caps], "cells", dims)
+    assert 3 <= len(s["dts"]) <= 4
+    # 4 cells per axis at the first build, then the stale box: the previous build's cells and a guard cell per side (4 + 2;
+    # 3 + 2 once the cube is less than three edges wide -- from there on it is one tile, need = n)
+    assert dims[0] == [4.0] * 3 and dims[1] == dims[2] == [6.0] * 3 and all(d in ([6.0] * 3, [5.0] * 3) for d in dims[3:])
+    # below 32768 at builds 0 and 1, inside [32768, 65535] at build 2, by a margin of 1000 records each; build 3 leaves
+    assert needs[0] < needs[1] <= S.LIST16_HALF - 1000 and S.LIST16_HALF + 1000 <= needs[2] <= S.LIST16_FULL - 1000
+    assert plan == ["tiled", "tiled", "tiled", "leaves", "untiled"]
+    assert 2 <= over[2] < fits[2]["need"].size // 4 and over[0] == over[1] == 0       # a few groups write bit-15 entries
+    # ... margins that the ~1e-12 between the oracle's and the GPU's trajectory cannot touch: no particle is that close to a
+    # cell face, so both sort every particle into the same cell
+    assert all(S.near_cell_faces(p, b[0]) == 0 for p, b in zip(pos, boxes))
+    # the lists grow by less than a quarter per step: regrown from stale reports at most, never overflowing
+    ratios = [b / a for a, b in zip(longest, longest[1:])]
+    assert max(ratios) < 1.25 and not any(c["overflow"] for c in caps) and not caps[0]["regrown"]
+    _spread(name, states[2])
+
+
+def test_rows_aligned_needs_pass_65536_within_one_build_and_no_list_grows():
+    name = "rows_aligned_last"
+    s, states, pos, stats, caps, fits, needs = big_case(name)
+    _common_conditions(name, s, states, pos, stats)
+    mid = S.build("rows_aligned_mid")
+    assert all(np.array_equal(mid["gas"][k], s["gas"][k]) for k in S.STATE) and mid["dts"][0] == s["dts"][0]
+    assert len(s["dts"]) == 1 and len(mid["dts"]) == 3
+    clump, nb = s["clump"], S.ROWS["blobs"]
+    boxes = S.build_boxes(pos)
+    dims = [list(S.cells_of(*b)[0]) for b in boxes]
+    longest = [p["longest"] for p in stats]
+    print(name, "needs", needs, S.list16_replay(needs), "cells", dims, "longest", longest, [c["cap"] for c in caps])
+    # x has the fewest cells at both builds (the markers stretch y and z): it is the fastest axis of the cell key
+    assert all(d[0] < d[1] < d[2] for d in dims)
+    # every blob alone stays tiled at a first build; aligned, the largest need passes 65536: each by 1000 records and more
+    assert needs[0] <= S.LIST16_HALF - 1000 and needs[1] >= S.LIST16_FULL + 1000
+    assert S.list16_replay(needs) == ["tiled", "drained"] and S.list16_replay(needs + [0, 0]) == ["tiled", "tiled", "error"]
+    assert all(S.near_cell_faces(p, b[0]) == 0 for p, b in zip(pos, boxes))
+    # the blobs start in different rows (four cells apart along y) and end in the same ones
+    cy = [np.floor((p[:, 1] - b[0][1]) / S.EDGE) for p, b in zip(pos, boxes)]
+    for b in range(nb):
+        assert set(cy[0][clump == b]) == {4.0 * b, 4.0 * b + 1, 4.0 * b + 2} and set(cy[1][clump == b]) == {1.0, 2.0, 3.0}
+    # no pair of different blobs comes within 2 h during the step: they stay apart along x, before and after (the bulk
+    # motion has no x component and the random velocities move a particle by 0.005 a step)
+    for p in pos:
+        for b in range(nb - 1):
+            gap = p[clump == b + 1, 0].min() - p[clump == b, 0].max()
+            assert gap > S.RCUT + 0.5, (b, gap)
+    # the markers are the box's corners at both builds; no list grows, nothing is regrown, nothing overflows
+    for p in pos:
+        assert np.array_equal(p[clump == nb][0], p.min(axis=0)) and np.array_equal(p[clump == nb + 1][0], p.max(axis=0))
+    assert longest[1] <= 1.02 * longest[0] and not any(c["regrown"] or c["overflow"] for c in caps)
+    _spread(name, states[0])
+
+
+def test_sheet_with_knot_keeps_both_tile_fits_while_the_knot_passes_through_the_window():
+    """(75 s of this file: the oracle's three steps on 754000 particles)"""
+    name = "sheet_with_knot"
+    s = S.build(name)
+    states = S.trajectory(name)[0]
+    pos = [S.positions(st) for st in states]
+    clump, n = s["clump"], pos[0].shape[0]
+    assert all(np.all(np.isfinite(a)) for st in states for a in st.values())
+    assert all(np.array_equal(s["gas"][k], S.BUILDERS[name]()["gas"][k]) for k in ("x", "vz", "alpha"))        # seeded
+    boxes = S.build_boxes(pos)
+    fits, needs = S.need_replay(pos)
+    plan = S.list16_replay(needs)
+    dims = [list(S.cells_of(*b)[0]) for b in boxes]
+    over = [np.flatnonzero(f["need"] >= S.LIST16_HALF) for f in fits]
+    print(name, "needs", needs, plan, "groups at or above 32768", [o.size for o in over], "of", fits[0]["need"].size, "tile fit",
+          [f["fit_pct"] for f in fits], [f["misfits_d"] for f in fits], "forces", [f["fit_pct_forces"] for f in fits],
+          [f["misfits"] for f in fits], "cells", dims)
+    assert 2 <= len(s["dts"]) <= 3 and 300000 <= n <= 800000
+    # z has the fewest cells by far: the fastest axis of the cell key, the knot's columns run over its whole height
+    assert all(d[2] <= 12 and min(d[0], d[1]) >= 100 for d in dims)
+    # the knot passes through the window as dense_cube_window does, by margins of 800 records
+    assert needs[0] < needs[1] <= S.LIST16_HALF - 800 and S.LIST16_HALF + 800 <= needs[2] <= S.LIST16_FULL - 800
+    assert plan == ["tiled", "tiled", "tiled", "leaves"]
+    assert all(S.near_cell_faces(p, b[0]) == 0 for p, b in zip(pos, boxes))
+    # both geometries fit nine groups in ten at every build (so the whole-tile kernels run, with 256-target forces groups),
+    # with at least a group in a hundred to spare: the knot's groups are fewer than one in ten of either
+    d_blocks, f_blocks = (n + 1023) // 1024, (n + 255) // 256
+    for k, f in enumerate(fits):
+        assert f["fit_pct"] >= 90 and f["ok_d"] and f["fit_pct_forces"] >= 90 and f["ok"] and not f["half"], k
+        assert min(f["misfits_d"]) * 10 <= 0.9 * d_blocks and f["misfits"][1] * 10 <= 0.9 * f_blocks, k
+    # the groups that write bit-15 entries are the knot's, and they misfit in both geometries: the fall-back loops serve them
+    f = fits[2]
+    assert over[2].size >= 2 and not over[0].size and not over[1].size
+    assert np.all(f["need"][over[2]] > S.TILE_CAP_Q[1]) and np.all(f["need_d"][over[2] // 4] > S.TILE_CAP_D[1])
+    assert all(np.count_nonzero(clump[f["order"][256 * g:256 * (g + 1)]] == 1) >= 128 for g in over[2])
+    # the lists: the longest are the knot's (exact counts on the knot's box, 2 h wider: complete for every particle inside the
+    # box), growing by less than a quarter per step; the sheet's are bounded by its surface density
+    longest = []
+    for p in pos:
+        klo, khi = p[clump == 1].min(axis=0), p[clump == 1].max(axis=0)
+        sub = np.flatnonzero(np.all((p >= klo - 1.01 * S.RCUT) & (p <= khi + 1.01 * S.RCUT), axis=1))
+        ps = S.pair_stats_binned(p[sub])
+        inside = np.all((p[sub] >= klo) & (p[sub] <= khi), axis=1)
+        assert ps["entries_lo"] == ps["entries"] == ps["entries_hi"]
+        longest.append(int(ps["per"][inside].max()))
+    caps = S.capacity_replay(longest)
+    print(name, "longest", longest, [(c["cap"], c["regrown"]) for c in caps])
+    per_area = s["gas"]["x"][clump == 0].size / S.KNOT["side"] ** 2
+    assert 3.0 * per_area * np.pi * S.RCUT ** 2 < min(longest)
+    assert max(b / a for a, b in zip(longest, longest[1:])) < 1.25 and not any(c["overflow"] for c in caps)
+    # (the knot and its surroundings: both references on the same subset, whose sums are as long as the whole set's)
+    p = pos[2]
+    sub = np.flatnonzero(np.all(np.abs(p) <= np.abs(p[clump == 1]).max(axis=0) + 2.0 * S.RCUT, axis=1))
+    _spread(name, {k: states[2][k][sub] for k in S.STATE}, targets=200)
