@@ -61,8 +61,7 @@ int ensure_capacity(sph_ctx *c, int64_t n) {
     c->sort_tmp_bytes = tmp;
     SPH_TRY(ctx_alloc_bytes(c, &c->sort_tmp, tmp ? tmp : 1, "sort scratch"));
     c->nl_waves_cap = (cap + 63) / 64;
-    c->nl_cap = 96;   // grows on demand (nlist_build); the tiled fixed-h build writes 16-bit entries (tile_common.hpp)
-    SPH_TRY(ctx_alloc(c, &c->nlist, (size_t)c->nl_waves_cap * c->nl_cap * (c->tiled ? 32 : 64), "neighbour list"));
+    SPH_TRY(list_alloc(c, 96));   // grows on demand (nlist_build); the tiled fixed-h build writes 16-bit entries (tile_common.hpp)
     SPH_TRY(ctx_alloc(c, &c->ncount, (size_t)cap, "neighbour counts"));
     SPH_TRY(ctx_alloc(c, &c->wave_max, (size_t)c->nl_waves_cap, "wave max"));
     SPH_TRY(ctx_alloc(c, &c->wave_class, (size_t)c->nl_waves_cap, "wave classes"));
@@ -163,11 +162,7 @@ void resolve_timing(sph_ctx *c) {
 // table-free tile): 0.205 vs 0.358 -- hence one group per CU at least.  forces_q (groups of 256, four lanes per target) wins at every
 // size, 47 groups included (12 000 particles: 0.032 vs 0.049 ms).  SPH_TILE_MIN_GROUPS_D / _F: A/B switches (x0.01 groups per CU).
 bool use_tile_kernel(const sph_ctx *c, bool forces) {
-    static const int thr_d = getenv("SPH_TILE_MIN_GROUPS_D") ? atoi(getenv("SPH_TILE_MIN_GROUPS_D")) : 100;
-    static const int thr_f = getenv("SPH_TILE_MIN_GROUPS_F") ? atoi(getenv("SPH_TILE_MIN_GROUPS_F")) : 0;
-    if (!c->whole_tile || !(forces ? c->wt_ok_f : c->wt_ok)) return false;
-    const int64_t groups = (c->n + (forces ? 255 : 1023)) / (forces ? 256 : 1024);
-    return 100 * groups >= (int64_t)(forces ? thr_f : thr_d) * c->num_cus;
+    return sph::use_tile_kernel(c->tile, c->whole_tile, forces, c->n, c->num_cus, switches().tile_min_groups_d, switches().tile_min_groups_f);
 }
 
 // Riders (rider_common.hpp, DESIGN section 4 "Round 6"): on the plain fixed-h step -- no variable h, no self-gravity, no accretion, no
@@ -176,16 +171,14 @@ bool use_tile_kernel(const sph_ctx *c, bool forces) {
 // A/B switches: SPH_NO_SINK_RIDE (here: the step does not ask for sink_accel_partial / _final to ride, the one item that does) and
 // SPH_NO_RIDERS (tiled.hip: the launchers carry no rider workgroup whatever they are asked).
 bool riders_allowed(const sph_ctx *c) {
-    static const bool off = getenv("SPH_NO_SINK_RIDE") != nullptr;
-    return !(off || c->variable || c->gravity || (c->p.flags & SPH_FLAG_ACCRETE_CULL) || c->n_slots != c->n || c->dead_below != 0 ||
-             c->n_owned != c->n || c->nranks != 1);
+    const StepConditions s{c->variable, c->gravity, (c->p.flags & SPH_FLAG_ACCRETE_CULL) != 0, c->n, c->n_slots, c->dead_below, c->n_owned, c->nranks};
+    return sph::riders_allowed(s, switches().no_sink_ride);
 }
 
 // in_step: called by a step (one_step_device_dt), which evaluates the forces on the same positions right behind and hands
 // *rode -- the blocks of sink_accel_partial that rode on this density pass, 0 for none -- on to do_forces
 int do_density(sph_ctx *c, bool in_step = false, int32_t *rode = nullptr) {
     if (rode) *rode = 0;
-    static const bool no_refresh = getenv("SPH_NO_H_REFRESH") != nullptr;      // A/B switch
     if (c->nl_overflowed) {
         // drain_reports cleared the stale report along with the validity flags, so the next build would wait for its own, regrow
         // and go on -- inside sph_step / sph_run from velocities that the truncated sums kicked.  The context cannot tell whether
@@ -193,7 +186,7 @@ int do_density(sph_ctx *c, bool in_step = false, int32_t *rode = nullptr) {
         c->err = "neighbour list overflowed in an earlier build: the state is incomplete, upload the particle set again";
         return SPH_ERR_STATE;
     }
-    if (!no_refresh && !c->grid_valid && c->variable && c->h_refresh_ok && c->order_valid && c->leaf_valid && c->n_slots == c->n) {
+    if (!switches().no_h_refresh && !c->grid_valid && c->variable && c->h_refresh_ok && c->order_valid && c->leaf_valid && c->n_slots == c->n) {
         // same positions, same particles, new h (calc_smoothing, Variable.f90:1152): the sorted order, the cell table and
         // the leaf cells stand; only what depends on h is redone -- and a self-gravity tree stays valid
         // growth of h against the lengths the list was built with -- known only when sph_update_h produced the new h (its
@@ -203,9 +196,8 @@ int do_density(sph_ctx *c, bool in_step = false, int32_t *rode = nullptr) {
         { Timed t(c, SPH_K_LEAF); SPH_TRY(varh_refresh_h(c)); }
         // the list of the new lengths: re-flagged from the list in place when no h outgrew its margin, else built.  The
         // re-flag pass and the density pass that follows it walk the same rows: one kernel does both (SPH_NO_FUSED_REFLAG: A/B)
-        static const bool no_fused = getenv("SPH_NO_FUSED_REFLAG") != nullptr;
         c->h_records_refreshed();
-        if (varh_can_reflag(c) && !no_fused) {
+        if (varh_can_reflag(c) && !switches().no_fused_reflag) {
             Timed t(c, SPH_K_REFLAG);
             SPH_TRY(varh_reflag_density(c, make_pair_const(c)));
             c->grid_valid = true; c->h_refresh_settled();
@@ -276,7 +268,7 @@ int do_forces(sph_ctx *c, int32_t rode = 0) {
     // (two sinks or more), now behind forces_q.  The timing group SPH_K_SINKACC then holds that launch or none; the riders' time is
     // their host kernels'.
     const bool tile_f = !c->variable && use_tile_kernel(c, true);
-    const bool ride_final = rode > 0 && tile_f && !c->wt_half_f;      // (the half-group variants of forces_q take no rider)
+    const bool ride_final = sph::ride_final(rode, tile_f, c->tile);   // (the half-group variants of forces_q take no rider)
     if (!ride_final) { Timed t(c, SPH_K_SINKACC); SPH_HIP(launch_sink_accel(c, pc, rode > 0 ? 1 : 0)); }
     { Timed t(c, SPH_K_FORCES); SPH_HIP(c->variable ? launch_forces_v(c, pc) : (tile_f ? launch_forces_wt(c, pc, 0, ride_final ? rode : 0) : launch_forces(c, pc))); }
     if (ride_final && pc.ns >= 2) { Timed t(c, SPH_K_SINKACC); SPH_HIP(launch_sink_accel(c, pc, 2)); }
@@ -331,12 +323,11 @@ int put_dt(sph_ctx *c, double dt, double t) {
 // The fixed-h build path reads its reports (longest list, non-finite positions) one build late so that the steady state never
 // waits for the host.  Every entry point that synchronises anyway and hands results to the caller calls this afterwards: the
 // reports of the LAST build have arrived by then, so a list that overflowed in the final build of a run (or in the only build
-// after an upload) is an error here, never a silently truncated result.  The same for a tile need that reached 65536 in that
-// build (rep[3]): its entries were truncated to 16 bits.  Requires the stream to be idle.
+// after an upload) is an error here, never a silently truncated result.  The same for a tile need that reached LIST16_MAX_NEED
+// in that build: its entries were truncated to 16 bits (judge_list, fixed_plan.hpp).  Requires the stream to be idle.
 int drain_reports(sph_ctx *c) {
     if (c->ring_nl_valid) {
-        const int32_t *rep = c->pin->nl[1 - c->ring_nl].v;
-        if (rep[0] > c->nl_cap || (c->tiled && rep[3] >= 65536)) {
+        if (judge_list(c->pin->nl[1 - c->ring_nl].v, c->nl_cap, ListReportAge::DRAIN, c->tiled).kind != ListKind::FITS) {
             c->err = "neighbour list overflowed in the last build (lists or candidate intervals grew beyond their headroom within one step): results are incomplete";
             c->list_overflow_reported();
             return SPH_ERR_STATE;
@@ -533,7 +524,7 @@ int sph_ctx_create(const sph_params *p, int device, sph_ctx **out) {
     for (int k = 0; k < 2; k++)
         if (hipEventCreateWithFlags(&c->ev_bbox[k], hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&c->ev_nl[k], hipEventDisableTiming) != hipSuccess) return fail(SPH_ERR_HIP);
-    c->no_stale = getenv("SPH_SYNC_EVERY_BUILD") != nullptr;
+    c->no_stale = ContextSwitches().sync_every_build;
     if (hipHostMalloc(reinterpret_cast<void **>(&c->pin), sizeof(PinnedSlots), hipHostMallocDefault) != hipSuccess) return fail(SPH_ERR_NOMEM);
     std::memset(c->pin, 0, sizeof(PinnedSlots));
     if ((st = ctx_alloc(c, &c->bbox_part, BBOX_PART_CLASSIC + (size_t)EARLY_MAX_BLOCKS * 6, "bbox")) != SPH_OK) return fail(st);
@@ -736,8 +727,8 @@ int sph_get_stats(sph_ctx *c, sph_stats *o) {
     }
     for (int a = 0; a < 3; a++) o->grid_dim[a] = c->grid.dim[a];
     o->nlist_capacity = c->nl_cap; o->nlist_max = c->nl_max;
-    o->tile_fit_pct = c->whole_tile ? c->wt_fit_pct : -1;
-    o->tile_fit_pct_forces = c->whole_tile ? c->wt_fit_pct_f : -1;
+    o->tile_fit_pct = c->whole_tile ? c->tile.fit_pct : -1;
+    o->tile_fit_pct_forces = c->whole_tile ? c->tile.fit_pct_f : -1;
     o->host_syncs = (int32_t)c->host_syncs;
     o->grid_builds = c->grid_builds; o->nlist_builds = c->nlist_builds;
     o->density_passes = c->density_passes; o->force_passes = c->force_passes;
@@ -758,7 +749,7 @@ int sph_get_stats(sph_ctx *c, sph_stats *o) {
             sw += m;
         }
         o->nlist_wave_mean = sw / (double)((cnt.size() + 63) / 64);
-        o->lane_efficiency_forces = (c->whole_tile && c->wt_ok_f) ? forces_lane_efficiency(cnt) : (sw > 0.0 ? s / (64.0 * sw) : 0.0);
+        o->lane_efficiency_forces = (c->whole_tile && c->tile.ok_f) ? forces_lane_efficiency(cnt) : (sw > 0.0 ? s / (64.0 * sw) : 0.0);
     }
     return SPH_OK;
 }

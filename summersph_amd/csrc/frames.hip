@@ -313,10 +313,7 @@ __global__ __launch_bounds__(256) void frames_finish(Args a) {
 
 // the splat's form: SPH_FRAMES_SPLAT=plain takes every pair straight to the global limbs (the form the window is measured
 // against); the result is the same bit for bit
-bool splat_plain() {
-    static const bool plain = [] { const char *e = std::getenv("SPH_FRAMES_SPLAT"); return e && std::strcmp(e, "plain") == 0; }();
-    return plain;
-}
+bool splat_plain() { return switches().frames_splat_plain; }
 
 int check_desc(sph_ctx *c, const char *who, const sph_frames_desc *d, bool log) {
     if (!d) return arg_error(c, who, "null descriptor");

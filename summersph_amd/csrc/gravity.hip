@@ -744,8 +744,7 @@ hipError_t launch_gravity(sph_ctx *c, double *ax, double *ay, double *az) {
     for (int a = 0; a < 3; a++) rb.c[a] = c->root_box[a];
     rb.size = c->root_box[3];
     const double soft2 = 0.001 * 2.5;                                   // 0.001_dp*smoothing, MODULE constant ([F]:275, [V]:296)
-    static int wave_walk = -1;
-    if (wave_walk < 0) { const char *e = getenv("SPH_GRAV_WAVE"); wave_walk = e ? atoi(e) : 1; }
+    const int wave_walk = switches().grav_wave;                         // SPH_GRAV_WAVE: A/B switch
     if (wave_walk || ext) {
         TreeArrays ta = tree_arrays(c);
         unsigned long long *stats = nullptr;

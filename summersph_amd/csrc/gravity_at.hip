@@ -124,13 +124,6 @@ __global__ __launch_bounds__(PB) void gravat_finish(const double *__restrict__ p
     }
 }
 
-// A/B switch for the measurements of DESIGN.md section 14 (the results do not depend on it)
-int env_flag(const char *name, int fallback) {
-    const char *v = std::getenv(name);
-    if (!v || !*v) return fallback;
-    return std::atoi(v) != 0;
-}
-
 }  // namespace
 
 int gravity_at_run(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_points, const double *px, const double *py,
@@ -172,7 +165,7 @@ int gravity_at_run(sph_ctx *c, const sph_gravity_at_desc *d, int64_t n_points, c
     const int64_t n_src = gas ? (ext ? c->gx_n : no) : 0;
     const bool walk = n_src > 0;
     const bool stage = walk && !ext;
-    const bool sort_points = walk && env_flag("SPH_GRAVAT_POINT_SORT", 1);
+    const bool sort_points = walk && GravityAtSwitches().point_sort;      // A/B switch for the measurements of DESIGN.md section 14 (the results do not depend on it)
     const int nb = stage_blocks(no);
     size_t psort_bytes = 0;
     if (sort_points)

@@ -650,8 +650,7 @@ static int reorder_sorted(sph_ctx *c, bool ranked = false) {
     for (int k = 0; k < 9; k++) { ra.src[k] = c->f[k]; ra.dst[k] = c->f_alt[k]; }
     ra.nf = 9; ra.prec = nullptr;
     if (c->variable) { ra.src[9] = c->f[SPH_F_H]; ra.dst[9] = c->f_alt[9]; ra.nf = 10; ra.prec = c->prec; }
-    static const bool store_inv = getenv("SPH_NO_LAZY_INV") != nullptr;                 // A/B switch
-    c->inv_valid = store_inv || c->nranks > 1 || c->n_owned != n;
+    c->inv_valid = switches().no_lazy_inv || c->nranks > 1 || c->n_owned != n;          // SPH_NO_LAZY_INV: A/B switch
     // ranked: c->vals holds the cells' entries in arrival order (cell_scatter); the rank is taken on the way
     if (ranked) reorder_ranked<<<dim3(gb), dim3(256), 0, st>>>(ra, c->keys, c->cell_start, c->vals, c->orig, c->orig_alt, c->inv_valid ? c->inv : nullptr, c->drec, n);
     else reorder<<<dim3(gb), dim3(256), 0, st>>>(ra, c->vals_alt, c->orig, c->orig_alt, c->inv_valid ? c->inv : nullptr, c->drec, n);
@@ -745,10 +744,7 @@ static int hash_build(sph_ctx *c, bool swap) {
     return SPH_OK;
 }
 
-static bool sort_radix_forced() {
-    static const bool force_radix = getenv("SPH_SORT_RADIX") != nullptr;             // A/B switch
-    return force_radix;
-}
+static bool sort_radix_forced() { return switches().sort_radix; }      // SPH_SORT_RADIX: A/B switch
 
 static bool same_grid(const GridDesc &a, const GridDesc &b) {
     bool same = a.inv_edge == b.inv_edge && a.ncells == b.ncells;
@@ -763,10 +759,9 @@ static bool same_grid(const GridDesc &a, const GridDesc &b) {
 // within the capacity in place, no trim, counting sort, no ghosts pending -- and grid_rebuild checks that its own grid is this
 // one before it believes the keys.  Zeroes the table and the cursors on the stream; sets c->keys_early.  SPH_NO_DRIFT_KEYS: A/B.
 int grid_prepare_early(sph_ctx *c) {
-    static const bool off = getenv("SPH_NO_DRIFT_KEYS") != nullptr;
     c->keys_early = false;
     const int64_t n = c->n;
-    if (off || n <= 0 || c->n_slots != n || c->dead_below != 0 || c->variable || c->gravity ||
+    if (switches().no_drift_keys || n <= 0 || c->n_slots != n || c->dead_below != 0 || c->variable || c->gravity ||
         (c->p.flags & (SPH_FLAG_ACCRETE_CULL | SPH_FLAG_HASHED_GRID)) || !c->ring_bbox_valid || c->no_stale || c->hash_sticky ||
         sort_radix_forced())
         return SPH_OK;
@@ -1003,9 +998,8 @@ int grid_rebuild(sph_ctx *c) {
         SPH_HIP(rocprim::exclusive_scan(c->sort_tmp, scan_tmp, c->cell_start, c->cell_start, 0, (size_t)(g.ncells + 2), rocprim::plus<int32_t>(), st));
         if (early) {
             // SPH_NO_BOX_RIDE (A/B switch): the box of the early partials by a launch of its own
-            static const bool no_ride = getenv("SPH_NO_BOX_RIDE") != nullptr;
             const BoxFinal bf{c->bbox_part + BBOX_PART_CLASSIC, c->early_blocks, c->bbox_part + (size_t)BB_MAX_BLOCKS * 6, slot, c->d_flags};
-            if (no_ride) {
+            if (switches().no_box_ride) {
                 bbox_final<<<dim3(1), dim3(384), 0, st>>>(bf.partial, bf.nblocks, bf.out, bf.host_slot, bf.flags);
                 cell_scatter<false><<<dim3(gbs), dim3(256), 0, st>>>(c->keys, ns, c->cell_start, c->cell_fill, c->vals, BoxFinal{});
             } else {
@@ -1017,8 +1011,7 @@ int grid_rebuild(sph_ctx *c) {
             cell_scatter<false><<<dim3(gbs), dim3(256), 0, st>>>(c->keys, ns, c->cell_start, c->cell_fill, c->vals, BoxFinal{});
         }
         // SPH_NO_RANK_REORDER (A/B switch): the rank by a launch of its own, as every other configuration has it
-        static const bool no_ranked = getenv("SPH_NO_RANK_REORDER") != nullptr;
-        ranked = early && !no_ranked;
+        ranked = early && !switches().no_rank_reorder;
         if (!ranked) cell_rank<<<dim3(gb), dim3(256), 0, st>>>(c->keys, n, c->cell_start, c->vals, c->vals_alt);
         SPH_HIP(hipGetLastError());
         c->n_slots = n; c->dead_below = 0;

@@ -327,10 +327,7 @@ int nlist_build(sph_ctx *c) {
         c->nl_max = mx;
         if (mx <= c->nl_cap) { c->nlist_builds++; return SPH_OK; }
         // grow: the list is sized for the densest wave; 288 GB of HBM make this cheap
-        int32_t want = mx + mx / 8 + 8;
-        ctx_free(c, c->nlist);
-        c->nl_cap = want;
-        if (ctx_alloc(c, &c->nlist, (size_t)c->nl_waves_cap * c->nl_cap * 64, "neighbour list") != SPH_OK) { c->nl_cap = 0; return SPH_ERR_NOMEM; }
+        SPH_TRY(list_alloc(c, mx + mx / 8 + 8));
     }
     c->err = "neighbour list did not converge";
     return SPH_ERR_STATE;
@@ -340,8 +337,7 @@ int nlist_build(sph_ctx *c) {
 // 12 000 particles are 47 workgroups of 256) were measured and lose at every size -- 12 000 particles: density 0.037 vs 0.032 ms
 // per pass, 100 000: 0.089 vs 0.048 (the 40-KB kernel table is loaded per workgroup); SPH_GATHER_BLOCK=64 keeps the A/B switch
 static int gather_block(const sph_ctx *) {
-    static const int forced = getenv("SPH_GATHER_BLOCK") ? atoi(getenv("SPH_GATHER_BLOCK")) : 0;
-    return forced == 64 ? 64 : PAIR_BLOCK;
+    return switches().gather_block == 64 ? 64 : PAIR_BLOCK;
 }
 
 hipError_t launch_density(sph_ctx *c, const PairConst &pc) {

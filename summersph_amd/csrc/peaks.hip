@@ -557,8 +557,7 @@ int peaks_run(sph_ctx *c, const sph_peaks_desc *d, int32_t *labels, int64_t n_la
     }
     // SPH_PEAKS_TIMING: one line per call for profiles/peaks_time.py (pairs, edges, passes over the pairs, the host merge,
     // and when the three waits and the merge ended, in ms since the call began)
-    static const bool timing = getenv("SPH_PEAKS_TIMING") != nullptr;
-    if (timing)
+    if (switches().peaks_timing)
         fprintf(stderr, "sph_peaks: pairs %lld edges %lld passes %d merge_ms %.3f waits_ms %.3f %.3f %.3f merged_ms %.3f\n", (long long)T,
                 (long long)E, passes, merge_ms, at_pairs, at_edges, at_list, at_merged);
     SPH_HIP(hipMemsetAsync(top, 0xff, (size_t)no * sizeof(int32_t), st));          // no entry: a peak is its own top

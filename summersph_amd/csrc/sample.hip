@@ -345,13 +345,6 @@ hipError_t launch_walk(bool per_h, hipStream_t st, const WalkArgs &a) {
     return hipGetLastError();
 }
 
-// A/B switches for the measurements of DESIGN.md section 13 (the results do not depend on them beyond the level order)
-int env_int(const char *name, int fallback, int lo, int hi) {
-    const char *v = std::getenv(name);
-    if (!v || !*v) return fallback;
-    return std::min(std::max(std::atoi(v), lo), hi);
-}
-
 }  // namespace
 
 int sample_build(sph_ctx *c, const SampleSources &src, size_t extra_bytes, SampleView *view, char **extra, char **sort_tmp_out) {
@@ -361,7 +354,8 @@ int sample_build(sph_ctx *c, const SampleSources &src, size_t extra_bytes, Sampl
     const bool held = ns > 0 && n > 0;
     const bool per_h = src.per_h, host = src.host;
     const int nf = src.nf;
-    const int g0 = env_int("SPH_SAMPLE_LEVEL_WIDTH", 1, 0, 13);            // 2^g0 quarter octaves per level
+    // (SampleSwitches: A/B switches for the measurements of DESIGN.md section 13; the results do not depend on them beyond the level order)
+    const int g0 = SampleSwitches().level_width;                           // 2^g0 quarter octaves per level
     const int64_t nn = std::max<int64_t>(n, 1);
     const int nb = (int)std::min<int64_t>((std::max<int64_t>(ns, 1) + SB - 1) / SB, BOX_BLOCKS);
     int64_t tl = 1;
@@ -489,7 +483,7 @@ int sample_run(sph_ctx *c, const sph_sample_desc *d, int64_t n_points, const dou
 
     hipStream_t st = c->stream;
     const int64_t m = n_points;
-    const bool sort_points = env_int("SPH_SAMPLE_POINT_SORT", 1, 0, 1) != 0;
+    const bool sort_points = SampleSwitches().point_sort;
     size_t psort_bytes = 0;
     if (sort_points)
         SPH_HIP(rocprim::radix_sort_pairs(nullptr, psort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,

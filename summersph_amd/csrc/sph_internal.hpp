@@ -13,6 +13,8 @@
 
 #include "../../include/summersph.h"
 #include "ctx_state.hpp"
+#include "fixed_plan.hpp"
+#include "switches.hpp"
 
 namespace sph {
 
@@ -93,7 +95,7 @@ struct TimingSlot {
 struct DtWords { double dt, t, cand; };                      // the layout of d_dt
 struct HStats { double h_max, h_sum, growth, shrink; };      // h_stats_final
 struct BoxReport { double box[6]; int32_t nonfinite; };      // bbox_final: min xyz, max xyz, then the flag as an int at double 6
-struct ListReport { int32_t v[8]; };                         // plan_reduce_kernel: longest list, misfits, largest tile need (tiled.hip)
+struct ListReport { int32_t v[REP_WORDS]; };                 // plan_reduce_kernel (tiled.hip); the words: ListReportWord, fixed_plan.hpp
 struct AccWords { int32_t pos_last, keep_last, ns; };        // the packs: scan and mark of the last particle, sinks after the cull
 struct PinnedSlots {
     int32_t wave_max;                              // max_to_host: the longest list of the untiled builds
@@ -160,10 +162,7 @@ struct sph_ctx : sph::CtxState {
     bool variable = false;
     bool tiled = true;               // fixed-h: LDS-staged neighbour-list build (tiled.hip) unless SPH_FLAG_NO_LDS_TILES
     bool whole_tile = false;         // fixed-h: density/forces read the neighbours' {x,y,z,m} from one LDS tile per workgroup (tiled.hip)
-    bool wt_ok = false, wt_ok_f = false;   // ... and the last list build found that the workgroups' intervals fit the tile (density / forces geometry)
-    bool wt_half_f = false;                // forces_q on groups of 128 targets (eight lanes each): half the tile need of a group of 256
-    bool wt_big = false, wt_big_f = false; // ... only the table-free tile (the kernel table's knots recomputed, 40 KB more for the tile)
-    int32_t wt_fit_pct = -1, wt_fit_pct_f = -1;   // percentage of workgroups that fit (-1: kernels off)
+    sph::TileChoice tile;            // ... and which of them the last list build's report allows (fixed_plan.hpp: choose_tiles)
     bool packed_list = true;         // list layout: 4-packed (tiled build) or wave-strided dwords (nlist_kernel)
     double *prec = nullptr;          // 4 doubles: x y z h        (neighbour-list build)
     double *lrec = nullptr;          // 4 doubles: leaf centre x y z, reach = 2h + leaf_edge/2 (<0: unresolved)
@@ -217,7 +216,7 @@ struct sph_ctx : sph::CtxState {
     // truncated sums: every evaluation is refused until sph_upload.
     hipEvent_t ev_bbox[2] = {nullptr, nullptr}, ev_nl[2] = {nullptr, nullptr};
     int ring_bbox = 0, ring_nl = 0;
-    bool no_stale = false;           // SPH_SYNC_EVERY_BUILD: wait for every read-back (A/B switch)
+    bool no_stale = false;           // SPH_SYNC_EVERY_BUILD: wait for every read-back (A/B switch, switches.hpp)
     int64_t host_syncs = 0;          // stream synchronisations inside the build path (statistics)
     // hashed cell table (grid.hip): used instead of cell_start when the current grid is hashed
     bool hashed = false;             // the current grid build is hashed
@@ -346,6 +345,15 @@ template <class T>
 inline void ctx_free(sph_ctx *c, T *&p) {
     ctx_free_ptr(c, p);
     p = nullptr;
+}
+
+// The neighbour list's allocation, for every build that (re)sizes it: frees the list in place and allocates nl_cap entries a
+// lane -- 16-bit ones on the tiled path (tile_common.hpp), 32-bit ones otherwise.  On failure the context holds no list.
+inline int list_alloc(sph_ctx *c, int32_t new_cap) {
+    ctx_free(c, c->nlist);
+    c->nl_cap = new_cap;
+    if (ctx_alloc(c, &c->nlist, (size_t)c->nl_waves_cap * c->nl_cap * (c->tiled ? 32 : 64), "neighbour list") != SPH_OK) { c->nl_cap = 0; return SPH_ERR_NOMEM; }
+    return SPH_OK;
 }
 
 // all launchers enqueue on ctx->stream and return a hipError_t (no synchronisation unless noted)

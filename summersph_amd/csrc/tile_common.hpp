@@ -14,9 +14,8 @@ namespace sph {
 // Layout ("ELL, wave-strided, 8-packed"): entry k of particle i = (wave w, lane l) is halfword ent_pos(k & 7) of the int4 at
 // nlist4[(w * cap/8 + k/8) * 64 + l].  ent_pos puts entries 4t .. 4t+3 of a row into the SAME half of its four words, so the
 // four lanes of a forces_q target (lane s = word s) consume a row in two trips of four consecutive entries each.
-// The three intervals of a group must stay below 65536 records together (LIST16_MAX_NEED); a context whose groups outgrow
-// that (a very dense thick domain) falls back to the untiled 32-bit list of pairs.hip for good (nlist_build_tiled).
-constexpr int LIST16_MAX_NEED = 65536;
+// The three intervals of a group must stay below LIST16_MAX_NEED records together (fixed_plan.hpp); a context whose groups
+// outgrow that (a very dense thick domain) falls back to the untiled 32-bit list of pairs.hip for good (nlist_build_tiled).
 constexpr double SENTINEL_POS = 1.0e30;       // coordinates of the sentinel record of the whole-tile kernels (tiled.hip): q is astronomically > 2
 __device__ __host__ __forceinline__ int ent_pos(int k) { return ((k & 3) << 1) | ((k >> 2) & 1); }
 // halfword p (compile-time in the unrolled loops) of a row.  NOT CALLED by any kernel at present (the kernels decode through

@@ -34,7 +34,7 @@ namespace {
 constexpr int TB = 256;              // neighbour-list build: threads (= targets) per workgroup
 constexpr int T_NL = 512;            // ... and staged records per chunk (32 B each)
 constexpr int DEAL_BINS = 1024;      // counting sort of a group's list lengths (longer lists share the last bin)
-constexpr int WT_BS = 1024;          // density_wt: threads (= targets) per workgroup, one workgroup per CU
+// (WT_BS, the targets of a density_wt workgroup, and FQ_T, those of a forces_q group: fixed_plan.hpp)
 // the arguments of forces_q / density_wt that only their epilogues read (kept in LDS, see there)
 struct alignas(16) DensEpiArgs { const double *u, *alpha, *vx, *vy, *vz; double *rho, *P, *cs, *frec; double wnorm, gamma, gamma_m1, h; };
 struct alignas(16) EpiArgs { double G, alpha_floor, alpha_decay, inv_dwnorm; double *ax, *ay, *az, *du, *dalpha; int ns, grav; };
@@ -713,15 +713,12 @@ __global__ __launch_bounds__(1024) void plan_reduce_kernel(int64_t ngroups_d, in
             r0 = max(r0, s_red[0][k]); r1 += s_red[1][k]; r2 += s_red[2][k]; r3 = max(r3, s_red[3][k]); r4 += s_red[4][k]; r5 += s_red[5][k];
             r6 += s_red[6][k]; r7 += s_red[7][k];
         }
-        // {longest list, misfits density, misfits forces, largest need, misfits density / forces with the table-free tiles,
-        //  misfits of the half groups of forces_q with the table / table-free tile}
-        report[0] = r0; report[1] = r1; report[2] = r2; report[3] = r3; report[4] = r4; report[5] = r5; report[6] = r6; report[7] = r7;
+        report[REP_LONGEST] = r0; report[REP_MISFIT_D] = r1; report[REP_MISFIT_F] = r2; report[REP_NEED] = r3;
+        report[REP_MISFIT_D_FREE] = r4; report[REP_MISFIT_F_FREE] = r5; report[REP_MISFIT_H] = r6; report[REP_MISFIT_H_FREE] = r7;
     }
 }
 
 inline unsigned tb_blocks(int64_t n) { return (unsigned)((n + TB - 1) / TB); }
-
-constexpr int FQ_T = 256;            // forces_q: targets per group
 
 int32_t tile_cap(int nq, int rec, bool tablds) {
     const size_t tab = tablds ? (size_t)(TAB_LDS(nq)) * sizeof(double) : 0;
@@ -745,10 +742,9 @@ int32_t tile_cap_q(int nq, bool tablds = true) {
 // (for good: c->tiled is set at sph_create only, a later sph_upload of a small set stays untiled)
 static int leave_tiled_path(sph_ctx *c) {
     c->tiled = false; c->whole_tile = false; c->packed_list = false;
-    c->wt_ok = c->wt_ok_f = false; c->wt_fit_pct = c->wt_fit_pct_f = -1;
+    c->tile = TileChoice{};
     c->ring_nl_valid = false;
-    ctx_free(c, c->nlist);
-    if (ctx_alloc(c, &c->nlist, (size_t)c->nl_waves_cap * c->nl_cap * 64, "neighbour list") != SPH_OK) { c->nl_cap = 0; return SPH_ERR_NOMEM; }
+    SPH_TRY(list_alloc(c, c->nl_cap));
     return nlist_build(c);
 }
 
@@ -756,61 +752,29 @@ int nlist_build_tiled(sph_ctx *c) {
     const int64_t n = c->n;
     if (n == 0) return SPH_OK;
     const PairConst pc = make_pair_const(c);
-    const unsigned d_blocks = (unsigned)((n + WT_BS - 1) / WT_BS), f_blocks = (unsigned)((n + FQ_T - 1) / FQ_T);
-    auto regrow = [&](int32_t want) {
-        ctx_free(c, c->nlist);
-        c->nl_cap = (want + 7) & ~7;
-        if (ctx_alloc(c, &c->nlist, (size_t)c->nl_waves_cap * c->nl_cap * 32, "neighbour list") != SPH_OK) { c->nl_cap = 0; return SPH_ERR_NOMEM; }     // 16-bit entries
-        return SPH_OK;
-    };
-    // what a build reports: {longest list, misfits of the density geometry, misfits of the forces geometry, largest tile need}
+    // what a build reports (ListReportWord): the longest list and, for the whole-tile kernels, which of them its tiles allow
+    // (SPH_TILE_TABLE=regs, SPH_FORCES_HALF_GROUPS: A/B switches)
     auto digest = [&](const int32_t *rep) {
-        c->nl_max = rep[0];
-        if (c->whole_tile) {
-            // the whole-tile kernels pay a prologue and run their fall-back loop at one workgroup per CU: use them when
-            // (nearly) every workgroup's intervals fit the tile -- thin discs and sheets; thick domains keep pairs.hip
-            // ... with the kernel table beside the tile; where that fails but the table-free tile (40 KB larger, knots recomputed)
-            // holds the intervals -- dense neighbourhoods -- the table-free variant runs (SPH_TILE_TABLE=regs: always, A/B)
-            static const bool force_big = getenv("SPH_TILE_TABLE") && std::string(getenv("SPH_TILE_TABLE")) == "regs";
-            const bool ok_d = (int64_t)rep[1] * 10 <= (int64_t)d_blocks, ok_db = (int64_t)rep[4] * 10 <= (int64_t)d_blocks;
-            const bool ok_f = (int64_t)rep[2] * 10 <= (int64_t)f_blocks, ok_fb = (int64_t)rep[5] * 10 <= (int64_t)f_blocks;
-            // forces: groups of 256 with the table (1.0), table-free (x1.1 on the bench disc), groups of 128 -- eight lanes per
-            // target, every record staged more often -- with the table, table-free; the first whose tiles fit nine groups in ten
-            static const int force_half = getenv("SPH_FORCES_HALF_GROUPS") ? atoi(getenv("SPH_FORCES_HALF_GROUPS")) : 0;     // A/B switch
-            const bool ok_h = (int64_t)rep[6] * 10 <= 2 * (int64_t)f_blocks, ok_hb = (int64_t)rep[7] * 10 <= 2 * (int64_t)f_blocks;
-            c->wt_big = force_big || (!ok_d && ok_db);
-            c->wt_ok = c->wt_big ? ok_db : ok_d;
-            c->wt_fit_pct = (int32_t)(100 - (100 * (int64_t)rep[c->wt_big ? 4 : 1]) / std::max<int64_t>(d_blocks, 1));
-            c->wt_half_f = force_half != 0 || (!ok_f && !ok_fb && (ok_h || ok_hb));
-            if (c->wt_half_f) {
-                c->wt_big_f = force_big || !ok_h;
-                c->wt_ok_f = c->wt_big_f ? ok_hb : ok_h;
-                c->wt_fit_pct_f = (int32_t)(100 - (100 * (int64_t)rep[c->wt_big_f ? 7 : 6]) / std::max<int64_t>(2 * (int64_t)f_blocks, 1));
-            } else {
-                c->wt_big_f = force_big || (!ok_f && ok_fb);
-                c->wt_ok_f = c->wt_big_f ? ok_fb : ok_f;
-                c->wt_fit_pct_f = (int32_t)(100 - (100 * (int64_t)rep[c->wt_big_f ? 5 : 2]) / std::max<int64_t>(f_blocks, 1));
-            }
-        }
+        c->nl_max = rep[REP_LONGEST];
+        if (c->whole_tile) c->tile = choose_tiles(rep, n, switches().tile_table_regs, switches().forces_half_groups);
     };
-    // Steady state: the report of the PREVIOUS build (it arrived long ago) is read instead of waiting for this one's.  The
-    // list keeps a third of headroom, so a list that overflows within one step (which the dt control all but excludes) is
-    // an error reported one build late, not a silent truncation.  The same for the 16-bit entries: the context leaves the
-    // tiled path when a group's intervals reach HALF of what an entry can address.  So entries with bit 15 set are written
-    // by one build only -- the one whose need has grown into [32768, 65535] -- and decoded in that step alone.  The four
-    // branches (the two guards, the error below, drain_reports' term) and that step are pinned by tests/test_list16_edges_gpu.py.
+    // Steady state: the report of the PREVIOUS build (it arrived long ago) is read instead of waiting for this one's, and
+    // judged by judge_list (fixed_plan.hpp).  Entries with bit 15 set are written by one build only -- the one whose need has
+    // grown into [32768, 65535] -- and decoded in that step alone.  The four branches (the two guards, the error below,
+    // drain_reports' term) and that step are pinned by tests/test_list16_edges_gpu.py.
     const bool trusted = c->ring_nl_valid && !c->no_stale;
     const int p = c->ring_nl;
     int32_t *slot = c->pin->nl[p].v;
     if (trusted) {
         SPH_HIP(hipEventSynchronize(c->ev_nl[1 - p]));
         const int32_t *prev = c->pin->nl[1 - p].v;
+        const ListVerdict v = judge_list(prev, c->nl_cap, ListReportAge::PREVIOUS_BUILD);
         // either way the context refuses every evaluation from here on (nl_overflowed, do_density)
-        if (prev[0] > c->nl_cap) { c->nl_overflowed = true; c->err = "neighbour list overflowed in the previous build (lists grew by more than a third within one step)"; return SPH_ERR_STATE; }
-        if (prev[3] >= LIST16_MAX_NEED) { c->nl_overflowed = true; c->err = "neighbour list: a group's candidate intervals outgrew the 16-bit entries within one step"; return SPH_ERR_STATE; }
-        if (2 * (int64_t)prev[3] >= LIST16_MAX_NEED) return leave_tiled_path(c);
+        if (v.kind == ListKind::LIST_OVERFLOWED) { c->nl_overflowed = true; c->err = "neighbour list overflowed in the previous build (lists grew by more than a third within one step)"; return SPH_ERR_STATE; }
+        if (v.kind == ListKind::OUTGREW_16BIT) { c->nl_overflowed = true; c->err = "neighbour list: a group's candidate intervals outgrew the 16-bit entries within one step"; return SPH_ERR_STATE; }
+        if (v.kind == ListKind::LEAVE_TILED) return leave_tiled_path(c);
         digest(prev);
-        if (4 * (int64_t)prev[0] > 3 * (int64_t)c->nl_cap) { const int st = regrow(prev[0] + prev[0] / 2 + 8); if (st != SPH_OK) return st; }
+        if (v.kind == ListKind::REGROW) SPH_TRY(list_alloc(c, v.new_cap));
     }
     for (int attempt = 0; attempt < 8; attempt++) {
         auto nl = c->hashed ? nlist_tiled<true> : nlist_tiled<false>;
@@ -832,12 +796,12 @@ int nlist_build_tiled(sph_ctx *c) {
         if (trusted) break;
         SPH_HIP(hipStreamSynchronize(c->stream));
         c->host_syncs++;
-        if (2 * (int64_t)slot[3] >= LIST16_MAX_NEED) return leave_tiled_path(c);
+        const ListVerdict v = judge_list(slot, c->nl_cap, ListReportAge::OWN_BUILD);
+        if (v.kind == ListKind::LEAVE_TILED) return leave_tiled_path(c);
         digest(slot);
-        const int32_t mx = slot[0];
-        if (4 * (int64_t)mx <= 3 * (int64_t)c->nl_cap) break;            // fits, with the headroom the steady state relies on
+        if (v.kind == ListKind::FITS) break;                             // with the headroom the steady state relies on
         if (attempt == 7) { c->err = "neighbour list did not converge"; return SPH_ERR_STATE; }
-        { const int st = regrow(mx + mx / 2 + 8); if (st != SPH_OK) return st; }
+        SPH_TRY(list_alloc(c, v.new_cap));
     }
     c->ring_nl = 1 - p; c->ring_nl_valid = true;
     c->nlist_builds++;
@@ -888,10 +852,7 @@ static hipError_t sync_rider_args(sph_ctx *c, void *&dev, std::vector<unsigned c
 
 // SPH_NO_RIDERS (A/B switch): no launch of the two kernels carries a rider workgroup, whatever its caller asks for; the caller
 // learns it from what the launcher reports back and takes the stand-alone launches
-static bool riders_off() {
-    static const bool off = getenv("SPH_NO_RIDERS") != nullptr;
-    return off;
-}
+static bool riders_off() { return switches().no_riders; }
 
 // rode: the blocks of sink_accel_partial that this launch carried as riders (0: none)
 template <bool TAB>
@@ -924,7 +885,7 @@ static hipError_t density_wt_launch(sph_ctx *c, const PairConst &pc, bool ride_s
 hipError_t launch_density_wt(sph_ctx *c, const PairConst &pc, bool ride_sink, int32_t *rode) {
     if (rode) *rode = 0;
     if (c->n == 0) return hipSuccess;
-    return c->wt_big ? density_wt_launch<false>(c, pc, ride_sink, rode) : density_wt_launch<true>(c, pc, ride_sink, rode);
+    return c->tile.big ? density_wt_launch<false>(c, pc, ride_sink, rode) : density_wt_launch<true>(c, pc, ride_sink, rode);
 }
 
 template <int LPT, bool TAB>
@@ -957,8 +918,8 @@ static hipError_t forces_q_launch(sph_ctx *c, const PairConst &pc, int part, int
 // part 0: every wave.  part 1 / 2: only the waves of class 0 (interior) / class 1, as launch_forces
 hipError_t launch_forces_wt(sph_ctx *c, const PairConst &pc, int part, int32_t rode) {
     if (c->n == 0) return hipSuccess;
-    if (c->wt_half_f) return c->wt_big_f ? forces_q_launch<8, false>(c, pc, part, rode) : forces_q_launch<8, true>(c, pc, part, rode);
-    return c->wt_big_f ? forces_q_launch<4, false>(c, pc, part, rode) : forces_q_launch<4, true>(c, pc, part, rode);
+    if (c->tile.half_f) return c->tile.big_f ? forces_q_launch<8, false>(c, pc, part, rode) : forces_q_launch<8, true>(c, pc, part, rode);
+    return c->tile.big_f ? forces_q_launch<4, false>(c, pc, part, rode) : forces_q_launch<4, true>(c, pc, part, rode);
 }
 
 }  // namespace sph

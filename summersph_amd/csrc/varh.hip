@@ -1185,8 +1185,7 @@ int varh_refresh_h(sph_ctx *c) {
 }
 
 int varh_nlist_build(sph_ctx *c) {
-    static const bool no_reflag_env = getenv("SPH_NO_REFLAG") != nullptr;      // A/B switches: always build, no re-flag margin
-    const bool no_reflag = no_reflag_env || (c->p.flags & SPH_FLAG_NO_REFLAG) != 0;
+    const bool no_reflag = switches().no_reflag || (c->p.flags & SPH_FLAG_NO_REFLAG) != 0;      // A/B switches: always build, no re-flag margin
     const int64_t n = c->n;
     if (n == 0) return SPH_OK;
     const int R = std::max(1, (int)std::ceil(2.0 * H_MARGIN * c->h_max_glob * c->grid.inv_edge * (1.0 + 1e-9)));
@@ -1210,9 +1209,7 @@ int varh_nlist_build(sph_ctx *c) {
             c->vl_grow = grow;
             return SPH_OK;
         }
-        ctx_free(c, c->nlist);
-        c->nl_cap = ((mx + mx / 8 + 8) + 3) & ~3;
-        if (ctx_alloc(c, &c->nlist, (size_t)c->nl_waves_cap * c->nl_cap * 64, "neighbour list") != SPH_OK) { c->nl_cap = 0; return SPH_ERR_NOMEM; }
+        SPH_TRY(list_alloc(c, ((mx + mx / 8 + 8) + 3) & ~3));
     }
     c->err = "neighbour list did not converge";
     return SPH_ERR_STATE;
