@@ -1588,6 +1588,99 @@ int sph_track_read_dev(sph_ctx *ctx, int64_t first, int64_t count, double *d_hea
 int sph_track_fates(sph_ctx *ctx, int32_t *host_fates);
 int sph_track_fates_dev(sph_ctx *ctx, int32_t *d_fates);
 
+/* ---- dust: drag-coupled tracer grains advanced with the run (where a mm grain goes, compared with a micron grain: into the
+ *      arms and clumps, onto a sink, out of the disc) ----------------------------------------------------------------------
+ * A dust set is M massless test grains on the device, each with a position, a velocity and one drag parameter par.  The
+ * grains feel the sinks' gravity and the drag of the SPH-interpolated gas and act on nothing: the gas run with grains is
+ * bitwise the gas run without them.  Between sph_dust_begin and sph_dust_end every step of sph_step / sph_run whose running
+ * number (counted since begin) is a multiple of `every` advances all live grains from their own clock t_d to the gas clock
+ * t (the device's time word), at the very end of the step, after sph_history's, sph_track's and sph_frames' rows: a few
+ * launches on the context's stream, no stream synchronisation, no host read-back.  Without dust the step is exactly what it
+ * is without this section: no kernel, no argument, no allocation and no synchronisation differ.
+ * Scheme   kick-drift-kick with exact drag and one gas evaluation per advance.  Each grain keeps the sample S = (a[3], vg[3],
+ *          r) of the end of its last advance: the sinks' acceleration, the gas velocity and the drag rate r = 1 / t_s at
+ *          the grain.  With D = t - t_d an advance does, in this order and without fused multiply-adds:
+ *          1 half kick with the stored S: tau = D / 2, k = r tau; where k > 0: e = -expm1(-k) and
+ *            v <- (v + (vg - v) e) + a (tau (e / k)), the exact solution of dv/dt = a - r (v - vg) with a, vg and r frozen
+ *            (finite however stiff the drag; k -> infinity gives the terminal velocity vg + a / r); where r == 0:
+ *            v <- v + a tau.
+ *          2 drift: x <- x + v D.
+ *          3 fates, with SPH_DUST_REMOVE only: the sinks in sink order, the first with |x - R_s| < radius_s (Euclidean,
+ *            sph_set_sink_radii's radii) takes the grain, fate 1; otherwise any |x_k| > params.bounding_size is fate 2.
+ *            With or without the flag a non-finite x or v is fate 3.  A grain with a fate stops here.
+ *          4 the gas at the new x in the state the step just left: sph_sample's sums den, num[0..3] over the owned gas,
+ *            mass-weighted, fields vx vy vz u, no clip box, desc.h = 0.  rho = den, vg = num[0..2] / den, u = num[3] / den,
+ *            c = sqrt((gamma gamma_m1) u).  Where den == 0: r = 0 and vg = 0 (and u = 0).  Otherwise
+ *            SPH_DUST_EPSTEIN: r = ((rho c) cE) / (rho_grain par) with par the grain size and cE = sqrt(8 / pi) in double;
+ *            SPH_DUST_FIXED_TS: r = 1 / par with par the stopping time.
+ *            The sinks' a in sink order with sph_gravity_at's arithmetic (its "Sinks" paragraph), unsoftened.
+ *          5 the second half kick, step 1's formula with the new S.  A grain whose v or a is not finite now (a grain
+ *            placed exactly on a massive sink), and every grain if a gas particle has a bad h (sph_sample would return
+ *            NaN), is fate 3.
+ *          6 S is stored, t_d = t, and the row is appended if this advance is one to record.
+ *          Where D <= 0 or D is not finite (after a sph_set_dt that moved t back) only steps 4 to 6 run, without the kick:
+ *          nothing moves.  sph_dust_begin does that once (advance number 0, no row), so that S exists before the first
+ *          step; it may wait for the stream.
+ * Order    one lane per grain adds its sources in sph_sample's documented order.  The grains are walked in the order of
+ *          their cells, which is a matter of speed only: a grain's result depends on the gas, the sinks, its own x, v,
+ *          par, S and D alone, not on the other grains, M, the walk order, the gas's sorted order or the kind of cell grid.
+ * Row      head: SPH_DUST_NHEAD doubles: the advance number (advances are counted since begin, from 1, the explicit ones
+ *          included), t, the D of this advance, the grains alive after it.  body: SPH_DUST_NCOL values per grain, x y z vx
+ *          vy vz rho_g u_g vgx vgy vgz rate, laid out [column][p]: body is (rows, SPH_DUST_NCOL, M) in C order, sph_track's
+ *          shape.  rho_g, u_g and vg are bitwise what sph_sample returns at (x, y, z) with fields vx vy vz u, normalised,
+ *          and its weight output.  A grain with a fate is NaN in the row of that advance and in every later row (the log is
+ *          filled with NaN once, at begin).  A step-driven advance appends a row where the count of step-driven advances is a
+ *          multiple of record_every; sph_dust_advance always appends one.  A full log drops further rows and counts them.
+ * Fates    three int32 per grain, {fate, advance, sink}: fate 0 alive, 1 accreted, 2 culled, 3 non-finite; the number of the
+ *          advance that removed it; the sink that took it (-1 unless accreted).
+ * advance  sph_dust_advance advances to the clock now, outside a step, and appends a row; the first call after begin (D = 0)
+ *          is the t = 0 row.
+ * Scope    one rank, no ghosts: begin returns SPH_ERR_STATE where nranks > 1 or n_owned != n.  The gas's self-gravity does
+ *          not act on the grains.  Grains are not gas ids: sph_upload keeps them, they are sampled against the new gas.
+ *          sph_set_owned, sph_replace_ghosts_dev and sph_set_rank with nranks > 1 *close* the dust: no further advance
+ *          (sph_dust_advance returns SPH_ERR_STATE); rows, state and fates stay readable until sph_dust_end.
+ * read     sph_dust_read copies rows [first, first + count) to the host, the heads to head (count x SPH_DUST_NHEAD) and the
+ *          bodies to body (count x SPH_DUST_NCOL x M); either pointer may be null.  sph_dust_state copies the seven arrays
+ *          x y z vx vy vz par as they are now (a removed grain keeps its last values), so that grains can be saved and begun
+ *          again; sph_dust_fates copies 3 M int32.  The host forms synchronise the stream; the _dev forms copy to device
+ *          memory in the stream's order without waiting.  sph_dust_begin_dev takes the arrays from device memory; both forms
+ *          of begin check par on the host.  sph_dust_info: the rows held and dropped, the advances counted, M and the live
+ *          count (null outputs are skipped); asking for n_live reads the device's count and synchronises.  None of these
+ *          waits is counted in sph_stats.host_syncs.
+ * cost     an advance is one sample_build over the gas, a launch over the grains, a radix sort of M pairs, the walk and a
+ *          one-lane launch.  The log (capacity x (4 + 12 M) doubles), 16 M doubles of state and sample and 12 M bytes of fates
+ *          are counted in device_bytes from begin to end; the advance works in the analysis scratch and keeps nothing there.
+ * SPH_ERR_STATE: advance, info, read, state, fates or end without begin; begin with several ranks or ghosts; advance on closed
+ * dust.  SPH_ERR_ARG: a null descriptor, M < 1, null arrays, capacity < 0, every < 1, record_every < 1, an unknown law or
+ * flags, a par <= 0 or not finite, rho_grain <= 0 or not finite with SPH_DUST_EPSTEIN, first or count outside [0, rows], a
+ * null output.  SPH_ERR_NOMEM: the log does not fit. */
+typedef struct sph_dust_desc {
+    int64_t capacity;      /* rows the log holds (>= 0; 0: no log, state and fates only)                       */
+    int32_t every;         /* advance at the steps whose running number is a multiple of this (>= 1)           */
+    int32_t record_every;  /* append a row at every record_every-th advance (>= 1)                             */
+    int32_t law;           /* SPH_DUST_EPSTEIN | SPH_DUST_FIXED_TS                                             */
+    int32_t flags;         /* SPH_DUST_REMOVE                                                                  */
+    double  rho_grain;     /* > 0 with EPSTEIN (mass / length^3 in code units); unused otherwise               */
+} sph_dust_desc;           /* 32 bytes */
+#define SPH_DUST_EPSTEIN 0
+#define SPH_DUST_FIXED_TS 1
+#define SPH_DUST_REMOVE 1
+#define SPH_DUST_NHEAD 4   /* advance number, t, D of this advance, grains alive */
+#define SPH_DUST_NCOL 12   /* x y z vx vy vz rho_g u_g vgx vgy vgz rate */
+int sph_dust_begin(sph_ctx *ctx, const sph_dust_desc *d, int64_t m, const double *x, const double *y, const double *z,
+                   const double *vx, const double *vy, const double *vz, const double *par);   /* a second begin replaces the first */
+int sph_dust_begin_dev(sph_ctx *ctx, const sph_dust_desc *d, int64_t m, const double *d_x, const double *d_y, const double *d_z,
+                       const double *d_vx, const double *d_vy, const double *d_vz, const double *d_par);
+int sph_dust_end(sph_ctx *ctx);
+int sph_dust_advance(sph_ctx *ctx);
+int sph_dust_info(sph_ctx *ctx, int64_t *rows, int64_t *dropped, int64_t *advances, int64_t *n_grains, int64_t *n_live);
+int sph_dust_read(sph_ctx *ctx, int64_t first, int64_t count, double *host_head, double *host_body);
+int sph_dust_read_dev(sph_ctx *ctx, int64_t first, int64_t count, double *d_head, double *d_body);
+int sph_dust_state(sph_ctx *ctx, double *x, double *y, double *z, double *vx, double *vy, double *vz, double *par);
+int sph_dust_state_dev(sph_ctx *ctx, double *d_x, double *d_y, double *d_z, double *d_vx, double *d_vy, double *d_vz, double *d_par);
+int sph_dust_fates(sph_ctx *ctx, int32_t *host_fates);
+int sph_dust_fates_dev(sph_ctx *ctx, int32_t *d_fates);
+
 /* ---- frames: a device-resident movie of a run -- line-of-sight-integrated maps of the owned gas appended from the end of
  *      the step, and the same map as a one-shot call (summersph_amd/frames.py) ------------------------------------------
  * Between sph_frames_begin and sph_frames_end the steps of sph_step / sph_run append frames to a log of `capacity` rows, at

@@ -63,6 +63,8 @@ SYMBOLS = [
     "sph_track_read_dev", "sph_track_fates", "sph_track_fates_dev",
     "sph_frames_begin", "sph_frames_end", "sph_frames_record", "sph_frames_rewind", "sph_frames_info", "sph_frames_read",
     "sph_frames_read_dev", "sph_frame", "sph_frame_dev",
+    "sph_dust_begin", "sph_dust_begin_dev", "sph_dust_end", "sph_dust_advance", "sph_dust_info", "sph_dust_read",
+    "sph_dust_read_dev", "sph_dust_state", "sph_dust_state_dev", "sph_dust_fates", "sph_dust_fates_dev",
 ]
 RENDER_AUTO_BOUNDS = 1
 RENDER_SPACING = 2
@@ -95,6 +97,17 @@ TRACK_HEAD = ["step", "t", "n", "n_live"]
 TRACK_COLUMNS = ["x", "y", "z", "vx", "vy", "vz", "u", "rho", "h", "alpha"]
 TRACK_FATES = ["fate", "step", "sink", "current_id"]
 TRACK_ALIVE, TRACK_ACCRETED, TRACK_CULLED = 0, 1, 2
+DUST_NHEAD = 4
+DUST_NCOL = 12
+# a row of sph_dust (include/summersph.h, "Row"): the head's columns, the per-grain columns of the body, the fates' entries
+DUST_HEAD = ["advance", "t", "delta", "n_live"]
+DUST_COLUMNS = ["x", "y", "z", "vx", "vy", "vz", "rho_g", "u_g", "vgx", "vgy", "vgz", "rate"]
+DUST_FATES = ["fate", "advance", "sink"]
+DUST_STATE = ["x", "y", "z", "vx", "vy", "vz", "par"]
+DUST_ALIVE, DUST_ACCRETED, DUST_CULLED, DUST_NONFINITE = 0, 1, 2, 3
+DUST_EPSTEIN, DUST_FIXED_TS = 0, 1
+DUST_LAWS = {"epstein": DUST_EPSTEIN, "fixed_ts": DUST_FIXED_TS}
+DUST_REMOVE = 1
 FRAMES_NHEAD = 16
 FRAMES_MAX_FIELDS = 3
 FRAMES_MAX_SINKS = 64
@@ -768,6 +781,41 @@ def track_fates_columns(fates) -> dict:
     return {k: f[:, i] for i, k in enumerate(TRACK_FATES)}
 
 
+class DustDesc(C.Structure):
+    """sph_dust_desc (include/summersph.h)"""
+    _fields_ = [("capacity", C.c_int64), ("every", C.c_int32), ("record_every", C.c_int32), ("law", C.c_int32),
+                ("flags", C.c_int32), ("rho_grain", C.c_double)]
+
+
+def dust_desc(law="epstein", rho_grain=None, capacity=0, every=1, record_every=1, remove=False) -> DustDesc:
+    """The DustDesc of a sph_dust_begin call.  law: "epstein" (par is the grain size, rho_grain the grains' material
+    density in code units) or "fixed_ts" (par is the stopping time); remove: SPH_DUST_REMOVE."""
+    if law not in DUST_LAWS:
+        raise ValueError(f"dust: law must be one of {sorted(DUST_LAWS)}")
+    if law == "epstein" and rho_grain is None:
+        raise ValueError("dust: the epstein law needs rho_grain")
+    d = DustDesc()
+    d.capacity, d.every, d.record_every = int(capacity), int(every), int(record_every)
+    d.law, d.flags = DUST_LAWS[law], DUST_REMOVE if remove else 0
+    d.rho_grain = 0.0 if rho_grain is None else float(rho_grain)
+    return d
+
+
+def dust_columns(head, body, dropped=0) -> dict:
+    """Raw dust rows, head (R, DUST_NHEAD) and body (R, DUST_NCOL, M), -> the dict Context.dust returns: advance and n_live
+    as int64 (R,), t and delta (R,), one (R, M) view per name of DUST_COLUMNS, body, head and dropped."""
+    hd, bd = np.asarray(head, dtype=np.float64), np.asarray(body, dtype=np.float64)
+    if hd.ndim != 2 or hd.shape[1] != DUST_NHEAD or bd.ndim != 3 or bd.shape[1] != DUST_NCOL or bd.shape[0] != hd.shape[0]:
+        raise ValueError("dust: head must be (R, DUST_NHEAD) and body (R, DUST_NCOL, M)")
+    out = {k: hd[:, i] for i, k in enumerate(DUST_HEAD)}
+    for k in ("advance", "n_live"):
+        out[k] = out[k].astype(np.int64)
+    for i, k in enumerate(DUST_COLUMNS):
+        out[k] = bd[:, i, :]
+    out["body"], out["head"], out["dropped"] = bd, hd, int(dropped)
+    return out
+
+
 def bound_desc(h=None, soft2=GRAVAT_REF_SOFT2, thermal=False, max_rounds=0, min_members=1, max_members=2**31 - 1) -> BoundDesc:
     """The descriptor of Context.bound's arguments (see there)."""
     d = BoundDesc()
@@ -1091,6 +1139,17 @@ def load():
     for fn in (lib.sph_track_read, lib.sph_track_read_dev):
         fn.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
     for fn in (lib.sph_track_fates, lib.sph_track_fates_dev):
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+    for fn in (lib.sph_dust_begin, lib.sph_dust_begin_dev):
+        fn.argtypes = [C.c_void_p, C.POINTER(DustDesc), C.c_int64] + [C.c_void_p] * 7
+    lib.sph_dust_end.argtypes = [C.c_void_p]
+    lib.sph_dust_advance.argtypes = [C.c_void_p]
+    lib.sph_dust_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 5
+    for fn in (lib.sph_dust_read, lib.sph_dust_read_dev):
+        fn.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    for fn in (lib.sph_dust_state, lib.sph_dust_state_dev):
+        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 7
+    for fn in (lib.sph_dust_fates, lib.sph_dust_fates_dev):
         fn.argtypes = [C.c_void_p, C.c_void_p]
     lib.sph_frames_begin.argtypes = [C.c_void_p, C.POINTER(FramesDesc)]
     for fn in (lib.sph_frames_end, lib.sph_frames_record, lib.sph_frames_rewind):
@@ -1765,6 +1824,80 @@ class Context:
         if not device:
             return track_fates_columns(fates)
         return {name: fates[:, i] for i, name in enumerate(TRACK_FATES)}
+
+    # ---- drag-coupled tracer grains (sph_dust) -------------------------------------------------------
+    def dust_begin(self, x, v, par, law="epstein", rho_grain=None, capacity=0, every=1, record_every=1, remove=False):
+        """Starts (or restarts) M tracer grains (include/summersph.h, sph_dust) at positions x and velocities v, each an
+        (M, 3) array or three arrays of M, with the drag parameter par (M values: the grain size under law="epstein" with
+        rho_grain in code units, the stopping time under law="fixed_ts").  Every every-th step of step / run advances them,
+        every record_every-th advance appends a row to a log of capacity rows; remove=True lets sinks accrete them and the
+        bound cull them.  numpy arrays, or float64 torch tensors on the context's GPU (sph_dust_begin_dev)."""
+        d = dust_desc(law, rho_grain, capacity, every, record_every, remove)
+        device = any(_on_gpu(t, self.device) for t in (*(x if isinstance(x, (tuple, list)) else (x,)), par))
+        f = self._form(device)
+        p, m = _points("dust", x, f, noun="grain")
+        q, mv = _points("dust", v, f, {"par": par}, noun="grain")
+        if mv != m or q[3] is None:
+            raise ValueError(f"dust: {m} positions, {mv} velocities; par must be given")
+        f.call("sph_dust_begin", C.byref(d), m, *(f.ptr(a) for a in p), *(f.ptr(a) for a in q))
+        self.dust_desc = d
+
+    def dust_advance(self):
+        """Advances the grains to the clock now, outside a step, and appends a row (the first call after dust_begin is the
+        t = 0 row)."""
+        self._ck(self.lib.sph_dust_advance(self._h))
+
+    def dust_end(self):
+        self._ck(self.lib.sph_dust_end(self._h))
+
+    def dust_info(self, live=True) -> dict:
+        """rows held, rows dropped, advances counted since dust_begin, the grains and (live=True: one read-back, waits for
+        the stream) how many of them are still alive"""
+        v = [C.c_int64(0) for _ in range(5)]
+        self._ck(self.lib.sph_dust_info(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(v[3]),
+                                        C.byref(v[4]) if live else None))
+        out = {"rows": v[0].value, "dropped": v[1].value, "advances": v[2].value, "n_grains": v[3].value}
+        if live:
+            out["n_live"] = v[4].value
+        return out
+
+    def dust(self, first=0, count=None, device=False):
+        """Rows [first, first + count) of the grains' log (count None: all from first) as dust_columns' dict: advance, t,
+        delta, n_live per row, one (rows, M) array per name of DUST_COLUMNS (NaN once a grain has a fate) and body
+        (rows, 12, M).  device=True: the rows are copied on the context's GPU in the stream's order (sph_dust_read_dev);
+        body, head and the named columns are torch tensors, the head's columns are read from it."""
+        info = self.dust_info(live=False)
+        first = int(first)
+        cnt = info["rows"] - first if count is None else int(count)
+        f = self._form(device)
+        head = f.empty((max(cnt, 0), DUST_NHEAD))
+        body = f.empty((max(cnt, 0), DUST_NCOL, info["n_grains"]))
+        f.call("sph_dust_read", first, cnt, f.ptr(head), f.ptr(body))
+        if not device:
+            return dust_columns(head, body, info["dropped"])
+        out = dust_columns(f.host(head), np.empty((head.shape[0], DUST_NCOL, 0)), info["dropped"])
+        for i, k in enumerate(DUST_COLUMNS):
+            out[k] = body[:, i, :]
+        out["body"], out["head"] = body, head
+        return out
+
+    def dust_state(self, device=False) -> dict:
+        """The grains as they are now: {"x", "y", "z", "vx", "vy", "vz", "par"}, seven (M,) arrays (torch tensors with
+        device=True); dust_begin of them continues the run.  A removed grain keeps its last values."""
+        m = self.dust_info(live=False)["n_grains"]
+        f = self._form(device)
+        a = [f.empty(m) for _ in DUST_STATE]
+        f.call("sph_dust_state", *(f.ptr(t) for t in a))
+        return dict(zip(DUST_STATE, a))
+
+    def dust_fates(self, device=False) -> dict:
+        """The fates of the grains: {"fate", "advance", "sink"}, three (M,) int32 arrays (torch tensors with device=True).
+        fate: DUST_ALIVE, DUST_ACCRETED, DUST_CULLED, DUST_NONFINITE."""
+        m = self.dust_info(live=False)["n_grains"]
+        f = self._form(device)
+        fates = f.empty((m, len(DUST_FATES)), np.int32)
+        f.call("sph_dust_fates", f.ptr(fates))
+        return {name: fates[:, i] for i, name in enumerate(DUST_FATES)}
 
     # ---- friends-of-friends groups (sph_groups) --------------------------------------------------
     # ---- the movie of a run (sph_frames) -------------------------------------------------------------

@@ -407,7 +407,9 @@ int one_step_device_dt(sph_ctx *c) {
     }
     SPH_TRY(history_step(c));                          // sph_history: a row of the state sph_download_state would return now
     if (c->track) SPH_TRY(track_step(c));              // sph_track: the tracked particles' row of the same state
-    return c->frames ? frames_step(c) : SPH_OK;        // sph_frames: the maps of the same state
+    if (c->frames) SPH_TRY(frames_step(c));            // sph_frames: the maps of the same state
+    if (c->dust) SPH_TRY(dust_step(c));                // sph_dust: the grains advanced to the clock of the same state
+    return SPH_OK;
 }
 
 }  // namespace
@@ -581,6 +583,7 @@ int sph_ctx_destroy(sph_ctx *c) {
     history_free(c);
     track_free(c);
     frames_free(c);
+    dust_free(c);
     if (c->stream && c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return SPH_OK;
@@ -817,6 +820,7 @@ int sph_set_owned(sph_ctx *c, int64_t n_owned) {
     c->n_owned = n_owned;
     c->owned_count_changed();
     if (c->track) track_close(c);
+    if (c->dust && n_owned != c->n) dust_close(c);
     return SPH_OK;
 }
 
@@ -824,6 +828,7 @@ int sph_set_rank(sph_ctx *c, int32_t rank, int32_t nranks) {
     if (!c || nranks < 1 || rank < 0 || rank >= nranks) return SPH_ERR_ARG;
     c->rank = rank; c->nranks = nranks;
     if (c->track && nranks > 1) track_close(c);
+    if (c->dust && nranks > 1) dust_close(c);
     return SPH_OK;
 }
 
@@ -979,6 +984,7 @@ int sph_replace_ghosts_dev(sph_ctx *c, int64_t count, const double *d_state) {
     if (c->own_stream) SPH_HIP(hipStreamSynchronize(c->stream));
     c->ghosts_replaced();
     if (c->track) track_close(c);
+    if (c->dust) dust_close(c);
     return SPH_OK;
 }
 
@@ -1514,6 +1520,84 @@ int sph_track_fates_dev(sph_ctx *c, int32_t *d_fates) {
     if (!c) return SPH_ERR_ARG;
     DeviceGuard g(c->device);
     return track_fates(c, d_fates, false);
+}
+
+int sph_dust_begin(sph_ctx *c, const sph_dust_desc *d, int64_t m, const double *x, const double *y, const double *z,
+                   const double *vx, const double *vy, const double *vz, const double *par) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    const double *a[7] = {x, y, z, vx, vy, vz, par};
+    return dust_begin(c, d, m, a, true);
+}
+
+int sph_dust_begin_dev(sph_ctx *c, const sph_dust_desc *d, int64_t m, const double *d_x, const double *d_y, const double *d_z,
+                       const double *d_vx, const double *d_vy, const double *d_vz, const double *d_par) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    const double *a[7] = {d_x, d_y, d_z, d_vx, d_vy, d_vz, d_par};
+    return dust_begin(c, d, m, a, false);
+}
+
+int sph_dust_end(sph_ctx *c) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return dust_end(c);
+}
+
+int sph_dust_advance(sph_ctx *c) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return dust_advance(c);
+}
+
+int sph_dust_info(sph_ctx *c, int64_t *rows, int64_t *dropped, int64_t *advances, int64_t *n_grains, int64_t *n_live) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return dust_info(c, rows, dropped, advances, n_grains, n_live);
+}
+
+int sph_dust_read(sph_ctx *c, int64_t first, int64_t count, double *host_head, double *host_body) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    SPH_TRY(dust_read(c, first, count, host_head, host_body, true));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    return SPH_OK;
+}
+
+int sph_dust_read_dev(sph_ctx *c, int64_t first, int64_t count, double *d_head, double *d_body) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return dust_read(c, first, count, d_head, d_body, false);
+}
+
+int sph_dust_state(sph_ctx *c, double *x, double *y, double *z, double *vx, double *vy, double *vz, double *par) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    double *a[7] = {x, y, z, vx, vy, vz, par};
+    SPH_TRY(dust_state(c, a, true));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    return SPH_OK;
+}
+
+int sph_dust_state_dev(sph_ctx *c, double *d_x, double *d_y, double *d_z, double *d_vx, double *d_vy, double *d_vz, double *d_par) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    double *a[7] = {d_x, d_y, d_z, d_vx, d_vy, d_vz, d_par};
+    return dust_state(c, a, false);
+}
+
+int sph_dust_fates(sph_ctx *c, int32_t *host_fates) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    SPH_TRY(dust_fates(c, host_fates, true));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    return SPH_OK;
+}
+
+int sph_dust_fates_dev(sph_ctx *c, int32_t *d_fates) {
+    if (!c) return SPH_ERR_ARG;
+    DeviceGuard g(c->device);
+    return dust_fates(c, d_fates, false);
 }
 
 int sph_frames_begin(sph_ctx *c, const sph_frames_desc *d) {

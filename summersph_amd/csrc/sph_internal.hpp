@@ -113,6 +113,7 @@ struct PinnedSlots {
 struct History;                                              // the per-step time series (history.hip); null: none begun
 struct Track;                                                // the tracked particles' log (track.hip); null: none begun
 struct Frames;                                               // the movie's log (frames.hip); null: none begun
+struct Dust;                                                 // the tracer grains (dust.hip); null: none begun
 static_assert(offsetof(BoxReport, nonfinite) == 6 * sizeof(double) && sizeof(BoxReport) % 8 == 0, "bbox_final's layout");
 static_assert(sizeof(DtWords) == 3 * sizeof(double) && sizeof(HStats) == 4 * sizeof(double), "copied as arrays of doubles");
 #define SPH_PIN_ALIGNED(m, a) static_assert(offsetof(PinnedSlots, m) % (a) == 0, #m " is misaligned for its writer")
@@ -286,6 +287,8 @@ struct sph_ctx : sph::CtxState {
     sph::History *hist = nullptr;
     // sph_track (track.hip): the log, the membership bitmap with its prefix and tags, the fates and the host-side counts
     sph::Track *track = nullptr;
+    // sph_dust (dust.hip): the grains' state, stored sample, log and fates and the host-side counts
+    sph::Dust *dust = nullptr;
     // sph_frames (frames.hip): the log, the limb image, the partials, the device words and the host-side step count
     sph::Frames *frames = nullptr;
 };
@@ -612,6 +615,20 @@ int track_packed(sph_ctx *c, const int32_t *keep, const int32_t *pos, const unsi
 int track_info(sph_ctx *c, int64_t *rows, int64_t *dropped, int64_t *steps, int64_t *n_tracked, int64_t *n_live, int32_t *closed);
 int track_read(sph_ctx *c, int64_t first, int64_t count, double *head, double *body, bool host);
 int track_fates(sph_ctx *c, int32_t *fates, bool host);
+
+// drag-coupled tracer grains (dust.hip).  dust_step is the step's hook (called where c->dust is set; a no-op on closed
+// dust); arrays: x y z vx vy vz par.  dust_close: ghosts or several ranks, no further advance.  dust_read, dust_state and
+// dust_fates only enqueue the copies (the host forms' callers synchronise)
+int dust_begin(sph_ctx *c, const sph_dust_desc *d, int64_t n, const double *const *arrays, bool host);
+int dust_end(sph_ctx *c);
+void dust_free(sph_ctx *c);
+void dust_close(sph_ctx *c);
+int dust_advance(sph_ctx *c);
+int dust_step(sph_ctx *c);
+int dust_info(sph_ctx *c, int64_t *rows, int64_t *dropped, int64_t *advances, int64_t *n_grains, int64_t *n_live);
+int dust_read(sph_ctx *c, int64_t first, int64_t count, double *head, double *body, bool host);
+int dust_state(sph_ctx *c, double *const *arrays, bool host);
+int dust_fates(sph_ctx *c, int32_t *fates, bool host);
 
 // the movie of a run (frames.hip).  frames_step is the step's hook (called where c->frames is set); frames_read and frame_run
 // only enqueue the copies (the host forms' callers synchronise); frames_info reads the device's counts and synchronises

@@ -73,6 +73,9 @@ module sph_hip_binding
   public :: sph_track_desc, sph_track_begin, sph_track_begin_dev, sph_track_end, sph_track_record, sph_track_info, sph_track_read
   public :: sph_track_read_dev, sph_track_fates, sph_track_fates_dev, SPH_TRACK_NHEAD, SPH_TRACK_NCOL, sph_track_begin_env
   public :: sph_track_write
+  public :: sph_dust_desc, sph_dust_begin, sph_dust_begin_dev, sph_dust_end, sph_dust_advance, sph_dust_info, sph_dust_read
+  public :: sph_dust_read_dev, sph_dust_state, sph_dust_state_dev, sph_dust_fates, sph_dust_fates_dev
+  public :: SPH_DUST_NHEAD, SPH_DUST_NCOL, SPH_DUST_EPSTEIN, SPH_DUST_FIXED_TS, SPH_DUST_REMOVE
   ! the movie of a run: line-of-sight-integrated maps of the owned gas appended on the device, and the one-shot frame
   public :: sph_frames_desc, sph_frames_begin, sph_frames_end, sph_frames_record, sph_frames_rewind, sph_frames_info
   public :: sph_frames_read, sph_frames_read_dev, sph_frame, sph_frame_dev, SPH_FRAMES_NHEAD, SPH_FRAMES_MAX_FIELDS
@@ -345,6 +348,16 @@ module sph_hip_binding
     integer(c_int64_t) :: capacity
     integer(c_int32_t) :: every, flags
   end type sph_track_desc
+
+  ! sph_dust: a row is a head of SPH_DUST_NHEAD doubles and a body of SPH_DUST_NCOL values per grain, body(m, SPH_DUST_NCOL,
+  ! count) in Fortran order; fates(3, m).  32 bytes.
+  integer(c_int32_t), parameter :: SPH_DUST_NHEAD = 4, SPH_DUST_NCOL = 12
+  integer(c_int32_t), parameter :: SPH_DUST_EPSTEIN = 0, SPH_DUST_FIXED_TS = 1, SPH_DUST_REMOVE = 1
+  type, bind(C) :: sph_dust_desc
+    integer(c_int64_t) :: capacity
+    integer(c_int32_t) :: every, record_every, law, flags
+    real(c_double) :: rho_grain
+  end type sph_dust_desc
 
   ! sph_frames: a frame is a head of SPH_FRAMES_NHEAD doubles and 1 + nq planes, planes(n_v, n_u, 1 + nq, count) in Fortran
   ! order; rot(9) holds the rows u^, v^, w^ one after the other.  240 bytes.
@@ -1102,6 +1115,59 @@ module sph_hip_binding
       type(c_ptr), value :: ctx, host_fates
     end function
     integer(c_int) function sph_track_fates_dev(ctx, d_fates) bind(C, name='sph_track_fates_dev')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, d_fates
+    end function
+    ! ---- tracer grains: begin's seven arrays of m are x y z vx vy vz par; info's outputs, read's head and body, state's arrays
+    !      and the fates are c_loc(...) (info's and either of read's may be c_null_ptr); the d_ arguments are device memory
+    integer(c_int) function sph_dust_begin(ctx, d, m, x, y, z, vx, vy, vz, par) bind(C, name='sph_dust_begin')
+      import :: c_int, c_int64_t, c_double, c_ptr, sph_dust_desc
+      type(c_ptr), value :: ctx
+      type(sph_dust_desc), intent(in) :: d
+      integer(c_int64_t), value :: m
+      real(c_double), intent(in) :: x(*), y(*), z(*), vx(*), vy(*), vz(*), par(*)
+    end function
+    integer(c_int) function sph_dust_begin_dev(ctx, d, m, d_x, d_y, d_z, d_vx, d_vy, d_vz, d_par) bind(C, name='sph_dust_begin_dev')
+      import :: c_int, c_int64_t, c_ptr, sph_dust_desc
+      type(c_ptr), value :: ctx, d_x, d_y, d_z, d_vx, d_vy, d_vz, d_par
+      type(sph_dust_desc), intent(in) :: d
+      integer(c_int64_t), value :: m
+    end function
+    integer(c_int) function sph_dust_end(ctx) bind(C, name='sph_dust_end')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function sph_dust_advance(ctx) bind(C, name='sph_dust_advance')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function sph_dust_info(ctx, rows, dropped, advances, n_grains, n_live) bind(C, name='sph_dust_info')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, rows, dropped, advances, n_grains, n_live
+    end function
+    integer(c_int) function sph_dust_read(ctx, first, count, host_head, host_body) bind(C, name='sph_dust_read')
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: ctx, host_head, host_body
+      integer(c_int64_t), value :: first, count
+    end function
+    integer(c_int) function sph_dust_read_dev(ctx, first, count, d_head, d_body) bind(C, name='sph_dust_read_dev')
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: ctx, d_head, d_body
+      integer(c_int64_t), value :: first, count
+    end function
+    integer(c_int) function sph_dust_state(ctx, x, y, z, vx, vy, vz, par) bind(C, name='sph_dust_state')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, x, y, z, vx, vy, vz, par
+    end function
+    integer(c_int) function sph_dust_state_dev(ctx, d_x, d_y, d_z, d_vx, d_vy, d_vz, d_par) bind(C, name='sph_dust_state_dev')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, d_x, d_y, d_z, d_vx, d_vy, d_vz, d_par
+    end function
+    integer(c_int) function sph_dust_fates(ctx, host_fates) bind(C, name='sph_dust_fates')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, host_fates
+    end function
+    integer(c_int) function sph_dust_fates_dev(ctx, d_fates) bind(C, name='sph_dust_fates_dev')
       import :: c_int, c_ptr
       type(c_ptr), value :: ctx, d_fates
     end function
